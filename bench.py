@@ -22,12 +22,19 @@ ranks on 127.0.0.1; under torchrun it checks WORLD_SIZE == N.  Every rank owns i
 no data-path collective; SURVEY.md 8e = BASELINE configs[3]: 1000 pockets per GPU); the timed region is bracketed by
 barrier + synchronize, the MAX over ranks is reported and `ranks_seen` comes from an RCCL all-reduce.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline` (dominant kernel =
-the fused x2h edge kernel, timed live with HIP events on its own stream via cbgx_profile_*) and
-`cpu_baseline` (the CPU oracle = port of the reference's PyTorch-CPU path, timed on this host: one process at its best thread
-count, and `cores / threads` such processes side by side).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the --steps steps,
+writes the last timed step's outputs when --dump-outputs DIR is given, and prints the headline line.  Everything else is
+measured only with --full: `roofline` (dominant kernel = the fused x2h edge kernel, timed live with HIP events on its own
+stream via cbgx_profile_*), `cpu_baseline` (the CPU oracle = port of the reference's PyTorch-CPU path, timed on this host:
+one process at its best thread count, and `cores / threads` such processes side by side) and the `secondary` block below;
+--no-roofline / --no-cpu-baseline / --no-secondary leave single parts of it out.
 
-At N = 1 the default run also measures a `secondary` block in the same process, a few seconds each, so that every BASELINE
+--dump-outputs DIR: after the timed steps, what the timed path handed its caller in its last step, as DIR/<name>.npy (float32):
+sampling -- x_lig.npy, c_lig.npy (the ligand state of every resident batch, in batch order); training -- the losses, the
+clipped gradient norm, the flat clipped gradients and the parameters after the optimiser step.  The inputs are seeded, so
+the same arguments give the same inputs in every run.
+
+At N = 1, --full also measures a `secondary` block in the same process, a few seconds each, so that every BASELINE
 config is under the driver's eyes and not only in builder-side files (--no-secondary skips it): the linker batch of 256
 (configs[2]), the training step at 32 graphs per GPU with its own roofline (configs[4] shape), the diffbp and diffsbdd samplers,
 the reference's own 10-graph batch (sample.py:177-183) and a single graph, and ONE END-TO-END run of
@@ -284,9 +291,14 @@ def bench_train(args, rank, world, dev):
     sharding.barrier(); torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        t_ar += TRN.train_step(model, batch, opt, fg, weights, 8.0)[3]
+        last = TRN.train_step(model, batch, opt, fg, weights, 8.0)
+        t_ar += last[3]
     torch.cuda.synchronize(); sharding.barrier()
     elapsed = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs and args.steps > 0:
+        loss, loss_dict, grad_norm = last[:3]
+        dump_outputs(args.dump_outputs, {"loss": loss, **{f"loss_{k}": v for k, v in loss_dict.items()}, "grad_norm": grad_norm,
+                                         "grads": fg.flat, "params": torch.cat([p.detach().flatten() for p in fg.params])})
     el_max, units = sharding.reduce_max_sum(elapsed, n_graphs * args.steps, device=dev)
     per_rank = sharding.gather_values(round(n_graphs * args.steps / elapsed, 1), device=dev)
     seen = ranks_seen(dev)
@@ -445,7 +457,32 @@ def parse_args(argv=None):
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary block (other configs measured in the same run; N = 1, default workload only)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the roofline pass, the CPU baselines and (N = 1, default "
+                         "workload) the secondary block; without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32)")
+    args = ap.parse_args(argv)
+    if not args.full:
+        args.no_roofline = args.no_cpu_baseline = args.no_secondary = True
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: `arrays` (name -> tensor) as directory/<name>.npy in float32.  Above DUMP_LIMIT_BYTES in all, every array
+    keeps the same fraction of its rows, chosen by a fixed seed (the same rows in every run of the same arguments)."""
+    arrays = {k: np.atleast_1d(torch.as_tensor(v).detach().float().cpu().numpy()) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        rng = np.random.default_rng(0)
+        keep = DUMP_LIMIT_BYTES / total
+        arrays = {k: a[np.sort(rng.choice(a.shape[0], max(1, int(a.shape[0] * keep)), replace=False))] for k, a in arrays.items()}
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
 
 
 def main():
@@ -579,6 +616,13 @@ def bench_sampling(args, rank, world, dev):
                 bench_step(i)
             torch.cuda.synchronize(); sharding.barrier()
             elapsed = time.perf_counter() - t0
+        if rank == 0 and args.dump_outputs and args.steps > 0:
+            if use_graph:      # the replays leave the state in the trajectory: the slot the last timed step wrote
+                last = [(st["traj_x"][T - made[b][1] - args.warmup - args.steps], st["traj_c"][T - made[b][1] - args.warmup - args.steps])
+                        for b, st in enumerate(states)]
+            else:
+                last = [(st["x_lig"], st["c_lig"]) for st in states]
+            dump_outputs(args.dump_outputs, {"x_lig": torch.cat([x for x, _ in last]), "c_lig": torch.cat([c for _, c in last])})
         el_max, graph_steps = sharding.reduce_max_sum(elapsed, n_graphs * n_blocks * args.steps, device=dev)
         per_rank = sharding.gather_values(round(n_graphs * n_blocks * args.steps / elapsed, 1), device=dev)   # a straggler shows here
         seen = ranks_seen(dev)
@@ -724,7 +768,7 @@ def sample_cli_end_to_end(dev, pockets=20, samples=10, config="targetdiff_test.y
 
 def secondary_block(args, dev, primary):
     """Other BASELINE configs measured in the same process as the headline (rank 0, N = 1): a few seconds each."""
-    ns = lambda **kw: argparse.Namespace(**{**vars(args), "no_cpu_baseline": True, "no_secondary": True, **kw})
+    ns = lambda **kw: argparse.Namespace(**{**vars(args), "no_cpu_baseline": True, "no_secondary": True, "dump_outputs": None, **kw})
     sec = {}
     t_all = time.perf_counter()
 

@@ -12,6 +12,7 @@ are both checked against these files.
 """
 import json
 import os
+import shutil
 import sys
 
 import numpy as np
@@ -526,6 +527,13 @@ def context_prior_case(name):
     print(name, keys)
 
 
+def atom_num_table(name="atom_num_dist.npy"):
+    """the reference's atom-count histogram table (repo/datasets/transforms/_atom_num_dist.npy: a pickled {'bounds', 'bins'}
+    dict), stored as a data fixture so that tests/test_priors.py reads it from tests/golden/"""
+    shutil.copyfile(os.path.join(ref_shim.REFERENCE_ROOT, "repo", "datasets", "transforms", "_atom_num_dist.npy"), os.path.join(OUT, name))
+    print(name)
+
+
 def _selected(name):
     """``python -m oracle.make_golden train_`` regenerates only the fixtures whose name contains an argument."""
     sel = sys.argv[1:]
@@ -581,6 +589,8 @@ def main():
     train_case(model, "train_loss_t0_linker", small_batch([(58, 15), (44, 12)], seed=68, ctx=[10, 8]), seed=16,
                t_override=torch.tensor([0, 700]))
     priors_case("priors_atom_num")
+    if _selected("atom_num_dist"):
+        atom_num_table()
     context_prior_case("priors_context_tasks")
     diffsbdd_train_case("train_loss_diffsbdd", small_batch([(64, 10), (50, 12), (57, 9)], seed=64, num_classes=8), seed=18)
     # (seed chosen so that no ReLU of the t = 0 graph sits within rounding of zero: with the unnormalised t = 0 term such

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 cd /tmp
 rocprofv3 -L > $OUT/counters_list.txt 2>&1
 grep -c . $OUT/counters_list.txt
-CMD="python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline"
+CMD="python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-roofline"
 i=0
 while read -r GROUP; do
   [ -z "$GROUP" ] && continue

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Evidence call of a round (one gpurun): all GPU tests (the driver's command with -x), smoke, the driver's default bench command
+# Evidence call of a round (one GPU job): all GPU tests (the driver's command with -x), smoke, the driver's bench command with --full
 # (headline + secondary block + the CPU legs), rocprofv3 kernel stats of the sampling and the training command, PMC passes of the dominant
 # forward kernel (instruction mix / waits, HBM traffic in separate FETCH_SIZE / WRITE_SIZE passes) and of the x2h edge backward.
 # Usage (repo root on the GPU box): bash scripts/gpu_round_final.sh [tag]
@@ -13,12 +13,12 @@ timeout 1800 python -m pytest tests/ -x -q -m gpu --durations=6 -s -p no:faultha
 echo "== smoke =="
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 | tee $OUT/smoke_$TAG.log
 echo "== bench: the driver's command =="
-( time timeout 1200 python bench.py ) 2>&1 | tail -5 | tee $OUT/bench_$TAG.json | cut -c1-300
+( time timeout 1200 python bench.py --full ) 2>&1 | tail -5 | tee $OUT/bench_$TAG.json | cut -c1-300
 grep -m1 '^{' $OUT/bench_$TAG.json | wc -c
 echo "== bench: one stream (round-2 schedule) for comparison =="
-timeout 600 python bench.py --streams 1 --no-cpu-baseline --no-secondary 2>&1 | tail -1 | tee $OUT/bench_1stream_$TAG.json | cut -c1-200
+timeout 600 python bench.py --full --streams 1 --no-cpu-baseline --no-secondary 2>&1 | tail -1 | tee $OUT/bench_1stream_$TAG.json | cut -c1-200
 echo "== rocprofv3 kernel stats: sampling (one stream: per-kernel times without overlap), training =="
-( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o bench -- python $ROOT/bench.py --steps 2 --warmup 1 --streams 1 --no-cpu-baseline --no-secondary > $OUT/rocprof_$TAG.log 2>&1 ; tail -1 $OUT/rocprof_$TAG.log | cut -c1-200 )
+( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o bench -- python $ROOT/bench.py --full --steps 2 --warmup 1 --streams 1 --no-cpu-baseline --no-secondary > $OUT/rocprof_$TAG.log 2>&1 ; tail -1 $OUT/rocprof_$TAG.log | cut -c1-200 )
 f=$(find $OUT/prof_$TAG -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -10 "$f" | cut -c1-160 && cp "$f" $OUT/kernel_stats_$TAG.csv
 ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_train_$TAG -o tr -- python $ROOT/bench.py --workload train --steps 4 --warmup 2 --no-cpu-baseline --no-roofline > $OUT/rocprof_train_$TAG.log 2>&1 ; tail -1 $OUT/rocprof_train_$TAG.log | cut -c1-200 )
 f=$(find $OUT/prof_train_$TAG -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -8 "$f" | cut -c1-160 && cp "$f" $OUT/kernel_stats_train_$TAG.csv
@@ -58,7 +58,7 @@ du -sh $OUT | tail -1
 if [ -f $ROOT/ab_libs/base.so ]; then
 echo "== headline on ab_libs/base.so, then on the tree again =="
 for L in $ROOT/ab_libs/base.so $ROOT/cbgbench_amd/lib/libcbgx.so; do
-CBGX_LIBRARY=$L timeout 300 python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "
+CBGX_LIBRARY=$L timeout 300 python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['roofline']['per_kernel_us_avg_and_launches']
 print('$L'.split('/')[-1], d['value'], {n: v for n, v in k.items() if v[1]})"
@@ -69,7 +69,7 @@ bash scripts/gpu_trace_train.sh $TAG 2>&1 | head -12
 cp $OUT/trace_train_$TAG/critical.txt $OUT/trace_train_critical_$TAG.txt 2>/dev/null
 echo "== training line under the per-call knobs (edge rows, schedule) =="
 for set in "" "CBGX_BX_EDGE_ROWS=1" "CBGX_TRAIN_FWD_OVERLAP=0 CBGX_TRAIN_ZERO_ROWS=0" "CBGX_TRAIN_OVERLAP=0"; do for rep in 1 2; do
-env $set python bench.py --workload train --steps 20 --warmup 4 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+env $set python bench.py --full --workload train --steps 20 --warmup 4 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']['per_kernel_us_avg_and_launches']
 print('[$set] train', d['value'], 'graph-steps/s; x2h backward', d['roofline']['avg_launch_us'], 'us; gather', r.get('edge_rows_reduce'))"; done; done | tee $OUT/train_knobs_$TAG.log

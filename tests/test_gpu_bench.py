@@ -25,7 +25,7 @@ def _run(args, env=None, timeout=600):
 
 
 def test_bench_line_contract_small_job():
-    out = _run(["--steps", "2", "--warmup", "1", "--pockets", "4", "--graphs-per-batch", "20", "--no-cpu-baseline"])
+    out = _run(["--full", "--steps", "2", "--warmup", "1", "--pockets", "4", "--graphs-per-batch", "20", "--no-cpu-baseline"])
     assert "secondary" not in out          # only the default (driver) workload carries the secondary block
     assert "profiles/traffic_x2h.json" in out["roofline"]["traffic_source"]
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -39,6 +39,28 @@ def test_bench_line_contract_small_job():
     r = out["roofline"]
     assert r["bound"] == "hbm" and 0 < r["frac"] < 1.5 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-4
 
+
+
+@pytest.mark.parametrize("workload", ["denovo", "train"])
+def test_plain_bench_line_and_dumped_outputs(workload, tmp_path):
+    """a plain run (no --full) measures the headline only; --dump-outputs writes what the last timed step computed, as float32"""
+    args = ["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)]
+    args += ["--pockets", "4", "--graphs-per-batch", "20"] if workload == "denovo" else ["--workload", "train", "--pockets", "4"]
+    out = _run(args)
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["dtype"] == "f32"
+    for k in ("roofline", "cpu_baseline", "secondary"):
+        assert k not in out, k
+    import numpy as np
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    if workload == "denovo":
+        assert sorted(got) == ["c_lig", "x_lig"]
+        n_lig = got["x_lig"].shape[0]
+        assert got["x_lig"].shape == (n_lig, 3) and got["c_lig"].shape == (n_lig, 13) and 40 * 10 <= n_lig <= 40 * 45
+    else:
+        assert {"loss", "grad_norm", "grads", "params"} <= set(got) and got["grads"].shape == got["params"].shape
+        assert got["params"].size > 1_000_000 and got["loss"].shape == (1,)
 
 def test_bench_one_rank_through_rccl():
     """the collectives of the N-GPU job on the backend the driver's run uses: a one-rank RCCL group (CBGX_DIST_FORCE=1) takes

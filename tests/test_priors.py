@@ -9,8 +9,6 @@ import torch
 
 from cbgbench_amd import priors, synthetic
 
-REF_TABLE = "/root/reference/repo/datasets/transforms/_atom_num_dist.npy"
-
 
 @pytest.fixture(scope="module")
 def gold(golden_dir):
@@ -32,9 +30,9 @@ def test_bin_lookup_matches_reference(gold):
     assert dist.bin_index(1e9) == len(gold["bounds"])
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TABLE), reason="the reference's histogram table is only in the build container")
-def test_sampler_distribution_matches_reference_table(gold):
-    dist = priors.NumDist.from_npy(REF_TABLE)
+def test_sampler_distribution_matches_reference_table(gold, golden_dir):
+    # the reference's _atom_num_dist.npy, stored as tests/golden/atom_num_dist.npy (oracle/make_golden.py::atom_num_table)
+    dist = priors.NumDist.from_npy(os.path.join(golden_dir, "atom_num_dist.npy"))
     assert np.allclose(dist.bounds, gold["bounds"])
     rng = np.random.default_rng(0)
     draws = dist.sample(gold["space_size"], 20000, rng)

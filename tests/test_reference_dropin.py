@@ -12,7 +12,7 @@ import pytest
 import torch
 
 REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "repo")), reason="needs the reference tree at /root/reference")
+needs_reference = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "repo")), reason="needs the reference tree")
 
 
 @pytest.fixture(scope="module")
@@ -67,6 +67,7 @@ def _plain(c):
     return c
 
 
+@needs_reference
 @pytest.mark.parametrize("name", ["targetdiff", "diffbp", "diffsbdd"])
 def test_reference_model_class_builds_with_the_libcbgx_encoder_and_loads_strictly_both_ways(ref, patched_factory, name):
     from cbgbench_amd.unitransformer import UniTransformer as CbgxUniTransformer
@@ -105,6 +106,7 @@ def test_reference_model_class_builds_with_the_libcbgx_encoder_and_loads_strictl
         assert kb == kb2 and torch.equal(b, b2), kb
 
 
+@needs_reference
 def test_forward_signature_is_the_reference_keyword_call():
     """targetdiff.py:158-162: self.denoiser(batch_idx=batch_idx, **context_composed), keys {'x','h','gen_flag','lig_flag'}; the
     reference's own forward is (x, h, batch_idx, lig_flag, gen_flag) positionally (unitransformer.py:102)"""
@@ -119,6 +121,7 @@ def test_forward_signature_is_the_reference_keyword_call():
     ours.bind(None, batch_idx=0, x=1, h=2, gen_flag=3, lig_flag=4)
 
 
+@needs_reference
 def test_reference_sample_loop_reaches_the_libcbgx_forward_with_the_composed_tensors(ref, patched_factory, monkeypatch):
     """the reference's TargetDiff.sample (targetdiff.py:127-184), unmodified, with the swapped encoder: it composes the context and
     makes the keyword call; on this GPU-less container our forward must refuse loudly (no CPU fallback), and what it was handed must
@@ -158,6 +161,7 @@ def test_reference_sample_loop_reaches_the_libcbgx_forward_with_the_composed_ten
     assert torch.equal(torch.cat([h_rec, h_lig])[sort_idx], kw["h"])
 
 
+@needs_reference
 @pytest.mark.parametrize("override,text", [
     (dict(cutoff_mode="radius"), "Not supported cutoff mode"),           # the reference's own text (unitransformer.py:85)
     (dict(cutoff_mode="hybrid"), "Not supported cutoff mode"),
