@@ -62,6 +62,8 @@ EXPORTS = {
                                                   _vp, _sz, _vp]),
     "cbgx_unitransformer_backward": (_i, [_vp, _i, _i, _vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, ctypes.POINTER(_vp), _i,
                                           _vp, _vp, _sz, _vp]),
+    "cbgx_unitransformer_backward_ex": (_i, [_vp, _i, _i, _vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, ctypes.POINTER(_vp), _i,
+                                             _vp, _vp, _vp, _sz, _vp]),
     "cbgx_x2h_attention_backward": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,
                                          ctypes.POINTER(_vp), _vp, _sz, _vp]),
     "cbgx_h2x_attention_backward": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,
@@ -70,6 +72,8 @@ EXPORTS = {
     "cbgx_h2x_stack_forward_train": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp, _sz, _vp]),
     "cbgx_h2x_stack_backward": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp, _i, _vp, ctypes.POINTER(_vp), _i, _vp, _vp, _sz,
                                      _vp]),
+    "cbgx_h2x_stack_backward_ex": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp, _i, _vp, ctypes.POINTER(_vp), _i, _vp, _vp, _vp,
+                                        _sz, _vp]),
     "cbgx_profile_begin": (_i, [_i]),
     "cbgx_profile_end": (_i, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i), _i]),
 }

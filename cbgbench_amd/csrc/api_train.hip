@@ -451,12 +451,14 @@ static int attention_block_backward(bool x2h, const float* att, const float* x, 
     return CBGX_OK;
 }
 
-// backward of the distance gate: weight gradients from the accumulated dL/de_w, on the workspace's gate slabs (no buffer of a block set)
+// backward of the distance gate: weight gradients from the accumulated dL/de_w, on the workspace's gate slabs (no buffer of a block set);
+// grad_x != NULL: the gate's coordinate gradient is also ADDED to grad_x (the kernel's DX variant)
 static int gate_backward(const float* packed, const float* xs, const int32_t* nbr, const int32_t* deg, int n, TrainWs& w_all,
-                         float* const* grads, hipStream_t s, const int* rows = nullptr, const int* n_rows = nullptr) {
+                         float* const* grads, hipStream_t s, const int* rows = nullptr, const int* n_rows = nullptr,
+                         float* grad_x = nullptr) {
     TrainWs w = w_all;
     w.folded = w_all.gate_folded;
-    HIP_TRY(launch_gate_backward_mfma(packed, xs, nbr, deg, n, w.de_w, w.gate_partial, GATE_GRID, s, rows, n_rows));
+    HIP_TRY(launch_gate_backward_mfma(packed, xs, nbr, deg, n, w.de_w, w.gate_partial, GATE_GRID, s, rows, n_rows, grad_x));
     FOLDED(w.gate_partial, GATE_GRID, GB_SIZE, GB_SIZE);
     RS(fz + GB_W1, fn, fs, G, GH, G, grads[0], G, 0);
     RS(fz + GB_B1, fn, fs, GH, 1, GH, grads[1], GH, 0);
@@ -650,6 +652,16 @@ int cbgx_unitransformer_backward(const float* packed, int num_layers, int num_cl
                                  const float* grad_x_out, const float* grad_h_out, const float* grad_logits,
                                  float* const* grads, int num_grads, float* grad_h_in, void* workspace,
                                  size_t workspace_bytes, void* stream) {
+    return cbgx_unitransformer_backward_ex(packed, num_layers, num_classes, tape, tape_bytes, lig_flag, gen_flag, n_nodes, grad_x_out,
+                                           grad_h_out, grad_logits, grads, num_grads, grad_h_in, nullptr, workspace, workspace_bytes,
+                                           stream);
+}
+
+int cbgx_unitransformer_backward_ex(const float* packed, int num_layers, int num_classes, const void* tape,
+                                    size_t tape_bytes, const uint8_t* lig_flag, const uint8_t* gen_flag, int n_nodes,
+                                    const float* grad_x_out, const float* grad_h_out, const float* grad_logits,
+                                    float* const* grads, int num_grads, float* grad_h_in, float* grad_x_in, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
     if (n_nodes <= 0 || num_layers < 1 || num_classes < 1) return set_error(CBGX_E_INVALID, "backward: bad sizes");
     if (!packed || !tape || !lig_flag || !gen_flag || !workspace) return set_error(CBGX_E_INVALID, "backward: NULL pointer");
     if (num_grads != 6 + 36 * num_layers + 4)
@@ -808,9 +820,16 @@ int cbgx_unitransformer_backward(const float* packed, int num_layers, int num_cl
         cur = nxt;
     }
     if (grad_h_in) HIP_TRY(hipMemcpyAsync(grad_h_in, gh_cur, nh * 4, hipMemcpyDeviceToDevice, s));
+    // grad_x_in: w.gx[cur] now holds dL/dx_0 through the layer chain (the identity paths, every h2x block's rel_x and distance terms,
+    // the distance terms of every x2h block); the gate adds its own distance path below.  Under every pruning mode this is exact:
+    // a block skips only rows whose dL/dh (x2h) or dL/dx (h2x) is exactly zero, and every coordinate term of an edge (i, j) is a
+    // product with that edge's upstream gradient, which is zero when row i is skipped -- so the skipped rows contribute exactly
+    // zero to both x_i and x_j.  The same holds for the gate: dL/de_w is zero on every edge no block wrote.  (The edge-row mode
+    // changes only how dL/dh is summed; its coordinate terms use the same atomics.)
+    if (grad_x_in) HIP_TRY(hipMemcpyAsync(grad_x_in, w.gx[cur], nx * 4, hipMemcpyDeviceToDevice, s));
     // distance gate (computed once from the input coordinates, used by all 2L blocks): on its own slab buffers, BEFORE the auxiliary
     // stream is joined -- the last blocks' weight-gradient kernels (~150 us) run beside it instead of ahead of it
-    RC_TRY(gate_backward(packed, tp.xs, tp.nbr, tp.deg, n, w, grads, s));
+    RC_TRY(gate_backward(packed, tp.xs, tp.nbr, tp.deg, n, w, grads, s, nullptr, nullptr, grad_x_in));
     // the auxiliary stream's last weight gradients must be in place when this call's work on `s` is: join both sets
     if (ov.aux)
         for (int k = 0; k < 2; ++k)
@@ -884,6 +903,14 @@ int cbgx_h2x_stack_backward(const float* packed, int num_layers, const void* tap
                             const uint8_t* lig_flag, const uint8_t* gen_flag, int n_nodes, const float* grad_x_out,
                             float* const* grads, int num_grads, float* grad_h, void* workspace, size_t workspace_bytes,
                             void* stream) {
+    return cbgx_h2x_stack_backward_ex(packed, num_layers, tape, tape_bytes, h, lig_flag, gen_flag, n_nodes, grad_x_out, grads,
+                                      num_grads, grad_h, nullptr, workspace, workspace_bytes, stream);
+}
+
+int cbgx_h2x_stack_backward_ex(const float* packed, int num_layers, const void* tape, size_t tape_bytes, const float* h,
+                               const uint8_t* lig_flag, const uint8_t* gen_flag, int n_nodes, const float* grad_x_out,
+                               float* const* grads, int num_grads, float* grad_h, float* grad_x_in, void* workspace,
+                               size_t workspace_bytes, void* stream) {
     if (n_nodes <= 0 || num_layers < 1) return set_error(CBGX_E_INVALID, "h2x_stack_backward: bad sizes");
     if (!packed || !tape || !h || !lig_flag || !gen_flag || !grad_x_out || !grad_h || !workspace)
         return set_error(CBGX_E_INVALID, "h2x_stack_backward: NULL pointer");
@@ -927,8 +954,12 @@ int cbgx_h2x_stack_backward(const float* packed, int num_layers, const void* tap
         cur = nxt;
     }
     HIP_TRY(hipMemcpyAsync(grad_h, w.gh, nh * 4, hipMemcpyDeviceToDevice, s));
+    // grad_x_in: the chain's dL/dx_0 (identity paths + the blocks' coordinate terms; the listed products skip only rows whose terms are
+    // exactly zero, as in the denoiser's backward), then the gate's distance path, which lives on the movable rows' edges only
+    if (grad_x_in) HIP_TRY(hipMemcpyAsync(grad_x_in, w.gx[cur], nx * 4, hipMemcpyDeviceToDevice, s));
     // (the stack's blocks add to de_w on the movable rows only: the gate backward walks that list -- 16.5 k rows -> ~900)
-    RC_TRY(gate_backward(packed, tp.xs, tp.nbr, tp.deg, n, w, grads, s, lists ? w.act : nullptr, lists ? w.act_count : nullptr));
+    RC_TRY(gate_backward(packed, tp.xs, tp.nbr, tp.deg, n, w, grads, s, lists ? w.act : nullptr, lists ? w.act_count : nullptr,
+                         grad_x_in));
     if (ov.aux)
         for (int k = 0; k < 2; ++k)
             if (ov.used[k]) HIP_TRY(hipStreamWaitEvent(s, ov.aux->done[k], 0));

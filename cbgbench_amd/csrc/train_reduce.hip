@@ -290,8 +290,8 @@ __global__ __launch_bounds__(256) void sgemm_kernel(const float* __restrict__ A,
 
 // ------------------------------------------------------------------------------------------------
 // distance gate backward (unitransformer.py:109-112): pass 1 per edge (scalars of the LayerNorm
-// backward), pass 2 per hidden unit (weight gradients).  The gate reads the *input* coordinates, which
-// are data, so no coordinate gradient is produced.
+// backward), pass 2 per hidden unit (weight gradients).  The gate reads the *input* coordinates: the
+// training step treats them as data (no coordinate gradient); gate_bwd_dx_mfma_kernel below also forms it.
 // ------------------------------------------------------------------------------------------------
 
 // ONE kernel on the matrix pipe.  A wave owns tiles of 16 edge slots (half a node):
@@ -469,6 +469,216 @@ __global__ __launch_bounds__(GATE_WAVES * 64) void gate_bwd_mfma_kernel(const fl
     if (lane == 0) slab[GB_B2] = vb2;
 }
 
+// DX variant: the same weight gradients, and also dL/dx_in of the gate ADDED to grad_x (fp32 atomics) -- callers that differentiate with
+// respect to the input coordinates (cbgx_unitransformer_backward_ex / cbgx_h2x_stack_backward_ex).  A kernel of its own, so that the one
+// every training step launches keeps its instruction stream; the two must stay in step (both are pinned by the same oracle gradients).
+// The coordinate gradient, dL/dd = sum_g dR_g drbf_g/dd with dR = dpre W1, is reassociated as
+//   dL/dd = sum_u dpre_u V_u,   V = R' W1^T,   R'_g = drbf_g/dd = -(d - mu_g) exp(-0.5 (d - mu_g)^2)
+// V is the forward product with the rbf derivative in place of the rbf: the same A / B layouts (W1 is already in registers as its B
+// operand), 5 MFMAs per unit tile issued next to that tile's d W1 MFMAs, and V lands in the D layout of dpre -- the sum over the 160
+// units is one multiply-add per (tile, register) and a row16_sum per edge: no transpose of dpre, four live accumulators instead of a
+// [16 x 20] dR.  The derivative operand is recomputed there rather than kept from the Y product (5 registers less through the tile).
+// Then dx_i += dL/dd (x_i - x_j) / d and dx_j -= the same (d == 0: zero, as the edge backwards do); node i's share is summed over the
+// tile's 16 slots before its atomic.  Invalid slots have a zero upstream dew, hence a zero dpre and dL/dd, and issue no atomic.
+// Modelled lane by lane in tests/test_lanesim_gate_dx.py.
+__global__ __launch_bounds__(GATE_WAVES * 64) void gate_bwd_dx_mfma_kernel(const float* __restrict__ wts, const float* __restrict__ x,
+                                                                         const int32_t* __restrict__ nbr,
+                                                                         const int32_t* __restrict__ deg, int n_nodes,
+                                                                         const float* __restrict__ de_w, float* __restrict__ partial,
+                                                                         const int* __restrict__ rows, const int* __restrict__ n_rows_ptr,
+                                                                         float* __restrict__ grad_x) {
+    typedef float floatx4 __attribute__((ext_vector_type(4)));
+    constexpr int NT = GH / 16;
+    constexpr int KS = G / 4;
+    __shared__ float sP[4][GH];      // b1 | gamma | beta | W2
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, q = lane >> 4;
+    for (int u = tid; u < 4 * GH; u += GATE_WAVES * 64) (&sP[0][0])[u] = wts[GATE_B1 + u];
+    __syncthreads();
+    float w1[NT][KS];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int s = 0; s < KS; ++s) w1[nt][s] = wts[GATE_W1 + (size_t)(16 * nt + j) * G + 4 * s + q];
+    const float b2 = wts[GATE_B2];
+    float mu_a[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) mu_a[s] = c_mu_b[4 * s + q];
+    const float mu_b0 = c_mu_b[j], mu_b1 = c_mu_b[16 + (j & 3)];
+    floatx4 dw[NT][2];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) { dw[nt][0] = floatx4{0.f, 0.f, 0.f, 0.f}; dw[nt][1] = floatx4{0.f, 0.f, 0.f, 0.f}; }
+    float aB1[NT], aG[NT], aBe[NT], aW2[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) { aB1[nt] = 0.f; aG[nt] = 0.f; aBe[nt] = 0.f; aW2[nt] = 0.f; }
+    float aB2 = 0.f;
+    const long n_tiles = (long)(rows ? *n_rows_ptr : n_nodes) * (KNN / 16);
+    const long stride = (long)gridDim.x * GATE_WAVES;
+    long tile = (long)blockIdx.x * GATE_WAVES + wave;
+    // lane (j, *) <-> edge slot 16 (tile & 1) + j of node tile >> 1; fetched one tile ahead (with the neighbour: the coordinate atomics)
+    float dist_n = 0.f, dew_n = 0.f;
+    int nb_n = 0;
+    auto fetch = [&](long tl) {
+        const int i = rows ? rows[tl >> 1] : (int)(tl >> 1), sl = 16 * (int)(tl & 1) + j;
+        const bool valid = sl < deg[i];
+        const int nb = valid ? nbr[(size_t)i * KNN + sl] : i;
+        const float dx = x[3 * i] - x[3 * nb], dy = x[3 * i + 1] - x[3 * nb + 1], dz = x[3 * i + 2] - x[3 * nb + 2];
+        dist_n = sqrtf(dx * dx + dy * dy + dz * dz);
+        dew_n = valid ? de_w[(size_t)i * KNN + sl] : 0.f;
+        nb_n = nb;
+    };
+    if (tile < n_tiles) fetch(tile);
+    for (; tile < n_tiles; tile += stride) {
+        const float dist = dist_n, dew = dew_n;
+        const int nbj = nb_n;
+        fetch(tile + stride < n_tiles ? tile + stride : tile);
+        // ---- Y = R W1^T + b1
+        floatx4 y[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) y[nt] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const float t = dist - mu_a[s];
+            const float ra = expf(-0.5f * (t * t));
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) y[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(ra, w1[nt][s], y[nt], 0, 0, 0);
+        }
+        float sum[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const float b1 = sP[0][16 * nt + j];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { y[nt][r] += b1; sum[r] += y[nt][r]; }
+        }
+        float mean[4], rstd[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) mean[r] = row16_sum(sum[r]) * (1.f / GH);
+        float var[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { y[nt][r] -= mean[r]; var[r] = fmaf(y[nt][r], y[nt][r], var[r]); }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) rstd[r] = 1.f / sqrtf(row16_sum(var[r]) * (1.f / GH) + 1e-5f);
+        // ---- gate value -> d L / d (pre-sigmoid) of the four edges 4 q + r
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const float gam = sP[1][16 * nt + j], bet = sP[2][16 * nt + j], w2 = sP[3][16 * nt + j];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                y[nt][r] *= rstd[r];
+                acc[r] = fmaf(w2, fmaxf(fmaf(y[nt][r], gam, bet), 0.f), acc[r]);
+            }
+        }
+        float dacc[4], dist_e[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float a = row16_sum(acc[r]) + b2;
+            const float ew = 1.f / (1.f + expf(-a));
+            dacc[r] = __shfl(dew, 4 * q + r, 64) * ew * (1.f - ew);
+            dist_e[r] = __shfl(dist, 4 * q + r, 64);
+        }
+        // ---- LayerNorm backward
+        float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const float gam = sP[1][16 * nt + j], bet = sP[2][16 * nt + j], w2 = sP[3][16 * nt + j];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float n = y[nt][r];
+                const float ya = fmaf(n, gam, bet);
+                aW2[nt] = fmaf(dacc[r], fmaxf(ya, 0.f), aW2[nt]);
+                const float dy = ya > 0.f ? dacc[r] * w2 : 0.f;
+                aG[nt] = fmaf(dy, n, aG[nt]);
+                aBe[nt] += dy;
+                const float dn = dy * gam;
+                s1[r] += dn;
+                s2[r] = fmaf(dn, n, s2[r]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { s1[r] = row16_sum(s1[r]) * (1.f / GH); s2[r] = row16_sum(s2[r]) * (1.f / GH); }
+        if (j == 0) aB2 += (dacc[0] + dacc[1]) + (dacc[2] + dacc[3]);
+        float rb0[4], rb1[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float t0 = dist_e[r] - mu_b0, t1 = dist_e[r] - mu_b1;
+            rb0[r] = expf(-0.5f * (t0 * t0));
+            rb1[r] = j < 4 ? expf(-0.5f * (t1 * t1)) : 0.f;
+        }
+        // A operand of V = R' W1^T: the rbf derivative of edge j at g = 4 s + q
+        float rd[KS];
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const float t = dist - mu_a[s];
+            rd[s] = -t * expf(-0.5f * (t * t));
+        }
+        float ddp[4] = {0.f, 0.f, 0.f, 0.f};      // this lane's part of dL/dd of edge 4 q + r (units 16 nt + j)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const float gam = sP[1][16 * nt + j], bet = sP[2][16 * nt + j], w2 = sP[3][16 * nt + j];
+            floatx4 v = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < KS; ++s) v = __builtin_amdgcn_mfma_f32_16x16x4f32(rd[s], w1[nt][s], v, 0, 0, 0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float n = y[nt][r];
+                const float dn = fmaf(n, gam, bet) > 0.f ? dacc[r] * w2 * gam : 0.f;
+                const float dp = rstd[r] * (dn - s1[r] - n * s2[r]);
+                aB1[nt] += dp;
+                ddp[r] = fmaf(dp, v[r], ddp[r]);
+                dw[nt][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(dp, rb0[r], dw[nt][0], 0, 0, 0);
+                dw[nt][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(dp, rb1[r], dw[nt][1], 0, 0, 0);
+            }
+        }
+        // ---- coordinates.  dL/dd of edge 4 q + r is in every lane of row q; lane (j, *) takes its own slot's (row j >> 2, register j & 3)
+        float dd[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dd[r] = __shfl(row16_sum(ddp[r]), 16 * (j >> 2), 64);
+        const float ddj = (j & 2) ? ((j & 1) ? dd[3] : dd[2]) : ((j & 1) ? dd[1] : dd[0]);
+        const int inode = rows ? rows[tile >> 1] : (int)(tile >> 1);
+        // (x_i - x_j) / d, reloaded here (L2 hits: the fetch read them one tile ago) rather than carried through the tile
+        const float inv = dist > 0.f ? ddj / dist : 0.f;
+        const float cx = (x[3 * inode] - x[3 * nbj]) * inv, cy = (x[3 * inode + 1] - x[3 * nbj + 1]) * inv,
+                    cz = (x[3 * inode + 2] - x[3 * nbj + 2]) * inv;
+        // node i: the tile's 16 slots summed over the row first, one atomic per component; the neighbours: one per valid slot
+        const float sx = row16_sum(cx), sy = row16_sum(cy), sz = row16_sum(cz);
+        if (q == 0) {
+            if (j == 0) {
+                atomicAdd(grad_x + 3 * inode, sx);
+                atomicAdd(grad_x + 3 * inode + 1, sy);
+                atomicAdd(grad_x + 3 * inode + 2, sz);
+            }
+            if (nbj != inode) {
+                atomicAdd(grad_x + 3 * nbj, -cx);
+                atomicAdd(grad_x + 3 * nbj + 1, -cy);
+                atomicAdd(grad_x + 3 * nbj + 2, -cz);
+            }
+        }
+    }
+    float* slab = partial + ((size_t)blockIdx.x * GATE_WAVES + wave) * GB_SIZE;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int u = 16 * nt + 4 * q + rr;
+            slab[GB_W1 + u * G + j] = dw[nt][0][rr];
+            if (j < 4) slab[GB_W1 + u * G + 16 + j] = dw[nt][1][rr];
+        }
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const float v1 = xrow_sum(aB1[nt]), v2 = xrow_sum(aG[nt]), v3 = xrow_sum(aBe[nt]), v4 = xrow_sum(aW2[nt]);
+        if (q == 0) {
+            slab[GB_B1 + 16 * nt + j] = v1;
+            slab[GB_LNG + 16 * nt + j] = v2;
+            slab[GB_LNB + 16 * nt + j] = v3;
+            slab[GB_W2 + 16 * nt + j] = v4;
+        }
+    }
+    const float vb2 = xrow_sum(aB2);
+    if (lane == 0) slab[GB_B2] = vb2;
+}
+
 // classifier: d(pre) = d(act) * sigmoid(pre)   (derivative of softplus(x) - ln 2)
 __global__ void ssp_backward_kernel(const float* __restrict__ pre, const float* __restrict__ dact, long n,
                                     float* __restrict__ dpre) {
@@ -613,10 +823,16 @@ hipError_t launch_sgemm(bool ta, bool tb, const float* A, int lda, const float* 
 }
 
 // product path: one fused kernel; `grid` slabs of GB_SIZE floats in `partial`, every one written (grid a multiple of GATE_WAVES)
+// grad_x != NULL: the DX variant, which also adds the gate's coordinate gradient to grad_x
 hipError_t launch_gate_backward_mfma(const float* packed, const float* x, const int32_t* nbr, const int32_t* deg, int n_nodes,
-                                     const float* de_w, float* partial, int grid, hipStream_t s, const int* rows, const int* n_rows) {
-    hipLaunchKernelGGL(gate_bwd_mfma_kernel, dim3(grid / GATE_WAVES), dim3(GATE_WAVES * 64), 0, s, packed, x, nbr, deg, n_nodes,
-                       de_w, partial, rows, n_rows);
+                                     const float* de_w, float* partial, int grid, hipStream_t s, const int* rows, const int* n_rows,
+                                     float* grad_x) {
+    if (grad_x)
+        hipLaunchKernelGGL(gate_bwd_dx_mfma_kernel, dim3(grid / GATE_WAVES), dim3(GATE_WAVES * 64), 0, s, packed, x, nbr, deg, n_nodes,
+                           de_w, partial, rows, n_rows, grad_x);
+    else
+        hipLaunchKernelGGL(gate_bwd_mfma_kernel, dim3(grid / GATE_WAVES), dim3(GATE_WAVES * 64), 0, s, packed, x, nbr, deg, n_nodes,
+                           de_w, partial, rows, n_rows);
     CBGX_LAUNCH_CHECK();
     return hipSuccess;
 }

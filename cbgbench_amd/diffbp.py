@@ -71,7 +71,8 @@ class MaskTypeSchedule(nn.Module):
 
 class _H2XStackFunction(torch.autograd.Function):
     """taped forward / hand-written backward of the H2X stack (cbgx_h2x_stack_forward_train / _backward); gradients flow
-    to h (the denoiser's output features) and to the stack's parameters, not to the input coordinates (data)."""
+    to h (the denoiser's output features), to the stack's parameters and, when x requires grad, to the input coordinates
+    (cbgx_h2x_stack_backward_ex: the blocks and the stack's distance gate)."""
 
     @staticmethod
     def forward(ctx, module, x, h, graph_ptr, lig, gen, *params):
@@ -109,14 +110,19 @@ class _H2XStackFunction(torch.autograd.Function):
         ws = module.train_workspace(N, dev)
         if direct:
             module._direct_written = True
-        rc = _native.lib().cbgx_h2x_stack_backward(
-            _native.ptr(ctx.packed), L, _native.ptr(ctx.tape), ctx.tape.numel(), _native.ptr(ctx.h), _native.ptr(lig),
-            _native.ptr(gen), N, _native.ptr(gx.contiguous().float()), arr, len(views), _native.ptr(gh), _native.ptr(ws),
-            ws.numel(), _native.current_stream(dev))
+        args = (_native.ptr(ctx.packed), L, _native.ptr(ctx.tape), ctx.tape.numel(), _native.ptr(ctx.h), _native.ptr(lig),
+                _native.ptr(gen), N, _native.ptr(gx.contiguous().float()), arr, len(views), _native.ptr(gh))
+        tail = (_native.ptr(ws), ws.numel(), _native.current_stream(dev))
+        gx_in = None
+        if ctx.needs_input_grad[1]:
+            gx_in = torch.empty(N, 3, dtype=torch.float32, device=dev)
+            rc = _native.lib().cbgx_h2x_stack_backward_ex(*args, _native.ptr(gx_in), *tail)
+        else:
+            rc = _native.lib().cbgx_h2x_stack_backward(*args, *tail)
         _native.check(rc, "cbgx_h2x_stack_backward")
         if direct:
-            return (None, None, gh, None, None, None) + (None,) * len(views)
-        return (None, None, gh, None, None, None, *[v.view(s) for v, s in zip(views, ctx.param_shapes)])
+            return (None, gx_in, gh, None, None, None) + (None,) * len(views)
+        return (None, gx_in, gh, None, None, None, *[v.view(s) for v, s in zip(views, ctx.param_shapes)])
 
 
 class _DiffBPLossFunction(torch.autograd.Function):
@@ -251,12 +257,14 @@ class CoMPredictor(nn.Module):
     def stack_output(self, x_composed, h_composed, gen_flag_composed, lig_flag_composed, graph_ptr):
         """the stack's output positions [N,3] for the composed graph, with the autograd bridge of ``forward`` (training path of the
         fused losses, which take the ligand rows' displacement themselves)"""
-        x_in = x_composed.detach().float().contiguous()
         lig8 = lig_flag_composed.to(torch.uint8).contiguous()
         gen8 = gen_flag_composed.to(torch.uint8).contiguous()
-        if torch.is_grad_enabled() and (h_composed.requires_grad or any(p.requires_grad for p in self.parameters())):
+        if torch.is_grad_enabled() and (x_composed.requires_grad or h_composed.requires_grad
+                                        or any(p.requires_grad for p in self.parameters())):
+            x_in = x_composed.float().contiguous() if x_composed.requires_grad else x_composed.detach().float().contiguous()
             return _H2XStackFunction.apply(self, x_in, h_composed.float().contiguous(), graph_ptr, lig8, gen8, *self._ordered_params())
-        return self.stack_forward(x_in, h_composed.detach().float().contiguous(), graph_ptr, lig8, gen8)
+        return self.stack_forward(x_composed.detach().float().contiguous(), h_composed.detach().float().contiguous(), graph_ptr, lig8,
+                                  gen8)
 
     def forward(self, x_lig_pred, batch_idx_lig, x_composed, h_composed, gen_flag_composed, lig_flag_composed,
                 batch_idx_composed, graph_ptr=None, n_graphs=None, lig_rows=None):
@@ -276,7 +284,10 @@ class CoMPredictor(nn.Module):
         noise = x_lig_pred - pick(x_composed)
         noise = noise - _S.scatter_mean(noise, batch_idx_lig, B)[batch_idx_lig]
         x_in = x_composed.detach().float().contiguous()
-        if torch.is_grad_enabled() and (h_composed.requires_grad or any(p.requires_grad for p in self.parameters())):
+        if torch.is_grad_enabled() and (x_composed.requires_grad or h_composed.requires_grad
+                                        or any(p.requires_grad for p in self.parameters())):
+            if x_composed.requires_grad:       # the coordinates are differentiated too: the stack's input and the displacement
+                x_in = x_composed.float().contiguous()
             x_out = _H2XStackFunction.apply(self, x_in, h_composed.float().contiguous(), graph_ptr,
                                             lig_flag_composed.to(torch.uint8).contiguous(),
                                             gen_flag_composed.to(torch.uint8).contiguous(), *self._ordered_params())

@@ -350,7 +350,9 @@ class _ComposeEmbedFunction(torch.autograd.Function):
     """``PLContextEmbedder`` on both atom sets + ``compose_context`` of coordinates, features and the movable flag
     (repo/modules/context_emb.py:137-230, repo/modules/common.py:189-214) as one launch; the backward is the weight gradient of ONE
     Linear over "extended input" rows the forward leaves behind (csrc/train_embed.hip, cbgx_embed_compose{,_backward}) -- two launches
-    instead of index_put's sort, three thin GEMMs and five column sums."""
+    instead of index_put's sort, three thin GEMMs and five column sums.  The composed coordinates are a permutation of
+    ``cat(x_rec, x_lig)``: differentiable when either input requires grad (the gradient is permuted back), otherwise marked
+    non-differentiable as before, so a training step's autograd graph is unchanged."""
 
     @staticmethod
     def forward(ctx, x_rec, x_lig, feat, aa, c_lig, sort_idx, gen_r, gen_l, w_pa, b_pa, w_res, b_res, w_la, b_la, w_ind, b_ind):
@@ -368,14 +370,26 @@ class _ComposeEmbedFunction(torch.autograd.Function):
             _native.ptr(x_rec), _native.ptr(x_lig), _native.ptr(feat), _native.ptr(aa), _native.ptr(c_lig), _native.ptr(sort_idx),
             _native.ptr(gen_r), _native.ptr(gen_l), n_rec, n_lig, dims[0], dims[1], dims[2], arr, _native.ptr(x), _native.ptr(h),
             _native.ptr(ext), _native.ptr(gen), _native.current_stream(dev)), "cbgx_embed_compose")
-        ctx.save_for_backward(ext)
+        need_x = x_rec.requires_grad or x_lig.requires_grad
+        ctx.save_for_backward(ext, sort_idx if need_x else None)
         ctx.dims = dims
-        ctx.mark_non_differentiable(x, gen)
+        ctx.n_rec = n_rec
+        if need_x:
+            ctx.mark_non_differentiable(gen)
+        else:
+            ctx.mark_non_differentiable(x, gen)
         return x, h, gen
 
     @staticmethod
-    def backward(ctx, _gx, gh, _gg):
-        (ext,) = ctx.saved_tensors
+    def backward(ctx, gx, gh, _gg):
+        ext, sort_idx = ctx.saved_tensors
+        gx_rec = gx_lig = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            # x = cat(x_rec, x_lig)[sort_idx], sort_idx a permutation: dL/dcat[sort_idx] = dL/dx
+            g = torch.zeros(sort_idx.shape[0], 3, dtype=torch.float32, device=ext.device)
+            if gx is not None:
+                g[sort_idx] = gx.to(torch.float32)
+            gx_rec, gx_lig = g[:ctx.n_rec], g[ctx.n_rec:]
         Fd, A, C = ctx.dims
         N, dev = ext.shape[0], ext.device
         groups = max(1, min(64, (N + 127) // 128))
@@ -385,7 +399,8 @@ class _ComposeEmbedFunction(torch.autograd.Function):
             _native.ptr(gh.to(torch.float32).contiguous()), _native.ptr(ext), N, Fd, A, C, _native.ptr(partial), groups,
             _native.ptr(out), _native.current_stream(dev)), "cbgx_embed_compose_backward")
         dw_pa, dw_res, u, dw_la, v = out.split([128 * Fd, 128 * A, 128, 128 * C, 128])
-        return (None,) * 8 + (dw_pa.view(128, Fd), u, dw_res.view(128, A), u, dw_la.view(128, C), v, v.view(128, 1), u + v)
+        return (gx_rec, gx_lig) + (None,) * 6 + (dw_pa.view(128, Fd), u, dw_res.view(128, A), u, dw_la.view(128, C), v, v.view(128, 1),
+                                                 u + v)
 
 
 def compose_embed(embedder, x_rec, x_lig, feat_rec, aa_rec, c_lig, sort_idx, gen_r, gen_l, fused=True):

@@ -3,7 +3,8 @@
 reference's checkpoints ``load_state_dict(strict=True)``), same ``forward`` signature -- but
 ``forward`` runs entirely in libcbgx (hand-written gfx950 kernels) through the C ABI of
 include/cbgx.h; with gradients enabled it goes through ``_DenoiserFunction``, whose backward is
-libcbgx's hand-written backward (``cbgx_unitransformer_backward``).  There is no PyTorch / CPU implementation of the math here: a CPU tensor or a missing
+libcbgx's hand-written backward (``cbgx_unitransformer_backward``; ``cbgx_unitransformer_backward_ex`` when the input coordinates
+require grad).  There is no PyTorch / CPU implementation of the math here: a CPU tensor or a missing
 library raises.
 
 The sub-modules below are *parameter containers* whose names reproduce the reference state-dict keys
@@ -88,8 +89,9 @@ def graph_ptr_from_batch(batch_idx, n_graphs=None):
 class _DenoiserFunction(torch.autograd.Function):
     """autograd bridge of the training path: forward = cbgx_unitransformer_forward_train (keeps a tape of the
     per-layer inputs), backward = cbgx_unitransformer_backward (hand-written gfx950 backward kernels).  The
-    parameters are passed as inputs so that autograd routes their gradients; no gradient is produced for the
-    coordinates (they are data in every training loss of the reference, targetdiff.py:87-101)."""
+    parameters are passed as inputs so that autograd routes their gradients.  The coordinates are data in every training loss of
+    the reference (targetdiff.py:87-101); when they require grad (guidance, sensitivity analyses), the backward is
+    cbgx_unitransformer_backward_ex, which also returns dL/dx: the layer chain and the distance gate."""
 
     @staticmethod
     def forward(ctx, module, ligand_outputs_only, x, h, graph_ptr, lig, gen, *params):
@@ -169,15 +171,20 @@ class _DenoiserFunction(torch.autograd.Function):
             gh = torch.zeros(N, module.hidden_dim, dtype=torch.float32, device=device)
         if direct:
             module._direct_written = True
-        rc = _native.lib().cbgx_unitransformer_backward(
-            _native.ptr(ctx.packed), L, C, _native.ptr(ctx.tape), ctx.tape.numel(), _native.ptr(lig),
-            _native.ptr(gen), N, _native.ptr(gx), _native.ptr(gh), _native.ptr(gl), arr, len(views),
-            _native.ptr(gh_in), _native.ptr(ws), ws.numel(), _native.current_stream(device))
+        args = (_native.ptr(ctx.packed), L, C, _native.ptr(ctx.tape), ctx.tape.numel(), _native.ptr(lig),
+                _native.ptr(gen), N, _native.ptr(gx), _native.ptr(gh), _native.ptr(gl), arr, len(views), _native.ptr(gh_in))
+        tail = (_native.ptr(ws), ws.numel(), _native.current_stream(device))
+        gx_in = None
+        if ctx.needs_input_grad[2]:
+            gx_in = torch.empty(N, 3, dtype=torch.float32, device=device)
+            rc = _native.lib().cbgx_unitransformer_backward_ex(*args, _native.ptr(gx_in), *tail)
+        else:
+            rc = _native.lib().cbgx_unitransformer_backward(*args, *tail)
         _native.check(rc, "cbgx_unitransformer_backward")
         if direct:
-            return (None, None, None, gh_in, None, None, None) + (None,) * len(views)
+            return (None, None, gx_in, gh_in, None, None, None) + (None,) * len(views)
         grads = [v.view(s) for v, s in zip(views, ctx.param_shapes)]
-        return (None, None, None, gh_in, None, None, None, *grads)
+        return (None, None, gx_in, gh_in, None, None, None, *grads)
 
 
 class UniTransformer(nn.Module):
@@ -412,10 +419,11 @@ class UniTransformer(nn.Module):
             graph_ptr = graph_ptr_from_batch(batch_idx)
         B = graph_ptr.numel() - 1
         lig, gen = self._as_u8(lig_flag), self._as_u8(gen_flag)
-        if torch.is_grad_enabled() and (h.requires_grad or any(p.requires_grad for p in self.parameters())):
-            # training: taped forward + hand-written backward behind torch.autograd
+        if torch.is_grad_enabled() and (x.requires_grad or h.requires_grad or any(p.requires_grad for p in self.parameters())):
+            # training: taped forward + hand-written backward behind torch.autograd (x stays attached only when it requires grad: the
+            # backward then also returns dL/dx)
             return _DenoiserFunction.apply(self, "h_on_sources" if (h_on_sources and not ligand_outputs_only) else bool(ligand_outputs_only),
-                                           x.detach().to(torch.float32).contiguous(),
+                                           (x if x.requires_grad else x.detach()).to(torch.float32).contiguous(),
                                            h.to(torch.float32).contiguous(), graph_ptr, lig, gen,
                                            *self._ordered_params())
         x = x.detach().to(torch.float32).contiguous()

@@ -282,7 +282,8 @@ int cbgx_diffsbdd_step(const float *x_den, const float *logits, const int32_t *g
  *       NULL = zero) it recomputes the per-edge intermediates block by block (nothing per-edge is ever stored) and
  *       writes dL/dh_in [N,128] (may be NULL) and the gradient of every parameter tensor: `grads` is a HOST array
  *       of DEVICE pointers, same order and shapes as the `tensors` of cbgx_pack_weights (6 + 36*L + 4), each
- *       OVERWRITTEN.  No gradient is produced for the input coordinates (they are data: targetdiff.py:87-101).
+ *       OVERWRITTEN.  No gradient is produced for the input coordinates (the training losses treat them as data:
+ *       targetdiff.py:87-101); cbgx_unitransformer_backward_ex below also returns it.
  *       PRECONDITION of grad_h_out == NULL: the caller's loss reads x_out on gen_flag rows and logits on lig_flag rows only
  *       (what TargetDiff.get_loss / DiffSBDD.get_loss do, targetdiff.py:103-121); the backward of the last x2h blocks is
  *       then pruned to the receptive field of those rows, the classifier head's backward walks the lig_flag rows only, and
@@ -313,6 +314,19 @@ int cbgx_unitransformer_backward(const float *packed, int num_layers, int num_cl
                                  const float *grad_x_out, const float *grad_h_out, const float *grad_logits,
                                  float *const *grads, int num_grads, float *grad_h_in, void *workspace,
                                  size_t workspace_bytes, void *stream);
+/* cbgx_unitransformer_backward_ex (ABI 6, additive): the same, plus grad_x_in [N,3] (may be NULL) = the full dL/dx_in, OVERWRITTEN --
+ * what autograd gives the reference's UniTransformer input `x` (unitransformer.py:102-123): the layer chain x_{l+1} = x_l + gen * H2X
+ * (h2x_attention.py:34-73: rel_x and the distance features of every block, x2h_attention.py:43-97: the distance features) and the
+ * distance gate e_w = sigmoid(MLP(rbf(|x_i - x_j|))) computed once from x (unitransformer.py:109-112).  The kNN selection itself is
+ * piecewise constant (no gradient), as in the reference.  Exact under every pruning mode of the backward above (grad_h_out == NULL,
+ * the marked support, CBGX_FWD_H_ON_SOURCES) and in the edge-row mode: skipped rows carry an exactly zero gradient.  grad_x_in is
+ * accumulated with fp32 atomics: reproducible only up to summation order.  grad_x_in == NULL: exactly cbgx_unitransformer_backward
+ * (same launches). */
+int cbgx_unitransformer_backward_ex(const float *packed, int num_layers, int num_classes, const void *tape,
+                                    size_t tape_bytes, const uint8_t *lig_flag, const uint8_t *gen_flag, int n_nodes,
+                                    const float *grad_x_out, const float *grad_h_out, const float *grad_logits,
+                                    float *const *grads, int num_grads, float *grad_h_in, float *grad_x_in, void *workspace,
+                                    size_t workspace_bytes, void *stream);
 /* Backward of one attention block (stage-level parity tests).  Inputs as the forward stage; `grads` = 18 DEVICE
  * pointers {hk,hv,hq}_func (x2h) / {xk,xv,xq}_func (h2x) x net.{0.weight,0.bias,1.weight,1.bias,3.weight,3.bias}.
  * x2h: grad_h includes the residual path.  h2x: grad_x includes the identity path of x_out = x + delta_x * gen_flag.
@@ -335,7 +349,11 @@ int cbgx_h2x_attention_backward(const float *packed, int layer, const float *x, 
  * (repo/models/diffusion/diffbp.py:79-101, 195-198).  The tape holds the stack's kNN lists, gate and per-layer
  * coordinates; h is the same tensor in every layer.  backward: grad_x_out [N,3] -> grad_h [N,128] (overwritten) and
  * `grads` = 6 + 18*L DEVICE pointers in the order of cbgx_pack_h2x_stack's `tensors`, each overwritten.  No gradient for the
- * input coordinates (they are the noised data). */
+ * input coordinates (in DiffBP's losses they are the noised data); cbgx_h2x_stack_backward_ex returns it.
+ * cbgx_h2x_stack_backward_ex (ABI 6, additive): the same, plus grad_x_in [N,3] (may be NULL) = dL/dx_in, OVERWRITTEN -- autograd of
+ * CoMPredictor's input x (diffbp.py:79-101): the stack's blocks (h2x_attention.py:34-73) and its own distance gate
+ * (diffbp.py:87-90), exact on the movable-row lists the backward walks.  fp32 atomics: reproducible only up to summation order.
+ * grad_x_in == NULL: exactly cbgx_h2x_stack_backward. */
 size_t cbgx_h2x_stack_tape_bytes(int n_nodes, int num_layers);
 int cbgx_h2x_stack_forward_train(const float *packed, int num_layers, const float *x, const float *h,
                                  const int32_t *graph_ptr, const uint8_t *lig_flag, const uint8_t *gen_flag,
@@ -345,6 +363,10 @@ int cbgx_h2x_stack_backward(const float *packed, int num_layers, const void *tap
                             const uint8_t *lig_flag, const uint8_t *gen_flag, int n_nodes, const float *grad_x_out,
                             float *const *grads, int num_grads, float *grad_h, void *workspace,
                             size_t workspace_bytes, void *stream);
+int cbgx_h2x_stack_backward_ex(const float *packed, int num_layers, const void *tape, size_t tape_bytes, const float *h,
+                               const uint8_t *lig_flag, const uint8_t *gen_flag, int n_nodes, const float *grad_x_out,
+                               float *const *grads, int num_grads, float *grad_h, float *grad_x_in, void *workspace,
+                               size_t workspace_bytes, void *stream);
 
 /* TargetDiff's training arithmetic around the denoiser call (targetdiff.py:82-124), one launch each instead of the ~260 small
  * launches the same formulas take as tensor operations (a training step is bound by its launch count as much as by its kernels).
