@@ -399,7 +399,11 @@ class _ComposeEmbedFunction(torch.autograd.Function):
             _native.ptr(gh.to(torch.float32).contiguous()), _native.ptr(ext), N, Fd, A, C, _native.ptr(partial), groups,
             _native.ptr(out), _native.current_stream(dev)), "cbgx_embed_compose_backward")
         dw_pa, dw_res, u, dw_la, v = out.split([128 * Fd, 128 * A, 128, 128 * C, 128])
-        return (gx_rec, gx_lig) + (None,) * 6 + (dw_pa.view(128, Fd), u, dw_res.view(128, A), u, dw_la.view(128, C), v, v.view(128, 1),
+        # every parameter gets gradient memory of its own: with `.grad` unset, AccumulateGrad adopts the returned tensor as it is, so a
+        # tensor returned for two parameters would leave them one shared `.grad` (clip_grad_norm_ would scale it twice, a second backward
+        # would add into it twice)
+        u2, v2 = torch.stack([u, v]).unbind(0)
+        return (gx_rec, gx_lig) + (None,) * 6 + (dw_pa.view(128, Fd), u, dw_res.view(128, A), u2, dw_la.view(128, C), v, v2.view(128, 1),
                                                  u + v)
 
 

@@ -57,6 +57,19 @@ def small_batch(sizes, seed, num_classes=13, ctx=None):
     return S.make_batch(pockets, [nl for _, nl in sizes], rng, num_classes, n_ctx_list=ctx)
 
 
+def sidechain_order(batch, seed):
+    """Sidechain-style context mask: the ligand rows of every graph in a seeded random order, so that context and generated
+    atoms interleave instead of the context forming a prefix.  Position, type and ``ligand_gen_flag`` move together; the graph
+    ids stay sorted."""
+    rng = np.random.default_rng(seed)
+    bl = batch["ligand_element_batch"].numpy()
+    perm = np.concatenate([rng.permutation(np.flatnonzero(bl == g)) for g in range(int(bl.max()) + 1)])
+    out = dict(batch)
+    for k in ("ligand_pos", "ligand_atom_type", "ligand_gen_flag"):
+        out[k] = batch[k][torch.from_numpy(perm)]
+    return out
+
+
 def _denoiser_case(model, name, batch):
     c_lig = F.one_hot(batch["ligand_atom_type"], model.num_classes).float()
     ctx, batch_idx = compose_inputs(model, batch, batch["ligand_pos"], c_lig)
@@ -317,9 +330,10 @@ def diffsbdd_case(name, *a, **k):
         _diffsbdd_case(name, *a, **k)
 
 
-def diffbp_train_case(name, batch, seed):
+def diffbp_train_case(name, batch, seed, t_override=None):
     """DiffBP training step of the unmodified reference (diffbp.py:154-231; loss weights all 1,
-    configs/denovo/train/diffbp.yml:37-41): the four losses and the gradient of every trainable tensor."""
+    configs/denovo/train/diffbp.yml:37-41): the four losses and the gradient of every trainable tensor.  With
+    ``t_override`` the reference's ``get_loss`` runs at that time vector and no time is drawn."""
     if not _selected(name):
         return
     M = ref_shim.load_reference()
@@ -338,11 +352,21 @@ def diffbp_train_case(name, batch, seed):
     bl = batch["ligand_element_batch"]
     B = int(bl.max()) + 1
     torch.manual_seed(seed)
-    loss_dict, _ = model(batch)
+    if t_override is None:
+        loss_dict, _ = model(batch)
+    else:
+        lig_flag, rec_flag = batch["ligand_lig_flag"], batch["protein_lig_flag"]
+        loss_dict, _ = model.get_loss(batch["ligand_pos"], batch["protein_pos"], batch["ligand_atom_type"],
+                                      batch["protein_atom_feature"], batch["protein_aa_type"], lig_flag, rec_flag, bl,
+                                      batch["protein_element_batch"], batch.get("ligand_gen_flag", lig_flag),
+                                      torch.zeros_like(rec_flag), t_override)
     sum(loss_dict.values()).backward()
     torch.manual_seed(seed)
-    draws = torch.randint(0, T, size=(B // 2 + 1,))
-    t = torch.cat([draws, T - draws - 1], 0)[:B]
+    if t_override is None:
+        draws = torch.randint(0, T, size=(B // 2 + 1,))
+        t = torch.cat([draws, T - draws - 1], 0)[:B]
+    else:
+        t = t_override
     eps = torch.randn_like(batch["ligand_pos"])
     u = torch.rand(batch["ligand_pos"].shape[0])
     out = {"seed": seed, "t": _np(t), "eps": _np(eps), "u": _np(u)}
@@ -604,6 +628,22 @@ def main():
     b["ligand_atom_type"] = torch.zeros_like(b["ligand_atom_type"])        # absorbing-state prior (assign_atomtype: absorbing)
     diffbp_case("diffbp_sample_T5", b, T=5, seed=13)
     diffsbdd_case("diffsbdd_sample_T5", small_batch([(42, 9), (38, 7)], seed=41, num_classes=8), T=5, seed=11)
+
+    # context tasks (linker / frag / scaffold / sidechain configs): fixed context atoms next to generated ones.  "_ctx" cases
+    # with sidechain_order interleave the two kinds; the others keep make_batch's context prefix (linker-style).
+    b = sidechain_order(small_batch([(44, 12), (37, 10)], seed=52, ctx=[5, 4]), seed=1)
+    b["ligand_atom_type"] = torch.where(b["ligand_gen_flag"], torch.zeros_like(b["ligand_atom_type"]), b["ligand_atom_type"])
+    diffbp_case("diffbp_sample_T5_ctx", b, T=5, seed=14)
+    diffsbdd_case("diffsbdd_sample_T5_ctx", small_batch([(42, 11), (38, 9)], seed=42, num_classes=8, ctx=[5, 3]), T=5, seed=12)
+    diffbp_train_case("train_loss_diffbp_ctx", sidechain_order(small_batch([(64, 14), (50, 12), (57, 9)], seed=73, ctx=[6, 5, 0]),
+                                                               seed=2), seed=21)
+    # the last graph at t = 0: no type-masked atom there, so the per-graph loss tables end below B
+    diffbp_train_case("train_loss_diffbp_ctx_t0", small_batch([(58, 13), (44, 11), (50, 10)], seed=74, ctx=[5, 4, 3]), seed=22,
+                      t_override=torch.tensor([650, 300, 0]))
+    # a context graph at t = 0: zero_time_loss masks with gen & (t == 0)
+    diffsbdd_train_case("train_loss_diffsbdd_ctx", sidechain_order(small_batch([(58, 12), (44, 10), (50, 9)], seed=75, num_classes=8,
+                                                                               ctx=[5, 0, 4]), seed=3),
+                        seed=23, t_override=torch.tensor([0.0, 640.0, 300.0]))
 
 
 if __name__ == "__main__":

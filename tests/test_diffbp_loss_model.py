@@ -113,3 +113,67 @@ def test_fused_diffbp_loss_formulas_match_autograd_on_the_tensor_path(seed, empt
     for got, ref, name in ((gx, xo.grad, "x_out"), (gs, x_stack.grad, "x_stack"), (gl, logits.grad, "logits")):
         assert float(ref[~lig_flag].abs().max()) == 0.0 and float(got[~lig_flag].abs().max()) == 0.0, name
         assert torch.allclose(got, ref, rtol=2e-4, atol=2e-7), (name, float((got - ref).abs().max()), float(ref.abs().max()))
+
+
+@pytest.mark.parametrize("case", ["train_loss_diffbp", "train_loss_diffbp_ctx", "train_loss_diffbp_ctx_t0"])
+def test_fused_diffbp_loss_formulas_on_the_reference_goldens(golden_dir, case):
+    """the same formulas on the batches, times and draws the reference recorded -- context atoms (prefix and interleaved), a graph
+    without context and a last graph at t = 0 with no type-masked atom (the two loss denominators end below B) -- against autograd
+    on the tensor path of DiffBP.get_loss and against the reference's four losses"""
+    from oracle import diffbp as OD
+    from oracle import unitransformer as OU
+    from oracle import weights as W
+    from tests.test_host_models_cpu import OracleDenoiser, golden_batch, load
+    g = load(golden_dir, case)
+    batch, t = golden_batch(g), g["t"]
+    sd = W.synthetic_state_dict_diffbp(13, 9, seed=0, num_timesteps=1000)
+    m = C.get_model(C.default_diffbp_config(13))
+    m.load_state_dict(sd, strict=True)
+    m.train()
+    inner, seen = OracleDenoiser(sd), {}
+    B = int(t.shape[0])
+
+    class SpyDenoiser(torch.nn.Module):        # what the tensor path feeds the denoiser and gets back, outputs as leaves
+        def forward(self, **kw):
+            with torch.no_grad():
+                xo, ho, logits = inner(**kw)
+            seen.update(x=kw["x"].detach(), xo=xo.requires_grad_(True), logits=logits.requires_grad_(True))
+            return seen["xo"], ho, seen["logits"]
+
+    class SpyComHead(torch.nn.Module):         # CoMPredictor.forward on the oracle with the stack's output x_stack as a leaf
+        def forward(self, x_lig_pred, bl, x, h, gen_flag, lig_flag, batch_idx, graph_ptr=None, lig_rows=None, **_):
+            with torch.no_grad():
+                x, h = x.detach(), h.detach()
+                ei = OU.knn_graph(x, batch_idx, 32)
+                et = OU.build_edge_type(ei, lig_flag)
+                e_w = OU.edge_gate(sd, "com_head", x, ei)
+                xs = x.clone()
+                for layer in range(3):
+                    xs = xs + OU.h2x_attention(sd, f"com_head.h2xattentions.{layer}", xs, h, et, ei, e_w) * gen_flag[:, None].float()
+            seen["x_stack"] = xs.requires_grad_(True)
+            noise = x_lig_pred - x[lig_flag]
+            noise = noise - OD.scatter_mean(noise, bl, B)[bl]
+            return noise, OD.scatter_mean((seen["x_stack"] - x)[lig_flag], bl, B)[bl]
+    m.denoiser, m.com_head = SpyDenoiser(), SpyComHead()
+    ld, _ = m(batch, t=t, noise=(g["eps"], g["u"]))
+    sum(ld.values()).backward()
+    x0, v0, gen_l = batch["ligand_pos"], batch["ligand_atom_type"], batch.get("ligand_gen_flag", batch["ligand_lig_flag"])
+    bl, br = batch["ligand_element_batch"], batch["protein_element_batch"]
+    ps = m.pos_scheduler
+    _, pos_noise, com_noise = ps.forward_add_noise(x0, t, bl, gen_l, noise=g["eps"], zero_center=True)
+    _, _, type_flag = m.type_scheduler.forward_add_noise(v0, t, bl, gen_l, uniform=g["u"])
+    sort_idx, _, lig_flag, _, graph_ptr = TargetDiff.compose_plan(bl, br, B)
+    with torch.no_grad():
+        losses, scal, a_pos, a_int, b_com, b_int, z_atom = kernel_model(
+            seen["xo"].detach(), seen["x"], seen["x_stack"].detach(), seen["logits"].detach(), sort_idx, graph_ptr, pos_noise, com_noise,
+            v0, type_flag, gen_l, t, br.shape[0], ps.alphas_cumprod.float(), ps.betas.float())
+    if "ligand_gen_flag" in batch:
+        assert bool((~gen_l).any()) and bool((type_flag <= gen_l).all())
+    for k, key in enumerate(("pos", "atom", "com", "inter")):
+        ref = float(ld[key].detach())
+        assert abs(float(losses[k]) - ref) <= 2e-5 * abs(ref) + 1e-7, (key, float(losses[k]), ref)
+        assert abs(float(losses[k]) - g["loss_" + key]) <= 2e-5 * abs(g["loss_" + key]) + 1e-7, (key, float(losses[k]), g["loss_" + key])
+    gx, gs, gl = scal[0] * a_pos + a_int, scal[0] * b_com + b_int, scal[1] * z_atom
+    for got, ref, name in ((gx, seen["xo"].grad, "x_out"), (gs, seen["x_stack"].grad, "x_stack"), (gl, seen["logits"].grad, "logits")):
+        assert float(ref[~lig_flag].abs().max()) == 0.0 and float(got[~lig_flag].abs().max()) == 0.0, name
+        assert torch.allclose(got, ref, rtol=2e-4, atol=2e-7), (name, float((got - ref).abs().max()), float(ref.abs().max()))

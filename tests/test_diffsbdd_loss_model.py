@@ -66,7 +66,7 @@ def kernel_model(model, batch, t_int, eps_x, eps_c, xo, logits):
     return x_t, xr_t, c_t, gl[:, 0].sum() / B, gl[:, 1].sum() / B, gpos, gz      # diffsbdd_finish_kernel: mean over the graphs
 
 
-@pytest.mark.parametrize("case", ["train_loss_diffsbdd", "train_loss_diffsbdd_t0"])
+@pytest.mark.parametrize("case", ["train_loss_diffsbdd", "train_loss_diffsbdd_t0", "train_loss_diffsbdd_ctx"])
 def test_fused_diffsbdd_arithmetic_equals_the_tensor_path(golden_dir, case):
     g = load(golden_dir, case)
     sd = W.synthetic_state_dict_diffsbdd(8, 9, seed=0, num_timesteps=1000)

@@ -173,15 +173,16 @@ def _bp_model(T):
     return m.to(DEV), sd
 
 
-def test_diffbp_training_gradients_at_config5_shape():
+def test_diffbp_training_gradients_at_config5_shape(maker=synthetic.denovo_batch):
     """DiffBP (denoiser + CoMPredictor's H2X stack on its own graph + score / mask-type / COM / interior losses, diffbp.py:154-231)
     at 32 real-size graphs: all 404 parameter gradients of `model(batch); sum(losses).backward()` against autograd on the oracle.
-    pos / atom / com are means over graphs of per-graph means, the interior loss a mean over the ligand atoms of the batch, so
-    the oracle runs on 8 sub-batches of 4 graphs with the matching weights.  Tolerance 2e-4 per tensor (ReLU-flip criterion in
+    pos / atom / com are means of per-graph means over the graphs up to the last one with a generated (pos, com) or type-masked
+    (atom) atom, the interior loss a mean over the ligand atoms of the batch, so the oracle runs on 8 sub-batches of 4 graphs with
+    the matching weights: a sub-batch's own count of such graphs over the batch's.  Tolerance 2e-4 per tensor (ReLU-flip criterion in
     compare_gradients_at_config_size); the four loss values to 1e-4 relative."""
     _oracle_threads()
     B = 32
-    batch = synthetic.denovo_batch(B, seed=405)
+    batch = maker(B, seed=405)
     n_lig = batch["ligand_pos"].shape[0]
     g = torch.Generator().manual_seed(8)
     draws = torch.randint(0, 1000, (B // 2 + 1,), generator=g)
@@ -194,13 +195,24 @@ def test_diffbp_training_gradients_at_config5_shape():
     dbatch = synthetic.batch_to(batch, DEV)
     dbatch["num_graphs"] = B
     dbatch["max_ligand_atoms"] = int(torch.bincount(batch["ligand_element_batch"]).max())
-    ld, _ = m(dbatch, t=t.to(DEV), noise=(eps.to(DEV), u.to(DEV)))
+    bl = batch["ligand_element_batch"]
+    gen_l = batch.get("ligand_gen_flag", torch.ones(n_lig, dtype=torch.bool))
+    type_flag = OB.mask_forward_add_noise(1000, 13, batch["ligand_atom_type"], t, bl, gen_l, u)[2]
+
+    def extent(flag, g0, g1):       # graphs g0 .. the last one in [g0, g1) with a flagged atom: what the per-graph means divide by
+        ids = bl[flag & (bl >= g0) & (bl < g1)]
+        return float(ids.max() - g0 + 1) if ids.numel() else 0.0
+    ld, res = m(dbatch, t=t.to(DEV), noise=(eps.to(DEV), u.to(DEV)))
+    assert ("fused_bad" in res) == (dbatch["max_ligand_atoms"] <= 48)       # over 48 ligand atoms: the tensor path
+    if "fused_bad" in res:
+        assert int(res["fused_bad"]) == 0
     sum(ld.values()).backward()
     torch.cuda.synchronize()
 
     def run(g0, g1, _):
         sb, ml = sub_batch(batch, g0, g1)
-        w = {"pos": 4.0 / B, "atom": 4.0 / B, "com": 4.0 / B, "inter": float(ml.sum()) / n_lig}
+        wg, wt = extent(gen_l, g0, g1) / extent(gen_l, 0, B), extent(type_flag, g0, g1) / extent(type_flag, 0, B)
+        w = {"pos": wg, "atom": wt, "com": wg, "inter": float(ml.sum()) / n_lig}
         ls, grads = OB.loss_and_grads(sd, sb, t[g0:g1], eps[ml], u[ml], 13, 1000, weights=w)
         return ls, w, grads
 
@@ -211,12 +223,17 @@ def test_diffbp_training_gradients_at_config5_shape():
     compare_gradients_at_config_size(m, oracle, 8 + 6 + 9 * 36 + 4 + (6 + 3 * 18))
 
 
-def test_diffsbdd_training_gradients_at_config5_shape():
+def test_diffbp_training_gradients_at_config5_shape_linker():
+    """the same with linker-style batches (synthetic.linker_batch: 10 - 35 fixed context atoms + 3 - 14 generated ones per graph)"""
+    test_diffbp_training_gradients_at_config5_shape(synthetic.linker_batch)
+
+
+def test_diffsbdd_training_gradients_at_config5_shape(maker=synthetic.denovo_batch):
     """DiffSBDD's training-mode variational loss (diffsbdd.py:91-195; per-graph terms, mean over graphs) at 32 real-size graphs,
     one of them at t = 0 (reconstruction branch): all 342 parameter gradients against autograd on the oracle, 2e-4 per tensor."""
     _oracle_threads()
     B = 32
-    batch = synthetic.denovo_batch(B, seed=406, num_classes=8)
+    batch = maker(B, seed=406, num_classes=8)
     n_lig = batch["ligand_pos"].shape[0]
     g = torch.Generator().manual_seed(9)
     t = torch.randint(0, 1001, (B,), generator=g).float()
@@ -245,11 +262,15 @@ def test_diffsbdd_training_gradients_at_config5_shape():
     compare_gradients_at_config_size(m, oracle, 8 + 6 + 9 * 36 + 4)
 
 
-def test_diffbp_static_context_cache_is_exact():
+def test_diffsbdd_training_gradients_at_config5_shape_linker():
+    test_diffsbdd_training_gradients_at_config5_shape(synthetic.linker_batch)
+
+
+def test_diffbp_static_context_cache_is_exact(maker=synthetic.denovo_batch):
     """DiffBP.begin_sampling keeps the denoiser's static-context cache (the pocket never moves, diffbp.py:262-297): three
     steps on real-size pockets with and without it, identical bits although DiffBP also consumes the denoiser's h'"""
     m, _ = _bp_model(1000)
-    batch = synthetic.batch_to(synthetic.denovo_batch(3, seed=31), DEV)
+    batch = synthetic.batch_to(maker(3, seed=31), DEV)
     n_lig = batch["ligand_pos"].shape[0]
     g = torch.Generator(device=DEV).manual_seed(5)
     noise = [(torch.randn(n_lig, 3, device=DEV, generator=g), torch.rand(n_lig, device=DEV, generator=g)) for _ in range(3)]
@@ -263,8 +284,12 @@ def test_diffbp_static_context_cache_is_exact():
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
 
 
+def test_diffbp_static_context_cache_is_exact_linker():
+    test_diffbp_static_context_cache_is_exact(synthetic.linker_batch)
+
+
 @pytest.mark.parametrize("name", ["diffbp", "diffsbdd"])
-def test_native_step_kernels_match_the_torch_step(name):
+def test_native_step_kernels_match_the_torch_step(name, maker=synthetic.denovo_batch):
     """cbgx_diffbp_epilogue / cbgx_diffsbdd_step (one launch around the network calls) against the same step written with
     torch ops on the device (the restatement of diffbp.py:262-297 / diffsbdd.py:296-304 that the oracle tests pin): three
     steps on real-size pockets with shared noise; positions within 2e-6 absolute (per-graph means are summed in a different
@@ -276,7 +301,7 @@ def test_native_step_kernels_match_the_torch_step(name):
         m.load_state_dict(W.synthetic_state_dict_diffsbdd(8, 9, seed=0, num_timesteps=1000), strict=True)
         m = m.to(DEV)
     Cn = m.num_classes
-    batch = synthetic.batch_to(synthetic.denovo_batch(4, seed=52, num_classes=Cn), DEV)
+    batch = synthetic.batch_to(maker(4, seed=52, num_classes=Cn), DEV)
     n_lig = batch["ligand_pos"].shape[0]
     g = torch.Generator(device=DEV).manual_seed(9)
     if name == "diffbp":
@@ -307,6 +332,15 @@ def test_native_step_kernels_match_the_torch_step(name):
         assert torch.equal(ca, cb)
     else:
         assert float((ca - cb).abs().max()) <= 2e-6 * max(1.0, float(cb.abs().max()))
+    if "ligand_gen_flag" in batch and name == "diffbp":     # DiffBP's context rows never move, on either side
+        ctx = ~batch["ligand_gen_flag"]
+        assert torch.equal(xa[ctx], batch["ligand_pos"][ctx]) and torch.equal(xb[ctx], batch["ligand_pos"][ctx])
+
+
+@pytest.mark.parametrize("name", ["diffbp", "diffsbdd"])
+def test_native_step_kernels_match_the_torch_step_linker(name):
+    """linker-style batches: context atoms next to the generated ones (the gen gating of both step kernels)"""
+    test_native_step_kernels_match_the_torch_step(name, synthetic.linker_batch)
 
 
 def test_diffbp_sampler_on_real_size_pockets():
@@ -456,7 +490,7 @@ def test_targetdiff_rollout_200_steps_real_pocket(synthetic_sd):
     assert len(resyncs) <= 2, resyncs
 
 
-def test_diffsbdd_pocket_frame_equals_moving_pocket():
+def test_diffsbdd_pocket_frame_equals_moving_pocket(maker=synthetic.denovo_batch):
     """DiffSBDD with the composed coordinates kept in the pocket's own frame (static-context cache on, the default of the native
     step: cbgx_diffsbdd_step frame_shift) against the same native step with the pocket translated in place every step
     (static_cache=False; diffsbdd.py:296-304 literally), shared Gaussian draws, real-size pockets.
@@ -473,7 +507,7 @@ def test_diffsbdd_pocket_frame_equals_moving_pocket():
     m = C.get_model(C.default_diffsbdd_config(Cn)).eval()
     m.load_state_dict(W.synthetic_state_dict_diffsbdd(Cn, 9, seed=0, num_timesteps=1000), strict=True)
     m = m.to(DEV)
-    batch = synthetic.batch_to(synthetic.denovo_batch(4, seed=53, num_classes=Cn), DEV)
+    batch = synthetic.batch_to(maker(4, seed=53, num_classes=Cn), DEV)
     n_lig = batch["ligand_pos"].shape[0]
     g = torch.Generator(device=DEV).manual_seed(10)
     steps = list(range(999, 993, -1)) + list(range(5, -1, -1))
@@ -512,3 +546,7 @@ def test_diffsbdd_pocket_frame_equals_moving_pocket():
     assert tight >= 8
     # the pocket has really moved (the frame carries it) while its rows in the composed x never changed
     assert float((m.pocket_positions(sa) - p0).abs().max()) > 1e-3 and torch.equal(sa["x"][sa["rec_rows"]], p0)
+
+
+def test_diffsbdd_pocket_frame_equals_moving_pocket_linker():
+    test_diffsbdd_pocket_frame_equals_moving_pocket(synthetic.linker_batch)

@@ -408,9 +408,9 @@ def test_native_step_kernels(golden_dir, model, case):
         assert torch.equal(st["x_lig"].cpu()[keep], batch["ligand_pos"][keep])
 
 
-def test_diffsbdd_sample_matches_reference(golden_dir):
+def test_diffsbdd_sample_matches_reference(golden_dir, case="diffsbdd_sample_T5"):
     """DiffSBDD.sample (5-step model) on the GPU with the reference's Gaussian draws replayed."""
-    g = load(golden_dir, "diffsbdd_sample_T5")
+    g = load(golden_dir, case)
     T, Cn = int(g["T"]), 8
     m = C.get_model(C.default_diffsbdd_config(Cn, num_diffusion_timesteps=T)).eval()
     m.load_state_dict(W.synthetic_state_dict_diffsbdd(Cn, 9, seed=0, num_timesteps=T), strict=True)
@@ -428,9 +428,15 @@ def test_diffsbdd_sample_matches_reference(golden_dir):
         close(traj[t][1], g[f"traj_c_{t}"], f"diffsbdd traj c[{t}]", scale=10.0)
 
 
-def test_diffbp_sample_matches_reference(golden_dir):
+def test_diffsbdd_sample_with_context_atoms_matches_reference(golden_dir):
+    """context atoms in both graphs: the whole trajectory within the same tolerance, context rows included (the reference's
+    DiffSBDD.sample moves them; only the denoiser's H2X update is gated)"""
+    test_diffsbdd_sample_matches_reference(golden_dir, "diffsbdd_sample_T5_ctx")
+
+
+def test_diffbp_sample_matches_reference(golden_dir, case="diffbp_sample_T5"):
     """DiffBP.sample (5-step model): denoiser + CoMPredictor (cbgx_h2x_stack_forward) + samplers, noise replayed."""
-    g = load(golden_dir, "diffbp_sample_T5")
+    g = load(golden_dir, case)
     T, Cn = int(g["T"]), 13
     m = C.get_model(C.default_diffbp_config(Cn, num_diffusion_timesteps=T)).eval()
     m.load_state_dict(W.synthetic_state_dict_diffbp(Cn, 9, seed=0, num_timesteps=T), strict=True)
@@ -446,6 +452,15 @@ def test_diffbp_sample_matches_reference(golden_dir):
     for t in range(-1, T):
         close(traj[t][0], g[f"traj_x_{t}"], f"diffbp traj x[{t}]")
         assert torch.equal(traj[t][1], g[f"traj_c_{t}"]), f"diffbp traj c[{t}]"
+        if "ligand_gen_flag" in batch:
+            ctx = ~batch["ligand_gen_flag"]
+            assert torch.equal(traj[t][0].cpu()[ctx], batch["ligand_pos"][ctx]), f"diffbp context rows x[{t}]"
+
+
+def test_diffbp_sample_with_context_atoms_matches_reference(golden_dir):
+    """sidechain-style context atoms (interleaved with the generated ones): identical atom types at every step, the context rows
+    equal to the input bit for bit at every step (cbgx_diffbp_epilogue and the CoM head gate them)"""
+    test_diffbp_sample_matches_reference(golden_dir, "diffbp_sample_T5_ctx")
 
 
 @pytest.mark.parametrize("maker,n", [(synthetic.denovo_batch, 6), (synthetic.linker_batch, 5)])

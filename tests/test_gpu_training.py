@@ -455,16 +455,23 @@ def test_direct_gradient_write_equals_autograd_accumulation(synthetic_sd):
     assert torch.allclose(grads[0], grads[1], rtol=1e-4, atol=1e-6 * float(grads[0].abs().max()))
 
 
-def test_diffbp_training_step_matches_reference_gradients(golden_dir):
+def test_diffbp_training_step_matches_reference_gradients(golden_dir, case="train_loss_diffbp", fused=False):
     """DiffBP: denoiser + CoMPredictor (H2X stack with its own graph) + score / mask-type / COM / interior losses;
-    losses and the gradients of all 404 tensors against the unmodified reference's ``model(batch); loss.backward()``"""
+    losses and the gradients of all 404 tensors against the unmodified reference's ``model(batch); loss.backward()``.
+    ``fused``: the collate's `max_ligand_atoms` is recorded, so the fused losses (cbgx_diffbp_loss) run instead of the tensor path."""
     from oracle import weights as W
-    g = load(golden_dir, "train_loss_diffbp")
+    g = load(golden_dir, case)
     m = C.get_model(C.default_diffbp_config(13))
     m.load_state_dict(W.synthetic_state_dict_diffbp(13, 9, seed=0, num_timesteps=1000), strict=True)
     m = m.to(DEV).train()
     batch = golden_batch(g, DEV)
-    ld, _ = m(batch, t=g["t"].to(DEV), noise=(g["eps"].to(DEV), g["u"].to(DEV)))
+    if fused:
+        batch["max_ligand_atoms"] = int(torch.bincount(batch["ligand_element_batch"]).max())
+        assert batch["max_ligand_atoms"] <= 48
+    ld, res = m(batch, t=g["t"].to(DEV), noise=(g["eps"].to(DEV), g["u"].to(DEV)))
+    assert ("fused_bad" in res) == fused
+    if fused:
+        assert int(res["fused_bad"]) == 0
     for k in ("pos", "atom", "com", "inter"):
         assert abs(float(ld[k].detach()) - g["loss_" + k]) <= 2e-4 * abs(g["loss_" + k]) + 1e-6, (k, float(ld[k].detach()), g["loss_" + k])
     sum(ld.values()).backward()
@@ -479,12 +486,20 @@ def test_diffbp_training_step_matches_reference_gradients(golden_dir):
     check_golden_gradients(m, g, 8 + 6 + 9 * 36 + 4 + (6 + 3 * 18), oracle_run)
 
 
-def test_diffbp_fused_losses_match_the_tensor_path(golden_dir):
+@pytest.mark.parametrize("fused", [False, True], ids=["tensor", "fused"])
+@pytest.mark.parametrize("case", ["train_loss_diffbp_ctx", "train_loss_diffbp_ctx_t0"])
+def test_diffbp_training_step_with_context_atoms_matches_reference_gradients(golden_dir, case, fused):
+    """context atoms (interleaved, and a graph without any; prefix, with the last graph at t = 0 and no type-masked atom), on the
+    tensor path and through the fused losses"""
+    test_diffbp_training_step_matches_reference_gradients(golden_dir, case, fused)
+
+
+def test_diffbp_fused_losses_match_the_tensor_path(golden_dir, case="train_loss_diffbp"):
     """Round 6: DiffBP's arithmetic between the two network calls and its four losses as two launches (cbgx_diffbp_loss,
     csrc/train_loss_diffbp.hip; taken when the collate records `max_ligand_atoms` <= 48) against the tensor path that the golden
     test above pins to the reference: the four losses, and every parameter gradient of the summed loss."""
     from oracle import weights as W
-    g = load(golden_dir, "train_loss_diffbp")
+    g = load(golden_dir, case)
     sd = W.synthetic_state_dict_diffbp(13, 9, seed=0, num_timesteps=1000)
     out = {}
     for fused in (False, True):
@@ -513,6 +528,11 @@ def test_diffbp_fused_losses_match_the_tensor_path(golden_dir):
             continue
         d = float((out[True][1][k] - ref).norm()) / rn
         assert d <= 2e-4, (k, d)
+
+
+@pytest.mark.parametrize("case", ["train_loss_diffbp_ctx", "train_loss_diffbp_ctx_t0"])
+def test_diffbp_fused_losses_with_context_atoms_match_the_tensor_path(golden_dir, case):
+    test_diffbp_fused_losses_match_the_tensor_path(golden_dir, case)
 
 
 @contextlib.contextmanager
@@ -653,7 +673,68 @@ def test_fused_embedder_gives_the_model_the_same_gradients(golden_dir, synthetic
     assert len(mlps) <= 2 and all(d <= 5e-3 for d in over.values()) and all(".net." in k for k in over), over
 
 
-@pytest.mark.parametrize("case", ["train_loss_diffsbdd", "train_loss_diffsbdd_t0"])
+def overlapping_gradients(m):
+    """pairs of parameters whose `.grad` tensors share memory (disjoint views of one buffer, as the backward kernels hand out, are fine)"""
+    spans = sorted((p.grad.data_ptr(), p.grad.data_ptr() + p.grad.numel() * p.grad.element_size(), k)
+                   for k, p in m.named_parameters() if p.grad is not None and p.grad.numel() > 0)
+    assert all(p.grad is None or p.grad.is_contiguous() for p in m.parameters())
+    return [(a[2], b[2]) for a, b in zip(spans, spans[1:]) if b[0] < a[1]]
+
+
+@pytest.mark.parametrize("name", ["targetdiff", "diffbp", "diffsbdd"])
+def test_grad_storage_of_the_fused_embedder_under_clipping_and_accumulation(golden_dir, synthetic_sd, name):
+    """gradients as an optimizer consumes them, the reference's train.py loop without this project's FlatGradients: `.grad` set to
+    None, backward, clip_grad_norm_ below the actual norm, a second backward without zeroing (gradient accumulation).  Fused embedder
+    (CBGX_FUSED_EMBED=1) and tensor path must end with the same `.grad` on every parameter, and no two parameters may share gradient
+    memory -- AccumulateGrad adopts a returned tensor as the parameter's `.grad`, so a tensor returned for two parameters is clipped
+    and accumulated twice."""
+    from oracle import weights as W
+    if name == "targetdiff":
+        g, sd, cfg = load(golden_dir, "train_loss_denovo"), synthetic_sd, C.default_targetdiff_config(13)
+        noise = lambda: (g["eps"].to(DEV), g["u"].to(DEV))
+    elif name == "diffbp":
+        g, cfg = load(golden_dir, "train_loss_diffbp_ctx"), C.default_diffbp_config(13)
+        sd = W.synthetic_state_dict_diffbp(13, 9, seed=0, num_timesteps=1000)
+        noise = lambda: (g["eps"].to(DEV), g["u"].to(DEV))
+    else:
+        g, cfg = load(golden_dir, "train_loss_diffsbdd_ctx"), C.default_diffsbdd_config(8)
+        sd = W.synthetic_state_dict_diffsbdd(8, 9, seed=0, num_timesteps=1000)
+        noise = lambda: (g["eps_x"].to(DEV), g["eps_c"].to(DEV))
+    out, max_norm = {}, None
+    for fused in (False, True):
+        m = C.get_model(cfg)
+        m.load_state_dict(sd, strict=True)
+        m = m.to(DEV).train()
+        m.zero_grad(set_to_none=True)
+        with fused_embed(fused):
+            ld, _ = m(golden_batch(g, DEV), t=g["t"].to(DEV), noise=noise())
+            sum(ld.values()).backward()
+            norm = float(torch.nn.utils.clip_grad_norm_(m.parameters(), float("inf")))
+            max_norm = 0.3 * norm if max_norm is None else max_norm
+            assert norm > max_norm
+            torch.nn.utils.clip_grad_norm_(m.parameters(), max_norm)
+            ld, _ = m(golden_batch(g, DEV), t=g["t"].to(DEV), noise=noise())
+            sum(ld.values()).backward()
+        torch.cuda.synchronize()
+        assert overlapping_gradients(m) == [], (fused, overlapping_gradients(m))
+        out[fused] = {k: p.grad.detach().clone() for k, p in m.named_parameters() if p.grad is not None}
+    assert out[True].keys() == out[False].keys()
+    assert sum(k.startswith("context_embedder.") for k in out[True]) == 8
+    over = {}
+    for k, ref in out[False].items():
+        rn = float(ref.norm())
+        if rn < 1e-7:
+            continue
+        d = float((out[True][k] - ref).norm()) / rn
+        if d > 2e-4:
+            over[k] = d
+    # (as in test_fused_embedder_gives_the_model_the_same_gradients: the two sides' embeddings differ in the last bit, which may flip a
+    # ReLU within that bit of zero inside at most two MLPs; the embedder's own tensors are held to 2e-4)
+    mlps = {k.split(".net.")[0] for k in over}
+    assert len(mlps) <= 2 and all(d <= 5e-3 for d in over.values()) and all(".net." in k for k in over), over
+
+
+@pytest.mark.parametrize("case", ["train_loss_diffsbdd", "train_loss_diffsbdd_t0", "train_loss_diffsbdd_ctx"])
 def test_diffsbdd_training_step_matches_reference_gradients(golden_dir, case):
     """DiffSBDD: variational training loss around the shared denoiser (diffsbdd.py:91-195) against the reference's losses and
     gradients, incl. the t = 0 reconstruction branch"""
@@ -678,7 +759,7 @@ def test_diffsbdd_training_step_matches_reference_gradients(golden_dir, case):
     check_golden_gradients(m, g, 8 + 6 + 9 * 36 + 4, oracle_run)
 
 
-@pytest.mark.parametrize("case", ["train_loss_diffsbdd", "train_loss_diffsbdd_t0"])
+@pytest.mark.parametrize("case", ["train_loss_diffsbdd", "train_loss_diffsbdd_t0", "train_loss_diffsbdd_ctx"])
 def test_diffsbdd_fused_losses_match_the_tensor_path(golden_dir, case):
     """Round 6: DiffSBDD's noising, the network-independent loss terms and both losses as three launches (cbgx_diffsbdd_train_noise /
     cbgx_diffsbdd_loss, csrc/train_loss_diffsbdd.hip) against the tensor path that the golden test above pins to the reference: the

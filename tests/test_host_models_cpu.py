@@ -94,7 +94,7 @@ def test_targetdiff_eval_mode_averages_the_evaluation_times(synthetic_sd):
         assert torch.allclose(mean[k], torch.stack([p[k] for p in parts]).mean())
 
 
-@pytest.mark.parametrize("case", ["train_loss_diffsbdd", "train_loss_diffsbdd_t0"])
+@pytest.mark.parametrize("case", ["train_loss_diffsbdd", "train_loss_diffsbdd_t0", "train_loss_diffsbdd_ctx"])
 def test_diffsbdd_training_plumbing_matches_reference(golden_dir, case):
     g = load(golden_dir, case)
     sd = W.synthetic_state_dict_diffsbdd(8, 9, seed=0, num_timesteps=1000)
@@ -140,10 +140,10 @@ class OracleComHead(torch.nn.Module):
         return OD.com_head(sd, x_lig_pred, batch_idx_lig, x, h, gen_flag, lig_flag, batch_idx, B)
 
 
-def test_diffbp_training_plumbing_matches_reference(golden_dir):
+def test_diffbp_training_plumbing_matches_reference(golden_dir, case="train_loss_diffbp"):
     """zero-COM noising, absorbing-state type noising, the four losses (score, mask-type, COM shift, interior) of
     DiffBP.get_loss (diffbp.py:154-231) around stand-ins for the two libcbgx calls"""
-    g = load(golden_dir, "train_loss_diffbp")
+    g = load(golden_dir, case)
     sd = W.synthetic_state_dict_diffbp(13, 9, seed=0, num_timesteps=1000)
     m = C.get_model(C.default_diffbp_config(13))
     m.load_state_dict(sd, strict=True)
@@ -163,10 +163,15 @@ def test_diffbp_training_plumbing_matches_reference(golden_dir):
     assert abs(float(gd.double().norm()) - float(g["gnorm/" + k0])) <= 2e-5 * float(g["gnorm/" + k0])
 
 
-def test_diffsbdd_sampler_plumbing_matches_reference(golden_dir):
+@pytest.mark.parametrize("case", ["train_loss_diffbp_ctx", "train_loss_diffbp_ctx_t0"])
+def test_diffbp_training_plumbing_with_context_atoms(golden_dir, case):
+    test_diffbp_training_plumbing_matches_reference(golden_dir, case)
+
+
+def test_diffsbdd_sampler_plumbing_matches_reference(golden_dir, case="diffsbdd_sample_T5"):
     """DiffSBDD.sample (diffsbdd.py:240-319) of a 5-step model: the gamma-schedule ancestral sampler, COM projection and the
     final p(x, h | z_0) draw, bit for bit against the reference's trajectory with its Gaussian draws replayed"""
-    g = load(golden_dir, "diffsbdd_sample_T5")
+    g = load(golden_dir, case)
     T, Cn = int(g["T"]), 8
     sd = W.synthetic_state_dict_diffsbdd(Cn, 9, seed=0, num_timesteps=T)
     m = with_oracle_denoiser(C.get_model(C.default_diffsbdd_config(Cn, num_diffusion_timesteps=T)), sd).eval()
@@ -181,12 +186,19 @@ def test_diffsbdd_sampler_plumbing_matches_reference(golden_dir):
     for t in range(-1, T):
         torch.testing.assert_close(traj[t][0], g[f"traj_x_{t}"], rtol=1e-5, atol=1e-5)
         torch.testing.assert_close(traj[t][1], g[f"traj_c_{t}"], rtol=1e-5, atol=1e-5)
+    if "ligand_gen_flag" in batch:     # like the reference, the sampler moves the context rows too
+        ctx = ~batch["ligand_gen_flag"]
+        assert (traj[-1][0][ctx] - batch["ligand_pos"][ctx]).abs().max() > 1e-2
 
 
-def test_diffbp_sampler_plumbing_matches_reference(golden_dir):
+def test_diffsbdd_sampler_plumbing_with_context_atoms(golden_dir):
+    test_diffsbdd_sampler_plumbing_matches_reference(golden_dir, "diffsbdd_sample_T5_ctx")
+
+
+def test_diffbp_sampler_plumbing_matches_reference(golden_dir, case="diffbp_sample_T5"):
     """DiffBP.sample (diffbp.py:240-299) of a 5-step model: score-type position update with the COM shift, absorbing-state
     type sampler, the reference's noise tape replayed"""
-    g = load(golden_dir, "diffbp_sample_T5")
+    g = load(golden_dir, case)
     T, Cn = int(g["T"]), 13
     sd = W.synthetic_state_dict_diffbp(Cn, 9, seed=0, num_timesteps=T)
     m = C.get_model(C.default_diffbp_config(Cn, num_diffusion_timesteps=T))
@@ -203,6 +215,13 @@ def test_diffbp_sampler_plumbing_matches_reference(golden_dir):
     for t in range(-1, T):
         torch.testing.assert_close(traj[t][0], g[f"traj_x_{t}"], rtol=1e-5, atol=1e-5)
         assert torch.equal(traj[t][1], g[f"traj_c_{t}"]), t
+        if "ligand_gen_flag" in batch:     # context rows: the input, bit for bit, at every step
+            ctx = ~batch["ligand_gen_flag"]
+            assert torch.equal(traj[t][0][ctx], batch["ligand_pos"][ctx]), t
+
+
+def test_diffbp_sampler_plumbing_with_context_atoms(golden_dir):
+    test_diffbp_sampler_plumbing_matches_reference(golden_dir, "diffbp_sample_T5_ctx")
 
 
 def test_diffsbdd_ordered_graph_mean_equals_the_scatter_form():

@@ -93,11 +93,11 @@ def test_sample_loop_matches_reference(golden_dir):
     assert torch.equal(x, g["traj_x_-1"]) and torch.equal(c, g["traj_c_-1"])
 
 
-def test_diffsbdd_sample_matches_reference(golden_dir):
+def test_diffsbdd_sample_matches_reference(golden_dir, case="diffsbdd_sample_T5"):
     """oracle/diffsbdd.py replays the reference's full 5-step DiffSBDD.sample (draw order, COM projection, the
     translated pocket, the final p(x,h | z0) call) bit-exactly."""
     from oracle import diffsbdd as D
-    g = load(golden_dir, "diffsbdd_sample_T5")
+    g = load(golden_dir, case)
     Tn, C = int(g["T"]), 8
     sd = W.synthetic_state_dict_diffsbdd(C, 9, seed=0, num_timesteps=Tn)
     assert torch.equal(sd["pos_scheduler.gamma.gamma"], g["gamma"])
@@ -111,6 +111,20 @@ def test_diffsbdd_sample_matches_reference(golden_dir):
     for t in range(-1, Tn):
         assert torch.equal(traj[t][0], g[f"traj_x_{t}"]), t
         assert torch.equal(traj[t][1], g[f"traj_c_{t}"]), t
+    if "ligand_gen_flag" in batch:
+        # the reference's DiffSBDD.sample never reads gen_flag: its context rows move, and not only by a shift of each graph
+        ctx = ~batch["ligand_gen_flag"]
+        x0, x1 = batch["ligand_pos"][ctx], g["traj_x_-1"][ctx]
+        bl = batch["ligand_element_batch"][ctx]
+        assert not torch.equal(x0, x1)
+        for b in bl.unique():
+            d0, d1 = torch.cdist(x0[bl == b], x0[bl == b]), torch.cdist(x1[bl == b], x1[bl == b])
+            assert (d0 - d1).abs().max() > 1e-2, int(b)
+
+
+def test_diffsbdd_sample_with_context_atoms_matches_reference(golden_dir):
+    """context atoms (linker-style prefix) in both graphs: the same replay, and the reference moves the context rows"""
+    test_diffsbdd_sample_matches_reference(golden_dir, "diffsbdd_sample_T5_ctx")
 
 
 def test_diffsbdd_gamma_table_matches_reference(golden_dir):
@@ -119,11 +133,11 @@ def test_diffsbdd_gamma_table_matches_reference(golden_dir):
     assert np.array_equal(z["gamma"], D.polynomial_gamma(1000).numpy())
 
 
-def test_diffbp_sample_matches_reference(golden_dir):
+def test_diffbp_sample_matches_reference(golden_dir, case="diffbp_sample_T5"):
     """oracle/diffbp.py replays the reference's full 5-step DiffBP.sample (denoiser + CoMPredictor + score-type
     position step + absorbing-state type step) bit-exactly."""
     from oracle import diffbp as D
-    g = load(golden_dir, "diffbp_sample_T5")
+    g = load(golden_dir, case)
     Tn, C = int(g["T"]), 13
     sd = W.synthetic_state_dict_diffbp(C, 9, seed=0, num_timesteps=Tn)
     batch = {k[len("batch_"):]: v for k, v in g.items() if k.startswith("batch_")}
@@ -137,6 +151,21 @@ def test_diffbp_sample_matches_reference(golden_dir):
         x, c = D.denoise_step(sd, batch, x, c, t, eps, u, C, Tn)
     assert torch.equal(x, g["traj_x_-1"]) and torch.equal(c, g["traj_c_-1"])
     assert bool((c.argmax(-1) != 0).any()), "some atoms must have left the absorbing state"
+    if "ligand_gen_flag" in batch:
+        # the reference's DiffBP.sample leaves the context rows (position and type) untouched at every step
+        ctx, gen = ~batch["ligand_gen_flag"], batch["ligand_gen_flag"]
+        assert ctx.any() and gen.any() and bool((batch["ligand_atom_type"][ctx] != 0).any())
+        c0 = torch.nn.functional.one_hot(batch["ligand_atom_type"], C).float()
+        for t in list(range(Tn)) + [-1]:
+            assert torch.equal(g[f"traj_x_{t}"][ctx], batch["ligand_pos"][ctx]), t
+            assert torch.equal(g[f"traj_c_{t}"][ctx], c0[ctx]), t
+        assert not torch.equal(g["traj_x_-1"][gen], batch["ligand_pos"][gen])
+
+
+def test_diffbp_sample_with_context_atoms_matches_reference(golden_dir):
+    """sidechain-style context atoms (interleaved with the generated ones, which start in the absorbing type): the same replay,
+    and the reference leaves every context row untouched"""
+    test_diffbp_sample_matches_reference(golden_dir, "diffbp_sample_T5_ctx")
 
 
 def golden_batch(g):
@@ -167,11 +196,11 @@ def test_training_loss_and_gradients_match_reference(golden_dir, synthetic_sd, c
     assert float(g["gnorm/denoiser.blocks.3.x2h_layers.0.hk_func.net.3.bias"]) < 1e-6
 
 
-def test_diffbp_training_loss_and_gradients_match_reference(golden_dir):
+def test_diffbp_training_loss_and_gradients_match_reference(golden_dir, case="train_loss_diffbp"):
     """DiffBP training objective (diffbp.py:154-231 incl. CoMPredictor and interior_loss): the reference's four losses and
     the gradients of all 400+ tensors vs autograd on the restatement"""
     from oracle import diffbp as OD
-    g = load(golden_dir, "train_loss_diffbp")
+    g = load(golden_dir, case)
     batch = golden_batch(g)
     sd = W.synthetic_state_dict_diffbp(13, 9, seed=0, num_timesteps=1000)
     losses, grads = OD.loss_and_grads(sd, batch, g["t"], g["eps"], g["u"], 13, 1000)
@@ -188,7 +217,13 @@ def test_diffbp_training_loss_and_gradients_match_reference(golden_dir):
     assert n == 8 + 6 + 9 * 36 + 4 + (6 + 3 * 18)
 
 
-@pytest.mark.parametrize("case", ["train_loss_diffsbdd", "train_loss_diffsbdd_t0"])
+@pytest.mark.parametrize("case", ["train_loss_diffbp_ctx", "train_loss_diffbp_ctx_t0"])
+def test_diffbp_training_with_context_atoms_matches_reference(golden_dir, case):
+    """context atoms (interleaved, one graph without any; prefix, the last graph at t = 0 without a type-masked atom)"""
+    test_diffbp_training_loss_and_gradients_match_reference(golden_dir, case)
+
+
+@pytest.mark.parametrize("case", ["train_loss_diffsbdd", "train_loss_diffsbdd_t0", "train_loss_diffsbdd_ctx"])
 def test_diffsbdd_training_loss_and_gradients_match_reference(golden_dir, case):
     """DiffSBDD's variational training loss (diffsbdd.py:91-195): loss_t, the t = 0 reconstruction terms and the KL
     prior, against the unmodified reference's losses and gradients"""
