@@ -54,6 +54,8 @@ EXPORTS = {
     "cbgx_embed_compose": (_i, [_vp] * 8 + [_i] * 5 + [ctypes.POINTER(_vp)] + [_vp] * 5),
     "cbgx_embed_compose_backward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "cbgx_diffbp_loss": (_i, [_vp] * 13 + [_i, _i, _i, _i, _vp, _vp, ctypes.c_float, ctypes.c_float] + [_vp] * 9 + [_vp]),
+    "cbgx_diffbp_loss_knn": (_i, [_vp] * 13 + [_i, _i, _i, _i, _vp, _vp, ctypes.c_float, ctypes.c_float] + [_vp] * 9 + [_vp, _vp]),
+    "cbgx_diffbp_train_noise": (_i, [_vp] * 8 + [_i] * 4 + [_vp, _i, _i] + [_vp] * 6 + [_vp]),
     "cbgx_train_tape_bytes": (_sz, [_i, _i]),
     "cbgx_train_workspace_bytes": (_sz, [_i]),
     "cbgx_unitransformer_forward_train": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz,

@@ -1004,12 +1004,12 @@ int cbgx_targetdiff_loss(const float* x_out, const float* logits, const int64_t*
     return CBGX_OK;
 }
 
-int cbgx_diffbp_loss(const float* x_out, const float* x_in, const float* x_stack, const float* logits, const int64_t* sort_idx,
-                     const int32_t* graph_ptr, const uint8_t* lig_flag, const float* pos_noise, const float* com_noise,
-                     const int64_t* v0, const uint8_t* type_flag, const uint8_t* gen, const int64_t* t, int n_protein, int n_lig,
-                     int n_graphs, int num_classes, const float* alphas_cumprod, const float* betas, float rho, float gamma,
-                     float* losses, float* scal, float* gstats, float* a_pos, float* a_int, float* b_com, float* b_int, float* z_atom,
-                     int32_t* bad, void* stream) {
+static int diffbp_loss_entry(const float* x_out, const float* x_in, const float* x_stack, const float* logits, const int64_t* sort_idx,
+                             const int32_t* graph_ptr, const uint8_t* lig_flag, const float* pos_noise, const float* com_noise,
+                             const int64_t* v0, const uint8_t* type_flag, const uint8_t* gen, const int64_t* t, int n_protein, int n_lig,
+                             int n_graphs, int num_classes, const float* alphas_cumprod, const float* betas, float rho, float gamma,
+                             float* losses, float* scal, float* gstats, float* a_pos, float* a_int, float* b_com, float* b_int,
+                             float* z_atom, int32_t* bad, float* knn_scratch, void* stream) {
     if (n_lig <= 0 || n_graphs <= 0 || n_protein < 0 || num_classes < 1 || num_classes > 32)
         return set_error(CBGX_E_INVALID, "diffbp_loss: bad sizes (n_lig=%d B=%d C=%d)", n_lig, n_graphs, num_classes);
     if (!x_out || !x_in || !x_stack || !logits || !sort_idx || !graph_ptr || !lig_flag || !pos_noise || !com_noise || !v0 || !type_flag ||
@@ -1018,7 +1018,47 @@ int cbgx_diffbp_loss(const float* x_out, const float* x_in, const float* x_stack
     HIP_TRY(hipMemsetAsync(bad, 0, sizeof(int32_t), (hipStream_t)stream));
     HIP_TRY(launch_diffbp_loss(x_out, x_in, x_stack, logits, sort_idx, graph_ptr, lig_flag, pos_noise, com_noise, v0, type_flag, gen, t,
                                n_protein, n_lig, n_graphs, num_classes, alphas_cumprod, betas, rho, gamma, gstats, losses, scal, a_pos,
-                               a_int, b_com, b_int, z_atom, bad, (hipStream_t)stream));
+                               a_int, b_com, b_int, z_atom, bad, knn_scratch, (hipStream_t)stream));
+    return CBGX_OK;
+}
+
+int cbgx_diffbp_loss(const float* x_out, const float* x_in, const float* x_stack, const float* logits, const int64_t* sort_idx,
+                     const int32_t* graph_ptr, const uint8_t* lig_flag, const float* pos_noise, const float* com_noise,
+                     const int64_t* v0, const uint8_t* type_flag, const uint8_t* gen, const int64_t* t, int n_protein, int n_lig,
+                     int n_graphs, int num_classes, const float* alphas_cumprod, const float* betas, float rho, float gamma,
+                     float* losses, float* scal, float* gstats, float* a_pos, float* a_int, float* b_com, float* b_int, float* z_atom,
+                     int32_t* bad, void* stream) {
+    return diffbp_loss_entry(x_out, x_in, x_stack, logits, sort_idx, graph_ptr, lig_flag, pos_noise, com_noise, v0, type_flag, gen, t,
+                             n_protein, n_lig, n_graphs, num_classes, alphas_cumprod, betas, rho, gamma, losses, scal, gstats, a_pos,
+                             a_int, b_com, b_int, z_atom, bad, nullptr, stream);
+}
+
+int cbgx_diffbp_loss_knn(const float* x_out, const float* x_in, const float* x_stack, const float* logits, const int64_t* sort_idx,
+                         const int32_t* graph_ptr, const uint8_t* lig_flag, const float* pos_noise, const float* com_noise,
+                         const int64_t* v0, const uint8_t* type_flag, const uint8_t* gen, const int64_t* t, int n_protein, int n_lig,
+                         int n_graphs, int num_classes, const float* alphas_cumprod, const float* betas, float rho, float gamma,
+                         float* losses, float* scal, float* gstats, float* a_pos, float* a_int, float* b_com, float* b_int,
+                         float* z_atom, int32_t* bad, float* knn_scratch, void* stream) {
+    if (!knn_scratch) return set_error(CBGX_E_INVALID, "diffbp_loss_knn: NULL scratch");
+    return diffbp_loss_entry(x_out, x_in, x_stack, logits, sort_idx, graph_ptr, lig_flag, pos_noise, com_noise, v0, type_flag, gen, t,
+                             n_protein, n_lig, n_graphs, num_classes, alphas_cumprod, betas, rho, gamma, losses, scal, gstats, a_pos,
+                             a_int, b_com, b_int, z_atom, bad, knn_scratch, stream);
+}
+
+int cbgx_diffbp_train_noise(const float* x0, const int64_t* v0, const int64_t* t, const uint8_t* gen, const float* eps, const float* u,
+                            const int64_t* sort_idx, const int32_t* graph_ptr, int n_protein, int n_lig, int n_graphs, int num_classes,
+                            const float* alphas_cumprod, int num_timesteps, int absorbing_state, float* x_t, float* pos_noise,
+                            float* com_noise, int64_t* v_t, float* c_t, uint8_t* type_flag, void* stream) {
+    if (n_lig == 0) return CBGX_OK;
+    if (n_lig < 0 || n_graphs <= 0 || n_protein < 0 || num_classes < 1 || num_timesteps < 1 || absorbing_state < 0 ||
+        absorbing_state >= num_classes)
+        return set_error(CBGX_E_INVALID, "diffbp_train_noise: bad sizes (n_lig=%d B=%d C=%d T=%d absorbing=%d)", n_lig, n_graphs,
+                         num_classes, num_timesteps, absorbing_state);
+    if (!x0 || !v0 || !t || !gen || !eps || !u || !sort_idx || !graph_ptr || !alphas_cumprod || !x_t || !pos_noise || !com_noise ||
+        !v_t || !c_t || !type_flag)
+        return set_error(CBGX_E_INVALID, "diffbp_train_noise: NULL pointer");
+    HIP_TRY(launch_diffbp_noise(x0, v0, t, gen, eps, u, sort_idx, graph_ptr, n_protein, n_graphs, num_classes, alphas_cumprod,
+                                num_timesteps, absorbing_state, x_t, pos_noise, com_noise, v_t, c_t, type_flag, (hipStream_t)stream));
     return CBGX_OK;
 }
 

@@ -155,8 +155,13 @@ hipError_t launch_diffbp_loss(const float* x_out, const float* x_in, const float
                               const int32_t* graph_ptr, const uint8_t* lig, const float* pos_noise, const float* com_noise,
                               const int64_t* v0, const uint8_t* type_flag, const uint8_t* gen, const int64_t* t, int n_rec, int n_lig,
                               int B, int C, const float* acp, const float* betas, float rho, float gamma, float* gstats, float* losses,
-                              float* scal, float* a_pos, float* a_int, float* b_com, float* b_int, float* z_atom, int* bad,
+                              float* scal, float* a_pos, float* a_int, float* b_com, float* b_int, float* z_atom, int* bad, float* knn,
                               hipStream_t s);
+// DiffBP's forward noising (zero-centred position noise, absorbing-state type mask), one workgroup per graph of the composed order
+hipError_t launch_diffbp_noise(const float* x0, const int64_t* v0, const int64_t* t, const uint8_t* gen, const float* eps, const float* u,
+                               const int64_t* sort_idx, const int32_t* graph_ptr, int n_rec, int B, int C, const float* acp,
+                               int num_timesteps, int absorbing, float* x_t, float* pos_noise, float* com_noise, int64_t* v_t, float* c_t,
+                               uint8_t* type_flag, hipStream_t s);
 hipError_t launch_ssp_backward_rows(const float* pre, const float* dact, const int* rows, const int* n_rows, int max_rows,
                                     float* dpre, hipStream_t s);
 hipError_t launch_cls_w1_grad_rows(const float* dlogits, int C, const float* act, const int* rows, const int* n_rows, float* dW1,

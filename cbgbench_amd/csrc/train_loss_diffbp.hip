@@ -10,9 +10,15 @@
 //                               ligand atom of its graph, loss_l = -rho log(acc_l + 1e-3), mean_l max(gamma - loss_l, 0)   diffbp.py:18-28
 // The tensor path (cbgbench_amd/diffbp.py, CBGX_FUSED_TRAINING_OPS=0) takes ~350 small launches and their autograd for the same numbers
 // and leaves the device idle for a fifth of the step while the host issues them (profiles/trace_train_r06/, DiffBP).
-// One workgroup per graph, everything of a graph in LDS / registers; ligands of at most DBP_MAXL atoms (beyond k = 48 ligand atoms the
-// reference restricts every protein atom to its 48 nearest: the host keeps the tensor path for such batches).  Works on the COMPOSED
+// One workgroup per graph, everything of a graph in LDS / registers; ligands of at most DBP_MAXL = 128 atoms, one thread per atom.
+// Beyond DBP_K = 48 ligand atoms the reference restricts every protein atom to its 48 nearest ligand atoms (torch_cluster.knn(k=48),
+// diffbp.py:18-28): for such a graph every protein atom first finds the 48th-smallest d^2 of its row by bisection on the bit pattern
+// of the non-negative float (no array per thread), and the ligand-major walk keeps the pairs (d^2, l) that are among the 48
+// lexicographically smallest of the row -- exactly 48, ties broken by the ligand index; the selection carries no gradient.  Graphs of
+// at most 48 ligand atoms keep the instruction path and the summation order they always had.  Works on the COMPOSED
 // row order (per graph: protein rows, then ligand rows; `sort_idx` maps a composed row to its index in cat(protein, ligand)).
+// diffbp_noise_kernel: the forward noising in front of the networks (CTNVPScheduler.forward_add_noise(zero_center=True),
+// diffusion_scheduler.py:117-134, and MaskTypeSchedule.forward_add_noise, :452-473), one workgroup per graph, fixed summation order.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -22,8 +28,13 @@
 
 namespace cbgx {
 
-constexpr int DBP_MAXL = 48;
+constexpr int DBP_MAXL = 128;     // one thread per ligand atom, a few KB of LDS (the size prior of the sampler ends at 86 atoms)
+constexpr int DBP_K = 48;         // interior_loss: every protein atom looks at its k = 48 nearest ligand atoms
 constexpr int DBP_GSTATS = 8;     // per-graph record: L_pos, L_com, L_atom, sum r, gen count, type count, (unused) x 2
+
+// the ONE d^2 expression of the selection and of the accumulation of a graph with more than DBP_K ligand atoms: explicit fmas, so
+// that both places round alike whatever the compiler contracts elsewhere
+__device__ __forceinline__ float dbp_d2(float dx, float dy, float dz) { return fmaf(dz, dz, fmaf(dy, dy, dx * dx)); }
 
 template <int LC>
 __global__ __launch_bounds__(256) void diffbp_loss_kernel(
@@ -33,7 +44,7 @@ __global__ __launch_bounds__(256) void diffbp_loss_kernel(
     const uint8_t* __restrict__ type_flag, const uint8_t* __restrict__ gen, const int64_t* __restrict__ t, int n_rec_total, int n_lig_total,
     int C, const float* __restrict__ acp, const float* __restrict__ betas, float rho, float gamma, float* __restrict__ gstats,
     float* __restrict__ a_pos, float* __restrict__ a_int, float* __restrict__ b_com, float* __restrict__ b_int, float* __restrict__ z_atom,
-    int* __restrict__ bad) {
+    int* __restrict__ bad, float* knn) {
     __shared__ float s_xs[DBP_MAXL][3], s_v[DBP_MAXL][3], s_w[DBP_MAXL][3], s_acc[4][DBP_MAXL], s_sx[4][DBP_MAXL][3];
     __shared__ float s_sum[4][3], s_scal[8];
     __shared__ int s_cnt;
@@ -53,14 +64,21 @@ __global__ __launch_bounds__(256) void diffbp_loss_kernel(
         for (int k = 0; k < 3; ++k) { a_pos[3 * r + k] = 0.f; a_int[3 * r + k] = 0.f; b_com[3 * r + k] = 0.f; b_int[3 * r + k] = 0.f; }
         for (int k = 0; k < C; ++k) z_atom[(size_t)r * C + k] = 0.f;
     }
-    if (nl > DBP_MAXL || nl < 0) {      // the host promised otherwise: flag it (the Python side raises)
+    if (nl > (knn ? DBP_MAXL : DBP_K) || nl < 0) {      // the host promised otherwise: flag it (the Python side raises); the graph
+        // contributes nothing, and its ligand rows of the gradient pieces are zero too (the backward reads every row)
+        for (int r = l0 + tid; r < r1; r += 256) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { a_pos[3 * r + k] = 0.f; a_int[3 * r + k] = 0.f; b_com[3 * r + k] = 0.f; b_int[3 * r + k] = 0.f; }
+            for (int k = 0; k < C; ++k) z_atom[(size_t)r * C + k] = 0.f;
+        }
         if (tid == 0) { *bad = 1; for (int k = 0; k < DBP_GSTATS; ++k) gstats[g * DBP_GSTATS + k] = 0.f; }
         return;
     }
+    const bool big = nl > DBP_K;      // workgroup-uniform: the k-nearest restriction applies, and the sums take a fixed order in LDS
     const int tb = (int)t[g];
     const float a = acp[tb], b = betas[tb];
     const float kap = -b / (sqrtf(1.f - a) * sqrtf(1.f - b)), isb = 1.f / sqrtf(1.f - b);
-    const bool atom = tid < nl;                    // one thread per ligand atom (first wave)
+    const bool atom = tid < nl;                    // one thread per ligand atom (first wave; the first two when `big`)
     const int row = l0 + (atom ? tid : 0);
     const int ai = atom ? (int)(sort_idx[row] - n_rec_total) : 0;      // index in ligand order
     float nz[3] = {0.f, 0.f, 0.f}, dl[3] = {0.f, 0.f, 0.f}, xt[3] = {0.f, 0.f, 0.f};
@@ -118,12 +136,25 @@ __global__ __launch_bounds__(256) void diffbp_loss_kernel(
     // masked per-graph sums: movable atoms (pos, com), masked atoms (atom)
     if (tid < 8) s_scal[tid] = 0.f;
     __syncthreads();
-    if (gn) { atomicAdd(&s_scal[0], mp); atomicAdd(&s_scal[1], mc); atomicAdd(&s_scal[2], 1.f); }
-    if (tf) { atomicAdd(&s_scal[3], ce); atomicAdd(&s_scal[4], 1.f); }
+    if (!big) {
+        if (gn) { atomicAdd(&s_scal[0], mp); atomicAdd(&s_scal[1], mc); atomicAdd(&s_scal[2], 1.f); }
+        if (tf) { atomicAdd(&s_scal[3], ce); atomicAdd(&s_scal[4], 1.f); }
+    } else {      // two waves of atoms: summed in atom order by one thread per quantity (s_acc / s_sx are free until the interior term)
+        if (atom) {
+            s_acc[0][tid] = gn ? mp : 0.f; s_acc[1][tid] = gn ? mc : 0.f; s_acc[2][tid] = gn ? 1.f : 0.f;
+            s_acc[3][tid] = tf ? ce : 0.f; s_sx[0][tid][0] = tf ? 1.f : 0.f;
+        }
+        __syncthreads();
+        if (tid < 5) {
+            float s = 0.f;
+            for (int l = 0; l < nl; ++l) s += tid < 4 ? s_acc[tid][l] : s_sx[0][l][0];
+            s_scal[tid] = s;
+        }
+    }
     // interior term: thread (lane = ligand atom, chunk) walks a quarter of the graph's protein atoms
-    {
+    __syncthreads();      // s_xs complete (and, when `big`, the sums above read)
+    if (!big) {
         float acc = 0.f, sx[3] = {0.f, 0.f, 0.f};
-        __syncthreads();      // s_xs complete
         if (lane < nl) {
             const float xl[3] = {s_xs[lane][0], s_xs[lane][1], s_xs[lane][2]};
             const int per = (nr + 3) / 4, p0 = r0 + chunk * per, p1 = min(r0 + nr, p0 + per);
@@ -137,6 +168,57 @@ __global__ __launch_bounds__(256) void diffbp_loss_kernel(
             s_acc[chunk][lane] = acc;
 #pragma unroll
             for (int k = 0; k < 3; ++k) s_sx[chunk][lane][k] = sx[k];
+        }
+    } else {
+        // selection: protein atom p (threads at stride 256) finds T = the 48th-smallest d^2 of its row as the smallest bit pattern b with
+        // |{l : bits(d^2_l) <= b}| >= 48 (non-negative floats order like their bit patterns; 31 halvings of [0, bits(inf)]), and the
+        // largest ligand index `cut` among the ties d^2 == T that still belong to the 48: pair (p, l) is kept iff
+        // d^2 < T or (d^2 == T and l <= cut).  knn [2 N], indexed by the composed row of p.
+        for (int p = r0 + tid; p < r0 + nr; p += 256) {
+            const float px = x_in[3 * p], py = x_in[3 * p + 1], pz = x_in[3 * p + 2];
+            uint32_t lo = 0u, hi = 0x7f800000u;
+            for (int it = 0; it < 31; ++it) {
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                int cnt = 0;
+                for (int l = 0; l < nl; ++l)
+                    cnt += __float_as_uint(dbp_d2(s_xs[l][0] - px, s_xs[l][1] - py, s_xs[l][2] - pz)) <= mid ? 1 : 0;
+                if (cnt >= DBP_K) hi = mid; else lo = mid + 1u;
+            }
+            int below = 0, ties = 0;
+            for (int l = 0; l < nl; ++l) {
+                const uint32_t b = __float_as_uint(dbp_d2(s_xs[l][0] - px, s_xs[l][1] - py, s_xs[l][2] - pz));
+                below += b < lo ? 1 : 0;
+                ties += b == lo ? 1 : 0;
+            }
+            int cut = nl;      // every tie belongs (the only case on tie-free rows)
+            if (below + ties > DBP_K) {
+                int left = DBP_K - below;
+                for (int l = 0; l < nl && left > 0; ++l)
+                    if (__float_as_uint(dbp_d2(s_xs[l][0] - px, s_xs[l][1] - py, s_xs[l][2] - pz)) == lo) { cut = l; --left; }
+            }
+            knn[2 * (size_t)p] = __uint_as_float(lo);
+            knn[2 * (size_t)p + 1] = __int_as_float(cut);
+        }
+        __threadfence_block();
+        __syncthreads();      // the thresholds of this graph are visible to the whole workgroup
+        const int per = (nr + 3) / 4, p0 = r0 + chunk * per, p1 = min(r0 + nr, p0 + per);
+        const float ir = 1.f / rho;
+        for (int l = lane; l < nl; l += 64) {      // ligand atoms above lane 63: a second pass
+            const float xl[3] = {s_xs[l][0], s_xs[l][1], s_xs[l][2]};
+            float acc = 0.f, sx[3] = {0.f, 0.f, 0.f};
+            for (int p = p0; p < p1; ++p) {
+                const float dx = xl[0] - x_in[3 * p], dy = xl[1] - x_in[3 * p + 1], dz = xl[2] - x_in[3 * p + 2];
+                const float d2 = dbp_d2(dx, dy, dz), kth = knn[2 * (size_t)p];
+                const int cut = __float_as_int(knn[2 * (size_t)p + 1]);
+                if (d2 < kth || (d2 == kth && l <= cut)) {
+                    const float e = expf(-d2 * ir);
+                    acc += e;
+                    sx[0] = fmaf(e, dx, sx[0]); sx[1] = fmaf(e, dy, sx[1]); sx[2] = fmaf(e, dz, sx[2]);
+                }
+            }
+            s_acc[chunk][l] = acc;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s_sx[chunk][l][k] = sx[k];
         }
     }
     __syncthreads();
@@ -158,9 +240,15 @@ __global__ __launch_bounds__(256) void diffbp_loss_kernel(
             s_w[tid][k] = gi[k];
             s_xs[tid][k] = gc[k];
         }
-        atomicAdd(&s_scal[5], rl);
+        if (!big) atomicAdd(&s_scal[5], rl);
+        else s_acc[0][tid] = rl;      // (this thread alone read s_acc[.][tid]) summed in atom order below
     }
     __syncthreads();
+    if (big && tid == 9) {
+        float s = 0.f;
+        for (int l = 0; l < nl; ++l) s += s_acc[0][l];
+        s_scal[5] = s;
+    }
     if (tid < 9) {      // graph means of gp (0..2), gi (3..5), gc (6..8)
         float s = 0.f;
         const int k = tid % 3, which = tid / 3;
@@ -220,21 +308,98 @@ __global__ __launch_bounds__(256) void diffbp_loss_finish_kernel(const float* __
     }
 }
 
+// Forward noising of a DiffBP training step, one workgroup per graph of the composed order (the ligand rows are the tail of the graph's
+// range; sort_idx gives each one's index in ligand order, so `ligand_element_batch` need not be sorted):
+//   x_t = gen ? sqrt(a_t) x0 + sqrt(1 - a_t) eps : x0;  com_noise = mean of eps over ALL ligand atoms of the graph (context atoms too);
+//   pos_noise = eps - com_noise;  type_flag = (u < t / T) & gen;  v_t = type_flag ? absorbing : v0;  c_t = onehot(v_t).
+// The mean: thread-strided partial sums, then a fixed tree in LDS -- the same bits run to run.
+__global__ __launch_bounds__(256) void diffbp_noise_kernel(
+    const float* __restrict__ x0, const int64_t* __restrict__ v0, const int64_t* __restrict__ t, const uint8_t* __restrict__ gen,
+    const float* __restrict__ eps, const float* __restrict__ u, const int64_t* __restrict__ sort_idx, const int32_t* __restrict__ graph_ptr,
+    int n_rec_total, int C, const float* __restrict__ acp, int num_timesteps, int absorbing, float* __restrict__ x_t,
+    float* __restrict__ pos_noise, float* __restrict__ com_noise, int64_t* __restrict__ v_t, float* __restrict__ c_t,
+    uint8_t* __restrict__ type_flag) {
+    __shared__ float s_red[256][3];
+    __shared__ int s_cnt;
+    const int g = blockIdx.x, tid = threadIdx.x;
+    const int r0 = graph_ptr[g], r1 = graph_ptr[g + 1];
+    if (tid == 0) s_cnt = 0;
+    __syncthreads();
+    int c = 0;
+    for (int r = r0 + tid; r < r1; r += 256) c += sort_idx[r] >= n_rec_total ? 1 : 0;
+    if (c) atomicAdd(&s_cnt, c);
+    __syncthreads();
+    const int nl = s_cnt, l0 = r1 - nl;
+    float s[3] = {0.f, 0.f, 0.f};
+    for (int r = l0 + tid; r < r1; r += 256) {
+        const int a = (int)(sort_idx[r] - n_rec_total);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s[k] += eps[3 * a + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s_red[tid][k] = s[k];
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) s_red[tid][k] += s_red[tid + h][k];
+        }
+        __syncthreads();
+    }
+    const float cnt = (float)(nl > 0 ? nl : 1);
+    const float com[3] = {s_red[0][0] / cnt, s_red[0][1] / cnt, s_red[0][2] / cnt};
+    const int64_t tg = t[g];
+    const int tb = (int)tg;
+    const float ab = acp[tb];
+    const float sa = sqrtf(ab), sb = sqrtf(1.0f - ab);
+    // tb.float().clamp(min=0) / T: an fp32 division of the same operands as the tensor path
+    const float prob = fmaxf((float)tg, 0.f) / (float)num_timesteps;
+    for (int r = l0 + tid; r < r1; r += 256) {
+        const int a = (int)(sort_idx[r] - n_rec_total);
+        const bool gn = gen[a] != 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float x = x0[3 * a + k], e = eps[3 * a + k];
+            // each product rounded, as the three kernels of the tensor path (no contraction into an fma)
+            const float xn = __fadd_rn(__fmul_rn(sa, x), __fmul_rn(sb, e));
+            x_t[3 * a + k] = gn ? xn : x;
+            com_noise[3 * a + k] = com[k];
+            pos_noise[3 * a + k] = e - com[k];
+        }
+        const bool tf = (u[a] < prob) && gn;
+        const int64_t v = tf ? (int64_t)absorbing : v0[a];
+        type_flag[a] = tf ? 1 : 0;
+        v_t[a] = v;
+        for (int k = 0; k < C; ++k) c_t[(size_t)a * C + k] = k == (int)v ? 1.f : 0.f;
+    }
+}
+
+hipError_t launch_diffbp_noise(const float* x0, const int64_t* v0, const int64_t* t, const uint8_t* gen, const float* eps, const float* u,
+                               const int64_t* sort_idx, const int32_t* graph_ptr, int n_rec, int B, int C, const float* acp,
+                               int num_timesteps, int absorbing, float* x_t, float* pos_noise, float* com_noise, int64_t* v_t, float* c_t,
+                               uint8_t* type_flag, hipStream_t s) {
+    if (B <= 0) return hipSuccess;
+    hipLaunchKernelGGL(diffbp_noise_kernel, dim3(B), dim3(256), 0, s, x0, v0, t, gen, eps, u, sort_idx, graph_ptr, n_rec, C, acp,
+                       num_timesteps, absorbing, x_t, pos_noise, com_noise, v_t, c_t, type_flag);
+    return hipGetLastError();
+}
+
+// knn: scratch of 2 N floats for the k-nearest selection (NULL: ligands of at most DBP_K atoms only)
 hipError_t launch_diffbp_loss(const float* x_out, const float* x_in, const float* x_stack, const float* logits, const int64_t* sort_idx,
                               const int32_t* graph_ptr, const uint8_t* lig, const float* pos_noise, const float* com_noise,
                               const int64_t* v0, const uint8_t* type_flag, const uint8_t* gen, const int64_t* t, int n_rec, int n_lig,
                               int B, int C, const float* acp, const float* betas, float rho, float gamma, float* gstats, float* losses,
-                              float* scal, float* a_pos, float* a_int, float* b_com, float* b_int, float* z_atom, int* bad,
+                              float* scal, float* a_pos, float* a_int, float* b_com, float* b_int, float* z_atom, int* bad, float* knn,
                               hipStream_t s) {
     if (B <= 0) return hipSuccess;
     if (C <= 16)
         hipLaunchKernelGGL(diffbp_loss_kernel<16>, dim3(B), dim3(256), 0, s, x_out, x_in, x_stack, logits, sort_idx, graph_ptr, lig,
                            pos_noise, com_noise, v0, type_flag, gen, t, n_rec, n_lig, C, acp, betas, rho, gamma, gstats, a_pos, a_int,
-                           b_com, b_int, z_atom, bad);
+                           b_com, b_int, z_atom, bad, knn);
     else
         hipLaunchKernelGGL(diffbp_loss_kernel<32>, dim3(B), dim3(256), 0, s, x_out, x_in, x_stack, logits, sort_idx, graph_ptr, lig,
                            pos_noise, com_noise, v0, type_flag, gen, t, n_rec, n_lig, C, acp, betas, rho, gamma, gstats, a_pos, a_int,
-                           b_com, b_int, z_atom, bad);
+                           b_com, b_int, z_atom, bad, knn);
     hipLaunchKernelGGL(diffbp_loss_finish_kernel, dim3(1), dim3(256), 0, s, gstats, B, n_lig, losses, scal);
     return hipGetLastError();
 }

@@ -402,8 +402,13 @@ int cbgx_targetdiff_loss_backward(const float *grad_pos, const float *grad_logit
  *   -- in two launches, with their gradients with respect to the network outputs.  All [N,.] arrays are in the COMPOSED row order
  *   (per graph: protein rows, then ligand rows; graph_ptr [B+1]; sort_idx [N] as above; lig_flag [N]); x_in = the composed input
  *   positions (protein positions and x_t), x_stack = the centre-of-mass head's output positions.  pos_noise / com_noise [n_lig,3],
- *   v0, type_flag (the mask of the type loss), gen [n_lig] in LIGAND order; t [B].  Ligands of at most 48 atoms (beyond that the
- *   reference restricts every protein atom to its 48 nearest ligand atoms: *bad is set to 1 and the host must take its tensor path).
+ *   v0, type_flag (the mask of the type loss), gen [n_lig] in LIGAND order; t [B].  cbgx_diffbp_loss takes ligands of at most 48 atoms.
+ *   Beyond that the reference restricts every protein atom to its 48 nearest ligand atoms (torch_cluster.knn(k=48), diffbp.py:18-28):
+ *   cbgx_diffbp_loss_knn, the same entry with knn_scratch [2 N] floats (N = n_protein + n_lig), takes ligands of at most 128 atoms and,
+ *   for a graph of more than 48, keeps the pair (protein p, ligand l) iff (d^2(p,l), l) is among the 48 lexicographically smallest pairs
+ *   of p's row -- exactly 48 neighbours, ties broken by the ligand's index within its graph; the selection carries no gradient; graphs of
+ *   at most 48 ligand atoms get the same bits from both entries.  A graph over the entry's limit sets *bad to 1 (the host must take its
+ *   tensor path), adds nothing to the losses and gets zeros in its rows of the five gradient pieces.
  *   losses [4] = {pos, atom, com, inter}; scal [2] = {1 / D_gen, 1 / D_type}, the graph-count divisors of the masked means;
  *   gstats [8 n_graphs] scratch.  Gradient pieces, [N,3] / [N,C], zero on protein rows, to be combined by the caller with the
  *   upstream gradients g_* of the four losses:
@@ -415,6 +420,24 @@ int cbgx_diffbp_loss(const float *x_out, const float *x_in, const float *x_stack
                      int n_graphs, int num_classes, const float *alphas_cumprod, const float *betas, float rho, float gamma,
                      float *losses, float *scal, float *gstats, float *a_pos, float *a_int, float *b_com, float *b_int,
                      float *z_atom, int32_t *bad, void *stream);
+int cbgx_diffbp_loss_knn(const float *x_out, const float *x_in, const float *x_stack, const float *logits, const int64_t *sort_idx,
+                         const int32_t *graph_ptr, const uint8_t *lig_flag, const float *pos_noise, const float *com_noise,
+                         const int64_t *v0, const uint8_t *type_flag, const uint8_t *gen, const int64_t *t, int n_protein, int n_lig,
+                         int n_graphs, int num_classes, const float *alphas_cumprod, const float *betas, float rho, float gamma,
+                         float *losses, float *scal, float *gstats, float *a_pos, float *a_int, float *b_com, float *b_int,
+                         float *z_atom, int32_t *bad, float *knn_scratch, void *stream);
+/* cbgx_diffbp_train_noise: the forward noising of a DiffBP training step in one launch -- CTNVPScheduler.forward_add_noise with
+ *   zero_center=True (diffusion_scheduler.py:117-134) and MaskTypeSchedule.forward_add_noise (:452-473).  x0 [n_lig,3], v0 [n_lig], gen
+ *   [n_lig], eps [n_lig,3] ~ N(0,1), u [n_lig] ~ U(0,1) in LIGAND order; t [B]; sort_idx [N] / graph_ptr [B+1] from cbgx_compose_plan
+ *   (the ligand index array need not be sorted).  Outputs, in ligand order:
+ *     x_t = gen ? sqrt(a_t) x0 + sqrt(1 - a_t) eps : x0        com_noise = the graph's mean of eps over ALL its ligand atoms
+ *     pos_noise = eps - com_noise                               type_flag = (u < t / T) & gen   (bytes; t / T an fp32 division)
+ *     v_t = type_flag ? absorbing_state : v0                    c_t [n_lig,C] = onehot(v_t)
+ *   The mean is summed in a fixed order (no atomics): the same bits run to run. */
+int cbgx_diffbp_train_noise(const float *x0, const int64_t *v0, const int64_t *t, const uint8_t *gen, const float *eps, const float *u,
+                            const int64_t *sort_idx, const int32_t *graph_ptr, int n_protein, int n_lig, int n_graphs,
+                            int num_classes, const float *alphas_cumprod, int num_timesteps, int absorbing_state, float *x_t,
+                            float *pos_noise, float *com_noise, int64_t *v_t, float *c_t, uint8_t *type_flag, void *stream);
 
 /* cbgx_compose_plan (ABI 6): the index work of compose_context (repo/modules/common.py:189-214) -- sort_idx [N] = the STABLE argsort of
  *   cat(batch_protein, batch_ligand) (graph ids in [0, n_graphs), int64), and what its callers derive from it: batch_idx [N] the sorted ids,
