@@ -499,6 +499,16 @@ int cbgx_h2x_attention(const float* packed, int layer, const float* x, const flo
     return CBGX_OK;
 }
 
+int cbgx_node_stage(const float* packed, int layer, int x2h, const float* h, const uint8_t* lig_flag, int n_nodes,
+                    const int32_t* rows, const int32_t* n_rows, int q_direct, float* P, float* q, float* Qt, void* stream) {
+    if (n_nodes == 0) return CBGX_OK;
+    if (!packed || !h || !lig_flag || !P || !q || !Qt || layer < 0 || n_nodes < 0 || (rows == nullptr) != (n_rows == nullptr))
+        return fail(CBGX_E_INVALID, "node_stage: bad argument");
+    HIP_TRY(launch_node_mfma(packed + (x2h ? x2h_off(layer) : h2x_off(layer)), h, lig_flag, n_nodes, P, q, Qt, rows, n_rows, nullptr,
+                             nullptr, (hipStream_t)stream, true, nullptr, nullptr, q_direct != 0));
+    return CBGX_OK;
+}
+
 int cbgx_classifier(const float* packed, int num_layers, int num_classes, const float* h, int n_nodes, float* logits,
                     void* workspace, size_t workspace_bytes, void* stream) {
     if (n_nodes == 0) return CBGX_OK;
@@ -713,12 +723,14 @@ static int forward_impl(const float* packed, int num_layers, int num_classes, co
             hc = hn;
         }
     } else {
+    // x2h node stages of these two schedules: q straight from h, no q-hidden columns in P (launch_node_mfma; large inputs only)
+    const bool q_direct = node_qdirect_enabled();
     if (overlap) {
         const int *dst, *dst_n, *src, *src_n;
         layer_lists(0, dst, dst_n, src, src_n);
         const X2HLists xl = x2h_lists(0);
         HIP_TRY(launch_node_mfma(packed + x2h_off(0), h, lig_flag, n_nodes, Pset[0], qset[0], Qtset[0], dst, dst_n, src,
-                                 src_n, s, true, xl.gen, xl.gen_n));
+                                 src_n, s, true, xl.gen, xl.gen_n, q_direct));
     }
     for (int l = 0; l < num_layers; ++l) {
         float* hn = (l == num_layers - 1 && h_out) ? h_out : w.hbuf[l & 1];
@@ -732,7 +744,7 @@ static int forward_impl(const float* packed, int num_layers, int num_classes, co
         if (!overlap) {
             if (dual) {
                 HIP_TRY(launch_node_mfma(packed + x2h_off(l), hc, lig_flag, n_nodes, w.P, w.q, w.Qt, dst, dst_n, src, src_n, s, true,
-                                         xl.gen, xl.gen_n));
+                                         xl.gen, xl.gen_n, q_direct));
                 HIP_TRY(launch_edge_x2h_dual(packed + x2h_off(l), xc, hc, w.P, w.Qt, w.q, w.nbr, w.deg, lig_flag, gen_flag, w.e_w,
                                              n_nodes, hn, xl.pp, xl.pp_n, xl.gen, xl.gen_n, xl.full, s));
             } else {
@@ -753,7 +765,7 @@ static int forward_impl(const float* packed, int num_layers, int num_classes, co
                 HIP_TRY(hipStreamWaitEvent(aux->s, aux->fork, 0));
                 const X2HLists xn = x2h_lists(l + 1);
                 HIP_TRY(launch_node_mfma(packed + x2h_off(l + 1), hn, lig_flag, n_nodes, Pset[set ^ 1], qset[set ^ 1],
-                                         Qtset[set ^ 1], d2, d2n, s2, s2n, aux->s, true, xn.gen, xn.gen_n));
+                                         Qtset[set ^ 1], d2, d2n, s2, s2n, aux->s, true, xn.gen, xn.gen_n, q_direct));
                 HIP_TRY(hipEventRecord(aux->join, aux->s));
             }
             HIP_TRY(launch_attention(false, packed + h2x_off(l), xc, hn, w.nbr, w.deg, lig_flag, gen_flag, w.e_w, n_nodes,

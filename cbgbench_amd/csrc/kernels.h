@@ -115,9 +115,14 @@ hipError_t launch_mark_nbr(const int* list, const int* count, int n_upper, const
                            uint8_t* m, hipStream_t s);
 // large_lists: the destination list (when given) is expected to hold a sizeable part of the nodes (x2h blocks of the cached / pruned
 // layers) rather than the few movable atoms of an h2x block: throughput launches instead of one workgroup per column chunk
+// q_direct (inputs above NODE_STAGE_MAX_ROWS only): q comes straight from h (node_query_kernel) and the q-hidden columns of P are
+// NOT produced -- for callers whose edge stage is all that reads P (the inference forward; the training tape keeps them)
 hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig, int n_nodes, float* P, float* qbuf,
                             float* Qt, const int* act, const int* act_count, const int* src, const int* src_count,
-                            hipStream_t s, bool large_lists = false, const int* fold = nullptr, const int* fold_count = nullptr);
+                            hipStream_t s, bool large_lists = false, const int* fold = nullptr, const int* fold_count = nullptr,
+                            bool q_direct = false);
+// CBGX_NODE_QDIRECT=0 in the environment: the inference forward keeps the projection -> query MLP chain (A/B runs, bit-identity tests)
+bool node_qdirect_enabled();
 // the fused node stage (node_stage_kernel, inputs of <= NODE_STAGE_MAX_ROWS rows) as a list of jobs on the same input features:
 // blockIdx.y = job.  `rows` NULL: all n_nodes rows.  `chunk_mask`: 64-column chunks of the projection to produce (CHUNKS_*);
 // `proj_only`: phase 1 only (the PS columns of a block's source rows).

@@ -120,7 +120,11 @@ constexpr size_t PP_WBV = PP_LN + 4 * H;
 constexpr size_t PP_WFOLD = PP_WBV + (size_t)H * H;
 constexpr size_t PP_IMG_SIZE = PP_WFOLD + (size_t)H * H;      // 38400 floats = 153600 B, the size of the general image
 constexpr size_t A_IMG_PP = A_WQ1_CINV + H;
-constexpr size_t ATT_SIZE = A_IMG_PP + PP_IMG_SIZE;
+// ---- the q-hidden columns of the node projection (A_NPROJ_FRAG chunks 8 and 9: the same scaled values Wn[:, col] 2^kc) in the order
+// of node_query_kernel's swapped first product (node_mfma.hip): [part hi|lo][t 8][u 4][lane 64][8 f16], lane (c, q) <-> output
+// channel 16t + c, slot j of instruction u <-> k = 16 (2u + (j >> 2)) + 4q + (j & 3).  64 KB, copied verbatim into LDS.
+constexpr size_t A_NQ_FRAG = A_IMG_PP + PP_IMG_SIZE;
+constexpr size_t ATT_SIZE = A_NQ_FRAG + (size_t)H * H;
 
 constexpr size_t LAYER_SIZE = 2 * ATT_SIZE;       // x2h then h2x
 

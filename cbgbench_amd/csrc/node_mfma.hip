@@ -2,6 +2,7 @@
 //
 //   node_proj :  P[N,640]   = h[N,128] @ Wn + bn          (PDk | PDv | PSk | PSv | q-hidden), LDS-staged Wn chunks
 //   node_qmlp :  q[N,128]   = ReLU(LN(P[:,512:640])) @ Wq1^T + bq1
+//   node_query:  the same q straight from h (inference forward on large inputs: P then has no q-hidden columns)
 //   node_qfold:  Qt[N,16,128] = (1/sqrt 8) * q[N, 8a:8a+8] @ Wbk[8a:8a+8, :]      (key's 2nd Linear folded into q)
 //
 // Common shape: one wavefront owns 16 rows (nodes); its A operand is read straight from global memory in
@@ -95,23 +96,23 @@ constexpr int NP_WGS_PER_CU = NP_CPW == 1 ? 3 : 2;   // node_proj_kernel: __laun
 constexpr int NP_RESIDENT_WGS = 256 * NP_WGS_PER_CU;
 
 typedef float lds_fx4 __attribute__((ext_vector_type(4)));
-// LDS fill of the float4 range [begin, end) by 256 threads with every load of a thread requested before its first store (at most
+// LDS fill of the float4 range [begin, end) by NT threads with every load of a thread requested before its first store (at most
 // MAXV per thread).  Written as a plain loop the compiler emits load -> wait -> ds_write per iteration: up to 16 dependent L2 round
 // trips (~11 us) at the head of every launch.
-template <int MAXV>
+template <int MAXV, int NT = 256>
 __device__ __forceinline__ void lds_fill_f4(float* lds, const float* src_base, int begin, int end, int tid) {
     const lds_fx4* src = reinterpret_cast<const lds_fx4*>(src_base);
     lds_fx4* dst = reinterpret_cast<lds_fx4*>(lds);
     lds_fx4 v[MAXV];
 #pragma unroll
     for (int u = 0; u < MAXV; ++u) {
-        const int t = begin + tid + 256 * u;
+        const int t = begin + tid + NT * u;
         v[u] = src[t < end ? t : end - 1];
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int u = 0; u < MAXV; ++u) {
-        const int t = begin + tid + 256 * u;
+        const int t = begin + tid + NT * u;
         if (t < end) dst[t] = v[u];
     }
 }
@@ -290,6 +291,70 @@ __global__ __launch_bounds__(256, NP_WGS_PER_CU) void node_proj_kernel(const flo
 // ------------------------------------------------------------------------------------------------
 constexpr int NQ_FRAG = 8 * 8 * 64 * 4;  // 16384 floats = 64 KB
 
+// The two halves of the query MLP's tail on one wave's 16-row tile, shared by node_qmlp_kernel and node_query_kernel (the same code,
+// so the same bits).  z[4u + i] <-> q-hidden channel 16u + 4q + i of the row of lane c (A layout).
+// LayerNorm + ReLU (in-lane + across q), then the range-safe split: z[8u + j] <-> k = 16 (2u + (j >> 2)) + 4q + (j & 3), the slot order
+// of the MFMA's A operand.  `lng` / `lnb`: gamma and beta, indexed by channel (global memory or LDS).
+__device__ __forceinline__ void query_ln_split(float (&z)[32], const float* __restrict__ lng, const float* __restrict__ lnb, int q,
+                                               half8 (&zh)[4], half8 (&zl)[4], float (&rinv)[4]) {
+    float sm = 0.f;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) sm += (z[4 * u] + z[4 * u + 1]) + (z[4 * u + 2] + z[4 * u + 3]);
+    const float mean = nxrow_sum(sm) * (1.f / H);
+    float var = 0.f;
+#pragma unroll
+    for (int u = 0; u < 32; ++u) { z[u] -= mean; var += z[u] * z[u]; }
+    const float rstd = 1.f / sqrtf(nxrow_sum(var) * (1.f / H) + 1e-5f);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const float4 g = nld4(lng + 16 * u + 4 * q), b = nld4(lnb + 16 * u + 4 * q);
+        z[4 * u + 0] = fmaxf(z[4 * u + 0] * rstd * g.x + b.x, 0.f);
+        z[4 * u + 1] = fmaxf(z[4 * u + 1] * rstd * g.y + b.y, 0.f);
+        z[4 * u + 2] = fmaxf(z[4 * u + 2] * rstd * g.z + b.z, 0.f);
+        z[4 * u + 3] = fmaxf(z[4 * u + 3] * rstd * g.w + b.w, 0.f);
+    }
+    float mx = 0.f;   // z >= 0 after the ReLU
+#pragma unroll
+    for (int u = 0; u < 32; ++u) mx = fmaxf(mx, z[u]);
+    float inv;
+    const float up = row_pow2(nxrow_max(mx), inv);
+    rows_to_c_layout(inv, q, rinv);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const float v[8] = {z[8 * u], z[8 * u + 1], z[8 * u + 2], z[8 * u + 3], z[8 * u + 4], z[8 * u + 5], z[8 * u + 6], z[8 * u + 7]};
+        split8(v, up, zh[u], zl[u]);
+    }
+}
+// 64 output columns (group `grp`) of q = z @ Wq1^T + bq1 for the tile: 48 MFMAs against the Wq1 table in LDS (Bh / Bl: this lane's
+// entry of tile 0, [nt][u][lane]) and the scaled stores of the rows 4q + r
+__device__ __forceinline__ void query_out_group(const half8 (&zh)[4], const half8 (&zl)[4], const half8* Bh, const half8* Bl, int grp,
+                                                float4 b4, float4 ci, const float (&rinv)[4], const int (&orow)[4],
+                                                float* __restrict__ qout, int c) {
+    floatx4 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        half8 bh[4], bl[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { bh[j] = Bh[((grp * 4 + j) * 4 + u) * 64]; bl[j] = Bl[((grp * 4 + j) * 4 + u) * 64]; }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = MFMAH32(zh[u], bl[j], acc[j]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = MFMAH32(zl[u], bh[j], acc[j]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = MFMAH32(zh[u], bh[j], acc[j]);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        if (orow[r] >= 0) {
+            float4 o = {fmaf(acc[0][r] * rinv[r], ci.x, b4.x), fmaf(acc[1][r] * rinv[r], ci.y, b4.y),
+                        fmaf(acc[2][r] * rinv[r], ci.z, b4.z), fmaf(acc[3][r] * rinv[r], ci.w, b4.w)};
+            *reinterpret_cast<float4*>(qout + (size_t)orow[r] * H + 64 * grp + 4 * c) = o;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void node_qmlp_kernel(const float* __restrict__ att, const float* __restrict__ P,
                                                         float* __restrict__ qout, int n_nodes,
                                                         const int* __restrict__ rows, const int* __restrict__ n_rows_ptr) {
@@ -328,72 +393,162 @@ __global__ __launch_bounds__(256) void node_qmlp_kernel(const float* __restrict_
             orow[r] = k < n_rows ? o : -1;
         }
         float z[32];
-        float sm = 0.f;
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const float4 v = nld4(P + (size_t)arow * PROW + 4 * H + 16 * u + 4 * q);
             z[4 * u] = v.x; z[4 * u + 1] = v.y; z[4 * u + 2] = v.z; z[4 * u + 3] = v.w;
-            sm += (v.x + v.y) + (v.z + v.w);
         }
-        const float mean = nxrow_sum(sm) * (1.f / H);
-        float var = 0.f;
-#pragma unroll
-        for (int u = 0; u < 32; ++u) { z[u] -= mean; var += z[u] * z[u]; }
-        const float rstd = 1.f / sqrtf(nxrow_sum(var) * (1.f / H) + 1e-5f);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const float4 g = nld4(att + A_LNQ_G + 16 * u + 4 * q), b = nld4(att + A_LNQ_B + 16 * u + 4 * q);
-            z[4 * u + 0] = fmaxf(z[4 * u + 0] * rstd * g.x + b.x, 0.f);
-            z[4 * u + 1] = fmaxf(z[4 * u + 1] * rstd * g.y + b.y, 0.f);
-            z[4 * u + 2] = fmaxf(z[4 * u + 2] * rstd * g.z + b.z, 0.f);
-            z[4 * u + 3] = fmaxf(z[4 * u + 3] * rstd * g.w + b.w, 0.f);
-        }
-        half8 zh[4], zl[4];   // z[8u + j] <-> k = 16 (2u + (j >> 2)) + 4q + (j & 3): exactly the order z was loaded in
+        half8 zh[4], zl[4];
         float rinv[4];
-        {
-            float mx = 0.f;   // z >= 0 after the ReLU
-#pragma unroll
-            for (int u = 0; u < 32; ++u) mx = fmaxf(mx, z[u]);
-            float inv;
-            const float up = row_pow2(nxrow_max(mx), inv);
-            rows_to_c_layout(inv, q, rinv);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float v[8] = {z[8 * u], z[8 * u + 1], z[8 * u + 2], z[8 * u + 3], z[8 * u + 4], z[8 * u + 5], z[8 * u + 6], z[8 * u + 7]};
-                split8(v, up, zh[u], zl[u]);
-            }
-        }
+        query_ln_split(z, att + A_LNQ_G, att + A_LNQ_B, q, zh, zl, rinv);
         const half8* Bh = reinterpret_cast<const half8*>(lds) + lane;   // [nt][u][lane]
         const half8* Bl = Bh + 8 * 4 * 64;
 #pragma unroll
         for (int gi = 0; gi < 2; ++gi) {
             const int grp = grp_begin + gi;
             if (grp >= grp_end) break;
-            const float4 b4 = b4g[gi], ci = cig[gi];
-            floatx4 acc[4];
+            query_out_group(zh, zl, Bh, Bl, grp, b4g[gi], cig[gi], rinv, orow, qout, c);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// node_query: q straight from h in ONE launch -- q = ReLU(LN(h Wn[:, 512:640] + bq0)) Wq1^T + bq1 -- for the inference forward on
+// large inputs: the q-hidden fifth of P is gathered by no edge kernel, so node_proj_kernel need not write it (and run a fifth chunk
+// group for it) only for node_qmlp_kernel to read it back.
+// The first product runs with its operands SWAPPED, MFMA(weights, activations): the activation operand is node_proj_kernel's
+// ah[u] / al[u] (lane c = node, slot j of instruction u <-> k = 16 (2u + (j >> 2)) + 4q + (j & 3)), the weight operand has lane c <->
+// output channel 16t + c with the same k slots, so register r of tile t in lane (c, q) is channel 16t + 4q + r of node c: element
+// z[4t + r] of node_qmlp_kernel's A-layout register file, and the tail above runs on it without a transpose.  Per output element
+// the arithmetic is node_proj_kernel's: the same f16 pieces in the same k slots, per u the products ah wl, al wh, ah wh, then
+// fmaf(acc * rinv, cinv, bias) (bn2's q-hidden part is bq0 for both destination classes).  q is bit-identical to the chain's.
+// Weight table A_NQ_FRAG [part hi|lo][t 8][u 4][lane 64][8 f16] = split(Wn[k(u, q, j)][512 + 16t + c] 2^kc): the values of
+// A_NPROJ_FRAG's chunks 8 and 9 in another order.
+// 8-wave workgroups with a CU to themselves (both 64 KB tables resident in LDS), persistent over 128-row tiles, one wave per 16 rows;
+// the next tile's rows are requested before the current tile's MFMAs and its list entries one tile earlier.
+// ------------------------------------------------------------------------------------------------
+constexpr int NQK_THREADS = 512;
+constexpr int NQK_ROWS = 16 * (NQK_THREADS / 64);      // rows per workgroup tile
+// Workgroups per launch: NOT one per CU.  With 256 the kernel itself is fastest (about the time of node_qmlp_kernel: both move 1 KB per
+// row), but every edge kernel that follows runs 8 - 10 % longer (x2h 1 160 -> 1 260 us, h2x 83 -> 89 us, same box, serial schedule:
+// profiles/ab_classes_r07a.log) -- the chip holds a lower clock after 256 CUs of back-to-back MFMAs on LDS operands, for longer than
+// a layer lasts; the loss grows with the number of CUs the kernel takes (160: + 2 %, 208: + 6 %, 240: + 8 % on a second box) and is
+// gone at 128.  Fewer CUs cost the kernel time of its own (128: + 13 us per x2h launch, 64: + 54 us), part of it hidden behind the h2x
+// block of the two-stream schedule; the headline is the same within its spread at 96, 128 and 160 (profiles/ab_grid_r07a.log).
+constexpr int NQK_GRID = 96;
+
+__global__ __launch_bounds__(NQK_THREADS) void node_query_kernel(const float* __restrict__ att, const float* __restrict__ h,
+                                                                 float* __restrict__ qout, int n_nodes,
+                                                                 const int* __restrict__ rows, const int* __restrict__ n_rows_ptr) {
+    // q-hidden table | Wq1 table | per-channel constants of the first half: column scale, bias, LayerNorm gamma and beta
+    __shared__ __attribute__((aligned(16))) float lds[2 * NQ_FRAG + 4 * H];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, c = lane & 15, q = lane >> 4;
+    const int n_rows = rows ? *n_rows_ptr : n_nodes;
+    const int n_tiles = (n_rows + NQK_ROWS - 1) / NQK_ROWS;
+    if ((int)blockIdx.x >= n_tiles) return;   // no tile for this workgroup
+    auto list_row = [&](int tile) {      // the list entry of this lane's row (clamped past the end)
+        const int ak = min(tile * NQK_ROWS + wave * 16 + c, n_rows - 1);
+        return rows ? rows[ak] : ak;
+    };
+    auto load_row = [&](int row, float4 (&hv)[8]) {      // h[row][32u + 4q ..], h[row][32u + 16 + 4q ..]
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = floatx4{0.f, 0.f, 0.f, 0.f};
+        for (int u = 0; u < 4; ++u) {
+            hv[2 * u] = nld4(h + (size_t)row * H + 32 * u + 4 * q);
+            hv[2 * u + 1] = nld4(h + (size_t)row * H + 32 * u + 16 + 4 * q);
+        }
+    };
+    // the first tile's rows travel with the table fill
+    int arow = list_row(blockIdx.x), arow_next = list_row(blockIdx.x + gridDim.x);
+    float4 hv[8];
+    load_row(arow, hv);
+    lds_fill_f4<8, NQK_THREADS>(lds, att + A_NQ_FRAG, 0, NQ_FRAG / 4, tid);
+    lds_fill_f4<8, NQK_THREADS>(lds + NQ_FRAG, att + A_WQ1_FRAG, 0, NQ_FRAG / 4, tid);
+    if (tid < H) {
+        const int k = tid >> 5, m = 4 * (tid & 31);
+        const size_t src = k == 0 ? A_NPROJ_CINV + 4 * H : (k == 1 ? A_BN2 + 4 * H : (k == 2 ? A_LNQ_G : A_LNQ_B));
+        *reinterpret_cast<float4*>(lds + 2 * NQ_FRAG + k * H + m) = nld4(att + src + m);
+    }
+    float4 b4g[2], cig[2];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                half8 bh[4], bl[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { bh[j] = Bh[((grp * 4 + j) * 4 + u) * 64]; bl[j] = Bl[((grp * 4 + j) * 4 + u) * 64]; }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = MFMAH32(zh[u], bl[j], acc[j]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = MFMAH32(zl[u], bh[j], acc[j]);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j] = MFMAH32(zh[u], bh[j], acc[j]);
-            }
+    for (int g = 0; g < 2; ++g) {
+        b4g[g] = nld4(att + A_BQ1 + 64 * g + 4 * c);
+        cig[g] = nld4(att + A_WQ1_CINV + 64 * g + 4 * c);
+    }
+    __syncthreads();
+    const half8* Wh = reinterpret_cast<const half8*>(lds) + lane;   // [t][u][lane]
+    const half8* Wl = Wh + 8 * 4 * 64;
+    const half8* Bh = reinterpret_cast<const half8*>(lds + NQ_FRAG) + lane;   // [nt][u][lane]
+    const half8* Bl = Bh + 8 * 4 * 64;
+    const float* cst = lds + 2 * NQ_FRAG;
+    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        float4 hn[8];
+        load_row(arow_next, hn);
+        const int arow_next2 = list_row(tile + 2 * (int)gridDim.x);
+        __builtin_amdgcn_sched_barrier(0);
+        const int row0 = tile * NQK_ROWS + wave * 16;
+        if (row0 < n_rows) {      // (wave-uniform: the last tile's trailing waves)
+            int orow[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if (orow[r] >= 0) {
-                    float4 o = {fmaf(acc[0][r] * rinv[r], ci.x, b4.x), fmaf(acc[1][r] * rinv[r], ci.y, b4.y),
-                                fmaf(acc[2][r] * rinv[r], ci.z, b4.z), fmaf(acc[3][r] * rinv[r], ci.w, b4.w)};
-                    *reinterpret_cast<float4*>(qout + (size_t)orow[r] * H + 64 * grp + 4 * c) = o;
+                const int k = row0 + 4 * q + r;
+                const int o = __builtin_amdgcn_ds_bpermute((4 * q + r) << 2, arow);      // lane 4q + r holds row 4q + r of the tile
+                orow[r] = k < n_rows ? o : -1;
+            }
+            half8 ah[4], al[4];
+            float inv;      // of the lane's own row: the swapped product's columns are the nodes
+            {
+                float mx = 0.f;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    mx = fmaxf(fmaxf(mx, fabsf(hv[u].x)), fabsf(hv[u].y));
+                    mx = fmaxf(fmaxf(mx, fabsf(hv[u].z)), fabsf(hv[u].w));
+                }
+                const float up = row_pow2(nxrow_max(mx), inv);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float4 v0 = hv[2 * u], v1 = hv[2 * u + 1];
+                    const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+                    split8(v, up, ah[u], al[u]);
                 }
             }
+            float z[32];
+#pragma unroll
+            for (int g = 0; g < 2; ++g) {      // four channel tiles at a time: independent accumulators back to back
+                floatx4 acc[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[j] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    half8 wh[4], wl[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) { wh[j] = Wh[((4 * g + j) * 4 + u) * 64]; wl[j] = Wl[((4 * g + j) * 4 + u) * 64]; }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[j] = MFMAH32(wl[j], ah[u], acc[j]);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[j] = MFMAH32(wh[j], al[u], acc[j]);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[j] = MFMAH32(wh[j], ah[u], acc[j]);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int t = 4 * g + j;
+                    const float4 ci = nld4(cst + 16 * t + 4 * q), b = nld4(cst + H + 16 * t + 4 * q);
+                    z[4 * t + 0] = fmaf(acc[j][0] * inv, ci.x, b.x);
+                    z[4 * t + 1] = fmaf(acc[j][1] * inv, ci.y, b.y);
+                    z[4 * t + 2] = fmaf(acc[j][2] * inv, ci.z, b.z);
+                    z[4 * t + 3] = fmaf(acc[j][3] * inv, ci.w, b.w);
+                }
+            }
+            half8 zh[4], zl[4];
+            float rinv[4];
+            query_ln_split(z, cst + 2 * H, cst + 3 * H, q, zh, zl, rinv);
+#pragma unroll
+            for (int grp = 0; grp < 2; ++grp) query_out_group(zh, zl, Bh, Bl, grp, b4g[grp], cig[grp], rinv, orow, qout, c);
         }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) hv[u] = hn[u];
+        arow = arow_next;
+        arow_next = arow_next2;
     }
 }
 
@@ -929,6 +1084,22 @@ __global__ void pack_nproj_kernel(PackBlocks pb) {
     chunk[(size_t)4 * 4 * 64 * 8 + off] = lo;
 }
 
+// the q-hidden columns once more, in the order of node_query_kernel's swapped first product: dst[part][t][u][lane][j] (f16) = hi / lo of
+// Wcat[col = 512 + 16t + c][k = 16 (2u + (j >> 2)) + 4q + (j & 3)] 2^kc -- the same scaled values as chunks 8 and 9 above
+__global__ void pack_nquery_kernel(PackBlocks pb) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;   // one thread per weight: [t 8][u 4][lane 64][j 8]
+    if (idx >= H * H) return;
+    float* att = pb.att[blockIdx.y];
+    const int j = idx & 7, lane = (idx >> 3) & 63, u = (idx >> 9) & 3, t = idx >> 11;
+    const int c = lane & 15, q = lane >> 4;
+    const int col = 4 * H + 16 * t + c, k = 16 * (2 * u + (j >> 2)) + 4 * q + (j & 3);
+    const float v = nproj_weight(pb, blockIdx.y, col, k) * (1.f / att[A_NPROJ_CINV + col]);   // exact: a power of two
+    const _Float16 hi = (_Float16)v;
+    _Float16* dst = reinterpret_cast<_Float16*>(att + A_NQ_FRAG);
+    dst[idx] = hi;
+    dst[(size_t)H * H + idx] = (_Float16)(v - (float)hi);
+}
+
 __global__ void pack_wq1_kernel(PackBlocks pb) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;  // one thread per weight: [nt 8][u 4][lane 64][j 8]
     if (idx >= H * H) return;
@@ -968,6 +1139,7 @@ __global__ void pack_bn2_kernel(PackBlocks pb) {
 hipError_t launch_pack_node_tables(const PackBlocks& pb, hipStream_t s) {
     hipLaunchKernelGGL(pack_colscale_kernel, dim3((PROW + H + 3) / 4, pb.n), dim3(256), 0, s, pb);
     hipLaunchKernelGGL(pack_nproj_kernel, dim3(NP_CHUNKS * 4 * 4 * 64 * 8 / 256, pb.n), dim3(256), 0, s, pb);
+    hipLaunchKernelGGL(pack_nquery_kernel, dim3(H * H / 256, pb.n), dim3(256), 0, s, pb);
     hipLaunchKernelGGL(pack_wq1_kernel, dim3(H * H / 256, pb.n), dim3(256), 0, s, pb);
     hipLaunchKernelGGL(pack_wbk_kernel, dim3(NF_FRAG / 256, pb.n), dim3(256), 0, s, pb);
     hipLaunchKernelGGL(pack_bn2_kernel, dim3((2 * PROW + 255) / 256, pb.n), dim3(256), 0, s, pb);
@@ -1351,6 +1523,7 @@ hipError_t launch_build_active(const uint8_t* flag, int n, int* list, int* count
 constexpr unsigned CHUNKS_ALL = 0x3ffu;   // PDk PDv PSk PSv qh
 constexpr unsigned CHUNKS_PS = 0x0f0u;    // PSk | PSv  (columns 256..511): what *neighbours* contribute
 constexpr unsigned CHUNKS_OWN = 0x30fu;   // PDk | PDv | qh: what the destination node itself contributes
+constexpr unsigned CHUNKS_QH = 0x300u;    // the q-hidden columns: read by node_qmlp_kernel (and the training backward) only
 
 // node stage of one attention block: P, q (scratch), Qt.
 // `act` / `act_count` (optional): only the listed destination nodes will be processed by the edge kernel (h2x: nodes
@@ -1388,12 +1561,17 @@ hipError_t launch_node_stage_jobs(const NodeStageJobs& jobs, const float* h, con
     return hipGetLastError();
 }
 
+bool node_qdirect_enabled() {
+    static const bool on = [] { const char* e = getenv("CBGX_NODE_QDIRECT"); return !e || atoi(e) != 0; }();
+    return on;
+}
+
 // `fold` / `fold_count` (optional, x2h blocks of the inference path): the rows whose folded query Qt the edge stage will read -- the
 // GENERAL list of the layer; protein-only destinations fold in registers (edge_mfma.hip) and only need q.  Without it Qt is
 // produced for every destination.
 hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig, int n_nodes, float* P, float* qbuf,
                             float* Qt, const int* act, const int* act_count, const int* src, const int* src_count,
-                            hipStream_t s, bool large_lists, const int* fold, const int* fold_count) {
+                            hipStream_t s, bool large_lists, const int* fold, const int* fold_count, bool q_direct) {
     if (n_nodes == 0) return hipSuccess;
     const int tiles = (n_nodes + 63) / 64;
     const int grid = min(tiles, 512);
@@ -1415,13 +1593,16 @@ hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig
     // three-kernel chain: the fused kernel was measured there in round 4, 40 us against 10 + 8 + 12: its 16-wave workgroups, one
     // per CU, need two rounds for 313 row tiles.)
     const bool fused = n_nodes <= NODE_STAGE_MAX_ROWS;
+    // q straight from h: the projection launches drop the q-hidden chunks (four chunk groups instead of five on a full layer)
+    const bool direct = q_direct && !fused;
+    const unsigned chunks_all = direct ? CHUNKS_ALL & ~CHUNKS_QH : CHUNKS_ALL, chunks_own = direct ? CHUNKS_OWN & ~CHUNKS_QH : CHUNKS_OWN;
     profile_mark_begin(K_NODE_GEMM, s);
     // fused with a destination list: the source rows' PS columns are the second job of the node_stage_kernel launch below
     const bool two_jobs = fused && act != nullptr;
     if (!act) {
         if (!fused)
-            hipLaunchKernelGGL(node_proj_kernel<false>, proj_grid(CHUNKS_ALL), dim3(256), 0, s, att, h, lig, P, n_nodes,
-                               (const int*)nullptr, (const int*)nullptr, CHUNKS_ALL);
+            hipLaunchKernelGGL(node_proj_kernel<false>, proj_grid(chunks_all), dim3(256), 0, s, att, h, lig, P, n_nodes,
+                               (const int*)nullptr, (const int*)nullptr, chunks_all);
     } else {
         if (!two_jobs) {     // without a source list the PS columns are produced for every node
             if (src)
@@ -1432,8 +1613,8 @@ hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig
                                    (const int*)nullptr, (const int*)nullptr, CHUNKS_PS);
         }
         if (!fused)
-            hipLaunchKernelGGL(node_proj_kernel<true>, proj_grid(CHUNKS_OWN), dim3(256), 0, s, att, h, lig, P, n_nodes, act, act_count,
-                               CHUNKS_OWN);
+            hipLaunchKernelGGL(node_proj_kernel<true>, proj_grid(chunks_own), dim3(256), 0, s, att, h, lig, P, n_nodes, act, act_count,
+                               chunks_own);
     }
     profile_mark_end(s);
     hipError_t e = hipGetLastError();
@@ -1445,7 +1626,11 @@ hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig
         add_node_stage_jobs(jobs, att, P, qbuf, Qt, act, act_count, src, src_count);
         launch_node_stage_grid(jobs, h, lig, n_nodes, s);
     } else {
-        hipLaunchKernelGGL(node_qmlp_kernel, dim3(grid, small ? 2 : 1), dim3(256), 0, s, att, P, qbuf, n_nodes, act, act_count);
+        if (direct)      // persistent 8-wave workgroups, one per CU on NQK_GRID of them
+            hipLaunchKernelGGL(node_query_kernel, dim3(min((n_nodes + NQK_ROWS - 1) / NQK_ROWS, NQK_GRID)), dim3(NQK_THREADS), 0, s, att, h,
+                               qbuf, n_nodes, act, act_count);
+        else
+            hipLaunchKernelGGL(node_qmlp_kernel, dim3(grid, small ? 2 : 1), dim3(256), 0, s, att, P, qbuf, n_nodes, act, act_count);
         if (fold)    // heads spread over four workgroups per row tile: the list is a fraction of the nodes, of unknown length
             hipLaunchKernelGGL(node_qfold_kernel<4>, dim3(grid, 4), dim3(256), 0, s, att, qbuf, Qt, n_nodes, fold, fold_count);
         else if (small)

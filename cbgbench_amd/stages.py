@@ -77,6 +77,21 @@ def classifier(packed, num_layers, num_classes, h):
     return logits
 
 
+def node_stage(packed, layer, x2h, h, lig_flag, rows=None, q_direct=False, fill=0.0):
+    """-> (P [N,640], q [N,128], Qt [N,16,128]) of one attention block's node stage (cbgx_node_stage).  ``rows`` (int32, on the
+    device): own columns, q and Qt for the listed rows only.  What the call does not write keeps ``fill``."""
+    N = h.shape[0]
+    P = torch.full((N, 640), fill, dtype=torch.float32, device=h.device)
+    q = torch.full((N, 128), fill, dtype=torch.float32, device=h.device)
+    Qt = torch.full((N, 16, 128), fill, dtype=torch.float32, device=h.device)
+    n_rows = None if rows is None else torch.tensor([rows.numel()], dtype=torch.int32, device=h.device)
+    rc = _native.lib().cbgx_node_stage(_native.ptr(packed), layer, int(bool(x2h)), _native.ptr(h), _native.ptr(lig_flag), N,
+                                       _native.ptr(rows), _native.ptr(n_rows), int(bool(q_direct)), _native.ptr(P),
+                                       _native.ptr(q), _native.ptr(Qt), _stream(h))
+    _native.check(rc, "cbgx_node_stage")
+    return P, q, Qt
+
+
 # ---- backward of single attention blocks (training; include/cbgx.h "training" section) ---------------------
 _MLP_SHAPES_X2H = [(128, 340), (128,), (128,), (128,), (128, 128), (128,)] * 2 + \
                   [(128, 128), (128,), (128,), (128,), (128, 128), (128,)]

@@ -176,6 +176,14 @@ int cbgx_h2x_attention(const float *packed, int layer, const float *x, const flo
                        const uint8_t *gen_flag, const float *e_w, int n_nodes,
                        float *x_out, float *delta_x, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The node stage of one attention block on its own (stage-level tests): P[N,640] = h Wn + bn (PDk | PDv | PSk | PSv | q hidden),
+ * q[N,128] = the query MLP and Qt[N,16,128] = the query folded into the key's second Linear, of denoiser.blocks[layer]'s x2h
+ * (x2h != 0) or h2x block.  `rows` / `n_rows` (DEVICE pointers, or both NULL): the own columns, q and Qt are produced for the rows
+ * rows[0 .. *n_rows) only, the PS columns for every row.  q_direct != 0: what the inference forward runs above 8192 rows -- q
+ * straight from h in one launch, the q-hidden columns P[:, 512:640) are NOT written; q_direct == 0: projection -> query MLP chain. */
+int cbgx_node_stage(const float *packed, int layer, int x2h, const float *h, const uint8_t *lig_flag, int n_nodes,
+                    const int32_t *rows, const int32_t *n_rows, int q_direct, float *P, float *q, float *Qt, void *stream);
+
 /* classifier head, unitransformer.py:46-51,119-120: Linear -> softplus - ln2 -> Linear. */
 int cbgx_classifier(const float *packed, int num_layers, int num_classes, const float *h, int n_nodes,
                     float *logits, void *workspace, size_t workspace_bytes, void *stream);
