@@ -81,6 +81,12 @@ EXPORTS = {
     "cbgx_profile_end": (_i, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i), _i]),
 }
 
+# what libcbgx_xcheck.so (TEST-ONLY, include/cbgx_xcheck.h) exports on top of EXPORTS
+XCHECK_EXPORTS = {
+    "cbgx_debug_set_edge_kernel": (_i, [_i]),
+    "cbgx_debug_gate_backward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _sz, _vp]),
+}
+
 PROFILE_CLASSES = ("knn", "gate", "node_gemm", "node_query", "edge_x2h", "edge_h2x", "edge_x2h_listed",
                    "edge_x2h_bwd", "edge_h2x_bwd", "train_gemm", "edge_x2h_bwd_listed", "edge_rows_reduce")
 
@@ -133,7 +139,7 @@ def first_generation_kernels(impl=1):
     if _XLIB is None:
         if not os.path.exists(XCHECK_LIBPATH):
             raise NativeError(f"{XCHECK_LIBPATH} not found: build it with `python -m cbgbench_amd.build`")
-        _XLIB = _load(XCHECK_LIBPATH, {"cbgx_debug_set_edge_kernel": (_i, [_i])})
+        _XLIB = _load(XCHECK_LIBPATH, XCHECK_EXPORTS)
     old = _XLIB.cbgx_debug_set_edge_kernel(impl)
     token = _OVERRIDE.set(_XLIB)
     try:

@@ -9,6 +9,9 @@
 #include <cstdlib>
 
 #include "../../include/cbgx.h"
+#ifdef CBGX_XCHECK
+#include "../../include/cbgx_xcheck.h"
+#endif
 #include "kernels.h"
 #include "layout.h"
 #include "train.h"
@@ -1152,5 +1155,24 @@ int cbgx_targetdiff_loss_backward(const float* grad_pos, const float* grad_logit
                                   grad_x_out, grad_logits, (hipStream_t)stream));
     return CBGX_OK;
 }
+
+#ifdef CBGX_XCHECK
+// test-only library (include/cbgx_xcheck.h): the gate backward as a stage of its own -- the static gate_backward above, the kernels
+// and reductions the training steps run, on a caller-supplied dL/de_w
+int cbgx_debug_gate_backward(const float* packed, const float* x, const int32_t* nbr, const int32_t* deg, int n_nodes,
+                             const float* de_w, const int* rows, const int* n_rows, float* const* grads, float* grad_x,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+    if (n_nodes <= 0) return set_error(CBGX_E_INVALID, "debug_gate_backward: bad sizes");
+    if (!packed || !x || !nbr || !deg || !de_w || !workspace || (rows != nullptr) != (n_rows != nullptr))
+        return set_error(CBGX_E_INVALID, "debug_gate_backward: NULL pointer");
+    RC_TRY(check_grads(grads, 6, "debug_gate_backward"));
+    TrainWs w = carve_train(workspace, n_nodes);
+    if (workspace_bytes < w.total)
+        return set_error(CBGX_E_WORKSPACE, "debug_gate_backward: workspace %zu < %zu", workspace_bytes, w.total);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(w.de_w, de_w, (size_t)n_nodes * KNN * 4, hipMemcpyDeviceToDevice, s));
+    return gate_backward(packed, x, nbr, deg, n_nodes, w, grads, s, rows, n_rows, grad_x);
+}
+#endif
 
 }  // extern "C"

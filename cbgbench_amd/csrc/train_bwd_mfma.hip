@@ -688,7 +688,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CBGX_QB_WAV
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int k = part + 16 * u;
-                const float nq = (v[u] - mean) * rstd * live;
+                // a select, not `* live`: a padding row reads row 0 of P, whose query columns nobody wrote when row 0 is not listed, and
+                // 0 * (NaN or Inf) in sNq would reach the gamma gradient through fmaf(dy = 0, sNq, aG)
+                const float nq = node >= 0 ? (v[u] - mean) * rstd : 0.f;
                 const float z = fmaxf(nq * att[A_LNQ_G + k] + att[A_LNQ_B + k], 0.f) * live;
                 sNq[r][k] = nq;
                 sZ[r][k] = z;

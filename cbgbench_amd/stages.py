@@ -104,20 +104,25 @@ def _train_ws(n, device):
     return torch.empty(_native.lib().cbgx_train_workspace_bytes(n), dtype=torch.uint8, device=device)
 
 
-def _grad_tensors(shapes, device):
+def _grad_tensors(shapes, device, fill=None):
     import ctypes
-    gs = [torch.empty(s, dtype=torch.float32, device=device) for s in shapes]
+    gs = [torch.empty(s, dtype=torch.float32, device=device) if fill is None else
+          torch.full(s, fill, dtype=torch.float32, device=device) for s in shapes]
     arr = (ctypes.c_void_p * len(gs))(*[g.data_ptr() for g in gs])
     return gs, arr
 
 
-def x2h_attention_backward(packed, layer, x, h, nbr, deg, lig_flag, e_w, grad_h_out):
-    """-> (grad_h, grad_x, grad_e_w, [18 parameter gradients: hk_func(6), hv_func(6), hq_func(6)])."""
+def _outputs(fill, *like):
+    return [torch.empty_like(t) if fill is None else torch.full_like(t, fill) for t in like]
+
+
+def x2h_attention_backward(packed, layer, x, h, nbr, deg, lig_flag, e_w, grad_h_out, ws=None, fill=None):
+    """-> (grad_h, grad_x, grad_e_w, [18 parameter gradients: hk_func(6), hv_func(6), hq_func(6)]).  ``ws`` (uint8, at least
+    cbgx_train_workspace_bytes(N)): the caller's workspace, used as it is; ``fill``: what every output holds before the call."""
     N = x.shape[0]
-    gh, gx = torch.empty_like(h), torch.empty_like(x)
-    gew = torch.empty_like(e_w)
-    grads, arr = _grad_tensors(_MLP_SHAPES_X2H, x.device)
-    ws = _train_ws(N, x.device)
+    gh, gx, gew = _outputs(fill, h, x, e_w)
+    grads, arr = _grad_tensors(_MLP_SHAPES_X2H, x.device, fill)
+    ws = _train_ws(N, x.device) if ws is None else ws
     rc = _native.lib().cbgx_x2h_attention_backward(
         _native.ptr(packed), layer, _native.ptr(x), _native.ptr(h), _native.ptr(nbr), _native.ptr(deg),
         _native.ptr(lig_flag), _native.ptr(e_w), N, _native.ptr(grad_h_out.contiguous()), _native.ptr(gh),
@@ -126,16 +131,37 @@ def x2h_attention_backward(packed, layer, x, h, nbr, deg, lig_flag, e_w, grad_h_
     return gh, gx, gew, grads
 
 
-def h2x_attention_backward(packed, layer, x, h, nbr, deg, lig_flag, gen_flag, e_w, grad_x_out):
-    """-> (grad_h, grad_x, grad_e_w, [18 parameter gradients: xk_func(6), xv_func(6), xq_func(6)])."""
+def h2x_attention_backward(packed, layer, x, h, nbr, deg, lig_flag, gen_flag, e_w, grad_x_out, ws=None, fill=None):
+    """-> (grad_h, grad_x, grad_e_w, [18 parameter gradients: xk_func(6), xv_func(6), xq_func(6)]).  ``ws`` / ``fill``: as in
+    x2h_attention_backward."""
     N = x.shape[0]
-    gh, gx = torch.empty_like(h), torch.empty_like(x)
-    gew = torch.empty_like(e_w)
-    grads, arr = _grad_tensors(_MLP_SHAPES_H2X, x.device)
-    ws = _train_ws(N, x.device)
+    gh, gx, gew = _outputs(fill, h, x, e_w)
+    grads, arr = _grad_tensors(_MLP_SHAPES_H2X, x.device, fill)
+    ws = _train_ws(N, x.device) if ws is None else ws
     rc = _native.lib().cbgx_h2x_attention_backward(
         _native.ptr(packed), layer, _native.ptr(x), _native.ptr(h), _native.ptr(nbr), _native.ptr(deg),
         _native.ptr(lig_flag), _native.ptr(gen_flag), _native.ptr(e_w), N, _native.ptr(grad_x_out.contiguous()),
         _native.ptr(gh), _native.ptr(gx), _native.ptr(gew), arr, _native.ptr(ws), ws.numel(), _stream(x))
     _native.check(rc, "cbgx_h2x_attention_backward")
     return gh, gx, gew, grads
+
+
+_MLP_SHAPES_GATE = [(160, 20), (160,), (160,), (160,), (1, 160), (1,)]
+
+
+def gate_backward(packed, x, nbr, deg, de_w, rows=None, grad_x=None, ws=None, fill=None):
+    """TEST-ONLY (libcbgx_xcheck.so, include/cbgx_xcheck.h: call inside ``_native.first_generation_kernels(0)``): the distance gate's
+    backward on ``de_w`` = dL/de_w [N,32] -> [6 gradients of dist_emb.1].  ``rows`` (int32, on the device): walk the listed nodes only;
+    ``grad_x`` [N,3]: the gate's coordinate gradient is ADDED to it."""
+    N = x.shape[0]
+    if not hasattr(_native.lib(), "cbgx_debug_gate_backward"):
+        raise _native.NativeError("gate_backward is test-only: libcbgx.so has no cbgx_debug_gate_backward; call it inside "
+                                  "_native.first_generation_kernels(0), which switches to libcbgx_xcheck.so")
+    grads, arr = _grad_tensors(_MLP_SHAPES_GATE, x.device, fill)
+    ws = _train_ws(N, x.device) if ws is None else ws
+    n_rows = None if rows is None else torch.tensor([rows.numel()], dtype=torch.int32, device=x.device)
+    rc = _native.lib().cbgx_debug_gate_backward(
+        _native.ptr(packed), _native.ptr(x), _native.ptr(nbr), _native.ptr(deg), N, _native.ptr(de_w.contiguous()), _native.ptr(rows),
+        _native.ptr(n_rows), arr, _native.ptr(grad_x), _native.ptr(ws), ws.numel(), _stream(x))
+    _native.check(rc, "cbgx_debug_gate_backward")
+    return grads

@@ -10,10 +10,8 @@ import pytest
 BX_WAVES, DYN = 8, 2
 
 
-def schedule(count, grid):
-    """-> (list of nodes per (workgroup, wave) in processing order for ONE interleaving of the dynamic grabs, set of dynamic nodes)"""
-    done, dyn = [], set()
-    ctr = [0] * 8
+def wave_state(count, grid):
+    """-> {(workgroup, wave): the wave's range and schedule} as edge_backward_x2h_kernel derives it from (count, gridDim.x)"""
     state = {}
     for wg, wave in itertools.product(range(grid), range(BX_WAVES)):
         if grid % 8 == 0:
@@ -32,6 +30,16 @@ def schedule(count, grid):
             tail_base = full * stride
             c = 0
         state[(wg, wave)] = dict(it=it, it_end=it_end, stride=stride, full=full, tail=tail_base, c=c, round=0, started=False)
+    return state
+
+
+def schedule(count, grid, boundaries=False):
+    """-> (list of nodes per (workgroup, wave) in processing order for ONE interleaving of the dynamic grabs, set of dynamic nodes);
+    ``boundaries``: also the sorted node indices in (0, count) at which a range of the partition ends or its dynamic tail begins"""
+    done, dyn = [], set()
+    ctr = [0] * 8
+    state = wave_state(count, grid)
+    cuts = sorted({b for w in state.values() for b in (w["it_end"], w["tail"]) if 0 < b < count})
     # run all waves round-robin (any interleaving hands out the same SET of dynamic nodes)
     active = list(state)
     while active:
@@ -59,7 +67,7 @@ def schedule(count, grid):
                 w["dynamic"] = True
             nxt.append(key)
         active = nxt
-    return done, dyn
+    return (done, dyn, cuts) if boundaries else (done, dyn)
 
 
 @pytest.mark.parametrize("grid", [1, 2, 7, 8, 16, 64, 200, 256])

@@ -177,14 +177,15 @@ def test_library_exports_every_declared_symbol():
     assert lib.cbgx_abi_version() == _native.ABI_VERSION == 6
     # the product library carries no debug switch and none of the first-generation kernels; the test-only build has both
     import subprocess
-    assert not hasattr(lib, "cbgx_debug_set_edge_kernel")
+    assert not hasattr(lib, "cbgx_debug_set_edge_kernel") and not hasattr(lib, "cbgx_debug_gate_backward")
     from cbgbench_amd.build import LIBPATH, XCHECK_LIBPATH
     sym = subprocess.run(["nm", "-D", "--defined-only", LIBPATH], capture_output=True, text=True).stdout
     assert "cbgx_debug" not in sym and "_v1" not in sym and "edge_attention_kernel" not in sym
     xhdr = open(os.path.join(ROOT, "include", "cbgx_xcheck.h")).read()
-    assert set(re.findall(r"\b(cbgx_[a-z0-9_]+)\s*\(", xhdr)) == {"cbgx_debug_set_edge_kernel"}
+    debug = {"cbgx_debug_set_edge_kernel", "cbgx_debug_gate_backward"}
+    assert set(re.findall(r"\b(cbgx_[a-z0-9_]+)\s*\(", xhdr)) == debug == set(_native.XCHECK_EXPORTS)
     xsym = subprocess.run(["nm", "-D", "--defined-only", XCHECK_LIBPATH], capture_output=True, text=True).stdout
-    for name in declared | {"cbgx_debug_set_edge_kernel"}:
+    for name in declared | debug:
         assert f" {name}\n" in xsym, name
 
 
