@@ -85,6 +85,7 @@ EXPORTS = {
 XCHECK_EXPORTS = {
     "cbgx_debug_set_edge_kernel": (_i, [_i]),
     "cbgx_debug_gate_backward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, ctypes.POINTER(_vp), _vp, _vp, _sz, _vp]),
+    "cbgx_debug_forward_view": (_i, [_vp, _i, ctypes.POINTER(_vp)]),
 }
 
 PROFILE_CLASSES = ("knn", "gate", "node_gemm", "node_query", "edge_x2h", "edge_h2x", "edge_x2h_listed",

@@ -197,6 +197,24 @@ int cbgx_debug_set_edge_kernel(int impl) {
     g_edge_impl = impl;
     return old;
 }
+
+// test-only library: where a forward call of n_nodes nodes keeps its graph stage and node lists (the same carve, no launch)
+int cbgx_debug_forward_view(void* workspace, int n_nodes, void** out) {
+    if (!workspace || !out || n_nodes < 1) return fail(CBGX_E_INVALID, "debug_forward_view: bad argument");
+    const Workspace w = carve(workspace, n_nodes);
+    int k = 0;
+    out[k++] = w.nbr; out[k++] = w.deg; out[k++] = w.e_w; out[k++] = w.d1flag; out[k++] = w.fD1;
+    auto list = [&](int* l, int* c) { out[k++] = l; out[k++] = c; };
+    list(w.act, w.act_count);
+    for (int r = 0; r < 3; ++r) list(w.rf_list[r], w.rf_count + 16 * r);
+    for (int r = 0; r < 4; ++r) list(w.fw_list[r], w.fw_count + 16 * r);      // D1, S1, D2, S2
+    for (int set = 0; set < 4; ++set) {
+        list(w.sp_list[set][1], w.sp_count + 32 * set);
+        list(w.sp_list[set][0], w.sp_count + 32 * set + 16);
+    }
+    static_assert(CBGX_FWD_VIEW_PTRS == 5 + 2 * 16, "cbgx_debug_forward_view: list count");
+    return k == CBGX_FWD_VIEW_PTRS ? CBGX_OK : fail(CBGX_E_INVALID, "debug_forward_view: %d pointers", k);
+}
 #endif
 
 int cbgx_set_edge_workgroups(int n) { return set_edge_workgroup_limit(n); }

@@ -92,6 +92,79 @@ def node_stage(packed, layer, x2h, h, lig_flag, rows=None, q_direct=False, fill=
     return P, q, Qt
 
 
+def unitransformer_forward(packed, num_layers, num_classes, x, h, graph_ptr, lig_flag, gen_flag, static=None, graph_part=True,
+                           want_h=True, h_on_sources=False, ws=None, fill=None):
+    """-> (x_out, h_out or None, logits): cbgx_unitransformer_forward, or with ``static`` (the tuple of
+    ``UniTransformer.static_context``) cbgx_unitransformer_forward_cached -- ``graph_part=False`` hands over the static features only.
+    ``want_h=False``: h_out is NULL; ``h_on_sources``: CBGX_FWD_H_ON_SOURCES.  ``ws`` (uint8, at least cbgx_workspace_bytes(N, B)): the
+    caller's workspace, used as it is; ``fill``: what every output holds before the call."""
+    N, B = x.shape[0], graph_ptr.numel() - 1
+    x_out, h_out = _outputs(fill, x, h)
+    logits = torch.empty(N, num_classes, dtype=torch.float32, device=x.device) if fill is None else \
+        torch.full((N, num_classes), fill, dtype=torch.float32, device=x.device)
+    if not want_h:
+        h_out = None
+    ws = torch.empty(_native.lib().cbgx_workspace_bytes(N, B), dtype=torch.uint8, device=x.device) if ws is None else ws
+    head = (_native.ptr(packed), num_layers, num_classes, _native.ptr(x), _native.ptr(h), _native.ptr(graph_ptr), _native.ptr(lig_flag),
+            _native.ptr(gen_flag), N, B)
+    tail = (_native.ptr(ws), ws.numel(), _stream(x))
+    if static is None:
+        if h_on_sources:
+            raise ValueError("unitransformer_forward: CBGX_FWD_H_ON_SOURCES is a flag of the cached entry point")
+        rc = _native.lib().cbgx_unitransformer_forward(*head, _native.ptr(x_out), _native.ptr(h_out), _native.ptr(logits), *tail)
+    else:
+        graph = [_native.ptr(t) if graph_part else None for t in static[2:6]]
+        rc = _native.lib().cbgx_unitransformer_forward_cached(*head, _native.ptr(static[0]), _native.ptr(static[1]), *graph,
+                                                              _native.ptr(x_out), _native.ptr(h_out), _native.ptr(logits),
+                                                              1 if h_on_sources else 0, *tail)
+    _native.check(rc, "cbgx_unitransformer_forward")
+    return x_out, h_out, logits
+
+
+def h2x_stack_forward(packed, num_layers, x, h, graph_ptr, lig_flag, gen_flag, ws=None, fill=None):
+    """-> x_out [N,3] of cbgx_h2x_stack_forward (``packed``: cbgx_pack_h2x_stack).  ``ws`` / ``fill``: as in unitransformer_forward;
+    the call leaves its graph stage (the gen_flag rows only) where ``forward_view`` finds nbr / deg / e_w."""
+    N, B = x.shape[0], graph_ptr.numel() - 1
+    x_out, = _outputs(fill, x)
+    ws = torch.empty(_native.lib().cbgx_workspace_bytes(N, B), dtype=torch.uint8, device=x.device) if ws is None else ws
+    rc = _native.lib().cbgx_h2x_stack_forward(_native.ptr(packed), num_layers, _native.ptr(x), _native.ptr(h), _native.ptr(graph_ptr),
+                                              _native.ptr(lig_flag), _native.ptr(gen_flag), N, B, _native.ptr(x_out), _native.ptr(ws),
+                                              ws.numel(), _stream(x))
+    _native.check(rc, "cbgx_h2x_stack_forward")
+    return x_out
+
+
+FORWARD_LISTS = ("act", "A1", "A2", "A3", "D1", "S1", "D2", "S2", "all_general", "all_protein", "D2_general", "D2_protein",
+                 "A1_general", "A1_protein", "A2_general", "A2_protein")
+
+
+def forward_view(ws, n_nodes):
+    """TEST-ONLY (libcbgx_xcheck.so, include/cbgx_xcheck.h: call inside ``_native.first_generation_kernels(0)``): what the last forward
+    call of ``n_nodes`` nodes on the workspace ``ws`` left there, as views into ``ws`` -- {"nbr" [N,32], "deg" [N], "e_w" [N,32],
+    "d1flag" [N], "D1flag" [N], "lists": {name of FORWARD_LISTS: (list [N] int32, count [1] int32)}}."""
+    import ctypes
+    if not hasattr(_native.lib(), "cbgx_debug_forward_view"):
+        raise _native.NativeError("forward_view is test-only: libcbgx.so has no cbgx_debug_forward_view; call it inside "
+                                  "_native.first_generation_kernels(0), which switches to libcbgx_xcheck.so")
+    out = (ctypes.c_void_p * (5 + 2 * len(FORWARD_LISTS)))()
+    _native.check(_native.lib().cbgx_debug_forward_view(_native.ptr(ws), n_nodes, out), "cbgx_debug_forward_view")
+    base = ws.data_ptr()
+
+    def at(k, count, dtype):
+        off = out[k] - base
+        nbytes = count * torch.empty(0, dtype=dtype).element_size()
+        if off < 0 or off + nbytes > ws.numel():
+            raise _native.NativeError(f"cbgx_debug_forward_view: pointer {k} outside the workspace")
+        return ws[off:off + nbytes].view(dtype)
+
+    N = n_nodes
+    view = {"nbr": at(0, N * 32, torch.int32).view(N, 32), "deg": at(1, N, torch.int32), "e_w": at(2, N * 32, torch.float32).view(N, 32),
+            "d1flag": at(3, N, torch.uint8), "D1flag": at(4, N, torch.uint8), "lists": {}}
+    for k, name in enumerate(FORWARD_LISTS):
+        view["lists"][name] = (at(5 + 2 * k, N, torch.int32), at(6 + 2 * k, 1, torch.int32))
+    return view
+
+
 # ---- backward of single attention blocks (training; include/cbgx.h "training" section) ---------------------
 _MLP_SHAPES_X2H = [(128, 340), (128,), (128,), (128,), (128, 128), (128,)] * 2 + \
                   [(128, 128), (128,), (128,), (128,), (128, 128), (128,)]

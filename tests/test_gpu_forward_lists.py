@@ -1,0 +1,280 @@
+"""The inference forward on a poisoned workspace, its device-built node lists and its (cached) kNN graph at ties.
+
+Every forward call of this file gets a FRESH workspace filled with 0xFF bytes (NaN as float, -1 as int: the fill of
+tests/test_gpu_backward_boundaries.py) and outputs pre-filled with NaN -- a production caller hands in torch.empty memory, while
+every older comparison of two forward variants ran them back to back on one cached workspace, where a row the second variant
+fails to produce still holds the first one's (right) value.  Inputs are the integer-lattice batches of tests/lattice.py (pinned by
+tests/test_lattice_inputs.py): most centres have an exact tie between rank 32 and rank 33, some between a protein and a ligand
+atom, some protein atoms have their nearest ligand atom at exactly the cached 32nd distance, some atoms coincide.  The batches
+cover the per-graph list kernel / node_stage_kernel / knn_merge_gate_kernel (<= 8192 nodes, the threshold itself included) and the
+level kernels / knn_merge_kernel + newmask gate / node_query_kernel / auxiliary stream (8193 nodes and a little more).
+
+The lists and the graph stage are read through cbgx_debug_forward_view of the test-only library (include/cbgx_xcheck.h), which only
+carves the workspace as the forward does; the forward calls themselves run in the product library."""
+import hashlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import cbgbench_amd as C
+from cbgbench_amd import _native, stages
+from oracle import unitransformer as OU
+from tests import lattice
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+RTOL, ATOL = 1e-4, 1e-5          # the forward tolerance of tests/test_gpu_parity.py
+BATCHES = ["small", "context", "at_threshold", "above_threshold", "large"]
+NAN = float("nan")
+
+
+@pytest.fixture(scope="module")
+def model(synthetic_sd):
+    m = C.get_model(C.default_targetdiff_config(13)).eval()
+    m.load_state_dict(synthetic_sd, strict=True)
+    return m.to(DEV)
+
+
+def poisoned_workspace(n_nodes, n_graphs):
+    return torch.full((int(_native.lib().cbgx_workspace_bytes(n_nodes, n_graphs)),), 0xFF, dtype=torch.uint8, device=DEV)
+
+
+_DEV_CACHE = {}
+
+
+def on_device(model, name):
+    """the lattice batch `name` on the device, with the embedders' features and the static context of its raw protein rows (made once,
+    shared by the tests, left unchanged)"""
+    if name in _DEV_CACHE:
+        return _DEV_CACHE[name]
+    b = lattice.batch(name)
+    den = model.denoiser
+    x = b["x"].to(DEV)
+    lig, gen = b["lig_flag"].to(DEV), b["gen_flag"].to(DEV)
+    N, B = x.shape[0], len(b["sizes"])
+    with torch.no_grad():
+        h = torch.empty(N, 128, dtype=torch.float32, device=DEV)
+        aa = torch.nn.functional.one_hot(b["protein_aa"].to(DEV), 20).float()
+        h[~lig] = model.context_embedder.embed_protein(b["protein_feat"].to(DEV), aa)
+        h[lig] = model.context_embedder.embed_ligand(torch.nn.functional.one_hot(b["ligand_type"].to(DEV), 13).float())
+        rec_rows = torch.nonzero(~lig).flatten()
+        gp_rec = torch.tensor(np.concatenate([[0], np.cumsum([p for p, _ in b["sizes"]])]), dtype=torch.int32, device=DEV)
+        den.workspace(rec_rows.numel(), B, torch.device(DEV)).fill_(0xFF)      # static_context works in the module's own workspace
+        static = den.static_context(x[rec_rows].contiguous(), h[rec_rows].contiguous(), None, rec_rows, N, graph_ptr_rec=gp_rec)
+    d = {"b": b, "N": N, "B": B, "x": x, "h": h, "gp": b["graph_ptr"].to(DEV), "lig": lig.to(torch.uint8), "gen": gen.to(torch.uint8),
+         "static": static, "packed": den.packed_weights(torch.device(DEV)), "L": den.num_layers, "C": den.out_classes}
+    _DEV_CACHE[name] = d
+    return d
+
+
+VARIANTS = {     # name -> keyword arguments of stages.unitransformer_forward
+    "plain": dict(cached=None),
+    "pruned": dict(cached=None, want_h=False),
+    "h_on_sources": dict(cached="graph", h_on_sources=True),
+    "cached_static": dict(cached="static"),
+    "cached_graph": dict(cached="graph"),
+    "cached_graph_pruned": dict(cached="graph", want_h=False),
+}
+
+
+def run(d, variant):
+    """one forward call on a fresh poisoned workspace and NaN outputs -> (x_out, h_out, logits, workspace)"""
+    kw = dict(VARIANTS[variant])
+    cached = kw.pop("cached")
+    ws = poisoned_workspace(d["N"], d["B"])
+    out = stages.unitransformer_forward(d["packed"], d["L"], d["C"], d["x"], d["h"], d["gp"], d["lig"], d["gen"],
+                                        static=None if cached is None else d["static"], graph_part=cached == "graph", ws=ws, fill=NAN, **kw)
+    return out + (ws,)
+
+
+def view_of(ws, n):
+    with _native.first_generation_kernels(0):
+        return stages.forward_view(ws, n)
+
+
+# ---- variant identity on poison --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", BATCHES)
+def test_forward_variants_agree_bit_for_bit_on_poisoned_memory(model, name):
+    d = on_device(model, name)
+    lig, gen = d["lig"].bool(), d["gen"].bool()
+    a1 = torch.zeros(d["N"], dtype=torch.bool, device=DEV)
+    a1[torch.from_numpy(lattice.list_definitions(d["b"])["A1"]).long().to(DEV)] = True
+    assert bool(a1[lig].all()) and 0 < int(a1.sum()) < d["N"]
+    xo, ho, lo, _ = run(d, "plain")
+    assert bool(torch.isfinite(xo).all()) and bool(torch.isfinite(ho).all()) and bool(torch.isfinite(lo).all()), "plain"
+    assert torch.equal(xo[~gen], d["x"][~gen]) and bool((xo[gen] != d["x"][gen]).any())
+    for variant in list(VARIANTS)[1:]:
+        x2, h2, l2, _ = run(d, variant)
+        assert torch.equal(x2, xo), f"x_out: {variant} differs from plain on {int((x2 != xo).any(1).sum())} rows"
+        assert torch.equal(l2[lig], lo[lig]), f"ligand logits: {variant} differs from plain on {int((l2[lig] != lo[lig]).any(1).sum())} rows"
+        if variant in ("cached_static", "cached_graph"):
+            assert torch.equal(h2, ho), f"h_out: {variant} differs from plain on {int((h2 != ho).any(1).sum())} rows"
+            assert torch.equal(l2, lo), f"logits: {variant}"
+        elif variant == "h_on_sources":
+            assert torch.equal(h2[a1], ho[a1]), f"h_out on A1: {variant} differs on {int((h2[a1] != ho[a1]).any(1).sum())} rows"
+            assert bool(torch.isnan(h2[~a1]).all()), "rows of h_out outside A1 are declared unwritten (include/cbgx.h)"
+        else:
+            assert h2 is None
+
+
+ORACLE_GRAPHS = [0, 1, 3, 8, 13]      # (20,5) (33,40) (300,64) (501,12) (0,6): 981 nodes -- graphs are independent and the oracle's
+                                      # time is linear in the nodes, so five graphs of the batch are as good as all fourteen
+
+
+@pytest.mark.parametrize("name", ["small", "context"])
+def test_plain_forward_on_ties_against_the_oracle(model, synthetic_sd, name):
+    """the plain call on poisoned memory against the CPU oracle at the tolerance of tests/test_gpu_parity.py (1e-4 relative + 1e-5
+    absolute), identical ligand argmax.  Measured on an MI355X, worst err / tolerance on x_out, h_out, logits: 0.017, 0.099, 0.091
+    (all generated) and 0.013, 0.109, 0.087 (partial gen_flag); max abs err 1.9e-6 -- the ties cost nothing."""
+    d = on_device(model, name)
+    xo, ho, lo, _ = run(d, "plain")
+    gp = d["b"]["graph_ptr"].tolist()
+    rows = torch.cat([torch.arange(gp[g], gp[g + 1]) for g in ORACLE_GRAPHS])
+    bi = torch.cat([torch.full((gp[g + 1] - gp[g],), k, dtype=torch.long) for k, g in enumerate(ORACLE_GRAPHS)])
+    b = d["b"]
+    rx, rh, rl = OU.unitransformer_forward(synthetic_sd, b["x"][rows], d["h"].cpu()[rows], bi, b["lig_flag"][rows], b["gen_flag"][rows])
+    worst = {}
+    for what, got, ref in (("x_out", xo, rx), ("h_out", ho, rh), ("logits", lo, rl)):
+        got, ref = got.cpu()[rows].double(), ref.double()
+        ratio = ((got - ref).abs() / (ATOL + RTOL * ref.abs())).max()
+        worst[what] = float(ratio)
+        print(f"MEASURED {name} {what}: worst err / tolerance {float(ratio):.4f}, max abs err {float((got - ref).abs().max()):.3e}")
+    assert all(v <= 1.0 for v in worst.values()), worst
+    lig = b["lig_flag"][rows]
+    assert torch.equal(lo.cpu()[rows][lig].argmax(-1), rl[lig].argmax(-1))
+
+
+# ---- graph stage, read through the view ------------------------------------------------------------------------------------
+def check_graph_stage(d, nbr, deg, e_w, rows=None, packed=None, what=""):
+    """nbr / deg against the oracle's knn_graph with -1 padding, e_w bit-equal to cbgx_edge_gate on those lists with 0 in padded slots
+    (`rows`: on these rows only)"""
+    ref = lattice.reference(d["b"])
+    rows = np.arange(d["N"]) if rows is None else rows
+    nbr, deg = nbr.cpu().numpy(), deg.cpu().numpy()
+    bad = np.nonzero((nbr[rows] != ref["nbr"][rows]).any(1) | (deg[rows] != ref["deg"][rows]))[0]
+    assert bad.size == 0, f"{what}: neighbour list / degree differ from the oracle on {bad.size} rows, first {rows[bad[:5]]}"
+    pad = np.arange(32)[None, :] >= ref["deg"][rows][:, None]
+    assert (nbr[rows][pad] == -1).all(), what
+    gate = stages.edge_gate(d["packed"] if packed is None else packed, d["x"], torch.from_numpy(ref["nbr"]).to(DEV),
+                            torch.from_numpy(ref["deg"]).to(DEV)).cpu().numpy()
+    e_w = e_w.cpu().numpy()
+    assert (gate[rows][pad] == 0).all() and (e_w[rows][pad] == 0).all(), what
+    diff = np.nonzero((e_w[rows].view(np.uint32) != gate[rows].view(np.uint32)).any(1))[0]
+    assert diff.size == 0, f"{what}: e_w differs from cbgx_edge_gate on {diff.size} rows, first {rows[diff[:5]]}"
+
+
+@pytest.mark.parametrize("name", BATCHES)
+def test_graph_stage_at_ties_equals_the_oracle(model, name):
+    d = on_device(model, name)
+    nbr, deg = stages.knn_graph(d["x"], d["gp"])
+    check_graph_stage(d, nbr, deg, stages.edge_gate(d["packed"], d["x"], nbr, deg), what="stages.knn_graph")
+    ei = stages.edge_index_from_nbr(nbr, deg).cpu()
+    assert torch.equal(ei, lattice.reference(d["b"])["edge_index"])
+    for variant in ("cached_graph", "plain", "cached_static"):
+        ws = run(d, variant)[3]
+        v = view_of(ws, d["N"])
+        check_graph_stage(d, v["nbr"], v["deg"], v["e_w"], what=variant)
+
+
+@pytest.fixture(scope="module")
+def com_head():
+    torch.manual_seed(5)
+    return C.get_model(C.default_diffbp_config(13)).eval().to(DEV).com_head
+
+
+@pytest.mark.parametrize("name", ["small", "context", "large"])
+def test_listed_rows_search_of_the_h2x_stack_at_ties(model, com_head, name):
+    """cbgx_h2x_stack_forward searches and gates the gen_flag rows only: those rows of its graph stage against the oracle"""
+    d = on_device(model, name)
+    packed = com_head.packed_weights(torch.device(DEV))
+    ws = poisoned_workspace(d["N"], d["B"])
+    xo = stages.h2x_stack_forward(packed, com_head.num_layers, d["x"], d["h"], d["gp"], d["lig"], d["gen"], ws=ws, fill=NAN)
+    gen = d["gen"].bool()
+    assert bool(torch.isfinite(xo).all()) and torch.equal(xo[~gen], d["x"][~gen])
+    v = view_of(ws, d["N"])
+    check_graph_stage(d, v["nbr"], v["deg"], v["e_w"], rows=np.nonzero(d["b"]["gen_flag"].numpy())[0], packed=packed, what="h2x stack")
+
+
+def digest(*tensors):
+    return " ".join(hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()[:16] for t in tensors)
+
+
+_MERGE_PROBE = r"""
+import hashlib, sys, numpy as np, torch
+import cbgbench_amd as C
+from cbgbench_amd import _native, stages
+from oracle import weights as W
+from tests import lattice
+m = C.get_model(C.default_targetdiff_config(13)).eval()
+m.load_state_dict(W.synthetic_state_dict(13, 9, seed=0), strict=True)
+m = m.to("cuda:0")
+den, dev = m.denoiser, torch.device("cuda:0")
+out = []
+for name in ("small", "large"):
+    b = lattice.batch(name)
+    x, lig, gen = b["x"].to(dev), b["lig_flag"].to(dev), b["gen_flag"].to(dev)
+    N, B = x.shape[0], len(b["sizes"])
+    h = torch.randn(N, 128, generator=torch.Generator().manual_seed(1)).to(dev)     # (the graph stage does not read h)
+    rec = torch.nonzero(~lig).flatten()
+    gp_rec = torch.tensor(np.concatenate([[0], np.cumsum([p for p, _ in b["sizes"]])]), dtype=torch.int32, device=dev)
+    static = den.static_context(x[rec].contiguous(), h[rec].contiguous(), None, rec, N, graph_ptr_rec=gp_rec)
+    ws = torch.full((int(_native.lib().cbgx_workspace_bytes(N, B)),), 0xFF, dtype=torch.uint8, device=dev)
+    stages.unitransformer_forward(den.packed_weights(dev), den.num_layers, den.out_classes, x, h, b["graph_ptr"].to(dev), lig.to(torch.uint8),
+                                  gen.to(torch.uint8), static=static, ws=ws, fill=float("nan"))
+    torch.cuda.synchronize()
+    with _native.first_generation_kernels(0):
+        v = stages.forward_view(ws, N)
+    for t in (v["nbr"], v["deg"], v["e_w"]):
+        out.append(hashlib.sha256(t.cpu().contiguous().numpy().tobytes()).hexdigest()[:16])
+print("PROBE " + " ".join(out))
+"""
+
+
+def test_merge_without_the_fused_gate_gives_the_same_graph_stage(model):
+    """CBGX_MERGE_GATE=0 (knn_merge_kernel + the gate on every slot) is read once per process: one child runs a graph-cached call on the
+    small and the large batch and prints digests of nbr / deg / e_w, compared with this process's (knn_merge_gate_kernel below 8193
+    nodes, knn_merge_kernel + newmask gate above)."""
+    mine = []
+    for name in ("small", "large"):
+        d = on_device(model, name)
+        v = view_of(run(d, "cached_graph")[3], d["N"])
+        mine.append(digest(v["nbr"], v["deg"], v["e_w"]))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", _MERGE_PROBE], capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, CBGX_MERGE_GATE="0"), cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    theirs = [ln for ln in r.stdout.splitlines() if ln.startswith("PROBE ")][-1]
+    assert theirs == "PROBE " + " ".join(mine)
+
+
+# ---- the node lists --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("variant", ["cached_graph_pruned", "plain"])
+@pytest.mark.parametrize("name", BATCHES)
+def test_every_node_list_equals_its_definition(model, name, variant):
+    """each list the call builds, as a sorted set, against its definition on the oracle's edge list (tests/lattice.py
+    list_definitions); its count is its length, no node twice; a list the call does not need has count 0.  A list that is a superset of
+    its definition changes no output and would only cost time -- this is the one place it shows."""
+    d = on_device(model, name)
+    cached = variant == "cached_graph_pruned"
+    defs = lattice.list_definitions(d["b"], prune=cached, cached=cached)
+    v = view_of(run(d, variant)[3], d["N"])
+    assert np.array_equal(v["d1flag"].cpu().numpy(), defs["d1flag"]), "d1flag"
+    if cached:
+        assert np.array_equal(v["D1flag"].cpu().numpy(), defs["d1flag"]), "D1 (proximity test) against d1 (from the merged lists)"
+    wrong = []
+    for lname in stages.FORWARD_LISTS:
+        lst, cnt = v["lists"][lname]
+        cnt = int(cnt.item())
+        assert 0 <= cnt <= d["N"], (lname, cnt)
+        got = np.sort(lst[:cnt].cpu().numpy())
+        want = defs[lname]
+        if got.size > 1 and (got[1:] == got[:-1]).any():
+            wrong.append(f"{lname}: a node is listed twice")
+        elif not np.array_equal(got, want):
+            wrong.append(f"{lname}: {cnt} listed, {want.size} by definition, {np.setdiff1d(got, want).size} too many, "
+                         f"{np.setdiff1d(want, got).size} missing")
+    assert not wrong, wrong

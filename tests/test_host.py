@@ -182,7 +182,8 @@ def test_library_exports_every_declared_symbol():
     sym = subprocess.run(["nm", "-D", "--defined-only", LIBPATH], capture_output=True, text=True).stdout
     assert "cbgx_debug" not in sym and "_v1" not in sym and "edge_attention_kernel" not in sym
     xhdr = open(os.path.join(ROOT, "include", "cbgx_xcheck.h")).read()
-    debug = {"cbgx_debug_set_edge_kernel", "cbgx_debug_gate_backward"}
+    assert not hasattr(lib, "cbgx_debug_forward_view")
+    debug = {"cbgx_debug_set_edge_kernel", "cbgx_debug_gate_backward", "cbgx_debug_forward_view"}
     assert set(re.findall(r"\b(cbgx_[a-z0-9_]+)\s*\(", xhdr)) == debug == set(_native.XCHECK_EXPORTS)
     xsym = subprocess.run(["nm", "-D", "--defined-only", XCHECK_LIBPATH], capture_output=True, text=True).stdout
     for name in declared | debug:
