@@ -14,21 +14,14 @@
 #endif
 #include "kernels.h"
 #include "layout.h"
+#include "workspace.h"
 
 using namespace cbgx;
 
 static thread_local char g_err[512] = "";
 
-static int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 namespace cbgx {
-// same thread-local message for the entry points that live in other translation units (api_train.hip)
+// the thread-local message of cbgx_last_error, also for the entry points that live in other translation units (api_train.hip)
 int set_error(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -37,6 +30,7 @@ int set_error(int code, const char* fmt, ...) {
     return code;
 }
 }  // namespace cbgx
+static constexpr auto& fail = cbgx::set_error;
 
 #define HIP_TRY(expr)                                                                          \
     do {                                                                                       \
@@ -44,91 +38,78 @@ int set_error(int code, const char* fmt, ...) {
         if (_e != hipSuccess) return fail(CBGX_E_HIP, "%s: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
 
-static inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
+struct NodeBufs { float *P, *q, *Qt; };   // of one attention block's node stage: projection, query, folded query
 struct Workspace {
-    int32_t* nbr;
-    int32_t* deg;
+    int32_t *nbr, *deg;
     float* e_w;
-    float* P;
-    float* Qt;
-    float* q;
-    float* P2;       // second / third node-stage buffer sets: the x2h node stage of layer l+1 runs on an auxiliary
-    float* Qt2;      // stream while the h2x block of layer l runs on the caller's stream
-    float* q2;
-    float* P3;
-    float* Qt3;
-    float* q3;
-    int* act;        // indices of gen_flag nodes (h2x work list)
-    int* act_count;
-    int* rf_list[3]; // receptive-field pruning: A1, A2, A3
-    int* rf_count;   // [3], 64 B apart
-    int* fw_list[4];     // static-context cache: D1, S1 = D1 | nbr(D1), D2, S2
-    int* fw_count;       // [4], 64 B apart
-    // per-node flags behind the lists (node_mfma.hip, list_level_kernel), zeroed with the counters by ONE fill per forward call:
+    // three node-stage buffer sets: the x2h blocks alternate between 0 and 1 (the node stage of layer l + 1 runs before layer l is
+    // over: next to its h2x block on an auxiliary stream, or in one launch with that block's node stage), the h2x blocks use 2
+    NodeBufs set[3];
+    // The sixteen node lists of a forward call, in the order of stages.FORWARD_LISTS / include/cbgx_xcheck.h:
+    NodeList act;                 // gen_flag nodes (h2x work list)
+    NodeList A1, A2, A3;          // receptive-field pruning
+    NodeList D1, S1, D2, S2;      // static-context cache: D_k differs from the ligand-free pocket in layer k - 1, S_k = D_k | nbr(D_k)
+    // x2h layers run as ONE launch over two work lists (edge_mfma.hip, edge_x2h_dual_kernel): destinations with a ligand atom among
+    // themselves and their neighbours (d1flag; general role, folded query from Qt) and protein-only ones (query folded in registers).
+    // The (general, protein-only) split of: all nodes | the cached layer 1 (D2) | the pruned layers (A1, A2)
+    NodeList all_gen, all_pp, D2_gen, D2_pp, A1_gen, A1_pp, A2_gen, A2_pp;
+    NodeList empty;               // always empty: a count nothing writes after the call's fill
+    // per-node flags behind the lists (node_mfma.hip, list_level_kernel), zeroed with the counts by ONE fill per forward call:
     // receptive-field sets a1 a2 a3; "differs from the ligand-free pocket" D1 (proximity flags of the graph cache) D2 S1 S2; d1flag
     uint8_t *fa1, *fa2, *fa3, *fD1, *fD2, *fS1, *fS2;
-    float* hbuf[2];
-    float* xbuf[2];
-    // x2h layers run as ONE launch over two work lists (edge_mfma.hip, edge_x2h_dual_kernel): destinations with a ligand atom among
-    // themselves and their neighbours (d1flag; general role, folded query from Qt) and protein-only ones (query folded in registers)
     uint8_t* d1flag;     // the node or one of its neighbours is a ligand atom: general role of the x2h edge stage
-    int* sp_list[4][2];  // [all nodes | cached layer 1 (D2) | pruned A1 | pruned A2][1 = general, 0 = protein-only]
-    int* sp_count;       // per set one 128-byte region: general count at +0, protein-only count at +64 bytes
-    int* zero_count;     // an always-empty list's count
+    float *hbuf[2], *xbuf[2];
     unsigned* newmask;   // graph-cached calls: per listed centre, the ranks of its merged neighbour list that hold new entries
-    void* counters;      // flags + act_count, rf_count, fw_count, sp_count, zero_count are carved from ONE block: one fill per call
-    size_t counters_bytes;
-    size_t total;
+    void* counters;      // the flags and every list count are carved from ONE block: one fill per call
+    size_t counters_bytes, total;
 };
 
+// The only place that knows where a list's count lives (nothing else adds a literal to a count pointer).
 static Workspace carve(void* base, int n) {
     Workspace w;
-    size_t off = 0;
-    char* b = (char*)base;
-    auto take = [&](size_t bytes) { char* p = b + off; off += align_up(bytes); return p; };
+    Carver c(base);
     size_t N = (size_t)(n > 0 ? n : 1);
-    w.nbr = (int32_t*)take(N * KNN * 4);
-    w.deg = (int32_t*)take(N * 4);
-    w.e_w = (float*)take(N * KNN * 4);
-    w.P = (float*)take(N * PROW * 4);
-    w.Qt = (float*)take(N * HEADS * H * 4);
-    w.q = (float*)take(N * H * 4);
-    w.P2 = (float*)take(N * PROW * 4);
-    w.Qt2 = (float*)take(N * HEADS * H * 4);
-    w.q2 = (float*)take(N * H * 4);
-    w.P3 = (float*)take(N * PROW * 4);
-    w.Qt3 = (float*)take(N * HEADS * H * 4);
-    w.q3 = (float*)take(N * H * 4);
-    w.act = (int*)take(N * 4);
-    w.act_count = nullptr;       // (carved from the counter block below)
-    for (int k = 0; k < 3; ++k) w.rf_list[k] = (int*)take(N * 4);
-    w.rf_count = nullptr;
-    for (int k = 0; k < 4; ++k) w.fw_list[k] = (int*)take(N * 4);
-    w.fw_count = nullptr;
-    w.hbuf[0] = (float*)take(N * H * 4);
-    w.hbuf[1] = (float*)take(N * H * 4);
-    w.xbuf[0] = (float*)take(N * 3 * 4);
-    w.xbuf[1] = (float*)take(N * 3 * 4);
-    for (int k = 0; k < 4; ++k) { w.sp_list[k][1] = (int*)take(N * 4); w.sp_list[k][0] = (int*)take(N * 4); }
-    w.newmask = (unsigned*)take(N * 4);
-    {
-        // every device-side list count of a forward call, 64 bytes apart (a counter word is hammered by returning atomics)
-        const size_t fl = align_up(N);
-        w.counters_bytes = 8 * fl + 256 + 256 + 256 + 4 * 128 + 256;
-        char* c = take(w.counters_bytes);
-        w.counters = c;
-        w.d1flag = (uint8_t*)c; w.fa1 = w.d1flag + fl; w.fa2 = w.fa1 + fl; w.fa3 = w.fa2 + fl;
-        w.fD1 = w.fa3 + fl; w.fD2 = w.fD1 + fl; w.fS1 = w.fD2 + fl; w.fS2 = w.fS1 + fl;
-        c += 8 * fl;
-        w.act_count = (int*)c;
-        w.rf_count = (int*)(c + 256);
-        w.fw_count = (int*)(c + 512);
-        w.sp_count = (int*)(c + 768);
-        w.zero_count = (int*)(c + 768 + 4 * 128);
+    w.nbr = c.take<int32_t>(N * KNN * 4);
+    w.deg = c.take<int32_t>(N * 4);
+    w.e_w = c.take<float>(N * KNN * 4);
+    for (NodeBufs& b : w.set) {
+        b.P = c.take<float>(N * PROW * 4);
+        b.Qt = c.take<float>(N * HEADS * H * 4);
+        b.q = c.take<float>(N * H * 4);
     }
-    w.total = off;
+    for (NodeList* l : {&w.act, &w.A1, &w.A2, &w.A3, &w.D1, &w.S1, &w.D2, &w.S2}) l->rows = c.take<int>(N * 4);
+    for (float*& h : w.hbuf) h = c.take<float>(N * H * 4);
+    for (float*& x : w.xbuf) x = c.take<float>(N * 3 * 4);
+    for (NodeList* l : {&w.all_gen, &w.all_pp, &w.D2_gen, &w.D2_pp, &w.A1_gen, &w.A1_pp, &w.A2_gen, &w.A2_pp})
+        l->rows = c.take<int>(N * 4);
+    w.empty.rows = w.all_pp.rows;      // (never read: its count is zero)
+    w.newmask = c.take<unsigned>(N * 4);
+    // eight flag arrays, then every list count of a forward call, 64 bytes apart (a counter word is hammered by returning
+    // atomics): 256 bytes for act, 256 for A1 - A3, 256 for D1 - S2, 128 per (general, protein-only) pair, 256 for the empty list
+    const size_t fl = align_up(N);
+    w.counters_bytes = 8 * fl + 256 + 256 + 256 + 4 * 128 + 256;
+    uint8_t* f = c.take<uint8_t>(w.counters_bytes);
+    w.counters = f;
+    w.d1flag = f; w.fa1 = w.d1flag + fl; w.fa2 = w.fa1 + fl; w.fa3 = w.fa2 + fl;
+    w.fD1 = w.fa3 + fl; w.fD2 = w.fD1 + fl; w.fS1 = w.fD2 + fl; w.fS2 = w.fS1 + fl;
+    auto counts = [&](size_t region, std::initializer_list<NodeList*> lists) {
+        int k = 0;
+        for (NodeList* l : lists) l->count = (int*)(f + 8 * fl + region + 64 * k++);
+    };
+    counts(0, {&w.act});
+    counts(256, {&w.A1, &w.A2, &w.A3});
+    counts(512, {&w.D1, &w.S1, &w.D2, &w.S2});
+    counts(768, {&w.all_gen, &w.all_pp, &w.D2_gen, &w.D2_pp, &w.A1_gen, &w.A1_pp, &w.A2_gen, &w.A2_pp});
+    counts(768 + 4 * 128, {&w.empty});
+    w.total = c.off;
     return w;
+}
+
+// carve + size check of the entry points that take a forward workspace
+static int carve_checked(const char* who, void* workspace, size_t workspace_bytes, int n_nodes, Workspace& w) {
+    w = carve(workspace, n_nodes);
+    if (workspace_bytes < w.total) return fail(CBGX_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, w.total);
+    return CBGX_OK;
 }
 
 // Auxiliary streams: one per (host thread, caller stream), created on first use, with the two events that fork it from and join it
@@ -204,14 +185,10 @@ int cbgx_debug_forward_view(void* workspace, int n_nodes, void** out) {
     const Workspace w = carve(workspace, n_nodes);
     int k = 0;
     out[k++] = w.nbr; out[k++] = w.deg; out[k++] = w.e_w; out[k++] = w.d1flag; out[k++] = w.fD1;
-    auto list = [&](int* l, int* c) { out[k++] = l; out[k++] = c; };
-    list(w.act, w.act_count);
-    for (int r = 0; r < 3; ++r) list(w.rf_list[r], w.rf_count + 16 * r);
-    for (int r = 0; r < 4; ++r) list(w.fw_list[r], w.fw_count + 16 * r);      // D1, S1, D2, S2
-    for (int set = 0; set < 4; ++set) {
-        list(w.sp_list[set][1], w.sp_count + 32 * set);
-        list(w.sp_list[set][0], w.sp_count + 32 * set + 16);
-    }
+    const NodeList lists[] = {w.act,     w.A1,     w.A2,     w.A3,    w.D1,     w.S1,    w.D2,     w.S2,
+                              w.all_gen, w.all_pp, w.D2_gen, w.D2_pp, w.A1_gen, w.A1_pp, w.A2_gen, w.A2_pp};
+    for (const NodeList& l : lists) { out[k++] = l.rows; out[k++] = l.count; }
+    static_assert(sizeof(lists) / sizeof(lists[0]) == CBGX_FWD_VIEW_LISTS, "cbgx_debug_forward_view: list count");
     static_assert(CBGX_FWD_VIEW_PTRS == 5 + 2 * 16, "cbgx_debug_forward_view: list count");
     return k == CBGX_FWD_VIEW_PTRS ? CBGX_OK : fail(CBGX_E_INVALID, "debug_forward_view: %d pointers", k);
 }
@@ -406,11 +383,10 @@ int cbgx_h2x_stack_forward(const float* packed, int num_layers, const float* x, 
     if (n_nodes == 0) return CBGX_OK;
     if (!packed || !x || !h || !graph_ptr || !lig_flag || !gen_flag || !x_out || !workspace)
         return fail(CBGX_E_INVALID, "h2x_stack: NULL pointer");
-    Workspace w = carve(workspace, n_nodes);
-    if (workspace_bytes < w.total)
-        return fail(CBGX_E_WORKSPACE, "h2x_stack: workspace %zu < %zu", workspace_bytes, w.total);
+    Workspace w;
+    if (int rc = carve_checked("h2x_stack", workspace, workspace_bytes, n_nodes, w)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act, w.act_count, s));
+    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act.rows, w.act.count, s));
     if (g_edge_impl == 1) {
         HIP_TRY(launch_knn(x, graph_ptr, n_graphs, n_nodes, w.nbr, w.deg, s));
         HIP_TRY(launch_gate(packed, x, w.nbr, w.deg, n_nodes, w.e_w, s));
@@ -419,24 +395,25 @@ int cbgx_h2x_stack_forward(const float* packed, int num_layers, const float* x, 
         // both run over the gen_flag list), and the stack's graph is built once from the input coordinates (diffbp.py:84-93): the
         // kNN search and the gate MLP run on the listed rows only -- the ligand atoms, ~5 % of a pocket -- instead of on every node
         // (DiffBP paid 415 + 276 us per step for them at 200 graphs, against 163 + 112 us for the denoiser's cached graph).
-        HIP_TRY(launch_knn_reg(x, graph_ptr, n_graphs, n_nodes, w.nbr, w.deg, s, w.act, w.act_count));
-        HIP_TRY(launch_gate_mfma(packed, x, w.nbr, w.deg, n_nodes, w.e_w, s, w.act, w.act_count));
+        HIP_TRY(launch_knn_reg(x, graph_ptr, n_graphs, n_nodes, w.nbr, w.deg, s, w.act.rows, w.act.count));
+        HIP_TRY(launch_gate_mfma(packed, x, w.nbr, w.deg, n_nodes, w.e_w, s, w.act.rows, w.act.count));
     }
     // The source rows of the stack: the in-neighbours of the movable rows (and those rows themselves).  Only their PS columns are
     // ever gathered, so only they are projected -- and only their rows of h are read, which is what lets the denoiser in front
     // (cbgx_unitransformer_forward_cached, CBGX_FWD_H_ON_SOURCES) skip every other row of its last layers.
-    const int *src = nullptr, *src_n = nullptr;
+    NodeList src{nullptr, nullptr};
     if (g_edge_impl != 1) {
         HIP_TRY(launch_mark_seed(gen_flag, gen_flag, n_nodes, w.fa1, s));
-        HIP_TRY(launch_mark_nbr(w.act, w.act_count, n_nodes, w.nbr, w.deg, w.fa1, s));
-        HIP_TRY(launch_build_active(w.fa1, n_nodes, w.rf_list[0], w.rf_count, s));
-        src = w.rf_list[0]; src_n = w.rf_count;
+        HIP_TRY(launch_mark_nbr(w.act.rows, w.act.count, n_nodes, w.nbr, w.deg, w.fa1, s));
+        HIP_TRY(launch_build_active(w.fa1, n_nodes, w.A1.rows, w.A1.count, s));
+        src = w.A1;
     }
     const float* xc = x;
+    const NodeBufs& b = w.set[0];
     for (int l = 0; l < num_layers; ++l) {
         float* xn = (l == num_layers - 1) ? x_out : w.xbuf[l & 1];
         HIP_TRY(launch_attention(false, packed + GATE_SIZE + (size_t)l * ATT_SIZE, xc, h, w.nbr, w.deg, lig_flag, gen_flag,
-                                 w.e_w, n_nodes, w.P, w.Qt, w.q, xn, nullptr, w.act, w.act_count, src, src_n, s));
+                                 w.e_w, n_nodes, b.P, b.Qt, b.q, xn, nullptr, w.act.rows, w.act.count, src.rows, src.count, s));
         xc = xn;
     }
     return CBGX_OK;
@@ -465,38 +442,30 @@ int cbgx_edge_gate(const float* packed, const float* x, const int32_t* nbr, cons
     return CBGX_OK;
 }
 
-// (general, protein-only) list pair `set` of the workspace from a destination list (NULL = all nodes) and the d1 flags
-static int split_by_d1(const Workspace& w, int set, const int* list, const int* count, int n_nodes, hipStream_t s,
-                       bool counters_zeroed = false) {
-    HIP_TRY(launch_split_list(list, count, n_nodes, w.d1flag, w.sp_list[set][1], w.sp_count + 32 * set, w.sp_list[set][0],
-                              w.sp_count + 32 * set + 16, s, counters_zeroed));
-    return CBGX_OK;
-}
-
 int cbgx_x2h_attention(const float* packed, int layer, const float* x, const float* h, const int32_t* nbr,
                        const int32_t* deg, const uint8_t* lig_flag, const float* e_w, int n_nodes, float* h_out,
                        void* workspace, size_t workspace_bytes, void* stream) {
     if (n_nodes == 0) return CBGX_OK;
     if (!packed || !x || !h || !nbr || !deg || !lig_flag || !e_w || !h_out || !workspace || layer < 0 || n_nodes < 0)
         return fail(CBGX_E_INVALID, "x2h_attention: bad argument");
-    Workspace w = carve(workspace, n_nodes);
-    if (workspace_bytes < w.total)
-        return fail(CBGX_E_WORKSPACE, "x2h_attention: workspace %zu < %zu", workspace_bytes, w.total);
+    Workspace w;
+    if (int rc = carve_checked("x2h_attention", workspace, workspace_bytes, n_nodes, w)) return rc;
+    const NodeBufs& b = w.set[0];
     hipStream_t s = (hipStream_t)stream;
     if (g_edge_impl == 1) {
-        HIP_TRY(launch_attention(true, packed + x2h_off(layer), x, h, nbr, deg, lig_flag, nullptr, e_w, n_nodes, w.P,
-                                 w.Qt, w.q, h_out, nullptr, nullptr, nullptr, nullptr, nullptr, s));
+        HIP_TRY(launch_attention(true, packed + x2h_off(layer), x, h, nbr, deg, lig_flag, nullptr, e_w, n_nodes, b.P,
+                                 b.Qt, b.q, h_out, nullptr, nullptr, nullptr, nullptr, nullptr, s));
         return CBGX_OK;
     }
     // what a layer of cbgx_unitransformer_forward runs: protein-only destinations fold their query in registers, Qt is
     // produced for the others only, one two-role edge launch
     HIP_TRY(launch_mark_from_nbr(lig_flag, nbr, deg, n_nodes, w.d1flag, s));
-    { int rc = split_by_d1(w, 0, nullptr, nullptr, n_nodes, s); if (rc) return rc; }
+    HIP_TRY(launch_split_list(nullptr, nullptr, n_nodes, w.d1flag, w.all_gen.rows, w.all_gen.count, w.all_pp.rows, w.all_pp.count, s));
     const float* att = packed + x2h_off(layer);
-    HIP_TRY(launch_node_mfma(att, h, lig_flag, n_nodes, w.P, w.q, w.Qt, nullptr, nullptr, nullptr, nullptr, s, true,
-                             w.sp_list[0][1], w.sp_count));
-    HIP_TRY(launch_edge_x2h_dual(att, x, h, w.P, w.Qt, w.q, nbr, deg, lig_flag, nullptr, e_w, n_nodes, h_out, w.sp_list[0][0],
-                                 w.sp_count + 16, w.sp_list[0][1], w.sp_count, true, s));
+    HIP_TRY(launch_node_mfma(att, h, lig_flag, n_nodes, b.P, b.q, b.Qt, nullptr, nullptr, nullptr, nullptr, s, true,
+                             w.all_gen.rows, w.all_gen.count));
+    HIP_TRY(launch_edge_x2h_dual(att, x, h, b.P, b.Qt, b.q, nbr, deg, lig_flag, nullptr, e_w, n_nodes, h_out, w.all_pp.rows,
+                                 w.all_pp.count, w.all_gen.rows, w.all_gen.count, true, s));
     return CBGX_OK;
 }
 
@@ -508,12 +477,12 @@ int cbgx_h2x_attention(const float* packed, int layer, const float* x, const flo
     if (!packed || !x || !h || !nbr || !deg || !lig_flag || !gen_flag || !e_w || !x_out || !workspace || layer < 0 ||
         n_nodes < 0)
         return fail(CBGX_E_INVALID, "h2x_attention: bad argument");
-    Workspace w = carve(workspace, n_nodes);
-    if (workspace_bytes < w.total)
-        return fail(CBGX_E_WORKSPACE, "h2x_attention: workspace %zu < %zu", workspace_bytes, w.total);
-    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act, w.act_count, (hipStream_t)stream));
-    HIP_TRY(launch_attention(false, packed + h2x_off(layer), x, h, nbr, deg, lig_flag, gen_flag, e_w, n_nodes, w.P,
-                             w.Qt, w.q, x_out, delta_x, w.act, w.act_count, nullptr, nullptr, (hipStream_t)stream));
+    Workspace w;
+    if (int rc = carve_checked("h2x_attention", workspace, workspace_bytes, n_nodes, w)) return rc;
+    const NodeBufs& b = w.set[0];
+    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act.rows, w.act.count, (hipStream_t)stream));
+    HIP_TRY(launch_attention(false, packed + h2x_off(layer), x, h, nbr, deg, lig_flag, gen_flag, e_w, n_nodes, b.P,
+                             b.Qt, b.q, x_out, delta_x, w.act.rows, w.act.count, nullptr, nullptr, (hipStream_t)stream));
     return CBGX_OK;
 }
 
@@ -527,42 +496,283 @@ int cbgx_node_stage(const float* packed, int layer, int x2h, const float* h, con
     return CBGX_OK;
 }
 
+// the classifier head on every row, or on the listed ones (`hidden`: [n_nodes][128] scratch)
+static int classifier_head(const float* packed, int num_layers, int num_classes, const float* h, int n_nodes, float* hidden,
+                           float* logits, NodeList rows, hipStream_t s) {
+    const float* c = packed + cls_off(num_layers);
+    HIP_TRY(launch_node_gemm(h, H, c + C_W0T, c + C_B0, hidden, H, n_nodes, H, 1, s, rows.rows, rows.count));
+    HIP_TRY(launch_node_gemm(hidden, H, c + C_W1T, c + cls_b1(num_classes), logits, num_classes, n_nodes, num_classes, 0, s, rows.rows,
+                             rows.count));
+    return CBGX_OK;
+}
+
 int cbgx_classifier(const float* packed, int num_layers, int num_classes, const float* h, int n_nodes, float* logits,
                     void* workspace, size_t workspace_bytes, void* stream) {
     if (n_nodes == 0) return CBGX_OK;
     if (!packed || !h || !logits || !workspace || num_layers < 0 || num_classes < 1 || n_nodes < 0)
         return fail(CBGX_E_INVALID, "classifier: bad argument");
-    Workspace w = carve(workspace, n_nodes);
-    if (workspace_bytes < w.total)
-        return fail(CBGX_E_WORKSPACE, "classifier: workspace %zu < %zu", workspace_bytes, w.total);
-    const float* c = packed + cls_off(num_layers);
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(launch_node_gemm(h, H, c + C_W0T, c + C_B0, w.P, H, n_nodes, H, 1, s));
-    HIP_TRY(launch_node_gemm(w.P, H, c + C_W1T, c + cls_b1(num_classes), logits, num_classes, n_nodes, num_classes, 0, s));
+    Workspace w;
+    if (int rc = carve_checked("classifier", workspace, workspace_bytes, n_nodes, w)) return rc;
+    return classifier_head(packed, num_layers, num_classes, h, n_nodes, w.set[0].P, logits, NodeList{nullptr, nullptr},
+                           (hipStream_t)stream);
+}
+
+// ---- the denoiser's forward (cbgx_unitransformer_forward, cbgx_unitransformer_forward_cached) ---------------------------------------
+// What layer l works on, computed once per call (plan_layers) and read by all three schedules
+struct LayerPlan {
+    NodeList dst, src;          // x2h node stage: own columns, q and Qt on dst, PS columns on src ({NULL, NULL}: every row)
+    NodeList gen, pp;           // x2h edge launch: general-role and protein-only destinations
+    bool full_layer;            // ... which together are every node
+    const uint8_t* fold_flag;   // fused node stage: Qt only for the flagged rows of dst (NULL: for all of them)
+};
+
+// a forward call: its arguments, then what forward_impl derives from them for its parts
+struct Forward {
+    const float* packed; int num_layers, num_classes; const float *x, *h; const int32_t* graph_ptr; const uint8_t *lig_flag, *gen_flag;
+    int n_nodes, n_graphs; float *x_out, *h_out, *logits;
+    const float *static_h1, *static_h2; const int32_t *static_nbr, *static_deg; const float *static_ew, *static_r32sq;
+    unsigned flags; void* workspace; size_t workspace_bytes; hipStream_t s;
+    Workspace w;
+    bool cached, graph_cached, prune, dual;
+    std::vector<LayerPlan> plan;
+};
+
+// nbr / deg / e_w of the call
+static int forward_graph_stage(const Forward& f) {
+    const Workspace& w = f.w;
+    const int n_nodes = f.n_nodes, n_graphs = f.n_graphs;
+    hipStream_t s = f.s;
+    if (!f.graph_cached) {
+        HIP_TRY(launch_knn(f.x, f.graph_ptr, n_graphs, n_nodes, w.nbr, w.deg, s));
+        HIP_TRY(launch_gate(f.packed, f.x, w.nbr, w.deg, n_nodes, w.e_w, s));
+        return CBGX_OK;
+    }
+    // D1 flags + list, the pocket's own graph and the cached features of layers 0 / 1 (into hbuf[0] / hbuf[1]: num_layers >= 4,
+    // so neither is the caller's h_out, and nothing else touches them before their layer): one launch
+    HIP_TRY(launch_graph_cache_begin(f.x, f.graph_ptr, n_graphs, f.lig_flag, f.static_r32sq, n_nodes, w.fD1, w.D1.rows, w.D1.count,
+                                     f.static_nbr, f.static_deg, f.static_ew, w.nbr, w.deg, w.e_w, f.static_h1, f.static_h2, w.hbuf[0],
+                                     w.hbuf[1], s));
+    // the D1 centres' merged neighbour lists and gate values: kept pocket entries carry their cached value to their new rank, the gate
+    // MLP runs on the ligand atoms that entered the list.  Small inputs: ONE launch (knn_merge_gate_kernel: a persistent kernel at one
+    // wave per SIMD -- at 173 k nodes it measured 612 us against 153 + 175 for the two kernels, profiles/ab_fwd_r05f.log); large inputs:
+    // the merge marks the new ranks and the gate kernel evaluates only those.  CBGX_MERGE_GATE=0: the round-4 pair (all slots).
+    static const int merge_gate = [] { const char* e = getenv("CBGX_MERGE_GATE"); return e ? atoi(e) : 1; }();
+    if (merge_gate && n_nodes <= GRAPH_LISTS_MAX_NODES) {
+        HIP_TRY(launch_knn_merge_gate(f.packed, f.x, f.graph_ptr, n_graphs, n_nodes, f.lig_flag, f.static_nbr, f.static_deg, f.static_ew,
+                                      w.nbr, w.deg, w.e_w, s, w.D1.rows, w.D1.count));
+    } else {
+        const bool carry = merge_gate != 0;
+        HIP_TRY(launch_knn_merge(f.x, f.graph_ptr, n_graphs, n_nodes, f.lig_flag, f.static_nbr, f.static_deg, w.nbr, w.deg, s, w.D1.rows,
+                                 w.D1.count, carry ? f.static_ew : nullptr, carry ? w.e_w : nullptr, carry ? w.newmask : nullptr));
+        HIP_TRY(launch_gate_mfma(f.packed, f.x, w.nbr, w.deg, n_nodes, w.e_w, s, w.D1.rows, w.D1.count, carry ? w.newmask : nullptr));
+    }
     return CBGX_OK;
 }
 
-static int forward_impl(const float* packed, int num_layers, int num_classes, const float* x, const float* h,
-                        const int32_t* graph_ptr, const uint8_t* lig_flag, const uint8_t* gen_flag, int n_nodes,
-                        int n_graphs, float* x_out, float* h_out, float* logits, const float* static_h1,
-                        const float* static_h2, const int32_t* static_nbr, const int32_t* static_deg,
-                        const float* static_ew, const float* static_r32sq, unsigned flags, void* workspace,
-                        size_t workspace_bytes, void* stream) {
-    if (n_nodes < 0 || n_graphs < 0 || num_layers < 1) return fail(CBGX_E_INVALID, "forward: bad sizes");
-    if (flags & ~CBGX_FWD_H_ON_SOURCES) return fail(CBGX_E_INVALID, "forward: unknown flags 0x%x", flags);
-    if (n_nodes == 0) return CBGX_OK;
-    if (!packed || !x || !h || !graph_ptr || !lig_flag || !gen_flag || !x_out || !workspace)
+// Every list of the call.  Large inputs: three level kernels over the flags (a level reads what the previous one completed) and one
+// compaction; inputs of <= GRAPH_LISTS_MAX_NODES nodes: one launch, a workgroup per graph with the graph's flags in LDS (round 5:
+// the four launches were 20 us of a 600 us one-graph step)
+static int forward_list_stage(const Forward& f) {
+    const Workspace& w = f.w;
+    hipStream_t s = f.s;
+    const bool per_graph = f.n_nodes <= GRAPH_LISTS_MAX_NODES && g_edge_impl != 1;
+    const GraphFlags gf{f.gen_flag, f.lig_flag, f.graph_cached ? w.fD1 : w.d1flag, w.d1flag, w.fa1, w.fa2, w.fa3, w.fD2, w.fS1, w.fS2};
+    const uint8_t* flag_ptr[GF_COUNT] = {f.gen_flag, f.lig_flag, gf.D1, w.d1flag, w.fa1, w.fa2, w.fa3, w.fD2, w.fS1, w.fS2};
+    ListJobs jobs;
+    GraphListJobs gjobs;
+    memset(&jobs, 0, sizeof(jobs));
+    memset(&gjobs, 0, sizeof(gjobs));
+    bool jobs_overflow = false;
+    auto add = [&](int flag, int flag2, int want2, NodeList l) {
+        if (jobs.n_jobs >= LIST_JOBS_MAX) { jobs_overflow = true; return; }
+        const int k = jobs.n_jobs++;
+        jobs.flag[k] = flag == GF_ALL ? nullptr : flag_ptr[flag]; jobs.flag2[k] = flag2 == GF_ALL ? nullptr : flag_ptr[flag2];
+        jobs.want2[k] = want2; jobs.list[k] = l.rows; jobs.count[k] = l.count;
+        gjobs.flag[k] = (signed char)flag; gjobs.flag2[k] = (signed char)flag2; gjobs.want2[k] = (signed char)want2;
+        gjobs.list[k] = l.rows; gjobs.count[k] = l.count;
+        gjobs.n_jobs = jobs.n_jobs;
+    };
+    auto pair = [&](int flag, NodeList gen, NodeList pp) { add(flag, GF_d1, 1, gen); add(flag, GF_d1, 0, pp); };
+    add(GF_GEN, GF_ALL, 0, w.act);
+    add(GF_a1, GF_ALL, 0, w.A1);
+    if (f.prune) {
+        add(GF_a2, GF_ALL, 0, w.A2);
+        add(GF_a3, GF_ALL, 0, w.A3);
+    }
+    if (f.cached) {
+        if (!f.graph_cached) add(GF_d1, GF_ALL, 0, w.D1);      // (graph-cached calls: graph_cache_begin has built it)
+        add(GF_D2, GF_ALL, 0, w.D2);
+        add(GF_S1, GF_ALL, 0, w.S1);
+        add(GF_S2, GF_ALL, 0, w.S2);
+    }
+    if (f.dual) {
+        pair(GF_ALL, w.all_gen, w.all_pp);
+        if (f.cached) pair(GF_D2, w.D2_gen, w.D2_pp);
+        if (f.prune) { pair(GF_a1, w.A1_gen, w.A1_pp); pair(GF_a2, w.A2_gen, w.A2_pp); }
+    }
+    if (jobs_overflow) return fail(CBGX_E_INVALID, "forward: more than %d node lists (LIST_JOBS_MAX)", LIST_JOBS_MAX);
+    if (per_graph) {
+        HIP_TRY(launch_graph_lists(f.gen_flag, f.lig_flag, f.graph_cached ? w.fD1 : nullptr, w.nbr, w.deg, f.graph_ptr, f.n_graphs, gjobs,
+                                   f.cached, f.prune, w.d1flag, s));
+    } else {
+        HIP_TRY(launch_list_level(gf, w.nbr, w.deg, f.n_nodes, 0, f.cached, f.prune, s));
+        if (f.cached || f.prune) {
+            HIP_TRY(launch_list_level(gf, w.nbr, w.deg, f.n_nodes, 1, f.cached, f.prune, s));
+            HIP_TRY(launch_list_level(gf, w.nbr, w.deg, f.n_nodes, 2, f.cached, f.prune, s));
+        }
+        HIP_TRY(launch_build_lists(jobs, f.n_nodes, s));
+    }
+    return CBGX_OK;
+}
+
+static void plan_layers(Forward& f) {
+    const Workspace& w = f.w;
+    const int L = f.num_layers;
+    const NodeList every{nullptr, nullptr};
+    f.plan.assign(L, LayerPlan{every, every, w.all_gen, w.all_pp, true, w.d1flag});
+    if (f.cached) {     // (num_layers >= 4)
+        // layer 0 on D1, all of it in the general role -- every row of D1 has a ligand atom among itself and its neighbours -- so
+        // folded rows for the whole list; layer 1 on D2, of which d1flag picks the general part as in every other layer
+        f.plan[0] = LayerPlan{w.D1, w.S1, w.D1, w.empty, false, nullptr};
+        f.plan[1] = LayerPlan{w.D2, w.S2, w.D2_gen, w.D2_pp, false, w.d1flag};
+    }
+    if (f.prune) {      // (num_layers >= 3)
+        f.plan[L - 2] = LayerPlan{w.A2, w.A3, w.A2_gen, w.A2_pp, false, w.d1flag};
+        f.plan[L - 1] = LayerPlan{w.A1, w.A2, w.A1_gen, w.A1_pp, false, w.d1flag};
+    }
+}
+
+// Where layer l writes -- the caller's buffers for the last layer, the workspace's otherwise -- and, in a static-features call without
+// the graph part, the cached rows placed under the layer's output (graph-cached calls: graph_cache_begin has placed both)
+static hipError_t begin_layer(const Forward& f, int l, float*& hn, float*& xn) {
+    const bool last = l == f.num_layers - 1;
+    hn = (last && f.h_out) ? f.h_out : f.w.hbuf[l & 1];
+    xn = last ? f.x_out : f.w.xbuf[l & 1];
+    if (!f.cached || l >= 2 || f.graph_cached) return hipSuccess;
+    return hipMemcpyAsync(hn, l == 0 ? f.static_h1 : f.static_h2, (size_t)f.n_nodes * H * sizeof(float), hipMemcpyDeviceToDevice, f.s);
+}
+
+static hipError_t edge_x2h(const Forward& f, int l, const NodeBufs& b, const float* xc, const float* hc, float* hn) {
+    const LayerPlan& p = f.plan[l];
+    return launch_edge_x2h_dual(f.packed + x2h_off(l), xc, hc, b.P, b.Qt, b.q, f.w.nbr, f.w.deg, f.lig_flag, f.gen_flag, f.w.e_w,
+                                f.n_nodes, hn, p.pp.rows, p.pp.count, p.gen.rows, p.gen.count, p.full_layer, f.s);
+}
+// (q straight from h, no q-hidden columns in P: launch_node_mfma, large inputs only)
+static hipError_t node_x2h(const Forward& f, int l, const NodeBufs& b, const float* h_in, hipStream_t on) {
+    const LayerPlan& p = f.plan[l];
+    return launch_node_mfma(f.packed + x2h_off(l), h_in, f.lig_flag, f.n_nodes, b.P, b.q, b.Qt, p.dst.rows, p.dst.count, p.src.rows,
+                            p.src.count, on, true, p.gen.rows, p.gen.count, node_qdirect_enabled());
+}
+// the h2x block of layer l, node stage included: moves the `act` rows, whose sources are in A1
+static hipError_t block_h2x(const Forward& f, int l, const NodeBufs& b, const float* xc, const float* hn, float* xn) {
+    const Workspace& w = f.w;
+    return launch_attention(false, f.packed + h2x_off(l), xc, hn, w.nbr, w.deg, f.lig_flag, f.gen_flag, w.e_w, f.n_nodes, b.P, b.Qt, b.q,
+                            xn, nullptr, w.act.rows, w.act.count, w.A1.rows, w.A1.count, f.s);
+}
+
+// Small inputs (round 5): ONE stream and ONE node-stage launch per layer.  The h2x block of layer l and the x2h block of layer
+// l + 1 both read h_{l+1} and nothing else that is new, so their node stages are jobs of the same node_stage_kernel launch and a
+// layer is three dependent launches -- x2h edge, node stages, h2x edge -- with no event between them.  The two-stream schedule
+// hides the second node stage behind the h2x block instead, at the price of a fork and a join event per layer, ~7 us
+// each on the caller's queue: 80 us per layer at one graph, of which 14 are the events and 24 + 25 the two edge launches
+// (profiles/step_timeline_r05a_p1s1_ov1.json).
+static int forward_fused(const Forward& f) {
+    const Workspace& w = f.w;
+    hipStream_t s = f.s;
+    auto add_x2h = [&](NodeStageJobs& jobs, int l) {
+        const LayerPlan& p = f.plan[l];
+        const NodeBufs& b = w.set[l & 1];
+        add_node_stage_jobs(jobs, f.packed + x2h_off(l), b.P, b.q, b.Qt, p.dst.rows, p.dst.count, p.src.rows, p.src.count, p.fold_flag);
+    };
+    NodeStageJobs jobs;
+    jobs.n = 0;
+    add_x2h(jobs, 0);
+    HIP_TRY(launch_node_stage_jobs(jobs, f.h, f.lig_flag, f.n_nodes, s));
+    const float *xc = f.x, *hc = f.h;
+    for (int l = 0; l < f.num_layers; ++l) {
+        float *hn, *xn;
+        HIP_TRY(begin_layer(f, l, hn, xn));
+        HIP_TRY(edge_x2h(f, l, w.set[l & 1], xc, hc, hn));
+        jobs.n = 0;
+        add_node_stage_jobs(jobs, f.packed + h2x_off(l), w.set[2].P, w.set[2].q, w.set[2].Qt, w.act.rows, w.act.count, w.A1.rows,
+                            w.A1.count);
+        if (l + 1 < f.num_layers) add_x2h(jobs, l + 1);
+        HIP_TRY(launch_node_stage_jobs(jobs, hn, f.lig_flag, f.n_nodes, s));
+        HIP_TRY(launch_edge_mfma(false, f.packed + h2x_off(l), xc, hn, w.set[2].P, w.set[2].Qt, w.nbr, w.deg, f.lig_flag, f.gen_flag, w.e_w,
+                                 f.n_nodes, xn, nullptr, w.act.rows, w.act.count, s));
+        xc = xn;
+        hc = hn;
+    }
+    return CBGX_OK;
+}
+
+// Two-stream schedule (MFMA kernels, profiling off): the node stage of x2h(l+1) only needs h_{l+1}, which exists as
+// soon as the x2h edge kernel of layer l has run, while the h2x block of layer l (which only moves coordinates) is
+// still to come -- so it runs on an auxiliary stream next to that h2x block.  Three node-stage buffer sets: x2h
+// alternates between two, h2x has its own.
+static int forward_two_streams(const Forward& f, AuxStream* aux) {
+    hipStream_t s = f.s;
+    HIP_TRY(node_x2h(f, 0, f.w.set[0], f.h, s));
+    const float *xc = f.x, *hc = f.h;
+    for (int l = 0; l < f.num_layers; ++l) {
+        float *hn, *xn;
+        HIP_TRY(begin_layer(f, l, hn, xn));
+        if (l > 0) HIP_TRY(hipStreamWaitEvent(s, aux->join, 0));       // node stage of this layer (aux stream) done
+        HIP_TRY(edge_x2h(f, l, f.w.set[l & 1], xc, hc, hn));
+        if (l + 1 < f.num_layers) {
+            HIP_TRY(hipEventRecord(aux->fork, s));
+            HIP_TRY(hipStreamWaitEvent(aux->s, aux->fork, 0));
+            HIP_TRY(node_x2h(f, l + 1, f.w.set[(l + 1) & 1], hn, aux->s));
+            HIP_TRY(hipEventRecord(aux->join, aux->s));
+        }
+        HIP_TRY(block_h2x(f, l, f.w.set[2], xc, hn, xn));
+        xc = xn;
+        hc = hn;
+    }
+    return CBGX_OK;
+}
+
+// one stream, one node-stage buffer set, block after block (profiling, CBGX_OVERLAP=0, no auxiliary stream, first-generation kernels)
+static int forward_serial(const Forward& f) {
+    const Workspace& w = f.w;
+    const NodeBufs& b = w.set[0];
+    const float *xc = f.x, *hc = f.h;
+    for (int l = 0; l < f.num_layers; ++l) {
+        float *hn, *xn;
+        HIP_TRY(begin_layer(f, l, hn, xn));
+        if (f.dual) {
+            HIP_TRY(node_x2h(f, l, b, hc, f.s));
+            HIP_TRY(edge_x2h(f, l, b, xc, hc, hn));
+        } else {
+            const LayerPlan& p = f.plan[l];
+            HIP_TRY(launch_attention(true, f.packed + x2h_off(l), xc, hc, w.nbr, w.deg, f.lig_flag, f.gen_flag, w.e_w, f.n_nodes, b.P, b.Qt,
+                                     b.q, hn, nullptr, p.dst.rows, p.dst.count, p.src.rows, p.src.count, f.s));
+        }
+        HIP_TRY(block_h2x(f, l, b, xc, hn, xn));
+        xc = xn;
+        hc = hn;
+    }
+    return CBGX_OK;
+}
+
+static int forward_impl(Forward f) {
+    if (f.n_nodes < 0 || f.n_graphs < 0 || f.num_layers < 1) return fail(CBGX_E_INVALID, "forward: bad sizes");
+    if (f.flags & ~CBGX_FWD_H_ON_SOURCES) return fail(CBGX_E_INVALID, "forward: unknown flags 0x%x", f.flags);
+    if (f.n_nodes == 0) return CBGX_OK;
+    if (!f.packed || !f.x || !f.h || !f.graph_ptr || !f.lig_flag || !f.gen_flag || !f.x_out || !f.workspace)
         return fail(CBGX_E_INVALID, "forward: NULL pointer");
-    if (logits && num_classes < 1) return fail(CBGX_E_INVALID, "forward: num_classes=%d", num_classes);
-    Workspace w = carve(workspace, n_nodes);
-    if (workspace_bytes < w.total)
-        return fail(CBGX_E_WORKSPACE, "forward: workspace %zu < %zu", workspace_bytes, w.total);
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipMemsetAsync(w.counters, 0, w.counters_bytes, s));      // every list count of this call: one fill instead of ~15
-    const bool cached = static_h1 && static_h2 && num_layers >= 4;
+    if (f.logits && f.num_classes < 1) return fail(CBGX_E_INVALID, "forward: num_classes=%d", f.num_classes);
+    if (int rc = carve_checked("forward", f.workspace, f.workspace_bytes, f.n_nodes, f.w)) return rc;
+    HIP_TRY(hipMemsetAsync(f.w.counters, 0, f.w.counters_bytes, f.s));      // every list count of this call: one fill instead of ~15
+    // Static-context cache (optional): static_h1 / static_h2 [N,128] hold the features that leave layer 0 / layer 1 in
+    // the ligand-free pocket (rows of ligand atoms unused).  A protein node with no ligand atom among its neighbours sees
+    // exactly that pocket in layer 0, so its output is the cached row; the set that differs grows by one hop per layer:
+    //   D1 = lig | {i : nbr(i) has a ligand atom},   D2 = D1 | {i : nbr(i) meets D1};   sources S_k = D_k | nbr(D_k).
+    // Layers 0 and 1 then run on D1 / D2 only, every other row of their output is a copy of the cache.
+    f.cached = f.static_h1 && f.static_h2 && f.num_layers >= 4;
     // with the graph part of the cache, only the nodes that have a ligand atom within reach get a fresh neighbour list
     // and gate: everything else about the pocket's own graph was computed once (same order, same bits)
-    const bool graph_cached = cached && static_nbr && static_deg && static_ew && static_r32sq && g_edge_impl != 1;
+    f.graph_cached = f.cached && f.static_nbr && f.static_deg && f.static_ew && f.static_r32sq && g_edge_impl != 1;
     // H2X only ever moves gen_flag nodes (x_out = x + dx * gen_flag): they are listed once (`act`), every h2x block runs on the list.
     // Receptive-field pruning (only when the caller does not ask for h_out): the outputs that remain are x_out and the
     // logits of ligand rows, so the last x2h blocks only have to produce features that can still reach them:
@@ -571,247 +781,33 @@ static int forward_impl(const float* packed, int num_layers, int num_classes, co
     // Rows outside these sets are simply not written in the last two feature buffers (and never read).  A1 is built in every
     // call: it is also the set of possible *sources* of an H2X block, so the h2x node projection PS is produced for those rows only.
     // (CBGX_FWD_H_ON_SOURCES: h_out is wanted on A1 only -- the destinations of the last x2h block -- so the same pruning holds)
-    const bool prune = (h_out == nullptr || (flags & CBGX_FWD_H_ON_SOURCES)) && num_layers >= 3;
-    // Static-context cache (optional): static_h1 / static_h2 [N,128] hold the features that leave layer 0 / layer 1 in
-    // the ligand-free pocket (rows of ligand atoms unused).  A protein node with no ligand atom among its neighbours sees
-    // exactly that pocket in layer 0, so its output is the cached row; the set that differs grows by one hop per layer:
-    //   D1 = lig | {i : nbr(i) has a ligand atom},   D2 = D1 | {i : nbr(i) meets D1};   sources S_k = D_k | nbr(D_k).
-    // Layers 0 and 1 then run on D1 / D2 only, every other row of their output is a copy of the cache.
-    // x2h layers run their (general, protein-only) list pairs: d1flag = the node or one of its neighbours is a ligand atom, from
-    // the neighbour lists this call works with.  Set 0 all nodes, 1 the cached layer 1 (D2), 2 / 3 the pruned layers (A1 / A2).
-    const bool dual = g_edge_impl != 1;
-    GraphFlags gf{gen_flag, lig_flag, graph_cached ? w.fD1 : w.d1flag, w.d1flag, w.fa1, w.fa2, w.fa3, w.fD2, w.fS1, w.fS2};
-    if (graph_cached) {
-        // D1 flags + list, the pocket's own graph and the cached features of layers 0 / 1 (into hbuf[0] / hbuf[1]: num_layers >= 4,
-        // so neither is the caller's h_out, and nothing else touches them before their layer): one launch
-        HIP_TRY(launch_graph_cache_begin(x, graph_ptr, n_graphs, lig_flag, static_r32sq, n_nodes, w.fD1, w.fw_list[0], w.fw_count,
-                                         static_nbr, static_deg, static_ew, w.nbr, w.deg, w.e_w, static_h1, static_h2, w.hbuf[0],
-                                         w.hbuf[1], s));
-        // the D1 centres' merged neighbour lists and gate values (kept pocket entries carry their cached value to their new
-        // rank; the gate MLP runs on the ligand atoms that entered the list): one launch.  CBGX_MERGE_GATE=0: the two kernels.
-        // Small inputs: ONE launch (knn_merge_gate_kernel: a persistent kernel at one wave per SIMD -- at 173 k nodes it measured
-        // 612 us against 153 + 175 for the two kernels, profiles/ab_fwd_r05f.log, so large inputs keep two launches); large inputs:
-        // the merge marks the new ranks and the gate kernel evaluates only those.  CBGX_MERGE_GATE=0: the round-4 pair (all slots).
-        static const int merge_gate = [] { const char* e = getenv("CBGX_MERGE_GATE"); return e ? atoi(e) : 1; }();
-        if (merge_gate && n_nodes <= GRAPH_LISTS_MAX_NODES) {
-            HIP_TRY(launch_knn_merge_gate(packed, x, graph_ptr, n_graphs, n_nodes, lig_flag, static_nbr, static_deg, static_ew, w.nbr,
-                                          w.deg, w.e_w, s, w.fw_list[0], w.fw_count));
-        } else if (merge_gate) {
-            HIP_TRY(launch_knn_merge(x, graph_ptr, n_graphs, n_nodes, lig_flag, static_nbr, static_deg, w.nbr, w.deg, s, w.fw_list[0],
-                                     w.fw_count, static_ew, w.e_w, w.newmask));
-            HIP_TRY(launch_gate_mfma(packed, x, w.nbr, w.deg, n_nodes, w.e_w, s, w.fw_list[0], w.fw_count, w.newmask));
-        } else {
-            HIP_TRY(launch_knn_merge(x, graph_ptr, n_graphs, n_nodes, lig_flag, static_nbr, static_deg, w.nbr, w.deg, s, w.fw_list[0],
-                                     w.fw_count));
-            HIP_TRY(launch_gate_mfma(packed, x, w.nbr, w.deg, n_nodes, w.e_w, s, w.fw_list[0], w.fw_count));
-        }
-    } else {
-        HIP_TRY(launch_knn(x, graph_ptr, n_graphs, n_nodes, w.nbr, w.deg, s));
-        HIP_TRY(launch_gate(packed, x, w.nbr, w.deg, n_nodes, w.e_w, s));
-    }
-    // every list of the call.  Large inputs: three level kernels over the flags (a level reads what the previous one completed) and one
-    // compaction; inputs of <= GRAPH_LISTS_MAX_NODES nodes: one launch, a workgroup per graph with the graph's flags in LDS (round 5:
-    // the four launches were 20 us of a 600 us one-graph step)
-    {
-        const bool per_graph = n_nodes <= GRAPH_LISTS_MAX_NODES && g_edge_impl != 1;
-        const uint8_t* flag_ptr[GF_COUNT] = {gen_flag, lig_flag, gf.D1, w.d1flag, w.fa1, w.fa2, w.fa3, w.fD2, w.fS1, w.fS2};
-        ListJobs jobs;
-        GraphListJobs gjobs;
-        memset(&jobs, 0, sizeof(jobs));
-        memset(&gjobs, 0, sizeof(gjobs));
-        bool jobs_overflow = false;
-        auto add = [&](int f, int f2, int want2, int* list, int* count) {
-            if (jobs.n_jobs >= LIST_JOBS_MAX) { jobs_overflow = true; return; }
-            const int k = jobs.n_jobs++;
-            jobs.flag[k] = f == GF_ALL ? nullptr : flag_ptr[f]; jobs.flag2[k] = f2 == GF_ALL ? nullptr : flag_ptr[f2];
-            jobs.want2[k] = want2; jobs.list[k] = list; jobs.count[k] = count;
-            gjobs.flag[k] = (signed char)f; gjobs.flag2[k] = (signed char)f2; gjobs.want2[k] = (signed char)want2;
-            gjobs.list[k] = list; gjobs.count[k] = count;
-            gjobs.n_jobs = jobs.n_jobs;
-        };
-        add(GF_GEN, GF_ALL, 0, w.act, w.act_count);
-        add(GF_a1, GF_ALL, 0, w.rf_list[0], w.rf_count);
-        if (prune) {
-            add(GF_a2, GF_ALL, 0, w.rf_list[1], w.rf_count + 16);
-            add(GF_a3, GF_ALL, 0, w.rf_list[2], w.rf_count + 32);
-        }
-        if (cached) {
-            if (!graph_cached) add(GF_d1, GF_ALL, 0, w.fw_list[0], w.fw_count);
-            add(GF_D2, GF_ALL, 0, w.fw_list[2], w.fw_count + 32);
-            add(GF_S1, GF_ALL, 0, w.fw_list[1], w.fw_count + 16);
-            add(GF_S2, GF_ALL, 0, w.fw_list[3], w.fw_count + 48);
-        }
-        if (dual) {
-            auto pair = [&](int set, int f) {
-                add(f, GF_d1, 1, w.sp_list[set][1], w.sp_count + 32 * set);
-                add(f, GF_d1, 0, w.sp_list[set][0], w.sp_count + 32 * set + 16);
-            };
-            pair(0, GF_ALL);
-            if (cached) pair(1, GF_D2);
-            if (prune) { pair(2, GF_a1); pair(3, GF_a2); }
-        }
-        if (jobs_overflow) return fail(CBGX_E_INVALID, "forward: more than %d node lists (LIST_JOBS_MAX)", LIST_JOBS_MAX);
-        if (per_graph) {
-            HIP_TRY(launch_graph_lists(gen_flag, lig_flag, graph_cached ? w.fD1 : nullptr, w.nbr, w.deg, graph_ptr, n_graphs, gjobs,
-                                       cached, prune, w.d1flag, s));
-        } else {
-            HIP_TRY(launch_list_level(gf, w.nbr, w.deg, n_nodes, 0, cached, prune, s));
-            if (cached || prune) {
-                HIP_TRY(launch_list_level(gf, w.nbr, w.deg, n_nodes, 1, cached, prune, s));
-                HIP_TRY(launch_list_level(gf, w.nbr, w.deg, n_nodes, 2, cached, prune, s));
-            }
-            HIP_TRY(launch_build_lists(jobs, n_nodes, s));
-        }
-    }
-    struct X2HLists { const int *gen, *gen_n, *pp, *pp_n; bool full; };
-    auto x2h_lists = [&](int l) {
-        X2HLists r{w.sp_list[0][1], w.sp_count, w.sp_list[0][0], w.sp_count + 16, true};
-        auto set = [&](int k) { r = X2HLists{w.sp_list[k][1], w.sp_count + 32 * k, w.sp_list[k][0], w.sp_count + 32 * k + 16, false}; };
-        if (cached && l == 0) r = X2HLists{w.fw_list[0], w.fw_count, w.sp_list[0][0], w.zero_count, false};   // D1: general role only
-        if (cached && l == 1) set(1);
-        if (prune && l >= num_layers - 2) set(2 + (num_layers - 1 - l));
-        return r;
-    };
-    // Two-stream schedule (MFMA kernels, profiling off): the node stage of x2h(l+1) only needs h_{l+1}, which exists as
-    // soon as the x2h edge kernel of layer l has run, while the h2x block of layer l (which only moves coordinates) is
-    // still to come -- so it runs on an auxiliary stream next to that h2x block.  Three node-stage buffer sets: x2h
-    // alternates between two, h2x has its own.
+    f.prune = (f.h_out == nullptr || (f.flags & CBGX_FWD_H_ON_SOURCES)) && f.num_layers >= 3;
+    // x2h layers run their (general, protein-only) list pairs (first-generation kernels: one list)
+    f.dual = g_edge_impl != 1;
+    if (int rc = forward_graph_stage(f)) return rc;
+    if (int rc = forward_list_stage(f)) return rc;
+    plan_layers(f);
     static const bool overlap_env = [] { const char* e = getenv("CBGX_OVERLAP"); return !e || atoi(e) != 0; }();
-    AuxStream* aux = (overlap_env && g_edge_impl != 1 && !profile_is_on() && num_layers > 1) ? aux_for(s) : nullptr;
-    const bool overlap = aux != nullptr;
-    auto layer_lists = [&](int l, const int*& dst, const int*& dst_n, const int*& src, const int*& src_n) {
-        dst = dst_n = src = src_n = nullptr;
-        if (cached && l < 2) {
-            dst = w.fw_list[2 * l]; dst_n = w.fw_count + 32 * l;
-            src = w.fw_list[2 * l + 1]; src_n = w.fw_count + 32 * l + 16;
-        }
-        if (prune && l >= num_layers - 2) {
-            const int k = num_layers - 1 - l;   // 0 for the last layer, 1 for the one before
-            dst = w.rf_list[k]; dst_n = w.rf_count + 16 * k;
-            src = w.rf_list[k + 1]; src_n = w.rf_count + 16 * (k + 1);
-        }
-    };
-    float* Pset[2] = {w.P, w.P2};
-    float* Qtset[2] = {w.Qt, w.Qt2};
-    float* qset[2] = {w.q, w.q2};
-    const float* xc = x;
-    const float* hc = h;
-    // Small inputs (round 5): ONE stream and ONE node-stage launch per layer.  The h2x block of layer l and the x2h block of layer
-    // l + 1 both read h_{l+1} and nothing else that is new, so their node stages are jobs of the same node_stage_kernel launch and a
-    // layer is three dependent launches -- x2h edge, node stages, h2x edge -- with no event between them.  The two-stream schedule
-    // below hides the second node stage behind the h2x block instead, at the price of a fork and a join event per layer, ~7 us
-    // each on the caller's queue: 80 us per layer at one graph, of which 14 are the events and 24 + 25 the two edge launches
-    // (profiles/step_timeline_r05a_p1s1_ov1.json).  CBGX_FUSE_ROWS: largest input that takes this schedule (0 = never).
+    AuxStream* aux = (overlap_env && g_edge_impl != 1 && !profile_is_on() && f.num_layers > 1) ? aux_for(f.s) : nullptr;
+    // CBGX_FUSE_ROWS: largest input that takes the one-stream fused schedule (0 = never)
     static const int fuse_rows = [] { const char* e = getenv("CBGX_FUSE_ROWS"); return e ? atoi(e) : NODE_STAGE_MAX_ROWS; }();
-    if (dual && num_layers > 1 && n_nodes <= fuse_rows && n_nodes <= NODE_STAGE_MAX_ROWS) {
-        {
-            const int *dst, *dst_n, *src, *src_n;
-            layer_lists(0, dst, dst_n, src, src_n);
-            NodeStageJobs jobs;
-            jobs.n = 0;
-            // (the general role of a cached layer 0 is the whole D1 list: folded rows for all of it; every other x2h layer's
-            // general role is the d1-flagged part of its destinations)
-            add_node_stage_jobs(jobs, packed + x2h_off(0), Pset[0], qset[0], Qtset[0], dst, dst_n, src, src_n,
-                                cached ? nullptr : w.d1flag);
-            HIP_TRY(launch_node_stage_jobs(jobs, h, lig_flag, n_nodes, s));
-        }
-        for (int l = 0; l < num_layers; ++l) {
-            float* hn = (l == num_layers - 1 && h_out) ? h_out : w.hbuf[l & 1];
-            float* xn = (l == num_layers - 1) ? x_out : w.xbuf[l & 1];
-            if (cached && l < 2 && !graph_cached)     // (graph-cached calls: restore_graph_kernel has already placed both)
-                HIP_TRY(hipMemcpyAsync(hn, l == 0 ? static_h1 : static_h2, (size_t)n_nodes * H * sizeof(float),
-                                       hipMemcpyDeviceToDevice, s));
-            const X2HLists xl = x2h_lists(l);
-            const int set = l & 1;
-            HIP_TRY(launch_edge_x2h_dual(packed + x2h_off(l), xc, hc, Pset[set], Qtset[set], qset[set], w.nbr, w.deg, lig_flag,
-                                         gen_flag, w.e_w, n_nodes, hn, xl.pp, xl.pp_n, xl.gen, xl.gen_n, xl.full, s));
-            NodeStageJobs jobs;
-            jobs.n = 0;
-            add_node_stage_jobs(jobs, packed + h2x_off(l), w.P3, w.q3, w.Qt3, w.act, w.act_count, w.rf_list[0], w.rf_count);
-            if (l + 1 < num_layers) {
-                const int *d2, *d2n, *s2, *s2n;
-                layer_lists(l + 1, d2, d2n, s2, s2n);
-                add_node_stage_jobs(jobs, packed + x2h_off(l + 1), Pset[set ^ 1], qset[set ^ 1], Qtset[set ^ 1], d2, d2n, s2, s2n,
-                                    w.d1flag);
-            }
-            HIP_TRY(launch_node_stage_jobs(jobs, hn, lig_flag, n_nodes, s));
-            HIP_TRY(launch_edge_mfma(false, packed + h2x_off(l), xc, hn, w.P3, w.Qt3, w.nbr, w.deg, lig_flag, gen_flag, w.e_w,
-                                     n_nodes, xn, nullptr, w.act, w.act_count, s));
-            xc = xn;
-            hc = hn;
-        }
-    } else {
-    // x2h node stages of these two schedules: q straight from h, no q-hidden columns in P (launch_node_mfma; large inputs only)
-    const bool q_direct = node_qdirect_enabled();
-    if (overlap) {
-        const int *dst, *dst_n, *src, *src_n;
-        layer_lists(0, dst, dst_n, src, src_n);
-        const X2HLists xl = x2h_lists(0);
-        HIP_TRY(launch_node_mfma(packed + x2h_off(0), h, lig_flag, n_nodes, Pset[0], qset[0], Qtset[0], dst, dst_n, src,
-                                 src_n, s, true, xl.gen, xl.gen_n, q_direct));
-    }
-    for (int l = 0; l < num_layers; ++l) {
-        float* hn = (l == num_layers - 1 && h_out) ? h_out : w.hbuf[l & 1];
-        float* xn = (l == num_layers - 1) ? x_out : w.xbuf[l & 1];
-        const int *dst, *dst_n, *src, *src_n;
-        layer_lists(l, dst, dst_n, src, src_n);
-        if (cached && l < 2 && !graph_cached)
-            HIP_TRY(hipMemcpyAsync(hn, l == 0 ? static_h1 : static_h2, (size_t)n_nodes * H * sizeof(float),
-                                   hipMemcpyDeviceToDevice, s));
-        const X2HLists xl = x2h_lists(l);
-        if (!overlap) {
-            if (dual) {
-                HIP_TRY(launch_node_mfma(packed + x2h_off(l), hc, lig_flag, n_nodes, w.P, w.q, w.Qt, dst, dst_n, src, src_n, s, true,
-                                         xl.gen, xl.gen_n, q_direct));
-                HIP_TRY(launch_edge_x2h_dual(packed + x2h_off(l), xc, hc, w.P, w.Qt, w.q, w.nbr, w.deg, lig_flag, gen_flag, w.e_w,
-                                             n_nodes, hn, xl.pp, xl.pp_n, xl.gen, xl.gen_n, xl.full, s));
-            } else {
-                HIP_TRY(launch_attention(true, packed + x2h_off(l), xc, hc, w.nbr, w.deg, lig_flag, gen_flag, w.e_w, n_nodes,
-                                         w.P, w.Qt, w.q, hn, nullptr, dst, dst_n, src, src_n, s));
-            }
-            HIP_TRY(launch_attention(false, packed + h2x_off(l), xc, hn, w.nbr, w.deg, lig_flag, gen_flag, w.e_w, n_nodes,
-                                     w.P, w.Qt, w.q, xn, nullptr, w.act, w.act_count, w.rf_list[0], w.rf_count, s));
-        } else {
-            const int set = l & 1;
-            if (l > 0) HIP_TRY(hipStreamWaitEvent(s, aux->join, 0));       // node stage of this layer (aux stream) done
-            HIP_TRY(launch_edge_x2h_dual(packed + x2h_off(l), xc, hc, Pset[set], Qtset[set], qset[set], w.nbr, w.deg, lig_flag,
-                                         gen_flag, w.e_w, n_nodes, hn, xl.pp, xl.pp_n, xl.gen, xl.gen_n, xl.full, s));
-            if (l + 1 < num_layers) {
-                const int *d2, *d2n, *s2, *s2n;
-                layer_lists(l + 1, d2, d2n, s2, s2n);
-                HIP_TRY(hipEventRecord(aux->fork, s));
-                HIP_TRY(hipStreamWaitEvent(aux->s, aux->fork, 0));
-                const X2HLists xn = x2h_lists(l + 1);
-                HIP_TRY(launch_node_mfma(packed + x2h_off(l + 1), hn, lig_flag, n_nodes, Pset[set ^ 1], qset[set ^ 1],
-                                         Qtset[set ^ 1], d2, d2n, s2, s2n, aux->s, true, xn.gen, xn.gen_n, q_direct));
-                HIP_TRY(hipEventRecord(aux->join, aux->s));
-            }
-            HIP_TRY(launch_attention(false, packed + h2x_off(l), xc, hn, w.nbr, w.deg, lig_flag, gen_flag, w.e_w, n_nodes,
-                                     w.P3, w.Qt3, w.q3, xn, nullptr, w.act, w.act_count, w.rf_list[0], w.rf_count, s));
-        }
-        xc = xn;
-        hc = hn;
-    }
-    }   // two-stream / serial schedules
-    if (logits) {
-        const float* c = packed + cls_off(num_layers);
-        // pruned mode: logits are only defined on ligand rows, which are a subset of A1 (rf_list[0])
-        const int* rows = prune ? w.rf_list[0] : nullptr;
-        const int* n_rows = prune ? w.rf_count : nullptr;
-        HIP_TRY(launch_node_gemm(hc, H, c + C_W0T, c + C_B0, w.P, H, n_nodes, H, 1, s, rows, n_rows));
-        HIP_TRY(launch_node_gemm(w.P, H, c + C_W1T, c + cls_b1(num_classes), logits, num_classes, n_nodes,
-                                 num_classes, 0, s, rows, n_rows));
-    }
-    return CBGX_OK;
+    int rc;
+    if (f.dual && f.num_layers > 1 && f.n_nodes <= fuse_rows && f.n_nodes <= NODE_STAGE_MAX_ROWS) rc = forward_fused(f);
+    else if (aux) rc = forward_two_streams(f, aux);
+    else rc = forward_serial(f);
+    if (rc || !f.logits) return rc;
+    // on what the last layer wrote (begin_layer).  Pruned mode: logits are only defined on ligand rows, which are a subset of A1
+    return classifier_head(f.packed, f.num_layers, f.num_classes, f.h_out ? f.h_out : f.w.hbuf[(f.num_layers - 1) & 1], f.n_nodes,
+                           f.w.set[0].P, f.logits, f.prune ? f.w.A1 : NodeList{nullptr, nullptr}, f.s);
 }
 
 int cbgx_unitransformer_forward(const float* packed, int num_layers, int num_classes, const float* x, const float* h,
                                 const int32_t* graph_ptr, const uint8_t* lig_flag, const uint8_t* gen_flag,
                                 int n_nodes, int n_graphs, float* x_out, float* h_out, float* logits, void* workspace,
                                 size_t workspace_bytes, void* stream) {
-    return forward_impl(packed, num_layers, num_classes, x, h, graph_ptr, lig_flag, gen_flag, n_nodes, n_graphs, x_out,
-                        h_out, logits, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, workspace, workspace_bytes,
-                        stream);
+    return forward_impl(Forward{packed, num_layers, num_classes, x, h, graph_ptr, lig_flag, gen_flag, n_nodes, n_graphs, x_out,
+                                h_out, logits, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, workspace, workspace_bytes,
+                                (hipStream_t)stream});
 }
 
 int cbgx_unitransformer_forward_cached(const float* packed, int num_layers, int num_classes, const float* x,
@@ -821,9 +817,9 @@ int cbgx_unitransformer_forward_cached(const float* packed, int num_layers, int 
                                        const float* static_ew, const float* static_r32sq, float* x_out, float* h_out,
                                        float* logits, unsigned flags, void* workspace, size_t workspace_bytes, void* stream) {
     if (!static_h1 || !static_h2) return fail(CBGX_E_INVALID, "forward_cached: NULL static context");
-    return forward_impl(packed, num_layers, num_classes, x, h, graph_ptr, lig_flag, gen_flag, n_nodes, n_graphs, x_out,
-                        h_out, logits, static_h1, static_h2, static_nbr, static_deg, static_ew, static_r32sq, flags, workspace,
-                        workspace_bytes, stream);
+    return forward_impl(Forward{packed, num_layers, num_classes, x, h, graph_ptr, lig_flag, gen_flag, n_nodes, n_graphs, x_out,
+                                h_out, logits, static_h1, static_h2, static_nbr, static_deg, static_ew, static_r32sq, flags, workspace,
+                                workspace_bytes, (hipStream_t)stream});
 }
 
 int cbgx_targetdiff_prologue(const float* x_lig, const float* c_lig, const int32_t* lig_rows, int n_lig, int num_classes,

@@ -15,6 +15,7 @@
 #include "kernels.h"
 #include "layout.h"
 #include "train.h"
+#include "workspace.h"
 
 using namespace cbgx;
 
@@ -30,8 +31,6 @@ namespace cbgx { int set_error(int code, const char* fmt, ...); }
         int _rc = (expr);    \
         if (_rc) return _rc; \
     } while (0)
-
-static inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // Neighbour-row gradients of the x2h edge backward: 0 = fp32 atomics on dP (default: the faster training step), 1 = edge rows + a gather
 // in a fixed order (train_scatter.hip): the kernel is 10 % faster (750 vs 832 us per 16.5 k-node launch) and dL/dh becomes reproducible
@@ -74,18 +73,16 @@ struct Tape {
 
 static Tape carve_tape(void* base, int n, int L) {
     Tape t;
-    size_t off = 0;
-    char* b = (char*)base;
-    auto take = [&](size_t bytes) { char* p = b + off; off += align_up(bytes); return p; };
+    Carver c(base);
     const size_t N = (size_t)(n > 0 ? n : 1);
-    t.nbr = (int32_t*)take(N * KNN * 4);
-    t.deg = (int32_t*)take(N * 4);
-    t.e_w = (float*)take(N * KNN * 4);
-    t.xs = (float*)take((size_t)(L + 1) * N * 3 * 4);
-    t.hs = (float*)take((size_t)(L + 1) * N * H * 4);
-    t.P = (float*)take((size_t)2 * L * N * PROW * 4);
-    t.Qt = (float*)take((size_t)2 * L * N * HEADS * H * 4);
-    t.total = off;
+    t.nbr = c.take<int32_t>(N * KNN * 4);
+    t.deg = c.take<int32_t>(N * 4);
+    t.e_w = c.take<float>(N * KNN * 4);
+    t.xs = c.take<float>((size_t)(L + 1) * N * 3 * 4);
+    t.hs = c.take<float>((size_t)(L + 1) * N * H * 4);
+    t.P = c.take<float>((size_t)2 * L * N * PROW * 4);
+    t.Qt = c.take<float>((size_t)2 * L * N * HEADS * H * 4);
+    t.total = c.off;
     return t;
 }
 
@@ -123,63 +120,61 @@ static size_t partial_floats_needed() {
 
 static TrainWs carve_train(void* base, int n) {
     TrainWs w;
-    size_t off = 0;
-    char* b = (char*)base;
-    auto take = [&](size_t bytes) { char* p = b + off; off += align_up(bytes); return p; };
+    Carver c(base);
     const size_t N = (size_t)(n > 0 ? n : 1);
-    w.P = (float*)take(N * PROW * 4);
-    w.Qt = (float*)take(N * HEADS * H * 4);
-    w.Gt = (float*)take(N * HEADS * H * 4);
-    w.T = (float*)take(N * HEADS * H * 4);
-    w.S = (float*)take(N * HEADS * H * 4);
-    w.gb = (float*)take(N * HEADS * 4);
-    w.sw = (float*)take(N * HEADS * 4);
-    w.qs = (float*)take(N * H * 4);
-    w.dqb = (float*)take(N * H * 4);
-    w.zb = (float*)take(N * H * 4);
-    w.dP = (float*)take(N * PROW * 4 + 256);      // + the x2h edge backward's work counters: zeroed by the same fill
-    w.gh = (float*)take(N * H * 4);
-    w.gx[0] = (float*)take(N * 3 * 4);
-    w.gx[1] = (float*)take(N * 3 * 4);
-    w.de_w = (float*)take(N * KNN * 4);
-    w.tmp = (float*)take(N * H * 4);
-    w.act = (int*)take(N * 4);
-    w.act_count = (int*)take(256);
-    w.mask = (uint8_t*)take(N);
-    w.rf_list[0] = (int*)take(N * 4);
-    w.rf_list[1] = (int*)take(N * 4);
-    w.rf_count = (int*)take(256);
-    w.lig_list = (int*)take(N * 4);
+    w.P = c.take<float>(N * PROW * 4);
+    w.Qt = c.take<float>(N * HEADS * H * 4);
+    w.Gt = c.take<float>(N * HEADS * H * 4);
+    w.T = c.take<float>(N * HEADS * H * 4);
+    w.S = c.take<float>(N * HEADS * H * 4);
+    w.gb = c.take<float>(N * HEADS * 4);
+    w.sw = c.take<float>(N * HEADS * 4);
+    w.qs = c.take<float>(N * H * 4);
+    w.dqb = c.take<float>(N * H * 4);
+    w.zb = c.take<float>(N * H * 4);
+    w.dP = c.take<float>(N * PROW * 4 + 256);      // + the x2h edge backward's work counters: zeroed by the same fill
+    w.gh = c.take<float>(N * H * 4);
+    w.gx[0] = c.take<float>(N * 3 * 4);
+    w.gx[1] = c.take<float>(N * 3 * 4);
+    w.de_w = c.take<float>(N * KNN * 4);
+    w.tmp = c.take<float>(N * H * 4);
+    w.act = c.take<int>(N * 4);
+    w.act_count = c.take<int>(256);
+    w.mask = c.take<uint8_t>(N);
+    w.rf_list[0] = c.take<int>(N * 4);
+    w.rf_list[1] = c.take<int>(N * 4);
+    w.rf_count = c.take<int>(256);
+    w.lig_list = c.take<int>(N * 4);
     w.partial_floats = partial_floats_needed();
-    w.partial = (float*)take(w.partial_floats * 4);
-    w.folded = (float*)take((size_t)FOLD * H * PROW * 4);
-    w.qln = (float*)take((size_t)QLN_SLOTS * 2 * H * 4);
-    w.partial_node = (float*)take((size_t)NODE_GRID * NS_SIZE * 4);
-    w.partial_wgrad = (float*)take((size_t)MAX_SPLITS * H * PROW * 4);
-    w.folded_node = (float*)take((size_t)FOLD * NS_SIZE * 4);
-    w.folded_wgrad = (float*)take((size_t)FOLD * H * PROW * 4);
-    w.nk = (float*)take(BX_NK_FLOATS * 4);     // x2h edge backward: the key path of every wave in flight, parked between two phases
-    w.gate_partial = (float*)take((size_t)GATE_GRID * GB_SIZE * 4);
-    w.gate_folded = (float*)take((size_t)FOLD * GB_SIZE * 4);
-    w.dE = (float*)take(N * KNN * 2 * H * 4);
-    w.rin_cnt = (int*)take(N * 4);
-    w.rin_ptr = (int*)take((N + 1) * 4);
-    w.rin_tmp = (int*)take(N * KNN * 4);
-    w.rin_edge = (int*)take(N * KNN * 4);
-    w.T2 = (float*)take(N * HEADS * H * 4);
-    w.S2 = (float*)take(N * HEADS * H * 4);
-    w.sw2 = (float*)take(N * HEADS * 4);
-    w.qs2 = (float*)take(N * H * 4);
-    w.dqb2 = (float*)take(N * H * 4);
-    w.zb2 = (float*)take(N * H * 4);
-    w.dP2 = (float*)take(N * PROW * 4 + 256);
-    w.partial2 = (float*)take(w.partial_floats * 4);
-    w.folded2 = (float*)take((size_t)FOLD * H * PROW * 4);
-    w.partial_node2 = (float*)take((size_t)NODE_GRID * NS_SIZE * 4);
-    w.partial_wgrad2 = (float*)take((size_t)MAX_SPLITS * H * PROW * 4);
-    w.folded_node2 = (float*)take((size_t)FOLD * NS_SIZE * 4);
-    w.folded_wgrad2 = (float*)take((size_t)FOLD * H * PROW * 4);
-    w.total = off;
+    w.partial = c.take<float>(w.partial_floats * 4);
+    w.folded = c.take<float>((size_t)FOLD * H * PROW * 4);
+    w.qln = c.take<float>((size_t)QLN_SLOTS * 2 * H * 4);
+    w.partial_node = c.take<float>((size_t)NODE_GRID * NS_SIZE * 4);
+    w.partial_wgrad = c.take<float>((size_t)MAX_SPLITS * H * PROW * 4);
+    w.folded_node = c.take<float>((size_t)FOLD * NS_SIZE * 4);
+    w.folded_wgrad = c.take<float>((size_t)FOLD * H * PROW * 4);
+    w.nk = c.take<float>(BX_NK_FLOATS * 4);     // x2h edge backward: the key path of every wave in flight, parked between two phases
+    w.gate_partial = c.take<float>((size_t)GATE_GRID * GB_SIZE * 4);
+    w.gate_folded = c.take<float>((size_t)FOLD * GB_SIZE * 4);
+    w.dE = c.take<float>(N * KNN * 2 * H * 4);
+    w.rin_cnt = c.take<int>(N * 4);
+    w.rin_ptr = c.take<int>((N + 1) * 4);
+    w.rin_tmp = c.take<int>(N * KNN * 4);
+    w.rin_edge = c.take<int>(N * KNN * 4);
+    w.T2 = c.take<float>(N * HEADS * H * 4);
+    w.S2 = c.take<float>(N * HEADS * H * 4);
+    w.sw2 = c.take<float>(N * HEADS * 4);
+    w.qs2 = c.take<float>(N * H * 4);
+    w.dqb2 = c.take<float>(N * H * 4);
+    w.zb2 = c.take<float>(N * H * 4);
+    w.dP2 = c.take<float>(N * PROW * 4 + 256);
+    w.partial2 = c.take<float>(w.partial_floats * 4);
+    w.folded2 = c.take<float>((size_t)FOLD * H * PROW * 4);
+    w.partial_node2 = c.take<float>((size_t)NODE_GRID * NS_SIZE * 4);
+    w.partial_wgrad2 = c.take<float>((size_t)MAX_SPLITS * H * PROW * 4);
+    w.folded_node2 = c.take<float>((size_t)FOLD * NS_SIZE * 4);
+    w.folded_wgrad2 = c.take<float>((size_t)FOLD * H * PROW * 4);
+    w.total = c.off;
     return w;
 }
 
@@ -851,13 +846,12 @@ size_t cbgx_h2x_stack_tape_bytes(int n_nodes, int num_layers) {
 struct StackTape { int32_t* nbr; int32_t* deg; float* e_w; float* xs; };
 static StackTape carve_stack_tape(void* base, int n) {
     StackTape t;
-    char* b = (char*)base;
-    size_t off = 0;
+    Carver c(base);
     const size_t N = (size_t)(n > 0 ? n : 1);
-    t.nbr = (int32_t*)(b + off); off += align_up(N * KNN * 4);
-    t.deg = (int32_t*)(b + off); off += align_up(N * 4);
-    t.e_w = (float*)(b + off); off += align_up(N * KNN * 4);
-    t.xs = (float*)(b + off);
+    t.nbr = c.take<int32_t>(N * KNN * 4);
+    t.deg = c.take<int32_t>(N * 4);
+    t.e_w = c.take<float>(N * KNN * 4);
+    t.xs = (float*)(c.base + c.off);      // (L + 1 coordinate sets: cbgx_h2x_stack_tape_bytes)
     return t;
 }
 

@@ -251,6 +251,56 @@ def test_merge_without_the_fused_gate_gives_the_same_graph_stage(model):
     assert theirs == "PROBE " + " ".join(mine)
 
 
+# ---- the schedules behind CBGX_FUSE_ROWS / CBGX_OVERLAP -----------------------------------------------------------------------------
+def schedule_digests(model, names):
+    """one line per (batch, variant): digests of x_out, the ligand rows of the logits and h_out where the variant defines it (all rows;
+    the A1 rows under CBGX_FWD_H_ON_SOURCES; nothing without h_out) -- every call on a fresh poisoned workspace and NaN outputs"""
+    lines = []
+    for name in names:
+        d = on_device(model, name)
+        lig = d["lig"].bool()
+        a1 = torch.from_numpy(lattice.list_definitions(d["b"])["A1"]).long().to(DEV)
+        for variant in VARIANTS:
+            xo, ho, lo, _ = run(d, variant)
+            assert bool(torch.isfinite(xo).all()) and bool(torch.isfinite(lo[lig]).all()), (name, variant)
+            parts = [xo, lo[lig]] + ([] if ho is None else [ho[a1] if variant == "h_on_sources" else ho])
+            lines.append(f"PROBE {name} {variant} {digest(*parts)}")
+    return lines
+
+
+_SCHEDULE_PROBE = r"""
+import sys, torch
+import cbgbench_amd as C
+from oracle import weights as W
+from tests import test_gpu_forward_lists as T
+m = C.get_model(C.default_targetdiff_config(13)).eval()
+m.load_state_dict(W.synthetic_state_dict(13, 9, seed=0), strict=True)
+print("\n".join(T.schedule_digests(m.to(T.DEV), sys.argv[1:])))
+"""
+
+SCHEDULES = [      # (environment of the child, batches): the schedule those calls then take
+    ({"CBGX_FUSE_ROWS": "0"}, ["small", "at_threshold"]),                 # two streams at inputs the fused schedule normally takes
+    ({"CBGX_OVERLAP": "0"}, ["above_threshold"]),                         # serial, launch_node_mfma's large-input chain
+    ({"CBGX_FUSE_ROWS": "0", "CBGX_OVERLAP": "0"}, ["small"]),            # serial at a small input
+]
+
+
+def test_two_stream_and_serial_schedules_give_the_default_schedules_bits(model):
+    """CBGX_FUSE_ROWS=0 (no fused one-stream schedule) and CBGX_OVERLAP=0 (no auxiliary stream) are read once per process: three child
+    processes, one after another, run the six variants under them and print digests of x_out, the ligand logits and h_out, which
+    must equal this process's (default schedule: fused up to 8192 nodes, two streams above) bit for bit.  Measured on an MI355X before
+    the host path was split into its parts and after: 12 of 12, 6 of 6 and 6 of 6 digests equal -- the three schedules agree in every bit."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for env, names in SCHEDULES:
+        mine = schedule_digests(model, names)
+        r = subprocess.run([sys.executable, "-c", _SCHEDULE_PROBE] + names, capture_output=True, text=True, timeout=300,
+                           env=dict(os.environ, **env), cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        theirs = [ln for ln in r.stdout.splitlines() if ln.startswith("PROBE ")]
+        print(f"MEASURED {env}: {sum(a == b for a, b in zip(mine, theirs))} of {len(mine)} (batch, variant) digests equal")
+        assert theirs == mine, (env, [f"{a} != {b}" for a, b in zip(mine, theirs) if a != b])
+
+
 # ---- the node lists --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("variant", ["cached_graph_pruned", "plain"])
 @pytest.mark.parametrize("name", BATCHES)
