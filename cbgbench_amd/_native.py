@@ -45,6 +45,13 @@ EXPORTS = {
                                   _vp, _vp]),
     "cbgx_diffsbdd_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_float, ctypes.c_float,
                                 ctypes.c_float, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cbgx_noise_fill": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "cbgx_targetdiff_epilogue_rng": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.POINTER(_vp), _vp, _vp, _vp, _i, _i,
+                                          _vp, _vp, _vp, _vp]),
+    "cbgx_targetdiff_step_boundary_rng": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.POINTER(_vp), _vp, _vp, _vp, _i,
+                                               _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cbgx_targetdiff_epilogue_traj_rng": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, ctypes.POINTER(_vp), _vp, _vp, _vp, _i, _i,
+                                               _vp]),
     "cbgx_targetdiff_train_noise": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cbgx_targetdiff_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(_vp), _vp, _vp, _vp,
                                   _vp, _vp, _vp]),

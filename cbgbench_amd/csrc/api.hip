@@ -934,4 +934,84 @@ int cbgx_targetdiff_epilogue_traj(const float* x_den, const float* logits, const
     return CBGX_OK;
 }
 
+// ---- counter-based noise (rng.h): the fill entry and the TargetDiff step entries that generate in place ------------------------------
+static int noise_args(const char* who, const uint64_t* keys, const int32_t* lig_graph, bool need_graph, const int32_t* lig_ptr,
+                      int n_graphs, int purpose_base) {
+    if (!keys || !lig_ptr || (need_graph && !lig_graph)) return fail(CBGX_E_INVALID, "%s: NULL pointer (noise)", who);
+    if (n_graphs < 1) return fail(CBGX_E_INVALID, "%s: n_graphs=%d", who, n_graphs);
+    if (purpose_base < 0 || purpose_base % CBGX_NOISE_PURPOSE_STRIDE)
+        return fail(CBGX_E_INVALID, "%s: purpose_base=%d is not a non-negative multiple of %d", who, purpose_base,
+                    CBGX_NOISE_PURPOSE_STRIDE);
+    return CBGX_OK;
+}
+
+int cbgx_noise_fill(const uint64_t* stream_keys, const int32_t* lig_ptr, int n_graphs, int n_lig, int cols, int uniform,
+                    int purpose, int step, const int32_t* step_dev, float* out, void* stream) {
+    if (n_lig == 0 || n_graphs == 0 || cols == 0) return CBGX_OK;
+    if (n_lig < 0 || n_graphs < 0 || cols < 0 || purpose < 0 || (!step_dev && step < 0))
+        return fail(CBGX_E_INVALID, "noise_fill: bad sizes (n_lig=%d B=%d cols=%d purpose=%d step=%d)", n_lig, n_graphs, cols, purpose,
+                    step);
+    if (!stream_keys || !lig_ptr || !out) return fail(CBGX_E_INVALID, "noise_fill: NULL pointer");
+    HIP_TRY(launch_noise_fill(stream_keys, lig_ptr, n_graphs, n_lig, cols, uniform, (uint32_t)purpose, step, step_dev, out,
+                              (hipStream_t)stream));
+    return CBGX_OK;
+}
+
+int cbgx_targetdiff_epilogue_rng(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
+                                 const float* c_lig, const uint8_t* gen_lig, int n_lig, int num_classes, int t,
+                                 int num_timesteps, const float* const* tables, const uint64_t* stream_keys,
+                                 const int32_t* lig_graph, const int32_t* lig_ptr, int n_graphs, int purpose_base, float* x_next,
+                                 float* c_next, int32_t* v_next, void* stream) {
+    if (n_lig == 0) return CBGX_OK;
+    if (n_lig < 0 || num_classes < 1 || num_classes > 32 || t < 0 || t >= num_timesteps)
+        return fail(CBGX_E_INVALID, "epilogue_rng: bad sizes (n_lig=%d C=%d t=%d T=%d)", n_lig, num_classes, t, num_timesteps);
+    if (!x_den || !logits || !lig_rows || !x_lig || !c_lig || !gen_lig || !tables || !x_next || !c_next)
+        return fail(CBGX_E_INVALID, "epilogue_rng: NULL pointer");
+    for (int i = 0; i < 7; ++i)
+        if (!tables[i]) return fail(CBGX_E_INVALID, "epilogue_rng: table %d is NULL", i);
+    if (int rc = noise_args("epilogue_rng", stream_keys, lig_graph, true, lig_ptr, n_graphs, purpose_base)) return rc;
+    HIP_TRY(launch_step_epilogue_rng(x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig, num_classes, t, tables,
+                                     (float)log((double)num_classes), stream_keys, lig_graph, lig_ptr, (uint32_t)purpose_base,
+                                     x_next, c_next, v_next, (hipStream_t)stream));
+    return CBGX_OK;
+}
+
+int cbgx_targetdiff_step_boundary_rng(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
+                                      const float* c_lig, const uint8_t* gen_lig, int n_lig, int num_classes, int t,
+                                      int num_timesteps, const float* const* tables, const uint64_t* stream_keys,
+                                      const int32_t* lig_graph, const int32_t* lig_ptr, int n_graphs, int purpose_base,
+                                      float* x_next, float* c_next, const float* lig_emb_w, const float* lig_emb_b,
+                                      const float* ind_w, const float* ind_b, float* x, float* h, void* stream) {
+    if (n_lig == 0) return CBGX_OK;
+    if (n_lig < 0 || num_classes < 1 || num_classes > 32 || t < 0 || t >= num_timesteps)
+        return fail(CBGX_E_INVALID, "step_boundary_rng: bad sizes (n_lig=%d C=%d t=%d T=%d)", n_lig, num_classes, t, num_timesteps);
+    if (!x_den || !logits || !lig_rows || !x_lig || !c_lig || !gen_lig || !tables || !x_next || !c_next || !lig_emb_w ||
+        !lig_emb_b || !ind_w || !ind_b || !x || !h)
+        return fail(CBGX_E_INVALID, "step_boundary_rng: NULL pointer");
+    for (int i = 0; i < 7; ++i)
+        if (!tables[i]) return fail(CBGX_E_INVALID, "step_boundary_rng: table %d is NULL", i);
+    if (int rc = noise_args("step_boundary_rng", stream_keys, lig_graph, true, lig_ptr, n_graphs, purpose_base)) return rc;
+    HIP_TRY(launch_step_boundary_rng(x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig, num_classes, t, tables,
+                                     (float)log((double)num_classes), stream_keys, lig_graph, lig_ptr, (uint32_t)purpose_base,
+                                     x_next, c_next, lig_emb_w, lig_emb_b, ind_w, ind_b, x, h, (hipStream_t)stream));
+    return CBGX_OK;
+}
+
+int cbgx_targetdiff_epilogue_traj_rng(const float* x_den, const float* logits, const int32_t* lig_rows, float* traj_x,
+                                      float* traj_c, const uint8_t* gen_lig, int n_lig, int num_classes, int32_t* t_dev,
+                                      const float* const* tables, const uint64_t* stream_keys, const int32_t* lig_graph,
+                                      const int32_t* lig_ptr, int n_graphs, int purpose_base, void* stream) {
+    if (n_lig == 0) return CBGX_OK;
+    if (n_lig < 0 || num_classes < 1 || num_classes > 32) return fail(CBGX_E_INVALID, "epilogue_traj_rng: bad sizes");
+    if (!x_den || !logits || !lig_rows || !traj_x || !traj_c || !gen_lig || !t_dev || !tables)
+        return fail(CBGX_E_INVALID, "epilogue_traj_rng: NULL pointer");
+    for (int i = 0; i < 7; ++i)
+        if (!tables[i]) return fail(CBGX_E_INVALID, "epilogue_traj_rng: table %d is NULL", i);
+    if (int rc = noise_args("epilogue_traj_rng", stream_keys, lig_graph, true, lig_ptr, n_graphs, purpose_base)) return rc;
+    HIP_TRY(launch_step_epilogue_rng(x_den, logits, lig_rows, traj_x, traj_c, gen_lig, n_lig, num_classes, 0, tables,
+                                     (float)log((double)num_classes), stream_keys, lig_graph, lig_ptr, (uint32_t)purpose_base,
+                                     traj_x, traj_c, nullptr, (hipStream_t)stream, t_dev));
+    return CBGX_OK;
+}
+
 }  // extern "C"

@@ -205,6 +205,19 @@ hipError_t launch_step_boundary(const float* x_den, const float* logits, const i
                                 const float* c_lig, const uint8_t* gen_lig, int n_lig, int C, int t, const float* const* tabs,
                                 float log_c, const float* eps, const float* u, float* x_next, float* c_next, const float* emb_w,
                                 const float* emb_b, const float* ind_w, const float* ind_b, float* x, float* h, hipStream_t s);
+// the same two with the counter-based generator of rng.h in place of eps / u, and the fill kernel that writes the same numbers out
+hipError_t launch_step_epilogue_rng(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
+                                    const float* c_lig, const uint8_t* gen_lig, int n_lig, int C, int t,
+                                    const float* const* tabs, float log_c, const uint64_t* keys, const int32_t* lig_graph,
+                                    const int32_t* lig_ptr, uint32_t purpose_base, float* x_next, float* c_next, int32_t* v_next,
+                                    hipStream_t s, int32_t* t_ptr = nullptr);
+hipError_t launch_step_boundary_rng(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
+                                    const float* c_lig, const uint8_t* gen_lig, int n_lig, int C, int t, const float* const* tabs,
+                                    float log_c, const uint64_t* keys, const int32_t* lig_graph, const int32_t* lig_ptr,
+                                    uint32_t purpose_base, float* x_next, float* c_next, const float* emb_w, const float* emb_b,
+                                    const float* ind_w, const float* ind_b, float* x, float* h, hipStream_t s);
+hipError_t launch_noise_fill(const uint64_t* keys, const int32_t* lig_ptr, int n_graphs, int n_lig, int cols, int uniform,
+                             uint32_t purpose, int step, const int32_t* step_ptr, float* out, hipStream_t s);
 hipError_t launch_diffbp_epilogue(const float* x_den, const float* x_com, const float* x_in, const float* logits,
                                   const int32_t* lig_rows, const int32_t* lig_ptr, const float* x_lig, const float* c_lig,
                                   const uint8_t* gen_lig, int n_graphs, int C, int t, int T, const float* acp_tab,

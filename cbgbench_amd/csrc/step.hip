@@ -6,16 +6,59 @@
 //             atom types TypeVPScheduler.backward_remove_noise(pred_logit=True) :367-378, 407-441 + Gumbel argmax
 //                        (models/utils/categorical.py:26-32)
 // DiffBP (diffbp_epilogue_kernel) and DiffSBDD (diffsbdd_step_kernel): one kernel per step each, one wave per graph.
-// Noise (eps ~ N(0,1), u ~ U(0,1)) is an input, so the host decides the generator and tests can replay a tape.
+// Noise (eps ~ N(0,1), u ~ U(0,1)) has two sources.  NoiseTape: an input, so the host decides the generator and tests can replay a
+// tape (every class).  NoiseCounter: the TargetDiff kernels evaluate the counter-based generator of rng.h themselves, at the address
+// (graph's stream key, atom's index in its ligand, step, purpose, component) -- the numbers cbgx_noise_fill (noise_fill_kernel below)
+// writes for the same address, bit for bit; DiffBP and DiffSBDD take that mode through noise_fill_kernel and their tape kernels.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "kernels.h"
 #include "layout.h"
+#include "rng.h"
 
 namespace cbgx {
 
 constexpr int MAXC = 32;
+
+// ---- noise sources of step_epilogue_kernel / step_boundary_kernel: component k of atom a's position normal / type uniform at step t.
+// A source names the types of the two kernel arguments that stand where eps / u stand; what else it needs travels as trailing kernel
+// arguments (`Extra...`: none for the tape).  The tape's reads are written out in the kernels (`if constexpr`), not behind a call, so
+// that its instantiations are the kernels as they were before there was a second source, instruction for instruction.
+struct NoiseTape {
+    typedef const float* P0;      // eps [n_lig][3]
+    typedef const float* P1;      // u [n_lig][C]
+    static constexpr bool counter = false;
+};
+
+struct NoiseCounter {
+    typedef const uint64_t* P0;   // keys [B]: stream key of every graph
+    typedef const int32_t* P1;    // lig_graph [n_lig]: graph of every ligand atom
+    static constexpr bool counter = true;
+    struct Extra {
+        const int32_t* lig_ptr;   // [B+1] ligand CSR: atom a is atom a - lig_ptr[graph] of its ligand
+        uint32_t base;            // purpose base
+    };
+    // an atom's part of the address, looked up once per atom: the graph's key, the atom's index in its ligand, the purpose base
+    struct Atom {
+        uint64_t key;
+        uint32_t local, base;
+        __device__ __forceinline__ rng::Words words(int t, uint32_t purpose, int block) const {
+            return rng::draw(key, local, (uint32_t)t, base + purpose, (uint32_t)block);
+        }
+    };
+    static __device__ __forceinline__ Atom atom(P0 keys, P1 lig_graph, int a, Extra e) {
+        const int g = lig_graph[a];
+        return Atom{keys[g], (uint32_t)(a - e.lig_ptr[g]), e.base};
+    }
+    // one component for a lane of its own (step_boundary_kernel: lane k draws component k)
+    static __device__ __forceinline__ float pos(P0 keys, P1 lig_graph, int a, int k, int t, Extra e) {
+        return rng::normal_component(atom(keys, lig_graph, a, e).words(t, rng::POS_NORMAL, 0), k);
+    }
+    static __device__ __forceinline__ float type(P0 keys, P1 lig_graph, int a, int k, int, int t, Extra e) {
+        return rng::uniform_component(atom(keys, lig_graph, a, e).words(t, rng::TYPE_UNIFORM, k >> 2), k & 3);
+    }
+};
 
 __global__ __launch_bounds__(128) void step_prologue_kernel(const float* __restrict__ x_lig, const float* __restrict__ c_lig,
                                                             const int32_t* __restrict__ lig_rows, int n_lig, int C,
@@ -42,14 +85,15 @@ __device__ __forceinline__ float log_add_exp(float a, float b) {
     return mx + logf(expf(a - mx) + expf(b - mx));
 }
 
+template <class Noise, class... Extra>
 __global__ __launch_bounds__(256) void step_epilogue_kernel(
     const float* __restrict__ x_den, const float* __restrict__ logits, const int32_t* __restrict__ lig_rows,
     const float* __restrict__ x_lig, const float* __restrict__ c_lig, const uint8_t* __restrict__ gen_lig, int n_lig, int C,
     int t, const float* __restrict__ c0_tab, const float* __restrict__ ct_tab, const float* __restrict__ logvar_tab,
     const float* __restrict__ log_alpha, const float* __restrict__ log_1m_alpha, const float* __restrict__ log_acp,
-    const float* __restrict__ log_1m_acp, float log_c, const float* __restrict__ eps, const float* __restrict__ u,
+    const float* __restrict__ log_1m_acp, float log_c, typename Noise::P0 __restrict__ n0, typename Noise::P1 __restrict__ n1,
     float* __restrict__ x_next, float* __restrict__ c_next, int32_t* __restrict__ v_next,
-    const int32_t* __restrict__ t_ptr) {
+    const int32_t* __restrict__ t_ptr, Extra... nx) {
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a >= n_lig) return;
     if (t_ptr) {   // trajectory mode: state of slot t + 1 -> slot t of the same [T+1] arrays
@@ -64,10 +108,20 @@ __global__ __launch_bounds__(256) void step_epilogue_kernel(
     // ---- positions
     const float c0 = c0_tab[t], ct = ct_tab[t];
     const float sigma = t > 0 ? expf(0.5f * logvar_tab[t]) : 0.f;
+    // counter source: this thread walks all components of its atom, so it looks the atom up once and makes one Philox call per block of
+    // four components (the position block here, the type blocks in the Gumbel loop below)
+    [[maybe_unused]] NoiseCounter::Atom na{};
+    [[maybe_unused]] rng::Words nw{};
+    if constexpr (Noise::counter) {
+        na = Noise::atom(n0, n1, a, nx...);
+        nw = na.words(t, rng::POS_NORMAL, 0);
+    }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float xt = x_lig[3 * a + k];
-        const float xs = (c0 * x_den[3 * row + k] + ct * xt) + sigma * eps[3 * a + k];
+        float xs;
+        if constexpr (Noise::counter) xs = (c0 * x_den[3 * row + k] + ct * xt) + sigma * rng::normal_component(nw, k);
+        else xs = (c0 * x_den[3 * row + k] + ct * xt) + sigma * n0[3 * a + k];
         x_next[3 * a + k] = gen ? xs : xt;
     }
     // ---- atom types
@@ -98,7 +152,13 @@ __global__ __launch_bounds__(256) void step_epilogue_kernel(
     int best = 0;
     float best_v = -INFINITY;
     for (int k = 0; k < C; ++k) {
-        const float g = -logf(-logf(u[(size_t)a * C + k] + 1e-30f) + 1e-30f);
+        float g;
+        if constexpr (Noise::counter) {
+            if ((k & 3) == 0) nw = na.words(t, rng::TYPE_UNIFORM, k >> 2);
+            g = -logf(-logf(rng::uniform_component(nw, k & 3) + 1e-30f) + 1e-30f);
+        } else {
+            g = -logf(-logf(n1[(size_t)a * C + k] + 1e-30f) + 1e-30f);
+        }
         const float s = g + (un[k] - ulse);
         if (s > best_v) { best_v = s; best = k; }
     }
@@ -114,14 +174,16 @@ __global__ __launch_bounds__(256) void step_epilogue_kernel(
 // class each -- the one-thread-per-atom epilogue walked 13 classes x 7 transcendental calls serially, 12 us for 25 atoms -- with
 // every sum over the classes taken in the serial kernel's order (a broadcast loop), so the two kernels agree bit for bit; then all
 // 128 threads write the feature row.  11.8 + 5.3 us of a 550 us one-graph step become one launch.
+template <class Noise, class... Extra>
 __global__ __launch_bounds__(128) void step_boundary_kernel(
     const float* __restrict__ x_den, const float* __restrict__ logits, const int32_t* __restrict__ lig_rows,
     const float* __restrict__ x_lig, const float* __restrict__ c_lig, const uint8_t* __restrict__ gen_lig, int n_lig, int C,
     int t, const float* __restrict__ c0_tab, const float* __restrict__ ct_tab, const float* __restrict__ logvar_tab,
     const float* __restrict__ log_alpha, const float* __restrict__ log_1m_alpha, const float* __restrict__ log_acp,
-    const float* __restrict__ log_1m_acp, float log_c, const float* __restrict__ eps, const float* __restrict__ u,
+    const float* __restrict__ log_1m_acp, float log_c, typename Noise::P0 __restrict__ n0, typename Noise::P1 __restrict__ n1,
     float* __restrict__ x_next, float* __restrict__ c_next, const float* __restrict__ emb_w, const float* __restrict__ emb_b,
-    const float* __restrict__ ind_w, const float* __restrict__ ind_b, float* __restrict__ x, float* __restrict__ h) {
+    const float* __restrict__ ind_w, const float* __restrict__ ind_b, float* __restrict__ x, float* __restrict__ h,
+    Extra... nx) {
     __shared__ float s_c[MAXC];
     const int a = blockIdx.x, m = threadIdx.x;
     if (a >= n_lig) return;
@@ -136,7 +198,9 @@ __global__ __launch_bounds__(128) void step_boundary_kernel(
             const float c0 = c0_tab[t], ct = ct_tab[t];
             const float sigma = t > 0 ? expf(0.5f * logvar_tab[t]) : 0.f;
             const float xt = x_lig[3 * a + k];
-            const float xs = (c0 * x_den[3 * row + k] + ct * xt) + sigma * eps[3 * a + k];
+            float xs;
+            if constexpr (Noise::counter) xs = (c0 * x_den[3 * row + k] + ct * xt) + sigma * Noise::pos(n0, n1, a, k, t, nx...);
+            else xs = (c0 * x_den[3 * row + k] + ct * xt) + sigma * n0[3 * a + k];
             const float xn = gen ? xs : xt;
             x_next[3 * a + k] = xn;
             x[3 * row + k] = xn;
@@ -164,7 +228,9 @@ __global__ __launch_bounds__(128) void step_boundary_kernel(
         float us = 0.f;
         for (int j = 0; j < C; ++j) us += __shfl(euk, j, 64);
         const float ulse = umx + logf(us);
-        const float g = -logf(-logf(u[(size_t)a * C + kc] + 1e-30f) + 1e-30f);
+        float g;
+        if constexpr (Noise::counter) g = -logf(-logf(Noise::type(n0, n1, a, kc, C, t, nx...) + 1e-30f) + 1e-30f);
+        else g = -logf(-logf(n1[(size_t)a * C + kc] + 1e-30f) + 1e-30f);
         const float sk = g + (un - ulse);
         // first index of the maximum (the serial scan's strict '>'): of the current type vector and of the perturbed log-posterior
         float cmx = live ? ck : -INFINITY, smx = live ? sk : -INFINITY;
@@ -191,9 +257,21 @@ hipError_t launch_step_boundary(const float* x_den, const float* logits, const i
                                 float log_c, const float* eps, const float* u, float* x_next, float* c_next, const float* emb_w,
                                 const float* emb_b, const float* ind_w, const float* ind_b, float* x, float* h, hipStream_t s) {
     if (n_lig == 0) return hipSuccess;
-    hipLaunchKernelGGL(step_boundary_kernel, dim3(n_lig), dim3(128), 0, s, x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig, C,
+    hipLaunchKernelGGL(step_boundary_kernel<NoiseTape>, dim3(n_lig), dim3(128), 0, s, x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig, C,
                        t, tabs[0], tabs[1], tabs[2], tabs[3], tabs[4], tabs[5], tabs[6], log_c, eps, u, x_next, c_next, emb_w, emb_b,
                        ind_w, ind_b, x, h);
+    return hipGetLastError();
+}
+
+hipError_t launch_step_boundary_rng(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
+                                    const float* c_lig, const uint8_t* gen_lig, int n_lig, int C, int t, const float* const* tabs,
+                                    float log_c, const uint64_t* keys, const int32_t* lig_graph, const int32_t* lig_ptr,
+                                    uint32_t purpose_base, float* x_next, float* c_next, const float* emb_w, const float* emb_b,
+                                    const float* ind_w, const float* ind_b, float* x, float* h, hipStream_t s) {
+    if (n_lig == 0) return hipSuccess;
+    hipLaunchKernelGGL((step_boundary_kernel<NoiseCounter, NoiseCounter::Extra>), dim3(n_lig), dim3(128), 0, s, x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig,
+                       C, t, tabs[0], tabs[1], tabs[2], tabs[3], tabs[4], tabs[5], tabs[6], log_c, keys, lig_graph, x_next, c_next,
+                       emb_w, emb_b, ind_w, ind_b, x, h, NoiseCounter::Extra{lig_ptr, purpose_base});
     return hipGetLastError();
 }
 
@@ -352,15 +430,62 @@ hipError_t launch_step_prologue(const float* x_lig, const float* c_lig, const in
 
 __global__ void step_counter_kernel(int32_t* t_ptr) { *t_ptr -= 1; }
 
+template <class Noise, class... Extra>
+static hipError_t step_epilogue(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
+                                const float* c_lig, const uint8_t* gen_lig, int n_lig, int C, int t,
+                                const float* const* tabs, float log_c, typename Noise::P0 n0, typename Noise::P1 n1,
+                                float* x_next, float* c_next, int32_t* v_next, hipStream_t s, int32_t* t_ptr, Extra... nx) {
+    if (n_lig == 0) return hipSuccess;
+    hipLaunchKernelGGL((step_epilogue_kernel<Noise, Extra...>), dim3((n_lig + 255) / 256), dim3(256), 0, s, x_den, logits, lig_rows, x_lig,
+                       c_lig, gen_lig, n_lig, C, t, tabs[0], tabs[1], tabs[2], tabs[3], tabs[4], tabs[5], tabs[6], log_c, n0, n1,
+                       x_next, c_next, v_next, t_ptr, nx...);
+    if (t_ptr) hipLaunchKernelGGL(step_counter_kernel, dim3(1), dim3(1), 0, s, t_ptr);   // next step: t - 1
+    return hipGetLastError();
+}
+
 hipError_t launch_step_epilogue(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
                                 const float* c_lig, const uint8_t* gen_lig, int n_lig, int C, int t,
                                 const float* const* tabs, float log_c, const float* eps, const float* u, float* x_next,
                                 float* c_next, int32_t* v_next, hipStream_t s, int32_t* t_ptr) {
-    if (n_lig == 0) return hipSuccess;
-    hipLaunchKernelGGL(step_epilogue_kernel, dim3((n_lig + 255) / 256), dim3(256), 0, s, x_den, logits, lig_rows, x_lig,
-                       c_lig, gen_lig, n_lig, C, t, tabs[0], tabs[1], tabs[2], tabs[3], tabs[4], tabs[5], tabs[6], log_c, eps,
-                       u, x_next, c_next, v_next, t_ptr);
-    if (t_ptr) hipLaunchKernelGGL(step_counter_kernel, dim3(1), dim3(1), 0, s, t_ptr);   // next step: t - 1
+    return step_epilogue<NoiseTape>(x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig, C, t, tabs, log_c, eps, u,
+                                    x_next, c_next, v_next, s, t_ptr);
+}
+
+hipError_t launch_step_epilogue_rng(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
+                                    const float* c_lig, const uint8_t* gen_lig, int n_lig, int C, int t,
+                                    const float* const* tabs, float log_c, const uint64_t* keys, const int32_t* lig_graph,
+                                    const int32_t* lig_ptr, uint32_t purpose_base, float* x_next, float* c_next, int32_t* v_next,
+                                    hipStream_t s, int32_t* t_ptr) {
+    return step_epilogue<NoiseCounter>(x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig, C, t, tabs, log_c, keys, lig_graph,
+                                       x_next, c_next, v_next, s, t_ptr, NoiseCounter::Extra{lig_ptr, purpose_base});
+}
+
+// ---- cbgx_noise_fill: the draws of one purpose and one step for every ligand atom, out[a][col] = component col of atom a.
+// One workgroup per graph; a thread takes one (atom, block) pair = one Philox call = up to four components.
+__global__ __launch_bounds__(256) void noise_fill_kernel(const uint64_t* __restrict__ keys, const int32_t* __restrict__ lig_ptr,
+                                                         int n_lig, int cols, int uniform, uint32_t purpose, int step,
+                                                         const int32_t* __restrict__ step_ptr, float* __restrict__ out) {
+    const int g = blockIdx.x;
+    const int a0 = max(lig_ptr[g], 0), a1 = min(lig_ptr[g + 1], n_lig);
+    if (step_ptr) step = *step_ptr;
+    const uint64_t key = keys[g];
+    const int nblk = (cols + 3) >> 2;
+    for (int i = threadIdx.x; i < (a1 - a0) * nblk; i += blockDim.x) {
+        const int la = i / nblk, b = i - la * nblk;
+        const rng::Words o = rng::draw(key, (uint32_t)la, (uint32_t)step, purpose, (uint32_t)b);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int col = 4 * b + j;
+            if (col < cols) out[(size_t)(a0 + la) * cols + col] = uniform ? rng::uniform_component(o, j) : rng::normal_component(o, j);
+        }
+    }
+}
+
+hipError_t launch_noise_fill(const uint64_t* keys, const int32_t* lig_ptr, int n_graphs, int n_lig, int cols, int uniform,
+                             uint32_t purpose, int step, const int32_t* step_ptr, float* out, hipStream_t s) {
+    if (n_graphs == 0 || n_lig == 0 || cols == 0) return hipSuccess;
+    hipLaunchKernelGGL(noise_fill_kernel, dim3(n_graphs), dim3(256), 0, s, keys, lig_ptr, n_lig, cols, uniform, purpose, step,
+                       step_ptr, out);
     return hipGetLastError();
 }
 

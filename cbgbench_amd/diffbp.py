@@ -14,6 +14,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _native
+from . import noise as _noise
 from .registry import get_e3_gnn, register_model
 from .targetdiff import (NUM_AA, BatchesInFlight, CTNVPScheduler, PLContextEmbedder, TargetDiff, compose_embed, masked_graph_mean,
                          scatter_mean)
@@ -471,10 +472,12 @@ class DiffBP(BatchesInFlight, nn.Module):
         return {"pos": loss_pos, "atom": loss_atom, "com": loss_com, "inter": loss_inter}, results
 
     @torch.no_grad()
-    def begin_sampling(self, batch, keep_trajectory=True, static_cache=True):
+    def begin_sampling(self, batch, keep_trajectory=True, static_cache=True, noise=None):
         """Step-invariant part of ``sample`` (diffbp.py:240-262): composition plan, protein rows of x / h, flags -- and, as in
         TargetDiff.begin_sampling, the static-context cache of the denoiser (the pocket never moves in DiffBP either: what the
-        ligand-free pocket produces in layers 0 / 1, its neighbour lists and gate values are computed once per run)."""
+        ligand-free pocket produces in layers 0 / 1, its neighbour lists and gate values are computed once per run).
+        ``noise`` (a ``CounterNoise``; default: the batch's ``noise_keys``): counter mode, see cbgbench_amd/noise.py."""
+        noise = _noise.resolve(noise, batch)
         x_lig = batch["ligand_pos"].float()
         dev = x_lig.device
         x_rec = batch["protein_pos"].float()
@@ -510,17 +513,32 @@ class DiffBP(BatchesInFlight, nn.Module):
             st["lig_ptr"] = torch.cat([torch.zeros(1, dtype=torch.long, device=dev),
                                        torch.bincount(bl, minlength=B).cumsum(0)]).to(torch.int32).contiguous()
             st["x_lig"], st["c_lig"] = x_lig.contiguous(), c_lig.contiguous()
+        if noise is not None:
+            self._attach_noise(st, noise)
         if keep_trajectory:
             st["traj_x"] = torch.empty(T + 1, n_lig, 3, dtype=torch.float32, device=dev)
             st["traj_c"] = torch.empty(T + 1, n_lig, C, dtype=torch.float32, device=dev)
             st["traj_x"][T], st["traj_c"][T] = x_lig, c_lig
         return st
 
+    @staticmethod
+    def _attach_noise(st, noise):
+        if not st["native"]:
+            raise ValueError("counter noise needs the native step (GPU, denoise_structure and denoise_atom, ligand atoms sorted by graph)")
+        _noise.attach(st, noise, st["bl"], st["B"])
+
     @torch.no_grad()
     def denoise_step(self, st, t_idx, noise=None):
         """One reverse step (diffbp.py:263-296): denoiser, CoMPredictor, score step on the positions, mask-type step.
-        ``noise``: (eps [N_lig,3], u [N_lig]) replacing randn_like / rand_like."""
+        ``noise``: (eps [N_lig,3], u [N_lig]) replacing randn_like / rand_like -- or a ``CounterNoise`` for a state that has none yet
+        (counter mode: the draws come from cbgx_noise_fill at the step's addresses)."""
         dev = st["x"].device
+        if isinstance(noise, _noise.CounterNoise):
+            if st.get("noise") is None:
+                self._attach_noise(st, noise)
+            elif st["noise"] is not noise:
+                raise ValueError("denoise_step: the state already runs on another CounterNoise")
+            noise = None
         if st.get("native"):
             return self._denoise_step_native(st, t_idx, noise)
         t = torch.full((st["B"],), t_idx, dtype=torch.long, device=dev)
@@ -562,6 +580,9 @@ class DiffBP(BatchesInFlight, nn.Module):
         x_com = self.com_head.stack_forward(x, ho, st["graph_ptr"], st["lig8"], st["gen8"])
         if noise is not None:
             eps, u = noise[0].float().contiguous(), noise[1].float().contiguous()
+        elif st.get("noise") is not None:      # counter mode: position normal and mask uniform of (atom, step)
+            eps = _noise.fill(st, _noise.POS_NORMAL, t_idx, 3, uniform=False)
+            u = _noise.fill(st, _noise.MASK_UNIFORM, t_idx, 1, uniform=True).view(n_lig)
         else:   # the reference's draw order: randn_like(x_lig), then rand_like(v_t)
             eps = torch.randn(n_lig, 3, dtype=torch.float32, device=dev)
             u = torch.rand(n_lig, dtype=torch.float32, device=dev)
@@ -579,8 +600,8 @@ class DiffBP(BatchesInFlight, nn.Module):
         return st
 
     # hooks of BatchesInFlight.sample_many
-    def _many_begin(self, batch, tape):
-        return self.begin_sampling(batch, keep_trajectory=True)
+    def _many_begin(self, batch, tape, noise=None):
+        return self._begin(batch, noise, tape is not None)
 
     def _many_step(self, st, t_idx, tape):
         self.denoise_step(st, t_idx, tape[t_idx] if tape is not None else None)
@@ -591,10 +612,13 @@ class DiffBP(BatchesInFlight, nn.Module):
         return {t - 1: (traj_x[t], traj_c[t], bl_out) for t in range(T + 1)}
 
     @torch.no_grad()
-    def sample(self, batch, noise_tape=None, return_device=None):
-        """diffbp.py:240-299. ``noise_tape``: dict t -> (eps [N_lig,3], u [N_lig]) replacing randn_like / rand_like."""
+    def sample(self, batch, noise_tape=None, return_device=None, noise=None):
+        """diffbp.py:240-299. ``noise_tape``: dict t -> (eps [N_lig,3], u [N_lig]) replacing randn_like / rand_like.
+        ``noise`` (a ``CounterNoise``; default: the batch's ``noise_keys``): counter mode; not together with ``noise_tape``."""
+        if noise is not None and noise_tape is not None:
+            raise ValueError("sample: noise= (counter mode) and noise_tape (replay) exclude each other")
         T = self.num_diffusion_timesteps
-        st = self.begin_sampling(batch, keep_trajectory=True)
+        st = self._begin(batch, noise, noise_tape is not None)
         for t_idx in reversed(range(T)):
             self.denoise_step(st, t_idx, noise_tape[t_idx] if noise_tape is not None else None)
         out_dev = torch.device("cpu") if return_device is None else torch.device(return_device)

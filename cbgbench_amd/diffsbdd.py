@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _native
+from . import noise as _noise
 from .registry import get_e3_gnn, register_model
 from .targetdiff import NUM_AA, BatchesInFlight, PLContextEmbedder, TargetDiff, compose_embed
 
@@ -369,9 +370,11 @@ class DiffSBDD(BatchesInFlight, nn.Module):
         return {"pos": loss_pos, "atom": loss_atom}, results
 
     @torch.no_grad()
-    def begin_sampling(self, batch, keep_trajectory=True, noise_draws=None, static_cache=True):
+    def begin_sampling(self, batch, keep_trajectory=True, noise_draws=None, static_cache=True, noise=None):
         """Everything of ``sample`` (diffsbdd.py:240-319) before the loop: composition plan, protein features, the initial
         zero-COM draws.  ``noise_draws`` (tests): the randn tensors in the reference's draw order, consumed across the steps.
+        ``noise`` (a ``CounterNoise``; default: the batch's ``noise_keys``; not together with ``noise_draws``): counter mode -- the
+        initial draws, every step's two draws and the final draw come from cbgx_noise_fill at their addresses (cbgbench_amd/noise.py).
         ``static_cache`` (native step only): keep the composed coordinates in the pocket's own frame -- the reference translates the
         whole pocket by the ligand's new centre of mass every step (diffsbdd.py:296-304), a rigid motion that changes neither the
         pocket's neighbour lists, nor its gate values, nor its ligand-free layer-0/1 features -- and carry the accumulated
@@ -388,6 +391,9 @@ class DiffSBDD(BatchesInFlight, nn.Module):
         T, C = self.num_diffusion_timesteps, self.num_classes
         B = int(bl.max().item()) + 1
         n_lig, n_rec = bl.shape[0], x_rec.shape[0]
+        if noise is not None and noise_draws is not None:
+            raise ValueError("begin_sampling: noise= (counter mode) and noise_draws (replay) exclude each other")
+        noise = _noise.resolve(noise, batch) if noise_draws is None else None
         draws = iter(noise_draws) if noise_draws is not None else None
         nxt = (lambda: next(draws).to(dev)) if draws is not None else (lambda: None)
         aa = F.one_hot(batch["protein_aa_type"], NUM_AA).float()
@@ -402,12 +408,23 @@ class DiffSBDD(BatchesInFlight, nn.Module):
         mu_x = sch.scatter_mean(x_rec, br, B, br_ordered)[bl]
         mu_h = torch.zeros(B, C, device=dev)[bl]
         sigma1 = torch.ones(B, 1, device=dev)
-        x_lig, x_rec = sch.sample_normal_zero_com(mu_x, x_rec, sigma1, bl, br, B, com=True, eps=nxt(), ordered=bl_ordered)
-        c_lig = sch.sample_normal_zero_com(mu_h, v_rec, sigma1, bl, br, B, com=False, eps=nxt())
+        cn = {}
+        if noise is not None:
+            if not (dev.type == "cuda" and bl_ordered):
+                raise ValueError("counter noise needs the native step (GPU, ligand atoms sorted by graph)")
+            _noise.attach(cn, noise, bl, B)
+            eps_x0 = _noise.fill(cn, _noise.INIT_POS, 0, 3, uniform=False)
+            eps_c0 = _noise.fill(cn, _noise.INIT_TYPE, 0, C, uniform=False)
+        else:
+            eps_x0 = nxt()
+            eps_c0 = nxt()
+        x_lig, x_rec = sch.sample_normal_zero_com(mu_x, x_rec, sigma1, bl, br, B, com=True, eps=eps_x0, ordered=bl_ordered)
+        c_lig = sch.sample_normal_zero_com(mu_h, v_rec, sigma1, bl, br, B, com=False, eps=eps_c0)
         st = {"B": B, "N": n_rec + n_lig, "n_lig": n_lig, "x": x, "h": h, "x_lig": x_lig, "c_lig": c_lig, "x_rec": x_rec,
               "v_rec": v_rec, "bl": bl, "br": br, "batch_idx": batch_idx, "lig_flag": lig_flag, "gen_flag": gen_flag,
               "lig_rows": lig_rows, "rec_rows": rec_rows, "graph_ptr": graph_ptr, "nxt": nxt, "drawn": draws is not None,
               "traj_x": None, "traj_c": None, "static_h": None, "frame": None}
+        st.update(cn)
         if keep_trajectory:
             st["traj_x"] = torch.empty(T + 1, n_lig, 3, dtype=torch.float32, device=dev)
             st["traj_c"] = torch.empty(T + 1, n_lig, C, dtype=torch.float32, device=dev)
@@ -472,7 +489,10 @@ class DiffSBDD(BatchesInFlight, nn.Module):
     @torch.no_grad()
     def denoise_step(self, st, t_idx, noise=None):
         """One reverse step s = t_idx / T <- t = (t_idx + 1) / T (diffsbdd.py:296-304): denoiser call and the two
-        sample_p_zs_given_zt draws.  ``noise`` is ignored when the state was built with ``noise_draws``."""
+        sample_p_zs_given_zt draws.  ``noise`` is ignored when the state was built with ``noise_draws``; a ``CounterNoise`` must be the
+        one the state was begun with (the initial draws of ``begin_sampling`` belong to the same run)."""
+        if isinstance(noise, _noise.CounterNoise) and st.get("noise") is not noise:
+            raise ValueError("denoise_step: pass the CounterNoise to begin_sampling (it draws the initial state)")
         sch, T, B = self.pos_scheduler, self.num_diffusion_timesteps, st["B"]
         dev = st["x"].device
         bl, br, nxt = st["bl"], st["br"], st["nxt"]
@@ -498,10 +518,15 @@ class DiffSBDD(BatchesInFlight, nn.Module):
         xo, _, logits = self.denoiser(x=x, h=h, batch_idx=st["batch_idx"], lig_flag=st["lig_flag"], gen_flag=st["gen_flag"],
                                       graph_ptr=st["graph_ptr"], need_h=False, static_h=st.get("static_h"))
         eps_x = eps_c = None
-        if self.denoise_structure:      # the reference's draw order: positions, then types
+        if st.get("noise") is not None:     # counter mode: position and type normals of (atom, step)
+            if self.denoise_structure:
+                eps_x = _noise.fill(st, _noise.POS_NORMAL, t_idx, 3, uniform=False)
+            if self.denoise_atom:
+                eps_c = _noise.fill(st, _noise.TYPE_NORMAL, t_idx, C, uniform=False)
+        if self.denoise_structure and eps_x is None:      # the reference's draw order: positions, then types
             eps_x = nxt()
             eps_x = torch.randn(n_lig, 3, dtype=torch.float32, device=dev) if eps_x is None else eps_x.float().contiguous()
-        if self.denoise_atom:
+        if self.denoise_atom and eps_c is None:
             eps_c = nxt()
             eps_c = torch.randn(n_lig, C, dtype=torch.float32, device=dev) if eps_c is None else eps_c.float().contiguous()
         if st["traj_x"] is not None:
@@ -536,14 +561,20 @@ class DiffSBDD(BatchesInFlight, nn.Module):
         sig_t = torch.sqrt(torch.sigmoid(g0)).view(-1, 1)
         alp_t = torch.sqrt(torch.sigmoid(-g0)).view(-1, 1)
         mu_x = 1.0 / alp_t[bl] * (st["x_lig"] - sig_t[bl] * x_pred)
+        if st.get("noise") is not None:
+            # counter mode: the final draw has its own purpose; the per-graph mean is summed in index order (the state is native, so the
+            # ligand atoms are sorted by graph); the draw the reference makes and discards has no address and is not made
+            x_fin, _ = sch.sample_normal_zero_com(mu_x, st["x_rec"], sigma0, bl, br, B, com=True,
+                                                  eps=_noise.fill(st, _noise.FINAL_POS, 0, 3, uniform=False), ordered=True)
+            return x_fin, st["c_lig"] * 4.0
         x_fin, _ = sch.sample_normal_zero_com(mu_x, st["x_rec"], sigma0, bl, br, B, com=True, eps=nxt())
         nxt() if st["drawn"] else torch.randn(st["n_lig"], C, device=dev)   # the reference draws and discards it
         return x_fin, st["c_lig"] * 4.0
 
     # hooks of BatchesInFlight.sample_many (the tape of a batch = its list of randn draws in the reference's order)
     @torch.no_grad()
-    def _many_begin(self, batch, tape):
-        return self.begin_sampling(batch, keep_trajectory=True, noise_draws=tape)
+    def _many_begin(self, batch, tape, noise=None):
+        return self.begin_sampling(batch, keep_trajectory=True, noise_draws=tape, noise=noise)
 
     @torch.no_grad()
     def _many_step(self, st, t_idx, tape):
@@ -559,10 +590,11 @@ class DiffSBDD(BatchesInFlight, nn.Module):
         return traj
 
     @torch.no_grad()
-    def sample(self, batch, noise_draws=None, return_device=None):
-        """diffsbdd.py:240-319. ``noise_draws`` (tests): list of the randn tensors in the reference's draw order."""
+    def sample(self, batch, noise_draws=None, return_device=None, noise=None):
+        """diffsbdd.py:240-319. ``noise_draws`` (tests): list of the randn tensors in the reference's draw order.
+        ``noise`` (a ``CounterNoise``; default: the batch's ``noise_keys``): counter mode; not together with ``noise_draws``."""
         T = self.num_diffusion_timesteps
-        st = self.begin_sampling(batch, keep_trajectory=True, noise_draws=noise_draws)
+        st = self.begin_sampling(batch, keep_trajectory=True, noise_draws=noise_draws, noise=noise)
         for t_idx in reversed(range(T)):
             self.denoise_step(st, t_idx)
         x_fin, c_fin = self.finish_sampling(st)

@@ -18,9 +18,16 @@ produced for a whole batch of P pockets x S samples at once, on the device the t
 
 The random streams necessarily differ from the reference's (numpy global RNG per replica); the distributions are the
 same and are tested against the reference's tables and size function (tests/test_priors.py).
+
+``build_sampling_batch(..., sample_streams=(seed, pocket_ids))`` gives every graph (pocket p, sample s) a generator of its own,
+``np.random.default_rng([seed, pocket_ids[p], s])``: its ligand size, initial positions and initial types are then the same
+whatever else is in the batch and in whatever order, and the batch carries the stream keys (``noise_keys``) with which the
+samplers draw their step noise under the same rule (cbgbench_amd/noise.py).
 """
 import numpy as np
 import torch
+
+from . import noise as _noise
 
 ABSORBING_STATE = 0     # repo/utils/molecule/constants.py:8
 PROTEIN_ELEMENTS = torch.tensor([1, 6, 7, 8, 16, 34])     # repo/utils/protein/constants.py:37 (atomic_numbers)
@@ -192,7 +199,7 @@ def _segment_ids(counts, device):
 
 def build_sampling_batch(pocket_set, num_samples, num_classes, num_dist=None, generator=None, rng=None,
                          type_prior="uniform", pos_prior="gaussian", n_lig=None, context=None, gen_dist=None,
-                         center_on_context=False):
+                         center_on_context=False, sample_streams=None):
     """One batch of P x S graphs (graph g = p * S + s, all samples of a pocket adjacent, as sample.py builds them).
 
     ``num_dist``: NumDist for the ligand size (default U{10..45}, see NumDist.uniform); ``n_lig`` [P,S] overrides it.
@@ -203,19 +210,57 @@ def build_sampling_batch(pocket_set, num_samples, num_classes, num_dist=None, ge
     ``center_flag: ligand, mask_flag: ctx_flag``, translation.py:5-25, as configs/{linker,frag,scaffold,sidechain}/test/*.yml
     ask) instead of on the pocket set's own centre; a pocket without context atoms keeps the frame it came in (the reference
     then averages the all-zero positions ``assign_gensize`` has just written).  ``*_translation`` is the total shift either way.
+    ``sample_streams`` = (seed, pocket_ids [P]): placement-invariant priors.  Graph (p, s) draws from its own generator
+    ``np.random.default_rng([seed, pocket_ids[p], s])`` on the host, in a fixed order -- size uniform, top-up integer (both always,
+    used or not), positions [n, 3], then types ([n] integers for 'uniform', [n, C] normals for 'gaussian') --, the batch is uploaded
+    once, the mean that 'zero_mean_gaussian' removes is summed per graph in index order, and the batch gets ``noise_keys``: the
+    ``CounterNoise`` of its graphs, which the samplers pick up.  ``rng`` / ``generator`` are not used then.
     Returns the batch dict on ``pocket_set.device``."""
     ps, S, dev = pocket_set, int(num_samples), pocket_set.device
     P = ps.num_pockets
-    rng = rng if rng is not None else np.random.default_rng()
-    if n_lig is None:
-        dist = num_dist if num_dist is not None else NumDist.uniform(10, 45)
-        n_lig = dist.sample(ps.space, S, rng)
-    n_lig = np.asarray(n_lig, dtype=np.int64).reshape(P, S)
     n_ctx = np.zeros(P, dtype=np.int64)
     if context is not None:
         n_ctx = np.array([np.asarray(c[1]).shape[0] for c in context], dtype=np.int64)
-        short = n_lig <= n_ctx[:, None]
-        n_lig = np.where(short, n_ctx[:, None] + rng.integers(1, 8, size=n_lig.shape), n_lig)
+    streamed = None
+    if sample_streams is not None:
+        seed, pocket_ids = sample_streams
+        pocket_ids = np.asarray(pocket_ids, dtype=np.int64).reshape(-1)
+        if pocket_ids.shape[0] != P:
+            raise ValueError(f"sample_streams: {pocket_ids.shape[0]} pocket ids for {P} pockets")
+        if pos_prior not in ("gaussian", "zero_mean_gaussian"):
+            raise ValueError(f"Unknown distribution type: {pos_prior}")
+        if type_prior not in ("uniform", "absorbing", "zeros", "gaussian"):
+            raise ValueError(f"Unknown distribution type: {type_prior}")
+        dist = num_dist if num_dist is not None else NumDist.uniform(10, 45)
+        bins = np.atleast_1d(dist.bin_index(ps.space))
+        given = None if n_lig is None else np.asarray(n_lig, dtype=np.int64).reshape(P, S)
+        n_lig = np.empty((P, S), dtype=np.int64)
+        pos_parts, typ_parts = [], []
+        for p in range(P):
+            cdf, values = dist.cdfs[bins[p]], dist.values[bins[p]]
+            for k in range(S):
+                g = np.random.default_rng([int(seed), int(pocket_ids[p]), k])
+                u, top = g.random(), int(g.integers(1, 8))
+                n = int(values[min(int(np.searchsorted(cdf, u, side="right")), values.size - 1)]) if given is None else int(given[p, k])
+                if context is not None and n <= n_ctx[p]:
+                    n = int(n_ctx[p]) + top
+                n_lig[p, k] = n
+                pos_parts.append(g.standard_normal((n, 3)).astype(np.float32))
+                if type_prior == "uniform":
+                    typ_parts.append(g.integers(0, num_classes, size=n))
+                elif type_prior == "gaussian":
+                    typ_parts.append(g.standard_normal((n, num_classes)).astype(np.float32))
+        streamed = (np.concatenate(pos_parts), np.concatenate(typ_parts) if typ_parts else None)
+        noise_keys = _noise.CounterNoise(seed, np.repeat(pocket_ids, S), np.tile(np.arange(S), P))
+    else:
+        rng = rng if rng is not None else np.random.default_rng()
+        if n_lig is None:
+            dist = num_dist if num_dist is not None else NumDist.uniform(10, 45)
+            n_lig = dist.sample(ps.space, S, rng)
+        n_lig = np.asarray(n_lig, dtype=np.int64).reshape(P, S)
+        if context is not None:
+            short = n_lig <= n_ctx[:, None]
+            n_lig = np.where(short, n_ctx[:, None] + rng.integers(1, 8, size=n_lig.shape), n_lig)
     # ---- protein side: every graph repeats its pocket's rows --------------------------------------------
     g_pocket = torch.arange(P, device=dev).repeat_interleave(S)                    # pocket of graph g
     rec_counts = ps.sizes.to(dev)[g_pocket]
@@ -231,8 +276,13 @@ def build_sampling_batch(pocket_set, num_samples, num_classes, num_dist=None, ge
     local = torch.arange(n_tot, device=dev) - lig_start[lig_graph]                # index of the atom inside its ligand
     if pos_prior not in ("gaussian", "zero_mean_gaussian"):
         raise ValueError(f"Unknown distribution type: {pos_prior}")
-    pos = torch.randn(n_tot, 3, device=dev, generator=generator)
-    if type_prior == "uniform":
+    if streamed is not None:
+        pos = torch.from_numpy(streamed[0]).to(dev)
+    else:
+        pos = torch.randn(n_tot, 3, device=dev, generator=generator)
+    if streamed is not None and type_prior in ("uniform", "gaussian"):
+        typ = torch.from_numpy(streamed[1]).to(dev)
+    elif type_prior == "uniform":
         typ = torch.randint(0, num_classes, (n_tot,), device=dev, generator=generator)
     elif type_prior == "absorbing":
         typ = torch.full((n_tot,), ABSORBING_STATE, dtype=torch.long, device=dev)
@@ -273,7 +323,12 @@ def build_sampling_batch(pocket_set, num_samples, num_classes, num_dist=None, ge
         if all(len(c) > 2 and c[2] is not None for c in context):
             elem[is_ctx] = torch.cat([torch.as_tensor(np.asarray(c[2]), dtype=torch.long).reshape(-1) for c in context]).to(dev)[src]
         batch["ligand_element"] = elem
-    if pos_prior == "zero_mean_gaussian":
+    if pos_prior == "zero_mean_gaussian" and streamed is not None:
+        # one sequential sum per graph, in index order (index_add_ below is an atomic sum on the GPU: its order, and with it the last
+        # bit of the mean, depends on what else is in the batch)
+        mean = torch.segment_reduce(pos, "sum", lengths=lig_counts, axis=0, unsafe=True) / lig_counts.clamp(min=1)[:, None]
+        pos = pos - mean[lig_graph]
+    elif pos_prior == "zero_mean_gaussian":
         mean = torch.zeros(P * S, 3, device=dev).index_add_(0, lig_graph, pos) / lig_counts.clamp(min=1)[:, None]
         pos = pos - mean[lig_graph]
     batch.setdefault("ligand_element", torch.zeros(n_tot, dtype=torch.long, device=dev))     # assign_molsize (init_lig.py:252)
@@ -292,6 +347,8 @@ def build_sampling_batch(pocket_set, num_samples, num_classes, num_dist=None, ge
         "ligand_element_batch": lig_graph,
         "ligand_translation": (ps.center + shift)[g_pocket][lig_graph],
     })
+    if streamed is not None:
+        batch["noise_keys"] = noise_keys
     return batch
 
 

@@ -33,20 +33,22 @@ from .config import NUM_ATOM_TYPES, get_atomic_number_from_index, is_aromatic_fr
 
 
 def build_pocket_batch(pockets, num_samples, rng, num_classes, prior_types="uniform", device="cpu", num_dist=None,
-                       generator=None, plan=None, context=None):
+                       generator=None, plan=None, context=None, sample_streams=None):
     """num_samples replicas of every pocket with fresh priors (sample.py:177-183; init_lig.py:232-258, 376-432), built
     for the whole batch at once on ``device`` (cbgbench_amd/priors.py).  ``plan`` (priors.SamplingPlan) selects the priors and the
-    centring; ``context``: per pocket (pos, atom_type) of the fixed atoms of a linker / frag / scaffold / sidechain job."""
+    centring; ``context``: per pocket (pos, atom_type) of the fixed atoms of a linker / frag / scaffold / sidechain job;
+    ``sample_streams`` = (seed, pocket ids): ``--noise counter``, every graph draws from its own stream (``rng`` is then unused)."""
     ps = priors.PocketSet(pockets, device=device, center=False)   # pocket files are already centred (center_pos)
     if plan is None:
         return priors.build_sampling_batch(ps, num_samples, num_classes, num_dist=num_dist, rng=rng, generator=generator,
-                                           type_prior=prior_types)
+                                           type_prior=prior_types, sample_streams=sample_streams)
     if plan.task == "context" and context is None:
         raise ValueError("the config asks for a context task (assign_gensize) but no context atoms were given")
     return priors.build_sampling_batch(ps, num_samples, num_classes, num_dist=num_dist, rng=rng, generator=generator,
                                        type_prior=plan.type_prior, pos_prior=plan.pos_prior,
                                        context=context if plan.task == "context" else None,
-                                       center_on_context=plan.task == "context" and plan.center == "context")
+                                       center_on_context=plan.task == "context" and plan.center == "context",
+                                       sample_streams=sample_streams)
 
 
 def load_context(raw_pockets, path):
@@ -132,6 +134,13 @@ def main(argv=None, stats=None):
     ap.add_argument("--no_translate", action="store_true",
                     help="keep results in the sampling frame (default: add protein_translation back when the config's "
                          "sampling.translate is set, sample.py:198-201)")
+    ap.add_argument("--noise", choices=("torch", "counter"), default="torch",
+                    help="torch: priors and step noise from the seeded torch / numpy generators (seed + rank; the samples depend on the "
+                         "number of ranks, --pockets_per_batch, --streams and the pocket order).  counter: every random number is a "
+                         "function of (seed, pocket index, sample index, atom, step), generated in the step kernels: a pocket's file "
+                         "is the same however the job is split (cbgbench_amd/noise.py).  GPU only (the generator lives in the step "
+                         "kernels: --device cpu raises).  Nothing seeds torch in this mode, so --random_init weights differ from process "
+                         "to process: compare runs through a --checkpoint")
     ap.add_argument("--atom_num_dist", default=None,
                     help="the reference's size-conditioned ligand-size histogram (repo/datasets/transforms/_atom_num_dist.npy); "
                          "without it ligand sizes are U{10..45}")
@@ -195,8 +204,11 @@ def main(argv=None, stats=None):
     mine = sharding.shard_indices(len(pockets), rank, world)
     out_dir = os.path.join(args.out_root, args.tag or config_name)
     os.makedirs(out_dir, exist_ok=True)
-    torch.manual_seed(args.seed + rank)                 # independent noise streams per shard
-    rng = np.random.default_rng([args.seed, rank])
+    if args.noise == "counter":
+        rng = None                                      # no shared stream: priors and step noise are addressed per (pocket, sample)
+    else:
+        torch.manual_seed(args.seed + rank)             # independent noise streams per shard
+        rng = np.random.default_rng([args.seed, rank])
     def write_results(ids, traj, batch):
         # sample.py:198-201 hands traj[0] to the reconstruction -- for targetdiff / diffbp that is the state entering the
         # last step, not traj[-1]; kept as the default for drop-in outputs, --final_state selects traj[-1]
@@ -226,7 +238,8 @@ def main(argv=None, stats=None):
     for g0 in range(0, len(mine), group):
         chunk = [mine[b0:b0 + args.pockets_per_batch] for b0 in range(g0, min(g0 + group, len(mine)), args.pockets_per_batch)]
         batches = [build_pocket_batch([pockets[i] for i in ids], num_samples, rng, num_classes, device=dev, num_dist=num_dist,
-                                      plan=plan, context=[context[i] for i in ids] if context is not None else None)
+                                      plan=plan, context=[context[i] for i in ids] if context is not None else None,
+                                      sample_streams=(args.seed, ids) if args.noise == "counter" else None)
                    for ids in chunk]
         lap("batch", dev)
         # (targetdiff itemises its share of the `sample` phase: static context, the T steps, the trajectory download)
