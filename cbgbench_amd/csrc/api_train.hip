@@ -983,6 +983,42 @@ int cbgx_targetdiff_train_noise(const float* x0, const int64_t* v0, const int64_
     return CBGX_OK;
 }
 
+// ---- counter-mode draws of a training / validation call (train_noise.hip, rng.h) -----------------------------------------------------
+static bool bad_purpose_base(int purpose_base) { return purpose_base < 0 || purpose_base % CBGX_NOISE_PURPOSE_STRIDE != 0; }
+
+int cbgx_train_noise_draw(const uint64_t* stream_keys, const int32_t* lig_ptr, int n_graphs, int n_lig, int purpose_base, int n_t,
+                          const int64_t* t_in, int64_t* t_out, float* a, float* b, int cols_b, int purpose_b, int uniform_b,
+                          void* stream) {
+    if (n_graphs < 0 || n_lig < 0 || n_t < 1 || bad_purpose_base(purpose_base) ||
+        (b && (cols_b < 1 || cols_b > 32 || purpose_b < 0 || purpose_b >= CBGX_NOISE_PURPOSE_STRIDE)))
+        return set_error(CBGX_E_INVALID, "train_noise_draw: bad sizes (n_lig=%d B=%d n_t=%d purpose_base=%d cols_b=%d purpose_b=%d)",
+                         n_lig, n_graphs, n_t, purpose_base, cols_b, purpose_b);
+    if (n_graphs == 0) return CBGX_OK;
+    if (!stream_keys || !lig_ptr || !t_out) return set_error(CBGX_E_INVALID, "train_noise_draw: NULL pointer");
+    HIP_TRY(launch_train_noise_draw(stream_keys, lig_ptr, n_graphs, n_lig, (uint32_t)purpose_base, (uint32_t)n_t, t_in, t_out, a, b,
+                                    cols_b, (uint32_t)purpose_b, uniform_b, (hipStream_t)stream));
+    return CBGX_OK;
+}
+
+int cbgx_targetdiff_train_noise_rng(const float* x0, const int64_t* v0, const int64_t* batch, const uint8_t* gen, int n_lig,
+                                    int num_classes, const float* alphas_cumprod, const float* log_alphas_cumprod,
+                                    const float* log_one_minus_alphas_cumprod, const uint64_t* stream_keys, const int32_t* lig_ptr,
+                                    int n_graphs, int purpose_base, int n_t, const int64_t* t_in, int64_t* t_out, float* x_t,
+                                    float* c_t, int64_t* v_t, void* stream) {
+    if (n_lig < 0 || n_graphs < 0 || num_classes < 1 || num_classes > 32 || n_t < 1 || bad_purpose_base(purpose_base))
+        return set_error(CBGX_E_INVALID, "train_noise_rng: bad sizes (n_lig=%d B=%d C=%d n_t=%d purpose_base=%d)", n_lig, n_graphs,
+                         num_classes, n_t, purpose_base);
+    if (n_graphs == 0) return CBGX_OK;     // (no graph: no atom either)
+    if (!stream_keys || !lig_ptr || !t_out ||
+        (n_lig > 0 && (!x0 || !v0 || !batch || !gen || !alphas_cumprod || !log_alphas_cumprod || !log_one_minus_alphas_cumprod ||
+                       !x_t || !c_t || !v_t)))
+        return set_error(CBGX_E_INVALID, "train_noise_rng: NULL pointer");
+    HIP_TRY(launch_train_noise_rng(x0, v0, batch, gen, n_lig, n_graphs, num_classes, alphas_cumprod, log_alphas_cumprod,
+                                   log_one_minus_alphas_cumprod, (float)log((double)num_classes), stream_keys, lig_ptr,
+                                   (uint32_t)purpose_base, (uint32_t)n_t, t_in, t_out, x_t, c_t, v_t, (hipStream_t)stream));
+    return CBGX_OK;
+}
+
 int cbgx_targetdiff_loss(const float* x_out, const float* logits, const int64_t* lig_rows, const float* x0, const int64_t* v0,
                          const int64_t* v_t, const int64_t* t, const int64_t* batch, const uint8_t* gen, int n_lig, int n_graphs,
                          int num_classes, const float* const* tables, float* losses, float* x_pred, float* c_pred,

@@ -19,6 +19,20 @@
 //               (2, 3) components 4 block + 2 / + 3: one call, four normals.
 // The words and the uniforms are the same bits on every compiler; the normals go through the platform's logf / sqrtf / sincosf.
 // No two draws of a run share an address as long as the atoms of a ligand keep their order (the one precondition of the mode).
+//
+// TRAINING AND VALIDATION draw from the same generator (purposes TRAIN_*).  The key of a graph is stream_key(seed, example index,
+// visit): the example's index in its dataset -- a global identity -- stands where the pocket index stands, the training iteration
+// (the same number on every rank) where the sample index stands; validation uses visit 0 under the purpose base PURPOSE_STRIDE, so
+// no validation draw shares an address with a training draw of an example with the same number.
+//   time        t_g = (uint64(w0) * n_t) >> 32 in [0, n_t), w0 = word 0 of the call at counter (0, 0, base + TRAIN_TIME, 0) under the
+//               graph's key (train_time below); n_t = T for TargetDiff and DiffBP ('symmetric' sampler), T + 1 for DiffSBDD ('random').
+//               Every t_g has the symmetric sampler's marginal (uniform on [0, T)); the antithetic pairing t, T - 1 - t inside a batch
+//               is a function of batch position and is NOT kept.
+//   per atom    counter = (index inside the ligand, step = the graph's integer time t_g, base + purpose, block): words, uniforms and
+//               Box-Muller as above.  The step word is the graph's time in training and in eval mode, so the evaluation times of one
+//               validation call draw at different addresses; DiffSBDD's second eval-mode network call (time 0) draws at step 0, which
+//               none of its evaluation times linspace(1, T) uses.  Two evaluation times that coincide after truncation to an integer
+//               (tiny T) get the same draw.
 // Plain C++: a host compiler builds this header for the stand-alone known-answer program of tests/test_counter_noise.py.
 #pragma once
 #include <math.h>
@@ -42,6 +56,11 @@ enum Purpose : uint32_t {
     INIT_TYPE = 5,      // initial type normal, step 0, components 0..C-1                (DiffSBDD z_T)
     FINAL_POS = 6,      // position normal of sample_p_xh_given_z0, step 0               (DiffSBDD; the type normal the reference draws
                         // there and discards has no address)
+    TRAIN_TIME = 7,         // the graph's time of a training call: counter (0, 0, base + TRAIN_TIME, 0), word 0
+    TRAIN_POS_NORMAL = 8,   // position normal of a training / validation call, components 0..2, step = the graph's time  (all classes)
+    TRAIN_TYPE_UNIFORM = 9, // type uniform, components 0..C-1                              (TargetDiff: the Gumbel draw)
+    TRAIN_MASK_UNIFORM = 10,// mask draw, component 0                                       (DiffBP)
+    TRAIN_TYPE_NORMAL = 11, // type normal, components 0..C-1                               (DiffSBDD)
     PURPOSE_STRIDE = 16 // purpose bases are multiples of this
 };
 
@@ -79,6 +98,14 @@ CBGX_HD Words draw(uint64_t stream_key, uint32_t atom, uint32_t step, uint32_t p
 CBGX_HD uint64_t stream_key(uint64_t seed, uint32_t pocket, uint32_t sample) {
     const Words o = philox4x32_10((uint32_t)seed, (uint32_t)(seed >> 32), pocket, sample, STREAM_KEY0, STREAM_KEY1);
     return (uint64_t)o.w0 | ((uint64_t)o.w1 << 32);
+}
+
+// a word mapped to an integer in [0, n): floor(w * n / 2^32); w = 0xFFFFFFFF gives n - 1, never n
+CBGX_HD uint32_t scale_word(uint32_t w, uint32_t n) { return (uint32_t)(((uint64_t)w * (uint64_t)n) >> 32); }
+
+// the time of a graph in a training call: in [0, n_t)
+CBGX_HD uint32_t train_time(uint64_t stream_key, uint32_t purpose_base, uint32_t n_t) {
+    return scale_word(draw(stream_key, 0u, 0u, purpose_base + TRAIN_TIME, 0u).w0, n_t);
 }
 
 CBGX_HD float uniform(uint32_t w) { return (float)(w >> 8) * 5.9604644775390625e-8f; }            // [0, 1)

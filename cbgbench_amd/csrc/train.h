@@ -150,6 +150,14 @@ hipError_t launch_train_loss(const float* x_out, const float* logits, const int6
                              float* c_pred, float* gpos, float* gz, hipStream_t s);
 hipError_t launch_train_loss_bwd(const float* gpos, const float* gz, const int64_t* sort_idx, int n_rec, int n_nodes, int C,
                                  const float* g_pos, const float* g_typ, float* grad_x, float* grad_logits, hipStream_t s);
+// train_noise.hip: the counter-mode draws of a training / validation call (rng.h), and TargetDiff's noising with the draws made in place
+hipError_t launch_train_noise_draw(const uint64_t* keys, const int32_t* lig_ptr, int n_graphs, int n_lig, uint32_t purpose_base,
+                                   uint32_t n_t, const int64_t* t_in, int64_t* t_out, float* a, float* b, int cols_b,
+                                   uint32_t purpose_b, int uniform_b, hipStream_t s);
+hipError_t launch_train_noise_rng(const float* x0, const int64_t* v0, const int64_t* batch, const uint8_t* gen, int n_lig, int n_graphs,
+                                  int C, const float* acp, const float* log_acp, const float* log_1m_acp, float log_c,
+                                  const uint64_t* keys, const int32_t* lig_ptr, uint32_t purpose_base, uint32_t n_t,
+                                  const int64_t* t_in, int64_t* t_out, float* x_t, float* c_t, int64_t* v_t, hipStream_t s);
 // train_loss_diffbp.hip: DiffBP's four losses and their gradients with respect to the network outputs (composed row order)
 hipError_t launch_diffbp_loss(const float* x_out, const float* x_in, const float* x_stack, const float* logits, const int64_t* sort_idx,
                               const int32_t* graph_ptr, const uint8_t* lig, const float* pos_noise, const float* com_noise,

@@ -367,20 +367,24 @@ class DiffBP(BatchesInFlight, nn.Module):
 
     def forward(self, batch, t=None, noise=None):
         """``loss_dict, results = model(batch)``: {'pos', 'atom', 'com', 'inter'} (all weights 1 in
-        configs/denovo/train/diffbp.yml:37-41).  ``t`` / ``noise=(eps [N_lig,3], u [N_lig])`` replay the draws in tests."""
+        configs/denovo/train/diffbp.yml:37-41).  ``t`` / ``noise=(eps [N_lig,3], u [N_lig])`` replay the draws in tests.  ``noise`` a
+        ``CounterNoise``: the counter mode in training and in eval mode (cbgbench_amd/noise.py) -- one ``cbgx_train_noise_draw`` launch
+        makes the times (unless ``t`` gives them) and both buffers; ``results`` then also carries ``t`` [B] and ``xt``."""
+        cn = noise if isinstance(noise, _noise.CounterNoise) else None
         bl = batch["ligand_element_batch"]
         # the graph count: from the batch if the collate recorded it (no host synchronisation in the training step), else as the
         # reference computes it
-        B = int(batch["num_graphs"]) if "num_graphs" in batch else (int(t.shape[0]) if t is not None else int(bl.max().item()) + 1)
+        B = int(batch["num_graphs"]) if "num_graphs" in batch else (
+            int(t.shape[0]) if t is not None else cn.num_graphs if cn is not None else int(bl.max().item()) + 1)
         dev = batch["ligand_pos"].device
         if self.training or t is not None:
-            if t is None:
+            if t is None and cn is None:
                 t = self.sample_time(B, device=dev)
             return self.get_loss(batch, t, noise)
         import numpy as np
         dicts, results = [], []
         for tv in np.linspace(0, self.num_diffusion_timesteps - 1, self.cfg.get("eval_interval", 10)):
-            ld, res = self.get_loss(batch, torch.tensor([tv] * B).long().to(dev), None)
+            ld, res = self.get_loss(batch, torch.tensor([tv] * B).long().to(dev), cn)
             dicts.append(ld)
             results.append(res)
         return {k: torch.stack([d[k] for d in dicts]).mean() for k in dicts[0]}, results
@@ -419,7 +423,15 @@ class DiffBP(BatchesInFlight, nn.Module):
         gen_l = batch.get("ligand_gen_flag", lig_flag_l).bool()
         gen_r = batch.get("protein_gen_flag", torch.zeros_like(batch["protein_lig_flag"])).bool()
         bl, br = batch["ligand_element_batch"], batch["protein_element_batch"]
-        eps, u = noise if noise is not None else (None, None)
+        if isinstance(noise, _noise.CounterNoise):
+            # counter mode: the times (``t`` None: drawn) and both buffers in one launch, then the replay route below
+            B = int(t.shape[0]) if t is not None else int(batch.get("num_graphs", noise.num_graphs))
+            ops = _noise.train_operands(noise, batch, B)
+            t, eps, u = _noise.train_draw(ops, x0.shape[0], self.num_diffusion_timesteps, t, 1, _noise.TRAIN_MASK_UNIFORM, True)
+            u, counter = u.view(-1), True
+        else:
+            eps, u = noise if noise is not None else (None, None)
+            counter = False
         sort_idx, batch_idx, lig_flag, lig_rows, graph_ptr = TargetDiff.compose_plan(bl, br, int(t.shape[0]))
         # the forward noising in one launch (cbgx_diffbp_train_noise; training and eval mode) under the guards of TargetDiff's
         type8 = gen8 = None
@@ -456,6 +468,8 @@ class DiffBP(BatchesInFlight, nn.Module):
                 ps.alphas_cumprod.float().contiguous(),
                 ps.betas.float().contiguous(), int(mla) > 48)
             results = {"mask_gen": gen_l, "v0": v0, "vt": v_t, "fused_bad": bad}
+            if counter:
+                results["t"], results["xt"] = t, x_t
             return {"pos": loss_pos, "atom": loss_atom, "com": loss_com, "inter": loss_inter}, results
         if type8 is not None:
             type_flag = type8.bool()
@@ -469,6 +483,8 @@ class DiffBP(BatchesInFlight, nn.Module):
         loss_inter = self.interior_loss(xs, x_rec, bl, br, n_graphs=int(t.shape[0]), max_ligand_atoms=batch.get("max_ligand_atoms", None))
         results = {}
         results.update(pos_info); results.update(atom_info); results.update(com_info)
+        if counter:
+            results["t"], results["xt"] = t, x_t
         return {"pos": loss_pos, "atom": loss_atom, "com": loss_com, "inter": loss_inter}, results
 
     @torch.no_grad()

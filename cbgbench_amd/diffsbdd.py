@@ -78,13 +78,14 @@ class DiffsbddVariationalScheduler(nn.Module):
     def sigma(self, gamma):
         return torch.sqrt(torch.sigmoid(gamma))
 
-    def forward_pos_center_noise(self, x_lig, x_rec, t, bl, br, B, gen_flag, noise=None):
-        """q(z_t | x) for the coordinates with the pocket re-centred on the noisy ligand (:740-763, zero_center=False)"""
+    def forward_pos_center_noise(self, x_lig, x_rec, t, bl, br, B, gen_flag, noise=None, ordered=False):
+        """q(z_t | x) for the coordinates with the pocket re-centred on the noisy ligand (:740-763, zero_center=False); ``ordered``: the
+        mean as a sequential sum per graph (``scatter_mean``)"""
         if noise is None:
             noise = torch.randn_like(x_lig)
         g = self.gamma(t).view(B, 1)
         x_noisy = self.alpha(g)[bl] * x_lig + self.sigma(g)[bl] * noise
-        x_noisy, x_rec = self.remove_mean_batch(x_noisy, x_rec.detach().clone(), bl, br, B)
+        x_noisy, x_rec = self.remove_mean_batch(x_noisy, x_rec.detach().clone(), bl, br, B, ordered)
         return torch.where(gen_flag.unsqueeze(-1), x_noisy, x_lig), noise, x_rec
 
     def forward_type_add_noise(self, c, t, bl, B, gen_flag, noise=None):
@@ -243,6 +244,10 @@ class DiffSBDD(BatchesInFlight, nn.Module):
         self.intersect_reg = cfg.get("intersect_reg", True)
         # CBGX_FUSED_TRAINING_OPS=0: the noising and both losses as tensor operations (the path the evaluation mode always takes)
         self.fused_training_ops = os.environ.get("CBGX_FUSED_TRAINING_OPS", "1") != "0"
+        # the per-graph means of the tensor path of get_loss (the ligand's centre, twice) as sequential sums instead of index_add_'s float
+        # atomics, whose order -- and with it the last bit of x_t -- changes from run to run.  Needs the ligand atoms sorted by graph.  The
+        # counter noise mode always takes them (its noised inputs are functions of the address); this switch gives the same to a replay.
+        self.ordered_means = False
 
     # ---- training (diffsbdd.py:45-195, training mode) ----------------------------------------------------------
     def sample_time(self, batch_size, device="cuda"):
@@ -255,21 +260,26 @@ class DiffSBDD(BatchesInFlight, nn.Module):
         ``noise=(eps_x [N_lig,3], eps_c [N_lig,C])`` replay the draws in tests.  Evaluation mode: the variational bound
         (SNR-weighted loss_t + KL prior + the t = 0 reconstruction term from a second denoiser call) averaged over
         ``cfg.eval_interval`` (10) evenly spaced times, ``results`` a list with one entry per time; ``noise`` is then a
-        list of (eps_x, eps_c, eps_x0, eps_c0) per time."""
+        list of (eps_x, eps_c, eps_x0, eps_c0) per time.  ``noise`` a ``CounterNoise``: the counter mode in training and in eval
+        mode (cbgbench_amd/noise.py) -- ``cbgx_train_noise_draw`` makes the time of every graph (uniform on 0..T, unless ``t`` gives it)
+        and both buffers in one launch; eval mode takes two such launches per time, the second at step 0 for the second network
+        call.  ``results`` then also carries ``t`` [B] int64 and ``xt``."""
+        cn = noise if isinstance(noise, _noise.CounterNoise) else None
         bl = batch["ligand_element_batch"]
         # the graph count: from the batch if the collate recorded it (no host synchronisation in the training step), else as the
         # reference computes it
-        B = int(batch["num_graphs"]) if "num_graphs" in batch else (int(t.shape[0]) if t is not None else int(bl.max().item()) + 1)
+        B = int(batch["num_graphs"]) if "num_graphs" in batch else (
+            int(t.shape[0]) if t is not None else cn.num_graphs if cn is not None else int(bl.max().item()) + 1)
         dev = batch["ligand_pos"].device
         if self.training or t is not None:
-            if t is None:
+            if t is None and cn is None:
                 t = self.sample_time(B, device=dev)
             return self.get_loss(batch, t, noise)
         times = np.linspace(1, self.num_diffusion_timesteps, self.cfg.get("eval_interval", 10))
         tot, results = {"pos": 0.0, "atom": 0.0}, []
         for k, tv in enumerate(times):
             t_long = torch.full((B,), int(tv), dtype=torch.long, device=dev)
-            ld, res = self.get_loss(batch, t_long, noise[k] if noise is not None else None, evaluate=True)
+            ld, res = self.get_loss(batch, t_long, cn if cn is not None else noise[k] if noise is not None else None, evaluate=True)
             for key in tot:
                 tot[key] = tot[key] + ld[key]
             results.append(res)
@@ -282,6 +292,16 @@ class DiffSBDD(BatchesInFlight, nn.Module):
         lig_flag_l = batch["ligand_lig_flag"]
         gen_l = batch.get("ligand_gen_flag", lig_flag_l).bool()
         gen_r = batch.get("protein_gen_flag", torch.zeros_like(batch["protein_lig_flag"])).bool()
+        counter = isinstance(noise, _noise.CounterNoise)
+        if counter:
+            # counter mode: the times (``t_int`` None: drawn on 0..T) and the two buffers in one launch -- eval mode: two more buffers at
+            # step 0 for the second network call -- then the replay route below
+            B = int(t_int.shape[0]) if t_int is not None else int(batch.get("num_graphs", noise.num_graphs))
+            ops = _noise.train_operands(noise, batch, B)
+            t_int, eps_x, eps_c = _noise.train_draw(ops, x0.shape[0], T + 1, t_int, C, _noise.TRAIN_TYPE_NORMAL, False)
+            noise = (eps_x, eps_c)
+            if evaluate:
+                noise += _noise.train_draw(ops, x0.shape[0], T + 1, torch.zeros_like(t_int), C, _noise.TRAIN_TYPE_NORMAL, False)[1:]
         B = int(t_int.shape[0])
         v_rec = batch["protein_atom_feature"].float() / 4.0
         t = t_int / T
@@ -289,22 +309,27 @@ class DiffSBDD(BatchesInFlight, nn.Module):
         if (self.fused_training_ops and not evaluate and x0.is_cuda and C <= 32 and v0.dtype == torch.int64 and x0.shape[0] > 0
                 and batch["protein_pos"].shape[0] > 0 and self.pos_scheduler.gamma.gamma.shape[0] == T + 1):
             sort_idx, batch_idx, lig_flag, lig_rows, graph_ptr = TargetDiff.compose_plan(bl, br, B)
-            return self._get_loss_fused(batch, t_int, t, noise, x0, v0, v_rec, gen_l, gen_r, sort_idx, batch_idx, lig_flag, graph_ptr, B)
+            ld, res, x_t = self._get_loss_fused(batch, t_int, t, noise, x0, v0, v_rec, gen_l, gen_r, sort_idx, batch_idx, lig_flag,
+                                                graph_ptr, B)
+            if counter:
+                res["t"], res["xt"] = t_int, x_t
+            return ld, res
         c0 = F.one_hot(v0, C).float() / 4.0
-        x0c, xr0 = self.pos_scheduler.remove_mean_batch(x0, batch["protein_pos"].float(), bl, br, B)
+        ordered = counter or self.ordered_means
+        x0c, xr0 = self.pos_scheduler.remove_mean_batch(x0, batch["protein_pos"].float(), bl, br, B, ordered)
         sort_idx, batch_idx, lig_flag, lig_rows, graph_ptr = TargetDiff.compose_plan(bl, br, B)
 
         def noise_and_denoise(tt, eps_x, eps_c):
-            x_t, pos_noise, xr_t = self.pos_scheduler.forward_pos_center_noise(x0c, xr0, tt, bl, br, B, gen_l, noise=eps_x)
+            x_t, pos_noise, xr_t = self.pos_scheduler.forward_pos_center_noise(x0c, xr0, tt, bl, br, B, gen_l, noise=eps_x, ordered=ordered)
             c_t, type_noise = self.type_scheduler.forward_type_add_noise(c0, tt, bl, B, gen_l, noise=eps_c)
             x, h, gen_flag = compose_embed(self.context_embedder, xr_t, x_t, v_rec, batch["protein_aa_type"], c_t, sort_idx, gen_r,
                                            gen_l)
             xo, _, logits = self.denoiser(x=x, h=h, batch_idx=batch_idx, lig_flag=lig_flag, gen_flag=gen_flag,
                                           graph_ptr=graph_ptr, ligand_outputs_only=True)
-            return xo[lig_rows], logits[lig_rows], pos_noise, type_noise, c_t
+            return xo[lig_rows], logits[lig_rows], pos_noise, type_noise, c_t, x_t
 
         noise = noise if noise is not None else (None,) * (4 if evaluate else 2)
-        x_pred, c_pred, pos_noise, type_noise, c_t = noise_and_denoise(t, noise[0], noise[1])
+        x_pred, c_pred, pos_noise, type_noise, c_t, x_t = noise_and_denoise(t, noise[0], noise[1])
         if not evaluate:
             t_is_zero = (t_int == 0).float()
             loss_pos, pos_info = self.pos_scheduler.get_score_loss(x_pred, pos_noise, t, gen_l, bl, B, t_is_zero, x_lig_0=x0c)
@@ -312,13 +337,15 @@ class DiffSBDD(BatchesInFlight, nn.Module):
                                                                       c_lig_0=c0, c_lig_t=c_t)
         else:
             s = (t_int - 1) / T
-            x_pred0, c_pred0, pos_noise0, type_noise0, c_t0 = noise_and_denoise(torch.zeros_like(s), noise[2], noise[3])
+            x_pred0, c_pred0, pos_noise0, type_noise0, c_t0, _ = noise_and_denoise(torch.zeros_like(s), noise[2], noise[3])
             loss_pos, pos_info = self.pos_scheduler.get_score_loss_eval(x_pred, pos_noise, s, t, gen_l, bl, B, x_pred0,
                                                                         pos_noise0, x_lig_0=x0c)
             loss_atom, atom_info = self.type_scheduler.get_score_loss_eval(c_pred, type_noise, s, t, gen_l, bl, B, c_pred0,
                                                                            type_noise0, c_lig_0=c0, c_lig_t0=c_t0)
         results = {k + "_pos": v for k, v in pos_info.items()}
         results.update({k + "_atom": v for k, v in atom_info.items()})
+        if counter:
+            results["t"], results["xt"] = t_int, x_t
         return {"pos": loss_pos, "atom": loss_atom}, results
 
     def _schedule_tables(self, dev):
@@ -339,7 +366,7 @@ class DiffSBDD(BatchesInFlight, nn.Module):
 
     def _get_loss_fused(self, batch, t_int, t, noise, x0, v0, v_rec, gen_l, gen_r, sort_idx, batch_idx, lig_flag, graph_ptr, B):
         """training-mode ``get_loss`` with its tensor operations in three launches (csrc/train_loss_diffsbdd.hip): the noising and the
-        network-independent loss terms before the denoiser, both losses and their gradients after it.  Draws are made here, in the
+        network-independent loss terms before the denoiser, both losses and their gradients after it; returns (losses, results, x_t).  Draws are made here, in the
         order and shapes of the tensor path, so a seeded run sees the same noise on both."""
         T, C = self.num_diffusion_timesteps, self.num_classes
         dev = x0.device
@@ -367,7 +394,7 @@ class DiffSBDD(BatchesInFlight, nn.Module):
                                                                            gdata)
         results = {"eps_0_pos": eps_x, "eps_pred_pos": x_pred, "mask_gen_pos": gen_l,
                    "eps_0_atom": eps_c, "eps_pred_atom": c_pred, "mask_gen_atom": gen_l}
-        return {"pos": loss_pos, "atom": loss_atom}, results
+        return {"pos": loss_pos, "atom": loss_atom}, results, x_t
 
     @torch.no_grad()
     def begin_sampling(self, batch, keep_trajectory=True, noise_draws=None, static_cache=True, noise=None):

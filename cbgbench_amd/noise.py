@@ -14,6 +14,20 @@ ligand keep their order (an atom is addressed by its index inside its ligand).
 the three model classes take as ``noise=``; ``priors.build_sampling_batch(..., sample_streams=(seed, pocket_ids))`` puts one into
 the batch it builds (key ``noise_keys``), with priors that have the same property.
 
+Training and validation take the same mode (``model(batch, noise=CounterNoise(...))`` in training and in eval mode, ``train_cli --noise
+counter``).  The key of a graph is ``stream_keys(seed, example index, visit)``: the example's index in its dataset -- a global identity --
+stands where the pocket index stands, the training iteration (the same number on every rank) where the sample index stands
+(``training_noise``); validation uses visit 0 under the purpose base ``PURPOSE_STRIDE`` (``validation_noise``), so it shares no address
+with training.  The time of a graph is ``(uint64(w0) * n_t) >> 32`` with ``w0`` = word 0 at counter (0, 0, base + TRAIN_TIME, 0)
+(``train_times``; n_t = T for TargetDiff and DiffBP, T + 1 for DiffSBDD); the per-atom draws (purposes TRAIN_*) use the graph's integer
+time as their step word, in training and in eval mode.  What this gives up: every time keeps the symmetric sampler's marginal (uniform
+on [0, T)), but the antithetic pairing t, T - 1 - t inside a batch is a function of batch position and is not kept; TargetDiff's
+``time_sampler: uniform`` is refused rather than silently replaced.  What it does not separate: two evaluation times of one validation
+call that coincide after truncation to an integer (tiny T) draw at the same addresses, hence get the same noise.  What it buys: the noised
+inputs of an example at an iteration are the same for every world size, batch size and batch position, a validation loss is a function of
+the weights, and a resumed run sees the noise the uninterrupted run saw.  (The gradients keep their fp32 atomics: the inputs of a step
+are reproducible, not the step.)
+
 The numpy functions below restate the generator from its definition (Salmon et al., SC'11); tests compare the header (built with a
 host compiler) and the kernels against them: words and uniforms bit for bit, normals within the rounding of the device's
 logf / sqrtf / sincosf.
@@ -25,8 +39,10 @@ from . import _native
 
 # purposes (csrc/rng.h ``Purpose``, include/cbgx.h CBGX_NOISE_*)
 POS_NORMAL, TYPE_UNIFORM, MASK_UNIFORM, TYPE_NORMAL, INIT_POS, INIT_TYPE, FINAL_POS = range(7)
+TRAIN_TIME, TRAIN_POS_NORMAL, TRAIN_TYPE_UNIFORM, TRAIN_MASK_UNIFORM, TRAIN_TYPE_NORMAL = range(7, 12)
 PURPOSE_STRIDE = 16
-PURPOSE_NAMES = ("pos_normal", "type_uniform", "mask_uniform", "type_normal", "init_pos", "init_type", "final_pos")
+PURPOSE_NAMES = ("pos_normal", "type_uniform", "mask_uniform", "type_normal", "init_pos", "init_type", "final_pos",
+                 "train_time", "train_pos_normal", "train_type_uniform", "train_mask_uniform", "train_type_normal")
 STREAM_KEY = (0x58474243, 0x53494F4E)
 
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
@@ -64,7 +80,8 @@ def stream_keys(seed, pocket_index, sample_index):
 
 def words(keys, lig_ptr, step, purpose, cols):
     """the words behind ``cbgx_noise_fill``: [n_lig, cols] uint32, word of component ``col`` of atom ``a`` = output ``col % 4`` of the
-    call with counter (a - lig_ptr[graph], step, purpose, col // 4) under the graph's key"""
+    call with counter (a - lig_ptr[graph], step, purpose, col // 4) under the graph's key.  ``step``: one integer, or one per atom as
+    an [n_lig, 1] array (training: the time of the atom's graph)"""
     keys = np.asarray(keys, dtype=np.uint64)
     lig_ptr = np.asarray(lig_ptr, dtype=np.int64)
     counts = np.diff(lig_ptr)
@@ -102,6 +119,77 @@ def fill_model(keys, lig_ptr, step, purpose, cols, uniform):
     """numpy model of ``cbgx_noise_fill``: uniforms fp32 (bit-exact), normals float64"""
     w = words(keys, lig_ptr, step, purpose, 4 * ((cols + 3) // 4))
     return uniforms(w)[:, :cols] if uniform else normals(w)[:, :cols]
+
+
+def scale_word(w, n):
+    """``rng::scale_word``: (uint64(w) * n) >> 32 in [0, n) -- 0xFFFFFFFF gives n - 1, never n"""
+    return ((np.asarray(w, dtype=np.uint64) & _MASK) * np.uint64(n)) >> np.uint64(32)
+
+
+def train_times(keys, n_t, purpose_base=0):
+    """``rng::train_time``: [B] int64 times in [0, n_t) of the graphs with stream keys ``keys``"""
+    keys = np.asarray(keys, dtype=np.uint64).reshape(-1)
+    ctr = np.zeros((keys.size, 4), dtype=np.uint64)
+    ctr[:, 2] = purpose_base + TRAIN_TIME
+    key = np.stack([keys & _MASK, keys >> np.uint64(32)], -1)
+    return scale_word(philox4x32_10(ctr, key)[:, 0], n_t).astype(np.int64)
+
+
+def train_draw_model(keys, lig_ptr, n_t, purpose_base=0, cols_b=0, purpose_b=TRAIN_TYPE_UNIFORM, uniform_b=True, t_in=None):
+    """numpy model of ``cbgx_train_noise_draw``: (t [B] int64, a [n_lig, 3] float64 normals, b [n_lig, cols_b] fp32 uniforms (bit-exact)
+    or float64 normals, None when ``cols_b`` is 0) -- ``fill_model`` with the time of the atom's graph as the step"""
+    lig_ptr = np.asarray(lig_ptr, dtype=np.int64)
+    t = train_times(keys, n_t, purpose_base) if t_in is None else np.asarray(t_in, dtype=np.int64).reshape(-1).copy()
+    step = np.repeat(t, np.diff(lig_ptr))[:, None]
+    a = fill_model(keys, lig_ptr, step, purpose_base + TRAIN_POS_NORMAL, 3, False)
+    b = fill_model(keys, lig_ptr, step, purpose_base + purpose_b, cols_b, uniform_b) if cols_b else None
+    return t, a, b
+
+
+TRAIN_PURPOSE_B = {"targetdiff": TRAIN_TYPE_UNIFORM, "diffbp": TRAIN_MASK_UNIFORM, "diffsbdd": TRAIN_TYPE_NORMAL}
+
+
+def eval_times(model_type, T, eval_interval):
+    """the integer times of one eval-mode ``forward`` (what the model classes truncate their ``linspace`` to)"""
+    lin = np.linspace(1, T, eval_interval) if model_type == "diffsbdd" else np.linspace(0, T - 1, eval_interval)
+    return [int(v) for v in lin]
+
+
+def _call_addresses(model_type, keys, lig_ptr, t, C, purpose_base):
+    counts = np.diff(np.asarray(lig_ptr, dtype=np.int64))
+    blocks_b = 1 if model_type == "diffbp" else (C + 3) // 4
+    rows = []
+    for g, n in enumerate(counts):
+        for a in range(int(n)):
+            rows.append((keys[g], a, int(t[g]), purpose_base + TRAIN_POS_NORMAL, 0))
+            rows += [(keys[g], a, int(t[g]), purpose_base + TRAIN_PURPOSE_B[model_type], b) for b in range(blocks_b)]
+    return rows
+
+
+def train_addresses(model_type, keys, lig_ptr, T, C, purpose_base=0, t_in=None):
+    """every (key, atom, step, purpose, block) address ONE training call of ``model_type`` draws from, [n, 5] uint64, one row per
+    Philox call: the time of every graph (not with ``t_in``: given times draw nothing) and the per-atom draws at that time"""
+    keys = np.asarray(keys, dtype=np.uint64)
+    n_t = T + 1 if model_type == "diffsbdd" else T
+    rows = []
+    if t_in is None:
+        rows = [(k, 0, 0, purpose_base + TRAIN_TIME, 0) for k in keys]
+        t_in = train_times(keys, n_t, purpose_base)
+    rows += _call_addresses(model_type, keys, lig_ptr, t_in, C, purpose_base)
+    return np.array(rows, dtype=np.uint64).reshape(-1, 5)
+
+
+def validation_addresses(model_type, keys, lig_ptr, T, C, eval_interval, purpose_base=PURPOSE_STRIDE):
+    """the addresses of ONE eval-mode call, evaluation time after evaluation time in call order (DiffSBDD: per time the draws at the
+    time and the draws of its second network call at step 0) -- a list with one [n, 5] array per draw call, so that a test can tell the
+    documented repetition (two evaluation times equal after truncation) from an overlap"""
+    keys = np.asarray(keys, dtype=np.uint64)
+    out = []
+    for tv in eval_times(model_type, T, eval_interval):
+        out.append(np.array(_call_addresses(model_type, keys, lig_ptr, [tv] * keys.size, C, purpose_base), dtype=np.uint64).reshape(-1, 5))
+        if model_type == "diffsbdd":
+            out.append(np.array(_call_addresses(model_type, keys, lig_ptr, [0] * keys.size, C, purpose_base), dtype=np.uint64).reshape(-1, 5))
+    return out
 
 
 def run_addresses(model_type, keys, lig_ptr, T, C):
@@ -146,7 +234,13 @@ class CounterNoise:
         """[B] int64 tensor holding the uint64 keys' bits"""
         k = str(device)
         if k not in self._dev:
-            self._dev[k] = torch.from_numpy(self.keys.view(np.int64).copy()).to(device)
+            host = torch.from_numpy(self.keys.view(np.int64).copy())
+            if torch.device(device).type == "cuda":
+                # from pinned memory, without waiting: a pageable copy would make the host wait for everything queued on the stream,
+                # and a training step builds a new CounterNoise every iteration (measured: + 0.4 ... 1 ms per 32-graph step)
+                self._dev[k] = host.pin_memory().to(device, non_blocking=True)
+            else:
+                self._dev[k] = host.to(device)
         return self._dev[k]
 
     def __repr__(self):
@@ -192,3 +286,57 @@ def fill(st, purpose, step, cols, uniform, out=None, step_dev=None):
         st["noise"].purpose_base + int(purpose), int(step), _native.ptr(step_dev), _native.ptr(out), _native.current_stream(dev)),
         "cbgx_noise_fill")
     return out
+
+
+# ---- training and validation -----------------------------------------------------------------------------------------------------
+def training_noise(seed, example_index, iteration):
+    """the ``noise=`` of the training call of iteration ``iteration`` on the examples ``example_index`` [B] (indices in the dataset)"""
+    ex = np.asarray(example_index, dtype=np.int64).reshape(-1)
+    return CounterNoise(seed, ex, np.full(ex.shape, int(iteration), dtype=np.int64), purpose_base=0)
+
+
+def validation_noise(seed, example_index):
+    """the ``noise=`` of a validation call on the examples ``example_index``: visit 0, purpose base PURPOSE_STRIDE"""
+    ex = np.asarray(example_index, dtype=np.int64).reshape(-1)
+    return CounterNoise(seed, ex, np.zeros(ex.shape, dtype=np.int64), purpose_base=PURPOSE_STRIDE)
+
+
+def train_operands(noise, batch, B):
+    """the operands of the counter mode of one ``get_loss`` call: (keys [B] int64 bits, lig_ptr [B+1] int32, noise) on the batch's device.
+    A batch that carries ``ligand_ptr`` (``ComplexSet.collate(..., example_ids=True)``: built on the host from the ligand sizes, so the
+    atoms are sorted by construction) spares the check and the prefix sum their launches and their host synchronisation."""
+    bl = batch["ligand_element_batch"]
+    if noise.num_graphs != B:
+        raise ValueError(f"noise has {noise.num_graphs} stream keys for a batch of {B} graphs")
+    ptr = batch.get("ligand_ptr", None)
+    if ptr is None and not bool((bl[1:] >= bl[:-1]).all()):
+        raise ValueError("counter noise needs the ligand atoms sorted by graph (an atom is addressed by its index inside its ligand)")
+    dev = bl.device
+    if dev.type != "cuda":
+        raise ValueError("counter noise is generated by the GPU kernels: the batch must live on the GPU")
+    if ptr is None:
+        ptr = torch.cat([torch.zeros(1, dtype=torch.long, device=dev), torch.bincount(bl, minlength=B).cumsum(0)]).to(torch.int32)
+        if ptr.shape[0] != B + 1:
+            raise ValueError(f"noise has {noise.num_graphs} stream keys for a batch of {ptr.shape[0] - 1} graphs")
+    elif ptr.dtype != torch.int32 or ptr.shape[0] != B + 1 or ptr.device != dev:
+        raise ValueError("ligand_ptr must be the [B + 1] int32 ligand CSR on the batch's device")
+    return noise.device_keys(dev), ptr.contiguous(), noise
+
+
+def train_draw(ops, n_lig, n_t, t_in=None, cols_b=0, purpose_b=TRAIN_TYPE_UNIFORM, uniform_b=True, positions=True):
+    """``cbgx_train_noise_draw`` on the current stream: (t [B] int64 -- ``t_in``, or drawn --, a [n_lig, 3] normals or None,
+    b [n_lig, cols_b] or None), both at the step t[graph]"""
+    keys, ptr, noise = ops
+    dev, B = keys.device, int(keys.shape[0])
+    t_out = torch.empty(B, dtype=torch.int64, device=dev)
+    a = torch.empty(n_lig, 3, dtype=torch.float32, device=dev) if positions else None
+    b = torch.empty(n_lig, cols_b, dtype=torch.float32, device=dev) if cols_b else None
+    if t_in is not None:
+        t_in = t_in.to(device=dev, dtype=torch.int64).contiguous()
+        if t_in.shape[0] != B:
+            raise ValueError(f"t has {t_in.shape[0]} entries for a batch of {B} graphs")
+    _native.check(_native.lib().cbgx_train_noise_draw(
+        _native.ptr(keys), _native.ptr(ptr), B, int(n_lig), noise.purpose_base, int(n_t), _native.ptr(t_in), _native.ptr(t_out),
+        _native.ptr(a), _native.ptr(b), int(cols_b), int(purpose_b), int(bool(uniform_b)), _native.current_stream(dev)),
+        "cbgx_train_noise_draw")
+    return t_out, a, b

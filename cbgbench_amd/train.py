@@ -249,17 +249,20 @@ def train_step(model, batch, optimizer, flat_grads, loss_weights=None, max_grad_
 
 
 @torch.no_grad()
-def validate(model, batches, loss_weights=None, evaluator=None):
+def validate(model, batches, loss_weights=None, evaluator=None, noise_for=None):
     """train.py:207-246: mean weighted loss over the batches at the model's evenly spaced evaluation times (each batch weighted
     by its graph count, like the reference's ScalarMetricAccumulator, train.py:222-238), all-reduced so every rank sees the same
     value (ReduceLROnPlateau input).  ``evaluator`` (``evaluate.Evaluator``, the config's ``eval.metrics``): its metrics of every
-    batch's ``results`` are averaged and all-reduced the same way; the call then returns ``(avg_loss, {metric: value})``."""
+    batch's ``results`` are averaged and all-reduced the same way; the call then returns ``(avg_loss, {metric: value})``.
+    ``noise_for`` (a callable, batch -> ``noise.CounterNoise``; ``noise.validation_noise`` of the batch's example indices): every batch is
+    evaluated in the counter noise mode, so the result is a function of the weights -- without it, every call draws fresh noise from the
+    torch generator, as the reference does."""
     model.eval()
     names = sorted(evaluator.evaluators) if evaluator is not None and len(evaluator) else []
     acc = [0.0] * (2 + 2 * len(names))      # [sum loss * B, sum B, (sum metric_k * B, sum B over the batches where it is defined) ...]
     with torch.no_grad():
         for batch in batches:
-            loss_dict, results = model(batch)
+            loss_dict, results = model(batch) if noise_for is None else model(batch, noise=noise_for(batch))
             # weighted by the number of graphs, like the reference's ScalarMetricAccumulator (train.py:222-232)
             bl = batch.get("ligand_element_batch", None) if isinstance(batch, dict) else None
             B = batch.get("num_graphs") if isinstance(batch, dict) and batch.get("num_graphs") else (

@@ -16,6 +16,7 @@ data-parallel the way SURVEY.md 8e/8f-4 asks:
 
     python -m cbgbench_amd.train_cli --config configs/denovo/train/targetdiff.yml --logdir logs
                                      [--data complexes.pt | --synthetic 256] [--resume ckpt.pt] [--max_iters N]
+                                     [--noise {torch,counter}]
 
 Complex input: a ``torch.save``d list of dicts with ``protein_pos [n,3]``, ``protein_atom_feature [n,7]``,
 ``protein_aa_type [n]``, ``ligand_pos [m,3]``, ``ligand_atom_type [m]`` and optionally ``ligand_gen_flag [m]`` (what the
@@ -30,6 +31,7 @@ import numpy as np
 import torch
 
 from . import get_model, load_config, set_num_atom_type, sharding, synthetic
+from . import noise as _noise
 from .config import checkpoint_config, load_checkpoint_file
 from .evaluate import Evaluator
 from .train import FlatGradients, broadcast_parameters, get_optimizer, get_scheduler, train_step, validate
@@ -68,7 +70,9 @@ class ComplexSet:
         start = torch.cumsum(cnt, 0) - cnt
         return ptr[ids][seg] + (torch.arange(int(cnt.sum())) - start[seg]), seg
 
-    def collate(self, ids, device="cpu"):
+    def collate(self, ids, device="cpu", example_ids=False):
+        """``example_ids=True`` (the counter noise mode): the batch also carries ``example_index`` -- ``ids`` as a host array, the
+        global identity its noise is keyed by -- and ``ligand_ptr``, the [B + 1] int32 ligand CSR on ``device``."""
         ids = torch.as_tensor(ids, dtype=torch.long)
         rr, rseg = self._rows(self.rec_ptr, ids)
         lr, lseg = self._rows(self.lig_ptr, ids)
@@ -84,6 +88,10 @@ class ComplexSet:
         b = {k: v.to(device) for k, v in b.items()}
         b["num_graphs"] = int(ids.numel())       # known on the host: spares the model a device round trip per step
         b["max_ligand_atoms"] = int((self.lig_ptr[ids + 1] - self.lig_ptr[ids]).max())     # DiffBP's interior loss sizes a tile with it
+        if example_ids:
+            b["example_index"] = ids.numpy().copy()
+            cnt = self.lig_ptr[ids + 1] - self.lig_ptr[ids]
+            b["ligand_ptr"] = torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(cnt, 0)]).to(torch.int32).to(device)
         return b
 
 
@@ -131,6 +139,41 @@ class ShardedLoader:
             e += 1
 
 
+class PositionedLoader:
+    """The loader of the counter noise mode: the batch of iteration ``it`` (1-based) is a function of ``it`` -- not of how many times
+    ``next()`` was called since the process started -- and the GLOBAL batch of an iteration is the same for every world size that
+    divides it.  One permutation of ``range(n_items)`` per epoch (``seed + epoch``, as ShardedLoader), wrapped around to a whole number
+    of global batches of ``batch_size * world`` items; iteration ``it`` is global batch ``(it - 1) % steps`` of epoch ``(it - 1) // steps``,
+    of which rank r takes the entries r, r + W, ...  So a resumed run sees, from its first iteration on, the batches the uninterrupted
+    run saw there, and world sizes 1, 2, 4 with batch sizes 8, 4, 2 train on the same examples at every iteration."""
+
+    def __init__(self, n_items, batch_size, rank=0, world=1, seed=0, shuffle=True):
+        if n_items < 1:
+            raise ValueError("PositionedLoader: empty dataset")
+        self.n, self.bs, self.rank, self.world, self.seed, self.shuffle = n_items, batch_size, rank, world, seed, shuffle
+        self.global_bs = batch_size * world
+        self.steps = (n_items + self.global_bs - 1) // self.global_bs
+        self._epoch = (None, None)
+
+    def _perm(self, e):
+        if self._epoch[0] != e:
+            perm = torch.randperm(self.n, generator=torch.Generator().manual_seed(self.seed + e)) if self.shuffle else torch.arange(self.n)
+            total = self.steps * self.global_bs
+            if total > self.n:
+                perm = perm.repeat((total + self.n - 1) // self.n)[:total]
+            self._epoch = (e, perm)
+        return self._epoch[1]
+
+    def position(self, it):
+        """(epoch, step in the epoch) of iteration ``it`` >= 1"""
+        return (it - 1) // self.steps, (it - 1) % self.steps
+
+    def batch(self, it):
+        """this rank's example indices at iteration ``it``"""
+        e, k = self.position(it)
+        return self._perm(e)[k * self.global_bs:(k + 1) * self.global_bs][self.rank::self.world].tolist()
+
+
 # ---- checkpoints -----------------------------------------------------------------------------------------------
 def save_checkpoint(path, config, model, optimizer, scheduler, iteration, avg_val_loss):
     os.makedirs(os.path.dirname(path), exist_ok=True)
@@ -159,7 +202,14 @@ def load_checkpoint(path, model, optimizer=None, scheduler=None, finetune=False,
 
 # ---- the loop --------------------------------------------------------------------------------------------------
 def run(config, config_name, train_set, val_set, dev, logdir, tag="", resume=None, finetune=False, max_iters=None,
-        log=print):
+        log=print, noise="torch"):
+    """``noise="counter"``: every training call gets ``noise.training_noise(seed, example indices, it)``, every validation call
+    ``noise.validation_noise(seed, example indices)``, and the loader is positioned from the iteration (``PositionedLoader``): the noised
+    inputs of an iteration do not depend on the world size, validation is a function of the weights, and a resumed run sees the
+    batches and the noise the uninterrupted run saw.  ``"torch"`` (default): the torch generator and ShardedLoader, as before."""
+    if noise not in ("torch", "counter"):
+        raise ValueError(f"noise must be 'torch' or 'counter', not {noise!r}")
+    counter = noise == "counter"
     rank, world, _ = sharding.env_rank_world()
     tc, ec = config.train, config.get("eval", {})
     max_iters = int(max_iters if max_iters is not None else tc.max_iters)
@@ -179,15 +229,23 @@ def run(config, config_name, train_set, val_set, dev, logdir, tag="", resume=Non
     else:
         broadcast_parameters(model)                              # every replica starts from rank 0's initialisation
     flat = FlatGradients(model)
-    train_it = iter(ShardedLoader(len(train_set), int(tc.batch_size), rank, world, seed=int(tc.get("seed", 2022))))
+    seed = int(tc.get("seed", 2022))
+    if counter:
+        positioned = PositionedLoader(len(train_set), int(tc.batch_size), rank, world, seed=seed)
+    else:
+        train_it = iter(ShardedLoader(len(train_set), int(tc.batch_size), rank, world, seed=seed))
     val_batches = ShardedLoader(len(val_set), int(tc.batch_size), rank, world, shuffle=False).epoch(0)
     ckpt_dir = os.path.join(logdir, tag or config_name, "checkpoints")
     best_loss, best_iter, history, metric_history = None, None, [], []
     t_last = time.perf_counter()
     for it in range(it_first, max_iters + 1):
-        batch = train_set.collate(next(train_it), dev)
+        if counter:
+            batch = train_set.collate(positioned.batch(it), dev, example_ids=True)
+            step_noise = {"noise": _noise.training_noise(seed, batch["example_index"], it)}
+        else:
+            batch, step_noise = train_set.collate(next(train_it), dev), {}
         loss, loss_dict, grad_norm, t_ar = train_step(model, batch, optimizer, flat, weights,
-                                                      max_grad_norm=float(tc.get("max_grad_norm", 8.0)))
+                                                      max_grad_norm=float(tc.get("max_grad_norm", 8.0)), **step_noise)
         if it % report_freq == 0 and rank == 0:
             now = time.perf_counter()
             parts = " | ".join(f"loss({k}) {float(v):.4f}" for k, v in loss_dict.items())
@@ -196,7 +254,11 @@ def run(config, config_name, train_set, val_set, dev, logdir, tag="", resume=Non
                 f"(all-reduce {1e3 * t_ar:.2f} ms)")
             t_last = now
         if it % val_freq == 0:
-            avg, metrics = validate(model, (val_set.collate(ids, dev) for ids in val_batches), weights, evaluator)
+            if counter:
+                avg, metrics = validate(model, (val_set.collate(ids, dev, example_ids=True) for ids in val_batches), weights, evaluator,
+                                        noise_for=lambda b: _noise.validation_noise(seed, b["example_index"]))
+            else:
+                avg, metrics = validate(model, (val_set.collate(ids, dev) for ids in val_batches), weights, evaluator)
             history.append((it, avg))
             metric_history.append((it, metrics))
             if scheduler is not None and it != it_first:         # train.py:247-251
@@ -228,6 +290,9 @@ def main(argv=None):
     ap.add_argument("--resume", default=None)
     ap.add_argument("--finetune", action="store_true")
     ap.add_argument("--max_iters", type=int, default=None)
+    ap.add_argument("--noise", choices=("torch", "counter"), default="torch",
+                    help="counter: time and noise of every training and validation call are functions of (seed, example, iteration) "
+                         "-- independent of world size, batch size and batch position; resume continues data order and noise")
     args = ap.parse_args(argv)
 
     rank, world, local = sharding.init_process_group()
@@ -251,7 +316,7 @@ def main(argv=None):
         tr, va = raw[:-k], raw[-k:]
     resume = args.resume or config.get("resume", None)
     out = run(config, config_name, ComplexSet(tr), ComplexSet(va), dev, args.logdir, args.tag, resume, args.finetune,
-              args.max_iters)
+              args.max_iters, noise=args.noise)
     if rank == 0:
         print(f"done: best validation loss at iteration {out['best_iter']}, checkpoints in {out['ckpt_dir']}")
     return 0

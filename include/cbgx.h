@@ -294,6 +294,11 @@ int cbgx_diffsbdd_step(const float *x_den, const float *logits, const int32_t *g
 #define CBGX_NOISE_INIT_TYPE 5    /* initial type normal, step 0 (DiffSBDD) */
 #define CBGX_NOISE_FINAL_POS 6    /* position normal of sample_p_xh_given_z0, step 0 (DiffSBDD; the type normal the reference
                                      draws there and discards has no address) */
+#define CBGX_NOISE_TRAIN_TIME 7          /* time of a graph in a training call: counter (0, 0, base + 7, 0), word 0 */
+#define CBGX_NOISE_TRAIN_POS_NORMAL 8    /* position normal of a training / validation call, components 0..2 (all three classes) */
+#define CBGX_NOISE_TRAIN_TYPE_UNIFORM 9  /* type uniform, components 0..C-1 (TargetDiff's Gumbel draw) */
+#define CBGX_NOISE_TRAIN_MASK_UNIFORM 10 /* mask draw, component 0 (DiffBP) */
+#define CBGX_NOISE_TRAIN_TYPE_NORMAL 11  /* type normal, components 0..C-1 (DiffSBDD) */
 #define CBGX_NOISE_PURPOSE_STRIDE 16 /* purpose bases are multiples of this (0: a plain run) */
 /* cbgx_noise_fill: out[a][col] (caller-owned, [n_lig, cols] floats) = component col of the draw of `purpose` at `step` for ligand
  *   atom a -- normals (uniform == 0) or uniforms (uniform != 0).  stream_keys [B] uint64; lig_ptr [B+1] the ligand CSR (ligand arrays
@@ -308,6 +313,36 @@ int cbgx_diffsbdd_step(const float *x_den, const float *logits, const int32_t *g
  *   with lig_ptr (lig_ptr[lig_graph[a]] <= a < lig_ptr[lig_graph[a] + 1]); keys[] and lig_ptr[] are indexed with it unchecked. */
 int cbgx_noise_fill(const uint64_t *stream_keys, const int32_t *lig_ptr, int n_graphs, int n_lig, int cols, int uniform,
                     int purpose, int step, const int32_t *step_dev, float *out, void *stream);
+/* Training and validation in counter mode (purposes CBGX_NOISE_TRAIN_*).  The stream key of a graph is the key of (seed, example index,
+ *   visit): the example's index in its dataset stands where the pocket index stands, the training iteration -- the same number on
+ *   every rank -- where the sample index stands.  Validation uses visit 0 and purpose_base = CBGX_NOISE_PURPOSE_STRIDE, so it never
+ *   shares an address with a training draw.  The noised inputs of an example at an iteration then depend neither on the world size nor
+ *   on the batch size nor on the example's place in its batch.
+ *   Time of a graph: t_g = (uint64(w0) * n_t) >> 32 in [0, n_t) (w0 = 0xFFFFFFFF gives n_t - 1), w0 = word 0 of the call at counter
+ *   (0, 0, purpose_base + CBGX_NOISE_TRAIN_TIME, 0) under the graph's key; n_t = T for TargetDiff and DiffBP, T + 1 for DiffSBDD.  The
+ *   marginal of every t_g is the 'symmetric' sampler's (uniform on [0, T)); its antithetic pairing t, T - 1 - t inside a batch is a
+ *   function of batch position and is not kept.
+ *   Per-atom draws: counter (atom's index inside its ligand, step = t_g, purpose_base + purpose, block), words / uniforms / Box-Muller
+ *   as in cbgx_noise_fill.  The step word is the graph's integer time in training and in eval mode: the evaluation times of one
+ *   validation call draw at different addresses (two that coincide after truncation to an integer -- tiny T -- get the same draw), and
+ *   DiffSBDD's second eval-mode network call (time 0) draws at step 0, which none of its evaluation times uses.
+ * cbgx_train_noise_draw: the draws of one get_loss call in ONE launch.  t_out [B] int64 = t_in (when t_in != NULL: the caller's times)
+ *   or the drawn times; written for every graph, a graph without a ligand atom included.  a [n_lig,3] (may be NULL): normals of
+ *   CBGX_NOISE_TRAIN_POS_NORMAL; b [n_lig,cols_b] (may be NULL; cols_b in 1..32): normals (uniform_b == 0) or uniforms of purpose_b
+ *   (0..15); both at step t_out[graph].  lig_ptr [B+1] the ligand CSR (ligand arrays sorted by graph).
+ * cbgx_targetdiff_train_noise_rng: cbgx_targetdiff_train_noise (below) with eps / u / t replaced by (stream_keys, lig_ptr, n_graphs,
+ *   purpose_base, n_t, t_in or NULL, t_out): every lane evaluates its graph's time, its position normal and its type uniforms
+ *   (CBGX_NOISE_TRAIN_TYPE_UNIFORM, one Philox call per block of four classes) itself -- the numbers cbgx_train_noise_draw followed
+ *   by cbgx_targetdiff_train_noise give, bit for bit, without a noise buffer.  An atom whose batch[a] is outside [0, n_graphs) is
+ *   left unwritten. */
+int cbgx_train_noise_draw(const uint64_t *stream_keys, const int32_t *lig_ptr, int n_graphs, int n_lig, int purpose_base, int n_t,
+                          const int64_t *t_in, int64_t *t_out, float *a, float *b, int cols_b, int purpose_b, int uniform_b,
+                          void *stream);
+int cbgx_targetdiff_train_noise_rng(const float *x0, const int64_t *v0, const int64_t *batch, const uint8_t *gen, int n_lig,
+                                    int num_classes, const float *alphas_cumprod, const float *log_alphas_cumprod,
+                                    const float *log_one_minus_alphas_cumprod, const uint64_t *stream_keys,
+                                    const int32_t *lig_ptr, int n_graphs, int purpose_base, int n_t, const int64_t *t_in,
+                                    int64_t *t_out, float *x_t, float *c_t, int64_t *v_t, void *stream);
 int cbgx_targetdiff_epilogue_rng(const float *x_den, const float *logits, const int32_t *lig_rows, const float *x_lig,
                                  const float *c_lig, const uint8_t *gen_lig, int n_lig, int num_classes, int t,
                                  int num_timesteps, const float *const *tables, const uint64_t *stream_keys,
