@@ -56,6 +56,8 @@ EXPORTS = {
     "cbgx_train_noise_draw": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "cbgx_targetdiff_train_noise_rng": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
                                              _vp]),
+    "cbgx_train_transform": (_i, [_vp] * 5 + [_i, _i, _i, ctypes.c_float, _i, _vp] + [_vp] * 4),
+    "cbgx_train_transform_rng": (_i, [_vp] * 5 + [_i, _i, _i, ctypes.c_float, _i, _vp, _i] + [_vp] * 4),
     "cbgx_targetdiff_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(_vp), _vp, _vp, _vp,
                                   _vp, _vp, _vp]),
     "cbgx_targetdiff_loss_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -1019,6 +1019,49 @@ int cbgx_targetdiff_train_noise_rng(const float* x0, const int64_t* v0, const in
     return CBGX_OK;
 }
 
+// ---- per-visit transforms of a training batch: protein noise + centring (train_transform.hip) ------------------------------------------
+static int tt_check(const char* what, const float* x_rec, const float* x_lig, const int32_t* rec_ptr, const int32_t* lig_ptr,
+                    int n_graphs, int n_rec, int n_lig, float sigma, int center_mode, const float* x_rec_out, const float* x_lig_out,
+                    const float* center_out) {
+    if (n_graphs < 0 || n_rec < 0 || n_lig < 0 || !(sigma >= 0.f) ||
+        center_mode < CBGX_CENTER_PROTEIN || center_mode > CBGX_CENTER_WHOLE)
+        return set_error(CBGX_E_INVALID, "%s: bad arguments (B=%d n_rec=%d n_lig=%d sigma=%g center_mode=%d)", what, n_graphs, n_rec,
+                         n_lig, (double)sigma, center_mode);
+    if ((n_graphs > 0 && (!rec_ptr || !lig_ptr || !center_out)) || (n_rec > 0 && (!x_rec || !x_rec_out)) ||
+        (n_lig > 0 && (!x_lig || !x_lig_out)))
+        return set_error(CBGX_E_INVALID, "%s: NULL pointer", what);
+    return CBGX_OK;
+}
+
+int cbgx_train_transform(const float* x_rec, const float* x_lig, const int32_t* rec_ptr, const int32_t* lig_ptr, const uint8_t* ctx,
+                         int n_graphs, int n_rec, int n_lig, float sigma, int center_mode, const float* eps, float* x_rec_out,
+                         float* x_lig_out, float* center_out, void* stream) {
+    const int rc = tt_check("train_transform", x_rec, x_lig, rec_ptr, lig_ptr, n_graphs, n_rec, n_lig, sigma, center_mode, x_rec_out,
+                            x_lig_out, center_out);
+    if (rc != CBGX_OK) return rc;
+    if (!eps && sigma > 0.f) return set_error(CBGX_E_INVALID, "train_transform: eps == NULL needs sigma == 0 (got %g)", (double)sigma);
+    HIP_TRY(launch_train_transform(x_rec, x_lig, rec_ptr, lig_ptr, ctx, n_graphs, n_rec, n_lig, sigma, center_mode, eps, nullptr, 0u,
+                                   x_rec_out, x_lig_out, center_out, (hipStream_t)stream));
+    return CBGX_OK;
+}
+
+int cbgx_train_transform_rng(const float* x_rec, const float* x_lig, const int32_t* rec_ptr, const int32_t* lig_ptr,
+                             const uint8_t* ctx, int n_graphs, int n_rec, int n_lig, float sigma, int center_mode,
+                             const uint64_t* stream_keys, int purpose_base, float* x_rec_out, float* x_lig_out, float* center_out,
+                             void* stream) {
+    const int rc = tt_check("train_transform_rng", x_rec, x_lig, rec_ptr, lig_ptr, n_graphs, n_rec, n_lig, sigma, center_mode,
+                            x_rec_out, x_lig_out, center_out);
+    if (rc != CBGX_OK) return rc;
+    if (purpose_base < 0 || purpose_base % CBGX_NOISE_PURPOSE_STRIDE != 0)
+        return set_error(CBGX_E_INVALID, "train_transform_rng: purpose_base=%d is not a non-negative multiple of %d", purpose_base,
+                         CBGX_NOISE_PURPOSE_STRIDE);
+    if (n_graphs > 0 && !stream_keys) return set_error(CBGX_E_INVALID, "train_transform_rng: NULL pointer");
+    HIP_TRY(launch_train_transform(x_rec, x_lig, rec_ptr, lig_ptr, ctx, n_graphs, n_rec, n_lig, sigma, center_mode, nullptr,
+                                   stream_keys, (uint32_t)purpose_base + (uint32_t)CBGX_NOISE_TRAIN_PROTEIN_NORMAL, x_rec_out, x_lig_out,
+                                   center_out, (hipStream_t)stream));
+    return CBGX_OK;
+}
+
 int cbgx_targetdiff_loss(const float* x_out, const float* logits, const int64_t* lig_rows, const float* x0, const int64_t* v0,
                          const int64_t* v_t, const int64_t* t, const int64_t* batch, const uint8_t* gen, int n_lig, int n_graphs,
                          int num_classes, const float* const* tables, float* losses, float* x_pred, float* c_pred,

@@ -33,6 +33,10 @@
 //               validation call draw at different addresses; DiffSBDD's second eval-mode network call (time 0) draws at step 0, which
 //               none of its evaluation times linspace(1, T) uses.  Two evaluation times that coincide after truncation to an integer
 //               (tiny T) get the same draw.
+//   protein     the protein-coordinate augmentation of a visit (the config's add_pos_noise, applied before the model call): counter =
+//               (index of the protein atom INSIDE ITS POCKET, step 0, base + TRAIN_PROTEIN_NORMAL, 0), components 0..2, under the same
+//               graph key -- training base 0, validation base PURPOSE_STRIDE.  It does not depend on the graph's time.  Precondition: the
+//               protein atoms of an example keep their order.
 // Plain C++: a host compiler builds this header for the stand-alone known-answer program of tests/test_counter_noise.py.
 #pragma once
 #include <math.h>
@@ -61,6 +65,8 @@ enum Purpose : uint32_t {
     TRAIN_TYPE_UNIFORM = 9, // type uniform, components 0..C-1                              (TargetDiff: the Gumbel draw)
     TRAIN_MASK_UNIFORM = 10,// mask draw, component 0                                       (DiffBP)
     TRAIN_TYPE_NORMAL = 11, // type normal, components 0..C-1                               (DiffSBDD)
+    TRAIN_PROTEIN_NORMAL = 12, // protein-coordinate augmentation of a training visit (add_pos_noise), components 0..2: counter (the
+                            // atom's index INSIDE ITS POCKET, step 0, base + TRAIN_PROTEIN_NORMAL, 0)   (train_transform.hip)
     PURPOSE_STRIDE = 16 // purpose bases are multiples of this
 };
 

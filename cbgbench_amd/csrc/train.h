@@ -158,6 +158,11 @@ hipError_t launch_train_noise_rng(const float* x0, const int64_t* v0, const int6
                                   int C, const float* acp, const float* log_acp, const float* log_1m_acp, float log_c,
                                   const uint64_t* keys, const int32_t* lig_ptr, uint32_t purpose_base, uint32_t n_t,
                                   const int64_t* t_in, int64_t* t_out, float* x_t, float* c_t, int64_t* v_t, hipStream_t s);
+// train_transform.hip: protein noise + centring of a training batch, one workgroup per graph (keys != NULL: eps drawn in place)
+hipError_t launch_train_transform(const float* x_rec, const float* x_lig, const int32_t* rec_ptr, const int32_t* lig_ptr,
+                                  const uint8_t* ctx, int n_graphs, int n_rec, int n_lig, float sigma, int mode, const float* eps,
+                                  const uint64_t* keys, uint32_t purpose, float* x_rec_out, float* x_lig_out, float* center_out,
+                                  hipStream_t s);
 // train_loss_diffbp.hip: DiffBP's four losses and their gradients with respect to the network outputs (composed row order)
 hipError_t launch_diffbp_loss(const float* x_out, const float* x_in, const float* x_stack, const float* logits, const int64_t* sort_idx,
                               const int32_t* graph_ptr, const uint8_t* lig, const float* pos_noise, const float* com_noise,

@@ -28,6 +28,12 @@ inputs of an example at an iteration are the same for every world size, batch si
 the weights, and a resumed run sees the noise the uninterrupted run saw.  (The gradients keep their fp32 atomics: the inputs of a step
 are reproducible, not the step.)
 
+The protein-coordinate augmentation of a training visit (the config's ``add_pos_noise``, applied by ``train_cli.apply_plan`` before the
+model call; ``cbgx_train_transform_rng``) has its own purpose, TRAIN_PROTEIN_NORMAL: counter = (the protein atom's index inside its pocket,
+step 0, base + TRAIN_PROTEIN_NORMAL, block 0), components 0..2, under the graph's training / validation key above -- it does not depend on
+the graph's time.  Precondition: the protein atoms of an example keep their order.  ``protein_draw_model`` / ``protein_addresses`` are its
+numpy model; ``train_addresses`` / ``validation_addresses`` list the draws of the model call only, as before.
+
 The numpy functions below restate the generator from its definition (Salmon et al., SC'11); tests compare the header (built with a
 host compiler) and the kernels against them: words and uniforms bit for bit, normals within the rounding of the device's
 logf / sqrtf / sincosf.
@@ -39,10 +45,11 @@ from . import _native
 
 # purposes (csrc/rng.h ``Purpose``, include/cbgx.h CBGX_NOISE_*)
 POS_NORMAL, TYPE_UNIFORM, MASK_UNIFORM, TYPE_NORMAL, INIT_POS, INIT_TYPE, FINAL_POS = range(7)
-TRAIN_TIME, TRAIN_POS_NORMAL, TRAIN_TYPE_UNIFORM, TRAIN_MASK_UNIFORM, TRAIN_TYPE_NORMAL = range(7, 12)
+TRAIN_TIME, TRAIN_POS_NORMAL, TRAIN_TYPE_UNIFORM, TRAIN_MASK_UNIFORM, TRAIN_TYPE_NORMAL, TRAIN_PROTEIN_NORMAL = range(7, 13)
 PURPOSE_STRIDE = 16
 PURPOSE_NAMES = ("pos_normal", "type_uniform", "mask_uniform", "type_normal", "init_pos", "init_type", "final_pos",
-                 "train_time", "train_pos_normal", "train_type_uniform", "train_mask_uniform", "train_type_normal")
+                 "train_time", "train_pos_normal", "train_type_uniform", "train_mask_uniform", "train_type_normal",
+                 "train_protein_normal")
 STREAM_KEY = (0x58474243, 0x53494F4E)
 
 _M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
@@ -144,6 +151,20 @@ def train_draw_model(keys, lig_ptr, n_t, purpose_base=0, cols_b=0, purpose_b=TRA
     a = fill_model(keys, lig_ptr, step, purpose_base + TRAIN_POS_NORMAL, 3, False)
     b = fill_model(keys, lig_ptr, step, purpose_base + purpose_b, cols_b, uniform_b) if cols_b else None
     return t, a, b
+
+
+def protein_draw_model(keys, rec_ptr, purpose_base=0):
+    """numpy model of the normals ``cbgx_train_transform_rng`` draws: [n_rec, 3] float64, atom ``a`` of graph ``g`` at counter
+    (a - rec_ptr[g], 0, purpose_base + TRAIN_PROTEIN_NORMAL, 0) under ``keys[g]`` -- ``fill_model`` on the protein CSR at step 0"""
+    return fill_model(keys, rec_ptr, 0, purpose_base + TRAIN_PROTEIN_NORMAL, 3, False)
+
+
+def protein_addresses(keys, rec_ptr, purpose_base=0):
+    """the (key, atom, step, purpose, block) addresses of ``protein_draw_model``: [n_rec, 5] uint64, one row (one Philox call) per atom"""
+    keys = np.asarray(keys, dtype=np.uint64)
+    counts = np.diff(np.asarray(rec_ptr, dtype=np.int64))
+    rows = [(keys[g], a, 0, purpose_base + TRAIN_PROTEIN_NORMAL, 0) for g, n in enumerate(counts) for a in range(int(n))]
+    return np.array(rows, dtype=np.uint64).reshape(-1, 5)
 
 
 TRAIN_PURPOSE_B = {"targetdiff": TRAIN_TYPE_UNIFORM, "diffbp": TRAIN_MASK_UNIFORM, "diffsbdd": TRAIN_TYPE_NORMAL}

@@ -23,6 +23,9 @@ same and are tested against the reference's tables and size function (tests/test
 ``np.random.default_rng([seed, pocket_ids[p], s])``: its ligand size, initial positions and initial types are then the same
 whatever else is in the batch and in whatever order, and the batch carries the stream keys (``noise_keys``) with which the
 samplers draw their step noise under the same rule (cbgbench_amd/noise.py).
+
+``TrainingPlan`` is the training-side counterpart of ``SamplingPlan``: what ``config.data.{train,val}.transform`` asks for at every visit
+of an example (protein noise, centring), applied to collated batches by ``train_cli.apply_plan``.
 """
 import numpy as np
 import torch
@@ -167,6 +170,93 @@ class SamplingPlan:
         if "assign_molsize" in seen and "assign_gensize" in seen:
             raise ValueError("transform list has both assign_molsize and assign_gensize")
         return plan
+
+
+class TrainingPlan:
+    """What the transform list of a training config (``config.data.train.transform`` / ``config.data.val.transform``) asks for at every
+    visit of an example -- the two entries of the reference's per-item chain that the stored complexes have not been through:
+
+    ======================  ===========================================  ==========================================================
+    transform               reference                                    field
+    ======================  ===========================================  ==========================================================
+    add_pos_noise           translation.py:74-89   protein pos + N(0, s) noise_std = s (0 when absent)
+    center_pos              translation.py:5-25                          center = 'protein'   center_flag protein, no mask: the mean
+                                                                                              of the NOISED protein (noise comes first)
+                                                                         center = 'context'   center_flag ligand, mask_flag ctx_flag:
+                                                                                              the ligand atoms with ~ligand_gen_flag; a
+                                                                                              graph without one: its whole ligand
+                                                                         center = 'ligand'    center_flag ligand, no mask
+    center_whole_pos        translation.py:27-50                         center = 'whole'     all protein and ligand atoms
+    ======================  ===========================================  ==========================================================
+
+    The entries must come in the order noise, then centre, as in every shipped list.  What is not known raises ``ValueError``:
+    ``frame_mode: true``, a ``graph_name`` other than protein, any other flag combination, the other order, an entry twice.
+    A list with neither entry -- or a config without a ``data`` section -- gives ``(0, 'protein')``, the identity on complexes that
+    ``ComplexSet`` has already centred on their protein mean: ``train_cli.apply_plan`` then launches nothing and draws nothing."""
+
+    CENTERS = ("protein", "context", "ligand", "whole")
+
+    def __init__(self, noise_std=0.0, center="protein"):
+        noise_std = float(noise_std)
+        if not noise_std >= 0.0:
+            raise ValueError(f"add_pos_noise: noise_std={noise_std} must be >= 0")
+        if center not in self.CENTERS:
+            raise ValueError(f"unknown centring {center!r} (one of {', '.join(self.CENTERS)})")
+        self.noise_std, self.center = noise_std, center
+
+    @property
+    def identity(self):
+        return self.noise_std == 0.0 and self.center == "protein"
+
+    def __eq__(self, other):
+        return isinstance(other, TrainingPlan) and (self.noise_std, self.center) == (other.noise_std, other.center)
+
+    def __repr__(self):
+        return f"TrainingPlan(noise_std={self.noise_std!r}, center={self.center!r})"
+
+    @classmethod
+    def from_config(cls, config, split="train"):
+        """plan of ``config.data.<split>.transform``, ``split`` 'train' or 'val'.  Without ``data.val``: validation is not noised and
+        uses the train list's centring."""
+        if split not in ("train", "val"):
+            raise ValueError(f"split must be 'train' or 'val', not {split!r}")
+        data = (config.get("data", None) or {}) if config is not None else {}
+        section, keep_noise = data.get(split, None), True
+        if section is None and split == "val":
+            section, keep_noise = data.get("train", None), False
+        tlist = (section or {}).get("transform", None) or []
+        noise_std, center = None, None
+        for t in tlist:
+            ty = t["type"]
+            if ty == "add_pos_noise":
+                if center is not None:
+                    raise ValueError("add_pos_noise after the centring transform: only the order noise, then centre is known")
+                if noise_std is not None:
+                    raise ValueError("transform list has add_pos_noise twice")
+                if t.get("frame_mode", False):
+                    raise ValueError("add_pos_noise: frame_mode is not supported (heavy-atom frames are D3FG's, out of scope)")
+                if t.get("graph_name", "protein") != "protein":
+                    raise ValueError(f"add_pos_noise: graph_name={t.get('graph_name')!r} is not supported (protein only)")
+                noise_std = float(t["noise_std"])
+            elif ty in ("center_pos", "center_whole_pos"):
+                if center is not None:
+                    raise ValueError("transform list has two centring transforms")
+                if ty == "center_whole_pos":
+                    center = "whole"
+                    continue
+                flag, mask = t.get("center_flag", None), t.get("mask_flag", None)
+                if flag == "protein" and mask is None:
+                    center = "protein"
+                elif flag == "ligand" and mask == "ctx_flag":
+                    center = "context"
+                elif flag == "ligand" and mask is None:
+                    center = "ligand"
+                else:
+                    raise ValueError(f"center_pos: center_flag={flag!r} mask_flag={mask!r} is not a training-time centring this "
+                                     f"driver knows (protein | ligand | ligand + ctx_flag)")
+            elif ty == "center_frame_pos":
+                raise ValueError("center_frame_pos is not supported (heavy-atom frames are D3FG's, out of scope)")
+        return cls(noise_std if noise_std is not None and keep_noise else 0.0, center if center is not None else "protein")
 
 
 class PocketSet:

@@ -16,12 +16,21 @@ data-parallel the way SURVEY.md 8e/8f-4 asks:
 
     python -m cbgbench_amd.train_cli --config configs/denovo/train/targetdiff.yml --logdir logs
                                      [--data complexes.pt | --synthetic 256] [--resume ckpt.pt] [--max_iters N]
-                                     [--noise {torch,counter}]
+                                     [--noise {torch,counter}] [--ignore_data_transforms]
 
 Complex input: a ``torch.save``d list of dicts with ``protein_pos [n,3]``, ``protein_atom_feature [n,7]``,
 ``protein_aa_type [n]``, ``ligand_pos [m,3]``, ``ligand_atom_type [m]`` and optionally ``ligand_gen_flag [m]`` (what the
-reference's featurizers produce); they are centred on the protein mean (``center_pos``, translation.py:5-25) and collated into
+reference's featurizers produce); they are stored centred on the protein mean (``center_pos``, translation.py:5-25) and collated into
 the ``MergeKeys`` + ``follow_batch`` schema.  Without ``--data``, synthetic complexes stand in.
+
+Every batch then goes through the per-visit transforms of its split's transform list (``config.data.train.transform``,
+``config.data.val.transform``; ``priors.TrainingPlan``), as the reference's dataset does at every ``__getitem__``: ``add_pos_noise`` --
+fresh protein-coordinate noise at every visit of an example -- followed by the config's centring (``center_pos`` on the noised protein,
+on the context atoms ``~ligand_gen_flag`` or on the ligand; ``center_whole_pos``), in ONE libcbgx launch per batch (``apply_plan``,
+csrc/train_transform.hip), and the batch records the shift as ``translation``.  A list with neither entry, or a config without a ``data``
+section, leaves the batches as collated (no launch, no draw); ``--ignore_data_transforms`` does so for any config.  With
+``--noise counter`` the protein noise is a function of (seed, example, iteration, atom) like the rest of the step's noise; validation
+without a ``data.val`` section is not noised and takes the train list's centring.
 """
 import argparse
 import os
@@ -34,6 +43,7 @@ from . import get_model, load_config, set_num_atom_type, sharding, synthetic
 from . import noise as _noise
 from .config import checkpoint_config, load_checkpoint_file
 from .evaluate import Evaluator
+from .priors import TrainingPlan
 from .train import FlatGradients, broadcast_parameters, get_optimizer, get_scheduler, train_step, validate
 
 
@@ -70,9 +80,10 @@ class ComplexSet:
         start = torch.cumsum(cnt, 0) - cnt
         return ptr[ids][seg] + (torch.arange(int(cnt.sum())) - start[seg]), seg
 
-    def collate(self, ids, device="cpu", example_ids=False):
+    def collate(self, ids, device="cpu", example_ids=False, ptrs=False):
         """``example_ids=True`` (the counter noise mode): the batch also carries ``example_index`` -- ``ids`` as a host array, the
-        global identity its noise is keyed by -- and ``ligand_ptr``, the [B + 1] int32 ligand CSR on ``device``."""
+        global identity its noise is keyed by -- and ``ligand_ptr``, the [B + 1] int32 ligand CSR on ``device``.
+        ``ptrs=True`` (a batch that ``apply_plan`` will transform): ``protein_ptr`` and ``ligand_ptr``, both CSRs, built on the host."""
         ids = torch.as_tensor(ids, dtype=torch.long)
         rr, rseg = self._rows(self.rec_ptr, ids)
         lr, lseg = self._rows(self.lig_ptr, ids)
@@ -92,6 +103,11 @@ class ComplexSet:
             b["example_index"] = ids.numpy().copy()
             cnt = self.lig_ptr[ids + 1] - self.lig_ptr[ids]
             b["ligand_ptr"] = torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(cnt, 0)]).to(torch.int32).to(device)
+        if ptrs:
+            for name, ptr in (("protein_ptr", self.rec_ptr), ("ligand_ptr", self.lig_ptr)):
+                if name not in b:
+                    cnt = ptr[ids + 1] - ptr[ids]
+                    b[name] = torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(cnt, 0)]).to(torch.int32).to(device)
         return b
 
 
@@ -174,6 +190,127 @@ class PositionedLoader:
         return self._perm(e)[k * self.global_bs:(k + 1) * self.global_bs][self.rank::self.world].tolist()
 
 
+# ---- the config's per-visit transforms ---------------------------------------------------------------------------------------------
+CENTER_MODES = {"protein": 0, "context": 1, "ligand": 2, "whole": 3}      # include/cbgx.h CBGX_CENTER_*
+
+
+def _csr(batch, ptr_key, batch_key, B, counts=False):
+    """the [B + 1] int32 CSR of one side of the batch on its device: the batch's own (``collate(ptrs=True)``), else from the sorted
+    ``*_element_batch`` ids.  ``counts=True``: the per-graph sizes as a host list instead."""
+    ptr = batch.get(ptr_key, None)
+    idx = batch[batch_key]
+    if ptr is None:
+        if idx.numel() and not bool((idx[1:] >= idx[:-1]).all()):
+            raise ValueError(f"apply_plan needs {batch_key} sorted by graph")
+        ptr = torch.cat([torch.zeros(1, dtype=torch.long, device=idx.device), torch.bincount(idx, minlength=B).cumsum(0)]).to(torch.int32)
+    if ptr.dtype != torch.int32 or ptr.shape[0] != B + 1 or ptr.device != idx.device:
+        raise ValueError(f"{ptr_key} must be the [B + 1] int32 CSR on the batch's device (B = {B})")
+    return (ptr[1:] - ptr[:-1]).tolist() if counts else ptr.contiguous()
+
+
+def _context_flag(batch):
+    """context atoms = ~ligand_gen_flag; a batch without the flag has none"""
+    gen = batch.get("ligand_gen_flag", None)
+    return None if gen is None else ~gen.to(torch.bool)
+
+
+def apply_plan_tensors(batch, plan, eps=None):
+    """``apply_plan`` restated with tensor operations, graph by graph in the reference's own expressions (``AddPosNoise`` then
+    ``CenterPos`` / ``CenterWholePos``, translation.py): ``pos + eps * noise_std``, then ``mean(dim=0)`` of the centre set --
+    ``(ligand.sum(0) + protein.sum(0)) / n`` for 'whole'.  On one graph it gives the bits of the reference's classes.  It is what a CPU
+    batch gets (stub models, gloo tests) and what the GPU tests compare the kernel with; an empty centre set gives the zero vector."""
+    x_rec, x_lig = batch["protein_pos"], batch["ligand_pos"]
+    B = int(batch["num_graphs"])
+    rec_n = _csr(batch, "protein_ptr", "protein_element_batch", B, counts=True)
+    lig_n = _csr(batch, "ligand_ptr", "ligand_element_batch", B, counts=True)
+    ctx = _context_flag(batch)
+    if plan.noise_std > 0:
+        if eps is None:
+            raise ValueError("apply_plan_tensors: a plan with noise needs eps")
+        x_rec = x_rec + eps * plan.noise_std
+    rec_out, lig_out, centers, r0, l0 = [], [], [], 0, 0
+    for nr, nl in zip(rec_n, lig_n):
+        P, L = x_rec[r0:r0 + nr], x_lig[l0:l0 + nl]
+        zero = x_rec.new_zeros(3)
+        if plan.center == "protein":
+            c = P.mean(dim=0) if nr else zero
+        elif plan.center == "whole":
+            c = (L.sum(0) + P.sum(0)) / (nl + nr) if nl + nr else zero
+        else:
+            m = ctx[l0:l0 + nl] if plan.center == "context" and ctx is not None else None
+            if m is not None and int(m.sum()) > 0:
+                c = L[m].mean(dim=0)
+            else:
+                c = L.mean(dim=0) if nl else zero
+        rec_out.append(P - c)
+        lig_out.append(L - c)
+        centers.append(c)
+        r0, l0 = r0 + nr, l0 + nl
+    out = dict(batch)
+    out["protein_pos"] = torch.cat(rec_out) if rec_out else x_rec
+    out["ligand_pos"] = torch.cat(lig_out) if lig_out else x_lig
+    out["translation"] = torch.stack(centers) if centers else x_rec.new_zeros(0, 3)
+    return out
+
+
+def apply_plan(batch, plan, noise=None, eps=None):
+    """The per-visit transforms of the config (``priors.TrainingPlan``) on a collated batch: protein noise, then the centring.  Returns the
+    batch with ``protein_pos`` / ``ligand_pos`` replaced and ``translation`` [B, 3] added -- the shift relative to the stored frame
+    (``ComplexSet``: the protein mean of the stored coordinates).  The identity plan ``(0, 'protein')`` returns ``batch`` itself: no
+    launch, no draw.
+    On a CUDA device: ONE libcbgx launch (csrc/train_transform.hip).  ``noise`` a ``CounterNoise`` (``noise.training_noise`` /
+    ``validation_noise`` of the batch's examples) selects ``cbgx_train_transform_rng``: the normals are drawn in the kernel at the
+    protein atoms' addresses (noise.py), so an example's transformed coordinates do not depend on its batch; the batch should carry
+    ``protein_ptr`` / ``ligand_ptr`` (``collate(ptrs=True)``), else they are rebuilt from the batch ids.  Otherwise ``eps`` [n_rec, 3]
+    -- the caller's (a replay), or ``torch.randn`` from the torch generator, drawn only when ``noise_std > 0`` -- goes to
+    ``cbgx_train_transform``.  On a CPU device ``apply_plan_tensors`` runs instead; a ``CounterNoise`` there raises: its draws are made
+    by GPU kernels."""
+    if plan is None or plan.identity:
+        return batch
+    noise = _noise.resolve(noise)
+    x_rec, x_lig = batch["protein_pos"], batch["ligand_pos"]
+    dev, n_rec, n_lig = x_rec.device, int(x_rec.shape[0]), int(x_lig.shape[0])
+    B = batch.get("num_graphs", None)
+    if B is None:
+        B = batch["num_graphs"] = int(max(batch["protein_element_batch"].max(), batch["ligand_element_batch"].max())) + 1
+    B = int(B)
+    if noise is not None and noise.num_graphs != B:
+        raise ValueError(f"noise has {noise.num_graphs} stream keys for a batch of {B} graphs")
+    if noise is not None and eps is not None:
+        raise ValueError("apply_plan: pass either noise= (counter mode) or eps= (a replay), not both")
+    if eps is not None and (tuple(eps.shape) != (n_rec, 3) or eps.device != dev or eps.dtype != torch.float32):
+        raise ValueError(f"eps must be a float32 [{n_rec}, 3] tensor on the batch's device")
+    if dev.type != "cuda":
+        if noise is not None:
+            raise ValueError("counter noise is generated by the GPU kernels: the batch must live on the GPU")
+        if eps is None and plan.noise_std > 0:
+            eps = torch.randn(n_rec, 3, device=dev)
+        return apply_plan_tensors(batch, plan, eps if plan.noise_std > 0 else None)
+    from . import _native
+    rec_ptr = _csr(batch, "protein_ptr", "protein_element_batch", B)
+    lig_ptr = _csr(batch, "ligand_ptr", "ligand_element_batch", B)
+    ctx = _context_flag(batch) if plan.center == "context" else None
+    if ctx is not None:
+        ctx = ctx.contiguous().view(torch.uint8)
+    x_rec, x_lig = x_rec.to(torch.float32).contiguous(), x_lig.to(torch.float32).contiguous()
+    rec_out, lig_out = torch.empty_like(x_rec), torch.empty_like(x_lig)
+    center = torch.empty(B, 3, dtype=torch.float32, device=dev)
+    head = (_native.ptr(x_rec), _native.ptr(x_lig), _native.ptr(rec_ptr), _native.ptr(lig_ptr), _native.ptr(ctx), B, n_rec, n_lig,
+            float(plan.noise_std), CENTER_MODES[plan.center])
+    tail = (_native.ptr(rec_out), _native.ptr(lig_out), _native.ptr(center), _native.current_stream(dev))
+    if noise is not None:
+        _native.check(_native.lib().cbgx_train_transform_rng(*head, _native.ptr(noise.device_keys(dev)), noise.purpose_base, *tail),
+                      "cbgx_train_transform_rng")
+    else:
+        if eps is None and plan.noise_std > 0:
+            eps = torch.randn(n_rec, 3, device=dev)
+        eps = eps.contiguous() if eps is not None and plan.noise_std > 0 else None
+        _native.check(_native.lib().cbgx_train_transform(*head, _native.ptr(eps), *tail), "cbgx_train_transform")
+    out = dict(batch)
+    out["protein_pos"], out["ligand_pos"], out["translation"] = rec_out, lig_out, center
+    return out
+
+
 # ---- checkpoints -----------------------------------------------------------------------------------------------
 def save_checkpoint(path, config, model, optimizer, scheduler, iteration, avg_val_loss):
     os.makedirs(os.path.dirname(path), exist_ok=True)
@@ -202,15 +339,22 @@ def load_checkpoint(path, model, optimizer=None, scheduler=None, finetune=False,
 
 # ---- the loop --------------------------------------------------------------------------------------------------
 def run(config, config_name, train_set, val_set, dev, logdir, tag="", resume=None, finetune=False, max_iters=None,
-        log=print, noise="torch"):
-    """``noise="counter"``: every training call gets ``noise.training_noise(seed, example indices, it)``, every validation call
+        log=print, noise="torch", data_transforms=True):
+    """``data_transforms`` (default on): every training batch goes through the per-visit transforms of ``config.data.train.transform``,
+    every validation batch through those of ``config.data.val.transform`` (``priors.TrainingPlan``, ``apply_plan``) before the model
+    call; a config without them is not touched.  Off (``--ignore_data_transforms``): protein-centred, unnoised batches for any config.
+    ``noise="counter"``: every training call gets ``noise.training_noise(seed, example indices, it)``, every validation call
     ``noise.validation_noise(seed, example indices)``, and the loader is positioned from the iteration (``PositionedLoader``): the noised
     inputs of an iteration do not depend on the world size, validation is a function of the weights, and a resumed run sees the
     batches and the noise the uninterrupted run saw.  ``"torch"`` (default): the torch generator and ShardedLoader, as before."""
     if noise not in ("torch", "counter"):
         raise ValueError(f"noise must be 'torch' or 'counter', not {noise!r}")
     counter = noise == "counter"
+    plan_tr = TrainingPlan.from_config(config, "train") if data_transforms else TrainingPlan()
+    plan_va = TrainingPlan.from_config(config, "val") if data_transforms else TrainingPlan()
     rank, world, _ = sharding.env_rank_world()
+    if rank == 0 and not (plan_tr.identity and plan_va.identity):
+        log(f"[data] train {plan_tr} | val {plan_va}")
     tc, ec = config.train, config.get("eval", {})
     max_iters = int(max_iters if max_iters is not None else tc.max_iters)
     val_freq = int(ec.get("val_freq", 1000))
@@ -240,10 +384,11 @@ def run(config, config_name, train_set, val_set, dev, logdir, tag="", resume=Non
     t_last = time.perf_counter()
     for it in range(it_first, max_iters + 1):
         if counter:
-            batch = train_set.collate(positioned.batch(it), dev, example_ids=True)
+            batch = train_set.collate(positioned.batch(it), dev, example_ids=True, ptrs=not plan_tr.identity)
             step_noise = {"noise": _noise.training_noise(seed, batch["example_index"], it)}
         else:
-            batch, step_noise = train_set.collate(next(train_it), dev), {}
+            batch, step_noise = train_set.collate(next(train_it), dev, ptrs=not plan_tr.identity), {}
+        batch = apply_plan(batch, plan_tr, **step_noise)
         loss, loss_dict, grad_norm, t_ar = train_step(model, batch, optimizer, flat, weights,
                                                       max_grad_norm=float(tc.get("max_grad_norm", 8.0)), **step_noise)
         if it % report_freq == 0 and rank == 0:
@@ -255,10 +400,13 @@ def run(config, config_name, train_set, val_set, dev, logdir, tag="", resume=Non
             t_last = now
         if it % val_freq == 0:
             if counter:
-                avg, metrics = validate(model, (val_set.collate(ids, dev, example_ids=True) for ids in val_batches), weights, evaluator,
-                                        noise_for=lambda b: _noise.validation_noise(seed, b["example_index"]))
+                val_noise = lambda b: _noise.validation_noise(seed, b["example_index"])
+                avg, metrics = validate(model, (apply_plan(b, plan_va, noise=val_noise(b) if plan_va.noise_std > 0 else None) for b in
+                                                (val_set.collate(ids, dev, example_ids=True, ptrs=not plan_va.identity)
+                                                 for ids in val_batches)), weights, evaluator, noise_for=val_noise)
             else:
-                avg, metrics = validate(model, (val_set.collate(ids, dev) for ids in val_batches), weights, evaluator)
+                avg, metrics = validate(model, (apply_plan(val_set.collate(ids, dev, ptrs=not plan_va.identity), plan_va)
+                                                for ids in val_batches), weights, evaluator)
             history.append((it, avg))
             metric_history.append((it, metrics))
             if scheduler is not None and it != it_first:         # train.py:247-251
@@ -293,6 +441,9 @@ def main(argv=None):
     ap.add_argument("--noise", choices=("torch", "counter"), default="torch",
                     help="counter: time and noise of every training and validation call are functions of (seed, example, iteration) "
                          "-- independent of world size, batch size and batch position; resume continues data order and noise")
+    ap.add_argument("--ignore_data_transforms", action="store_true",
+                    help="do not apply the config's per-visit transforms (add_pos_noise, center_pos / center_whole_pos of "
+                         "data.train.transform / data.val.transform): protein-centred, unnoised batches for any config")
     args = ap.parse_args(argv)
 
     rank, world, local = sharding.init_process_group()
@@ -316,7 +467,7 @@ def main(argv=None):
         tr, va = raw[:-k], raw[-k:]
     resume = args.resume or config.get("resume", None)
     out = run(config, config_name, ComplexSet(tr), ComplexSet(va), dev, args.logdir, args.tag, resume, args.finetune,
-              args.max_iters, noise=args.noise)
+              args.max_iters, noise=args.noise, data_transforms=not args.ignore_data_transforms)
     if rank == 0:
         print(f"done: best validation loss at iteration {out['best_iter']}, checkpoints in {out['ckpt_dir']}")
     return 0

@@ -299,6 +299,8 @@ int cbgx_diffsbdd_step(const float *x_den, const float *logits, const int32_t *g
 #define CBGX_NOISE_TRAIN_TYPE_UNIFORM 9  /* type uniform, components 0..C-1 (TargetDiff's Gumbel draw) */
 #define CBGX_NOISE_TRAIN_MASK_UNIFORM 10 /* mask draw, component 0 (DiffBP) */
 #define CBGX_NOISE_TRAIN_TYPE_NORMAL 11  /* type normal, components 0..C-1 (DiffSBDD) */
+#define CBGX_NOISE_TRAIN_PROTEIN_NORMAL 12 /* protein-coordinate augmentation of a training visit, components 0..2: counter (the atom's
+                                            index inside its POCKET, 0, base + 12, 0); see cbgx_train_transform_rng */
 #define CBGX_NOISE_PURPOSE_STRIDE 16 /* purpose bases are multiples of this (0: a plain run) */
 /* cbgx_noise_fill: out[a][col] (caller-owned, [n_lig, cols] floats) = component col of the draw of `purpose` at `step` for ligand
  *   atom a -- normals (uniform == 0) or uniforms (uniform != 0).  stream_keys [B] uint64; lig_ptr [B+1] the ligand CSR (ligand arrays
@@ -343,6 +345,37 @@ int cbgx_targetdiff_train_noise_rng(const float *x0, const int64_t *v0, const in
                                     const float *log_one_minus_alphas_cumprod, const uint64_t *stream_keys,
                                     const int32_t *lig_ptr, int n_graphs, int purpose_base, int n_t, const int64_t *t_in,
                                     int64_t *t_out, float *x_t, float *c_t, int64_t *v_t, void *stream);
+/* Per-visit transforms of a training batch: the protein-coordinate augmentation (add_pos_noise) followed by the centring of the graph
+ *   (center_pos / center_whole_pos), for the whole batch in ONE launch, one 256-thread workgroup per graph, out of place; the caller
+ *   owns every buffer.  x_rec [n_rec,3], x_lig [n_lig,3]: the stored coordinates, both arrays sorted by graph; rec_ptr, lig_ptr [B+1]
+ *   int32: their CSR; ctx [n_lig] uint8 (context atoms != 0) or NULL (no graph has a context atom).
+ *   Noise: x_rec' = fmaf(sigma, eps, x_rec) when sigma > 0, x_rec itself when sigma == 0.  eps [n_rec,3], or NULL, which means no noise
+ *   and requires sigma == 0.
+ *   Centre of graph g = mean of its centre set: */
+#define CBGX_CENTER_PROTEIN 0 /* the NOISED protein atoms (center_pos, center_flag protein, after add_pos_noise) */
+#define CBGX_CENTER_CONTEXT 1 /* the ligand atoms with ctx != 0; a graph without one: its whole ligand (translation.py:13-16) */
+#define CBGX_CENTER_LIGAND 2  /* the ligand atoms */
+#define CBGX_CENTER_WHOLE 3   /* the noised protein atoms followed by the ligand atoms (center_whole_pos) */
+/*   The sum has a fixed order that depends on the graph's own atoms only: the candidates of the set are numbered in atom order (WHOLE:
+ *   protein atoms first, then ligand atoms; CONTEXT: every ligand atom is a candidate and an atom outside the context adds nothing),
+ *   thread k adds candidates k, k + 256, ... in that order, a fixed tree (strides 128 ... 1) adds the 256 partial sums, one IEEE
+ *   division by the member count follows; no atomics.  An empty set (after the CONTEXT -> LIGAND fallback) gives the zero vector.
+ *   Outputs: x_rec_out [n_rec,3] = x_rec' - centre, x_lig_out [n_lig,3] = x_lig - centre, center_out [B,3] = centre.  Every element of
+ *   every graph is written, center_out rows of empty graphs too.  CSR entries outside [0, n] are clamped.
+ *   CBGX_E_INVALID, before anything touches the device: a NULL output or input that has elements, negative sizes, sigma < 0 (or NaN), an
+ *   unknown center_mode, eps == NULL with sigma > 0, a purpose_base that is not a non-negative multiple of CBGX_NOISE_PURPOSE_STRIDE.
+ * cbgx_train_transform_rng: the same with eps replaced by (stream_keys [B], purpose_base): every lane evaluates the normals of its
+ *   protein atoms itself, at counter (the atom's index inside its pocket, step 0, purpose_base + CBGX_NOISE_TRAIN_PROTEIN_NORMAL,
+ *   block 0), components 0..2, under the graph's training / validation stream key -- the bits of cbgx_noise_fill(stream_keys, rec_ptr,
+ *   B, n_rec, cols = 3, normals, purpose_base + CBGX_NOISE_TRAIN_PROTEIN_NORMAL, step = 0) followed by cbgx_train_transform.
+ *   Precondition: the protein atoms of an example keep their order. */
+int cbgx_train_transform(const float *x_rec, const float *x_lig, const int32_t *rec_ptr, const int32_t *lig_ptr,
+                         const uint8_t *ctx, int n_graphs, int n_rec, int n_lig, float sigma, int center_mode, const float *eps,
+                         float *x_rec_out, float *x_lig_out, float *center_out, void *stream);
+int cbgx_train_transform_rng(const float *x_rec, const float *x_lig, const int32_t *rec_ptr, const int32_t *lig_ptr,
+                             const uint8_t *ctx, int n_graphs, int n_rec, int n_lig, float sigma, int center_mode,
+                             const uint64_t *stream_keys, int purpose_base, float *x_rec_out, float *x_lig_out,
+                             float *center_out, void *stream);
 int cbgx_targetdiff_epilogue_rng(const float *x_den, const float *logits, const int32_t *lig_rows, const float *x_lig,
                                  const float *c_lig, const uint8_t *gen_lig, int n_lig, int num_classes, int t,
                                  int num_timesteps, const float *const *tables, const uint64_t *stream_keys,
