@@ -89,6 +89,8 @@ EXPORTS = {
                                      _vp]),
     "cbgx_h2x_stack_backward_ex": (_i, [_vp, _i, _vp, _sz, _vp, _vp, _vp, _i, _vp, ctypes.POINTER(_vp), _i, _vp, _vp, _vp,
                                         _sz, _vp]),
+    "cbgx_ligand_geometry": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "cbgx_ligand_geometry_tables": (_i, [_vp] * 7),
     "cbgx_profile_begin": (_i, [_i]),
     "cbgx_profile_end": (_i, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i), _i]),
 }

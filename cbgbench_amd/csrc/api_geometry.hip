@@ -1,0 +1,69 @@
+// libcbgx -- C ABI of the geometry report (include/cbgx.h, geometry.hip): argument checks, the ligand-size check, the launch
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "../../include/cbgx.h"
+#include "kernels.h"
+
+namespace cbgx { int set_error(int code, const char* fmt, ...); }
+using namespace cbgx;
+
+// lig_ptr [count] on the host.  Device (or managed) memory: a copy on the caller's stream and a wait for it.  Pinned host memory: read in
+// place.  Anything the runtime does not know -- plain host memory, or no device at all -- is read in place too and reported as not
+// visible to the device, so that the size check works without one and nothing is launched on such a pointer.
+static int fetch_csr(const int32_t* p, int count, std::vector<int32_t>& host, bool& device_visible, hipStream_t s) {
+    host.resize((size_t)count);
+    hipPointerAttribute_t attr;
+    const hipError_t e = hipPointerGetAttributes(&attr, p);
+    if (e == hipSuccess && attr.type != hipMemoryTypeUnregistered && attr.type != hipMemoryTypeHost) {
+        device_visible = true;
+        hipError_t c = hipMemcpyAsync(host.data(), p, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, s);
+        if (c == hipSuccess) c = hipStreamSynchronize(s);
+        if (c != hipSuccess) return set_error(CBGX_E_HIP, "ligand_geometry: reading lig_ptr: %s", hipGetErrorString(c));
+        return CBGX_OK;
+    }
+    device_visible = e == hipSuccess && attr.type == hipMemoryTypeHost;
+    if (e != hipSuccess) (void)hipGetLastError();      // not an error of this call: the pointer is simply not the runtime's
+    memcpy(host.data(), p, sizeof(int32_t) * (size_t)count);
+    return CBGX_OK;
+}
+
+extern "C" {
+
+int cbgx_ligand_geometry(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, const float* x_rec,
+                         const uint8_t* z_rec, const int32_t* rec_ptr, int n_rec, int n_graphs, int32_t* nr_bonds, uint8_t* flags,
+                         int32_t* graph_out, void* stream) {
+    if (n_graphs < 0 || n_lig < 0 || n_rec < 0)
+        return set_error(CBGX_E_INVALID, "ligand_geometry: negative count (B=%d n_lig=%d n_rec=%d)", n_graphs, n_lig, n_rec);
+    if ((n_graphs > 0 && (!lig_ptr || !rec_ptr || !graph_out)) || (n_lig > 0 && (!x_lig || !z_lig || !nr_bonds || !flags)) ||
+        (n_rec > 0 && (!x_rec || !z_rec)))
+        return set_error(CBGX_E_INVALID, "ligand_geometry: NULL pointer");
+    if (n_graphs == 0) return CBGX_OK;
+    std::vector<int32_t> ptr;
+    bool device_visible = false;
+    const int rc = fetch_csr(lig_ptr, n_graphs + 1, ptr, device_visible, (hipStream_t)stream);
+    if (rc != CBGX_OK) return rc;
+    for (int g = 0; g < n_graphs; ++g) {       // the ranges the kernel uses: clamped to the array
+        const int l0 = std::min(std::max(ptr[g], 0), n_lig), l1 = std::min(std::max(ptr[g + 1], l0), n_lig);
+        if (l1 - l0 > CBGX_GEOMETRY_MAX_LIGAND)
+            return set_error(CBGX_E_INVALID, "ligand_geometry: graph %d has %d ligand atoms, more than the %d one workgroup stages", g,
+                             l1 - l0, CBGX_GEOMETRY_MAX_LIGAND);
+    }
+    if (!device_visible)
+        return set_error(CBGX_E_INVALID, "ligand_geometry: lig_ptr is not memory the device can read");
+    const hipError_t e = launch_ligand_geometry(x_lig, z_lig, lig_ptr, n_lig, x_rec, z_rec, rec_ptr, n_rec, n_graphs, nr_bonds, flags,
+                                                graph_out, (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(CBGX_E_HIP, "ligand_geometry: launch: %s", hipGetErrorString(e));
+    return CBGX_OK;
+}
+
+int cbgx_ligand_geometry_tables(int32_t* bond_pm, int32_t* margins, int32_t* allowed, uint8_t* elements, uint8_t* vdw_z, double* vdw_r,
+                                double* tolerance) {
+    ligand_geometry_tables(bond_pm, margins, allowed, elements, vdw_z, vdw_r, tolerance);
+    return CBGX_OK;
+}
+
+}  // extern "C"

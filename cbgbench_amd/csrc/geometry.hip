@@ -1,0 +1,232 @@
+// libcbgx -- geometry report of a batch of sampled ligands: atom / molecule stability and protein-ligand steric clash, the two metrics of
+// the reference's quality path that need coordinates and elements only (repo/tools/geometry/eval_stability.py, check_stability with
+// hs=False; repo/tools/geometry/eval_steric_clash.py, detect_clash), for a whole batch in ONE launch, one 256-thread workgroup per graph.
+//   staging   the graph's ligand coordinates (fp32) and element codes go to LDS; a ligand has at most GEO_MAX atoms (the host entry
+//             refuses larger ones before the launch).  The number of protein atoms is not limited: they are streamed.
+//   distance  coordinates widened to fp64; dx = xi - xj (dy, dz likewise); s = (dx dx + dy dy) + dz dz, every product and sum rounded on
+//             its own; d = sqrt(s), correctly rounded.  Contraction is OFF for this translation unit (the pragma below): the products and
+//             sums are written as plain operators because the header's __dmul_rn / __dadd_rn are plain operators too and would be fused
+//             after inlining under the default -ffp-contract=fast-honor-pragmas.
+//   bonds     order(i, j) of a ligand pair i != j from the pair's single / double / triple bond lengths b1 / b2 / b3 (pm, -1: none) and
+//             p = 100.0 d:   p < b1 + 10 ? (p < b2 + 5 ? (p < b3 + 3 ? 3 : 2) : 1) : 0, comparisons strict.  nr_bonds[i] = sum_j order(i, j):
+//             thread i, i + 256, ... walks its whole row -- the symmetric work is done twice, so there are no atomics and no order.
+//             Atom i is stable iff allowed[z_i] >= nr_bonds[i] > 0.
+//   clash     d < (r_lig + r_other) - 0.4 in fp64, in that order.  Inter-clash: thread k, k + 256, ... takes protein atoms and tests them
+//             against the ligand in LDS; a hit marks the ligand atom with an LDS integer atomicOr (order-independent).  Intra-clash:
+//             ligand pairs i != j whose TABLE bond order is 0, found in the row walk.  The reference masks intra-ligand pairs with RDKit's
+//             bond adjacency; the table bond is this library's RDKit-free stand-in (flag CBGX_GEOM_INTRA_CLASH, field
+//             intra_clash_table_bonds of the Python side).
+//   elements  a protein atom whose element has no radius (Se: the reference raises KeyError there) takes no part and is counted per graph;
+//             a ligand atom outside {H, C, N, O, F, P, S, Cl} has nr_bonds = 0, is unstable, takes no part in bonds or clashes and carries
+//             CBGX_GEOM_UNKNOWN_ELEMENT.
+//   shortcut  a pair with s >= 25 (d >= 5 A exactly, sqrt being monotonic and sqrt(25) = 5) is skipped before the square root: the largest
+//             bond threshold is 2.31 A (P-P, 221 + 10 pm) and the largest clash threshold 4.14 A (Cl...Cl), so no result can change.
+//   outputs   nr_bonds, flags and the six per-graph counts (integer reductions of the flags) -- every element of every graph is written.
+//
+// Constants (physical; written here as dense arrays over an element code, built at compile time from pair lists):
+//   bond lengths  the table EDM's stability metric uses (Hoogeboom et al., "Equivariant Diffusion for Molecule Generation in 3D", 2022,
+//                 qm9/bond_analyze.py), itself from http://www.wiredchemist.com/chemistry/data/bond_energies_lengths.html and
+//                 http://chemistry-reference.com/tables/Bond%20Lengths%20and%20Enthalpies.pdf; margins 10 / 5 / 3 pm as tuned there on QM9.
+//   valences      the usual maximum valences of the eight elements (same source).
+//   radii, 0.4 A  van der Waals radii (Bondi-type) and the overlap of Proteopedia's definition: "a clash is considered to occur when the
+//                 van der Waals radii overlap by >= 0.4 A between non-bound atoms" (https://proteopedia.org/wiki/index.php/Clashes).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/cbgx.h"
+#include "kernels.h"
+
+#pragma clang fp contract(off)
+
+namespace cbgx {
+
+constexpr int GEO_THREADS = 256;
+constexpr int GEO_MAX = CBGX_GEOMETRY_MAX_LIGAND;
+constexpr int GEO_EL = 8;         // element codes 0..7 = H C N O F P S Cl: bond table, valences, radii
+constexpr int GEO_VDW = 9;        // code 8 = Br: a radius only
+constexpr int GEO_NONE = 255;     // no code
+constexpr double GEO_FAR2 = 25.0; // squared distance from which no threshold can be met (see `shortcut` above)
+
+enum : int { EL_H = 0, EL_C, EL_N, EL_O, EL_F, EL_P, EL_S, EL_CL, EL_BR };
+
+struct GeoPair { int a, b, pm; };
+
+struct GeoTables {
+    int32_t bond_pm[3][GEO_EL][GEO_EL];   // [order - 1][code][code], -1: no such bond
+    int32_t margin[3];
+    int32_t allowed[GEO_EL];
+    uint8_t z[GEO_VDW];                   // atomic number of a code
+    double radius[GEO_VDW];
+    double tolerance;
+};
+
+constexpr GeoTables make_geo_tables() {
+    constexpr GeoPair single_pm[] = {
+        {EL_H, EL_H, 74},   {EL_H, EL_C, 109},  {EL_H, EL_N, 101},  {EL_H, EL_O, 96},   {EL_H, EL_F, 92},   {EL_H, EL_P, 144},
+        {EL_H, EL_S, 134},  {EL_H, EL_CL, 127}, {EL_C, EL_C, 154},  {EL_C, EL_N, 147},  {EL_C, EL_O, 143},  {EL_C, EL_F, 135},
+        {EL_C, EL_P, 184},  {EL_C, EL_S, 182},  {EL_C, EL_CL, 177}, {EL_N, EL_N, 145},  {EL_N, EL_O, 140},  {EL_N, EL_F, 136},
+        {EL_N, EL_P, 177},  {EL_N, EL_S, 168},  {EL_N, EL_CL, 175}, {EL_O, EL_O, 148},  {EL_O, EL_F, 142},  {EL_O, EL_P, 163},
+        {EL_O, EL_S, 151},  {EL_O, EL_CL, 164}, {EL_F, EL_F, 142},  {EL_F, EL_P, 156},  {EL_F, EL_S, 158},  {EL_F, EL_CL, 166},
+        {EL_P, EL_P, 221},  {EL_P, EL_S, 210},  {EL_P, EL_CL, 203}, {EL_S, EL_S, 204},  {EL_S, EL_CL, 207}, {EL_CL, EL_CL, 199}};
+    constexpr GeoPair double_pm[] = {{EL_C, EL_C, 134}, {EL_C, EL_N, 129}, {EL_C, EL_O, 120}, {EL_C, EL_S, 160}, {EL_N, EL_N, 125},
+                                     {EL_N, EL_O, 121}, {EL_O, EL_O, 121}, {EL_O, EL_P, 150}, {EL_P, EL_S, 186}};
+    constexpr GeoPair triple_pm[] = {{EL_C, EL_C, 120}, {EL_C, EL_N, 116}, {EL_C, EL_O, 113}, {EL_N, EL_N, 110}};
+    GeoTables t{};
+    for (int o = 0; o < 3; ++o)
+        for (int a = 0; a < GEO_EL; ++a)
+            for (int b = 0; b < GEO_EL; ++b) t.bond_pm[o][a][b] = -1;
+    for (const GeoPair& p : single_pm) t.bond_pm[0][p.a][p.b] = t.bond_pm[0][p.b][p.a] = p.pm;
+    for (const GeoPair& p : double_pm) t.bond_pm[1][p.a][p.b] = t.bond_pm[1][p.b][p.a] = p.pm;
+    for (const GeoPair& p : triple_pm) t.bond_pm[2][p.a][p.b] = t.bond_pm[2][p.b][p.a] = p.pm;
+    t.margin[0] = 10; t.margin[1] = 5; t.margin[2] = 3;
+    //                      H  C  N  O  F  P   S   Cl  Br
+    constexpr int zs[] =   {1, 6, 7, 8, 9, 15, 16, 17, 35};
+    constexpr int val[] =  {1, 4, 3, 2, 1, 5,  4,  1};
+    constexpr double r[] = {1.2, 1.7, 1.55, 1.52, 1.47, 1.8, 1.8, 2.27, 1.85};
+    for (int c = 0; c < GEO_VDW; ++c) { t.z[c] = (uint8_t)zs[c]; t.radius[c] = r[c]; }
+    for (int c = 0; c < GEO_EL; ++c) t.allowed[c] = val[c];
+    t.tolerance = 0.4;
+    return t;
+}
+
+static const GeoTables h_geo = make_geo_tables();      // what cbgx_ligand_geometry_tables hands out
+__constant__ GeoTables d_geo = make_geo_tables();      // what the kernel reads: the same initialiser
+
+// element code of an atomic number among the first `n_codes` codes, GEO_NONE when it has none
+__device__ __forceinline__ int geo_code(uint8_t z, int n_codes) {
+    int code = GEO_NONE;
+#pragma unroll
+    for (int c = 0; c < GEO_VDW; ++c)
+        if (c < n_codes && d_geo.z[c] == z) code = c;
+    return code;
+}
+
+// squared distance in fp64 from fp32 coordinates, each operation rounded on its own
+__device__ __forceinline__ double geo_dist2(double ax, double ay, double az, float bx, float by, float bz) {
+    const double dx = ax - (double)bx, dy = ay - (double)by, dz = az - (double)bz;
+    const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
+    return (xx + yy) + zz;
+}
+
+__global__ __launch_bounds__(GEO_THREADS) void ligand_geometry_kernel(
+    const float* __restrict__ x_lig, const uint8_t* __restrict__ z_lig, const int32_t* __restrict__ lig_ptr, int n_lig,
+    const float* __restrict__ x_rec, const uint8_t* __restrict__ z_rec, const int32_t* __restrict__ rec_ptr, int n_rec,
+    int32_t* __restrict__ nr_bonds, uint8_t* __restrict__ flags, int32_t* __restrict__ graph_out) {
+    __shared__ float sx[GEO_MAX], sy[GEO_MAX], sz[GEO_MAX];
+    __shared__ uint8_t scode[GEO_MAX];
+    __shared__ int sflag[GEO_MAX];               // CBGX_GEOM_* bits of a ligand atom
+    __shared__ int snb[GEO_MAX];
+    __shared__ double sbond[GEO_EL * GEO_EL][3]; // bond length + margin of a pair, as the fp64 value p is compared with
+    __shared__ double sclash[GEO_EL][GEO_VDW];   // (r_lig + r_other) - tolerance
+    __shared__ int scount[4];                    // stable, inter-clash, intra-clash atoms; protein atoms without a radius
+    const int g = blockIdx.x, k = threadIdx.x;
+    // a malformed CSR must not reach outside the arrays: both ranges are clamped to them (and the ligand to the LDS it is staged in)
+    const int r0 = min(max(rec_ptr[g], 0), n_rec), r1 = min(max(rec_ptr[g + 1], r0), n_rec);
+    const int l0 = min(max(lig_ptr[g], 0), n_lig), l1 = min(max(lig_ptr[g + 1], l0), n_lig);
+    const int nr = r1 - r0, nl = min(l1 - l0, GEO_MAX);
+
+    for (int i = k; i < nl; i += GEO_THREADS) {
+        const size_t a = (size_t)(l0 + i);
+        sx[i] = x_lig[3 * a + 0]; sy[i] = x_lig[3 * a + 1]; sz[i] = x_lig[3 * a + 2];
+        const int code = geo_code(z_lig[a], GEO_EL);
+        scode[i] = (uint8_t)code;
+        sflag[i] = code == GEO_NONE ? (int)CBGX_GEOM_UNKNOWN_ELEMENT : 0;
+    }
+    for (int p = k; p < GEO_EL * GEO_EL; p += GEO_THREADS)
+        for (int o = 0; o < 3; ++o) sbond[p][o] = (double)(d_geo.bond_pm[o][p / GEO_EL][p % GEO_EL] + d_geo.margin[o]);
+    for (int p = k; p < GEO_EL * GEO_VDW; p += GEO_THREADS)
+        sclash[p / GEO_VDW][p % GEO_VDW] = (d_geo.radius[p / GEO_VDW] + d_geo.radius[p % GEO_VDW]) - d_geo.tolerance;
+    if (k < 4) scount[k] = 0;
+    __syncthreads();
+
+    // ---- ligand rows: bond orders and intra-ligand clashes ----------------------------------------------------------------------------
+    for (int i = k; i < nl; i += GEO_THREADS) {
+        const int ci = scode[i];
+        int nb = 0;
+        bool intra = false;
+        if (ci != GEO_NONE) {
+            const double xi = (double)sx[i], yi = (double)sy[i], zi = (double)sz[i];
+            for (int j = 0; j < nl; ++j) {
+                const int cj = scode[j];
+                if (j == i || cj == GEO_NONE) continue;
+                const double s = geo_dist2(xi, yi, zi, sx[j], sy[j], sz[j]);
+                if (s >= GEO_FAR2) continue;
+                const double d = __dsqrt_rn(s);
+                const double p = 100.0 * d;
+                const double* t = sbond[ci * GEO_EL + cj];
+                int order = 0;
+                if (p < t[0]) order = p < t[1] ? (p < t[2] ? 3 : 2) : 1;
+                nb += order;
+                intra = intra || (order == 0 && d < sclash[ci][cj]);
+            }
+        }
+        snb[i] = nb;
+        if (intra) atomicOr(&sflag[i], (int)CBGX_GEOM_INTRA_CLASH);
+    }
+    // ---- protein atoms against the ligand ---------------------------------------------------------------------------------------------
+    int no_radius = 0;
+    for (int q = k; q < nr; q += GEO_THREADS) {
+        const size_t a = (size_t)(r0 + q);
+        const int cr = geo_code(z_rec[a], GEO_VDW);
+        if (cr == GEO_NONE) { ++no_radius; continue; }
+        const double px = (double)x_rec[3 * a + 0], py = (double)x_rec[3 * a + 1], pz = (double)x_rec[3 * a + 2];
+        for (int j = 0; j < nl; ++j) {
+            const int cj = scode[j];
+            if (cj == GEO_NONE) continue;
+            // (d = |x_lig - x_rec|: the squares make the order of the subtraction irrelevant)
+            const double s = geo_dist2(px, py, pz, sx[j], sy[j], sz[j]);
+            if (s >= GEO_FAR2) continue;
+            if (__dsqrt_rn(s) < sclash[cj][cr]) atomicOr(&sflag[j], (int)CBGX_GEOM_INTER_CLASH);
+        }
+    }
+    if (no_radius) atomicAdd(&scount[3], no_radius);
+    __syncthreads();
+
+    // ---- flags, counts ----------------------------------------------------------------------------------------------------------------
+    int n_stable = 0, n_inter = 0, n_intra = 0;
+    for (int i = k; i < nl; i += GEO_THREADS) {
+        const int ci = scode[i], nb = snb[i];
+        int f = sflag[i];
+        if (ci != GEO_NONE && nb > 0 && nb <= d_geo.allowed[ci]) f |= (int)CBGX_GEOM_STABLE;
+        const size_t a = (size_t)(l0 + i);
+        nr_bonds[a] = nb;
+        flags[a] = (uint8_t)f;
+        n_stable += f & 1; n_inter += (f >> 1) & 1; n_intra += (f >> 2) & 1;
+    }
+    if (n_stable) atomicAdd(&scount[0], n_stable);
+    if (n_inter) atomicAdd(&scount[1], n_inter);
+    if (n_intra) atomicAdd(&scount[2], n_intra);
+    __syncthreads();
+    if (k == 0) {
+        int32_t* o = graph_out + (size_t)CBGX_GEOMETRY_GRAPH_COLS * g;
+        o[0] = nl; o[1] = scount[0]; o[2] = (scount[0] == nl && nl > 0) ? 1 : 0; o[3] = scount[1]; o[4] = scount[2]; o[5] = scount[3];
+    }
+}
+
+hipError_t launch_ligand_geometry(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, const float* x_rec,
+                                  const uint8_t* z_rec, const int32_t* rec_ptr, int n_rec, int n_graphs, int32_t* nr_bonds,
+                                  uint8_t* flags, int32_t* graph_out, hipStream_t s) {
+    if (n_graphs == 0) return hipSuccess;
+    hipLaunchKernelGGL(ligand_geometry_kernel, dim3(n_graphs), dim3(GEO_THREADS), 0, s, x_lig, z_lig, lig_ptr, n_lig, x_rec, z_rec,
+                       rec_ptr, n_rec, nr_bonds, flags, graph_out);
+    return hipGetLastError();
+}
+
+void ligand_geometry_tables(int32_t* bond_pm, int32_t* margins, int32_t* allowed, uint8_t* elements, uint8_t* vdw_z, double* vdw_r,
+                            double* tolerance) {
+    for (int o = 0; o < 3; ++o) {
+        if (margins) margins[o] = h_geo.margin[o];
+        for (int p = 0; bond_pm && p < GEO_EL * GEO_EL; ++p) bond_pm[o * GEO_EL * GEO_EL + p] = h_geo.bond_pm[o][p / GEO_EL][p % GEO_EL];
+    }
+    for (int c = 0; c < GEO_EL; ++c) {
+        if (allowed) allowed[c] = h_geo.allowed[c];
+        if (elements) elements[c] = h_geo.z[c];
+    }
+    for (int c = 0; c < GEO_VDW; ++c) {
+        if (vdw_z) vdw_z[c] = h_geo.z[c];
+        if (vdw_r) vdw_r[c] = h_geo.radius[c];
+    }
+    if (tolerance) *tolerance = h_geo.tolerance;
+}
+
+}  // namespace cbgx

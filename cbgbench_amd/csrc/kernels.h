@@ -229,6 +229,13 @@ hipError_t launch_diffsbdd_step(const float* x_den, const float* logits, const i
                                 const float* eps_x, const float* eps_c, const float* emb_w, const float* emb_b,
                                 const float* ind_w, const float* ind_b, float* x_next, float* c_next, float* x, float* h,
                                 float* shift_out, float* frame, hipStream_t s);
+// geometry.hip: stability and steric-clash report of a batch of ligands, one workgroup per graph (ligands of at most
+// CBGX_GEOMETRY_MAX_LIGAND atoms: the caller checks), and the host copies of its constant tables
+hipError_t launch_ligand_geometry(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, const float* x_rec,
+                                  const uint8_t* z_rec, const int32_t* rec_ptr, int n_rec, int n_graphs, int32_t* nr_bonds,
+                                  uint8_t* flags, int32_t* graph_out, hipStream_t s);
+void ligand_geometry_tables(int32_t* bond_pm, int32_t* margins, int32_t* allowed, uint8_t* elements, uint8_t* vdw_z, double* vdw_r,
+                            double* tolerance);
 constexpr int PACK_MAX = 64;
 struct PackPiece {
     const float* src; float* dst; int src_ld, src_off, transpose, dst_ld, rows, cols;

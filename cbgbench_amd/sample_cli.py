@@ -20,15 +20,18 @@ per pocket); synthetic pockets get synthetic fragments.  Every sample's frame is
 ``protein_translation`` records the shift (sample.py:198-201 adds it back: ``sampling.translate``, on in the shipped configs).
 Output: ``{out_root}/{tag}/pocket_{i:05d}.pt`` with the final ligand positions, atom types and
 (optionally) the trajectory for each sample -- the tensors ``sample.py:198-206`` hands to reconstruction.
+``--geometry`` adds a stability and steric-clash report per sample, computed on the device in one launch per batch
+(cbgbench_amd/geometry.py), and ``{out_dir}/geometry_summary.json`` for the job.
 A checkpoint is the reference's format: ``{'config': ..., 'model': state_dict}`` (``sample.py:153-156``)."""
 import argparse
+import json
 import os
 import time
 
 import numpy as np
 import torch
 
-from . import get_model, load_config, priors, set_num_atom_type, sharding, synthetic
+from . import geometry, get_model, load_config, priors, set_num_atom_type, sharding, synthetic
 from .config import NUM_ATOM_TYPES, get_atomic_number_from_index, is_aromatic_from_index, load_checkpoint_file
 
 
@@ -98,7 +101,8 @@ def decode_mode(plan_mode, config_mode, num_classes):
 
 def main(argv=None, stats=None):
     """``stats`` (optional dict): filled with the wall seconds of the phases (setup = config + model + weights, batch = prior
-    construction, sample = model.sample incl. the trajectory download, write = per-pocket records and files)."""
+    construction, sample = model.sample incl. the trajectory download, write = per-pocket records and files; with ``--geometry``
+    also geometry = the report's launches, a part of write)."""
     t_phase = time.perf_counter()
     phases = {"setup": 0.0, "batch": 0.0, "sample": 0.0, "write": 0.0}
 
@@ -141,6 +145,12 @@ def main(argv=None, stats=None):
                          "is the same however the job is split (cbgbench_amd/noise.py).  GPU only (the generator lives in the step "
                          "kernels: --device cpu raises).  Nothing seeds torch in this mode, so --random_init weights differ from process "
                          "to process: compare runs through a --checkpoint")
+    ap.add_argument("--geometry", action="store_true",
+                    help="add a geometry report to every sample (nr_bonds, atom_stable, inter_clash, intra_clash_table_bonds, mol_stable), "
+                         "a `geometry` dict of counts to every pocket record and {out_dir}/geometry_summary.json: atom / molecule "
+                         "stability and protein-ligand steric clash of the state the record holds, evaluated on the GPU in the "
+                         "sampling frame against the batch's own protein_pos, one launch per batch (cbgbench_amd/geometry.py).  "
+                         "Intra-ligand clashes exclude pairs with a TABLE bond (the reference uses RDKit's bonds)")
     ap.add_argument("--atom_num_dist", default=None,
                     help="the reference's size-conditioned ligand-size histogram (repo/datasets/transforms/_atom_num_dist.npy); "
                          "without it ligand sizes are U{10..45}")
@@ -157,6 +167,8 @@ def main(argv=None, stats=None):
         dev = torch.device("cuda", local)
     else:
         dev = torch.device(args.device)
+    if args.geometry and dev.type != "cuda":
+        raise SystemExit("sample_cli: --geometry runs on the GPU (cbgx_ligand_geometry has no CPU fallback)")
 
     ckpt_path = args.checkpoint or config.model.get("checkpoint", None)
     if ckpt_path and os.path.exists(ckpt_path):
@@ -209,10 +221,21 @@ def main(argv=None, stats=None):
     else:
         torch.manual_seed(args.seed + rank)             # independent noise streams per shard
         rng = np.random.default_rng([args.seed, rank])
+    geometry_seconds, job_counts = [0.0], []             # --geometry: wall time of the report, per-sample counts of this rank
+
     def write_results(ids, traj, batch):
         # sample.py:198-201 hands traj[0] to the reconstruction -- for targetdiff / diffbp that is the state entering the
         # last step, not traj[-1]; kept as the default for drop-in outputs, --final_state selects traj[-1]
         x, c, bidx = traj[-1] if (args.final_state and config.model.type != "diffsbdd") else traj[0]
+        geo = None
+        if args.geometry:
+            # the state the records hold, in the sampling frame (before ligand_translation), against the batch's own pocket
+            t_geo = time.perf_counter()
+            pocket = {k: batch[k].to(dev) for k in ("protein_pos", "protein_element", "protein_element_batch")}
+            pocket["num_graphs"] = len(ids) * num_samples
+            geo = geometry.batch_geometry(pocket, x.to(dev), c.to(dev), bidx.to(dev), mode)
+            geo = {k: v.cpu() for k, v in geo.items()}       # (the download waits for the launch)
+            geometry_seconds[0] += time.perf_counter() - t_geo
         x, c, bidx = x.cpu(), c.cpu(), bidx.cpu()
         if translate:       # back to the frame the pockets came in (sample.py:198-199; here per graph: a batch holds many pockets)
             x = x + batch["ligand_translation"].cpu()
@@ -221,8 +244,20 @@ def main(argv=None, stats=None):
             gen = batch["ligand_gen_flag"].cpu()
             for g, smp in enumerate(samples):
                 smp["gen_flag"] = gen[bidx == g].clone()
+        if geo is not None:
+            for g, smp in enumerate(samples):
+                m, f = bidx == g, geo["flags"]
+                smp["nr_bonds"] = geo["nr_bonds"][m].clone()
+                smp["atom_stable"] = (f[m] & geometry.STABLE) != 0
+                smp["inter_clash"] = (f[m] & geometry.INTER_CLASH) != 0
+                smp["intra_clash_table_bonds"] = (f[m] & geometry.INTRA_CLASH) != 0
+                smp["mol_stable"] = bool(geo["graph_counts"][g, 2])
         for k, pid in enumerate(ids):
             rec = {"pocket_index": pid, "samples": samples[k * num_samples:(k + 1) * num_samples]}
+            if geo is not None:
+                gc = geo["graph_counts"][k * num_samples:(k + 1) * num_samples].to(torch.int64)
+                job_counts.append(gc)
+                rec["geometry"] = geometry.summarise(gc)["counts"]
             if args.save_traj:
                 rec["traj_keys"] = sorted(traj.keys())
             torch.save(rec, os.path.join(out_dir, f"pocket_{pid:05d}.pt"))
@@ -257,6 +292,17 @@ def main(argv=None, stats=None):
     if stats is not None:
         stats.update(phases)
         stats.update(timing)
+        if args.geometry:
+            stats["geometry"] = geometry_seconds[0]
+    if args.geometry:
+        # integer counts of all ranks, summed: the job's numbers do not depend on how the pockets were sharded
+        totals = geometry.job_totals(torch.cat(job_counts) if job_counts else torch.zeros(0, len(geometry.GRAPH_COLUMNS)))
+        summary = geometry.summarise_totals(sharding.sum_counts(totals, device=dev))
+        if rank == 0:
+            with open(os.path.join(out_dir, "geometry_summary.json"), "w") as f:
+                json.dump(summary, f, indent=1, sort_keys=True)
+            print("geometry: " + ", ".join(f"{k} {summary[k]:.4f}" for k in geometry.RATIOS)
+                  + f" ({summary['counts']['n_mol']} molecules, {summary['counts']['n_atoms']} atoms)")
     if rank == 0:
         print(f"sampled {len(pockets)} pockets x {num_samples} samples on {world} rank(s): "
               f"{gs / el:.1f} graph-steps/s, results in {out_dir}")

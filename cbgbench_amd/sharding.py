@@ -75,3 +75,14 @@ def gather_values(value, device="cpu"):
     out = [torch.zeros_like(mine) for _ in range(dist.get_world_size())]
     dist.all_gather(out, mine)
     return [float(t.item()) for t in out]
+
+
+def sum_counts(counts, device="cpu"):
+    """element-wise sum over ranks of a list of integers (one all_reduce of int64): job totals that do not depend on the sharding"""
+    if not (dist.is_available() and dist.is_initialized()):
+        return [int(c) for c in counts]
+    if dist.get_backend() == "gloo":
+        device = "cpu"
+    t = torch.tensor([int(c) for c in counts], dtype=torch.int64, device=device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return [int(c) for c in t.tolist()]

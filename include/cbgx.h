@@ -617,6 +617,47 @@ int cbgx_embed_compose(const float *x_protein, const float *x_ligand, const floa
 int cbgx_embed_compose_backward(const float *grad_h, const float *ext, int n_nodes, int feat_dim, int num_aa, int lig_dim,
                                 float *partial, int groups, float *grad_out, void *stream);
 
+/* ---- geometry report of sampled ligands: stability and steric clash (geometry.hip) ---------------------------------------------------
+ * For a whole batch in ONE launch, one 256-thread workgroup per graph: the two coordinate-and-element metrics of the reference's
+ *   quality path -- atom / molecule stability (repo/tools/geometry/eval_stability.py, check_stability with hs=False) and steric clash
+ *   (repo/tools/geometry/eval_steric_clash.py, detect_clash) -- without RDKit.
+ *   x_lig [n_lig,3] fp32, z_lig [n_lig] uint8 atomic numbers, lig_ptr [B+1] int32; x_rec [n_rec,3], z_rec [n_rec], rec_ptr [B+1]
+ *   likewise; both arrays sorted by graph.  CSR entries outside [0, n] are clamped.  A ligand has at most CBGX_GEOMETRY_MAX_LIGAND
+ *   atoms (they are staged in LDS); the number of protein atoms is not limited.
+ *   Distance of two atoms: the fp32 coordinates widened to fp64, dx = xi - xj (dy, dz likewise), s = (dx dx + dy dy) + dz dz with every
+ *   product and sum rounded on its own (no contraction), d = sqrt(s) correctly rounded.
+ *   Bond order of a ligand pair i != j over the elements {H, C, N, O, F, P, S, Cl}, p = 100.0 d (pm), b1 / b2 / b3 the single / double /
+ *   triple bond lengths of the pair in pm (-1: none):  p < b1 + 10 ?  (p < b2 + 5 ? (p < b3 + 3 ? 3 : 2) : 1)  : 0, comparisons strict.
+ *   nr_bonds[i] = sum over j of order(i, j); atom i is stable iff allowed[z_i] >= nr_bonds[i] > 0 (a one-atom ligand is unstable).
+ *   Clash of a pair: d < (r_lig + r_other) - 0.4 in fp64, in that order, r the van der Waals radius of the element (H C N O F P S Cl Br).
+ *   Inter-clash: ligand atom x protein atom of the same graph, all pairs.  Intra-clash: ligand pairs i != j whose TABLE bond order is 0
+ *   -- the reference masks with RDKit's bond adjacency instead; the table bond is this library's RDKit-free stand-in.
+ *   A protein atom whose element has no radius takes no part and is counted.  A ligand atom outside the 8 elements has nr_bonds = 0, is
+ *   unstable, takes no part in bonds or clashes (of other atoms either) and carries CBGX_GEOM_UNKNOWN_ELEMENT.
+ *   Outputs, every element of every graph written (graphs without ligand or protein atoms too): nr_bonds [n_lig] int32; flags [n_lig]
+ *   uint8 (bits below); graph_out [B, CBGX_GEOMETRY_GRAPH_COLS] int32: n_atoms, n_stable, mol_stable (n_stable == n_atoms && n_atoms > 0),
+ *   n_inter_clash_atoms, n_intra_clash_atoms, n_protein_atoms_without_radius.  Integer results, no atomics on memory, no dependence on
+ *   the order of anything: a graph's rows are a function of its own atoms.
+ *   The pointers are device pointers.  The entry itself reads lig_ptr to find the largest ligand -- through a copy on `stream` and a
+ *   wait for it when lig_ptr is device memory -- before the launch.
+ *   Returns 0, and 0 without a launch when B == 0.  CBGX_E_INVALID, before anything is launched: a NULL pointer with a non-zero count,
+ *   negative counts, a ligand above CBGX_GEOMETRY_MAX_LIGAND atoms (lig_ptr in plain host memory is read in place for this check, so that
+ *   it needs no device; such a call is then refused as well: the kernel could not read it). */
+#define CBGX_GEOMETRY_MAX_LIGAND 1024
+#define CBGX_GEOMETRY_GRAPH_COLS 6
+#define CBGX_GEOM_STABLE 1u          /* flags bit 0 */
+#define CBGX_GEOM_INTER_CLASH 2u     /* bit 1: closer than the clash threshold to a protein atom */
+#define CBGX_GEOM_INTRA_CLASH 4u     /* bit 2: closer than the clash threshold to a ligand atom it has no table bond with */
+#define CBGX_GEOM_UNKNOWN_ELEMENT 8u /* bit 3: not one of H C N O F P S Cl */
+int cbgx_ligand_geometry(const float *x_lig, const uint8_t *z_lig, const int32_t *lig_ptr, int n_lig, const float *x_rec,
+                         const uint8_t *z_rec, const int32_t *rec_ptr, int n_rec, int n_graphs, int32_t *nr_bonds, uint8_t *flags,
+                         int32_t *graph_out, void *stream);
+/* The constants the kernel was built with (host only, no device): bond_pm [3][8][8] (order - 1, element code, element code), margins [3]
+ *   (pm), allowed [8] valences, elements [8] the atomic number of each element code, vdw_z [9] / vdw_r [9] the atomic numbers that have a
+ *   radius and the radii (Angstrom), tolerance (Angstrom).  A NULL argument is skipped.  Returns 0. */
+int cbgx_ligand_geometry_tables(int32_t *bond_pm, int32_t *margins, int32_t *allowed, uint8_t *elements, uint8_t *vdw_z, double *vdw_r,
+                                double *tolerance);
+
 /* ---- measurement hook (bench.py) ----------------------------------------------------------------
  * Between cbgx_profile_begin() and cbgx_profile_end() every kernel launch is bracketed by HIP events on
  * its own stream.  cbgx_profile_end() synchronises them and returns, per kernel class, the summed
