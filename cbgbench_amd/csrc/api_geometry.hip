@@ -1,4 +1,5 @@
-// libcbgx -- C ABI of the geometry report (include/cbgx.h, geometry.hip): argument checks, the ligand-size check, the launch
+// libcbgx -- C ABI of the geometry report and of the bond list (include/cbgx.h, geometry.hip): argument checks, the ligand-size check,
+// the launch
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,7 +15,7 @@ using namespace cbgx;
 // lig_ptr [count] on the host.  Device (or managed) memory: a copy on the caller's stream and a wait for it.  Pinned host memory: read in
 // place.  Anything the runtime does not know -- plain host memory, or no device at all -- is read in place too and reported as not
 // visible to the device, so that the size check works without one and nothing is launched on such a pointer.
-static int fetch_csr(const int32_t* p, int count, std::vector<int32_t>& host, bool& device_visible, hipStream_t s) {
+static int fetch_csr(const char* who, const int32_t* p, int count, std::vector<int32_t>& host, bool& device_visible, hipStream_t s) {
     host.resize((size_t)count);
     hipPointerAttribute_t attr;
     const hipError_t e = hipPointerGetAttributes(&attr, p);
@@ -22,12 +23,29 @@ static int fetch_csr(const int32_t* p, int count, std::vector<int32_t>& host, bo
         device_visible = true;
         hipError_t c = hipMemcpyAsync(host.data(), p, sizeof(int32_t) * (size_t)count, hipMemcpyDeviceToHost, s);
         if (c == hipSuccess) c = hipStreamSynchronize(s);
-        if (c != hipSuccess) return set_error(CBGX_E_HIP, "ligand_geometry: reading lig_ptr: %s", hipGetErrorString(c));
+        if (c != hipSuccess) return set_error(CBGX_E_HIP, "%s: reading lig_ptr: %s", who, hipGetErrorString(c));
         return CBGX_OK;
     }
     device_visible = e == hipSuccess && attr.type == hipMemoryTypeHost;
     if (e != hipSuccess) (void)hipGetLastError();      // not an error of this call: the pointer is simply not the runtime's
     memcpy(host.data(), p, sizeof(int32_t) * (size_t)count);
+    return CBGX_OK;
+}
+
+// what every entry does between its argument checks and its launch: the read-back of lig_ptr, the size check over the ranges the kernels
+// use (clamped to the array), and the refusal of a lig_ptr no kernel could read
+static int check_ligand_sizes(const char* who, const int32_t* lig_ptr, int n_lig, int n_graphs, hipStream_t s) {
+    std::vector<int32_t> ptr;
+    bool device_visible = false;
+    const int rc = fetch_csr(who, lig_ptr, n_graphs + 1, ptr, device_visible, s);
+    if (rc != CBGX_OK) return rc;
+    for (int g = 0; g < n_graphs; ++g) {
+        const int l0 = std::min(std::max(ptr[g], 0), n_lig), l1 = std::min(std::max(ptr[g + 1], l0), n_lig);
+        if (l1 - l0 > CBGX_GEOMETRY_MAX_LIGAND)
+            return set_error(CBGX_E_INVALID, "%s: graph %d has %d ligand atoms, more than the %d one workgroup stages", who, g, l1 - l0,
+                             CBGX_GEOMETRY_MAX_LIGAND);
+    }
+    if (!device_visible) return set_error(CBGX_E_INVALID, "%s: lig_ptr is not memory the device can read", who);
     return CBGX_OK;
 }
 
@@ -42,21 +60,41 @@ int cbgx_ligand_geometry(const float* x_lig, const uint8_t* z_lig, const int32_t
         (n_rec > 0 && (!x_rec || !z_rec)))
         return set_error(CBGX_E_INVALID, "ligand_geometry: NULL pointer");
     if (n_graphs == 0) return CBGX_OK;
-    std::vector<int32_t> ptr;
-    bool device_visible = false;
-    const int rc = fetch_csr(lig_ptr, n_graphs + 1, ptr, device_visible, (hipStream_t)stream);
+    const int rc = check_ligand_sizes("ligand_geometry", lig_ptr, n_lig, n_graphs, (hipStream_t)stream);
     if (rc != CBGX_OK) return rc;
-    for (int g = 0; g < n_graphs; ++g) {       // the ranges the kernel uses: clamped to the array
-        const int l0 = std::min(std::max(ptr[g], 0), n_lig), l1 = std::min(std::max(ptr[g + 1], l0), n_lig);
-        if (l1 - l0 > CBGX_GEOMETRY_MAX_LIGAND)
-            return set_error(CBGX_E_INVALID, "ligand_geometry: graph %d has %d ligand atoms, more than the %d one workgroup stages", g,
-                             l1 - l0, CBGX_GEOMETRY_MAX_LIGAND);
-    }
-    if (!device_visible)
-        return set_error(CBGX_E_INVALID, "ligand_geometry: lig_ptr is not memory the device can read");
     const hipError_t e = launch_ligand_geometry(x_lig, z_lig, lig_ptr, n_lig, x_rec, z_rec, rec_ptr, n_rec, n_graphs, nr_bonds, flags,
                                                 graph_out, (hipStream_t)stream);
     if (e != hipSuccess) return set_error(CBGX_E_HIP, "ligand_geometry: launch: %s", hipGetErrorString(e));
+    return CBGX_OK;
+}
+
+int cbgx_ligand_bonds_count(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs, int32_t* deg_up,
+                            int32_t* fragment, int32_t* graph_out, void* stream) {
+    if (n_graphs < 0 || n_lig < 0) return set_error(CBGX_E_INVALID, "ligand_bonds_count: negative count (B=%d n_lig=%d)", n_graphs, n_lig);
+    if ((n_graphs > 0 && (!lig_ptr || !graph_out)) || (n_lig > 0 && (!x_lig || !z_lig || !deg_up || !fragment)))
+        return set_error(CBGX_E_INVALID, "ligand_bonds_count: NULL pointer");
+    if (n_graphs == 0) return CBGX_OK;
+    const int rc = check_ligand_sizes("ligand_bonds_count", lig_ptr, n_lig, n_graphs, (hipStream_t)stream);
+    if (rc != CBGX_OK) return rc;
+    const hipError_t e = launch_ligand_bonds_count(x_lig, z_lig, lig_ptr, n_lig, n_graphs, deg_up, fragment, graph_out, (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(CBGX_E_HIP, "ligand_bonds_count: launch: %s", hipGetErrorString(e));
+    return CBGX_OK;
+}
+
+int cbgx_ligand_bonds_fill(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,
+                           const int32_t* bond_ptr, int n_bonds, int32_t* bond_index, uint8_t* bond_order, double* bond_length,
+                           void* stream) {
+    if (n_graphs < 0 || n_lig < 0 || n_bonds < 0)
+        return set_error(CBGX_E_INVALID, "ligand_bonds_fill: negative count (B=%d n_lig=%d n_bonds=%d)", n_graphs, n_lig, n_bonds);
+    if ((n_graphs > 0 && (!lig_ptr || !bond_ptr)) || (n_lig > 0 && (!x_lig || !z_lig)) ||
+        (n_bonds > 0 && (!bond_index || !bond_order || !bond_length)))
+        return set_error(CBGX_E_INVALID, "ligand_bonds_fill: NULL pointer");
+    if (n_graphs == 0 || n_bonds == 0) return CBGX_OK;
+    const int rc = check_ligand_sizes("ligand_bonds_fill", lig_ptr, n_lig, n_graphs, (hipStream_t)stream);
+    if (rc != CBGX_OK) return rc;
+    const hipError_t e = launch_ligand_bonds_fill(x_lig, z_lig, lig_ptr, n_lig, n_graphs, bond_ptr, n_bonds, bond_index, bond_order,
+                                                  bond_length, (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(CBGX_E_HIP, "ligand_bonds_fill: launch: %s", hipGetErrorString(e));
     return CBGX_OK;
 }
 

@@ -212,6 +212,199 @@ hipError_t launch_ligand_geometry(const float* x_lig, const uint8_t* z_lig, cons
     return hipGetLastError();
 }
 
+// ---- bond list, fragments and connectivity (cbgx_ligand_bonds_count / cbgx_ligand_bonds_fill) -------------------------------------------
+// The molecular graph the row walk above sums over and throws away, kept: the pairs i < j of a ligand whose table bond order is > 0, in
+// (i, j) order, and the connected components of that graph.  Same staging, same distance, same order, same tables as the kernel above;
+// proteins play no part.  The number of bonds of a graph is not bounded by its number of atoms (all atoms at one point: n (n - 1) / 2), so
+// the list is made in two launches: `count` writes every atom's number of partners j > i, the caller turns them into an exclusive prefix
+// sum, `fill` walks the same pairs again and writes atom a's partners in ascending j from bond_ptr[a] on -- no atomics, one order.
+//   components  label[i] = the smallest ligand-local index of i's component, by min-label propagation with root hooking and pointer
+//               jumping over rounds that recompute the distances (no adjacency is stored: 128 KiB of LDS for a bit matrix would leave one
+//               workgroup per CU).  Labels live in LDS, start at label[i] = i and only ever decrease, to labels of atoms of the same
+//               component; so label[i] <= i and label[i] >= min(component) throughout.
+//                 hook   atom i reads m = min(label[i], label[j] over its bonded j); if m < label[i]: integer atomicMin of label[i] and of
+//                        label[old label[i]] with m, and the round is marked as changed.
+//                 jump   label[i] = the root reached by following labels (l = label[l] while label[l] < l: strictly decreasing, ends).
+//               A round without a change read a snapshot nobody wrote to, in which no atom has a bonded partner with a smaller label:
+//               labels are constant over a component, and since the component's smallest atom m has label[m] <= m inside the component,
+//               that constant is m.  That fixed point is unique, so the result does not depend on the order in which threads saw each
+//               other's updates.  Plain propagation alone gives an atom at graph distance r from m the label m after r rounds, so n - 1
+//               rounds always suffice and the loop is bounded by n; hooking and jumping make it a handful in practice.
+//   counts      n_bonds, the sum of orders (integer LDS atomics), the number of roots, the largest component (integer LDS histogram over
+//               the roots), n_cycles = n_bonds - n_atoms + n_fragments (the cycle rank of the graph).
+
+struct GeoLigand {       // a graph's ligand in LDS
+    float x[GEO_MAX], y[GEO_MAX], z[GEO_MAX];
+    uint8_t code[GEO_MAX];
+    double bond[GEO_EL * GEO_EL][3];      // bond length + margin of a pair of codes, as the fp64 value p is compared with
+};
+
+// stages graph g's ligand; returns its number of atoms and its first row (the range clamped to the array and to the LDS, as above)
+__device__ __forceinline__ int geo_stage_ligand(GeoLigand& L, const float* __restrict__ x_lig, const uint8_t* __restrict__ z_lig,
+                                                const int32_t* __restrict__ lig_ptr, int n_lig, int g, int k, int& l0) {
+    l0 = min(max(lig_ptr[g], 0), n_lig);
+    const int l1 = min(max(lig_ptr[g + 1], l0), n_lig);
+    const int nl = min(l1 - l0, GEO_MAX);
+    for (int i = k; i < nl; i += GEO_THREADS) {
+        const size_t a = (size_t)(l0 + i);
+        L.x[i] = x_lig[3 * a + 0]; L.y[i] = x_lig[3 * a + 1]; L.z[i] = x_lig[3 * a + 2];
+        L.code[i] = (uint8_t)geo_code(z_lig[a], GEO_EL);
+    }
+    for (int p = k; p < GEO_EL * GEO_EL; p += GEO_THREADS)
+        for (int o = 0; o < 3; ++o) L.bond[p][o] = (double)(d_geo.bond_pm[o][p / GEO_EL][p % GEO_EL] + d_geo.margin[o]);
+    return nl;
+}
+
+// table bond order of the staged atoms i != j, both with a code (0: none); d: the distance the order was decided on (set when s < 25)
+__device__ __forceinline__ int geo_pair_order(const GeoLigand& L, double xi, double yi, double zi, int ci, int j, int cj, double& d) {
+    const double s = geo_dist2(xi, yi, zi, L.x[j], L.y[j], L.z[j]);
+    if (s >= GEO_FAR2) return 0;
+    d = __dsqrt_rn(s);
+    const double p = 100.0 * d;
+    const double* t = L.bond[ci * GEO_EL + cj];
+    return p < t[0] ? (p < t[1] ? (p < t[2] ? 3 : 2) : 1) : 0;
+}
+
+__device__ __forceinline__ int lds_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+
+__global__ __launch_bounds__(GEO_THREADS) void ligand_bonds_count_kernel(
+    const float* __restrict__ x_lig, const uint8_t* __restrict__ z_lig, const int32_t* __restrict__ lig_ptr, int n_lig,
+    int32_t* __restrict__ deg_up, int32_t* __restrict__ fragment, int32_t* __restrict__ graph_out) {
+    __shared__ GeoLigand L;
+    __shared__ int slabel[GEO_MAX];
+    __shared__ int ssize[GEO_MAX];      // atoms of the component whose root this is
+    __shared__ int scount[4];           // bonds, sum of orders, roots, largest component
+    __shared__ int schanged;
+    const int g = blockIdx.x, k = threadIdx.x;
+    int l0;
+    const int nl = geo_stage_ligand(L, x_lig, z_lig, lig_ptr, n_lig, g, k, l0);
+    for (int i = k; i < nl; i += GEO_THREADS) { slabel[i] = i; ssize[i] = 0; }
+    if (k < 4) scount[k] = 0;
+    __syncthreads();
+
+    // ---- partners j > i of every atom ----------------------------------------------------------------------------------------------
+    int n_bonds = 0, order_sum = 0;
+    for (int i = k; i < nl; i += GEO_THREADS) {
+        const int ci = L.code[i];
+        int deg = 0;
+        if (ci != GEO_NONE) {
+            const double xi = (double)L.x[i], yi = (double)L.y[i], zi = (double)L.z[i];
+            for (int j = i + 1; j < nl; ++j) {
+                const int cj = L.code[j];
+                if (cj == GEO_NONE) continue;
+                double d;
+                const int order = geo_pair_order(L, xi, yi, zi, ci, j, cj, d);
+                deg += order > 0;
+                order_sum += order;
+            }
+        }
+        deg_up[(size_t)(l0 + i)] = deg;
+        n_bonds += deg;
+    }
+    if (n_bonds) { atomicAdd(&scount[0], n_bonds); atomicAdd(&scount[1], order_sum); }
+    __syncthreads();
+
+    // ---- components: rounds of hook + jump until a round changes nothing; at most nl rounds (see above) --------------------------------
+    const bool any_bond = scount[0] > 0;                 // (uniform: read after the barrier, written before it)
+    for (int round = 0; any_bond && round < nl; ++round) {
+        if (k == 0) schanged = 0;
+        __syncthreads();
+        for (int i = k; i < nl; i += GEO_THREADS) {
+            const int ci = L.code[i];
+            if (ci == GEO_NONE) continue;
+            const double xi = (double)L.x[i], yi = (double)L.y[i], zi = (double)L.z[i];
+            const int li = lds_load(&slabel[i]);
+            int m = li;
+            for (int j = 0; j < nl; ++j) {
+                const int cj = L.code[j];
+                if (j == i || cj == GEO_NONE) continue;
+                double d;
+                if (geo_pair_order(L, xi, yi, zi, ci, j, cj, d) > 0) m = min(m, lds_load(&slabel[j]));
+            }
+            if (m < li) {
+                atomicMin(&slabel[i], m);
+                atomicMin(&slabel[li], m);
+                schanged = 1;
+            }
+        }
+        __syncthreads();
+        if (!schanged) break;                            // (uniform; thread 0 resets it only after the barrier below)
+        for (int i = k; i < nl; i += GEO_THREADS) {
+            int l = lds_load(&slabel[i]);
+            for (int next = lds_load(&slabel[l]); next < l; next = lds_load(&slabel[l])) l = next;
+            slabel[i] = l;                               // (only this thread writes label[i] in this phase; roots stay roots)
+        }
+        __syncthreads();
+    }
+
+    // ---- labels, counts ----------------------------------------------------------------------------------------------------------------
+    int n_roots = 0;
+    for (int i = k; i < nl; i += GEO_THREADS) {
+        const int l = slabel[i];
+        fragment[(size_t)(l0 + i)] = l;
+        n_roots += l == i;
+        atomicAdd(&ssize[l], 1);
+    }
+    if (n_roots) atomicAdd(&scount[2], n_roots);
+    __syncthreads();
+    int largest = 0;
+    for (int i = k; i < nl; i += GEO_THREADS) largest = max(largest, ssize[i]);
+    if (largest) atomicMax(&scount[3], largest);
+    __syncthreads();
+    if (k == 0) {
+        int32_t* o = graph_out + (size_t)CBGX_BONDS_GRAPH_COLS * g;
+        o[0] = nl; o[1] = scount[0]; o[2] = scount[1]; o[3] = scount[2]; o[4] = scount[3]; o[5] = scount[0] - nl + scount[2];
+    }
+}
+
+__global__ __launch_bounds__(GEO_THREADS) void ligand_bonds_fill_kernel(
+    const float* __restrict__ x_lig, const uint8_t* __restrict__ z_lig, const int32_t* __restrict__ lig_ptr, int n_lig,
+    const int32_t* __restrict__ bond_ptr, int n_bonds, int32_t* __restrict__ bond_index, uint8_t* __restrict__ bond_order,
+    double* __restrict__ bond_length) {
+    __shared__ GeoLigand L;
+    const int g = blockIdx.x, k = threadIdx.x;
+    int l0;
+    const int nl = geo_stage_ligand(L, x_lig, z_lig, lig_ptr, n_lig, g, k, l0);
+    __syncthreads();
+    for (int i = k; i < nl; i += GEO_THREADS) {
+        const int ci = L.code[i];
+        if (ci == GEO_NONE) continue;
+        // the atom's slots, clamped to the lists: a wrong bond_ptr loses bonds, it does not reach outside the buffers
+        const int b0 = min(max(bond_ptr[l0 + i], 0), n_bonds), b1 = min(max(bond_ptr[l0 + i + 1], b0), n_bonds);
+        int b = b0;
+        const double xi = (double)L.x[i], yi = (double)L.y[i], zi = (double)L.z[i];
+        for (int j = i + 1; j < nl && b < b1; ++j) {
+            const int cj = L.code[j];
+            if (cj == GEO_NONE) continue;
+            double d;
+            const int order = geo_pair_order(L, xi, yi, zi, ci, j, cj, d);
+            if (order == 0) continue;
+            bond_index[b] = l0 + i;
+            bond_index[(size_t)n_bonds + b] = l0 + j;
+            bond_order[b] = (uint8_t)order;
+            bond_length[b] = d;
+            ++b;
+        }
+    }
+}
+
+hipError_t launch_ligand_bonds_count(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,
+                                     int32_t* deg_up, int32_t* fragment, int32_t* graph_out, hipStream_t s) {
+    if (n_graphs == 0) return hipSuccess;
+    hipLaunchKernelGGL(ligand_bonds_count_kernel, dim3(n_graphs), dim3(GEO_THREADS), 0, s, x_lig, z_lig, lig_ptr, n_lig, deg_up, fragment,
+                       graph_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_ligand_bonds_fill(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,
+                                    const int32_t* bond_ptr, int n_bonds, int32_t* bond_index, uint8_t* bond_order, double* bond_length,
+                                    hipStream_t s) {
+    if (n_graphs == 0 || n_bonds == 0) return hipSuccess;
+    hipLaunchKernelGGL(ligand_bonds_fill_kernel, dim3(n_graphs), dim3(GEO_THREADS), 0, s, x_lig, z_lig, lig_ptr, n_lig, bond_ptr, n_bonds,
+                       bond_index, bond_order, bond_length);
+    return hipGetLastError();
+}
+
 void ligand_geometry_tables(int32_t* bond_pm, int32_t* margins, int32_t* allowed, uint8_t* elements, uint8_t* vdw_z, double* vdw_r,
                             double* tolerance) {
     for (int o = 0; o < 3; ++o) {

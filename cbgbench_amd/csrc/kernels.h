@@ -236,6 +236,13 @@ hipError_t launch_ligand_geometry(const float* x_lig, const uint8_t* z_lig, cons
                                   uint8_t* flags, int32_t* graph_out, hipStream_t s);
 void ligand_geometry_tables(int32_t* bond_pm, int32_t* margins, int32_t* allowed, uint8_t* elements, uint8_t* vdw_z, double* vdw_r,
                             double* tolerance);
+// geometry.hip: the table-bond graph of the same ligands in two launches -- partners j > i per atom, component labels and per-graph counts;
+// then, given the exclusive prefix sum of the partner counts, the bond list in (i, j) order
+hipError_t launch_ligand_bonds_count(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,
+                                     int32_t* deg_up, int32_t* fragment, int32_t* graph_out, hipStream_t s);
+hipError_t launch_ligand_bonds_fill(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,
+                                    const int32_t* bond_ptr, int n_bonds, int32_t* bond_index, uint8_t* bond_order, double* bond_length,
+                                    hipStream_t s);
 constexpr int PACK_MAX = 64;
 struct PackPiece {
     const float* src; float* dst; int src_ld, src_off, transpose, dst_ld, rows, cols;

@@ -11,7 +11,13 @@ Two stated deviations from the reference:
     (``n_protein_atoms_without_radius``); the reference raises ``KeyError``.
 
 The constants (bond lengths, margins, valences, radii, tolerance) live in the kernel's translation unit; ``tables()`` reads them from the
-library."""
+library.
+
+``ligand_bonds`` / ``batch_bonds`` / ``summarise_bonds`` keep what the stability metric throws away: the TABLE-bond graph itself -- the bond
+list in (i, j) order with orders and float64 lengths, the connected components (``fragment``) and six integer facts per molecule
+(BOND_GRAPH_COLUMNS) -- in two launches with a prefix sum between (``cbgx_ligand_bonds_count`` / ``cbgx_ligand_bonds_fill``).  These are
+table bonds, not RDKit's: no aromaticity, no valence repair.  A molecule is ``connected`` iff it has one fragment: the table-bond
+counterpart of the reference's ``'.' not in smiles`` (repo/tools/rdkit_utils.py:597-640)."""
 import ctypes
 
 import numpy as np
@@ -25,6 +31,8 @@ MAX_LIGAND_ATOMS = 1024       # include/cbgx.h CBGX_GEOMETRY_MAX_LIGAND
 STABLE, INTER_CLASH, INTRA_CLASH, UNKNOWN_ELEMENT = 1, 2, 4, 8
 # columns of graph_counts (include/cbgx.h)
 GRAPH_COLUMNS = ("n_atoms", "n_stable", "mol_stable", "n_inter_clash_atoms", "n_intra_clash_atoms", "n_protein_atoms_without_radius")
+# columns of ligand_bonds' graph_counts (include/cbgx.h CBGX_BONDS_GRAPH_COLS)
+BOND_GRAPH_COLUMNS = ("n_atoms", "n_bonds", "bond_order_sum", "n_fragments", "largest_fragment", "n_cycles")
 
 
 def tables():
@@ -133,3 +141,92 @@ def summarise(graph_counts):
     sum(n_intra_clash_atoms) / sum(n_atoms) (intra-ligand pairs without a TABLE bond), clash_mol_ratio = share of molecules with at least
     one inter-clash atom."""
     return summarise_totals(job_totals(graph_counts))
+
+
+# ---- the table-bond graph: bond list, fragments, connectivity ------------------------------------------------------------------------
+def ligand_bonds(x_lig, z_lig, lig_batch, n_graphs):
+    """The table bonds of ``n_graphs`` ligands and what follows from them, on the tensors' current stream: two launches
+    (``cbgx_ligand_bonds_count``, ``cbgx_ligand_bonds_fill``) with a ``torch.cumsum`` between, whose last element is read on the host to
+    size the list.
+
+    Arguments as ``ligand_geometry``'s ligand side.  Returns device tensors: ``bond_index`` [2, n_bonds] int32 global ligand rows with
+    i < j, in strict (i, j) order; ``bond_order`` [n_bonds] uint8 in 1..3; ``bond_length`` [n_bonds] float64, the distance the order was
+    decided on, in Angstrom; ``bond_graph`` [n_bonds] int64, the graph of every bond; ``fragment`` [n_lig] int32, the smallest
+    ligand-LOCAL index of the atom's connected component; ``graph_counts`` [n_graphs, 6] int32 (BOND_GRAPH_COLUMNS).  A ligand of more
+    than MAX_LIGAND_ATOMS atoms raises ValueError.  There is no CPU path."""
+    dev = x_lig.device
+    if dev.type != "cuda":
+        raise _native.NativeError("ligand_bonds runs on the GPU (cbgx_ligand_bonds_count / _fill): there is no CPU fallback")
+    n_graphs = int(n_graphs)
+    for name, t in (("z_lig", z_lig), ("lig_batch", lig_batch)):
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, x_lig on {dev}")
+    n_lig = int(x_lig.shape[0])
+    if tuple(x_lig.shape) != (n_lig, 3):
+        raise ValueError("coordinates must be [n, 3]")
+    if z_lig.shape != (n_lig,) or lig_batch.shape != (n_lig,):
+        raise ValueError("one atomic number and one graph index per atom")
+    lig_ptr = _csr(lig_batch, n_graphs, "lig_batch")
+    x_lig = x_lig.to(torch.float32).contiguous()
+    z_lig = torch.where((z_lig >= 0) & (z_lig <= 255), z_lig, torch.zeros_like(z_lig)).to(torch.uint8).contiguous()
+    deg_up = torch.empty(n_lig, dtype=torch.int32, device=dev)
+    fragment = torch.empty(n_lig, dtype=torch.int32, device=dev)
+    graph_counts = torch.empty(n_graphs, len(BOND_GRAPH_COLUMNS), dtype=torch.int32, device=dev)
+    p, lib, stream = _native.ptr, _native.lib(), _native.current_stream(dev)
+    _native.check(lib.cbgx_ligand_bonds_count(p(x_lig), p(z_lig), p(lig_ptr), n_lig, n_graphs, p(deg_up), p(fragment), p(graph_counts),
+                                              stream), "cbgx_ligand_bonds_count")
+    ends = deg_up.cumsum(0, dtype=torch.int64)
+    n_bonds = int(ends[-1]) if n_lig else 0
+    if n_bonds > 2 ** 31 - 1:
+        raise ValueError(f"{n_bonds} bonds in one batch: more than an int32 bond_ptr addresses")
+    bond_ptr = torch.cat([ends.new_zeros(1), ends]).to(torch.int32).contiguous()
+    bond_index = torch.empty(2, n_bonds, dtype=torch.int32, device=dev)
+    bond_order = torch.empty(n_bonds, dtype=torch.uint8, device=dev)
+    bond_length = torch.empty(n_bonds, dtype=torch.float64, device=dev)
+    _native.check(lib.cbgx_ligand_bonds_fill(p(x_lig), p(z_lig), p(lig_ptr), n_lig, n_graphs, p(bond_ptr), n_bonds, p(bond_index),
+                                             p(bond_order), p(bond_length), stream), "cbgx_ligand_bonds_fill")
+    bond_graph = lig_batch.to(torch.long)[bond_index[0].to(torch.long)]
+    return {"bond_index": bond_index, "bond_order": bond_order, "bond_length": bond_length, "bond_graph": bond_graph,
+            "fragment": fragment, "graph_counts": graph_counts}
+
+
+def batch_bonds(batch, x, c, lig_batch, mode):
+    """``ligand_bonds`` of a sampling state (``x`` [n_lig, 3], ``c`` type indices [n_lig] or scores [n_lig, C]: argmax, ``lig_batch``);
+    ``batch`` gives ``num_graphs`` when it has it.  ``mode``: the atom-type vocabulary that maps a type index to its atomic number."""
+    if mode not in _ATOMIC_NUMBER:
+        raise ValueError(mode)
+    typ = c.argmax(-1) if c.dim() == 2 else c
+    z = torch.tensor(_ATOMIC_NUMBER[mode], dtype=torch.long, device=x.device)[typ.to(torch.long)]
+    n_graphs = int(batch["num_graphs"]) if "num_graphs" in batch else (int(lig_batch.max()) + 1 if lig_batch.numel() else 0)
+    return ligand_bonds(x, z, lig_batch, n_graphs)
+
+
+BOND_COUNT_KEYS = ("n_mol", "n_atoms", "n_bonds", "n_connected_mol", "n_largest_fragment_atoms", "n_fragments", "n_cycles")
+BOND_RATIOS = ("connected_mol_ratio", "largest_fragment_atom_ratio", "fragments_per_mol", "cycles_per_mol", "bonds_per_atom")
+
+
+def bond_totals(graph_counts):
+    """per-molecule counts ``graph_counts`` [n_mol, 6] (BOND_GRAPH_COLUMNS; any array-like) -> the integer totals, in BOND_COUNT_KEYS
+    order; a molecule is connected iff n_fragments == 1"""
+    if isinstance(graph_counts, torch.Tensor):
+        graph_counts = graph_counts.cpu().numpy()
+    gc = np.asarray(graph_counts, dtype=np.int64).reshape(-1, len(BOND_GRAPH_COLUMNS))
+    n_atoms, n_bonds, _, n_frag, n_largest, n_cycles = (int(v) for v in gc.sum(0))
+    return [int(gc.shape[0]), n_atoms, n_bonds, int((gc[:, 3] == 1).sum()), n_largest, n_frag, n_cycles]
+
+
+def summarise_bond_totals(totals):
+    """the five ratios (BOND_RATIOS) of integer totals in BOND_COUNT_KEYS order, and the totals as ``counts``; a ratio over nothing is nan"""
+    c = {k: int(v) for k, v in zip(BOND_COUNT_KEYS, totals)}
+    ratio = lambda a, b: a / b if b else float("nan")
+    return {"connected_mol_ratio": ratio(c["n_connected_mol"], c["n_mol"]),
+            "largest_fragment_atom_ratio": ratio(c["n_largest_fragment_atoms"], c["n_atoms"]),
+            "fragments_per_mol": ratio(c["n_fragments"], c["n_mol"]), "cycles_per_mol": ratio(c["n_cycles"], c["n_mol"]),
+            "bonds_per_atom": ratio(c["n_bonds"], c["n_atoms"]), "counts": c}
+
+
+def summarise_bonds(graph_counts):
+    """connectivity of a set of molecules from integer per-molecule counts (``graph_counts`` [n_mol, 6], BOND_GRAPH_COLUMNS): the share of
+    connected molecules (one fragment: the table-bond counterpart of the reference's ``'.' not in smiles``), the share of atoms in their
+    molecule's largest fragment (what ``clean_frags`` would keep), fragments and cycles per molecule, bonds per atom; plus ``counts``"""
+    return summarise_bond_totals(bond_totals(graph_counts))

@@ -22,6 +22,8 @@ Output: ``{out_root}/{tag}/pocket_{i:05d}.pt`` with the final ligand positions, 
 (optionally) the trajectory for each sample -- the tensors ``sample.py:198-206`` hands to reconstruction.
 ``--geometry`` adds a stability and steric-clash report per sample, computed on the device in one launch per batch
 (cbgbench_amd/geometry.py), and ``{out_dir}/geometry_summary.json`` for the job.
+``--bonds`` adds the table-bond graph of every sample -- bond list, fragment labels, connectivity -- computed on the device in two
+launches per batch (``geometry.batch_bonds``), and ``{out_dir}/bonds_summary.json`` for the job.
 A checkpoint is the reference's format: ``{'config': ..., 'model': state_dict}`` (``sample.py:153-156``)."""
 import argparse
 import json
@@ -102,7 +104,8 @@ def decode_mode(plan_mode, config_mode, num_classes):
 def main(argv=None, stats=None):
     """``stats`` (optional dict): filled with the wall seconds of the phases (setup = config + model + weights, batch = prior
     construction, sample = model.sample incl. the trajectory download, write = per-pocket records and files; with ``--geometry``
-    also geometry = the report's launches, a part of write)."""
+    also geometry = the report's launches, a part of write; with ``--bonds`` also bonds = the bond report's launches and downloads, a part
+    of write)."""
     t_phase = time.perf_counter()
     phases = {"setup": 0.0, "batch": 0.0, "sample": 0.0, "write": 0.0}
 
@@ -151,6 +154,13 @@ def main(argv=None, stats=None):
                          "stability and protein-ligand steric clash of the state the record holds, evaluated on the GPU in the "
                          "sampling frame against the batch's own protein_pos, one launch per batch (cbgbench_amd/geometry.py).  "
                          "Intra-ligand clashes exclude pairs with a TABLE bond (the reference uses RDKit's bonds)")
+    ap.add_argument("--bonds", action="store_true",
+                    help="add the table-bond graph to every sample (bond_index [2, nb] ligand-local with i < j, bond_order, bond_length, "
+                         "fragment = smallest index of the atom's connected component, n_fragments, connected), a `bonds` dict of counts "
+                         "to every pocket record and {out_dir}/bonds_summary.json: which atoms are bonded and whether the sample is one "
+                         "molecule, of the state the record holds, evaluated on the GPU in two launches per batch "
+                         "(cbgbench_amd/geometry.py).  TABLE bonds from the stability metric's bond lengths, not RDKit's: no "
+                         "aromaticity, no valence repair.  Independent of --geometry")
     ap.add_argument("--atom_num_dist", default=None,
                     help="the reference's size-conditioned ligand-size histogram (repo/datasets/transforms/_atom_num_dist.npy); "
                          "without it ligand sizes are U{10..45}")
@@ -169,6 +179,8 @@ def main(argv=None, stats=None):
         dev = torch.device(args.device)
     if args.geometry and dev.type != "cuda":
         raise SystemExit("sample_cli: --geometry runs on the GPU (cbgx_ligand_geometry has no CPU fallback)")
+    if args.bonds and dev.type != "cuda":
+        raise SystemExit("sample_cli: --bonds runs on the GPU (cbgx_ligand_bonds_count / _fill have no CPU fallback)")
 
     ckpt_path = args.checkpoint or config.model.get("checkpoint", None)
     if ckpt_path and os.path.exists(ckpt_path):
@@ -222,6 +234,7 @@ def main(argv=None, stats=None):
         torch.manual_seed(args.seed + rank)             # independent noise streams per shard
         rng = np.random.default_rng([args.seed, rank])
     geometry_seconds, job_counts = [0.0], []             # --geometry: wall time of the report, per-sample counts of this rank
+    bonds_seconds, job_bond_counts = [0.0], []           # --bonds: likewise
 
     def write_results(ids, traj, batch):
         # sample.py:198-201 hands traj[0] to the reconstruction -- for targetdiff / diffbp that is the state entering the
@@ -236,6 +249,13 @@ def main(argv=None, stats=None):
             geo = geometry.batch_geometry(pocket, x.to(dev), c.to(dev), bidx.to(dev), mode)
             geo = {k: v.cpu() for k, v in geo.items()}       # (the download waits for the launch)
             geometry_seconds[0] += time.perf_counter() - t_geo
+        bonds = None
+        if args.bonds:
+            # the same state in the same frame; proteins play no part
+            t_bonds = time.perf_counter()
+            bonds = geometry.batch_bonds({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode)
+            bonds = {k: v.cpu() for k, v in bonds.items()}
+            bonds_seconds[0] += time.perf_counter() - t_bonds
         x, c, bidx = x.cpu(), c.cpu(), bidx.cpu()
         if translate:       # back to the frame the pockets came in (sample.py:198-199; here per graph: a batch holds many pockets)
             x = x + batch["ligand_translation"].cpu()
@@ -252,8 +272,24 @@ def main(argv=None, stats=None):
                 smp["inter_clash"] = (f[m] & geometry.INTER_CLASH) != 0
                 smp["intra_clash_table_bonds"] = (f[m] & geometry.INTRA_CLASH) != 0
                 smp["mol_stable"] = bool(geo["graph_counts"][g, 2])
+        if bonds is not None:
+            # bonds are sorted by their first atom and atoms by graph: a graph's bonds and atoms are ranges; rows become ligand-local
+            gc = bonds["graph_counts"].to(torch.int64)
+            atom_end, bond_end = gc[:, 0].cumsum(0).tolist(), gc[:, 1].cumsum(0).tolist()
+            for g, smp in enumerate(samples):
+                a0, b0, b1 = atom_end[g] - int(gc[g, 0]), bond_end[g] - int(gc[g, 1]), bond_end[g]
+                smp["bond_index"] = bonds["bond_index"][:, b0:b1] - a0
+                smp["bond_order"] = bonds["bond_order"][b0:b1].clone()
+                smp["bond_length"] = bonds["bond_length"][b0:b1].clone()
+                smp["fragment"] = bonds["fragment"][a0:atom_end[g]].clone()
+                smp["n_fragments"] = int(gc[g, 3])
+                smp["connected"] = int(gc[g, 3]) == 1
         for k, pid in enumerate(ids):
             rec = {"pocket_index": pid, "samples": samples[k * num_samples:(k + 1) * num_samples]}
+            if bonds is not None:
+                gc = bonds["graph_counts"][k * num_samples:(k + 1) * num_samples].to(torch.int64)
+                job_bond_counts.append(gc)
+                rec["bonds"] = geometry.summarise_bonds(gc)["counts"]
             if geo is not None:
                 gc = geo["graph_counts"][k * num_samples:(k + 1) * num_samples].to(torch.int64)
                 job_counts.append(gc)
@@ -294,6 +330,8 @@ def main(argv=None, stats=None):
         stats.update(timing)
         if args.geometry:
             stats["geometry"] = geometry_seconds[0]
+        if args.bonds:
+            stats["bonds"] = bonds_seconds[0]
     if args.geometry:
         # integer counts of all ranks, summed: the job's numbers do not depend on how the pockets were sharded
         totals = geometry.job_totals(torch.cat(job_counts) if job_counts else torch.zeros(0, len(geometry.GRAPH_COLUMNS)))
@@ -303,6 +341,15 @@ def main(argv=None, stats=None):
                 json.dump(summary, f, indent=1, sort_keys=True)
             print("geometry: " + ", ".join(f"{k} {summary[k]:.4f}" for k in geometry.RATIOS)
                   + f" ({summary['counts']['n_mol']} molecules, {summary['counts']['n_atoms']} atoms)")
+    if args.bonds:
+        totals = geometry.bond_totals(torch.cat(job_bond_counts) if job_bond_counts
+                                      else torch.zeros(0, len(geometry.BOND_GRAPH_COLUMNS)))
+        summary = geometry.summarise_bond_totals(sharding.sum_counts(totals, device=dev))
+        if rank == 0:
+            with open(os.path.join(out_dir, "bonds_summary.json"), "w") as f:
+                json.dump(summary, f, indent=1, sort_keys=True)
+            print("bonds: " + ", ".join(f"{k} {summary[k]:.4f}" for k in geometry.BOND_RATIOS)
+                  + f" ({summary['counts']['n_mol']} molecules, {summary['counts']['n_bonds']} bonds)")
     if rank == 0:
         print(f"sampled {len(pockets)} pockets x {num_samples} samples on {world} rank(s): "
               f"{gs / el:.1f} graph-steps/s, results in {out_dir}")

@@ -658,6 +658,37 @@ int cbgx_ligand_geometry(const float *x_lig, const uint8_t *z_lig, const int32_t
 int cbgx_ligand_geometry_tables(int32_t *bond_pm, int32_t *margins, int32_t *allowed, uint8_t *elements, uint8_t *vdw_z, double *vdw_r,
                                 double *tolerance);
 
+/* ---- table-bond graph of sampled ligands: bond list, fragments, connectivity (geometry.hip) ------------------------------------------------
+ * What the reference learns about a sample only after RDKit / OpenBabel reconstruction -- which atoms are bonded, and whether the sample
+ *   is one molecule or several pieces (repo/tools/rdkit_utils.py:597-640: clean_frags keeps the largest fragment, evaluate_validity calls
+ *   a sample incomplete when its SMILES contains a '.') -- from the TABLE bonds of cbgx_ligand_geometry above: same arrays, same limit
+ *   CBGX_GEOMETRY_MAX_LIGAND, same distance (fp32 widened to fp64, s = (dx dx + dy dy) + dz dz without contraction, d = sqrt(s) correctly
+ *   rounded), same order (p = 100.0 d compared strictly with b + margin; pairs with s >= 25 skipped; an atom outside the eight elements
+ *   has no bonds), same tables (cbgx_ligand_geometry_tables).  No aromaticity, no valence repair: these are not RDKit's bonds.  Proteins
+ *   play no part.  One 256-thread workgroup per graph; a graph's rows are a function of its own atoms.
+ * The number of bonds of a graph is not bounded by its number of atoms, so the list is made in two launches with a prefix sum between:
+ * cbgx_ligand_bonds_count: deg_up [n_lig] int32 = the number of bonded partners j > i of atom i inside its ligand; fragment [n_lig] int32
+ *   = the connected-component label of the atom, defined as the smallest ligand-local index in its component (an atom without bonds or
+ *   with an unknown element is its own fragment); graph_out [B, CBGX_BONDS_GRAPH_COLS] int32: n_atoms, n_bonds (pairs i < j with order
+ *   > 0), bond_order_sum (sum of the orders of those pairs), n_fragments, largest_fragment (atoms; 0 for an empty graph), n_cycles =
+ *   n_bonds - n_atoms + n_fragments.  Every element of every graph is written.  Integer results; the components are the unique fixed point
+ *   of min-label propagation, found in at most n_atoms rounds, independent of the order in which threads run.
+ *   Checks, the lig_ptr read-back and return values as cbgx_ligand_geometry: CBGX_E_INVALID before any dereference or launch for negative
+ *   counts, a NULL pointer with a non-zero count, a ligand above CBGX_GEOMETRY_MAX_LIGAND atoms (graph and size in the message), lig_ptr
+ *   the device cannot read; 0 without a launch when B == 0.
+ * cbgx_ligand_bonds_fill: bond_ptr [n_lig + 1] int32 = the exclusive prefix sum of deg_up, n_bonds = bond_ptr[n_lig]; bond_index
+ *   [2, n_bonds] int32 global ligand rows with i < j (row 0: i, row 1: j); bond_order [n_bonds] uint8 in 1..3; bond_length [n_bonds] fp64
+ *   = the d the order was decided on, in Angstrom.  Atom a writes its partners in ascending j at bond_ptr[a] ...: the list is in strict
+ *   lexicographic (i, j) order, without atomics.  bond_ptr entries are clamped to [0, n_bonds] and made non-decreasing per atom: an atom
+ *   writes at most bond_ptr[a + 1] - bond_ptr[a] entries and nothing at or beyond n_bonds, so a wrong bond_ptr loses bonds and never
+ *   reaches outside the buffers.  Same checks; 0 without a launch when B == 0 or n_bonds == 0. */
+#define CBGX_BONDS_GRAPH_COLS 6
+int cbgx_ligand_bonds_count(const float *x_lig, const uint8_t *z_lig, const int32_t *lig_ptr, int n_lig, int n_graphs, int32_t *deg_up,
+                            int32_t *fragment, int32_t *graph_out, void *stream);
+int cbgx_ligand_bonds_fill(const float *x_lig, const uint8_t *z_lig, const int32_t *lig_ptr, int n_lig, int n_graphs,
+                           const int32_t *bond_ptr, int n_bonds, int32_t *bond_index, uint8_t *bond_order, double *bond_length,
+                           void *stream);
+
 /* ---- measurement hook (bench.py) ----------------------------------------------------------------
  * Between cbgx_profile_begin() and cbgx_profile_end() every kernel launch is bracketed by HIP events on
  * its own stream.  cbgx_profile_end() synchronises them and returns, per kernel class, the summed
