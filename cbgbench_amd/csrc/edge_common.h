@@ -170,6 +170,60 @@ __device__ __forceinline__ RbfScale load_rbf_scale(const float* att, int kv) {
 }
 constexpr float RBF_UP = (float)(1 << RBF_EXP);
 
+// ---- split-f16 of activations (x2h scores and aggregation of edge_x2h_f16.hip) ---------------------------------
+// v = hi + lo with hi = f16(v) (round to nearest) and lo = f16(v - hi): the subtraction is exact in fp32 and is written as an fma on
+// the converted half (v_fma_mix_f32 reads it straight from the f16 register); lo lo products are dropped (2^-22 relative).
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+// two values at a time: one v_cvt_pk_f16_f32 for the hi pair, one v_fma_mix_f32 per residual (v - hi with hi read from its half of the
+// packed register: exact), one v_cvt_pk_f16_f32 for the lo pair -- 2 VALU instructions per split value.  The residual is an fma with
+// an OPAQUE -1 (a scalar register behind an empty asm): written as v - hi, or as an fma with the literal, it is canonicalised to a
+// subtraction before instruction selection and compiles to v_cvt_f32_f16 + v_sub_f32.  No instruction is written in inline asm here:
+// the compiler does not track matrix-pipe hazards (an MFMA still reading a register, a VALU write to it) across asm statements.
+__device__ __forceinline__ float opaque_minus_one() {
+    float m = -1.f;
+    asm("" : "+s"(m));
+    return m;
+}
+__device__ __forceinline__ void split_f16x2(const float a, const float b, unsigned& hi, unsigned& lo) {
+    const float m1 = opaque_minus_one();
+    const half2v h = {(_Float16)a, (_Float16)b};
+    hi = __builtin_bit_cast(unsigned, h);
+    const half2v l = {(_Float16)__builtin_fmaf((float)h[0], m1, a), (_Float16)__builtin_fmaf((float)h[1], m1, b)};
+    lo = __builtin_bit_cast(unsigned, l);
+}
+typedef unsigned uint2s __attribute__((ext_vector_type(2)));
+typedef unsigned uint4s __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void split_f16x4(const floatx4 v, half4& hi, half4& lo) {
+    unsigned h[2], l[2];
+    split_f16x2(v[0], v[1], h[0], l[0]);
+    split_f16x2(v[2], v[3], h[1], l[1]);
+    hi = __builtin_bit_cast(half4, (uint2s{h[0], h[1]}));
+    lo = __builtin_bit_cast(half4, (uint2s{l[0], l[1]}));
+}
+__device__ __forceinline__ void split_f16x8(const floatx4 a, const floatx4 b, half8& hi, half8& lo) {
+    unsigned h[4], l[4];
+    split_f16x2(a[0], a[1], h[0], l[0]);
+    split_f16x2(a[2], a[3], h[1], l[1]);
+    split_f16x2(b[0], b[1], h[2], l[2]);
+    split_f16x2(b[2], b[3], h[3], l[3]);
+    hi = __builtin_bit_cast(half8, (uint4s{h[0], h[1], h[2], h[3]}));
+    lo = __builtin_bit_cast(half8, (uint4s{l[0], l[1], l[2], l[3]}));
+}
+// the exponent k that puts a bound m >= 0 into [2^14, 2^15) as m 2^k, clamped so that 2^k and 2^-k are finite normal numbers;
+// `zero_is_one`: m = 0 (or subnormal) gets k = 0 (a zero query row), otherwise the clamp (a zero LayerNorm affine: 0 2^k = 0)
+constexpr int SPLIT_K_MAX = 126;
+__host__ __device__ __forceinline__ int split_exponent_bits(unsigned bits, bool zero_is_one) {
+    const int E = (int)((bits >> 23) & 0xffu);                      // m in [2^(E-127), 2^(E-126))
+    if (zero_is_one && E == 0) return 0;
+    const int k = 141 - E;
+    return k > SPLIT_K_MAX ? SPLIT_K_MAX : (k < -SPLIT_K_MAX ? -SPLIT_K_MAX : k);
+}
+__device__ __forceinline__ int split_exponent(float m, bool zero_is_one) { return split_exponent_bits(__float_as_uint(m), zero_is_one); }
+__device__ __forceinline__ float pow2_scale(int k) { return __uint_as_float((unsigned)(k + 127) << 23); }
+constexpr float LN_OUT_MAX = 11.27f;             // >= sqrt(127): the largest |value| a zero-mean row of 128 can have after normalisation
+constexpr float W_UP = 16384.f;                  // aggregation weights alpha e_w in [0, 1] -> [0, 2^14]
+
 // XOR mask of the second v Linear's LDS rows (x2h epilogue): heads {0-3, 12-15} -> 0..7, heads {4-11} -> 8..15, so that the two
 // half-rows of lanes a ds_read_b128 lane group combines never meet on a 16-byte slot (edge_mfma.hip, epilogue)
 __host__ __device__ __forceinline__ int wbv_swizzle(int head) { return head < 4 ? head : (head < 12 ? head + 4 : head - 8); }

@@ -192,6 +192,11 @@ hipError_t launch_edge_x2h_dual(const float* att, const float* x, const float* h
                                 const float* qbuf, const int32_t* nbr, const int32_t* deg, const uint8_t* lig,
                                 const uint8_t* gen, const float* e_w, int n_nodes, float* out, const int* list_pp,
                                 const int* count_pp, const int* list_gen, const int* count_gen, bool full_layer, hipStream_t s);
+// edge_x2h_f16.hip: the same launch with scores and aggregation in split-f16 (called by launch_edge_x2h_dual, which owns the grid)
+void launch_edge_x2h_f16_grid(int grid, const float* att, const float* x, const float* h, const float* P, const float* Qt,
+                              const float* qbuf, const int32_t* nbr, const int32_t* deg, const uint8_t* lig, const uint8_t* gen,
+                              const float* e_w, int n_nodes, float* out, const int* list_pp, const int* count_pp,
+                              const int* list_gen, const int* count_gen, bool full_layer, hipStream_t s);
 // TargetDiff step prologue / epilogue (step.hip)
 hipError_t launch_step_prologue(const float* x_lig, const float* c_lig, const int32_t* lig_rows, int n_lig, int C,
                                 const float* emb_w, const float* emb_b, const float* ind_w, const float* ind_b, float* x,
