@@ -393,7 +393,7 @@ __global__ __launch_bounds__(64) void diffsbdd_step_kernel(
         for (int k = 0; k < 3; ++k) {
             const float v = do_x ? x_next[3 * a + k] - mean[k] : x_lig[3 * a + k];
             x_next[3 * a + k] = v;
-            x[3 * row + k] = v + Sn[k];      // (Sn = 0 without a frame)
+            x[3 * row + k] = frame ? v + Sn[k] : v;      // without a frame the pocket itself moves (below): the ligand rows are x_next
         }
         for (int k = 0; k < C; ++k) {
             const float ck = c_lig[(size_t)a * C + k];

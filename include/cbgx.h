@@ -262,7 +262,11 @@ int cbgx_targetdiff_epilogue_traj(const float *x_den, const float *logits, const
  *   static-context cache of cbgx_unitransformer_forward_cached holds for the whole run) and the translation the reference applies
  *   to the pocket is accumulated in frame_shift instead: true position = position in x - frame_shift[graph].  x_den is then the
  *   denoiser's output in the frame of x (the network is translation-equivariant), x_lig / x_next stay in true coordinates, the
- *   ligand rows of x get x_next + frame_shift.  Start with frame_shift = 0. */
+ *   ligand rows of x get x_next + frame_shift (without frame_shift they get x_next).  Start with frame_shift = 0.
+ *   update_positions == 0: x_next = x_lig, the removed mean is 0 and the pocket stays; update_types == 0: c_next = c_lig.
+ * Both calls: a graph without ligand atoms has a zero mean (the reference's clamp(count, min=1)): its shift row is 0, its
+ *   frame_shift row and its pocket rows keep their values.  n_lig == 0 (with any n_graphs) or n_graphs == 0 returns CBGX_OK
+ *   before any other argument is looked at and writes NOTHING: not x_next / c_next, not x / h, not shift, not frame_shift. */
 int cbgx_diffbp_epilogue(const float *x_den, const float *x_com, const float *x_in, const float *logits,
                          const int32_t *lig_rows, const int32_t *lig_ptr, const float *x_lig, const float *c_lig,
                          const uint8_t *gen_lig, int n_lig, int n_graphs, int num_classes, int t, int num_timesteps,
