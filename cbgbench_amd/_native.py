@@ -58,6 +58,8 @@ EXPORTS = {
                                              _vp]),
     "cbgx_train_transform": (_i, [_vp] * 5 + [_i, _i, _i, ctypes.c_float, _i, _vp] + [_vp] * 4),
     "cbgx_train_transform_rng": (_i, [_vp] * 5 + [_i, _i, _i, ctypes.c_float, _i, _vp, _i] + [_vp] * 4),
+    "cbgx_train_transform_choose": (_i, [_vp] * 8 + [_i] * 5 + [ctypes.c_float, _i, _vp] + [_vp] * 6),
+    "cbgx_train_transform_choose_rng": (_i, [_vp] * 7 + [_i] * 5 + [ctypes.c_float, _i, _vp, _i] + [_vp] * 6),
     "cbgx_targetdiff_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.POINTER(_vp), _vp, _vp, _vp,
                                   _vp, _vp, _vp]),
     "cbgx_targetdiff_loss_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -1062,6 +1062,54 @@ int cbgx_train_transform_rng(const float* x_rec, const float* x_lig, const int32
     return CBGX_OK;
 }
 
+// the same behind the decomposition choice of every graph (choose_ctx_gen): what the three CSRs and the two further outputs must satisfy
+static int tt_choose_check(const char* what, const int32_t* dec_ptr, const int32_t* gen_ptr, const int32_t* gen_idx, int n_graphs,
+                           int n_lig, int n_dec, int n_idx, const uint8_t* gen_flag_out, const int32_t* choice_out) {
+    if (n_dec < 0 || n_idx < 0) return set_error(CBGX_E_INVALID, "%s: bad arguments (n_dec=%d n_idx=%d)", what, n_dec, n_idx);
+    if ((n_graphs > 0 && (!dec_ptr || !choice_out)) || (n_dec > 0 && !gen_ptr) || (n_idx > 0 && !gen_idx) || (n_lig > 0 && !gen_flag_out))
+        return set_error(CBGX_E_INVALID, "%s: NULL pointer", what);
+    return CBGX_OK;
+}
+
+int cbgx_train_transform_choose(const float* x_rec, const float* x_lig, const int32_t* rec_ptr, const int32_t* lig_ptr,
+                                const int32_t* dec_ptr, const int32_t* gen_ptr, const int32_t* gen_idx, const int32_t* choice_in,
+                                int n_graphs, int n_rec, int n_lig, int n_dec, int n_idx, float sigma, int center_mode, const float* eps,
+                                float* x_rec_out, float* x_lig_out, float* center_out, uint8_t* gen_flag_out, int32_t* choice_out,
+                                void* stream) {
+    int rc = tt_check("train_transform_choose", x_rec, x_lig, rec_ptr, lig_ptr, n_graphs, n_rec, n_lig, sigma, center_mode, x_rec_out,
+                      x_lig_out, center_out);
+    if (rc != CBGX_OK) return rc;
+    rc = tt_choose_check("train_transform_choose", dec_ptr, gen_ptr, gen_idx, n_graphs, n_lig, n_dec, n_idx, gen_flag_out, choice_out);
+    if (rc != CBGX_OK) return rc;
+    if (!eps && sigma > 0.f)
+        return set_error(CBGX_E_INVALID, "train_transform_choose: eps == NULL needs sigma == 0 (got %g)", (double)sigma);
+    HIP_TRY(launch_train_transform_choose(x_rec, x_lig, rec_ptr, lig_ptr, dec_ptr, gen_ptr, gen_idx, choice_in, n_graphs, n_rec, n_lig,
+                                          n_dec, n_idx, sigma, center_mode, eps, nullptr, 0u, x_rec_out, x_lig_out, center_out,
+                                          gen_flag_out, choice_out, (hipStream_t)stream));
+    return CBGX_OK;
+}
+
+int cbgx_train_transform_choose_rng(const float* x_rec, const float* x_lig, const int32_t* rec_ptr, const int32_t* lig_ptr,
+                                    const int32_t* dec_ptr, const int32_t* gen_ptr, const int32_t* gen_idx, int n_graphs, int n_rec,
+                                    int n_lig, int n_dec, int n_idx, float sigma, int center_mode, const uint64_t* stream_keys,
+                                    int purpose_base, float* x_rec_out, float* x_lig_out, float* center_out, uint8_t* gen_flag_out,
+                                    int32_t* choice_out, void* stream) {
+    int rc = tt_check("train_transform_choose_rng", x_rec, x_lig, rec_ptr, lig_ptr, n_graphs, n_rec, n_lig, sigma, center_mode,
+                      x_rec_out, x_lig_out, center_out);
+    if (rc != CBGX_OK) return rc;
+    rc = tt_choose_check("train_transform_choose_rng", dec_ptr, gen_ptr, gen_idx, n_graphs, n_lig, n_dec, n_idx, gen_flag_out,
+                         choice_out);
+    if (rc != CBGX_OK) return rc;
+    if (purpose_base < 0 || purpose_base % CBGX_NOISE_PURPOSE_STRIDE != 0)
+        return set_error(CBGX_E_INVALID, "train_transform_choose_rng: purpose_base=%d is not a non-negative multiple of %d", purpose_base,
+                         CBGX_NOISE_PURPOSE_STRIDE);
+    if (n_graphs > 0 && !stream_keys) return set_error(CBGX_E_INVALID, "train_transform_choose_rng: NULL pointer");
+    HIP_TRY(launch_train_transform_choose(x_rec, x_lig, rec_ptr, lig_ptr, dec_ptr, gen_ptr, gen_idx, nullptr, n_graphs, n_rec, n_lig,
+                                          n_dec, n_idx, sigma, center_mode, nullptr, stream_keys, (uint32_t)purpose_base, x_rec_out,
+                                          x_lig_out, center_out, gen_flag_out, choice_out, (hipStream_t)stream));
+    return CBGX_OK;
+}
+
 int cbgx_targetdiff_loss(const float* x_out, const float* logits, const int64_t* lig_rows, const float* x0, const int64_t* v0,
                          const int64_t* v_t, const int64_t* t, const int64_t* batch, const uint8_t* gen, int n_lig, int n_graphs,
                          int num_classes, const float* const* tables, float* losses, float* x_pred, float* c_pred,

@@ -37,6 +37,9 @@
 //               (index of the protein atom INSIDE ITS POCKET, step 0, base + TRAIN_PROTEIN_NORMAL, 0), components 0..2, under the same
 //               graph key -- training base 0, validation base PURPOSE_STRIDE.  It does not depend on the graph's time.  Precondition: the
 //               protein atoms of an example keep their order.
+//   choice      the decomposition of its ligand a visit trains on (the config's choose_ctx_gen): k = (uint64(w0) * K) >> 32 in [0, K),
+//               w0 = word 0 of the call at counter (0, 0, base + TRAIN_CHOOSE_CTX, 0) under the graph key -- the time's formula at an
+//               address of its own; training base 0, validation base PURPOSE_STRIDE.
 // Plain C++: a host compiler builds this header for the stand-alone known-answer program of tests/test_counter_noise.py.
 #pragma once
 #include <math.h>
@@ -67,6 +70,8 @@ enum Purpose : uint32_t {
     TRAIN_TYPE_NORMAL = 11, // type normal, components 0..C-1                               (DiffSBDD)
     TRAIN_PROTEIN_NORMAL = 12, // protein-coordinate augmentation of a training visit (add_pos_noise), components 0..2: counter (the
                             // atom's index INSIDE ITS POCKET, step 0, base + TRAIN_PROTEIN_NORMAL, 0)   (train_transform.hip)
+    TRAIN_CHOOSE_CTX = 13,  // which decomposition of its ligand a visit trains on (choose_ctx_gen): counter (0, 0, base +
+                            // TRAIN_CHOOSE_CTX, 0), word 0 through scale_word                           (train_transform.hip)
     PURPOSE_STRIDE = 16 // purpose bases are multiples of this
 };
 

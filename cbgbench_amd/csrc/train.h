@@ -163,6 +163,13 @@ hipError_t launch_train_transform(const float* x_rec, const float* x_lig, const 
                                   const uint8_t* ctx, int n_graphs, int n_rec, int n_lig, float sigma, int mode, const float* eps,
                                   const uint64_t* keys, uint32_t purpose, float* x_rec_out, float* x_lig_out, float* center_out,
                                   hipStream_t s);
+// the same behind the decomposition choice (choose_ctx_gen) of every graph; keys != NULL: choice and eps drawn in place
+hipError_t launch_train_transform_choose(const float* x_rec, const float* x_lig, const int32_t* rec_ptr, const int32_t* lig_ptr,
+                                         const int32_t* dec_ptr, const int32_t* gen_ptr, const int32_t* gen_idx,
+                                         const int32_t* choice_in, int n_graphs, int n_rec, int n_lig, int n_dec, int n_idx,
+                                         float sigma, int mode, const float* eps, const uint64_t* keys, uint32_t purpose_base,
+                                         float* x_rec_out, float* x_lig_out, float* center_out, uint8_t* gen_flag_out,
+                                         int32_t* choice_out, hipStream_t s);
 // train_loss_diffbp.hip: DiffBP's four losses and their gradients with respect to the network outputs (composed row order)
 hipError_t launch_diffbp_loss(const float* x_out, const float* x_in, const float* x_stack, const float* logits, const int64_t* sort_idx,
                               const int32_t* graph_ptr, const uint8_t* lig, const float* pos_noise, const float* com_noise,

@@ -1,7 +1,7 @@
 // libcbgx -- the per-visit transforms of a training batch (the reference's add_pos_noise followed by center_pos / center_whole_pos,
 // repo/datasets/transforms/translation.py), for a whole batch in ONE launch, one 256-thread workgroup per graph:
 //   1. protein noise   noised = fmaf(sigma, eps, x) for every protein atom (sigma > 0 only; sigma == 0 copies x).  eps comes from the
-//                      caller's tape (train_transform_kernel<false>) or is drawn in place (train_transform_kernel<true>): counter =
+//                      caller's tape (RNG false) or is drawn in place (RNG true): counter =
 //                      (the atom's index inside its pocket, step 0, purpose base + TRAIN_PROTEIN_NORMAL, block 0), components 0..2, under
 //                      the graph's stream key -- the expressions noise_fill_kernel (step.hip) stores, so the two routes agree bit for bit.
 //   2. centre          the mean of the graph's centre set: the NOISED protein atoms (CENTER_PROTEIN), the ligand atoms with ctx != 0
@@ -15,6 +15,17 @@
 // A thread keeps the noised coordinates of its first three protein atoms (pockets of up to 768 atoms) in registers between the sum and
 // the subtraction; those of further atoms wait in x_rec_out, where the same thread wrote them.  No coordinate is drawn twice.
 // Every product and sum is written as the rounding it is (fmaf / __fadd_rn / __fsub_rn / __fdiv_rn): nothing is left to contraction.
+//
+// train_transform_choose_kernel (cbgx_train_transform_choose{,_rng}; the body with CHOOSE) puts the reference's choose_ctx_gen (select.py:21-58) in front, in
+// the same launch -- the centre set of CENTER_CONTEXT is the complement of the atoms it picks:
+//   0. choice          graph g owns the decompositions dec_ptr[g] .. dec_ptr[g+1] (K of them); decomposition d names the ligand-local atoms
+//                      gen_idx[gen_ptr[d] .. gen_ptr[d+1]].  k = choice_in[g] clamped into [0, K) (tape; NULL: 0), or
+//                      scale_word(word 0 of the call at counter (0, 0, base + TRAIN_CHOOSE_CTX, 0) under the graph's key, K) (counter:
+//                      rng::train_time's formula at its own address).  K == 0: k = -1 and every ligand atom is generated.
+//      flag            gen_flag_out = 0 on the graph's ligand rows, barrier, = 1 on the rows decomposition k names (an index outside the
+//                      ligand is skipped, duplicates write the same byte twice), barrier; steps 1 - 3 then read ctx = !gen_flag_out.  The
+//                      flags live in global memory (a ligand has no size limit); a workgroup reads only the rows it wrote itself.
+// The three CSRs are clamped to their arrays like rec_ptr / lig_ptr.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -44,12 +55,21 @@ __device__ __forceinline__ void tt_tree(float (*red)[TT_THREADS], float& a, floa
     a = red[0][0]; b = red[1][0]; c = red[2][0]; d = red[3][0];
 }
 
-template <bool RNG>
-__global__ __launch_bounds__(TT_THREADS) void train_transform_kernel(
+// operands of the decomposition choice (train_transform_choose_kernel; the body without CHOOSE never reads them)
+struct TTChoose {
+    const int32_t* dec_ptr; const int32_t* gen_ptr; const int32_t* gen_idx; const int32_t* choice_in;
+    int n_dec, n_idx;
+    uint32_t purpose;           // base + TRAIN_CHOOSE_CTX
+    uint8_t* gen_flag_out; int32_t* choice_out;
+};
+
+// the one body of the four kernels below
+template <bool RNG, bool CHOOSE>
+__device__ __forceinline__ void train_transform_body(
     const float* __restrict__ x_rec, const float* __restrict__ x_lig, const int32_t* __restrict__ rec_ptr,
     const int32_t* __restrict__ lig_ptr, const uint8_t* __restrict__ ctx, int n_rec, int n_lig, float sigma, int mode,
     const float* __restrict__ eps, const uint64_t* __restrict__ keys, uint32_t purpose, float* x_rec_out, float* __restrict__ x_lig_out,
-    float* __restrict__ center_out) {
+    float* __restrict__ center_out, const TTChoose& ch) {
     __shared__ float red[4][TT_THREADS];
     const int g = blockIdx.x, k = threadIdx.x;
     // a malformed CSR must not reach outside the arrays: both ranges are clamped to them
@@ -59,7 +79,34 @@ __global__ __launch_bounds__(TT_THREADS) void train_transform_kernel(
     const bool noisy = sigma > 0.f;
     const bool rec_in_set = mode == CBGX_CENTER_PROTEIN || mode == CBGX_CENTER_WHOLE;
     uint64_t key = 0;
-    if (RNG && noisy) key = keys[g];
+    if (RNG && (noisy || CHOOSE)) key = keys[g];
+    // ---- decomposition choice and the generated-atom flag of the graph's ligand rows -------------------------------------------------
+    if constexpr (CHOOSE) {
+        const int d0 = min(max(ch.dec_ptr[g], 0), ch.n_dec), d1 = min(max(ch.dec_ptr[g + 1], d0), ch.n_dec);
+        const int K = d1 - d0;                   // uniform over the workgroup, and so is every branch on it
+        int kc = -1;
+        if (K > 0) {
+            if (RNG) kc = (int)rng::scale_word(rng::draw(key, 0u, 0u, ch.purpose, 0u).w0, (uint32_t)K);
+            else kc = ch.choice_in ? min(max(ch.choice_in[g], 0), K - 1) : 0;
+        }
+        if (k == 0) ch.choice_out[g] = kc;
+        const uint8_t rest = K > 0 ? 0 : 1;      // no decomposition: the whole ligand is generated
+        for (int la = k; la < nl; la += TT_THREADS) ch.gen_flag_out[(size_t)(l0 + la)] = rest;
+        if (K > 0) {
+            __syncthreads();                     // the scatter overwrites bytes that other threads have just cleared
+            const int d = d0 + kc;
+            const int i0 = min(max(ch.gen_ptr[d], 0), ch.n_idx), i1 = min(max(ch.gen_ptr[d + 1], i0), ch.n_idx);
+            for (int i = i0 + k; i < i1; i += TT_THREADS) {
+                const int la = ch.gen_idx[i];
+                if (la >= 0 && la < nl) ch.gen_flag_out[(size_t)(l0 + la)] = 1;
+            }
+        }
+        __syncthreads();                         // the sum below reads rows that other threads of the workgroup wrote
+    }
+    auto in_ctx = [&](size_t a) -> bool {
+        if constexpr (CHOOSE) return ch.gen_flag_out[a] == 0;
+        else return ctx[a] != 0;
+    };
 
     float sx = 0.f, sy = 0.f, sz = 0.f;
     float held[TT_HELD][3];
@@ -102,10 +149,10 @@ __global__ __launch_bounds__(TT_THREADS) void train_transform_kernel(
             sx = __fadd_rn(sx, x_lig[3 * a + 0]); sy = __fadd_rn(sy, x_lig[3 * a + 1]); sz = __fadd_rn(sz, x_lig[3 * a + 2]);
         }
         cnt = (float)nr + (float)nl;
-    } else if (mode == CBGX_CENTER_CONTEXT && ctx) {
+    } else if (mode == CBGX_CENTER_CONTEXT && (CHOOSE || ctx)) {
         for (int la = k; la < nl; la += TT_THREADS) {
             const size_t a = (size_t)(l0 + la);
-            if (ctx[a]) {
+            if (in_ctx(a)) {
                 sx = __fadd_rn(sx, x_lig[3 * a + 0]); sy = __fadd_rn(sy, x_lig[3 * a + 1]); sz = __fadd_rn(sz, x_lig[3 * a + 2]);
                 mine += 1.f;
             }
@@ -157,6 +204,28 @@ __global__ __launch_bounds__(TT_THREADS) void train_transform_kernel(
     }
 }
 
+// cbgx_train_transform (RNG false) / cbgx_train_transform_rng (true): the argument block they have always had
+template <bool RNG>
+__global__ __launch_bounds__(TT_THREADS) void train_transform_kernel(
+    const float* __restrict__ x_rec, const float* __restrict__ x_lig, const int32_t* __restrict__ rec_ptr,
+    const int32_t* __restrict__ lig_ptr, const uint8_t* __restrict__ ctx, int n_rec, int n_lig, float sigma, int mode,
+    const float* __restrict__ eps, const uint64_t* __restrict__ keys, uint32_t purpose, float* x_rec_out, float* __restrict__ x_lig_out,
+    float* __restrict__ center_out) {
+    train_transform_body<RNG, false>(x_rec, x_lig, rec_ptr, lig_ptr, ctx, n_rec, n_lig, sigma, mode, eps, keys, purpose, x_rec_out,
+                                     x_lig_out, center_out, TTChoose{});
+}
+
+// cbgx_train_transform_choose / cbgx_train_transform_choose_rng: the decompositions in place of the context flag
+template <bool RNG>
+__global__ __launch_bounds__(TT_THREADS) void train_transform_choose_kernel(
+    const float* __restrict__ x_rec, const float* __restrict__ x_lig, const int32_t* __restrict__ rec_ptr,
+    const int32_t* __restrict__ lig_ptr, int n_rec, int n_lig, float sigma, int mode, const float* __restrict__ eps,
+    const uint64_t* __restrict__ keys, uint32_t purpose, float* x_rec_out, float* __restrict__ x_lig_out,
+    float* __restrict__ center_out, TTChoose ch) {
+    train_transform_body<RNG, true>(x_rec, x_lig, rec_ptr, lig_ptr, nullptr, n_rec, n_lig, sigma, mode, eps, keys, purpose, x_rec_out,
+                                    x_lig_out, center_out, ch);
+}
+
 hipError_t launch_train_transform(const float* x_rec, const float* x_lig, const int32_t* rec_ptr, const int32_t* lig_ptr,
                                   const uint8_t* ctx, int n_graphs, int n_rec, int n_lig, float sigma, int mode, const float* eps,
                                   const uint64_t* keys, uint32_t purpose, float* x_rec_out, float* x_lig_out, float* center_out,
@@ -168,6 +237,25 @@ hipError_t launch_train_transform(const float* x_rec, const float* x_lig, const 
     else
         hipLaunchKernelGGL(train_transform_kernel<false>, dim3(n_graphs), dim3(TT_THREADS), 0, s, x_rec, x_lig, rec_ptr, lig_ptr, ctx,
                            n_rec, n_lig, sigma, mode, eps, keys, purpose, x_rec_out, x_lig_out, center_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_train_transform_choose(const float* x_rec, const float* x_lig, const int32_t* rec_ptr, const int32_t* lig_ptr,
+                                         const int32_t* dec_ptr, const int32_t* gen_ptr, const int32_t* gen_idx,
+                                         const int32_t* choice_in, int n_graphs, int n_rec, int n_lig, int n_dec, int n_idx,
+                                         float sigma, int mode, const float* eps, const uint64_t* keys, uint32_t purpose_base,
+                                         float* x_rec_out, float* x_lig_out, float* center_out, uint8_t* gen_flag_out,
+                                         int32_t* choice_out, hipStream_t s) {
+    if (n_graphs == 0) return hipSuccess;
+    const TTChoose ch = {dec_ptr, gen_ptr, gen_idx, choice_in, n_dec, n_idx, purpose_base + (uint32_t)rng::TRAIN_CHOOSE_CTX,
+                         gen_flag_out, choice_out};
+    const uint32_t purpose = purpose_base + (uint32_t)rng::TRAIN_PROTEIN_NORMAL;
+    if (keys)
+        hipLaunchKernelGGL(train_transform_choose_kernel<true>, dim3(n_graphs), dim3(TT_THREADS), 0, s, x_rec, x_lig, rec_ptr, lig_ptr,
+                           n_rec, n_lig, sigma, mode, eps, keys, purpose, x_rec_out, x_lig_out, center_out, ch);
+    else
+        hipLaunchKernelGGL(train_transform_choose_kernel<false>, dim3(n_graphs), dim3(TT_THREADS), 0, s, x_rec, x_lig, rec_ptr, lig_ptr,
+                           n_rec, n_lig, sigma, mode, eps, keys, purpose, x_rec_out, x_lig_out, center_out, ch);
     return hipGetLastError();
 }
 

@@ -34,6 +34,11 @@ step 0, base + TRAIN_PROTEIN_NORMAL, block 0), components 0..2, under the graph'
 the graph's time.  Precondition: the protein atoms of an example keep their order.  ``protein_draw_model`` / ``protein_addresses`` are its
 numpy model; ``train_addresses`` / ``validation_addresses`` list the draws of the model call only, as before.
 
+Which decomposition of its ligand a visit trains on (the config's ``choose_ctx_gen``; ``cbgx_train_transform_choose_rng``, in the same
+launch as the protein noise and the centring) is drawn at the purpose TRAIN_CHOOSE_CTX: k = ``scale_word``(word 0 of the call at counter
+(0, 0, base + TRAIN_CHOOSE_CTX, 0), K) under the graph's key -- the time's formula at an address of its own.  ``choose_model`` /
+``choose_addresses`` are its numpy model.
+
 The numpy functions below restate the generator from its definition (Salmon et al., SC'11); tests compare the header (built with a
 host compiler) and the kernels against them: words and uniforms bit for bit, normals within the rounding of the device's
 logf / sqrtf / sincosf.
@@ -46,6 +51,7 @@ from . import _native
 # purposes (csrc/rng.h ``Purpose``, include/cbgx.h CBGX_NOISE_*)
 POS_NORMAL, TYPE_UNIFORM, MASK_UNIFORM, TYPE_NORMAL, INIT_POS, INIT_TYPE, FINAL_POS = range(7)
 TRAIN_TIME, TRAIN_POS_NORMAL, TRAIN_TYPE_UNIFORM, TRAIN_MASK_UNIFORM, TRAIN_TYPE_NORMAL, TRAIN_PROTEIN_NORMAL = range(7, 13)
+TRAIN_CHOOSE_CTX = 13       # the decomposition choice of a visit (not a per-atom draw; PURPOSE_NAMES lists those)
 PURPOSE_STRIDE = 16
 PURPOSE_NAMES = ("pos_normal", "type_uniform", "mask_uniform", "type_normal", "init_pos", "init_type", "final_pos",
                  "train_time", "train_pos_normal", "train_type_uniform", "train_mask_uniform", "train_type_normal",
@@ -165,6 +171,28 @@ def protein_addresses(keys, rec_ptr, purpose_base=0):
     counts = np.diff(np.asarray(rec_ptr, dtype=np.int64))
     rows = [(keys[g], a, 0, purpose_base + TRAIN_PROTEIN_NORMAL, 0) for g, n in enumerate(counts) for a in range(int(n))]
     return np.array(rows, dtype=np.uint64).reshape(-1, 5)
+
+
+def choose_model(keys, K, purpose_base=0):
+    """numpy model of the choice ``cbgx_train_transform_choose_rng`` draws: [B] int64, graph ``g`` with ``K[g]`` decompositions (one
+    integer: the same for all) gets ``scale_word``(word 0 at counter (0, 0, purpose_base + TRAIN_CHOOSE_CTX, 0) under ``keys[g]``, K[g])
+    in [0, K[g]); -1 where K[g] is 0"""
+    keys = np.asarray(keys, dtype=np.uint64).reshape(-1)
+    K = np.broadcast_to(np.asarray(K, dtype=np.int64), keys.shape)
+    if K.size and K.min() < 0:
+        raise ValueError("choose_model: K must be >= 0")
+    ctr = np.zeros((keys.size, 4), dtype=np.uint64)
+    ctr[:, 2] = purpose_base + TRAIN_CHOOSE_CTX
+    key = np.stack([keys & _MASK, keys >> np.uint64(32)], -1)
+    w0 = philox4x32_10(ctr, key)[:, 0].astype(np.uint64)
+    k = ((w0 * K.astype(np.uint64)) >> np.uint64(32)).astype(np.int64)
+    return np.where(K > 0, k, -1)
+
+
+def choose_addresses(keys, purpose_base=0):
+    """the (key, atom, step, purpose, block) addresses of ``choose_model``: [B, 5] uint64, one row (one Philox call) per graph"""
+    keys = np.asarray(keys, dtype=np.uint64).reshape(-1)
+    return np.array([(k, 0, 0, purpose_base + TRAIN_CHOOSE_CTX, 0) for k in keys], dtype=np.uint64).reshape(-1, 5)
 
 
 TRAIN_PURPOSE_B = {"targetdiff": TRAIN_TYPE_UNIFORM, "diffbp": TRAIN_MASK_UNIFORM, "diffsbdd": TRAIN_TYPE_NORMAL}

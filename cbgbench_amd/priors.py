@@ -259,6 +259,54 @@ class TrainingPlan:
         return cls(noise_std if noise_std is not None and keep_noise else 0.0, center if center is not None else "protein")
 
 
+class ContextChoice:
+    """The ``choose_ctx_gen`` entry of a transform list (select.py:21-58): a stored ligand carries several decompositions into generated
+    and context atoms (``ligand_gen_index``, the reference's ``data['ligand']['gen_index']``), and every visit of the example picks one
+    -- ``sampling='uniform'`` (the default of the training lists: ``random.choice``) or ``'fix_zero'`` (the test lists: always the
+    first).  ``ligand_gen_flag`` is set on the atoms the picked entry names and the context is its complement, so the pick has to be
+    made before the centring: ``train_cli.apply_plan(batch, plan, choose=...)`` makes it in the launch that centres.  It is kept apart
+    from ``TrainingPlan``: a plan says what happens to coordinates, and two lists with and without the entry have equal plans."""
+
+    SAMPLINGS = ("uniform", "fix_zero")
+
+    def __init__(self, sampling="uniform"):
+        if sampling not in self.SAMPLINGS:
+            raise ValueError(f"choose_ctx_gen: not implemented sampling method {sampling!r} (one of {', '.join(self.SAMPLINGS)})")
+        self.sampling = sampling
+
+    def __eq__(self, other):
+        return isinstance(other, ContextChoice) and self.sampling == other.sampling
+
+    def __repr__(self):
+        return f"ContextChoice(sampling={self.sampling!r})"
+
+    @classmethod
+    def from_config(cls, config, split="train"):
+        """the choice of ``config.data.<split>.transform`` ('train', 'val' or 'test'), ``None`` for a list without ``choose_ctx_gen`` and
+        for a config without a ``data`` section.  Without ``data.val`` validation takes the train list's choice: the reference validates
+        on a subset of the same dataset, with the same transforms.  ``ref_key`` is ignored (it names the array whose length is the atom
+        count).  The entry after a centring entry, or twice, raises ``ValueError``."""
+        if split not in ("train", "val", "test"):
+            raise ValueError(f"split must be 'train', 'val' or 'test', not {split!r}")
+        data = (config.get("data", None) or {}) if config is not None else {}
+        section = data.get(split, None)
+        if section is None and split == "val":
+            section = data.get("train", None)
+        choice, centred = None, False
+        for t in (section or {}).get("transform", None) or []:
+            ty = t["type"]
+            if ty in ("center_pos", "center_whole_pos", "center_frame_pos"):
+                centred = True
+            elif ty == "choose_ctx_gen":
+                if centred:
+                    raise ValueError("choose_ctx_gen after the centring transform: the centre set is the complement of the chosen atoms, "
+                                     "only the order choice, then centre is known")
+                if choice is not None:
+                    raise ValueError("transform list has choose_ctx_gen twice")
+                choice = cls(t.get("sampling", "uniform"))
+        return choice
+
+
 class PocketSet:
     """P pockets packed once (CSR): what is constant across all samples and all steps of a sampling run."""
 

@@ -56,9 +56,14 @@ def build_pocket_batch(pockets, num_samples, rng, num_classes, prior_types="unif
                                        sample_streams=sample_streams)
 
 
-def load_context(raw_pockets, path):
+def load_context(raw_pockets, path, choose=None, rng=None, counter=False):
     """per-pocket context atoms [(pos [c,3] float32, atom_type [c] int64)] from the pocket dicts' ``ligand_ctx_*`` keys or from a
-    ``--context`` file (a list with one {'pos', 'atom_type'} dict or (pos, atom_type) pair per pocket); None when neither exists"""
+    ``--context`` file (a list with one {'pos', 'atom_type'} dict or (pos, atom_type) pair per pocket); None when neither exists.
+    Pockets that carry the native ligand and its decompositions instead (``ligand_pos``, ``ligand_atom_type``, ``ligand_gen_index``: a
+    list of K >= 1 index arrays, the reference's ``gen_index``) and no ``ligand_ctx_*``: the context is the complement of the
+    decomposition that ``choose`` (``priors.ContextChoice``: the config's ``choose_ctx_gen``) names -- decomposition 0 without the entry
+    (what ``remove_ligand_gen`` would leave) and under ``fix_zero``; under ``uniform`` one ``rng.integers(K)`` per pocket, in pocket
+    order, which ``counter=True`` (``--noise counter``: no shared stream) refuses."""
     def one(pos, typ):
         pos = np.asarray(pos, np.float32).reshape(-1, 3)
         typ = np.asarray(typ, np.int64).reshape(-1)
@@ -73,6 +78,27 @@ def load_context(raw_pockets, path):
         return out
     if raw_pockets is not None and all("ligand_ctx_pos" in p for p in raw_pockets):
         return [one(p["ligand_ctx_pos"], p["ligand_ctx_atom_type"]) for p in raw_pockets]
+    if raw_pockets is not None and len(raw_pockets) and all("ligand_gen_index" in p and "ligand_pos" in p and "ligand_atom_type" in p
+                                                            for p in raw_pockets):
+        uniform = choose is not None and choose.sampling == "uniform"
+        if uniform and counter:
+            raise ValueError("choose_ctx_gen with sampling 'uniform' draws from a shared stream: not available with --noise counter "
+                             "(the shipped test lists use fix_zero)")
+        if uniform and rng is None:
+            raise ValueError("choose_ctx_gen with sampling 'uniform' needs a generator (rng=)")
+        out = []
+        for k, p in enumerate(raw_pockets):
+            pos, typ = one(p["ligand_pos"], p["ligand_atom_type"])
+            decs = list(p["ligand_gen_index"])
+            if not decs:
+                raise ValueError(f"ligand_gen_index of pocket {k} is an empty list: a pocket needs at least one decomposition")
+            gen = np.asarray(decs[int(rng.integers(len(decs))) if uniform else 0]).reshape(-1).astype(np.int64)
+            if gen.size and (gen.min() < 0 or gen.max() >= typ.shape[0]):
+                raise ValueError(f"ligand_gen_index of pocket {k} has an index outside [0, {typ.shape[0]})")
+            ctx = np.ones(typ.shape[0], dtype=bool)
+            ctx[gen] = False
+            out.append((pos[ctx], typ[ctx]))
+        return out
     return None
 
 
@@ -208,7 +234,8 @@ def main(argv=None, stats=None):
         raw = torch.load(args.pockets, map_location="cpu", weights_only=False)
         pockets = [(np.asarray(p["protein_pos"], np.float32), np.asarray(p["protein_atom_feature"], np.float32),
                     np.asarray(p["protein_aa_type"], np.int64)) for p in raw]
-        context = load_context(raw, args.context)
+        context = load_context(raw, args.context, choose=priors.ContextChoice.from_config(config, "test"),
+                               rng=np.random.default_rng([args.seed, 0x63686F6F]), counter=args.noise == "counter")
     else:
         rng0 = np.random.default_rng(args.seed)
         pockets = [synthetic.make_pocket(rng0, int(rng0.integers(350, 651))) for _ in range(max(args.synthetic, 1))]

@@ -54,6 +54,17 @@ def make_context(rng, n_ctx, num_classes=13, offset=2.5, radius=1.5):
     return pos.astype(np.float32), rng.integers(0, num_classes, size=n_ctx).astype(np.int64)
 
 
+def decompositions(rng, n_lig, K):
+    """K decompositions of an ``n_lig``-atom ligand into generated and context atoms, in the shape of the reference's
+    ``data['ligand']['gen_index']`` (molecule_parser.py:442-486): a list of K ascending int64 index arrays.  Each names between one atom
+    and all but one (a ligand of one atom: that atom; of none: nothing), a random subset -- the sidechain-style interleaved kind."""
+    out = []
+    for _ in range(K):
+        size = int(rng.integers(1, n_lig)) if n_lig > 1 else n_lig
+        out.append(np.sort(rng.permutation(n_lig)[:size]).astype(np.int64))
+    return out
+
+
 def make_batch(pockets, n_lig_list, rng, num_classes=13, n_ctx_list=None, ctx_radius=3.0):
     """Collate pockets [(pos, feat, aa), ...] with fresh ligand priors.
 

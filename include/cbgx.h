@@ -305,6 +305,8 @@ int cbgx_diffsbdd_step(const float *x_den, const float *logits, const int32_t *g
 #define CBGX_NOISE_TRAIN_TYPE_NORMAL 11  /* type normal, components 0..C-1 (DiffSBDD) */
 #define CBGX_NOISE_TRAIN_PROTEIN_NORMAL 12 /* protein-coordinate augmentation of a training visit, components 0..2: counter (the atom's
                                             index inside its POCKET, 0, base + 12, 0); see cbgx_train_transform_rng */
+#define CBGX_NOISE_TRAIN_CHOOSE_CTX 13 /* which decomposition of its ligand a visit trains on: counter (0, 0, base + 13, 0), word 0; see
+                                        cbgx_train_transform_choose_rng */
 #define CBGX_NOISE_PURPOSE_STRIDE 16 /* purpose bases are multiples of this (0: a plain run) */
 /* cbgx_noise_fill: out[a][col] (caller-owned, [n_lig, cols] floats) = component col of the draw of `purpose` at `step` for ligand
  *   atom a -- normals (uniform == 0) or uniforms (uniform != 0).  stream_keys [B] uint64; lig_ptr [B+1] the ligand CSR (ligand arrays
@@ -380,6 +382,33 @@ int cbgx_train_transform_rng(const float *x_rec, const float *x_lig, const int32
                              const uint8_t *ctx, int n_graphs, int n_rec, int n_lig, float sigma, int center_mode,
                              const uint64_t *stream_keys, int purpose_base, float *x_rec_out, float *x_lig_out,
                              float *center_out, void *stream);
+/* The same behind the reference's choose_ctx_gen (select.py:21-58), in the same launch: every graph picks one of its decompositions, the
+ *   atoms that one names become the generated atoms, the others the context (ctx = !gen_flag) of the steps above.
+ *   dec_ptr [B+1] int32: graph g owns the decompositions dec_ptr[g] .. dec_ptr[g+1], K_g of them; gen_ptr [n_dec+1] int32:
+ *   decomposition d names the atoms gen_idx[gen_ptr[d] .. gen_ptr[d+1]]; gen_idx [n_idx] int32: indices INSIDE the graph's ligand.  All
+ *   three CSRs are clamped to their arrays; an index outside [0, atoms of the graph's ligand) is skipped; duplicates are harmless; an
+ *   empty decomposition (all context) and one that names every atom (no context: CBGX_CENTER_CONTEXT falls back to the whole ligand)
+ *   are both legal.
+ *   Choice k_g: choice_in[g] clamped into [0, K_g) (choice_in [B] int32, or NULL: decomposition 0 everywhere).  K_g == 0: k_g = -1 and
+ *   every ligand atom of the graph is generated.
+ *   Outputs beside those of cbgx_train_transform: gen_flag_out [n_lig] uint8 (1 generated, 0 context) and choice_out [B] int32 = k_g;
+ *   every element of every graph is written.  The noise, the centre and the shift are cbgx_train_transform's, bit for bit, on
+ *   ctx = !gen_flag_out.  All four centre modes are accepted; the flag is produced whatever the mode.
+ *   CBGX_E_INVALID as for cbgx_train_transform, and for negative n_dec / n_idx or a NULL dec_ptr, choice_out, gen_flag_out, gen_ptr or
+ *   gen_idx that has elements.
+ * cbgx_train_transform_choose_rng: choice and eps both drawn in the kernel: k_g = (uint64(w0) * K_g) >> 32 with w0 = word 0 of the call
+ *   at counter (0, 0, purpose_base + CBGX_NOISE_TRAIN_CHOOSE_CTX, 0) under stream_keys[g] (the formula of the training time at an
+ *   address no other draw uses); the protein normals as in cbgx_train_transform_rng. */
+int cbgx_train_transform_choose(const float *x_rec, const float *x_lig, const int32_t *rec_ptr, const int32_t *lig_ptr,
+                                const int32_t *dec_ptr, const int32_t *gen_ptr, const int32_t *gen_idx, const int32_t *choice_in,
+                                int n_graphs, int n_rec, int n_lig, int n_dec, int n_idx, float sigma, int center_mode,
+                                const float *eps, float *x_rec_out, float *x_lig_out, float *center_out, uint8_t *gen_flag_out,
+                                int32_t *choice_out, void *stream);
+int cbgx_train_transform_choose_rng(const float *x_rec, const float *x_lig, const int32_t *rec_ptr, const int32_t *lig_ptr,
+                                    const int32_t *dec_ptr, const int32_t *gen_ptr, const int32_t *gen_idx, int n_graphs, int n_rec,
+                                    int n_lig, int n_dec, int n_idx, float sigma, int center_mode, const uint64_t *stream_keys,
+                                    int purpose_base, float *x_rec_out, float *x_lig_out, float *center_out,
+                                    uint8_t *gen_flag_out, int32_t *choice_out, void *stream);
 int cbgx_targetdiff_epilogue_rng(const float *x_den, const float *logits, const int32_t *lig_rows, const float *x_lig,
                                  const float *c_lig, const uint8_t *gen_lig, int n_lig, int num_classes, int t,
                                  int num_timesteps, const float *const *tables, const uint64_t *stream_keys,
