@@ -404,8 +404,7 @@ int cbgx_h2x_stack_forward(const float* packed, int num_layers, const float* x, 
     NodeList src{nullptr, nullptr};
     if (g_edge_impl != 1) {
         HIP_TRY(launch_mark_seed(gen_flag, gen_flag, n_nodes, w.fa1, s));
-        HIP_TRY(launch_mark_nbr(w.act.rows, w.act.count, n_nodes, w.nbr, w.deg, w.fa1, s));
-        HIP_TRY(launch_build_active(w.fa1, n_nodes, w.A1.rows, w.A1.count, s));
+        HIP_TRY(walk_receptive_field(w.fa1, w.act, w.nbr, w.deg, n_nodes, {w.A1}, s));
         src = w.A1;
     }
     const float* xc = x;

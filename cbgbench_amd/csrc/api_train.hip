@@ -2,10 +2,10 @@
 // attention blocks (what the parity tests call) and of the whole denoiser.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
-
 #include <cstdlib>
 
 #include "../../include/cbgx.h"
@@ -87,93 +87,78 @@ static Tape carve_tape(void* base, int n, int L) {
 }
 
 // ---- backward workspace -----------------------------------------------------------------------------------
-struct TrainWs {
-    float *P, *Qt, *Gt, *T, *S, *gb, *sw, *qs, *dqb, *zb, *dP, *gh, *gx[2], *de_w, *tmp, *partial, *folded, *qln, *nk;
+// the per-block buffers: two sets, consecutive blocks alternate between them (BlockOverlap)
+struct BlockSet {
+    float *T, *S, *sw, *qs, *dqb, *zb, *dP;
     // an attention block's three slab sets live side by side (edge slabs in `partial`), so that ONE fold launch and ONE
     // reduce-and-store launch per block serve all of them
-    float *partial_node, *partial_wgrad, *folded_node, *folded_wgrad;
-    int *act, *act_count;
+    float *partial, *folded, *partial_node, *partial_wgrad, *folded_node, *folded_wgrad;
+};
+
+struct TrainWs {
+    float *P, *Qt, *Gt, *gb, *gh, *gx[2], *de_w, *tmp, *qln, *nk;
+    BlockSet set[2];
+    NodeList act;         // gen_flag rows (h2x work list)
     uint8_t* mask;        // receptive field of the loss, walked backwards (see cbgx_unitransformer_backward)
-    int *rf_list[2], *rf_count;
+    NodeList A1, A2, A3;  // receptive-field lists, one hop apart
+    // The third list has two lives: A3 of the pruned taped forward, and in the backward the classifier head's row list -- the rows with
+    // lig_flag (or the support of grad_logits), which the head's backward walks when the loss reads ligand rows only
+    NodeList head_rows() const { return A3; }
+    float *gate_partial, *gate_folded;     // the gate backward's own slabs: it runs before the auxiliary stream is joined (round 6)
     // round 6, x2h edge backward without neighbour-row atomics (train_scatter.hip, CBGX_BX_EDGE_ROWS=1): one row per edge, and the
     // incoming-edge lists of every source node (built once per backward call)
-    float *gate_partial, *gate_folded;     // the gate backward's own slabs: it runs before the auxiliary stream is joined (round 6)
     float* dE;            // [N][32][256]
     int *rin_cnt, *rin_ptr, *rin_tmp, *rin_edge;
-    int* lig_list;        // rows with lig_flag (count: rf_count + 32): the classifier head's backward walks it when the loss reads ligand rows only
-    // second set of the per-block buffers (round 5): the weight-gradient reductions of a block run on an auxiliary stream while the
-    // caller's stream is already in the next block, so consecutive blocks alternate between two sets (attention_block_backward)
-    float *T2, *S2, *sw2, *qs2, *dqb2, *zb2, *dP2, *partial2, *folded2, *partial_node2, *partial_wgrad2, *folded_node2, *folded_wgrad2;
-    size_t partial_floats;
     size_t total;
 };
 
-static size_t partial_floats_needed() {
-    size_t a = (size_t)EDGE_GRID * PB_SIZE;
-    size_t b = (size_t)NODE_GRID * NS_SIZE;
-    size_t c = (size_t)MAX_SPLITS * H * PROW;
-    size_t d = (size_t)GATE_GRID * GB_SIZE;
-    size_t m = a > b ? a : b;
-    m = m > c ? m : c;
-    return m > d ? m : d;
+static BlockSet carve_block_set(Carver& c, size_t N) {
+    BlockSet b;
+    for (float** p : {&b.T, &b.S}) *p = c.take<float>(N * HEADS * H * 4);
+    b.sw = c.take<float>(N * HEADS * 4);
+    for (float** p : {&b.qs, &b.dqb, &b.zb}) *p = c.take<float>(N * H * 4);
+    b.dP = c.take<float>(N * PROW * 4 + 256);      // + the x2h edge backward's work counters: zeroed by the same fill
+    // (the largest of the slab sets that borrow it: edge kernel, node-level reductions, split products, gate)
+    b.partial = c.take<float>(4 * std::max({(size_t)EDGE_GRID * PB_SIZE, (size_t)NODE_GRID * NS_SIZE, (size_t)MAX_SPLITS * H * PROW,
+                                            (size_t)GATE_GRID * GB_SIZE}));
+    b.folded = c.take<float>((size_t)FOLD * H * PROW * 4);
+    b.partial_node = c.take<float>((size_t)NODE_GRID * NS_SIZE * 4);
+    b.partial_wgrad = c.take<float>((size_t)MAX_SPLITS * H * PROW * 4);
+    b.folded_node = c.take<float>((size_t)FOLD * NS_SIZE * 4);
+    b.folded_wgrad = c.take<float>((size_t)FOLD * H * PROW * 4);
+    return b;
 }
 
+// The only place that knows where a list's count lives: 64 bytes apart (a counter word is hammered by returning atomics).
 static TrainWs carve_train(void* base, int n) {
     TrainWs w;
     Carver c(base);
     const size_t N = (size_t)(n > 0 ? n : 1);
     w.P = c.take<float>(N * PROW * 4);
-    w.Qt = c.take<float>(N * HEADS * H * 4);
-    w.Gt = c.take<float>(N * HEADS * H * 4);
-    w.T = c.take<float>(N * HEADS * H * 4);
-    w.S = c.take<float>(N * HEADS * H * 4);
+    for (float** p : {&w.Qt, &w.Gt}) *p = c.take<float>(N * HEADS * H * 4);
     w.gb = c.take<float>(N * HEADS * 4);
-    w.sw = c.take<float>(N * HEADS * 4);
-    w.qs = c.take<float>(N * H * 4);
-    w.dqb = c.take<float>(N * H * 4);
-    w.zb = c.take<float>(N * H * 4);
-    w.dP = c.take<float>(N * PROW * 4 + 256);      // + the x2h edge backward's work counters: zeroed by the same fill
+    w.set[0] = carve_block_set(c, N);
     w.gh = c.take<float>(N * H * 4);
-    w.gx[0] = c.take<float>(N * 3 * 4);
-    w.gx[1] = c.take<float>(N * 3 * 4);
+    for (float*& g : w.gx) g = c.take<float>(N * 3 * 4);
     w.de_w = c.take<float>(N * KNN * 4);
     w.tmp = c.take<float>(N * H * 4);
-    w.act = c.take<int>(N * 4);
-    w.act_count = c.take<int>(256);
+    w.act.rows = c.take<int>(N * 4);
+    w.act.count = c.take<int>(256);
     w.mask = c.take<uint8_t>(N);
-    w.rf_list[0] = c.take<int>(N * 4);
-    w.rf_list[1] = c.take<int>(N * 4);
-    w.rf_count = c.take<int>(256);
-    w.lig_list = c.take<int>(N * 4);
-    w.partial_floats = partial_floats_needed();
-    w.partial = c.take<float>(w.partial_floats * 4);
-    w.folded = c.take<float>((size_t)FOLD * H * PROW * 4);
+    w.A1.rows = c.take<int>(N * 4);
+    w.A2.rows = c.take<int>(N * 4);
+    int* counts = c.take<int>(256);
+    w.A1.count = counts; w.A2.count = counts + 16; w.A3.count = counts + 32;
+    w.A3.rows = c.take<int>(N * 4);
     w.qln = c.take<float>((size_t)QLN_SLOTS * 2 * H * 4);
-    w.partial_node = c.take<float>((size_t)NODE_GRID * NS_SIZE * 4);
-    w.partial_wgrad = c.take<float>((size_t)MAX_SPLITS * H * PROW * 4);
-    w.folded_node = c.take<float>((size_t)FOLD * NS_SIZE * 4);
-    w.folded_wgrad = c.take<float>((size_t)FOLD * H * PROW * 4);
     w.nk = c.take<float>(BX_NK_FLOATS * 4);     // x2h edge backward: the key path of every wave in flight, parked between two phases
     w.gate_partial = c.take<float>((size_t)GATE_GRID * GB_SIZE * 4);
     w.gate_folded = c.take<float>((size_t)FOLD * GB_SIZE * 4);
     w.dE = c.take<float>(N * KNN * 2 * H * 4);
     w.rin_cnt = c.take<int>(N * 4);
     w.rin_ptr = c.take<int>((N + 1) * 4);
-    w.rin_tmp = c.take<int>(N * KNN * 4);
-    w.rin_edge = c.take<int>(N * KNN * 4);
-    w.T2 = c.take<float>(N * HEADS * H * 4);
-    w.S2 = c.take<float>(N * HEADS * H * 4);
-    w.sw2 = c.take<float>(N * HEADS * 4);
-    w.qs2 = c.take<float>(N * H * 4);
-    w.dqb2 = c.take<float>(N * H * 4);
-    w.zb2 = c.take<float>(N * H * 4);
-    w.dP2 = c.take<float>(N * PROW * 4 + 256);
-    w.partial2 = c.take<float>(w.partial_floats * 4);
-    w.folded2 = c.take<float>((size_t)FOLD * H * PROW * 4);
-    w.partial_node2 = c.take<float>((size_t)NODE_GRID * NS_SIZE * 4);
-    w.partial_wgrad2 = c.take<float>((size_t)MAX_SPLITS * H * PROW * 4);
-    w.folded_node2 = c.take<float>((size_t)FOLD * NS_SIZE * 4);
-    w.folded_wgrad2 = c.take<float>((size_t)FOLD * H * PROW * 4);
+    for (int** p : {&w.rin_tmp, &w.rin_edge}) *p = c.take<int>(N * KNN * 4);
+    w.set[1] = carve_block_set(c, N);
     w.total = c.off;
     return w;
 }
@@ -194,20 +179,15 @@ static inline int splits_for(int n) {
     return s < 1 ? 1 : (s > MAX_SPLITS ? MAX_SPLITS : s);
 }
 
-#define RS(src, nsl, stride, ld, rows, cols, dst, dld, tr) \
-    HIP_TRY(launch_reduce_store(src, nsl, stride, ld, rows, cols, dst, dld, tr, s))
-
-// two-level reduction of `n_slabs` partial slabs of `size` floats: returns the FOLD-slab buffer (stride = size) through
-// *out / *n_out, or the input itself when it is already small
-static int fold_slabs(const float* src, int n_slabs, size_t stride, int size, TrainWs& w, const float** out, int* n_out,
-                      size_t* stride_out, hipStream_t s) {
-    if (n_slabs <= FOLD) { *out = src; *n_out = n_slabs; *stride_out = stride; return CBGX_OK; }
-    HIP_TRY(launch_slab_fold(src, n_slabs, stride, size, FOLD, w.folded, s));
-    *out = w.folded; *n_out = FOLD; *stride_out = (size_t)size;
+// two-level reduction of `n_slabs` partial slabs of `size` floats: what reduce_store then reads is the FOLD-slab buffer `folded`
+// (stride = size), or the input itself when it is already small
+struct Slabs { const float* p; int n; size_t stride; };
+static int fold_slabs(const float* src, int n_slabs, size_t stride, int size, float* folded, Slabs& out, hipStream_t s) {
+    if (n_slabs <= FOLD) { out = Slabs{src, n_slabs, stride}; return CBGX_OK; }
+    HIP_TRY(launch_slab_fold(src, n_slabs, stride, size, FOLD, folded, s));
+    out = Slabs{folded, FOLD, (size_t)size};
     return CBGX_OK;
 }
-#define FOLDED(src, nsl, stride, size) \
-    const float* fz; int fn; size_t fs; RC_TRY(fold_slabs(src, nsl, stride, size, w, &fz, &fn, &fs, s))
 
 // Backward of one attention block.
 //   x2h: g_out = dL/dh_out [N,128];   h2x: g_out = dL/dx_out [N,3] (only gen rows matter; rows = gen list)
@@ -235,29 +215,43 @@ struct BlockOverlap {
     }
 };
 
-static int attention_block_backward(bool x2h, const float* att, const float* x, const float* h_in, const float* g_out,
-                                    const int32_t* nbr, const int32_t* deg, const uint8_t* lig, const float* e_w,
-                                    const int* rows, const int* n_rows, int n, TrainWs& w_all, float* gh, float* dx,
-                                    float* de_w, float* const* grads, hipStream_t s, const float* P_saved = nullptr,
-                                    const float* Qt_saved = nullptr, float* qln = nullptr, const float* gh_src = nullptr,
-                                    const int* dp_rows = nullptr, const int* dp_n_rows = nullptr, BlockOverlap* ov = nullptr,
-                                    bool rin_ready = false, const float* dx_init = nullptr) {
-    // `dx_init` (h2x blocks of a layer loop): dx = dx_init (the identity path of x_{l+1} = x_l + ...) before the block adds to it
-    TrainWs w = w_all;      // this block's view of the workspace: the per-block buffers of its set
+struct BlockArgs {
+    // the block: x2h or h2x, its packed weights, its inputs as the forward saw them, the gradient of its output, the graph
+    bool x2h = false;
+    const float *att = nullptr, *x = nullptr, *h_in = nullptr, *g_out = nullptr, *e_w = nullptr;
+    const int32_t *nbr = nullptr, *deg = nullptr;
+    const uint8_t* lig = nullptr;
+    int n = 0;
+    NodeList rows{nullptr, nullptr};       // destination rows of the block ({NULL, NULL}: every row)
+    // (h2x blocks) a list that contains every row of dP this block can touch (the listed nodes and their neighbours); the dense
+    // products and column sums over dP then walk the list instead of all N rows
+    NodeList dp_rows{nullptr, nullptr};
+    // the outputs
+    float *gh = nullptr, *dx = nullptr, *de_w = nullptr;
+    float* const* grads = nullptr;
+    // gh = gh_src + (this block's contribution) instead of gh += (the caller then needs no snapshot of g_out == gh_src)
+    const float* gh_src = nullptr;
+    // (h2x blocks of a layer loop) dx = dx_init (the identity path of x_{l+1} = x_l + ...) before the block adds to it
+    const float* dx_init = nullptr;
+    const float *P_saved = nullptr, *Qt_saved = nullptr;    // the forward's own node stage from the tape (without both: recomputed)
+    float* qln = nullptr;       // [2][128] zeroed accumulator of the query LayerNorm's affine gradients (nullptr: w.qln, zeroed here)
+    BlockOverlap* ov = nullptr;
+    bool rin_ready = false;     // the caller has built the incoming-edge lists (w.rin_ptr / rin_edge): the edge-row mode may run
+};
+
+static int attention_block_backward(const BlockArgs& a, TrainWs& w, hipStream_t s) {
+    const bool x2h = a.x2h;
+    const int n = a.n;
+    BlockOverlap* const ov = a.ov;
+    const int *rows = a.rows.rows, *n_rows = a.rows.count, *dp_rows = a.dp_rows.rows, *dp_n_rows = a.dp_rows.count;
+    const float* dx_init = a.dx_init;
+    float* qln = a.qln;
     const int set = (ov && ov->aux) ? ov->next_set : 0;
-    if (set) {
-        w.T = w_all.T2; w.S = w_all.S2; w.sw = w_all.sw2; w.qs = w_all.qs2; w.dqb = w_all.dqb2; w.zb = w_all.zb2; w.dP = w_all.dP2;
-        w.partial = w_all.partial2; w.folded = w_all.folded2; w.partial_node = w_all.partial_node2;
-        w.partial_wgrad = w_all.partial_wgrad2; w.folded_node = w_all.folded_node2; w.folded_wgrad = w_all.folded_wgrad2;
-    }
+    BlockSet& b = w.set[set];      // this block's per-block buffers
     if (ov && ov->aux) {
         if (ov->used[set]) HIP_TRY(hipStreamWaitEvent(s, ov->aux->done[set], 0));    // the set's previous user has finished with it
         ov->next_set = set ^ 1;
     }
-    // `dp_rows` / `dp_n_rows` (h2x blocks): a device-side list that contains every row of dP this block can touch (the listed nodes
-    // and their neighbours); the dense products and column sums over dP then walk the list instead of all N rows
-    // `qln` [2][128]: zeroed accumulator of the query LayerNorm's affine gradients (nullptr: w.qln, zeroed here);
-    // `gh_src`: gh = gh_src + (this block's contribution) instead of gh += (the caller then needs no snapshot of g_out == gh_src)
     // x2h blocks run the one-wave-per-node backward (8 nodes in flight per workgroup); h2x blocks and, in libcbgx_xcheck.so,
     // cbgx_debug_set_edge_kernel(2) the second-generation workgroup-per-node kernel
     const bool gen3 = x2h && g_edge_impl == 0;
@@ -273,33 +267,33 @@ static int attention_block_backward(bool x2h, const float* att, const float* x, 
     // for the listed rows) with the MFMA edge backward, the first-generation ones with the VALU cross-check kernel
     // (skipped when the taped forward left its own P / Qt: P_saved, Qt_saved)
     const bool mfma = g_edge_impl != 1;
-    const bool saved = P_saved && Qt_saved;
-    const float* Pn = saved ? P_saved : w.P;
-    const float* Qn = saved ? Qt_saved : w.Qt;
+    const bool saved = a.P_saved && a.Qt_saved;
+    const float* Pn = saved ? a.P_saved : w.P;
+    const float* Qn = saved ? a.Qt_saved : w.Qt;
     if (!saved) {
 #ifdef CBGX_XCHECK
         if (!mfma) {
-            HIP_TRY(launch_node_gemm_v1(h_in, H, att + A_WN, att + A_BN, w.P, PROW, n, PROW, 0, s, nullptr, nullptr));
-            HIP_TRY(launch_node_query_v1(att, w.P, w.Qt, n, s));
+            HIP_TRY(launch_node_gemm_v1(a.h_in, H, a.att + A_WN, a.att + A_BN, w.P, PROW, n, PROW, 0, s, nullptr, nullptr));
+            HIP_TRY(launch_node_query_v1(a.att, w.P, w.Qt, n, s));
         } else
 #endif
-            HIP_TRY(launch_node_mfma(att, h_in, lig, n, w.P, w.qs, w.Qt, rows, n_rows, nullptr, nullptr, s, x2h));
+            HIP_TRY(launch_node_mfma(a.att, a.h_in, a.lig, n, w.P, b.qs, w.Qt, rows, n_rows, nullptr, nullptr, s, x2h));
     }
-    if (x2h) HIP_TRY(launch_fold_grad(att, g_out, n, w.Gt, w.gb, s, mfma ? rows : nullptr, mfma ? n_rows : nullptr));      // (a listed block reads listed rows' folds only)
+    if (x2h) HIP_TRY(launch_fold_grad(a.att, a.g_out, n, w.Gt, w.gb, s, mfma ? rows : nullptr, mfma ? n_rows : nullptr));      // (a listed block reads listed rows' folds only)
     // Edge rows (CBGX_BX_EDGE_ROWS=1, round 6): a full launch of the one-wave-per-node kernel writes d pre of every edge to the edge's own
     // row of w.dE and launch_edge_rows_reduce gathers the rows of every source node in a fixed order -- no atomics on dP.  Every column
     // of dP then has exactly one writer (PD: the edge kernel's plain stores, PS: the gather, q hidden: the query backward), so only the
-    // work counters behind it are zeroed.  `rin_ready`: the caller has built the incoming-edge lists (w_all.rin_ptr / rin_edge).
-    const bool er = gen3 && !rows && rin_ready;
-    if (er) HIP_TRY(hipMemsetAsync(w.dP + (size_t)n * PROW, 0, 256, s));
+    // work counters behind it are zeroed.
+    const bool er = gen3 && !rows && a.rin_ready;
+    if (er) HIP_TRY(hipMemsetAsync(b.dP + (size_t)n * PROW, 0, 256, s));
     else if (!x2h && dp_rows && mfma && ov && ov->aux && env_on("CBGX_TRAIN_ZERO_ROWS"))
         // h2x block in the layer loop: every reader of dP walks `dp_rows`, so only those rows are zeroed (a fill of all N rows was 42 MB
         // per block; +0.4 % on the training line, profiles/ab_train_r06r.log)
     {
-        HIP_TRY(launch_zero_rows(w.dP, PROW, dp_rows, dp_n_rows, n, s, dx_init ? dx : nullptr, dx_init, n * 3));
+        HIP_TRY(launch_zero_rows(b.dP, PROW, dp_rows, dp_n_rows, n, s, dx_init ? a.dx : nullptr, dx_init, n * 3));
         dx_init = nullptr;
-    } else HIP_TRY(hipMemsetAsync(w.dP, 0, (size_t)n * PROW * sizeof(float) + 256, s));     // (and the work counters behind it)
-    if (dx_init) HIP_TRY(hipMemcpyAsync(dx, dx_init, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    } else HIP_TRY(hipMemsetAsync(b.dP, 0, (size_t)n * PROW * sizeof(float) + 256, s));     // (and the work counters behind it)
+    if (dx_init) HIP_TRY(hipMemcpyAsync(a.dx, dx_init, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (!qln) {
         qln = w.qln;
         HIP_TRY(hipMemsetAsync(qln, 0, 2 * H * sizeof(float), s));
@@ -308,21 +302,21 @@ static int attention_block_backward(bool x2h, const float* att, const float* x, 
     // on-device cross-check
 #ifdef CBGX_XCHECK
     if (!mfma)
-        HIP_TRY(launch_edge_backward(x2h, att, x, Pn, Qn, w.Gt, w.gb, g_out, nbr, deg, lig, e_w, rows, n_rows, n, w.T,
-                                     w.S, w.sw, w.dP, dx, de_w, w.partial, eg, s));
+        HIP_TRY(launch_edge_backward(x2h, a.att, a.x, Pn, Qn, w.Gt, w.gb, a.g_out, a.nbr, a.deg, a.lig, a.e_w, rows, n_rows, n, b.T,
+                                     b.S, b.sw, b.dP, a.dx, a.de_w, b.partial, eg, s));
     else
 #endif
     if (gen3) {
-        HIP_TRY(launch_edge_backward_x2h(att, x, Pn, Qn, w.Gt, w.gb, nbr, deg, lig, e_w, rows, n_rows, n, w.T, w.S, w.sw,
-                                         w.dP, dx, de_w, w.partial, w.nk, reinterpret_cast<int*>(w.dP + (size_t)n * PROW), eg, s,
+        HIP_TRY(launch_edge_backward_x2h(a.att, a.x, Pn, Qn, w.Gt, w.gb, a.nbr, a.deg, a.lig, a.e_w, rows, n_rows, n, b.T, b.S, b.sw,
+                                         b.dP, a.dx, a.de_w, b.partial, w.nk, reinterpret_cast<int*>(b.dP + (size_t)n * PROW), eg, s,
                                          er ? w.dE : nullptr));
-        if (er) HIP_TRY(launch_edge_rows_reduce(w.dE, w.rin_ptr, w.rin_edge, n, w.dP, s));
+        if (er) HIP_TRY(launch_edge_rows_reduce(w.dE, w.rin_ptr, w.rin_edge, n, b.dP, s));
     } else
-        HIP_TRY(launch_edge_backward_mfma(x2h, att, x, Pn, Qn, w.Gt, w.gb, g_out, nbr, deg, lig, e_w, rows, n_rows, n,
-                                          w.T, w.S, w.sw, w.dP, dx, de_w, w.partial, eg, s, 1));
-    float *k0w = grads[0], *k0b = grads[1], *kg = grads[2], *kb = grads[3], *k1w = grads[4], *k1b = grads[5];
-    float *v0w = grads[6], *v0b = grads[7], *vg = grads[8], *vb = grads[9], *v1w = grads[10], *v1b = grads[11];
-    float *q0w = grads[12], *q0b = grads[13], *qg = grads[14], *qb = grads[15], *q1w = grads[16], *q1b = grads[17];
+        HIP_TRY(launch_edge_backward_mfma(x2h, a.att, a.x, Pn, Qn, w.Gt, w.gb, a.g_out, a.nbr, a.deg, a.lig, a.e_w, rows, n_rows, n,
+                                          b.T, b.S, b.sw, b.dP, a.dx, a.de_w, b.partial, eg, s, 1));
+    float *k0w = a.grads[0], *k0b = a.grads[1], *kg = a.grads[2], *kb = a.grads[3], *k1w = a.grads[4], *k1b = a.grads[5];
+    float *v0w = a.grads[6], *v0b = a.grads[7], *vg = a.grads[8], *vb = a.grads[9], *v1w = a.grads[10], *v1b = a.grads[11];
+    float *q0w = a.grads[12], *q0b = a.grads[13], *qg = a.grads[14], *qb = a.grads[15], *q1w = a.grads[16], *q1b = a.grads[17];
     // The block's three slab sets (edge kernel, node-level reductions, dense projection) are reduced at its end: one first-level
     // fold launch for the sets with more than FOLD slabs, one reduce-and-store launch for every gradient tensor of the block
     // (six launches and three 512-byte fills per block before; the sums are the same, slab by slab).
@@ -343,7 +337,7 @@ static int attention_block_backward(bool x2h, const float* att, const float* x, 
         fz = dst; fn = FOLD; fs = (size_t)size;
     };
     {   // edge-indexed weight gradients: type / rbf columns of the first Linears, LayerNorm affine
-        folded(w.partial, eg, PB_SIZE, PB_SIZE, w.folded);
+        folded(b.partial, eg, PB_SIZE, PB_SIZE, b.folded);
         piece(fz + PB_WT, fn, fs, 2 * H, NT, H, k0w, KV_IN, 1);
         piece(fz + PB_WT + H, fn, fs, 2 * H, NT, H, v0w, KV_IN, 1);
         piece(fz + PB_WR, fn, fs, 2 * H, NT * G, H, k0w + NT, KV_IN, 1);
@@ -361,25 +355,30 @@ static int attention_block_backward(bool x2h, const float* att, const float* x, 
     {
         const int tiles = (n + 15) / 16, qgrid = tiles < 1024 ? tiles : 1024;   // 25 KB of LDS, four waves per SIMD: four workgroups per CU
 #ifdef CBGX_XCHECK
-        if (!mfma) HIP_TRY(launch_q_backward(att, Pn, w.T, rows, n_rows, n, w.qs, w.dqb, w.zb, w.dP, qln, qgrid, s));
+        if (!mfma) HIP_TRY(launch_q_backward(a.att, Pn, b.T, rows, n_rows, n, b.qs, b.dqb, b.zb, b.dP, qln, qgrid, s));
         else
 #endif
-            HIP_TRY(launch_q_backward_mfma(att, Pn, w.T, rows, n_rows, n, w.qs, w.dqb, w.zb, w.dP, qln, qgrid, s));
+            HIP_TRY(launch_q_backward_mfma(a.att, Pn, b.T, rows, n_rows, n, b.qs, b.dqb, b.zb, b.dP, qln, qgrid, s));
     }
     // ---- from here to the reduce-and-store: weight gradients only.  With `ov` they go to the auxiliary stream (`s` is shadowed) and
     // dgrad -- what the next block waits for -- is issued on the caller's stream first.
     hipStream_t s_main = s;
     const bool deferred = ov && ov->aux;
+    // dL/dh_in = (gh_src or gh itself) + dP Wn^T
+    auto dgrad = [&](hipStream_t st) -> int {
+        if (mfma)
+            HIP_TRY(launch_dgrad_mfma(b.dP, PROW, a.att + A_WN, PROW, a.gh, H, n, PROW, 1, st, a.gh_src, a.gh_src ? nullptr : dp_rows,
+                                      a.gh_src ? nullptr : dp_n_rows));
+        else {
+            if (a.gh_src && a.gh_src != a.gh) HIP_TRY(hipMemcpyAsync(a.gh, a.gh_src, (size_t)n * H * 4, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(launch_sgemm(false, true, b.dP, PROW, a.att + A_WN, PROW, a.gh, H, n, H, PROW, 1, 0, 1, st));
+        }
+        return CBGX_OK;
+    };
     if (deferred) {
         HIP_TRY(hipEventRecord(ov->aux->fork, s_main));
         HIP_TRY(hipStreamWaitEvent(ov->aux->s, ov->aux->fork, 0));
-        if (mfma)
-            HIP_TRY(launch_dgrad_mfma(w.dP, PROW, att + A_WN, PROW, gh, H, n, PROW, 1, s_main, gh_src, gh_src ? nullptr : dp_rows,
-                                      gh_src ? nullptr : dp_n_rows));
-        else {
-            if (gh_src && gh_src != gh) HIP_TRY(hipMemcpyAsync(gh, gh_src, (size_t)n * H * 4, hipMemcpyDeviceToDevice, s_main));
-            HIP_TRY(launch_sgemm(false, true, w.dP, PROW, att + A_WN, PROW, gh, H, n, H, PROW, 1, 0, 1, s_main));
-        }
+        RC_TRY(dgrad(s_main));
         s = ov->aux->s;
     }
     // node-level reductions, all into one slab per workgroup (NS_* layout), folded and scattered once:
@@ -390,17 +389,17 @@ static int attention_block_backward(bool x2h, const float* att, const float* x, 
 #else
     const auto outer = launch_outer_accum_mfma;
 #endif
-    float* pn = w.partial_node;
-    HIP_TRY(outer(true, w.qs, w.T, rows, n_rows, n, pn + NS_WBK, NS_SIZE, ng, s));
+    float* pn = b.partial_node;
+    HIP_TRY(outer(true, b.qs, b.T, rows, n_rows, n, pn + NS_WBK, NS_SIZE, ng, s));
     if (x2h) {
-        HIP_TRY(outer(true, g_out, w.S, rows, n_rows, n, pn + NS_WBV, NS_SIZE, ng, s));
-        HIP_TRY(launch_colsum(g_out, H, H, w.sw, rows, n_rows, n, pn + NS_V1B, NS_SIZE, ng, s));
+        HIP_TRY(outer(true, a.g_out, b.S, rows, n_rows, n, pn + NS_WBV, NS_SIZE, ng, s));
+        HIP_TRY(launch_colsum(a.g_out, H, H, b.sw, rows, n_rows, n, pn + NS_V1B, NS_SIZE, ng, s));
     }
-    HIP_TRY(outer(false, w.dqb, w.zb, rows, n_rows, n, pn + NS_WQ1, NS_SIZE, ng, s));
-    HIP_TRY(launch_colsum(w.dqb, H, H, nullptr, rows, n_rows, n, pn + NS_Q1B, NS_SIZE, ng, s));
-    HIP_TRY(launch_colsum(w.dP, PROW, PROW, nullptr, dp_rows, dp_n_rows, n, pn + NS_DP, NS_SIZE, ng, s));
+    HIP_TRY(outer(false, b.dqb, b.zb, rows, n_rows, n, pn + NS_WQ1, NS_SIZE, ng, s));
+    HIP_TRY(launch_colsum(b.dqb, H, H, nullptr, rows, n_rows, n, pn + NS_Q1B, NS_SIZE, ng, s));
+    HIP_TRY(launch_colsum(b.dP, PROW, PROW, nullptr, dp_rows, dp_n_rows, n, pn + NS_DP, NS_SIZE, ng, s));
     {
-        folded(pn, ng, NS_SIZE, NS_SIZE, w.folded_node);
+        folded(pn, ng, NS_SIZE, NS_SIZE, b.folded_node);
         piece(fz + NS_WBK, fn, fs, H, H, H, k1w, H, 0);
         piece(fz + NS_WQ1, fn, fs, H, H, H, q1w, H, 0);
         piece(fz + NS_Q1B, fn, fs, H, 1, H, q1b, H, 0);
@@ -418,12 +417,12 @@ static int attention_block_backward(bool x2h, const float* att, const float* x, 
     // dense projection: dWn[k][n] = sum_i h_in[i][k] dP[i][n]  -> h_dst / h_src / q columns of the first Linears
     const int sp = mfma ? wgrad_groups(n) : (splits_for(n) > 32 ? 32 : splits_for(n));
     if (mfma)
-        HIP_TRY(launch_wgrad_mfma(h_in, H, w.dP, PROW, n, PROW / H, w.partial_wgrad, PROW, (size_t)H * PROW, sp, s, dp_rows,
+        HIP_TRY(launch_wgrad_mfma(a.h_in, H, b.dP, PROW, n, PROW / H, b.partial_wgrad, PROW, (size_t)H * PROW, sp, s, dp_rows,
                                   dp_n_rows));
     else
-        HIP_TRY(launch_sgemm(true, false, h_in, H, w.dP, PROW, w.partial_wgrad, PROW, H, PROW, n, sp, (size_t)H * PROW, 0, s));
+        HIP_TRY(launch_sgemm(true, false, a.h_in, H, b.dP, PROW, b.partial_wgrad, PROW, H, PROW, n, sp, (size_t)H * PROW, 0, s));
     {
-        folded(w.partial_wgrad, sp, (size_t)H * PROW, H * PROW, w.folded_wgrad);
+        folded(b.partial_wgrad, sp, (size_t)H * PROW, H * PROW, b.folded_wgrad);
         piece(fz + 0 * H, fn, fs, PROW, H, H, k0w + NT + NT * G, KV_IN, 1);
         piece(fz + 1 * H, fn, fs, PROW, H, H, v0w + NT + NT * G, KV_IN, 1);
         piece(fz + 2 * H, fn, fs, PROW, H, H, k0w + NT + NT * G + H, KV_IN, 1);
@@ -438,32 +437,66 @@ static int attention_block_backward(bool x2h, const float* att, const float* x, 
         ov->used[set] = true;
         return CBGX_OK;       // (dgrad was issued above, on the caller's stream)
     }
-    // dL/dh_in = (gh_src or gh itself) + dP Wn^T
-    if (mfma)
-        HIP_TRY(launch_dgrad_mfma(w.dP, PROW, att + A_WN, PROW, gh, H, n, PROW, 1, s, gh_src, gh_src ? nullptr : dp_rows,
-                                  gh_src ? nullptr : dp_n_rows));
-    else {
-        if (gh_src && gh_src != gh) HIP_TRY(hipMemcpyAsync(gh, gh_src, (size_t)n * H * 4, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(launch_sgemm(false, true, w.dP, PROW, att + A_WN, PROW, gh, H, n, H, PROW, 1, 0, 1, s));
-    }
-    return CBGX_OK;
+    return dgrad(s);
 }
 
 // backward of the distance gate: weight gradients from the accumulated dL/de_w, on the workspace's gate slabs (no buffer of a block set);
 // grad_x != NULL: the gate's coordinate gradient is also ADDED to grad_x (the kernel's DX variant)
-static int gate_backward(const float* packed, const float* xs, const int32_t* nbr, const int32_t* deg, int n, TrainWs& w_all,
-                         float* const* grads, hipStream_t s, const int* rows = nullptr, const int* n_rows = nullptr,
-                         float* grad_x = nullptr) {
-    TrainWs w = w_all;
-    w.folded = w_all.gate_folded;
-    HIP_TRY(launch_gate_backward_mfma(packed, xs, nbr, deg, n, w.de_w, w.gate_partial, GATE_GRID, s, rows, n_rows, grad_x));
-    FOLDED(w.gate_partial, GATE_GRID, GB_SIZE, GB_SIZE);
-    RS(fz + GB_W1, fn, fs, G, GH, G, grads[0], G, 0);
-    RS(fz + GB_B1, fn, fs, GH, 1, GH, grads[1], GH, 0);
-    RS(fz + GB_LNG, fn, fs, GH, 1, GH, grads[2], GH, 0);
-    RS(fz + GB_LNB, fn, fs, GH, 1, GH, grads[3], GH, 0);
-    RS(fz + GB_W2, fn, fs, GH, 1, GH, grads[4], GH, 0);
-    RS(fz + GB_B2, fn, fs, 1, 1, 1, grads[5], 1, 0);
+static int gate_backward(const float* packed, const float* xs, const int32_t* nbr, const int32_t* deg, int n, TrainWs& w,
+                         float* const* grads, hipStream_t s, NodeList rows, float* grad_x) {
+    HIP_TRY(launch_gate_backward_mfma(packed, xs, nbr, deg, n, w.de_w, w.gate_partial, GATE_GRID, s, rows.rows, rows.count, grad_x));
+    Slabs f;
+    RC_TRY(fold_slabs(w.gate_partial, GATE_GRID, GB_SIZE, GB_SIZE, w.gate_folded, f, s));
+    auto rs = [&](int off, int ld, int rws, int cls, float* dst) { return launch_reduce_store(f.p + off, f.n, f.stride, ld, rws, cls, dst, ld, 0, s); };
+    HIP_TRY(rs(GB_W1, G, GH, G, grads[0]));
+    HIP_TRY(rs(GB_B1, GH, 1, GH, grads[1]));
+    HIP_TRY(rs(GB_LNG, GH, 1, GH, grads[2]));
+    HIP_TRY(rs(GB_LNB, GH, 1, GH, grads[3]));
+    HIP_TRY(rs(GB_W2, GH, 1, GH, grads[4]));
+    HIP_TRY(rs(GB_B2, 1, 1, 1, grads[5]));
+    return CBGX_OK;
+}
+
+// Backward of the classifier head (Linear, shifted softplus, Linear on h_L = `hl`; `c`: its packed weights): cg[0..3] = dW0, db0, dW1,
+// db1 are overwritten and w.gh += dL/dh_L.  `rows`: rows outside it have a zero grad_logits -- the ligand rows by the caller's promise
+// behind grad_h_out == NULL (include/cbgx.h: its loss reads the logits on lig_flag rows only), or the support marked on the device.
+// The head then walks a twentieth of the nodes: listed node GEMMs for the recompute, listed weight- / input-gradient products, nothing
+// read outside the list.  {NULL, NULL}: every row.  The scratch is borrowed from block set 0 (no block has run yet).
+static int classifier_head_backward(const float* c, int C, const float* hl, const float* grad_logits, int n, TrainWs& w,
+                                    float* const* cg, NodeList rows, hipStream_t s) {
+    BlockSet& b = w.set[0];
+    float *pre = b.qs, *act = b.zb, *dact = b.dqb;      // [N,128] scratch (a listed head: listed rows only)
+    const int ng = node_grid(n), sp = splits_for(n), wg = wgrad_groups(n);
+    const bool mfma = g_edge_impl != 1;      // (a listed head always is)
+    // sum of `nsl` slabs [rws][cls] in b.partial -> dst
+    auto reduce = [&](int nsl, int rws, int cls, float* dst) -> int {
+        Slabs f;
+        RC_TRY(fold_slabs(b.partial, nsl, (size_t)rws * cls, rws * cls, b.folded, f, s));
+        HIP_TRY(launch_reduce_store(f.p, f.n, f.stride, cls, rws, cls, dst, cls, 0, s));
+        return CBGX_OK;
+    };
+    HIP_TRY(launch_node_gemm(hl, H, c + C_W0T, c + C_B0, pre, H, n, H, 0, s, rows.rows, rows.count));
+    HIP_TRY(launch_node_gemm(hl, H, c + C_W0T, c + C_B0, act, H, n, H, 1, s, rows.rows, rows.count));
+    // classifier.2: dW1[c][k] = sum_i dlogits[i][c] act[i][k];  db1 = colsum(dlogits)
+    if (rows.rows) HIP_TRY(launch_cls_w1_grad_rows(grad_logits, C, act, rows.rows, rows.count, cg[2], s));
+    else {
+        HIP_TRY(launch_sgemm(true, false, grad_logits, C, act, H, b.partial, H, C, H, n, sp, (size_t)C * H, 0, s));
+        RC_TRY(reduce(sp, C, H, cg[2]));
+    }
+    HIP_TRY(launch_colsum(grad_logits, C, C, nullptr, rows.rows, rows.count, n, b.partial, C, ng, s));
+    RC_TRY(reduce(ng, 1, C, cg[3]));
+    // d(act) = dlogits W1 (C_W1T is [128][C]; all rows: a [N x C] x [C x 128] product, zero outside the list);  d(pre) = d(act) sigmoid(pre)
+    HIP_TRY(launch_sgemm(false, true, grad_logits, C, c + C_W1T, C, dact, H, n, H, C, 1, 0, 0, s));
+    if (rows.rows) HIP_TRY(launch_ssp_backward_rows(pre, dact, rows.rows, rows.count, n, w.tmp, s));
+    else HIP_TRY(launch_ssp_backward(pre, dact, (long)n * H, w.tmp, s));
+    // classifier.0: dW0[n][k] = sum_i dpre[i][n] h[i][k];  db0 = colsum(dpre);  dh += dpre W0
+    if (mfma) HIP_TRY(launch_wgrad_mfma(w.tmp, H, hl, H, n, 1, b.partial, H, (size_t)H * H, wg, s, rows.rows, rows.count));
+    else HIP_TRY(launch_sgemm(true, false, w.tmp, H, hl, H, b.partial, H, H, H, n, sp, (size_t)H * H, 0, s));
+    RC_TRY(reduce(mfma ? wg : sp, H, H, cg[0]));
+    HIP_TRY(launch_colsum(w.tmp, H, H, nullptr, rows.rows, rows.count, n, b.partial, H, ng, s));
+    RC_TRY(reduce(ng, 1, H, cg[1]));
+    if (mfma) HIP_TRY(launch_dgrad_mfma(w.tmp, H, c + C_W0T, H, w.gh, H, n, H, 1, s, nullptr, rows.rows, rows.count));
+    else HIP_TRY(launch_sgemm(false, true, w.tmp, H, c + C_W0T, H, w.gh, H, n, H, H, 1, 0, 1, s));
     return CBGX_OK;
 }
 
@@ -472,6 +505,16 @@ static int check_grads(float* const* g, int count, const char* who) {
     for (int i = 0; i < count; ++i)
         if (!g[i]) return set_error(CBGX_E_INVALID, "%s: grads[%d] is NULL", who, i);
     return CBGX_OK;
+}
+
+// carve + size check of the entry points that take a training workspace / a denoiser tape (as carve_checked, api.hip)
+static int carve_train_checked(const char* who, void* workspace, size_t bytes, int n, TrainWs& w) {
+    w = carve_train(workspace, n);
+    return bytes < w.total ? set_error(CBGX_E_WORKSPACE, "%s: workspace %zu < %zu", who, bytes, w.total) : CBGX_OK;
+}
+static int carve_tape_checked(const char* who, const void* tape, size_t bytes, int n, int L, Tape& tp) {
+    tp = carve_tape((void*)tape, n, L);
+    return bytes < tp.total ? set_error(CBGX_E_WORKSPACE, "%s: tape %zu < %zu", who, bytes, tp.total) : CBGX_OK;
 }
 
 extern "C" {
@@ -505,18 +548,17 @@ int cbgx_unitransformer_forward_train_ex(const float* packed, int num_layers, in
     if (n_nodes == 0) return CBGX_OK;
     if (!packed || !x || !h || !graph_ptr || !lig_flag || !gen_flag || !x_out || !tape || !workspace)
         return set_error(CBGX_E_INVALID, "forward_train: NULL pointer");
-    Tape tp = carve_tape(tape, n_nodes, num_layers);
-    if (tape_bytes < tp.total) return set_error(CBGX_E_WORKSPACE, "forward_train: tape %zu < %zu", tape_bytes, tp.total);
-    TrainWs w = carve_train(workspace, n_nodes);
-    if (workspace_bytes < w.total)
-        return set_error(CBGX_E_WORKSPACE, "forward_train: workspace %zu < %zu", workspace_bytes, w.total);
+    Tape tp;
+    RC_TRY(carve_tape_checked("forward_train", tape, tape_bytes, n_nodes, num_layers, tp));
+    TrainWs w;
+    RC_TRY(carve_train_checked("forward_train", workspace, workspace_bytes, n_nodes, w));
     hipStream_t s = (hipStream_t)stream;
     const size_t nx = (size_t)n_nodes * 3, nh = (size_t)n_nodes * H;
     HIP_TRY(hipMemcpyAsync(tp.xs, x, nx * 4, hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemcpyAsync(tp.hs, h, nh * 4, hipMemcpyDeviceToDevice, s));
     HIP_TRY(launch_knn(x, graph_ptr, n_graphs, n_nodes, tp.nbr, tp.deg, s));
     HIP_TRY(launch_gate(packed, x, tp.nbr, tp.deg, n_nodes, tp.e_w, s));
-    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act, w.act_count, s));
+    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act.rows, w.act.count, s));
     // Round 6: the node stage of the x2h block of layer l + 1 (projection, query MLP, fold: ~57 us at 16.5 k nodes) reads h_{l+1} only,
     // like the h2x block of layer l (~60 us) -- it runs on the caller's auxiliary stream next to that block (what the sampling forward
     // has done since round 3); every block owns its P / Qt on the tape, the two node stages use different query scratch rows.
@@ -537,23 +579,20 @@ int cbgx_unitransformer_forward_train_ex(const float* packed, int num_layers, in
     // neighbours; the backward then prunes around the support of its dL/dh_out, which lies inside A1, unless CBGX_TRAIN_PRUNE_GH=0)
     const bool fprune = (!h_out || ((flags & CBGX_FWD_H_ON_SOURCES) && env_on("CBGX_TRAIN_PRUNE_GH"))) && num_layers >= 3 &&
                         g_edge_impl != 1 && env_on("CBGX_TRAIN_FWD_PRUNE") && (!h_out || !logits || num_classes <= 128);
-    const int* A[3] = {w.rf_list[0], w.rf_list[1], w.lig_list};
-    const int* An[3] = {w.rf_count, w.rf_count + 16, w.rf_count + 32};
+    const NodeList every{nullptr, nullptr};
+    const NodeList A[3] = {w.A1, w.A2, w.A3};
     if (fprune) {
         HIP_TRY(launch_mark_seed(gen_flag, lig_flag, n_nodes, w.mask, s));
-        HIP_TRY(launch_mark_nbr(w.act, w.act_count, n_nodes, tp.nbr, tp.deg, w.mask, s));
-        HIP_TRY(launch_build_active(w.mask, n_nodes, w.rf_list[0], w.rf_count, s));
-        HIP_TRY(launch_mark_nbr(w.rf_list[0], w.rf_count, n_nodes, tp.nbr, tp.deg, w.mask, s));
-        HIP_TRY(launch_build_active(w.mask, n_nodes, w.rf_list[1], w.rf_count + 16, s));
-        HIP_TRY(launch_mark_nbr(w.rf_list[1], w.rf_count + 16, n_nodes, tp.nbr, tp.deg, w.mask, s));
-        HIP_TRY(launch_build_active(w.mask, n_nodes, w.lig_list, w.rf_count + 32, s));
+        HIP_TRY(walk_receptive_field(w.mask, w.act, tp.nbr, tp.deg, n_nodes, {w.A1, w.A2, w.A3}, s));
     }
-    // (destination list, its count, source list, its count) of the x2h block of layer l
-    auto x2h_lists = [&](int l, const int*& d, const int*& dn, const int*& sr, const int*& sn) {
-        d = dn = sr = sn = nullptr;
+    // (destination list, source list) of the x2h block of layer l
+    auto x2h_lists = [&](int l, NodeList& d, NodeList& sr) {
+        d = sr = every;
         const int k = num_layers - 1 - l;      // 0 for the last layer
-        if (fprune && k < 2) { d = A[k]; dn = An[k]; sr = A[k + 1]; sn = An[k + 1]; }
+        if (fprune && k < 2) { d = A[k]; sr = A[k + 1]; }
     };
+    const NodeList a1 = fprune ? w.A1 : every;     // sources of the h2x blocks; rows of the logits
+    float *qs = w.set[0].qs, *qs_aux = w.set[1].qs;     // query scratch borrowed from the block sets: caller's / auxiliary stream
     for (int l = 0; l < num_layers; ++l) {
         const float* xc = tp.xs + (size_t)l * nx;
         const float* hc = tp.hs + (size_t)l * nh;
@@ -561,31 +600,34 @@ int cbgx_unitransformer_forward_train_ex(const float* packed, int num_layers, in
         float* hn = tp.hs + (size_t)(l + 1) * nh;
         float* Px = tp.P + (size_t)(2 * l) * n_nodes * PROW;
         float* Qx = tp.Qt + (size_t)(2 * l) * n_nodes * HEADS * H;
-        const int *d, *dn, *sr, *sn;
-        x2h_lists(l, d, dn, sr, sn);
-        if (d) HIP_TRY(hipMemsetAsync(hn, 0, nh * 4, s));      // rows the listed launch does not write
+        NodeList d, sr;
+        x2h_lists(l, d, sr);
+        if (d.rows) HIP_TRY(hipMemsetAsync(hn, 0, nh * 4, s));      // rows the listed launch does not write
         if (!aux) {
             HIP_TRY(launch_attention(true, packed + x2h_off(l), xc, hc, tp.nbr, tp.deg, lig_flag, gen_flag, tp.e_w, n_nodes,
-                                     Px, Qx, w.qs, hn, nullptr, d, dn, sr, sn, s));
+                                     Px, Qx, qs, hn, nullptr, d.rows, d.count, sr.rows, sr.count, s));
         } else {
-            if (l == 0) HIP_TRY(launch_node_mfma(packed + x2h_off(0), hc, lig_flag, n_nodes, Px, w.qs2, Qx, d, dn, sr, sn, s, true));
+            if (l == 0)
+                HIP_TRY(launch_node_mfma(packed + x2h_off(0), hc, lig_flag, n_nodes, Px, qs_aux, Qx, d.rows, d.count, sr.rows, sr.count, s,
+                                         true));
             else { HIP_TRY(hipStreamWaitEvent(s, aux->join, 0)); jn.out = false; }      // this layer's node stage (auxiliary stream)
             HIP_TRY(launch_edge_mfma(true, packed + x2h_off(l), xc, hc, Px, Qx, tp.nbr, tp.deg, lig_flag, gen_flag, tp.e_w, n_nodes,
-                                     hn, nullptr, d, dn, s));
+                                     hn, nullptr, d.rows, d.count, s));
             if (l + 1 < num_layers) {
-                const int *d2, *d2n, *s2, *s2n;
-                x2h_lists(l + 1, d2, d2n, s2, s2n);
+                NodeList d2, s2;
+                x2h_lists(l + 1, d2, s2);
                 HIP_TRY(hipEventRecord(aux->fork, s));
                 HIP_TRY(hipStreamWaitEvent(aux->s, aux->fork, 0));
                 jn.out = true;
                 HIP_TRY(launch_node_mfma(packed + x2h_off(l + 1), hn, lig_flag, n_nodes, tp.P + (size_t)(2 * l + 2) * n_nodes * PROW,
-                                         w.qs2, tp.Qt + (size_t)(2 * l + 2) * n_nodes * HEADS * H, d2, d2n, s2, s2n, aux->s, true));
+                                         qs_aux, tp.Qt + (size_t)(2 * l + 2) * n_nodes * HEADS * H, d2.rows, d2.count, s2.rows, s2.count,
+                                         aux->s, true));
                 HIP_TRY(hipEventRecord(aux->join, aux->s));
             }
         }
         HIP_TRY(launch_attention(false, packed + h2x_off(l), xc, hn, tp.nbr, tp.deg, lig_flag, gen_flag, tp.e_w, n_nodes,
-                                 Px + (size_t)n_nodes * PROW, Qx + (size_t)n_nodes * HEADS * H, w.qs, xn, nullptr, w.act,
-                                 w.act_count, fprune ? A[0] : nullptr, fprune ? An[0] : nullptr, s));
+                                 Px + (size_t)n_nodes * PROW, Qx + (size_t)n_nodes * HEADS * H, qs, xn, nullptr, w.act.rows,
+                                 w.act.count, a1.rows, a1.count, s));
     }
     const float* hl = tp.hs + (size_t)num_layers * nh;
     HIP_TRY(hipMemcpyAsync(x_out, tp.xs + (size_t)num_layers * nx, nx * 4, hipMemcpyDeviceToDevice, s));
@@ -594,9 +636,9 @@ int cbgx_unitransformer_forward_train_ex(const float* packed, int num_layers, in
         if (num_classes < 1) return set_error(CBGX_E_INVALID, "forward_train: num_classes=%d", num_classes);
         const float* c = packed + cls_off(num_layers);
         // (pruned: the logits of the A1 rows -- the ligand rows are among them; other rows of `logits` are not written)
-        HIP_TRY(launch_node_gemm(hl, H, c + C_W0T, c + C_B0, w.P, H, n_nodes, H, 1, s, fprune ? A[0] : nullptr, fprune ? An[0] : nullptr));
+        HIP_TRY(launch_node_gemm(hl, H, c + C_W0T, c + C_B0, w.P, H, n_nodes, H, 1, s, a1.rows, a1.count));
         HIP_TRY(launch_node_gemm(w.P, H, c + C_W1T, c + cls_b1(num_classes), logits, num_classes, n_nodes, num_classes,
-                                 0, s, fprune ? A[0] : nullptr, fprune ? An[0] : nullptr));
+                                 0, s, a1.rows, a1.count));
     }
     return CBGX_OK;
 }
@@ -610,18 +652,19 @@ int cbgx_x2h_attention_backward(const float* packed, int layer, const float* x, 
         !workspace)
         return set_error(CBGX_E_INVALID, "x2h_backward: NULL pointer");
     RC_TRY(check_grads(grads, 18, "x2h_backward"));
-    TrainWs w = carve_train(workspace, n_nodes);
-    if (workspace_bytes < w.total)
-        return set_error(CBGX_E_WORKSPACE, "x2h_backward: workspace %zu < %zu", workspace_bytes, w.total);
+    TrainWs w;
+    RC_TRY(carve_train_checked("x2h_backward", workspace, workspace_bytes, n_nodes, w));
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemcpyAsync(grad_h, grad_h_out, (size_t)n_nodes * H * 4, hipMemcpyDeviceToDevice, s));   // residual
     HIP_TRY(hipMemsetAsync(grad_x, 0, (size_t)n_nodes * 3 * 4, s));
     HIP_TRY(hipMemsetAsync(grad_e_w, 0, (size_t)n_nodes * KNN * 4, s));
     const bool rin = edge_rows_mode() && g_edge_impl == 0;
     if (rin) HIP_TRY(launch_rin_build(nbr, deg, n_nodes, w.rin_cnt, w.rin_ptr, w.rin_tmp, w.rin_edge, s));
-    return attention_block_backward(true, packed + x2h_off(layer), x, h, grad_h_out, nbr, deg, lig_flag, e_w, nullptr,
-                                    nullptr, n_nodes, w, grad_h, grad_x, grad_e_w, grads, s, nullptr, nullptr, nullptr, nullptr,
-                                    nullptr, nullptr, nullptr, rin);
+    BlockArgs a;
+    a.x2h = true; a.att = packed + x2h_off(layer); a.x = x; a.h_in = h; a.g_out = grad_h_out;
+    a.nbr = nbr; a.deg = deg; a.lig = lig_flag; a.e_w = e_w; a.n = n_nodes;
+    a.gh = grad_h; a.dx = grad_x; a.de_w = grad_e_w; a.grads = grads; a.rin_ready = rin;
+    return attention_block_backward(a, w, s);
 }
 
 int cbgx_h2x_attention_backward(const float* packed, int layer, const float* x, const float* h, const int32_t* nbr,
@@ -633,16 +676,18 @@ int cbgx_h2x_attention_backward(const float* packed, int layer, const float* x, 
         !grad_e_w || !workspace)
         return set_error(CBGX_E_INVALID, "h2x_backward: NULL pointer");
     RC_TRY(check_grads(grads, 18, "h2x_backward"));
-    TrainWs w = carve_train(workspace, n_nodes);
-    if (workspace_bytes < w.total)
-        return set_error(CBGX_E_WORKSPACE, "h2x_backward: workspace %zu < %zu", workspace_bytes, w.total);
+    TrainWs w;
+    RC_TRY(carve_train_checked("h2x_backward", workspace, workspace_bytes, n_nodes, w));
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act, w.act_count, s));
+    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act.rows, w.act.count, s));
     HIP_TRY(hipMemsetAsync(grad_h, 0, (size_t)n_nodes * H * 4, s));
     HIP_TRY(hipMemcpyAsync(grad_x, grad_x_out, (size_t)n_nodes * 3 * 4, hipMemcpyDeviceToDevice, s));   // x_out = x + ...
     HIP_TRY(hipMemsetAsync(grad_e_w, 0, (size_t)n_nodes * KNN * 4, s));
-    return attention_block_backward(false, packed + h2x_off(layer), x, h, grad_x_out, nbr, deg, lig_flag, e_w, w.act,
-                                    w.act_count, n_nodes, w, grad_h, grad_x, grad_e_w, grads, s);
+    BlockArgs a;
+    a.att = packed + h2x_off(layer); a.x = x; a.h_in = h; a.g_out = grad_x_out;
+    a.nbr = nbr; a.deg = deg; a.lig = lig_flag; a.e_w = e_w; a.n = n_nodes; a.rows = w.act;
+    a.gh = grad_h; a.dx = grad_x; a.de_w = grad_e_w; a.grads = grads;
+    return attention_block_backward(a, w, s);
 }
 
 int cbgx_unitransformer_backward(const float* packed, int num_layers, int num_classes, const void* tape,
@@ -665,87 +710,34 @@ int cbgx_unitransformer_backward_ex(const float* packed, int num_layers, int num
     if (num_grads != 6 + 36 * num_layers + 4)
         return set_error(CBGX_E_INVALID, "backward: expected %d gradient tensors, got %d", 6 + 36 * num_layers + 4, num_grads);
     RC_TRY(check_grads(grads, num_grads, "backward"));
-    Tape tp = carve_tape((void*)tape, n_nodes, num_layers);
-    if (tape_bytes < tp.total) return set_error(CBGX_E_WORKSPACE, "backward: tape %zu < %zu", tape_bytes, tp.total);
-    TrainWs w = carve_train(workspace, n_nodes);
-    if (workspace_bytes < w.total)
-        return set_error(CBGX_E_WORKSPACE, "backward: workspace %zu < %zu", workspace_bytes, w.total);
+    Tape tp;
+    RC_TRY(carve_tape_checked("backward", tape, tape_bytes, n_nodes, num_layers, tp));
+    TrainWs w;
+    RC_TRY(carve_train_checked("backward", workspace, workspace_bytes, n_nodes, w));
     hipStream_t s = (hipStream_t)stream;
     const int n = n_nodes, L = num_layers, C = num_classes;
     const size_t nx = (size_t)n * 3, nh = (size_t)n * H;
-    const int ng = node_grid(n), sp = splits_for(n);
+    const NodeList every{nullptr, nullptr};
 
     // dL/dh_L: the caller's gradient plus the classifier head
     if (grad_h_out) HIP_TRY(hipMemcpyAsync(w.gh, grad_h_out, nh * 4, hipMemcpyDeviceToDevice, s));
     else HIP_TRY(hipMemsetAsync(w.gh, 0, nh * 4, s));
-    float* const* cg = grads + 6 + 36 * L;
     // (round 6: with a caller gradient on h_out the same listed head runs on the SUPPORT of grad_logits -- the rows with a non-zero
     // entry, marked on the device; DiffBP's losses read the logits of ligand rows only as well.  CBGX_TRAIN_PRUNE_GH=0: the dense head)
     const bool head_listed = grad_logits && g_edge_impl != 1 && C <= 128 && (grad_h_out == nullptr || env_on("CBGX_TRAIN_PRUNE_GH"));
-    if (head_listed) {
-        // The caller's promise behind grad_h_out == NULL (include/cbgx.h): its loss reads the logits on lig_flag rows only, so
-        // grad_logits is zero elsewhere and the head's backward walks the ligand rows (a twentieth of the nodes) instead of all
-        // of them: listed node GEMMs for the recompute, listed weight- / input-gradient products, nothing read outside the list.
-        const float* c = packed + cls_off(L);
-        const float* hl = tp.hs + (size_t)L * nh;
-        float* pre = w.qs;    // [N,128] scratch: listed rows only
-        float* act = w.zb;
-        float* dact = w.dqb;
-        const int* ll = w.lig_list;
-        const int* lc = w.rf_count + 32;
-        if (grad_h_out) {       // no promise about grad_logits: its support
-            HIP_TRY(launch_mark_nonzero_rows(grad_logits, n, w.mask, s, C, 1));
-            HIP_TRY(launch_build_active(w.mask, n, w.lig_list, w.rf_count + 32, s));
-        } else
-            HIP_TRY(launch_build_active(lig_flag, n, w.lig_list, w.rf_count + 32, s));
-        HIP_TRY(launch_node_gemm(hl, H, c + C_W0T, c + C_B0, pre, H, n, H, 0, s, ll, lc));
-        HIP_TRY(launch_node_gemm(hl, H, c + C_W0T, c + C_B0, act, H, n, H, 1, s, ll, lc));
-        // classifier.2: dW1[c][k] = sum_i dlogits[i][c] act[i][k];  db1 = colsum(dlogits)
-        HIP_TRY(launch_cls_w1_grad_rows(grad_logits, C, act, ll, lc, cg[2], s));
-        HIP_TRY(launch_colsum(grad_logits, C, C, nullptr, ll, lc, n, w.partial, C, ng, s));
-        { FOLDED(w.partial, ng, C, C); RS(fz, fn, fs, C, 1, C, cg[3], C, 0); }
-        // d(act) = dlogits W1 (all rows: a [N x C] x [C x 128] product, zero outside the list);  d(pre) = d(act) sigmoid(pre) on the list
-        HIP_TRY(launch_sgemm(false, true, grad_logits, C, c + C_W1T, C, dact, H, n, H, C, 1, 0, 0, s));
-        HIP_TRY(launch_ssp_backward_rows(pre, dact, ll, lc, n, w.tmp, s));
-        // classifier.0: dW0[n][k] = sum_i dpre[i][n] h[i][k];  db0 = colsum(dpre);  dh += dpre W0
-        const int wg = wgrad_groups(n);
-        HIP_TRY(launch_wgrad_mfma(w.tmp, H, hl, H, n, 1, w.partial, H, (size_t)H * H, wg, s, ll, lc));
-        { FOLDED(w.partial, wg, (size_t)H * H, H * H); RS(fz, fn, fs, H, H, H, cg[0], H, 0); }
-        HIP_TRY(launch_colsum(w.tmp, H, H, nullptr, ll, lc, n, w.partial, H, ng, s));
-        { FOLDED(w.partial, ng, H, H); RS(fz, fn, fs, H, 1, H, cg[1], H, 0); }
-        HIP_TRY(launch_dgrad_mfma(w.tmp, H, c + C_W0T, H, w.gh, H, n, H, 1, s, nullptr, ll, lc));
-    } else if (grad_logits) {
-        const float* c = packed + cls_off(L);
-        const float* hl = tp.hs + (size_t)L * nh;
-        float* pre = w.qs;    // [N,128] scratch
-        float* act = w.zb;
-        float* dact = w.dqb;
-        HIP_TRY(launch_node_gemm(hl, H, c + C_W0T, c + C_B0, pre, H, n, H, 0, s));
-        HIP_TRY(launch_node_gemm(hl, H, c + C_W0T, c + C_B0, act, H, n, H, 1, s));
-        // classifier.2: dW1[c][k] = sum_i dlogits[i][c] act[i][k];  db1 = colsum(dlogits)
-        HIP_TRY(launch_sgemm(true, false, grad_logits, C, act, H, w.partial, H, C, H, n, sp, (size_t)C * H, 0, s));
-        { FOLDED(w.partial, sp, (size_t)C * H, C * H); RS(fz, fn, fs, H, C, H, cg[2], H, 0); }
-        HIP_TRY(launch_colsum(grad_logits, C, C, nullptr, nullptr, nullptr, n, w.partial, C, ng, s));
-        { FOLDED(w.partial, ng, C, C); RS(fz, fn, fs, C, 1, C, cg[3], C, 0); }
-        // d(act) = dlogits W1  (C_W1T is [128][C]);  d(pre) = d(act) sigmoid(pre)
-        HIP_TRY(launch_sgemm(false, true, grad_logits, C, c + C_W1T, C, dact, H, n, H, C, 1, 0, 0, s));
-        HIP_TRY(launch_ssp_backward(pre, dact, (long)nh, w.tmp, s));
-        // classifier.0: dW0[n][k] = sum_i dpre[i][n] h[i][k];  db0 = colsum(dpre);  dh += dpre W0
-        if (g_edge_impl != 1) {
-            const int wg = wgrad_groups(n);
-            HIP_TRY(launch_wgrad_mfma(w.tmp, H, hl, H, n, 1, w.partial, H, (size_t)H * H, wg, s));
-            FOLDED(w.partial, wg, (size_t)H * H, H * H); RS(fz, fn, fs, H, H, H, cg[0], H, 0);
-        } else {
-            HIP_TRY(launch_sgemm(true, false, w.tmp, H, hl, H, w.partial, H, H, H, n, sp, (size_t)H * H, 0, s));
-            FOLDED(w.partial, sp, (size_t)H * H, H * H); RS(fz, fn, fs, H, H, H, cg[0], H, 0);
+    if (grad_logits) {
+        NodeList rows = every;
+        if (head_listed) {
+            rows = w.head_rows();
+            if (grad_h_out) {       // no promise about grad_logits: its support
+                HIP_TRY(launch_mark_nonzero_rows(grad_logits, n, w.mask, s, C, 1));
+                HIP_TRY(launch_build_active(w.mask, n, rows.rows, rows.count, s));
+            } else
+                HIP_TRY(launch_build_active(lig_flag, n, rows.rows, rows.count, s));
         }
-        HIP_TRY(launch_colsum(w.tmp, H, H, nullptr, nullptr, nullptr, n, w.partial, H, ng, s));
-        { FOLDED(w.partial, ng, H, H); RS(fz, fn, fs, H, 1, H, cg[1], H, 0); }
-        if (g_edge_impl != 1)
-            HIP_TRY(launch_dgrad_mfma(w.tmp, H, c + C_W0T, H, w.gh, H, n, H, 1, s));
-        else
-            HIP_TRY(launch_sgemm(false, true, w.tmp, H, c + C_W0T, H, w.gh, H, n, H, H, 1, 0, 1, s));
+        RC_TRY(classifier_head_backward(packed + cls_off(L), C, tp.hs + (size_t)L * nh, grad_logits, n, w, grads + 6 + 36 * L, rows, s));
     } else {
+        float* const* cg = grads + 6 + 36 * L;
         HIP_TRY(hipMemsetAsync(cg[0], 0, (size_t)H * H * 4, s));
         HIP_TRY(hipMemsetAsync(cg[1], 0, H * 4, s));
         HIP_TRY(hipMemsetAsync(cg[2], 0, (size_t)C * H * 4, s));
@@ -755,7 +747,7 @@ int cbgx_unitransformer_backward_ex(const float* packed, int num_layers, int num
     if (grad_x_out) HIP_TRY(hipMemcpyAsync(w.gx[cur], grad_x_out, nx * 4, hipMemcpyDeviceToDevice, s));
     else HIP_TRY(hipMemsetAsync(w.gx[cur], 0, nx * 4, s));
     HIP_TRY(hipMemsetAsync(w.de_w, 0, (size_t)n * KNN * 4, s));
-    HIP_TRY(launch_build_active(gen_flag, n, w.act, w.act_count, s));
+    HIP_TRY(launch_build_active(gen_flag, n, w.act.rows, w.act.count, s));
     // Receptive-field pruning, the mirror image of the forward's: without a caller gradient on h_out, dL/dh_L is non-zero
     // on ligand rows only (classifier), the last h2x block adds rows of A1 = gen | lig | nbr(gen), and the x2h block of a
     // layer spreads its input gradient one hop further (A2 = A1 | nbr(A1)).  Rows outside carry an exactly zero gradient
@@ -770,10 +762,7 @@ int cbgx_unitransformer_backward_ex(const float* packed, int num_layers, int num
             HIP_TRY(launch_mark_nonzero_rows(grad_h_out, n, w.mask, s));
             if (grad_logits && C <= 128) HIP_TRY(launch_mark_nonzero_rows(grad_logits, n, w.mask, s, C, 0));
         }
-        HIP_TRY(launch_mark_nbr(w.act, w.act_count, n, tp.nbr, tp.deg, w.mask, s));
-        HIP_TRY(launch_build_active(w.mask, n, w.rf_list[0], w.rf_count, s));
-        HIP_TRY(launch_mark_nbr(w.rf_list[0], w.rf_count, n, tp.nbr, tp.deg, w.mask, s));
-        HIP_TRY(launch_build_active(w.mask, n, w.rf_list[1], w.rf_count + 16, s));
+        HIP_TRY(walk_receptive_field(w.mask, w.act, tp.nbr, tp.deg, n, {w.A1, w.A2}, s));
     }
 
     // one zeroed accumulator per attention block for the query LayerNorm's affine gradients (atomics): a single fill here
@@ -800,20 +789,25 @@ int cbgx_unitransformer_backward_ex(const float* packed, int num_layers, int num
         const int nxt = cur ^ 1;
         const float* Px = tp.P + (size_t)(2 * l) * n * PROW;
         const float* Qx = tp.Qt + (size_t)(2 * l) * n * HEADS * H;
-        RC_TRY(attention_block_backward(false, packed + h2x_off(l), xl, h_mid, w.gx[cur], tp.nbr, tp.deg, lig_flag, tp.e_w,
-                                        w.act, w.act_count, n, w, gh_cur, w.gx[nxt], w.de_w, g + 18, s,
-                                        Px + (size_t)n * PROW, Qx + (size_t)n * HEADS * H,
-                                        qln_slots ? w.qln + (size_t)(2 * l + 1) * 2 * H : nullptr, nullptr,
-                                        // dP of an h2x block is non-zero on gen | nbr(gen) only, a subset of the receptive-field list A1
-                                        prune ? w.rf_list[0] : nullptr, prune ? w.rf_count : nullptr, &ov, false, w.gx[cur]));
+        BlockArgs both;     // what the layer's two blocks share
+        both.x = xl; both.nbr = tp.nbr; both.deg = tp.deg; both.lig = lig_flag; both.e_w = tp.e_w; both.n = n;
+        both.dx = w.gx[nxt]; both.de_w = w.de_w; both.ov = &ov;
+        BlockArgs a = both;
+        a.att = packed + h2x_off(l); a.h_in = h_mid; a.g_out = w.gx[cur]; a.rows = w.act;
+        // dP of an h2x block is non-zero on gen | nbr(gen) only, a subset of the receptive-field list A1
+        a.dp_rows = prune ? w.A1 : every;
+        a.gh = gh_cur; a.dx_init = w.gx[cur]; a.grads = g + 18; a.P_saved = Px + (size_t)n * PROW; a.Qt_saved = Qx + (size_t)n * HEADS * H;
+        a.qln = qln_slots ? w.qln + (size_t)(2 * l + 1) * 2 * H : nullptr;
+        RC_TRY(attention_block_backward(a, w, s));
         // h_mid = h_in + X2H(x_l, h_in): gh_cur holds dL/dh_mid, which is also the residual part of dL/dh_in.  The block reads it
         // (fold, outer products, bias sums) and writes dL/dh_in = gh_cur + dP Wn^T into the OTHER buffer.
         const int k = L - 1 - l;      // 0 for the last layer
-        const int* rows = (prune && k < 2) ? w.rf_list[k] : nullptr;
-        const int* n_rows = (prune && k < 2) ? w.rf_count + 16 * k : nullptr;
-        RC_TRY(attention_block_backward(true, packed + x2h_off(l), xl, h_in, gh_cur, tp.nbr, tp.deg, lig_flag, tp.e_w,
-                                        rows, n_rows, n, w, gh_oth, w.gx[nxt], w.de_w, g, s, Px, Qx,
-                                        qln_slots ? w.qln + (size_t)(2 * l) * 2 * H : nullptr, gh_cur, nullptr, nullptr, &ov, rin));
+        BlockArgs c = both;
+        c.x2h = true; c.att = packed + x2h_off(l); c.h_in = h_in; c.g_out = gh_cur;
+        c.rows = (prune && k < 2) ? (k ? w.A2 : w.A1) : every;
+        c.gh = gh_oth; c.gh_src = gh_cur; c.grads = g; c.P_saved = Px; c.Qt_saved = Qx; c.rin_ready = rin;
+        c.qln = qln_slots ? w.qln + (size_t)(2 * l) * 2 * H : nullptr;
+        RC_TRY(attention_block_backward(c, w, s));
         { float* t = gh_cur; gh_cur = gh_oth; gh_oth = t; }
         cur = nxt;
     }
@@ -827,7 +821,7 @@ int cbgx_unitransformer_backward_ex(const float* packed, int num_layers, int num
     if (grad_x_in) HIP_TRY(hipMemcpyAsync(grad_x_in, w.gx[cur], nx * 4, hipMemcpyDeviceToDevice, s));
     // distance gate (computed once from the input coordinates, used by all 2L blocks): on its own slab buffers, BEFORE the auxiliary
     // stream is joined -- the last blocks' weight-gradient kernels (~150 us) run beside it instead of ahead of it
-    RC_TRY(gate_backward(packed, tp.xs, tp.nbr, tp.deg, n, w, grads, s, nullptr, nullptr, grad_x_in));
+    RC_TRY(gate_backward(packed, tp.xs, tp.nbr, tp.deg, n, w, grads, s, every, grad_x_in));
     // the auxiliary stream's last weight gradients must be in place when this call's work on `s` is: join both sets
     if (ov.aux)
         for (int k = 0; k < 2; ++k)
@@ -837,22 +831,26 @@ int cbgx_unitransformer_backward_ex(const float* packed, int num_layers, int num
 }
 
 // ---- a stack of H2X blocks on its own graph (DiffBP's CoMPredictor, diffbp.py:30-101): taped forward + backward -------
-size_t cbgx_h2x_stack_tape_bytes(int n_nodes, int num_layers) {
-    if (n_nodes < 0 || num_layers < 1) return 0;
-    const size_t N = (size_t)(n_nodes > 0 ? n_nodes : 1);
-    return align_up(N * KNN * 4) + align_up(N * 4) + align_up(N * KNN * 4) + align_up((size_t)(num_layers + 1) * N * 3 * 4);
-}
-
-struct StackTape { int32_t* nbr; int32_t* deg; float* e_w; float* xs; };
-static StackTape carve_stack_tape(void* base, int n) {
+struct StackTape { int32_t* nbr; int32_t* deg; float* e_w; float* xs; size_t total; };
+static StackTape carve_stack_tape(void* base, int n, int L) {
     StackTape t;
     Carver c(base);
     const size_t N = (size_t)(n > 0 ? n : 1);
     t.nbr = c.take<int32_t>(N * KNN * 4);
     t.deg = c.take<int32_t>(N * 4);
     t.e_w = c.take<float>(N * KNN * 4);
-    t.xs = (float*)(c.base + c.off);      // (L + 1 coordinate sets: cbgx_h2x_stack_tape_bytes)
+    t.xs = c.take<float>((size_t)(L + 1) * N * 3 * 4);
+    t.total = c.off;
     return t;
+}
+static int carve_stack_tape_checked(const char* who, const void* tape, size_t bytes, int n, int L, StackTape& tp) {
+    tp = carve_stack_tape((void*)tape, n, L);
+    return bytes < tp.total ? set_error(CBGX_E_WORKSPACE, "%s: tape too small", who) : CBGX_OK;
+}
+
+size_t cbgx_h2x_stack_tape_bytes(int n_nodes, int num_layers) {
+    if (n_nodes < 0 || num_layers < 1) return 0;
+    return carve_stack_tape(nullptr, n_nodes, num_layers).total;
 }
 
 int cbgx_h2x_stack_forward_train(const float* packed, int num_layers, const float* x, const float* h,
@@ -862,36 +860,33 @@ int cbgx_h2x_stack_forward_train(const float* packed, int num_layers, const floa
     if (n_nodes <= 0 || n_graphs < 1 || num_layers < 1) return set_error(CBGX_E_INVALID, "h2x_stack_forward_train: bad sizes");
     if (!packed || !x || !h || !graph_ptr || !lig_flag || !gen_flag || !x_out || !tape || !workspace)
         return set_error(CBGX_E_INVALID, "h2x_stack_forward_train: NULL pointer");
-    if (tape_bytes < cbgx_h2x_stack_tape_bytes(n_nodes, num_layers))
-        return set_error(CBGX_E_WORKSPACE, "h2x_stack_forward_train: tape too small");
-    TrainWs w = carve_train(workspace, n_nodes);
-    if (workspace_bytes < w.total)
-        return set_error(CBGX_E_WORKSPACE, "h2x_stack_forward_train: workspace %zu < %zu", workspace_bytes, w.total);
-    StackTape tp = carve_stack_tape(tape, n_nodes);
+    StackTape tp;
+    RC_TRY(carve_stack_tape_checked("h2x_stack_forward_train", tape, tape_bytes, n_nodes, num_layers, tp));
+    TrainWs w;
+    RC_TRY(carve_train_checked("h2x_stack_forward_train", workspace, workspace_bytes, n_nodes, w));
     hipStream_t s = (hipStream_t)stream;
     const size_t nx = (size_t)n_nodes * 3;
     HIP_TRY(hipMemcpyAsync(tp.xs, x, nx * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act, w.act_count, s));
+    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act.rows, w.act.count, s));
     // As cbgx_h2x_stack_forward (api.hip): an h2x block only reads the neighbour lists and gate values of the rows it moves and the
     // projections of their in-neighbours, so the kNN search, the gate MLP and the neighbour projection run on those lists (round 6;
     // the backward walks the same lists -- CBGX_TRAIN_STACK_LISTS=0 switches both back to all rows)
     const bool lists = g_edge_impl == 0 && env_on("CBGX_TRAIN_STACK_LISTS");
-    const int *src = nullptr, *src_n = nullptr;
+    NodeList src{nullptr, nullptr};
     if (lists) {
-        HIP_TRY(launch_knn_reg(x, graph_ptr, n_graphs, n_nodes, tp.nbr, tp.deg, s, w.act, w.act_count));
-        HIP_TRY(launch_gate_mfma(packed, x, tp.nbr, tp.deg, n_nodes, tp.e_w, s, w.act, w.act_count));
+        HIP_TRY(launch_knn_reg(x, graph_ptr, n_graphs, n_nodes, tp.nbr, tp.deg, s, w.act.rows, w.act.count));
+        HIP_TRY(launch_gate_mfma(packed, x, tp.nbr, tp.deg, n_nodes, tp.e_w, s, w.act.rows, w.act.count));
         HIP_TRY(launch_mark_seed(gen_flag, gen_flag, n_nodes, w.mask, s));
-        HIP_TRY(launch_mark_nbr(w.act, w.act_count, n_nodes, tp.nbr, tp.deg, w.mask, s));
-        HIP_TRY(launch_build_active(w.mask, n_nodes, w.rf_list[0], w.rf_count, s));
-        src = w.rf_list[0]; src_n = w.rf_count;
+        HIP_TRY(walk_receptive_field(w.mask, w.act, tp.nbr, tp.deg, n_nodes, {w.A1}, s));
+        src = w.A1;
     } else {
         HIP_TRY(launch_knn(x, graph_ptr, n_graphs, n_nodes, tp.nbr, tp.deg, s));
         HIP_TRY(launch_gate(packed, x, tp.nbr, tp.deg, n_nodes, tp.e_w, s));
     }
     for (int l = 0; l < num_layers; ++l)
         HIP_TRY(launch_attention(false, packed + GATE_SIZE + (size_t)l * ATT_SIZE, tp.xs + (size_t)l * nx, h, tp.nbr, tp.deg,
-                                 lig_flag, gen_flag, tp.e_w, n_nodes, w.P, w.Qt, w.qs, tp.xs + (size_t)(l + 1) * nx, nullptr,
-                                 w.act, w.act_count, src, src_n, s));
+                                 lig_flag, gen_flag, tp.e_w, n_nodes, w.P, w.Qt, w.set[0].qs, tp.xs + (size_t)(l + 1) * nx, nullptr,
+                                 w.act.rows, w.act.count, src.rows, src.count, s));
     HIP_TRY(hipMemcpyAsync(x_out, tp.xs + (size_t)num_layers * nx, nx * 4, hipMemcpyDeviceToDevice, s));
     return CBGX_OK;
 }
@@ -914,12 +909,10 @@ int cbgx_h2x_stack_backward_ex(const float* packed, int num_layers, const void* 
     if (num_grads != 6 + 18 * num_layers)
         return set_error(CBGX_E_INVALID, "h2x_stack_backward: expected %d gradient tensors, got %d", 6 + 18 * num_layers, num_grads);
     RC_TRY(check_grads(grads, num_grads, "h2x_stack_backward"));
-    if (tape_bytes < cbgx_h2x_stack_tape_bytes(n_nodes, num_layers))
-        return set_error(CBGX_E_WORKSPACE, "h2x_stack_backward: tape too small");
-    TrainWs w = carve_train(workspace, n_nodes);
-    if (workspace_bytes < w.total)
-        return set_error(CBGX_E_WORKSPACE, "h2x_stack_backward: workspace %zu < %zu", workspace_bytes, w.total);
-    StackTape tp = carve_stack_tape((void*)tape, n_nodes);
+    StackTape tp;
+    RC_TRY(carve_stack_tape_checked("h2x_stack_backward", tape, tape_bytes, n_nodes, num_layers, tp));
+    TrainWs w;
+    RC_TRY(carve_train_checked("h2x_stack_backward", workspace, workspace_bytes, n_nodes, w));
     hipStream_t s = (hipStream_t)stream;
     const int n = n_nodes;
     const size_t nx = (size_t)n * 3, nh = (size_t)n * H;
@@ -927,27 +920,29 @@ int cbgx_h2x_stack_backward_ex(const float* packed, int num_layers, const void* 
     int cur = 0;
     HIP_TRY(hipMemcpyAsync(w.gx[cur], grad_x_out, nx * 4, hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemsetAsync(w.de_w, 0, (size_t)n * KNN * 4, s));
-    HIP_TRY(launch_build_active(gen_flag, n, w.act, w.act_count, s));
+    HIP_TRY(launch_build_active(gen_flag, n, w.act.rows, w.act.count, s));
     // Round 6, as the denoiser's layer loop: the projection gradient of an h2x block is non-zero on gen | nbr(gen) only (this stack's
     // own graph), so its fill and every dense product over it walk that list; the weight-gradient kernels of a block run on the caller's
     // auxiliary stream on alternating buffer sets, one query-LayerNorm accumulator slot per block (CBGX_TRAIN_OVERLAP=0: one stream)
     const bool lists = g_edge_impl != 1 && env_on("CBGX_TRAIN_STACK_LISTS");
     if (lists) {
         HIP_TRY(launch_mark_seed(gen_flag, gen_flag, n, w.mask, s));
-        HIP_TRY(launch_mark_nbr(w.act, w.act_count, n, tp.nbr, tp.deg, w.mask, s));
-        HIP_TRY(launch_build_active(w.mask, n, w.rf_list[0], w.rf_count, s));
+        HIP_TRY(walk_receptive_field(w.mask, w.act, tp.nbr, tp.deg, n, {w.A1}, s));
     }
+    const NodeList every{nullptr, nullptr};
     const bool qln_slots = num_layers <= QLN_SLOTS;
     if (qln_slots) HIP_TRY(hipMemsetAsync(w.qln, 0, (size_t)num_layers * 2 * H * sizeof(float), s));
     BlockOverlap ov{(lists && env_on("CBGX_TRAIN_OVERLAP") && !profile_is_on() && qln_slots) ? aux_for(s) : nullptr, 0, {false, false}};
     for (int l = num_layers - 1; l >= 0; --l) {
         const int nxt = cur ^ 1;
         // x_out = x + gen * delta: the identity part of the coordinate gradient is the block's `dx_init`
-        RC_TRY(attention_block_backward(false, packed + GATE_SIZE + (size_t)l * ATT_SIZE, tp.xs + (size_t)l * nx, h, w.gx[cur],
-                                        tp.nbr, tp.deg, lig_flag, tp.e_w, w.act, w.act_count, n, w, w.gh, w.gx[nxt], w.de_w,
-                                        grads + 6 + 18 * l, s, nullptr, nullptr,
-                                        qln_slots ? w.qln + (size_t)l * 2 * H : nullptr, nullptr,
-                                        lists ? w.rf_list[0] : nullptr, lists ? w.rf_count : nullptr, &ov, false, w.gx[cur]));
+        BlockArgs a;
+        a.att = packed + GATE_SIZE + (size_t)l * ATT_SIZE; a.x = tp.xs + (size_t)l * nx; a.h_in = h; a.g_out = w.gx[cur];
+        a.nbr = tp.nbr; a.deg = tp.deg; a.lig = lig_flag; a.e_w = tp.e_w; a.n = n;
+        a.rows = w.act; a.dp_rows = lists ? w.A1 : every;
+        a.gh = w.gh; a.dx = w.gx[nxt]; a.dx_init = w.gx[cur]; a.de_w = w.de_w; a.grads = grads + 6 + 18 * l;
+        a.qln = qln_slots ? w.qln + (size_t)l * 2 * H : nullptr; a.ov = &ov;
+        RC_TRY(attention_block_backward(a, w, s));
         cur = nxt;
     }
     HIP_TRY(hipMemcpyAsync(grad_h, w.gh, nh * 4, hipMemcpyDeviceToDevice, s));
@@ -955,8 +950,7 @@ int cbgx_h2x_stack_backward_ex(const float* packed, int num_layers, const void* 
     // exactly zero, as in the denoiser's backward), then the gate's distance path, which lives on the movable rows' edges only
     if (grad_x_in) HIP_TRY(hipMemcpyAsync(grad_x_in, w.gx[cur], nx * 4, hipMemcpyDeviceToDevice, s));
     // (the stack's blocks add to de_w on the movable rows only: the gate backward walks that list -- 16.5 k rows -> ~900)
-    RC_TRY(gate_backward(packed, tp.xs, tp.nbr, tp.deg, n, w, grads, s, lists ? w.act : nullptr, lists ? w.act_count : nullptr,
-                         grad_x_in));
+    RC_TRY(gate_backward(packed, tp.xs, tp.nbr, tp.deg, n, w, grads, s, lists ? w.act : every, grad_x_in));
     if (ov.aux)
         for (int k = 0; k < 2; ++k)
             if (ov.used[k]) HIP_TRY(hipStreamWaitEvent(s, ov.aux->done[k], 0));
@@ -1287,12 +1281,11 @@ int cbgx_debug_gate_backward(const float* packed, const float* x, const int32_t*
     if (!packed || !x || !nbr || !deg || !de_w || !workspace || (rows != nullptr) != (n_rows != nullptr))
         return set_error(CBGX_E_INVALID, "debug_gate_backward: NULL pointer");
     RC_TRY(check_grads(grads, 6, "debug_gate_backward"));
-    TrainWs w = carve_train(workspace, n_nodes);
-    if (workspace_bytes < w.total)
-        return set_error(CBGX_E_WORKSPACE, "debug_gate_backward: workspace %zu < %zu", workspace_bytes, w.total);
+    TrainWs w;
+    RC_TRY(carve_train_checked("debug_gate_backward", workspace, workspace_bytes, n_nodes, w));
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemcpyAsync(w.de_w, de_w, (size_t)n_nodes * KNN * 4, hipMemcpyDeviceToDevice, s));
-    return gate_backward(packed, x, nbr, deg, n_nodes, w, grads, s, rows, n_rows, grad_x);
+    return gate_backward(packed, x, nbr, deg, n_nodes, w, grads, s, NodeList{(int*)rows, (int*)n_rows}, grad_x);
 }
 #endif
 
