@@ -13,6 +13,7 @@ _LIB = None
 _XLIB = None
 
 _vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+FWD_H_ON_SOURCES, FWD_GEN_IS_LIGAND = 1, 2      # include/cbgx.h CBGX_FWD_*
 ABI_VERSION = 6      # include/cbgx.h CBGX_ABI_VERSION: bumped whenever the packed-weight layout or an entry point changes
 
 EXPORTS = {
@@ -23,17 +24,20 @@ EXPORTS = {
     "cbgx_pack_weights": (_i, [ctypes.POINTER(_vp), _i, _i, _i, _vp, _vp]),
     "cbgx_workspace_bytes": (_sz, [_i, _i]),
     "cbgx_unitransformer_forward": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "cbgx_unitransformer_forward_v2": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, ctypes.c_uint, _vp, _sz, _vp]),
     "cbgx_unitransformer_forward_cached": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                                 _vp, _vp, _vp, ctypes.c_uint, _vp, _sz, _vp]),
     "cbgx_knn_graph": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "cbgx_edge_gate": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "cbgx_x2h_attention": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "cbgx_h2x_attention": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "cbgx_h2x_attention_v2": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, ctypes.c_uint, _vp, _sz, _vp]),
     "cbgx_classifier": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
     "cbgx_node_stage": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "cbgx_packed_h2x_stack_floats": (_sz, [_i]),
     "cbgx_pack_h2x_stack": (_i, [ctypes.POINTER(_vp), _i, _i, _vp, _vp]),
     "cbgx_h2x_stack_forward": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "cbgx_h2x_stack_forward_v2": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, ctypes.c_uint, _vp, _sz, _vp]),
     "cbgx_targetdiff_prologue": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cbgx_targetdiff_epilogue": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.POINTER(_vp), _vp, _vp, _vp, _vp,
                                       _vp, _vp]),

@@ -376,10 +376,15 @@ int cbgx_pack_h2x_stack(const float* const* t, int num_tensors, int L, float* pa
     return flush_pack(s);
 }
 
-int cbgx_h2x_stack_forward(const float* packed, int num_layers, const float* x, const float* h,
-                           const int32_t* graph_ptr, const uint8_t* lig_flag, const uint8_t* gen_flag, int n_nodes,
-                           int n_graphs, float* x_out, void* workspace, size_t workspace_bytes, void* stream) {
+// the h2x blocks of a call run the ligand-row edge kernel (edge_h2x_lig.hip; no folded rows Qt): the caller's promise, the product
+// kernels, and CBGX_H2X_FOLD
+static bool h2x_lig_selected(unsigned flags) { return (flags & CBGX_FWD_GEN_IS_LIGAND) && g_edge_impl != 1 && h2x_fold_enabled(); }
+
+int cbgx_h2x_stack_forward_v2(const float* packed, int num_layers, const float* x, const float* h,
+                              const int32_t* graph_ptr, const uint8_t* lig_flag, const uint8_t* gen_flag, int n_nodes,
+                              int n_graphs, float* x_out, unsigned flags, void* workspace, size_t workspace_bytes, void* stream) {
     if (n_nodes < 0 || n_graphs < 0 || num_layers < 1) return fail(CBGX_E_INVALID, "h2x_stack: bad sizes");
+    if (flags & ~CBGX_FWD_GEN_IS_LIGAND) return fail(CBGX_E_INVALID, "h2x_stack: unknown flags 0x%x", flags);
     if (n_nodes == 0) return CBGX_OK;
     if (!packed || !x || !h || !graph_ptr || !lig_flag || !gen_flag || !x_out || !workspace)
         return fail(CBGX_E_INVALID, "h2x_stack: NULL pointer");
@@ -412,10 +417,18 @@ int cbgx_h2x_stack_forward(const float* packed, int num_layers, const float* x, 
     for (int l = 0; l < num_layers; ++l) {
         float* xn = (l == num_layers - 1) ? x_out : w.xbuf[l & 1];
         HIP_TRY(launch_attention(false, packed + GATE_SIZE + (size_t)l * ATT_SIZE, xc, h, w.nbr, w.deg, lig_flag, gen_flag,
-                                 w.e_w, n_nodes, b.P, b.Qt, b.q, xn, nullptr, w.act.rows, w.act.count, src.rows, src.count, s));
+                                 w.e_w, n_nodes, b.P, b.Qt, b.q, xn, nullptr, w.act.rows, w.act.count, src.rows, src.count, s,
+                                 h2x_lig_selected(flags)));
         xc = xn;
     }
     return CBGX_OK;
+}
+
+int cbgx_h2x_stack_forward(const float* packed, int num_layers, const float* x, const float* h,
+                           const int32_t* graph_ptr, const uint8_t* lig_flag, const uint8_t* gen_flag, int n_nodes,
+                           int n_graphs, float* x_out, void* workspace, size_t workspace_bytes, void* stream) {
+    return cbgx_h2x_stack_forward_v2(packed, num_layers, x, h, graph_ptr, lig_flag, gen_flag, n_nodes, n_graphs, x_out, 0u, workspace,
+                                     workspace_bytes, stream);
 }
 
 size_t cbgx_workspace_bytes(int n_nodes, int n_graphs) {
@@ -468,10 +481,11 @@ int cbgx_x2h_attention(const float* packed, int layer, const float* x, const flo
     return CBGX_OK;
 }
 
-int cbgx_h2x_attention(const float* packed, int layer, const float* x, const float* h, const int32_t* nbr,
-                       const int32_t* deg, const uint8_t* lig_flag, const uint8_t* gen_flag, const float* e_w,
-                       int n_nodes, float* x_out, float* delta_x, void* workspace, size_t workspace_bytes,
-                       void* stream) {
+int cbgx_h2x_attention_v2(const float* packed, int layer, const float* x, const float* h, const int32_t* nbr,
+                          const int32_t* deg, const uint8_t* lig_flag, const uint8_t* gen_flag, const float* e_w,
+                          int n_nodes, float* x_out, float* delta_x, unsigned flags, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    if (flags & ~CBGX_FWD_GEN_IS_LIGAND) return fail(CBGX_E_INVALID, "h2x_attention: unknown flags 0x%x", flags);
     if (n_nodes == 0) return CBGX_OK;
     if (!packed || !x || !h || !nbr || !deg || !lig_flag || !gen_flag || !e_w || !x_out || !workspace || layer < 0 ||
         n_nodes < 0)
@@ -481,8 +495,17 @@ int cbgx_h2x_attention(const float* packed, int layer, const float* x, const flo
     const NodeBufs& b = w.set[0];
     HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act.rows, w.act.count, (hipStream_t)stream));
     HIP_TRY(launch_attention(false, packed + h2x_off(layer), x, h, nbr, deg, lig_flag, gen_flag, e_w, n_nodes, b.P,
-                             b.Qt, b.q, x_out, delta_x, w.act.rows, w.act.count, nullptr, nullptr, (hipStream_t)stream));
+                             b.Qt, b.q, x_out, delta_x, w.act.rows, w.act.count, nullptr, nullptr, (hipStream_t)stream,
+                             h2x_lig_selected(flags)));
     return CBGX_OK;
+}
+
+int cbgx_h2x_attention(const float* packed, int layer, const float* x, const float* h, const int32_t* nbr,
+                       const int32_t* deg, const uint8_t* lig_flag, const uint8_t* gen_flag, const float* e_w,
+                       int n_nodes, float* x_out, float* delta_x, void* workspace, size_t workspace_bytes,
+                       void* stream) {
+    return cbgx_h2x_attention_v2(packed, layer, x, h, nbr, deg, lig_flag, gen_flag, e_w, n_nodes, x_out, delta_x, 0u, workspace,
+                                 workspace_bytes, stream);
 }
 
 int cbgx_node_stage(const float* packed, int layer, int x2h, const float* h, const uint8_t* lig_flag, int n_nodes,
@@ -533,6 +556,7 @@ struct Forward {
     unsigned flags; void* workspace; size_t workspace_bytes; hipStream_t s;
     Workspace w;
     bool cached, graph_cached, prune, dual;
+    bool h2x_lig;               // h2x blocks: ligand-row edge kernel, node stage without the fold (CBGX_FWD_GEN_IS_LIGAND)
     std::vector<LayerPlan> plan;
 };
 
@@ -666,7 +690,7 @@ static hipError_t node_x2h(const Forward& f, int l, const NodeBufs& b, const flo
 static hipError_t block_h2x(const Forward& f, int l, const NodeBufs& b, const float* xc, const float* hn, float* xn) {
     const Workspace& w = f.w;
     return launch_attention(false, f.packed + h2x_off(l), xc, hn, w.nbr, w.deg, f.lig_flag, f.gen_flag, w.e_w, f.n_nodes, b.P, b.Qt, b.q,
-                            xn, nullptr, w.act.rows, w.act.count, w.A1.rows, w.A1.count, f.s);
+                            xn, nullptr, w.act.rows, w.act.count, w.A1.rows, w.A1.count, f.s, f.h2x_lig);
 }
 
 // Small inputs (round 5): ONE stream and ONE node-stage launch per layer.  The h2x block of layer l and the x2h block of layer
@@ -694,11 +718,15 @@ static int forward_fused(const Forward& f) {
         HIP_TRY(edge_x2h(f, l, w.set[l & 1], xc, hc, hn));
         jobs.n = 0;
         add_node_stage_jobs(jobs, f.packed + h2x_off(l), w.set[2].P, w.set[2].q, w.set[2].Qt, w.act.rows, w.act.count, w.A1.rows,
-                            w.A1.count);
+                            w.A1.count, nullptr, f.h2x_lig);
         if (l + 1 < f.num_layers) add_x2h(jobs, l + 1);
         HIP_TRY(launch_node_stage_jobs(jobs, hn, f.lig_flag, f.n_nodes, s));
-        HIP_TRY(launch_edge_mfma(false, f.packed + h2x_off(l), xc, hn, w.set[2].P, w.set[2].Qt, w.nbr, w.deg, f.lig_flag, f.gen_flag, w.e_w,
-                                 f.n_nodes, xn, nullptr, w.act.rows, w.act.count, s));
+        if (f.h2x_lig)
+            HIP_TRY(launch_edge_h2x_lig(f.packed + h2x_off(l), xc, hn, w.set[2].P, w.set[2].q, w.nbr, w.deg, f.lig_flag, f.gen_flag, w.e_w,
+                                        f.n_nodes, xn, nullptr, w.act.rows, w.act.count, s));
+        else
+            HIP_TRY(launch_edge_mfma(false, f.packed + h2x_off(l), xc, hn, w.set[2].P, w.set[2].Qt, w.nbr, w.deg, f.lig_flag, f.gen_flag,
+                                     w.e_w, f.n_nodes, xn, nullptr, w.act.rows, w.act.count, s));
         xc = xn;
         hc = hn;
     }
@@ -756,7 +784,7 @@ static int forward_serial(const Forward& f) {
 
 static int forward_impl(Forward f) {
     if (f.n_nodes < 0 || f.n_graphs < 0 || f.num_layers < 1) return fail(CBGX_E_INVALID, "forward: bad sizes");
-    if (f.flags & ~CBGX_FWD_H_ON_SOURCES) return fail(CBGX_E_INVALID, "forward: unknown flags 0x%x", f.flags);
+    if (f.flags & ~(CBGX_FWD_H_ON_SOURCES | CBGX_FWD_GEN_IS_LIGAND)) return fail(CBGX_E_INVALID, "forward: unknown flags 0x%x", f.flags);
     if (f.n_nodes == 0) return CBGX_OK;
     if (!f.packed || !f.x || !f.h || !f.graph_ptr || !f.lig_flag || !f.gen_flag || !f.x_out || !f.workspace)
         return fail(CBGX_E_INVALID, "forward: NULL pointer");
@@ -783,6 +811,7 @@ static int forward_impl(Forward f) {
     f.prune = (f.h_out == nullptr || (f.flags & CBGX_FWD_H_ON_SOURCES)) && f.num_layers >= 3;
     // x2h layers run their (general, protein-only) list pairs (first-generation kernels: one list)
     f.dual = g_edge_impl != 1;
+    f.h2x_lig = h2x_lig_selected(f.flags);
     if (int rc = forward_graph_stage(f)) return rc;
     if (int rc = forward_list_stage(f)) return rc;
     plan_layers(f);
@@ -800,13 +829,21 @@ static int forward_impl(Forward f) {
                            f.w.set[0].P, f.logits, f.prune ? f.w.A1 : NodeList{nullptr, nullptr}, f.s);
 }
 
+int cbgx_unitransformer_forward_v2(const float* packed, int num_layers, int num_classes, const float* x, const float* h,
+                                   const int32_t* graph_ptr, const uint8_t* lig_flag, const uint8_t* gen_flag,
+                                   int n_nodes, int n_graphs, float* x_out, float* h_out, float* logits, unsigned flags,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    return forward_impl(Forward{packed, num_layers, num_classes, x, h, graph_ptr, lig_flag, gen_flag, n_nodes, n_graphs, x_out,
+                                h_out, logits, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, flags, workspace, workspace_bytes,
+                                (hipStream_t)stream});
+}
+
 int cbgx_unitransformer_forward(const float* packed, int num_layers, int num_classes, const float* x, const float* h,
                                 const int32_t* graph_ptr, const uint8_t* lig_flag, const uint8_t* gen_flag,
                                 int n_nodes, int n_graphs, float* x_out, float* h_out, float* logits, void* workspace,
                                 size_t workspace_bytes, void* stream) {
-    return forward_impl(Forward{packed, num_layers, num_classes, x, h, graph_ptr, lig_flag, gen_flag, n_nodes, n_graphs, x_out,
-                                h_out, logits, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, workspace, workspace_bytes,
-                                (hipStream_t)stream});
+    return cbgx_unitransformer_forward_v2(packed, num_layers, num_classes, x, h, graph_ptr, lig_flag, gen_flag, n_nodes, n_graphs,
+                                          x_out, h_out, logits, 0u, workspace, workspace_bytes, stream);
 }
 
 int cbgx_unitransformer_forward_cached(const float* packed, int num_layers, int num_classes, const float* x,

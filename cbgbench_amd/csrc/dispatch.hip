@@ -44,13 +44,16 @@ hipError_t launch_gate(const float* packed, const float* x, const int32_t* nbr, 
 hipError_t launch_attention(bool x2h, const float* att, const float* x, const float* h, const int32_t* nbr,
                             const int32_t* deg, const uint8_t* lig, const uint8_t* gen, const float* e_w, int n_nodes,
                             float* P, float* Qt, float* qbuf, float* out, float* dx_out, const int* act, const int* act_count,
-                            const int* src, const int* src_count, hipStream_t s) {
+                            const int* src, const int* src_count, hipStream_t s, bool h2x_lig) {
     if (n_nodes == 0) return hipSuccess;
 #ifdef CBGX_XCHECK
     if (g_edge_impl == 1) return launch_attention_v1(x2h, att, x, h, nbr, deg, lig, gen, e_w, n_nodes, P, Qt, out, dx_out, s);
 #endif
-    hipError_t e0 = launch_node_mfma(att, h, lig, n_nodes, P, qbuf, Qt, act, act_count, src, src_count, s, x2h);
+    h2x_lig = h2x_lig && !x2h && act != nullptr;
+    hipError_t e0 = launch_node_mfma(att, h, lig, n_nodes, P, qbuf, Qt, act, act_count, src, src_count, s, x2h, nullptr, nullptr, false,
+                                     h2x_lig);
     if (e0 != hipSuccess) return e0;
+    if (h2x_lig) return launch_edge_h2x_lig(att, x, h, P, qbuf, nbr, deg, lig, gen, e_w, n_nodes, out, dx_out, act, act_count, s);
     return launch_edge_mfma(x2h, att, x, h, P, Qt, nbr, deg, lig, gen, e_w, n_nodes, out, dx_out, act, act_count, s);
 }
 

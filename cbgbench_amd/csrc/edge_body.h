@@ -1,6 +1,7 @@
 // libcbgx -- the body of the fused x2h / h2x edge kernels, shared by the translation units that instantiate it: edge_mfma.hip
 // (exact-fp32 scores and aggregation, v_mfma_f32_16x16x4_f32) and edge_x2h_f16.hip (the same two contractions in split-f16
-// arithmetic on the f16 matrix pipe, template flag F16).  The including file defines `c_mu` (the rbf centres, __constant__) in
+// arithmetic on the f16 matrix pipe, template flag F16), and edge_h2x_lig.hip (h2x on ligand rows with the query folded in registers,
+// template flag HL).  The including file defines `c_mu` (the rbf centres, __constant__) in
 // namespace cbgx before this header.  See edge_mfma.hip for the algebra, the lane mappings and the memory pipeline.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -226,7 +227,10 @@ __device__ __forceinline__ int e1_id(int raw, int e, int d, int self) { return e
 // below) instead of exact-fp32 16x16x4 MFMAs.  Once per launch the workgroup scales the LayerNorm affine of both paths in its LDS
 // image by 2^kh, kh from the bound sqrt(127) max|gamma| + max|beta| of a LayerNorm output (split_exponent): the hidden activations
 // then leave LayerNorm + ReLU with their largest possible value in [2^14, 2^15) at no per-node cost.
-template <bool X2H, int WAVES, bool LISTED, bool PP, bool F16 = false>
+// HL (h2x, listed, edge_h2x_lig.hip): the ligand-row specialisation -- every listed destination is a ligand atom (the caller's promise,
+// CBGX_FWD_GEN_IS_LIGAND), so lig_i = 1, only edge types 0 and 2 occur and the LDS image (layout.h A_IMG_H2L) carries the second k Linear
+// next to the 16 rows of the second v Linear: the query is folded in k half 0 as in PP, `Qt` is the UNFOLDED query q[N,128].
+template <bool X2H, int WAVES, bool LISTED, bool PP, bool F16 = false, bool HL = false>
 __device__ __forceinline__ void edge_body(
     float* __restrict__ lds, float* __restrict__ lds_mu, const int wg, const int n_wg,
     const float* __restrict__ att, const float* __restrict__ x, const float* __restrict__ h,
@@ -237,8 +241,9 @@ __device__ __forceinline__ void edge_body(
     const int* __restrict__ act = LISTED ? act_arg : nullptr;
     static_assert(!PP || (X2H && LISTED), "the protein-only kernel is an x2h work-list kernel");
     static_assert(!F16 || X2H, "split-f16 scores and aggregation: x2h only");
+    static_assert(!HL || (!X2H && LISTED && !PP), "the ligand-row kernel is an h2x work-list kernel");
     static_assert(PP_IMG_SIZE == IMG_SIZE_X2H, "both x2h images fill the same LDS array");
-    constexpr int IMG = X2H ? (int)IMG_SIZE_X2H : (int)IMG_SIZE_H2X;
+    constexpr int IMG = X2H ? (int)IMG_SIZE_X2H : (HL ? (int)H2L_IMG_SIZE : (int)IMG_SIZE_H2X);
     // work list mode of h2x: x_out = x for every node that cannot move -- by all workgroups, also those without an item.  The
     // flag and the position are requested together (one round trip, not two), and a workgroup with items does this behind its
     // LDS fill's loads instead of in front of them.
@@ -299,7 +304,7 @@ __device__ __forceinline__ void edge_body(
     auto first_header = [&]() {
         const int i = __builtin_amdgcn_readfirstlane(act ? act[i_begin] : i_begin);
         g.node = i;
-        g.d = deg[i]; lig_first = PP ? 0 : lig[i];
+        g.d = deg[i]; lig_first = PP ? 0 : (HL ? 1 : lig[i]);
         g.xi = x[3 * i]; g.yi = x[3 * i + 1]; g.zi = x[3 * i + 2];
         const gptr nrow = sbase(nbr + (size_t)i * KNN);
         const unsigned oc = vop(4 * c), oq = vop(16 * q);
@@ -310,7 +315,7 @@ __device__ __forceinline__ void edge_body(
         // LDS fill: every load of the thread is requested before the first is written (19 float4 per thread for the x2h image).
         // Left as a plain loop the compiler emits load -> wait -> ds_write per iteration: 19 dependent L2 round trips, ~25 us at
         // the head of EVERY launch -- the whole duration of a small one (a 1-graph step is 18 such launches).
-        const floatx4* src = reinterpret_cast<const floatx4*>(att + (PP ? A_IMG_PP : A_IMG));
+        const floatx4* src = reinterpret_cast<const floatx4*>(att + (PP ? A_IMG_PP : (HL ? A_IMG_H2L : A_IMG)));
         floatx4* dst = reinterpret_cast<floatx4*>(lds);
         constexpr int NV = (IMG / 4 + WAVES * 64 - 1) / (WAVES * 64);
         if constexpr (WAVES >= 8) {
@@ -371,10 +376,12 @@ __device__ __forceinline__ void edge_body(
         __syncthreads();
     }
     // PP: the tables of edge type 3 sit at the head of the image; the table bases are biased so that etype() = 3 indexes them
-    const float* lds_fk = PP ? lds + PP_FRAG_K - 3 * 8 * (int)FRAG_BLK : lds + IMG_FRAG_K;
-    const float* lds_fv = PP ? lds + PP_FRAG_V - 3 * 8 * (int)FRAG_BLK : lds + IMG_FRAG_V;
-    const float* lds_dwt = lds + IMG_WT;     // (never read by PP: no ligand source)
-    const float* lds_ln = lds + (PP ? PP_LN : IMG_LN);
+    // HL: slots [k type 0 | v type 0 | k type 2 | v type 2]: etype() = 0 / 2 from a k base at slot 0 and a v base at slot 1; the dwt
+    // base is biased so that lig_i = 1 indexes the image's only pair of rows
+    const float* lds_fk = PP ? lds + PP_FRAG_K - 3 * 8 * (int)FRAG_BLK : (HL ? lds + H2L_FRAG : lds + IMG_FRAG_K);
+    const float* lds_fv = PP ? lds + PP_FRAG_V - 3 * 8 * (int)FRAG_BLK : (HL ? lds + H2L_FRAG + 8 * (int)FRAG_BLK : lds + IMG_FRAG_V);
+    const float* lds_dwt = HL ? lds + H2L_WT - 2 * H : lds + IMG_WT;     // (never read by PP: no ligand source)
+    const float* lds_ln = lds + (PP ? PP_LN : (HL ? H2L_LN : IMG_LN));
 
     if (!has_item) return;     // (after the barrier: this wave has done its share of the LDS fill)
     if (!CBGX_EDGE_EARLY_HEADER) first_header();
@@ -417,7 +424,7 @@ __device__ __forceinline__ void edge_body(
         // rows below: in the latency regime (one node per wave: the rows were requested a moment ago) the two round trips then
         // overlap instead of following each other -- the fold sits one short MFMA block behind the top of the iteration
         float4 q8a = {0.f, 0.f, 0.f, 0.f}, q8b = {0.f, 0.f, 0.f, 0.f};
-        if (PP && CBGX_EDGE_EARLY_LOADS) {
+        if ((PP || HL) && CBGX_EDGE_EARLY_LOADS) {
             const gptr qp = sbase(Qt + (size_t)i * H);
             const unsigned oq8 = vop(32 * c);
             q8a = ldo4(qp, oq8); q8b = ldo4(qp, oq8 + 16);
@@ -439,7 +446,7 @@ __device__ __forceinline__ void edge_body(
         const int inext = __builtin_amdgcn_readfirstlane(more ? (act ? act[k_next] : k_next) : i);
         ng.node = inext;
         const int nd_raw = deg[inext];
-        const int nlig_raw = PP ? 0 : ldob(sbase(lig), vop((unsigned)inext));
+        const int nlig_raw = PP ? 0 : (HL ? 1 : ldob(sbase(lig), vop((unsigned)inext)));
         const gptr xrow = sbase(x + 3 * (size_t)inext);
         const unsigned ozero = vop(0u);
         const float nx_raw = ldo1(xrow, ozero), ny_raw = ldo1(xrow, ozero + 4), nz_raw = ldo1(xrow, ozero + 8);
@@ -449,12 +456,12 @@ __device__ __forceinline__ void edge_body(
         __builtin_amdgcn_sched_barrier(0);
         // this node's folded query row (B operand of the score MFMAs): consumed after the first pre-activation block
         float4 qrow[8];
-        if (PP && !CBGX_EDGE_EARLY_LOADS) {
+        if ((PP || HL) && !CBGX_EDGE_EARLY_LOADS) {
             const gptr qp = sbase(Qt + (size_t)i * H);
             const unsigned oq8 = vop(32 * c);
             q8a = ldo4(qp, oq8); q8b = ldo4(qp, oq8 + 16);
         }
-        if (!PP) {
+        if (!PP && !HL) {
             const gptr qp = sbase(Qt + (size_t)i * HEADS * H);
             const unsigned oqr = vop((c * H + 4 * q) * 4);
 #pragma unroll
@@ -497,8 +504,9 @@ __device__ __forceinline__ void edge_body(
         // ---- k path: hidden (edge-major) -> scores -> softmax ------------------------------------------
         floatx4 sc[2];
         float qun = 1.f;
-        sc[0] = edge_major_half<true, PP, F16 ? 1 : 0>(acc0, lg0[0], 0, lds_fk, lds_dwt, lds_ln, R[0], has_prot, has_lig, lig_i, lane, q,
-                                                       PP ? lds + PP_WFOLD + 4 * lane : nullptr, qrow, sck, q8a, q8b, khk_inv, &qun);
+        sc[0] = edge_major_half<true, PP || HL, F16 ? 1 : 0>(acc0, lg0[0], 0, lds_fk, lds_dwt, lds_ln, R[0], has_prot, has_lig, lig_i, lane, q,
+                                                             PP ? lds + PP_WFOLD + 4 * lane : (HL ? lds + H2L_WFOLD + 4 * lane : nullptr),
+                                                             qrow, sck, q8a, q8b, khk_inv, &qun);
         __builtin_amdgcn_sched_barrier(0);
         // (b) next item: resolve its neighbour ids (they arrived during the first half), request their flags and
         // coordinates; then the second half of the PS_v gather and the gate values
@@ -795,7 +803,7 @@ __device__ __forceinline__ void edge_body(
             // ---- h2x: v hidden edge-major, wv[e][a] = Wbv[a] . hid_v[e] + bbv[a] -------------------------------
             floatx4 wv[2];
             {
-                const float* lds_brow = lds + IMG_WBV + 4 * lane;       // Wbv[head c][16 t + 4 q ..] at 256 t (layout.h)
+                const float* lds_brow = HL ? lds + H2L_WBV + 4 * lane : lds + IMG_WBV + 4 * lane;       // Wbv[head c][16 t + 4 q ..] at 256 t (layout.h)
                 floatx4 acc[8];
 #pragma unroll
                 for (int t = 0; t < 8; ++t) { vd[t] = make_float4(vd[t].x * scv.S, vd[t].y * scv.S, vd[t].z * scv.S, vd[t].w * scv.S); acc[t] = f4(vs0[t]) * scv.S + f4(vd[t]); }

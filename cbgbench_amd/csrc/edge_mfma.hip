@@ -262,7 +262,9 @@ hipError_t launch_pack_stage2(const PackBlocks& pb, hipStream_t s) {
     hipLaunchKernelGGL(pack_dwt_kernel, dim3(2, pb.n), dim3(256), 0, s, pb);
     hipLaunchKernelGGL(pack_wbv_swz_kernel, dim3(H * H / 256, pb.n), dim3(256), 0, s, pb);
     hipLaunchKernelGGL(pack_pp_image_kernel, dim3((PP_IMG_SIZE + 255) / 256, pb.n), dim3(256), 0, s, pb);
-    return hipGetLastError();
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return launch_pack_h2l_image(pb, s);      // h2x blocks: the ligand-row kernel's image (edge_h2x_lig.hip), from the general one
 }
 
 // cbgx_set_edge_workgroups (include/cbgx.h): upper bound of the persistent x2h grid, 0 = one workgroup per CU

@@ -31,10 +31,11 @@ hipError_t launch_node_gemm(const float* A, int lda, const float* Wt, const floa
                             int nout, int act, hipStream_t s, const int* rows = nullptr, const int* n_rows = nullptr);
 // node projection + query fold + fused edge kernel of one attention block.
 // x2h: out = h_out[N,128]; h2x: out = x_out[N,3], dx_out optional.
+// h2x_lig (h2x on a work list of ligand atoms, h2x_lig_selected): no fold in the node stage, edge_h2x_lig_kernel folds in registers
 hipError_t launch_attention(bool x2h, const float* att, const float* x, const float* h, const int32_t* nbr,
                             const int32_t* deg, const uint8_t* lig, const uint8_t* gen, const float* e_w, int n_nodes,
                             float* P, float* Qt, float* qbuf, float* out, float* dx_out, const int* act, const int* act_count,
-                            const int* src, const int* src_count, hipStream_t s);
+                            const int* src, const int* src_count, hipStream_t s, bool h2x_lig = false);
 // which generation of kernels the stage dispatchers (dispatch.hip) use: always the MFMA one in libcbgx.so; the test-only
 // library libcbgx_xcheck.so (-DCBGX_XCHECK) can switch to the first-generation VALU kernels at run time
 #ifdef CBGX_XCHECK
@@ -120,7 +121,7 @@ hipError_t launch_mark_nbr(const int* list, const int* count, int n_upper, const
 hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig, int n_nodes, float* P, float* qbuf,
                             float* Qt, const int* act, const int* act_count, const int* src, const int* src_count,
                             hipStream_t s, bool large_lists = false, const int* fold = nullptr, const int* fold_count = nullptr,
-                            bool q_direct = false);
+                            bool q_direct = false, bool no_fold = false);
 // CBGX_NODE_QDIRECT=0 in the environment: the inference forward keeps the projection -> query MLP chain (A/B runs, bit-identity tests)
 bool node_qdirect_enabled();
 // the fused node stage (node_stage_kernel, inputs of <= NODE_STAGE_MAX_ROWS rows) as a list of jobs on the same input features:
@@ -136,6 +137,7 @@ struct NodeStageJob {
     // general-role destinations only (the node or a neighbour is a ligand atom: ~28 % of a pocket), protein-only ones fold in
     // registers (edge_mfma.hip) -- 8 KB of stores per row saved for the others
     const uint8_t* fold_flag;
+    int no_fold;        // the stage ends with the query MLP: the edge kernel folds q itself (edge_h2x_lig.hip), Qt is not written
 };
 constexpr int NS_JOBS_MAX = 4;
 struct NodeStageJobs { NodeStageJob j[NS_JOBS_MAX]; int n; };
@@ -143,7 +145,8 @@ constexpr int NODE_STAGE_MAX_ROWS = 8192;   // up to here the latency-built fuse
 // the jobs of one attention block's node stage appended to `jobs` (same selection as launch_node_mfma's fused path): with a
 // destination list two jobs (own columns on `act`, PS columns on `src` -- all rows when src is NULL), without one job on all rows
 bool add_node_stage_jobs(NodeStageJobs& jobs, const float* att, float* P, float* qbuf, float* Qt, const int* act,
-                         const int* act_count, const int* src, const int* src_count, const uint8_t* fold_flag = nullptr);
+                         const int* act_count, const int* src, const int* src_count, const uint8_t* fold_flag = nullptr,
+                         bool no_fold = false);
 hipError_t launch_node_stage_jobs(const NodeStageJobs& jobs, const float* h, const uint8_t* lig, int n_nodes, hipStream_t s);
 // all node lists of a forward call in four launches (node_mfma.hip): three level kernels over flags + one multi-job compaction
 struct GraphFlags {
@@ -192,6 +195,13 @@ hipError_t launch_edge_x2h_dual(const float* att, const float* x, const float* h
                                 const float* qbuf, const int32_t* nbr, const int32_t* deg, const uint8_t* lig,
                                 const uint8_t* gen, const float* e_w, int n_nodes, float* out, const int* list_pp,
                                 const int* count_pp, const int* list_gen, const int* count_gen, bool full_layer, hipStream_t s);
+// edge_h2x_lig.hip: the h2x edge kernel for work lists of ligand atoms (query folded in registers from `qbuf` = q[N,128]), the pack
+// kernel of its LDS image (part of stage 2), and CBGX_H2X_FOLD (default on)
+hipError_t launch_edge_h2x_lig(const float* att, const float* x, const float* h, const float* P, const float* qbuf,
+                               const int32_t* nbr, const int32_t* deg, const uint8_t* lig, const uint8_t* gen, const float* e_w,
+                               int n_nodes, float* out, float* dx_out, const int* act, const int* act_count, hipStream_t s);
+hipError_t launch_pack_h2l_image(const PackBlocks& pb, hipStream_t s);
+bool h2x_fold_enabled();
 // edge_x2h_f16.hip: the same launch with scores and aggregation in split-f16 (called by launch_edge_x2h_dual, which owns the grid)
 void launch_edge_x2h_f16_grid(int grid, const float* att, const float* x, const float* h, const float* P, const float* Qt,
                               const float* qbuf, const int32_t* nbr, const int32_t* deg, const uint8_t* lig, const uint8_t* gen,

@@ -124,7 +124,23 @@ constexpr size_t A_IMG_PP = A_WQ1_CINV + H;
 // of node_query_kernel's swapped first product (node_mfma.hip): [part hi|lo][t 8][u 4][lane 64][8 f16], lane (c, q) <-> output
 // channel 16t + c, slot j of instruction u <-> k = 16 (2u + (j >> 2)) + 4q + (j & 3).  64 KB, copied verbatim into LDS.
 constexpr size_t A_NQ_FRAG = A_IMG_PP + PP_IMG_SIZE;
-constexpr size_t ATT_SIZE = A_NQ_FRAG + (size_t)H * H;
+// ---- h2x blocks: LDS image of the LIGAND-ROW edge kernel (edge_h2x_lig.hip): every destination is a ligand atom (lig_i = 1), so only
+// edge types 0 (lig -> lig) and 2 (prot -> lig) occur and the second v Linear is 16 rows -- which leaves room for the second k Linear:
+// the query is folded in registers as in the protein-only x2h role and Qt never exists for an h2x block.  One contiguous region:
+//   frag [4 slots][8 t][320]   slot 0 = type-0 slice of IMG_FRAG_K, 1 = type-0 of IMG_FRAG_V, 2 = type-2 of K, 3 = type-2 of V: with
+//                              the k base at slot 0 and the v base at slot 1, etype() = 0 / 2 indexes both as in the general image
+//   dwt [256]                  the lig_i = 1 rows (k | v) of IMG_WT        ln [4][128]   as IMG_LN
+//   wbv [8 t][64 lanes][4]     as IMG_WBV of an h2x block                  wfold [8 t][8 d][64 lanes][4]   as PP_WFOLD
+constexpr size_t H2L_FRAG = 0;
+constexpr size_t H2L_WT = H2L_FRAG + 4 * 8 * FRAG_BLK;
+constexpr size_t H2L_LN = H2L_WT + 2 * H;
+constexpr size_t H2L_WBV = H2L_LN + 4 * H;
+constexpr size_t H2L_WFOLD = H2L_WBV + (size_t)HEADS * H;
+constexpr size_t H2L_IMG_SIZE = H2L_WFOLD + (size_t)H * H;    // 29440 floats = 117760 B
+constexpr size_t A_IMG_H2L = A_NQ_FRAG + (size_t)H * H;
+static_assert((H2L_IMG_SIZE + G) * sizeof(float) <= 163840, "h2x ligand-row image + rbf centres: one CU's LDS");
+static_assert(A_IMG_H2L % 4 == 0 && H2L_IMG_SIZE % 4 == 0, "the image is copied as 16-byte vectors");
+constexpr size_t ATT_SIZE = A_IMG_H2L + H2L_IMG_SIZE;
 
 constexpr size_t LAYER_SIZE = 2 * ATT_SIZE;       // x2h then h2x
 

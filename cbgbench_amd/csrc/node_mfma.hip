@@ -741,7 +741,7 @@ __global__ __launch_bounds__(NW * 64, 4) void node_stage_kernel(NodeStageJobs jo
         // lgm bit r: row 4q + r is a ligand row; fm bit r: its folded query is wanted (phase 3) -- rows past the list's end: no
         const unsigned valid16 = n_rows - row0 >= 16 ? 0xffffu : (1u << (n_rows - row0)) - 1u;
         const unsigned lig16 = (unsigned)__ballot(lig_b != 0u) & 0xffffu;
-        const unsigned fold16 = (fold_flag ? (unsigned)__ballot(fold_b != 0u) & 0xffffu : 0xffffu) & valid16;
+        const unsigned fold16 = jb.no_fold ? 0u : (fold_flag ? (unsigned)__ballot(fold_b != 0u) & 0xffffu : 0xffffu) & valid16;
         const unsigned lgm = (lig16 >> (4 * q)) & 15u, fm = (fold16 >> (4 * q)) & 15u;
         {
             float inv;
@@ -1531,10 +1531,10 @@ constexpr unsigned CHUNKS_QH = 0x300u;    // the q-hidden columns: read by node_
 // (optional): the nodes that can be *sources* of those destinations; without it PS is produced for every node.
 
 bool add_node_stage_jobs(NodeStageJobs& jobs, const float* att, float* P, float* qbuf, float* Qt, const int* act,
-                         const int* act_count, const int* src, const int* src_count, const uint8_t* fold_flag) {
+                         const int* act_count, const int* src, const int* src_count, const uint8_t* fold_flag, bool no_fold) {
     if (jobs.n + (act ? 2 : 1) > NS_JOBS_MAX) return false;
-    jobs.j[jobs.n++] = NodeStageJob{att, P, qbuf, Qt, act, act_count, act ? CHUNKS_OWN : CHUNKS_ALL, 0, fold_flag};
-    if (act) jobs.j[jobs.n++] = NodeStageJob{att, P, qbuf, Qt, src, src_count, CHUNKS_PS, 1, nullptr};
+    jobs.j[jobs.n++] = NodeStageJob{att, P, qbuf, Qt, act, act_count, act ? CHUNKS_OWN : CHUNKS_ALL, 0, fold_flag, no_fold ? 1 : 0};
+    if (act) jobs.j[jobs.n++] = NodeStageJob{att, P, qbuf, Qt, src, src_count, CHUNKS_PS, 1, nullptr, 0};
     return true;
 }
 
@@ -1568,10 +1568,10 @@ bool node_qdirect_enabled() {
 
 // `fold` / `fold_count` (optional, x2h blocks of the inference path): the rows whose folded query Qt the edge stage will read -- the
 // GENERAL list of the layer; protein-only destinations fold in registers (edge_mfma.hip) and only need q.  Without it Qt is
-// produced for every destination.
+// produced for every destination.  `no_fold`: Qt is not produced at all (the stage ends with q: edge_h2x_lig.hip folds in registers).
 hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig, int n_nodes, float* P, float* qbuf,
                             float* Qt, const int* act, const int* act_count, const int* src, const int* src_count,
-                            hipStream_t s, bool large_lists, const int* fold, const int* fold_count, bool q_direct) {
+                            hipStream_t s, bool large_lists, const int* fold, const int* fold_count, bool q_direct, bool no_fold) {
     if (n_nodes == 0) return hipSuccess;
     const int tiles = (n_nodes + 63) / 64;
     const int grid = min(tiles, 512);
@@ -1623,7 +1623,7 @@ hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig
     if (fused) {
         NodeStageJobs jobs;
         jobs.n = 0;
-        add_node_stage_jobs(jobs, att, P, qbuf, Qt, act, act_count, src, src_count);
+        add_node_stage_jobs(jobs, att, P, qbuf, Qt, act, act_count, src, src_count, nullptr, no_fold);
         launch_node_stage_grid(jobs, h, lig, n_nodes, s);
     } else {
         if (direct)      // persistent 8-wave workgroups, one per CU on NQK_GRID of them
@@ -1631,7 +1631,9 @@ hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig
                                qbuf, n_nodes, act, act_count);
         else
             hipLaunchKernelGGL(node_qmlp_kernel, dim3(grid, small ? 2 : 1), dim3(256), 0, s, att, P, qbuf, n_nodes, act, act_count);
-        if (fold)    // heads spread over four workgroups per row tile: the list is a fraction of the nodes, of unknown length
+        if (no_fold) {
+            // the edge kernel reads q
+        } else if (fold)    // heads spread over four workgroups per row tile: the list is a fraction of the nodes, of unknown length
             hipLaunchKernelGGL(node_qfold_kernel<4>, dim3(grid, 4), dim3(256), 0, s, att, qbuf, Qt, n_nodes, fold, fold_count);
         else if (small)
             hipLaunchKernelGGL(node_qfold_kernel<4>, dim3(grid, 4), dim3(256), 0, s, att, qbuf, Qt, n_nodes, act, act_count);

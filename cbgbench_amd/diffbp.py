@@ -274,18 +274,19 @@ class CoMPredictor(nn.Module):
         return ws
 
     @torch.no_grad()
-    def stack_forward(self, x_in, h_in, graph_ptr, lig8, gen8):
-        """the raw output coordinates [N,3] of the H2X stack on its own kNN graph (one cbgx_h2x_stack_forward call)"""
+    def stack_forward(self, x_in, h_in, graph_ptr, lig8, gen8, gen_is_ligand=False):
+        """the raw output coordinates [N,3] of the H2X stack on its own kNN graph (one cbgx_h2x_stack_forward_v2 call;
+        ``gen_is_ligand``: CBGX_FWD_GEN_IS_LIGAND)"""
         dev = x_in.device
         N, B = x_in.shape[0], graph_ptr.numel() - 1
         lib = _native.lib()
         ws = self._stream_workspace(lib.cbgx_workspace_bytes(N, B), dev)
         x_out = torch.empty_like(x_in)
-        rc = lib.cbgx_h2x_stack_forward(
+        rc = lib.cbgx_h2x_stack_forward_v2(
             _native.ptr(self.packed_weights(dev)), self.num_layers, _native.ptr(x_in), _native.ptr(h_in),
             _native.ptr(graph_ptr), _native.ptr(lig8), _native.ptr(gen8), N, B, _native.ptr(x_out),
-            _native.ptr(ws), ws.numel(), _native.current_stream(dev))
-        _native.check(rc, "cbgx_h2x_stack_forward")
+            _native.FWD_GEN_IS_LIGAND if gen_is_ligand else 0, _native.ptr(ws), ws.numel(), _native.current_stream(dev))
+        _native.check(rc, "cbgx_h2x_stack_forward_v2")
         return x_out
 
     def stack_output(self, x_composed, h_composed, gen_flag_composed, lig_flag_composed, graph_ptr):
@@ -517,7 +518,9 @@ class DiffBP(BatchesInFlight, nn.Module):
         st = {"B": B, "N": n_rec + n_lig, "n_lig": n_lig, "x": x, "h": h, "x_lig": x_lig, "c_lig": c_lig, "bl": bl,
               "gen_l": gen_l, "batch_idx": batch_idx, "lig_flag": lig_flag, "gen_flag": gen_flag, "lig_rows": lig_rows,
               "graph_ptr": graph_ptr, "traj_x": None, "traj_c": None, "static_h": None}
-        if dev.type == "cuda" and static_cache and not bool(gen_r.any()):
+        # every movable row is a ligand row: the h2x blocks fold the query in the edge kernel (CBGX_FWD_GEN_IS_LIGAND)
+        st["gen_is_ligand"] = not bool(gen_r.any())
+        if dev.type == "cuda" and static_cache and st["gen_is_ligand"]:
             st["static_h"] = self.denoiser.static_context(x_rec, h[rec_rows], br, rec_rows, n_rec + n_lig)
         # operands of the native step kernels (include/cbgx.h: cbgx_targetdiff_prologue, cbgx_diffbp_epilogue); they need the
         # ligand arrays sorted by graph, which is how every collate of the reference lays them out
@@ -563,9 +566,10 @@ class DiffBP(BatchesInFlight, nn.Module):
         h[lig_rows] = self.context_embedder.embed_ligand(st["c_lig"])
         xo, ho, logits = self.denoiser(x=x, h=h, batch_idx=st["batch_idx"], lig_flag=st["lig_flag"], gen_flag=st["gen_flag"],
                                        graph_ptr=st["graph_ptr"], static_h=st["static_h"],
-                                       h_on_sources=st["static_h"] is not None)      # h' is only read by the CoM stack (its source rows)
+                                       h_on_sources=st["static_h"] is not None,      # h' is only read by the CoM stack (its source rows)
+                                       gen_is_ligand=st.get("gen_is_ligand", False))
         eps_t, eps_com = self.com_head(xo[lig_rows], bl, x, ho, st["gen_flag"], st["lig_flag"], st["batch_idx"],
-                                       graph_ptr=st["graph_ptr"])
+                                       graph_ptr=st["graph_ptr"])      # (its own signature is the reference's: no promise is passed on)
         eps, u = noise if noise is not None else (None, None)
         if self.denoise_structure:
             st["x_lig"] = self.pos_scheduler.backward_remove_noise(eps_t + eps_com, st["x_lig"], t, bl, gen_l, type="score",
@@ -592,8 +596,9 @@ class DiffBP(BatchesInFlight, nn.Module):
             _native.ptr(x), _native.ptr(h), stream), "cbgx_targetdiff_prologue")
         xo, ho, logits = self.denoiser(x=x, h=h, batch_idx=st["batch_idx"], lig_flag=st["lig_flag"], gen_flag=st["gen_flag"],
                                        graph_ptr=st["graph_ptr"], static_h=st["static_h"],
-                                       h_on_sources=st["static_h"] is not None)      # h' is only read by the CoM stack (its source rows)
-        x_com = self.com_head.stack_forward(x, ho, st["graph_ptr"], st["lig8"], st["gen8"])
+                                       h_on_sources=st["static_h"] is not None,      # h' is only read by the CoM stack (its source rows)
+                                       gen_is_ligand=st.get("gen_is_ligand", False))
+        x_com = self.com_head.stack_forward(x, ho, st["graph_ptr"], st["lig8"], st["gen8"], st.get("gen_is_ligand", False))
         if noise is not None:
             eps, u = noise[0].float().contiguous(), noise[1].float().contiguous()
         elif st.get("noise") is not None:      # counter mode: position normal and mask uniform of (atom, step)

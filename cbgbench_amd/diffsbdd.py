@@ -452,6 +452,8 @@ class DiffSBDD(BatchesInFlight, nn.Module):
               "lig_rows": lig_rows, "rec_rows": rec_rows, "graph_ptr": graph_ptr, "nxt": nxt, "drawn": draws is not None,
               "traj_x": None, "traj_c": None, "static_h": None, "frame": None}
         st.update(cn)
+        # every movable row is a ligand row: the h2x blocks fold the query in the edge kernel (CBGX_FWD_GEN_IS_LIGAND)
+        st["gen_is_ligand"] = not bool(gen_r.any())
         if keep_trajectory:
             st["traj_x"] = torch.empty(T + 1, n_lig, 3, dtype=torch.float32, device=dev)
             st["traj_c"] = torch.empty(T + 1, n_lig, C, dtype=torch.float32, device=dev)
@@ -468,7 +470,7 @@ class DiffSBDD(BatchesInFlight, nn.Module):
             st["x_lig"], st["c_lig"] = x_lig.contiguous(), c_lig.contiguous()
             x[rec_rows], x[lig_rows] = x_rec, x_lig
             h[lig_rows] = self.context_embedder.embed_ligand(c_lig)
-            if static_cache and not bool(gen_r.any()):
+            if static_cache and st["gen_is_ligand"]:
                 st["static_h"] = self.denoiser.static_context(x_rec, h[rec_rows], br, rec_rows, n_rec + n_lig)
                 if st["static_h"] is not None:
                     st["frame"] = torch.zeros(B, 3, dtype=torch.float32, device=dev)     # sum of the removed means so far
@@ -501,7 +503,7 @@ class DiffSBDD(BatchesInFlight, nn.Module):
         if st.get("native"):   # x / h already hold the current state
             xo, _, logits = self.denoiser(x=x, h=h, batch_idx=st["batch_idx"], lig_flag=st["lig_flag"],
                                           gen_flag=st["gen_flag"], graph_ptr=st["graph_ptr"], need_h=False,
-                                          static_h=st.get("static_h"))
+                                          static_h=st.get("static_h"), gen_is_ligand=st.get("gen_is_ligand", False))
             x_pred = xo[st["lig_rows"]]
             if st.get("frame") is not None:       # the composed x lives in the pocket's frame: back to true coordinates
                 x_pred = x_pred - st["frame"][st["bl"]]
@@ -510,7 +512,7 @@ class DiffSBDD(BatchesInFlight, nn.Module):
         x[st["lig_rows"]] = st["x_lig"]
         h[st["lig_rows"]] = self.context_embedder.embed_ligand(st["c_lig"])
         xo, _, logits = self.denoiser(x=x, h=h, batch_idx=st["batch_idx"], lig_flag=st["lig_flag"], gen_flag=st["gen_flag"],
-                                      graph_ptr=st["graph_ptr"], need_h=False)
+                                      graph_ptr=st["graph_ptr"], need_h=False, gen_is_ligand=st.get("gen_is_ligand", False))
         return xo[st["lig_rows"]], logits[st["lig_rows"]]
 
     @torch.no_grad()
@@ -543,7 +545,8 @@ class DiffSBDD(BatchesInFlight, nn.Module):
         n_lig, C, B = st["n_lig"], self.num_classes, st["B"]
         x, h, x_lig, c_lig, nxt = st["x"], st["h"], st["x_lig"], st["c_lig"], st["nxt"]
         xo, _, logits = self.denoiser(x=x, h=h, batch_idx=st["batch_idx"], lig_flag=st["lig_flag"], gen_flag=st["gen_flag"],
-                                      graph_ptr=st["graph_ptr"], need_h=False, static_h=st.get("static_h"))
+                                      graph_ptr=st["graph_ptr"], need_h=False, static_h=st.get("static_h"),
+                                      gen_is_ligand=st.get("gen_is_ligand", False))
         eps_x = eps_c = None
         if st.get("noise") is not None:     # counter mode: position and type normals of (atom, step)
             if self.denoise_structure:

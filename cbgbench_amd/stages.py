@@ -54,15 +54,17 @@ def x2h_attention(packed, layer, x, h, nbr, deg, lig_flag, e_w):
     return out
 
 
-def h2x_attention(packed, layer, x, h, nbr, deg, lig_flag, gen_flag, e_w):
+def h2x_attention(packed, layer, x, h, nbr, deg, lig_flag, gen_flag, e_w, gen_is_ligand=False):
+    """``gen_is_ligand``: CBGX_FWD_GEN_IS_LIGAND (cbgx_h2x_attention_v2)"""
     N = x.shape[0]
     x_out = torch.empty_like(x)
     dx = torch.empty_like(x)
     ws = _ws(N, x.device)
-    rc = _native.lib().cbgx_h2x_attention(_native.ptr(packed), layer, _native.ptr(x), _native.ptr(h),
-                                          _native.ptr(nbr), _native.ptr(deg), _native.ptr(lig_flag),
-                                          _native.ptr(gen_flag), _native.ptr(e_w), N, _native.ptr(x_out),
-                                          _native.ptr(dx), _native.ptr(ws), ws.numel(), _stream(x))
+    rc = _native.lib().cbgx_h2x_attention_v2(_native.ptr(packed), layer, _native.ptr(x), _native.ptr(h),
+                                             _native.ptr(nbr), _native.ptr(deg), _native.ptr(lig_flag),
+                                             _native.ptr(gen_flag), _native.ptr(e_w), N, _native.ptr(x_out),
+                                             _native.ptr(dx), _native.FWD_GEN_IS_LIGAND if gen_is_ligand else 0, _native.ptr(ws),
+                                             ws.numel(), _stream(x))
     _native.check(rc, "cbgx_h2x_attention")
     return x_out, dx
 
@@ -93,10 +95,10 @@ def node_stage(packed, layer, x2h, h, lig_flag, rows=None, q_direct=False, fill=
 
 
 def unitransformer_forward(packed, num_layers, num_classes, x, h, graph_ptr, lig_flag, gen_flag, static=None, graph_part=True,
-                           want_h=True, h_on_sources=False, ws=None, fill=None):
+                           want_h=True, h_on_sources=False, ws=None, fill=None, gen_is_ligand=False):
     """-> (x_out, h_out or None, logits): cbgx_unitransformer_forward, or with ``static`` (the tuple of
     ``UniTransformer.static_context``) cbgx_unitransformer_forward_cached -- ``graph_part=False`` hands over the static features only.
-    ``want_h=False``: h_out is NULL; ``h_on_sources``: CBGX_FWD_H_ON_SOURCES.  ``ws`` (uint8, at least cbgx_workspace_bytes(N, B)): the
+    ``want_h=False``: h_out is NULL; ``h_on_sources``: CBGX_FWD_H_ON_SOURCES; ``gen_is_ligand``: CBGX_FWD_GEN_IS_LIGAND.  ``ws`` (uint8, at least cbgx_workspace_bytes(N, B)): the
     caller's workspace, used as it is; ``fill``: what every output holds before the call."""
     N, B = x.shape[0], graph_ptr.numel() - 1
     x_out, h_out = _outputs(fill, x, h)
@@ -108,28 +110,30 @@ def unitransformer_forward(packed, num_layers, num_classes, x, h, graph_ptr, lig
     head = (_native.ptr(packed), num_layers, num_classes, _native.ptr(x), _native.ptr(h), _native.ptr(graph_ptr), _native.ptr(lig_flag),
             _native.ptr(gen_flag), N, B)
     tail = (_native.ptr(ws), ws.numel(), _stream(x))
+    flags = _native.FWD_GEN_IS_LIGAND if gen_is_ligand else 0
     if static is None:
         if h_on_sources:
             raise ValueError("unitransformer_forward: CBGX_FWD_H_ON_SOURCES is a flag of the cached entry point")
-        rc = _native.lib().cbgx_unitransformer_forward(*head, _native.ptr(x_out), _native.ptr(h_out), _native.ptr(logits), *tail)
+        rc = _native.lib().cbgx_unitransformer_forward_v2(*head, _native.ptr(x_out), _native.ptr(h_out), _native.ptr(logits), flags, *tail)
     else:
         graph = [_native.ptr(t) if graph_part else None for t in static[2:6]]
         rc = _native.lib().cbgx_unitransformer_forward_cached(*head, _native.ptr(static[0]), _native.ptr(static[1]), *graph,
                                                               _native.ptr(x_out), _native.ptr(h_out), _native.ptr(logits),
-                                                              1 if h_on_sources else 0, *tail)
+                                                              flags | (_native.FWD_H_ON_SOURCES if h_on_sources else 0), *tail)
     _native.check(rc, "cbgx_unitransformer_forward")
     return x_out, h_out, logits
 
 
-def h2x_stack_forward(packed, num_layers, x, h, graph_ptr, lig_flag, gen_flag, ws=None, fill=None):
+def h2x_stack_forward(packed, num_layers, x, h, graph_ptr, lig_flag, gen_flag, ws=None, fill=None, gen_is_ligand=False):
     """-> x_out [N,3] of cbgx_h2x_stack_forward (``packed``: cbgx_pack_h2x_stack).  ``ws`` / ``fill``: as in unitransformer_forward;
     the call leaves its graph stage (the gen_flag rows only) where ``forward_view`` finds nbr / deg / e_w."""
     N, B = x.shape[0], graph_ptr.numel() - 1
     x_out, = _outputs(fill, x)
     ws = torch.empty(_native.lib().cbgx_workspace_bytes(N, B), dtype=torch.uint8, device=x.device) if ws is None else ws
-    rc = _native.lib().cbgx_h2x_stack_forward(_native.ptr(packed), num_layers, _native.ptr(x), _native.ptr(h), _native.ptr(graph_ptr),
-                                              _native.ptr(lig_flag), _native.ptr(gen_flag), N, B, _native.ptr(x_out), _native.ptr(ws),
-                                              ws.numel(), _stream(x))
+    rc = _native.lib().cbgx_h2x_stack_forward_v2(_native.ptr(packed), num_layers, _native.ptr(x), _native.ptr(h), _native.ptr(graph_ptr),
+                                                 _native.ptr(lig_flag), _native.ptr(gen_flag), N, B, _native.ptr(x_out),
+                                                 _native.FWD_GEN_IS_LIGAND if gen_is_ligand else 0, _native.ptr(ws), ws.numel(),
+                                                 _stream(x))
     _native.check(rc, "cbgx_h2x_stack_forward")
     return x_out
 

@@ -767,7 +767,9 @@ class TargetDiff(BatchesInFlight, nn.Module):
                   lig_flag=lig_flag, gen_flag=gen_flag, lig_rows=lig_rows, graph_ptr=graph_ptr, B=B, n_lig=n_lig, N=N,
                   traj_x=None, traj_c=None)
         st["static_h"] = None
-        if dev.type == "cuda" and static_cache and not bool(gen_r.any()):
+        # every movable row is a ligand row: the h2x blocks fold the query in the edge kernel (CBGX_FWD_GEN_IS_LIGAND)
+        st["gen_is_ligand"] = not bool(gen_r.any())
+        if dev.type == "cuda" and static_cache and st["gen_is_ligand"]:
             # protein rows of (x, h) are the same in all T denoiser calls: cache the ligand-free first two layers once
             st["static_h"] = self.denoiser.static_context(x_rec, h[rec_rows], br, rec_rows, N)
         if dev.type == "cuda":
@@ -813,7 +815,8 @@ class TargetDiff(BatchesInFlight, nn.Module):
         x[lig_rows] = st["x_lig"]
         h[lig_rows] = self.context_embedder.embed_ligand(st["c_lig"])
         xo, _, logits = self.denoiser(x=x, h=h, batch_idx=st["batch_idx"], lig_flag=st["lig_flag"],
-                                      gen_flag=st["gen_flag"], graph_ptr=st["graph_ptr"])
+                                      gen_flag=st["gen_flag"], graph_ptr=st["graph_ptr"],
+                                      gen_is_ligand=st.get("gen_is_ligand", False))
         x_pred, c_pred = xo[lig_rows], logits[lig_rows]
         eps, u = noise if noise is not None else (None, None)
         if self.denoise_structure:
@@ -869,7 +872,7 @@ class TargetDiff(BatchesInFlight, nn.Module):
                 _native.ptr(st["x"]), _native.ptr(st["h"]), stream), "cbgx_targetdiff_prologue")
         xo, _, logits = self.denoiser(x=st["x"], h=st["h"], batch_idx=st["batch_idx"], lig_flag=st["lig_flag"],
                                       gen_flag=st["gen_flag"], graph_ptr=st["graph_ptr"], need_h=False,
-                                      static_h=st["static_h"])
+                                      static_h=st["static_h"], gen_is_ligand=st.get("gen_is_ligand", False))
         counter = st.get("noise") if noise is None else None
         if noise is not None:
             eps, u = noise[0].float().contiguous(), noise[1].float().contiguous()
@@ -935,7 +938,8 @@ class TargetDiff(BatchesInFlight, nn.Module):
             _native.ptr(st["x"]), _native.ptr(st["h"]), stream), "cbgx_targetdiff_prologue_traj")
         xo, _, logits = self.denoiser(x=st["x"], h=st["h"], batch_idx=st["batch_idx"], lig_flag=st["lig_flag"],
                                       gen_flag=st["gen_flag"], graph_ptr=st["graph_ptr"], need_h=False,
-                                      static_h=st["static_h"], workspace=st.get("_ws"))
+                                      static_h=st["static_h"], workspace=st.get("_ws"),
+                                      gen_is_ligand=st.get("gen_is_ligand", False))
         if st.get("noise") is not None:     # counter mode: the step index on the device is the counter's step; no noise node
             _native.check(lib.cbgx_targetdiff_epilogue_traj_rng(
                 _native.ptr(xo), _native.ptr(logits), _native.ptr(st["lig_rows32"]), _native.ptr(st["traj_x"]),

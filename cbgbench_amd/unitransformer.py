@@ -394,7 +394,7 @@ class UniTransformer(nn.Module):
         return u8
 
     def forward(self, x, h, batch_idx, lig_flag, gen_flag, graph_ptr=None, need_h=True, static_h=None,
-                ligand_outputs_only=False, workspace=None, h_on_sources=False):
+                ligand_outputs_only=False, workspace=None, h_on_sources=False, gen_is_ligand=False):
         """Same contract as the reference (unitransformer.py:102-123): returns (x', h', logits).
         ``batch_idx`` must be sorted (compose_context guarantees it).  ``graph_ptr`` (int32 CSR
         offsets) may be passed to avoid recomputing it from ``batch_idx`` every call.  ``need_h=False`` (samplers that
@@ -408,6 +408,8 @@ class UniTransformer(nn.Module):
         ``h_on_sources`` (inference, with ``static_h``): the caller reads ``h'`` only on the rows gen | lig | in-neighbours of gen
         rows -- what an H2X stack on the same coordinates reads (DiffBP's CoMPredictor) -- so the last two layers are pruned as
         with ``need_h=False``; the other rows of ``h'`` are undefined, the logits are defined on those rows only.
+        ``gen_is_ligand`` (inference): the caller promises that every ``gen_flag`` row is a ``lig_flag`` row (CBGX_FWD_GEN_IS_LIGAND): the
+        h2x blocks then fold the query inside the edge kernel and skip the folded rows.
         ``workspace`` (inference): caller-owned scratch memory of at least ``workspace_bytes(N, B)`` bytes instead of the per-stream
         one the module keeps -- a captured hipGraph bakes the pointer in, so every captured sampling state brings its own."""
         if not x.is_cuda:
@@ -439,18 +441,20 @@ class UniTransformer(nn.Module):
         h_out = torch.empty_like(h) if need_h else None
         logits = torch.empty(N, self.out_classes, dtype=torch.float32, device=device)
         lib = _native.lib()
+        flags = _native.FWD_GEN_IS_LIGAND if gen_is_ligand else 0
         if static_h is not None:
             rc = lib.cbgx_unitransformer_forward_cached(
                 _native.ptr(packed), self.num_layers, self.out_classes, _native.ptr(x), _native.ptr(h),
                 _native.ptr(graph_ptr), _native.ptr(lig), _native.ptr(gen), N, B, _native.ptr(static_h[0]),
                 _native.ptr(static_h[1]), *[_native.ptr(t) for t in static_h[2:6]], _native.ptr(x_out),
-                _native.ptr(h_out), _native.ptr(logits), 1 if (h_on_sources and need_h) else 0, _native.ptr(ws), ws.numel(),
+                _native.ptr(h_out), _native.ptr(logits), flags | (_native.FWD_H_ON_SOURCES if (h_on_sources and need_h) else 0),
+                _native.ptr(ws), ws.numel(),
                 _native.current_stream(device))
         else:
-            rc = lib.cbgx_unitransformer_forward(
+            rc = lib.cbgx_unitransformer_forward_v2(
                 _native.ptr(packed), self.num_layers, self.out_classes, _native.ptr(x), _native.ptr(h),
                 _native.ptr(graph_ptr), _native.ptr(lig), _native.ptr(gen), N, B,
-                _native.ptr(x_out), _native.ptr(h_out), _native.ptr(logits),
+                _native.ptr(x_out), _native.ptr(h_out), _native.ptr(logits), flags,
                 _native.ptr(ws), ws.numel(), _native.current_stream(device))
         _native.check(rc, "cbgx_unitransformer_forward")
         return x_out, h_out, logits

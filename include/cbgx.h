@@ -139,6 +139,20 @@ int cbgx_unitransformer_forward(const float *packed, int num_layers, int num_cla
  *   cbgx_h2x_stack_forward).  The last two x2h blocks are then pruned to the receptive field of those rows exactly as when
  *   h_out is NULL; rows of h_out outside A1 are left unwritten.  Without the flag h_out is defined on every row (no pruning). */
 #define CBGX_FWD_H_ON_SOURCES 1u
+/* CBGX_FWD_GEN_IS_LIGAND -- the caller promises gen_flag[i] != 0 => lig_flag[i] != 0 (every movable node is a ligand atom: what all
+ *   samplers of this project produce).  The h2x blocks then run the ligand-row edge kernel (csrc/edge_h2x_lig.hip), which folds the
+ *   query into the key's second Linear in registers; the folded rows Qt are neither written nor read for those blocks.  Same
+ *   arithmetic per edge; the fold itself is eight fp32 FMAs per value in place of two 16x16x4 fp32 MFMA steps.  Without the flag, or
+ *   with CBGX_H2X_FOLD=0 in the environment (read once per process), nothing changes, launches included.  A call that sets the flag
+ *   on inputs that break the promise gets undefined coordinates for the offending rows (no out-of-bounds access). */
+#define CBGX_FWD_GEN_IS_LIGAND 2u
+/* cbgx_unitransformer_forward with `flags` (CBGX_FWD_GEN_IS_LIGAND; CBGX_FWD_H_ON_SOURCES as in the cached call) */
+int cbgx_unitransformer_forward_v2(const float *packed, int num_layers, int num_classes,
+                                   const float *x, const float *h, const int32_t *graph_ptr,
+                                   const uint8_t *lig_flag, const uint8_t *gen_flag,
+                                   int n_nodes, int n_graphs,
+                                   float *x_out, float *h_out, float *logits, unsigned flags,
+                                   void *workspace, size_t workspace_bytes, void *stream);
 int cbgx_unitransformer_forward_cached(const float *packed, int num_layers, int num_classes,
                                        const float *x, const float *h, const int32_t *graph_ptr,
                                        const uint8_t *lig_flag, const uint8_t *gen_flag, int n_nodes, int n_graphs,
@@ -175,6 +189,11 @@ int cbgx_h2x_attention(const float *packed, int layer, const float *x, const flo
                        const int32_t *nbr, const int32_t *deg, const uint8_t *lig_flag,
                        const uint8_t *gen_flag, const float *e_w, int n_nodes,
                        float *x_out, float *delta_x, void *workspace, size_t workspace_bytes, void *stream);
+/* the same with `flags`: CBGX_FWD_GEN_IS_LIGAND (above) or 0 */
+int cbgx_h2x_attention_v2(const float *packed, int layer, const float *x, const float *h,
+                          const int32_t *nbr, const int32_t *deg, const uint8_t *lig_flag,
+                          const uint8_t *gen_flag, const float *e_w, int n_nodes,
+                          float *x_out, float *delta_x, unsigned flags, void *workspace, size_t workspace_bytes, void *stream);
 
 /* The node stage of one attention block on its own (stage-level tests): P[N,640] = h Wn + bn (PDk | PDv | PSk | PSv | q hidden),
  * q[N,128] = the query MLP and Qt[N,16,128] = the query folded into the key's second Linear, of denoiser.blocks[layer]'s x2h
@@ -199,6 +218,11 @@ int cbgx_h2x_stack_forward(const float *packed, int num_layers, const float *x, 
                            const int32_t *graph_ptr, const uint8_t *lig_flag, const uint8_t *gen_flag,
                            int n_nodes, int n_graphs, float *x_out, void *workspace, size_t workspace_bytes,
                            void *stream);
+/* the same with `flags`: CBGX_FWD_GEN_IS_LIGAND (above) or 0 */
+int cbgx_h2x_stack_forward_v2(const float *packed, int num_layers, const float *x, const float *h,
+                              const int32_t *graph_ptr, const uint8_t *lig_flag, const uint8_t *gen_flag,
+                              int n_nodes, int n_graphs, float *x_out, unsigned flags, void *workspace,
+                              size_t workspace_bytes, void *stream);
 
 /* ---- TargetDiff step prologue / epilogue ----------------------------------------------------------
  * The per-step work around the denoiser in TargetDiff.sample (repo/models/diffusion/targetdiff.py:150-182).
