@@ -258,6 +258,9 @@ hipError_t launch_ligand_bonds_count(const float* x_lig, const uint8_t* z_lig, c
 hipError_t launch_ligand_bonds_fill(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,
                                     const int32_t* bond_ptr, int n_bonds, int32_t* bond_index, uint8_t* bond_order, double* bond_length,
                                     hipStream_t s);
+// rings.hip: ring sizes (lengths of a minimum cycle basis) and the shortest ring through every atom, from that bond list; one wave per graph
+hipError_t launch_ligand_rings(const int32_t* lig_ptr, int n_lig, int n_graphs, const int32_t* bond_ptr, const int32_t* bond_index,
+                               int n_bonds, uint8_t* atom_ring_min, int32_t* graph_out, hipStream_t s);
 constexpr int PACK_MAX = 64;
 struct PackPiece {
     const float* src; float* dst; int src_ld, src_off, transpose, dst_ld, rows, cols;

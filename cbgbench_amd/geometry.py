@@ -17,7 +17,13 @@ library.
 list in (i, j) order with orders and float64 lengths, the connected components (``fragment``) and six integer facts per molecule
 (BOND_GRAPH_COLUMNS) -- in two launches with a prefix sum between (``cbgx_ligand_bonds_count`` / ``cbgx_ligand_bonds_fill``).  These are
 table bonds, not RDKit's: no aromaticity, no valence repair.  A molecule is ``connected`` iff it has one fragment: the table-bond
-counterpart of the reference's ``'.' not in smiles`` (repo/tools/rdkit_utils.py:597-640)."""
+counterpart of the reference's ``'.' not in smiles`` (repo/tools/rdkit_utils.py:597-640).
+
+``ligand_rings`` / ``batch_rings`` / ``summarise_rings`` answer what rings that graph holds: the number of rings of every size 3 ... 9 in a
+minimum cycle basis, the rings above 9, and the shortest ring through every atom, in one launch on the bond list (``cbgx_ligand_rings``,
+csrc/rings.hip) -- the RDKit-free counterpart of the ring statistics of ``evaluate_geom_single.py:27-33`` (``print_ring_ratio``) and
+``repo/tools/eval_ring_type.py``, which read the sizes of RDKit's ``AtomRings()``.  Deviations: table bonds; RDKit's SSSR is a heuristic
+that can differ from a minimum cycle basis on cage-like graphs."""
 import ctypes
 
 import numpy as np
@@ -230,3 +236,114 @@ def summarise_bonds(graph_counts):
     connected molecules (one fragment: the table-bond counterpart of the reference's ``'.' not in smiles``), the share of atoms in their
     molecule's largest fragment (what ``clean_frags`` would keep), fragments and cycles per molecule, bonds per atom; plus ``counts``"""
     return summarise_bond_totals(bond_totals(graph_counts))
+
+
+# ---- ring sizes of the table-bond graph ----------------------------------------------------------------------------------------------
+MAX_RING_SIZE, MAX_RING_ATOMS, MAX_RING_CYCLES = 9, 256, 128      # include/cbgx.h CBGX_RINGS_MAX_SIZE / _MAX_ATOMS / _MAX_CYCLES
+RING_SIZES = range(3, MAX_RING_SIZE + 1)
+# columns of ligand_rings' graph_counts (include/cbgx.h CBGX_RINGS_GRAPH_COLS)
+RING_GRAPH_COLUMNS = (("n_atoms", "n_bonds", "n_cycles") + tuple(f"rings_{k}" for k in RING_SIZES)
+                      + ("n_rings_larger", "n_ring_atoms", "status"))
+# status bits (include/cbgx.h CBGX_RINGS_*): a graph with status != 0 was not evaluated
+RINGS_TOO_MANY_ATOMS, RINGS_TOO_MANY_CYCLES, RINGS_BAD_BONDS = 1, 2, 4
+
+
+def ligand_rings(bond_index, lig_batch, n_graphs):
+    """Ring sizes of the bond graphs of ``n_graphs`` ligands, one launch (``cbgx_ligand_rings``, csrc/rings.hip; the definition is in
+    include/cbgx.h) on the tensors' current stream.
+
+    ``bond_index`` [2, n_bonds]: what ``ligand_bonds`` returns (global ligand rows, i < j, in (i, j) order); ``lig_batch`` [n_lig] the
+    graph index of every atom, grouped by graph.  Returns device tensors: ``atom_ring_min`` [n_lig] uint8, the length of the shortest
+    cycle through the atom (0: none of length <= 9), and ``graph_counts`` [n_graphs, 13] int32 (RING_GRAPH_COLUMNS): rings_k = the number
+    of cycles of length k in a minimum cycle basis, n_rings_larger = n_cycles - sum_k rings_k, n_ring_atoms, status.  A graph of more than
+    MAX_RING_ATOMS atoms, of more than MAX_RING_CYCLES independent cycles, or whose bonds are not such a list, is not an error: its status
+    is non-zero (RINGS_*), its columns from n_cycles to n_ring_atoms are -1 and its atoms' ``atom_ring_min`` 255.  There is no CPU
+    path."""
+    dev = bond_index.device
+    if dev.type != "cuda":
+        raise _native.NativeError("ligand_rings runs on the GPU (cbgx_ligand_rings): there is no CPU fallback")
+    n_graphs = int(n_graphs)
+    if lig_batch.device != dev:
+        raise ValueError(f"lig_batch is on {lig_batch.device}, bond_index on {dev}")
+    if bond_index.dim() != 2 or bond_index.shape[0] != 2:
+        raise ValueError("bond_index must be [2, n_bonds]")
+    n_lig, n_bonds = int(lig_batch.shape[0]), int(bond_index.shape[1])
+    if lig_batch.shape != (n_lig,):
+        raise ValueError("one graph index per atom")
+    lig_ptr = _csr(lig_batch, n_graphs, "lig_batch")
+    bond_index = bond_index.to(torch.int32).contiguous()
+    # bond_ptr as the bond entries define it: the bonds are sorted by their first atom, a is the first atom of bond_ptr[a] ... bond_ptr[a + 1]
+    first = bond_index[0].to(torch.long).clamp(0, max(n_lig - 1, 0))
+    counts = torch.bincount(first, minlength=n_lig) if n_lig else first.new_zeros(0)
+    bond_ptr = torch.cat([counts.new_zeros(1), counts.cumsum(0)]).to(torch.int32).contiguous()
+    atom_ring_min = torch.empty(n_lig, dtype=torch.uint8, device=dev)
+    graph_counts = torch.empty(n_graphs, len(RING_GRAPH_COLUMNS), dtype=torch.int32, device=dev)
+    p = _native.ptr
+    _native.check(_native.lib().cbgx_ligand_rings(p(lig_ptr), n_lig, n_graphs, p(bond_ptr), p(bond_index) if n_bonds else None, n_bonds,
+                                                  p(atom_ring_min), p(graph_counts), _native.current_stream(dev)), "cbgx_ligand_rings")
+    return {"atom_ring_min": atom_ring_min, "graph_counts": graph_counts}
+
+
+def batch_rings(batch, x, c, lig_batch, mode, bonds=None):
+    """``ligand_rings`` of a sampling state; ``bonds``: what ``batch_bonds`` returned for the same state (it is called here when None)"""
+    if bonds is None:
+        bonds = batch_bonds(batch, x, c, lig_batch, mode)
+    return ligand_rings(bonds["bond_index"], lig_batch.to(bonds["bond_index"].device), bonds["graph_counts"].shape[0])
+
+
+RING_COUNT_KEYS = (("n_mol", "n_mol_evaluated", "n_mol_over_limit", "n_atoms", "n_ring_atoms", "n_rings")
+                   + tuple(f"n_rings_{k}" for k in RING_SIZES) + ("n_rings_larger",)
+                   + tuple(f"n_mol_with_ring_{k}" for k in RING_SIZES) + ("n_mol_with_larger_ring",))
+RING_RATIOS = (tuple(f"ring_mol_ratio_{k}" for k in RING_SIZES) + tuple(f"rings_per_mol_{k}" for k in range(3, 9))
+               + tuple(f"ring_size_distribution_{k}" for k in range(3, 9)) + ("macrocycle_mol_ratio", "ring_atom_ratio"))
+
+
+def ring_totals(graph_counts):
+    """per-molecule counts ``graph_counts`` [n_mol, 13] (RING_GRAPH_COLUMNS; any array-like) -> the integer totals, in RING_COUNT_KEYS
+    order.  Everything but n_mol and n_mol_over_limit is summed over the evaluated molecules (status == 0) only; n_rings = n_cycles"""
+    if isinstance(graph_counts, torch.Tensor):
+        graph_counts = graph_counts.cpu().numpy()
+    gc = np.asarray(graph_counts, dtype=np.int64).reshape(-1, len(RING_GRAPH_COLUMNS))
+    ok = gc[gc[:, -1] == 0]
+    sizes = ok[:, 3:3 + len(RING_SIZES) + 1]                    # rings_3 ... rings_9, n_rings_larger
+    return ([int(gc.shape[0]), int(ok.shape[0]), int(gc.shape[0] - ok.shape[0]), int(ok[:, 0].sum()), int(ok[:, -2].sum()),
+             int(ok[:, 2].sum())] + [int(v) for v in sizes.sum(0)] + [int(v) for v in (sizes > 0).sum(0)])
+
+
+def summarise_ring_totals(totals):
+    """the ratios (RING_RATIOS) of integer totals in RING_COUNT_KEYS order, and the totals as ``counts``.  Every ratio is over the EVALUATED
+    molecules (n_mol_evaluated: status == 0) -- a molecule over a limit is counted in n_mol and n_mol_over_limit and nowhere else; a
+    ratio over nothing is nan.  ring_mol_ratio_k, k = 3 ... 9: the share of molecules with at least one ring of size k
+    (evaluate_geom_single.py:27-33, print_ring_ratio); rings_per_mol_k, k = 3 ... 8: rings of size k per molecule (eval_ring_type.py,
+    eval_ring_type_ratio); ring_size_distribution_k, k = 3 ... 8: the share of size k among the rings of those six sizes
+    (eval_ring_type_distribution); macrocycle_mol_ratio: the share of molecules with a ring above 9; ring_atom_ratio: ring atoms / atoms"""
+    c = {k: int(v) for k, v in zip(RING_COUNT_KEYS, totals)}
+    ratio = lambda a, b: a / b if b else float("nan")
+    n_mol = c["n_mol_evaluated"]
+    in_six = sum(c[f"n_rings_{k}"] for k in range(3, 9))
+    out = {f"ring_mol_ratio_{k}": ratio(c[f"n_mol_with_ring_{k}"], n_mol) for k in RING_SIZES}
+    out.update({f"rings_per_mol_{k}": ratio(c[f"n_rings_{k}"], n_mol) for k in range(3, 9)})
+    out.update({f"ring_size_distribution_{k}": ratio(c[f"n_rings_{k}"], in_six) for k in range(3, 9)})
+    out["macrocycle_mol_ratio"] = ratio(c["n_mol_with_larger_ring"], n_mol)
+    out["ring_atom_ratio"] = ratio(c["n_ring_atoms"], c["n_atoms"])
+    out["counts"] = c
+    return out
+
+
+def summarise_rings(graph_counts):
+    """ring statistics of a set of molecules from integer per-molecule counts (``graph_counts`` [n_mol, 13], RING_GRAPH_COLUMNS): see
+    ``summarise_ring_totals``; ratios are over the evaluated molecules only"""
+    return summarise_ring_totals(ring_totals(graph_counts))
+
+
+def ring_jsd(distribution, reference):
+    """Jensen-Shannon distance (the square root of the divergence, natural logarithm: ``scipy.spatial.distance.jensenshannon``) of two
+    ring-size distributions over the sizes 3 ... 8, e.g. ``ring_size_distribution_k`` of a job against a dataset's.  Both are normalised
+    to sum 1 first; the reference's numbers are the caller's own: none ship with this package"""
+    p, q = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (distribution, reference))
+    if p.shape != (6,) or q.shape != (6,):
+        raise ValueError("ring_jsd takes two vectors over the six ring sizes 3 ... 8")
+    p, q = p / p.sum(), q / q.sum()
+    mid = 0.5 * (p + q)
+    kl = lambda a, b: float(np.sum(np.where(a > 0, a * np.log(np.where(a > 0, a, 1.0) / np.where(a > 0, b, 1.0)), 0.0)))
+    return float(np.sqrt(max(0.5 * (kl(p, mid) + kl(q, mid)), 0.0)))

@@ -24,6 +24,9 @@ Output: ``{out_root}/{tag}/pocket_{i:05d}.pt`` with the final ligand positions, 
 (cbgbench_amd/geometry.py), and ``{out_dir}/geometry_summary.json`` for the job.
 ``--bonds`` adds the table-bond graph of every sample -- bond list, fragment labels, connectivity -- computed on the device in two
 launches per batch (``geometry.batch_bonds``), and ``{out_dir}/bonds_summary.json`` for the job.
+``--rings`` adds the ring sizes of that graph -- rings of every size 3 ... 9 in a minimum cycle basis, rings above 9, the shortest ring
+through every atom -- computed on the device in one more launch per batch (``geometry.batch_rings``), and
+``{out_dir}/rings_summary.json`` for the job.
 A checkpoint is the reference's format: ``{'config': ..., 'model': state_dict}`` (``sample.py:153-156``)."""
 import argparse
 import json
@@ -131,7 +134,8 @@ def main(argv=None, stats=None):
     """``stats`` (optional dict): filled with the wall seconds of the phases (setup = config + model + weights, batch = prior
     construction, sample = model.sample incl. the trajectory download, write = per-pocket records and files; with ``--geometry``
     also geometry = the report's launches, a part of write; with ``--bonds`` also bonds = the bond report's launches and downloads, a part
-    of write)."""
+    of write; with ``--rings`` also rings = the ring report's launch and downloads -- and the bond launches when ``--bonds`` is absent --,
+    a part of write)."""
     t_phase = time.perf_counter()
     phases = {"setup": 0.0, "batch": 0.0, "sample": 0.0, "write": 0.0}
 
@@ -187,6 +191,14 @@ def main(argv=None, stats=None):
                          "molecule, of the state the record holds, evaluated on the GPU in two launches per batch "
                          "(cbgbench_amd/geometry.py).  TABLE bonds from the stability metric's bond lengths, not RDKit's: no "
                          "aromaticity, no valence repair.  Independent of --geometry")
+    ap.add_argument("--rings", action="store_true",
+                    help="add the ring sizes of the table-bond graph to every sample (ring_sizes [7] = rings of size 3 ... 9 in a "
+                         "minimum cycle basis, n_rings_larger, atom_ring_min = the shortest ring through every atom, ring_status), a "
+                         "`rings` dict of counts to every pocket record and {out_dir}/rings_summary.json: the ring ratios of the "
+                         "reference's quality path, of the state the record holds, evaluated on the GPU in one launch per batch on the "
+                         "bond list (cbgbench_amd/geometry.py).  A sample above 256 atoms or 128 independent cycles is reported "
+                         "(ring_status != 0, sizes -1) and left out of the ratios.  Rings of TABLE bonds, not RDKit's SSSR.  Independent "
+                         "of --geometry and --bonds: without --bonds the bonds are computed and not written")
     ap.add_argument("--atom_num_dist", default=None,
                     help="the reference's size-conditioned ligand-size histogram (repo/datasets/transforms/_atom_num_dist.npy); "
                          "without it ligand sizes are U{10..45}")
@@ -207,6 +219,8 @@ def main(argv=None, stats=None):
         raise SystemExit("sample_cli: --geometry runs on the GPU (cbgx_ligand_geometry has no CPU fallback)")
     if args.bonds and dev.type != "cuda":
         raise SystemExit("sample_cli: --bonds runs on the GPU (cbgx_ligand_bonds_count / _fill have no CPU fallback)")
+    if args.rings and dev.type != "cuda":
+        raise SystemExit("sample_cli: --rings runs on the GPU (cbgx_ligand_rings has no CPU fallback)")
 
     ckpt_path = args.checkpoint or config.model.get("checkpoint", None)
     if ckpt_path and os.path.exists(ckpt_path):
@@ -262,6 +276,7 @@ def main(argv=None, stats=None):
         rng = np.random.default_rng([args.seed, rank])
     geometry_seconds, job_counts = [0.0], []             # --geometry: wall time of the report, per-sample counts of this rank
     bonds_seconds, job_bond_counts = [0.0], []           # --bonds: likewise
+    rings_seconds, job_ring_counts = [0.0], []           # --rings: likewise
 
     def write_results(ids, traj, batch):
         # sample.py:198-201 hands traj[0] to the reconstruction -- for targetdiff / diffbp that is the state entering the
@@ -276,13 +291,20 @@ def main(argv=None, stats=None):
             geo = geometry.batch_geometry(pocket, x.to(dev), c.to(dev), bidx.to(dev), mode)
             geo = {k: v.cpu() for k, v in geo.items()}       # (the download waits for the launch)
             geometry_seconds[0] += time.perf_counter() - t_geo
-        bonds = None
+        bonds = bonds_dev = None
         if args.bonds:
             # the same state in the same frame; proteins play no part
             t_bonds = time.perf_counter()
-            bonds = geometry.batch_bonds({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode)
-            bonds = {k: v.cpu() for k, v in bonds.items()}
+            bonds_dev = geometry.batch_bonds({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode)
+            bonds = {k: v.cpu() for k, v in bonds_dev.items()}
             bonds_seconds[0] += time.perf_counter() - t_bonds
+        rings = None
+        if args.rings:
+            # the same state again, on the bond list of --bonds when there is one (else the bonds are made here and not written)
+            t_rings = time.perf_counter()
+            rings = geometry.batch_rings({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode, bonds=bonds_dev)
+            rings = {k: v.cpu() for k, v in rings.items()}
+            rings_seconds[0] += time.perf_counter() - t_rings
         x, c, bidx = x.cpu(), c.cpu(), bidx.cpu()
         if translate:       # back to the frame the pockets came in (sample.py:198-199; here per graph: a batch holds many pockets)
             x = x + batch["ligand_translation"].cpu()
@@ -311,8 +333,20 @@ def main(argv=None, stats=None):
                 smp["fragment"] = bonds["fragment"][a0:atom_end[g]].clone()
                 smp["n_fragments"] = int(gc[g, 3])
                 smp["connected"] = int(gc[g, 3]) == 1
+        if rings is not None:
+            gc = rings["graph_counts"].to(torch.int64)
+            atom_end = gc[:, 0].cumsum(0).tolist()
+            for g, smp in enumerate(samples):
+                smp["ring_sizes"] = gc[g, 3:3 + len(geometry.RING_SIZES)].clone()
+                smp["n_rings_larger"] = int(gc[g, -3])
+                smp["atom_ring_min"] = rings["atom_ring_min"][atom_end[g] - int(gc[g, 0]):atom_end[g]].clone()
+                smp["ring_status"] = int(gc[g, -1])
         for k, pid in enumerate(ids):
             rec = {"pocket_index": pid, "samples": samples[k * num_samples:(k + 1) * num_samples]}
+            if rings is not None:
+                gc = rings["graph_counts"][k * num_samples:(k + 1) * num_samples].to(torch.int64)
+                job_ring_counts.append(gc)
+                rec["rings"] = geometry.summarise_rings(gc)["counts"]
             if bonds is not None:
                 gc = bonds["graph_counts"][k * num_samples:(k + 1) * num_samples].to(torch.int64)
                 job_bond_counts.append(gc)
@@ -359,6 +393,8 @@ def main(argv=None, stats=None):
             stats["geometry"] = geometry_seconds[0]
         if args.bonds:
             stats["bonds"] = bonds_seconds[0]
+        if args.rings:
+            stats["rings"] = rings_seconds[0]
     if args.geometry:
         # integer counts of all ranks, summed: the job's numbers do not depend on how the pockets were sharded
         totals = geometry.job_totals(torch.cat(job_counts) if job_counts else torch.zeros(0, len(geometry.GRAPH_COLUMNS)))
@@ -377,6 +413,17 @@ def main(argv=None, stats=None):
                 json.dump(summary, f, indent=1, sort_keys=True)
             print("bonds: " + ", ".join(f"{k} {summary[k]:.4f}" for k in geometry.BOND_RATIOS)
                   + f" ({summary['counts']['n_mol']} molecules, {summary['counts']['n_bonds']} bonds)")
+    if args.rings:
+        totals = geometry.ring_totals(torch.cat(job_ring_counts) if job_ring_counts
+                                      else torch.zeros(0, len(geometry.RING_GRAPH_COLUMNS)))
+        summary = geometry.summarise_ring_totals(sharding.sum_counts(totals, device=dev))
+        if rank == 0:
+            with open(os.path.join(out_dir, "rings_summary.json"), "w") as f:
+                json.dump(summary, f, indent=1, sort_keys=True)
+            cnt = summary["counts"]
+            print("rings: " + ", ".join(f"ring_mol_ratio_{k} {summary[f'ring_mol_ratio_{k}']:.4f}" for k in geometry.RING_SIZES)
+                  + f", macrocycle_mol_ratio {summary['macrocycle_mol_ratio']:.4f}, ring_atom_ratio {summary['ring_atom_ratio']:.4f}"
+                  + f" ({cnt['n_mol_evaluated']} of {cnt['n_mol']} molecules evaluated, {cnt['n_rings']} rings)")
     if rank == 0:
         print(f"sampled {len(pockets)} pockets x {num_samples} samples on {world} rank(s): "
               f"{gs / el:.1f} graph-steps/s, results in {out_dir}")

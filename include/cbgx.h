@@ -746,6 +746,50 @@ int cbgx_ligand_bonds_fill(const float *x_lig, const uint8_t *z_lig, const int32
                            const int32_t *bond_ptr, int n_bonds, int32_t *bond_index, uint8_t *bond_order, double *bond_length,
                            void *stream);
 
+/* ---- ring sizes of the table-bond graph of sampled ligands (rings.hip) ------------------------------------------------------------------
+ * What rings a sample's bond graph holds: the substructure diagnostic of the reference's quality path -- the share of molecules with a
+ *   ring of size 3 ... 9 (evaluate_scripts/evaluate_geom_single.py:27-33, print_ring_ratio), rings of size k per molecule and the
+ *   distribution over sizes 3 ... 8 (repo/tools/eval_ring_type.py, eval_ring_type_ratio / eval_ring_type_distribution) -- which the
+ *   reference takes from RDKit's mol.GetRingInfo().AtomRings() after reconstruction.  Here: from the bond list of cbgx_ligand_bonds_fill,
+ *   in ONE launch, one wave per graph, integer work only.
+ *   lig_ptr [B + 1] int32 (entries clamped to [0, n_lig]); bond_ptr [n_lig + 1] int32 and bond_index [2, n_bonds] int32 as
+ *   cbgx_ligand_bonds_fill defines them: global ligand rows, i < j, in strict (i, j) order.  Graph g's atoms are the rows lig_ptr[g] ...
+ *   lig_ptr[g + 1], its bonds the entries bond_ptr[lig_ptr[g]] ... bond_ptr[lig_ptr[g + 1]] of the list.
+ * Ring sizes: rings_k, k = 3 ... CBGX_RINGS_MAX_SIZE, is the number of cycles of length k in a minimum cycle basis of the graph.  The
+ *   multiset of lengths of a minimum cycle basis is unique (the cycle space over GF(2) is a matroid), so rings_k does not depend on which
+ *   basis is taken.  n_rings_larger = n_cycles - sum_k rings_k, n_cycles = n_bonds - n_atoms + n_components.  Computed as
+ *   rings_k = rank(S_k) - rank(S_(k-1)), S_k the GF(2) span of the edge vectors of all closed walks P_v(x) + P_v(y) + xy with
+ *   depth_v(x) + depth_v(y) + 1 <= k, over every root atom v and every bond xy that is not an edge of a breadth-first tree of v (any such
+ *   tree, cut at depth 4; P_v: the tree path from v).  Horton's candidate set contains a minimum cycle basis, a degenerate candidate is a
+ *   sum of cycles no longer than itself, and matroid greedy does the rest: the ranks depend neither on the trees nor on the order in which
+ *   candidates of one length are inserted.
+ *   This is the RDKit-free counterpart of the sizes of AtomRings(), which RDKit takes from its SSSR.  Deviations: these are table bonds;
+ *   RDKit's SSSR is a heuristic that can differ from a minimum cycle basis on cage-like graphs.
+ * atom_ring_min [n_lig] uint8: the length of the shortest cycle through the atom, 0 if there is none of length <= CBGX_RINGS_MAX_SIZE:
+ *   the minimum of depth(x) + depth(y) + 1 over the non-tree bonds xy of the breadth-first tree rooted at the atom whose ends hang under
+ *   different children of the root.
+ * graph_out [B, CBGX_RINGS_GRAPH_COLS] int32: n_atoms, n_bonds, n_cycles, rings_3 ... rings_9, n_rings_larger, n_ring_atoms (atoms with
+ *   atom_ring_min > 0), status.  Every element of both outputs is written for every graph, empty graphs and graphs without bonds included.
+ * Limits, per graph, reported in status and never an error: more than CBGX_RINGS_MAX_ATOMS atoms (CBGX_RINGS_TOO_MANY_ATOMS); n_cycles
+ *   above CBGX_RINGS_MAX_CYCLES (CBGX_RINGS_TOO_MANY_CYCLES; a graph within both limits has fewer than n_atoms + CBGX_RINGS_MAX_CYCLES
+ *   bonds, and one with that many or more is refused before anything is built); a list that is not what cbgx_ligand_bonds_fill writes
+ *   (CBGX_RINGS_BAD_BONDS): bond_ptr decreasing over the graph's atoms or outside [0, n_bonds], a bond of the graph's range whose rows
+ *   are not i < j inside the graph's atom range, or bonds out of strict (i, j) order.  With status != 0 the columns n_cycles ...
+ *   n_ring_atoms are -1 and atom_ring_min is 255 for the graph's atoms; n_atoms and n_bonds are the (clamped) sizes of the two ranges.
+ *   Every entry of lig_ptr, bond_ptr and bond_index is clamped or checked before it is used as an index: no content of the three arrays
+ *   makes the kernel read or write outside the buffers.  No atomics on memory; a graph's rows are a function of its own bonds.
+ * Returns 0, and 0 without a launch when B == 0.  CBGX_E_INVALID before any dereference or launch: negative counts, a NULL pointer with
+ *   a non-zero count (bond_index may be NULL when n_bonds == 0), lig_ptr the device cannot read. */
+#define CBGX_RINGS_MAX_SIZE 9
+#define CBGX_RINGS_MAX_ATOMS 256
+#define CBGX_RINGS_MAX_CYCLES 128
+#define CBGX_RINGS_GRAPH_COLS 13   /* n_atoms, n_bonds, n_cycles, rings_3 ... rings_9, n_rings_larger, n_ring_atoms, status */
+#define CBGX_RINGS_TOO_MANY_ATOMS 1
+#define CBGX_RINGS_TOO_MANY_CYCLES 2
+#define CBGX_RINGS_BAD_BONDS 4
+int cbgx_ligand_rings(const int32_t *lig_ptr, int n_lig, int n_graphs, const int32_t *bond_ptr, const int32_t *bond_index, int n_bonds,
+                      uint8_t *atom_ring_min, int32_t *graph_out, void *stream);
+
 /* ---- measurement hook (bench.py) ----------------------------------------------------------------
  * Between cbgx_profile_begin() and cbgx_profile_end() every kernel launch is bracketed by HIP events on
  * its own stream.  cbgx_profile_end() synchronises them and returns, per kernel class, the summed
