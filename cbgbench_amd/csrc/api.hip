@@ -858,32 +858,102 @@ int cbgx_unitransformer_forward_cached(const float* packed, int num_layers, int 
                                 workspace_bytes, (hipStream_t)stream});
 }
 
+// ---- the TargetDiff step entries: the two prologues and the six epilogues fill one aggregate; one check and one launch per kind -------
+static int noise_args(const char* who, const uint64_t* keys, const int32_t* lig_graph, bool need_graph, const int32_t* lig_ptr,
+                      int n_graphs, int purpose_base) {
+    if (!keys || !lig_ptr || (need_graph && !lig_graph)) return fail(CBGX_E_INVALID, "%s: NULL pointer (noise)", who);
+    if (n_graphs < 1) return fail(CBGX_E_INVALID, "%s: n_graphs=%d", who, n_graphs);
+    if (purpose_base < 0 || purpose_base % CBGX_NOISE_PURPOSE_STRIDE)
+        return fail(CBGX_E_INVALID, "%s: purpose_base=%d is not a non-negative multiple of %d", who, purpose_base,
+                    CBGX_NOISE_PURPOSE_STRIDE);
+    return CBGX_OK;
+}
+
+// what an epilogue entry was given (unset: not one of its arguments)
+struct StepArgs {
+    const char* who = "";       // the entry's short name: what its messages begin with
+    // the step: the denoiser's outputs, the ligand atoms' rows in them, the ligand state and where the next one goes, the step index
+    const float *x_den = nullptr, *logits = nullptr, *x_lig = nullptr, *c_lig = nullptr;
+    const int32_t* lig_rows = nullptr;
+    const uint8_t* gen_lig = nullptr;
+    int n_lig = 0, num_classes = 0, t = 0, num_timesteps = 0;
+    const float* const* tables = nullptr;
+    float *x_next = nullptr, *c_next = nullptr;
+    int32_t* v_next = nullptr;      // (optional)
+    // traj: x_lig / c_lig = x_next / c_next are the bases of the [T+1] slot arrays and the step index lives on the device
+    bool traj = false;
+    int32_t* t_dev = nullptr;
+    // the noise source: the tape pair (noise.eps / u), or the generator's operands (the other fields of `noise`)
+    bool counter = false;
+    StepNoise noise;
+    // boundary: the embedder's ligand rows and the composed arrays that the next denoiser call reads
+    bool boundary = false;
+    const float *lig_emb_w = nullptr, *lig_emb_b = nullptr, *ind_w = nullptr, *ind_b = nullptr;
+    float *x = nullptr, *h = nullptr;
+};
+
+// both prologue entries (t_dev: the trajectory one)
+static int step_prologue(const char* who, const float* x_lig, const float* c_lig, bool traj, const int32_t* t_dev,
+                         const int32_t* lig_rows, int n_lig, int num_classes, const float* lig_emb_w, const float* lig_emb_b,
+                         const float* ind_w, const float* ind_b, float* x, float* h, void* stream) {
+    if (n_lig == 0) return CBGX_OK;
+    if (n_lig < 0 || num_classes < 1 || num_classes > 32) return fail(CBGX_E_INVALID, "%s: bad sizes", who);
+    if (!x_lig || !c_lig || (traj && !t_dev) || !lig_rows || !lig_emb_w || !lig_emb_b || !ind_w || !ind_b || !x || !h)
+        return fail(CBGX_E_INVALID, "%s: NULL pointer", who);
+    HIP_TRY(launch_step_prologue(x_lig, c_lig, lig_rows, n_lig, num_classes, lig_emb_w, lig_emb_b, ind_w, ind_b, x, h,
+                                 (hipStream_t)stream, t_dev));
+    return CBGX_OK;
+}
+
+// the checks of an epilogue entry, none of which touches the device: sizes, NULL pointers, the seven tables, the noise operands
+static int step_epilogue_check(const StepArgs& a) {
+    if (a.n_lig < 0 || a.num_classes < 1 || a.num_classes > 32 || (!a.traj && (a.t < 0 || a.t >= a.num_timesteps))) {
+        if (a.traj) return fail(CBGX_E_INVALID, "%s: bad sizes", a.who);
+        return fail(CBGX_E_INVALID, "%s: bad sizes (n_lig=%d C=%d t=%d T=%d)", a.who, a.n_lig, a.num_classes, a.t, a.num_timesteps);
+    }
+    if (!a.x_den || !a.logits || !a.lig_rows || !a.x_lig || !a.c_lig || !a.gen_lig || !a.tables || !a.x_next || !a.c_next ||
+        (a.traj && !a.t_dev) || (!a.counter && (!a.noise.eps || !a.noise.u)) ||
+        (a.boundary && (!a.lig_emb_w || !a.lig_emb_b || !a.ind_w || !a.ind_b || !a.x || !a.h)))
+        return fail(CBGX_E_INVALID, "%s: NULL pointer", a.who);
+    for (int i = 0; i < 7; ++i)
+        if (!a.tables[i]) return fail(CBGX_E_INVALID, "%s: table %d is NULL", a.who, i);
+    if (a.counter)
+        return noise_args(a.who, a.noise.keys, a.noise.lig_graph, true, a.noise.lig_ptr, a.noise.n_graphs, a.noise.purpose_base);
+    return CBGX_OK;
+}
+
+static int step_epilogue(const StepArgs& a, void* stream) {
+    if (a.n_lig == 0) return CBGX_OK;
+    if (int rc = step_epilogue_check(a)) return rc;
+    const float log_c = (float)log((double)a.num_classes);
+    if (a.boundary)
+        HIP_TRY(launch_step_boundary(a.x_den, a.logits, a.lig_rows, a.x_lig, a.c_lig, a.gen_lig, a.n_lig, a.num_classes, a.t, a.tables,
+                                     log_c, a.noise, a.x_next, a.c_next, a.lig_emb_w, a.lig_emb_b, a.ind_w, a.ind_b, a.x, a.h,
+                                     (hipStream_t)stream));
+    else
+        HIP_TRY(launch_step_epilogue(a.x_den, a.logits, a.lig_rows, a.x_lig, a.c_lig, a.gen_lig, a.n_lig, a.num_classes, a.t, a.tables,
+                                     log_c, a.noise, a.x_next, a.c_next, a.v_next, (hipStream_t)stream, a.t_dev));
+    return CBGX_OK;
+}
+
 int cbgx_targetdiff_prologue(const float* x_lig, const float* c_lig, const int32_t* lig_rows, int n_lig, int num_classes,
                              const float* lig_emb_w, const float* lig_emb_b, const float* ind_w, const float* ind_b,
                              float* x, float* h, void* stream) {
-    if (n_lig == 0) return CBGX_OK;
-    if (n_lig < 0 || num_classes < 1 || num_classes > 32) return fail(CBGX_E_INVALID, "prologue: bad sizes");
-    if (!x_lig || !c_lig || !lig_rows || !lig_emb_w || !lig_emb_b || !ind_w || !ind_b || !x || !h)
-        return fail(CBGX_E_INVALID, "prologue: NULL pointer");
-    HIP_TRY(launch_step_prologue(x_lig, c_lig, lig_rows, n_lig, num_classes, lig_emb_w, lig_emb_b, ind_w, ind_b, x, h,
-                                 (hipStream_t)stream));
-    return CBGX_OK;
+    return step_prologue("prologue", x_lig, c_lig, false, nullptr, lig_rows, n_lig, num_classes, lig_emb_w, lig_emb_b, ind_w, ind_b, x, h,
+                         stream);
 }
 
 int cbgx_targetdiff_epilogue(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
                              const float* c_lig, const uint8_t* gen_lig, int n_lig, int num_classes, int t,
                              int num_timesteps, const float* const* tables, const float* eps, const float* u,
                              float* x_next, float* c_next, int32_t* v_next, void* stream) {
-    if (n_lig == 0) return CBGX_OK;
-    if (n_lig < 0 || num_classes < 1 || num_classes > 32 || t < 0 || t >= num_timesteps)
-        return fail(CBGX_E_INVALID, "epilogue: bad sizes (n_lig=%d C=%d t=%d T=%d)", n_lig, num_classes, t, num_timesteps);
-    if (!x_den || !logits || !lig_rows || !x_lig || !c_lig || !gen_lig || !tables || !eps || !u || !x_next || !c_next)
-        return fail(CBGX_E_INVALID, "epilogue: NULL pointer");
-    for (int i = 0; i < 7; ++i)
-        if (!tables[i]) return fail(CBGX_E_INVALID, "epilogue: table %d is NULL", i);
-    HIP_TRY(launch_step_epilogue(x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig, num_classes, t, tables,
-                                 (float)log((double)num_classes), eps, u, x_next, c_next, v_next, (hipStream_t)stream));
-    return CBGX_OK;
+    StepArgs a;
+    a.who = "epilogue";
+    a.x_den = x_den, a.logits = logits, a.lig_rows = lig_rows, a.x_lig = x_lig, a.c_lig = c_lig, a.gen_lig = gen_lig;
+    a.n_lig = n_lig, a.num_classes = num_classes, a.t = t, a.num_timesteps = num_timesteps, a.tables = tables;
+    a.noise.eps = eps, a.noise.u = u;
+    a.x_next = x_next, a.c_next = c_next, a.v_next = v_next;
+    return step_epilogue(a, stream);
 }
 
 int cbgx_targetdiff_step_boundary(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
@@ -891,18 +961,14 @@ int cbgx_targetdiff_step_boundary(const float* x_den, const float* logits, const
                                   int num_timesteps, const float* const* tables, const float* eps, const float* u,
                                   float* x_next, float* c_next, const float* lig_emb_w, const float* lig_emb_b,
                                   const float* ind_w, const float* ind_b, float* x, float* h, void* stream) {
-    if (n_lig == 0) return CBGX_OK;
-    if (n_lig < 0 || num_classes < 1 || num_classes > 32 || t < 0 || t >= num_timesteps)
-        return fail(CBGX_E_INVALID, "step_boundary: bad sizes (n_lig=%d C=%d t=%d T=%d)", n_lig, num_classes, t, num_timesteps);
-    if (!x_den || !logits || !lig_rows || !x_lig || !c_lig || !gen_lig || !tables || !eps || !u || !x_next || !c_next ||
-        !lig_emb_w || !lig_emb_b || !ind_w || !ind_b || !x || !h)
-        return fail(CBGX_E_INVALID, "step_boundary: NULL pointer");
-    for (int i = 0; i < 7; ++i)
-        if (!tables[i]) return fail(CBGX_E_INVALID, "step_boundary: table %d is NULL", i);
-    HIP_TRY(launch_step_boundary(x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig, num_classes, t, tables,
-                                 (float)log((double)num_classes), eps, u, x_next, c_next, lig_emb_w, lig_emb_b, ind_w, ind_b, x, h,
-                                 (hipStream_t)stream));
-    return CBGX_OK;
+    StepArgs a;
+    a.who = "step_boundary";
+    a.x_den = x_den, a.logits = logits, a.lig_rows = lig_rows, a.x_lig = x_lig, a.c_lig = c_lig, a.gen_lig = gen_lig;
+    a.n_lig = n_lig, a.num_classes = num_classes, a.t = t, a.num_timesteps = num_timesteps, a.tables = tables;
+    a.noise.eps = eps, a.noise.u = u;
+    a.x_next = x_next, a.c_next = c_next;
+    a.boundary = true, a.lig_emb_w = lig_emb_w, a.lig_emb_b = lig_emb_b, a.ind_w = ind_w, a.ind_b = ind_b, a.x = x, a.h = h;
+    return step_epilogue(a, stream);
 }
 
 int cbgx_diffbp_epilogue(const float* x_den, const float* x_com, const float* x_in, const float* logits,
@@ -946,41 +1012,24 @@ int cbgx_diffsbdd_step(const float* x_den, const float* logits, const int32_t* g
 int cbgx_targetdiff_prologue_traj(const float* traj_x, const float* traj_c, const int32_t* t_dev, const int32_t* lig_rows,
                                   int n_lig, int num_classes, const float* lig_emb_w, const float* lig_emb_b,
                                   const float* ind_w, const float* ind_b, float* x, float* h, void* stream) {
-    if (n_lig == 0) return CBGX_OK;
-    if (n_lig < 0 || num_classes < 1 || num_classes > 32) return fail(CBGX_E_INVALID, "prologue_traj: bad sizes");
-    if (!traj_x || !traj_c || !t_dev || !lig_rows || !lig_emb_w || !lig_emb_b || !ind_w || !ind_b || !x || !h)
-        return fail(CBGX_E_INVALID, "prologue_traj: NULL pointer");
-    HIP_TRY(launch_step_prologue(traj_x, traj_c, lig_rows, n_lig, num_classes, lig_emb_w, lig_emb_b, ind_w, ind_b, x, h,
-                                 (hipStream_t)stream, t_dev));
-    return CBGX_OK;
+    return step_prologue("prologue_traj", traj_x, traj_c, true, t_dev, lig_rows, n_lig, num_classes, lig_emb_w, lig_emb_b, ind_w, ind_b,
+                         x, h, stream);
 }
 
 int cbgx_targetdiff_epilogue_traj(const float* x_den, const float* logits, const int32_t* lig_rows, float* traj_x,
                                   float* traj_c, const uint8_t* gen_lig, int n_lig, int num_classes, int32_t* t_dev,
                                   const float* const* tables, const float* eps, const float* u, void* stream) {
-    if (n_lig == 0) return CBGX_OK;
-    if (n_lig < 0 || num_classes < 1 || num_classes > 32) return fail(CBGX_E_INVALID, "epilogue_traj: bad sizes");
-    if (!x_den || !logits || !lig_rows || !traj_x || !traj_c || !gen_lig || !t_dev || !tables || !eps || !u)
-        return fail(CBGX_E_INVALID, "epilogue_traj: NULL pointer");
-    for (int i = 0; i < 7; ++i)
-        if (!tables[i]) return fail(CBGX_E_INVALID, "epilogue_traj: table %d is NULL", i);
-    HIP_TRY(launch_step_epilogue(x_den, logits, lig_rows, traj_x, traj_c, gen_lig, n_lig, num_classes, 0, tables,
-                                 (float)log((double)num_classes), eps, u, traj_x, traj_c, nullptr, (hipStream_t)stream,
-                                 t_dev));
-    return CBGX_OK;
+    StepArgs a;
+    a.who = "epilogue_traj";
+    a.x_den = x_den, a.logits = logits, a.lig_rows = lig_rows, a.x_lig = traj_x, a.c_lig = traj_c, a.gen_lig = gen_lig;
+    a.n_lig = n_lig, a.num_classes = num_classes, a.tables = tables;
+    a.noise.eps = eps, a.noise.u = u;
+    a.x_next = traj_x, a.c_next = traj_c;
+    a.traj = true, a.t_dev = t_dev;
+    return step_epilogue(a, stream);
 }
 
 // ---- counter-based noise (rng.h): the fill entry and the TargetDiff step entries that generate in place ------------------------------
-static int noise_args(const char* who, const uint64_t* keys, const int32_t* lig_graph, bool need_graph, const int32_t* lig_ptr,
-                      int n_graphs, int purpose_base) {
-    if (!keys || !lig_ptr || (need_graph && !lig_graph)) return fail(CBGX_E_INVALID, "%s: NULL pointer (noise)", who);
-    if (n_graphs < 1) return fail(CBGX_E_INVALID, "%s: n_graphs=%d", who, n_graphs);
-    if (purpose_base < 0 || purpose_base % CBGX_NOISE_PURPOSE_STRIDE)
-        return fail(CBGX_E_INVALID, "%s: purpose_base=%d is not a non-negative multiple of %d", who, purpose_base,
-                    CBGX_NOISE_PURPOSE_STRIDE);
-    return CBGX_OK;
-}
-
 int cbgx_noise_fill(const uint64_t* stream_keys, const int32_t* lig_ptr, int n_graphs, int n_lig, int cols, int uniform,
                     int purpose, int step, const int32_t* step_dev, float* out, void* stream) {
     if (n_lig == 0 || n_graphs == 0 || cols == 0) return CBGX_OK;
@@ -998,18 +1047,14 @@ int cbgx_targetdiff_epilogue_rng(const float* x_den, const float* logits, const 
                                  int num_timesteps, const float* const* tables, const uint64_t* stream_keys,
                                  const int32_t* lig_graph, const int32_t* lig_ptr, int n_graphs, int purpose_base, float* x_next,
                                  float* c_next, int32_t* v_next, void* stream) {
-    if (n_lig == 0) return CBGX_OK;
-    if (n_lig < 0 || num_classes < 1 || num_classes > 32 || t < 0 || t >= num_timesteps)
-        return fail(CBGX_E_INVALID, "epilogue_rng: bad sizes (n_lig=%d C=%d t=%d T=%d)", n_lig, num_classes, t, num_timesteps);
-    if (!x_den || !logits || !lig_rows || !x_lig || !c_lig || !gen_lig || !tables || !x_next || !c_next)
-        return fail(CBGX_E_INVALID, "epilogue_rng: NULL pointer");
-    for (int i = 0; i < 7; ++i)
-        if (!tables[i]) return fail(CBGX_E_INVALID, "epilogue_rng: table %d is NULL", i);
-    if (int rc = noise_args("epilogue_rng", stream_keys, lig_graph, true, lig_ptr, n_graphs, purpose_base)) return rc;
-    HIP_TRY(launch_step_epilogue_rng(x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig, num_classes, t, tables,
-                                     (float)log((double)num_classes), stream_keys, lig_graph, lig_ptr, (uint32_t)purpose_base,
-                                     x_next, c_next, v_next, (hipStream_t)stream));
-    return CBGX_OK;
+    StepArgs a;
+    a.who = "epilogue_rng";
+    a.x_den = x_den, a.logits = logits, a.lig_rows = lig_rows, a.x_lig = x_lig, a.c_lig = c_lig, a.gen_lig = gen_lig;
+    a.n_lig = n_lig, a.num_classes = num_classes, a.t = t, a.num_timesteps = num_timesteps, a.tables = tables;
+    a.counter = true, a.noise.keys = stream_keys, a.noise.lig_graph = lig_graph, a.noise.lig_ptr = lig_ptr;
+    a.noise.n_graphs = n_graphs, a.noise.purpose_base = purpose_base;
+    a.x_next = x_next, a.c_next = c_next, a.v_next = v_next;
+    return step_epilogue(a, stream);
 }
 
 int cbgx_targetdiff_step_boundary_rng(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
@@ -1018,36 +1063,30 @@ int cbgx_targetdiff_step_boundary_rng(const float* x_den, const float* logits, c
                                       const int32_t* lig_graph, const int32_t* lig_ptr, int n_graphs, int purpose_base,
                                       float* x_next, float* c_next, const float* lig_emb_w, const float* lig_emb_b,
                                       const float* ind_w, const float* ind_b, float* x, float* h, void* stream) {
-    if (n_lig == 0) return CBGX_OK;
-    if (n_lig < 0 || num_classes < 1 || num_classes > 32 || t < 0 || t >= num_timesteps)
-        return fail(CBGX_E_INVALID, "step_boundary_rng: bad sizes (n_lig=%d C=%d t=%d T=%d)", n_lig, num_classes, t, num_timesteps);
-    if (!x_den || !logits || !lig_rows || !x_lig || !c_lig || !gen_lig || !tables || !x_next || !c_next || !lig_emb_w ||
-        !lig_emb_b || !ind_w || !ind_b || !x || !h)
-        return fail(CBGX_E_INVALID, "step_boundary_rng: NULL pointer");
-    for (int i = 0; i < 7; ++i)
-        if (!tables[i]) return fail(CBGX_E_INVALID, "step_boundary_rng: table %d is NULL", i);
-    if (int rc = noise_args("step_boundary_rng", stream_keys, lig_graph, true, lig_ptr, n_graphs, purpose_base)) return rc;
-    HIP_TRY(launch_step_boundary_rng(x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig, num_classes, t, tables,
-                                     (float)log((double)num_classes), stream_keys, lig_graph, lig_ptr, (uint32_t)purpose_base,
-                                     x_next, c_next, lig_emb_w, lig_emb_b, ind_w, ind_b, x, h, (hipStream_t)stream));
-    return CBGX_OK;
+    StepArgs a;
+    a.who = "step_boundary_rng";
+    a.x_den = x_den, a.logits = logits, a.lig_rows = lig_rows, a.x_lig = x_lig, a.c_lig = c_lig, a.gen_lig = gen_lig;
+    a.n_lig = n_lig, a.num_classes = num_classes, a.t = t, a.num_timesteps = num_timesteps, a.tables = tables;
+    a.counter = true, a.noise.keys = stream_keys, a.noise.lig_graph = lig_graph, a.noise.lig_ptr = lig_ptr;
+    a.noise.n_graphs = n_graphs, a.noise.purpose_base = purpose_base;
+    a.x_next = x_next, a.c_next = c_next;
+    a.boundary = true, a.lig_emb_w = lig_emb_w, a.lig_emb_b = lig_emb_b, a.ind_w = ind_w, a.ind_b = ind_b, a.x = x, a.h = h;
+    return step_epilogue(a, stream);
 }
 
 int cbgx_targetdiff_epilogue_traj_rng(const float* x_den, const float* logits, const int32_t* lig_rows, float* traj_x,
                                       float* traj_c, const uint8_t* gen_lig, int n_lig, int num_classes, int32_t* t_dev,
                                       const float* const* tables, const uint64_t* stream_keys, const int32_t* lig_graph,
                                       const int32_t* lig_ptr, int n_graphs, int purpose_base, void* stream) {
-    if (n_lig == 0) return CBGX_OK;
-    if (n_lig < 0 || num_classes < 1 || num_classes > 32) return fail(CBGX_E_INVALID, "epilogue_traj_rng: bad sizes");
-    if (!x_den || !logits || !lig_rows || !traj_x || !traj_c || !gen_lig || !t_dev || !tables)
-        return fail(CBGX_E_INVALID, "epilogue_traj_rng: NULL pointer");
-    for (int i = 0; i < 7; ++i)
-        if (!tables[i]) return fail(CBGX_E_INVALID, "epilogue_traj_rng: table %d is NULL", i);
-    if (int rc = noise_args("epilogue_traj_rng", stream_keys, lig_graph, true, lig_ptr, n_graphs, purpose_base)) return rc;
-    HIP_TRY(launch_step_epilogue_rng(x_den, logits, lig_rows, traj_x, traj_c, gen_lig, n_lig, num_classes, 0, tables,
-                                     (float)log((double)num_classes), stream_keys, lig_graph, lig_ptr, (uint32_t)purpose_base,
-                                     traj_x, traj_c, nullptr, (hipStream_t)stream, t_dev));
-    return CBGX_OK;
+    StepArgs a;
+    a.who = "epilogue_traj_rng";
+    a.x_den = x_den, a.logits = logits, a.lig_rows = lig_rows, a.x_lig = traj_x, a.c_lig = traj_c, a.gen_lig = gen_lig;
+    a.n_lig = n_lig, a.num_classes = num_classes, a.tables = tables;
+    a.counter = true, a.noise.keys = stream_keys, a.noise.lig_graph = lig_graph, a.noise.lig_ptr = lig_ptr;
+    a.noise.n_graphs = n_graphs, a.noise.purpose_base = purpose_base;
+    a.x_next = traj_x, a.c_next = traj_c;
+    a.traj = true, a.t_dev = t_dev;
+    return step_epilogue(a, stream);
 }
 
 }  // extern "C"

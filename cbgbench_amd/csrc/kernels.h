@@ -211,26 +211,23 @@ void launch_edge_x2h_f16_grid(int grid, const float* att, const float* x, const 
 hipError_t launch_step_prologue(const float* x_lig, const float* c_lig, const int32_t* lig_rows, int n_lig, int C,
                                 const float* emb_w, const float* emb_b, const float* ind_w, const float* ind_b, float* x,
                                 float* h, hipStream_t s, const int32_t* t_ptr = nullptr);
+// where the eps / u of a TargetDiff step come from: the tape pair, or (keys != NULL) the counter-based generator of rng.h, evaluated by the
+// kernel at (keys[lig_graph[a]], a - lig_ptr[lig_graph[a]], step, purpose_base + purpose) -- the numbers launch_noise_fill writes out
+struct StepNoise {
+    const float *eps = nullptr, *u = nullptr;
+    const uint64_t* keys = nullptr;
+    const int32_t *lig_graph = nullptr, *lig_ptr = nullptr;
+    int n_graphs = 0, purpose_base = 0;
+};
 hipError_t launch_step_epilogue(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
                                 const float* c_lig, const uint8_t* gen_lig, int n_lig, int C, int t,
-                                const float* const* tabs, float log_c, const float* eps, const float* u, float* x_next,
-                                float* c_next, int32_t* v_next, hipStream_t s, int32_t* t_ptr = nullptr);
+                                const float* const* tabs, float log_c, const StepNoise& noise, float* x_next, float* c_next,
+                                int32_t* v_next, hipStream_t s, int32_t* t_ptr = nullptr);
 // epilogue of step t + prologue of step t - 1 (the composed rows x[lig_rows], h[lig_rows] of the next denoiser call) in one launch
 hipError_t launch_step_boundary(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
                                 const float* c_lig, const uint8_t* gen_lig, int n_lig, int C, int t, const float* const* tabs,
-                                float log_c, const float* eps, const float* u, float* x_next, float* c_next, const float* emb_w,
+                                float log_c, const StepNoise& noise, float* x_next, float* c_next, const float* emb_w,
                                 const float* emb_b, const float* ind_w, const float* ind_b, float* x, float* h, hipStream_t s);
-// the same two with the counter-based generator of rng.h in place of eps / u, and the fill kernel that writes the same numbers out
-hipError_t launch_step_epilogue_rng(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
-                                    const float* c_lig, const uint8_t* gen_lig, int n_lig, int C, int t,
-                                    const float* const* tabs, float log_c, const uint64_t* keys, const int32_t* lig_graph,
-                                    const int32_t* lig_ptr, uint32_t purpose_base, float* x_next, float* c_next, int32_t* v_next,
-                                    hipStream_t s, int32_t* t_ptr = nullptr);
-hipError_t launch_step_boundary_rng(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
-                                    const float* c_lig, const uint8_t* gen_lig, int n_lig, int C, int t, const float* const* tabs,
-                                    float log_c, const uint64_t* keys, const int32_t* lig_graph, const int32_t* lig_ptr,
-                                    uint32_t purpose_base, float* x_next, float* c_next, const float* emb_w, const float* emb_b,
-                                    const float* ind_w, const float* ind_b, float* x, float* h, hipStream_t s);
 hipError_t launch_noise_fill(const uint64_t* keys, const int32_t* lig_ptr, int n_graphs, int n_lig, int cols, int uniform,
                              uint32_t purpose, int step, const int32_t* step_ptr, float* out, hipStream_t s);
 hipError_t launch_diffbp_epilogue(const float* x_den, const float* x_com, const float* x_in, const float* logits,

@@ -254,24 +254,18 @@ __global__ __launch_bounds__(128) void step_boundary_kernel(
 
 hipError_t launch_step_boundary(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
                                 const float* c_lig, const uint8_t* gen_lig, int n_lig, int C, int t, const float* const* tabs,
-                                float log_c, const float* eps, const float* u, float* x_next, float* c_next, const float* emb_w,
+                                float log_c, const StepNoise& noise, float* x_next, float* c_next, const float* emb_w,
                                 const float* emb_b, const float* ind_w, const float* ind_b, float* x, float* h, hipStream_t s) {
     if (n_lig == 0) return hipSuccess;
-    hipLaunchKernelGGL(step_boundary_kernel<NoiseTape>, dim3(n_lig), dim3(128), 0, s, x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig, C,
-                       t, tabs[0], tabs[1], tabs[2], tabs[3], tabs[4], tabs[5], tabs[6], log_c, eps, u, x_next, c_next, emb_w, emb_b,
-                       ind_w, ind_b, x, h);
-    return hipGetLastError();
-}
-
-hipError_t launch_step_boundary_rng(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
-                                    const float* c_lig, const uint8_t* gen_lig, int n_lig, int C, int t, const float* const* tabs,
-                                    float log_c, const uint64_t* keys, const int32_t* lig_graph, const int32_t* lig_ptr,
-                                    uint32_t purpose_base, float* x_next, float* c_next, const float* emb_w, const float* emb_b,
-                                    const float* ind_w, const float* ind_b, float* x, float* h, hipStream_t s) {
-    if (n_lig == 0) return hipSuccess;
-    hipLaunchKernelGGL((step_boundary_kernel<NoiseCounter, NoiseCounter::Extra>), dim3(n_lig), dim3(128), 0, s, x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig,
-                       C, t, tabs[0], tabs[1], tabs[2], tabs[3], tabs[4], tabs[5], tabs[6], log_c, keys, lig_graph, x_next, c_next,
-                       emb_w, emb_b, ind_w, ind_b, x, h, NoiseCounter::Extra{lig_ptr, purpose_base});
+    if (!noise.keys)
+        hipLaunchKernelGGL(step_boundary_kernel<NoiseTape>, dim3(n_lig), dim3(128), 0, s, x_den, logits, lig_rows, x_lig, c_lig, gen_lig,
+                           n_lig, C, t, tabs[0], tabs[1], tabs[2], tabs[3], tabs[4], tabs[5], tabs[6], log_c, noise.eps, noise.u, x_next,
+                           c_next, emb_w, emb_b, ind_w, ind_b, x, h);
+    else
+        hipLaunchKernelGGL((step_boundary_kernel<NoiseCounter, NoiseCounter::Extra>), dim3(n_lig), dim3(128), 0, s, x_den, logits, lig_rows,
+                           x_lig, c_lig, gen_lig, n_lig, C, t, tabs[0], tabs[1], tabs[2], tabs[3], tabs[4], tabs[5], tabs[6], log_c,
+                           noise.keys, noise.lig_graph, x_next, c_next, emb_w, emb_b, ind_w, ind_b, x, h,
+                           NoiseCounter::Extra{noise.lig_ptr, (uint32_t)noise.purpose_base});
     return hipGetLastError();
 }
 
@@ -445,19 +439,14 @@ static hipError_t step_epilogue(const float* x_den, const float* logits, const i
 
 hipError_t launch_step_epilogue(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
                                 const float* c_lig, const uint8_t* gen_lig, int n_lig, int C, int t,
-                                const float* const* tabs, float log_c, const float* eps, const float* u, float* x_next,
-                                float* c_next, int32_t* v_next, hipStream_t s, int32_t* t_ptr) {
-    return step_epilogue<NoiseTape>(x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig, C, t, tabs, log_c, eps, u,
-                                    x_next, c_next, v_next, s, t_ptr);
-}
-
-hipError_t launch_step_epilogue_rng(const float* x_den, const float* logits, const int32_t* lig_rows, const float* x_lig,
-                                    const float* c_lig, const uint8_t* gen_lig, int n_lig, int C, int t,
-                                    const float* const* tabs, float log_c, const uint64_t* keys, const int32_t* lig_graph,
-                                    const int32_t* lig_ptr, uint32_t purpose_base, float* x_next, float* c_next, int32_t* v_next,
-                                    hipStream_t s, int32_t* t_ptr) {
-    return step_epilogue<NoiseCounter>(x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig, C, t, tabs, log_c, keys, lig_graph,
-                                       x_next, c_next, v_next, s, t_ptr, NoiseCounter::Extra{lig_ptr, purpose_base});
+                                const float* const* tabs, float log_c, const StepNoise& noise, float* x_next, float* c_next,
+                                int32_t* v_next, hipStream_t s, int32_t* t_ptr) {
+    if (!noise.keys)
+        return step_epilogue<NoiseTape>(x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig, C, t, tabs, log_c, noise.eps, noise.u,
+                                        x_next, c_next, v_next, s, t_ptr);
+    return step_epilogue<NoiseCounter>(x_den, logits, lig_rows, x_lig, c_lig, gen_lig, n_lig, C, t, tabs, log_c, noise.keys,
+                                       noise.lig_graph, x_next, c_next, v_next, s, t_ptr,
+                                       NoiseCounter::Extra{noise.lig_ptr, (uint32_t)noise.purpose_base});
 }
 
 // ---- cbgx_noise_fill: the draws of one purpose and one step for every ligand atom, out[a][col] = component col of atom a.

@@ -18,7 +18,7 @@ from torch import nn
 from . import _native
 from . import noise as _noise
 from .registry import get_e3_gnn, register_model
-from .targetdiff import NUM_AA, BatchesInFlight, PLContextEmbedder, TargetDiff, compose_embed
+from .targetdiff import BatchesInFlight, PLContextEmbedder, TargetDiff, compose_embed
 
 
 class PredefinedNoiseSchedule(nn.Module):
@@ -407,74 +407,48 @@ class DiffSBDD(BatchesInFlight, nn.Module):
         pocket's neighbour lists, nor its gate values, nor its ligand-free layer-0/1 features -- and carry the accumulated
         translation per graph in ``st['frame']`` (true position = frame position - frame[graph]; the network is
         translation-equivariant), so that the denoiser's static-context cache holds for all T steps as it does for TargetDiff."""
-        sch = self.pos_scheduler
+        sch, C = self.pos_scheduler, self.num_classes
         x_rec = batch["protein_pos"].float()
         dev = x_rec.device
         v_rec = batch["protein_atom_feature"].float() / 4.0
-        bl, br = batch["ligand_element_batch"], batch["protein_element_batch"]
-        lig_flag_l = batch["ligand_lig_flag"]
-        gen_l = batch.get("ligand_gen_flag", lig_flag_l).bool()
-        gen_r = batch.get("protein_gen_flag", torch.zeros_like(batch["protein_lig_flag"])).bool()
-        T, C = self.num_diffusion_timesteps, self.num_classes
-        B = int(bl.max().item()) + 1
-        n_lig, n_rec = bl.shape[0], x_rec.shape[0]
         if noise is not None and noise_draws is not None:
             raise ValueError("begin_sampling: noise= (counter mode) and noise_draws (replay) exclude each other")
         noise = _noise.resolve(noise, batch) if noise_draws is None else None
         draws = iter(noise_draws) if noise_draws is not None else None
         nxt = (lambda: next(draws).to(dev)) if draws is not None else (lambda: None)
-        aa = F.one_hot(batch["protein_aa_type"], NUM_AA).float()
-        sort_idx, batch_idx, lig_flag, lig_rows, graph_ptr = TargetDiff.compose_plan(bl, br, B)
-        gen_flag = torch.cat([gen_r, gen_l], 0)[sort_idx]
-        rec_rows = torch.nonzero(~lig_flag).flatten()
-        x = torch.empty(n_rec + n_lig, 3, dtype=torch.float32, device=dev)
-        h = torch.empty(n_rec + n_lig, self.context_embedder.emb_dim, dtype=torch.float32, device=dev)
-        h[rec_rows] = self.context_embedder.embed_protein(v_rec, aa)          # step-invariant
-        # graphs contiguous in both index vectors (the collated layout): deterministic per-graph sums, and the native step
-        bl_ordered, br_ordered = torch.stack([(bl[1:] >= bl[:-1]).all(), (br[1:] >= br[:-1]).all()]).tolist()
-        mu_x = sch.scatter_mean(x_rec, br, B, br_ordered)[bl]
+        # graphs contiguous in both index vectors (the collated layout): deterministic per-graph sums, and the native step (include/cbgx.h:
+        # cbgx_diffsbdd_step), which keeps the composed x / h up to date on the device itself (pocket translated in place, ligand rows
+        # rewritten); st["x_rec"] is then only refreshed on demand
+        st = self._plan_sampling(batch, noise, native=dev.type == "cuda", v_rec=v_rec, pocket_order=True)
+        st.update(v_rec=v_rec, nxt=nxt, drawn=draws is not None, frame=None)
+        bl, br, B = st["bl"], st["br"], st["B"]
+        mu_x = sch.scatter_mean(x_rec, br, B, st["br_sorted"])[bl]
         mu_h = torch.zeros(B, C, device=dev)[bl]
         sigma1 = torch.ones(B, 1, device=dev)
-        cn = {}
         if noise is not None:
-            if not (dev.type == "cuda" and bl_ordered):
-                raise ValueError("counter noise needs the native step (GPU, ligand atoms sorted by graph)")
-            _noise.attach(cn, noise, bl, B)
-            eps_x0 = _noise.fill(cn, _noise.INIT_POS, 0, 3, uniform=False)
-            eps_c0 = _noise.fill(cn, _noise.INIT_TYPE, 0, C, uniform=False)
+            self._attach_noise(st, noise)
+            eps_x0 = _noise.fill(st, _noise.INIT_POS, 0, 3, uniform=False)
+            eps_c0 = _noise.fill(st, _noise.INIT_TYPE, 0, C, uniform=False)
         else:
             eps_x0 = nxt()
             eps_c0 = nxt()
-        x_lig, x_rec = sch.sample_normal_zero_com(mu_x, x_rec, sigma1, bl, br, B, com=True, eps=eps_x0, ordered=bl_ordered)
+        x_lig, x_rec = sch.sample_normal_zero_com(mu_x, x_rec, sigma1, bl, br, B, com=True, eps=eps_x0, ordered=st["bl_sorted"])
         c_lig = sch.sample_normal_zero_com(mu_h, v_rec, sigma1, bl, br, B, com=False, eps=eps_c0)
-        st = {"B": B, "N": n_rec + n_lig, "n_lig": n_lig, "x": x, "h": h, "x_lig": x_lig, "c_lig": c_lig, "x_rec": x_rec,
-              "v_rec": v_rec, "bl": bl, "br": br, "batch_idx": batch_idx, "lig_flag": lig_flag, "gen_flag": gen_flag,
-              "lig_rows": lig_rows, "rec_rows": rec_rows, "graph_ptr": graph_ptr, "nxt": nxt, "drawn": draws is not None,
-              "traj_x": None, "traj_c": None, "static_h": None, "frame": None}
-        st.update(cn)
-        # every movable row is a ligand row: the h2x blocks fold the query in the edge kernel (CBGX_FWD_GEN_IS_LIGAND)
-        st["gen_is_ligand"] = not bool(gen_r.any())
-        if keep_trajectory:
-            st["traj_x"] = torch.empty(T + 1, n_lig, 3, dtype=torch.float32, device=dev)
-            st["traj_c"] = torch.empty(T + 1, n_lig, C, dtype=torch.float32, device=dev)
-            st["traj_x"][T], st["traj_c"][T] = x_lig, c_lig
-        # native step (include/cbgx.h: cbgx_diffsbdd_step): the composed x / h are then kept up to date on the device by the
-        # step kernel itself (pocket translated in place, ligand rows rewritten), st["x_rec"] is only refreshed on demand
-        st["native"] = dev.type == "cuda" and bl_ordered
+        st["x_rec"] = x_rec
+        self._finish_state(st, x_lig, c_lig, x_rec, keep_trajectory, static_cache and st["native"])
         if st["native"]:
-            st["lig_rows32"] = lig_rows.to(torch.int32).contiguous()
-            st["lig8"] = lig_flag.to(torch.uint8).contiguous()
-            st["lig_ptr"] = torch.cat([torch.zeros(1, dtype=torch.long, device=dev),
-                                       torch.bincount(bl, minlength=B).cumsum(0)]).to(torch.int32).contiguous()
             st["coef"] = self.step_tables()
-            st["x_lig"], st["c_lig"] = x_lig.contiguous(), c_lig.contiguous()
-            x[rec_rows], x[lig_rows] = x_rec, x_lig
-            h[lig_rows] = self.context_embedder.embed_ligand(c_lig)
-            if static_cache and st["gen_is_ligand"]:
-                st["static_h"] = self.denoiser.static_context(x_rec, h[rec_rows], br, rec_rows, n_rec + n_lig)
-                if st["static_h"] is not None:
-                    st["frame"] = torch.zeros(B, 3, dtype=torch.float32, device=dev)     # sum of the removed means so far
+            st["x"][st["lig_rows"]] = st["x_lig"]
+            st["h"][st["lig_rows"]] = self.context_embedder.embed_ligand(st["c_lig"])
+            if st["static_h"] is not None:
+                st["frame"] = torch.zeros(B, 3, dtype=torch.float32, device=dev)     # sum of the removed means so far
         return st
+
+    _step_operands = ("lig_rows32", "lig8", "lig_ptr")
+
+    def _counter_refused(self, st):
+        if not st["native"]:
+            return "counter noise needs the native step (GPU, ligand atoms sorted by graph)"
 
     @staticmethod
     def pocket_positions(st):
@@ -501,9 +475,7 @@ class DiffSBDD(BatchesInFlight, nn.Module):
     def _denoise(self, st):
         x, h = st["x"], st["h"]
         if st.get("native"):   # x / h already hold the current state
-            xo, _, logits = self.denoiser(x=x, h=h, batch_idx=st["batch_idx"], lig_flag=st["lig_flag"],
-                                          gen_flag=st["gen_flag"], graph_ptr=st["graph_ptr"], need_h=False,
-                                          static_h=st.get("static_h"), gen_is_ligand=st.get("gen_is_ligand", False))
+            xo, _, logits = self._run_denoiser(st, need_h=False)
             x_pred = xo[st["lig_rows"]]
             if st.get("frame") is not None:       # the composed x lives in the pocket's frame: back to true coordinates
                 x_pred = x_pred - st["frame"][st["bl"]]
@@ -511,8 +483,7 @@ class DiffSBDD(BatchesInFlight, nn.Module):
         x[st["rec_rows"]] = st["x_rec"]                                       # the pocket is translated every draw
         x[st["lig_rows"]] = st["x_lig"]
         h[st["lig_rows"]] = self.context_embedder.embed_ligand(st["c_lig"])
-        xo, _, logits = self.denoiser(x=x, h=h, batch_idx=st["batch_idx"], lig_flag=st["lig_flag"], gen_flag=st["gen_flag"],
-                                      graph_ptr=st["graph_ptr"], need_h=False, gen_is_ligand=st.get("gen_is_ligand", False))
+        xo, _, logits = self._run_denoiser(st, need_h=False)
         return xo[st["lig_rows"]], logits[st["lig_rows"]]
 
     @torch.no_grad()
@@ -544,9 +515,7 @@ class DiffSBDD(BatchesInFlight, nn.Module):
         dev = st["x"].device
         n_lig, C, B = st["n_lig"], self.num_classes, st["B"]
         x, h, x_lig, c_lig, nxt = st["x"], st["h"], st["x_lig"], st["c_lig"], st["nxt"]
-        xo, _, logits = self.denoiser(x=x, h=h, batch_idx=st["batch_idx"], lig_flag=st["lig_flag"], gen_flag=st["gen_flag"],
-                                      graph_ptr=st["graph_ptr"], need_h=False, static_h=st.get("static_h"),
-                                      gen_is_ligand=st.get("gen_is_ligand", False))
+        xo, _, logits = self._run_denoiser(st, need_h=False)
         eps_x = eps_c = None
         if st.get("noise") is not None:     # counter mode: position and type normals of (atom, step)
             if self.denoise_structure:
@@ -563,15 +532,13 @@ class DiffSBDD(BatchesInFlight, nn.Module):
             x_next, c_next = st["traj_x"][t_idx], st["traj_c"][t_idx]
         else:
             x_next, c_next = torch.empty_like(x_lig), torch.empty_like(c_lig)
-        emb = self.context_embedder
         inv_alpha, coef, sigma = (tab[t_idx] for tab in st["coef"])
         _native.check(lib.cbgx_diffsbdd_step(
             _native.ptr(xo), _native.ptr(logits), _native.ptr(st["graph_ptr"]), _native.ptr(st["lig_rows32"]),
             _native.ptr(st["lig_ptr"]), _native.ptr(st["lig8"]), _native.ptr(x_lig), _native.ptr(c_lig), n_lig, B, C,
             inv_alpha, coef, sigma, int(self.denoise_structure), int(self.denoise_atom), _native.ptr(eps_x), _native.ptr(eps_c),
-            _native.ptr(emb.ligand_atom_emb.weight), _native.ptr(emb.ligand_atom_emb.bias),
-            _native.ptr(emb.ligand_indicator.weight), _native.ptr(emb.ligand_indicator.bias), _native.ptr(x_next),
-            _native.ptr(c_next), _native.ptr(x), _native.ptr(h), None, _native.ptr(st.get("frame")),
+            *self.context_embedder.ligand_row_ptrs(), _native.ptr(x_next), _native.ptr(c_next), _native.ptr(x), _native.ptr(h), None,
+            _native.ptr(st.get("frame")),
             _native.current_stream(dev)), "cbgx_diffsbdd_step")
         st["x_lig"], st["c_lig"] = x_next, c_next
         st["x_rec"] = None      # lives in x[rec_rows] now
@@ -612,24 +579,10 @@ class DiffSBDD(BatchesInFlight, nn.Module):
 
     @torch.no_grad()
     def _many_finish(self, st, out_dev):
-        T = self.num_diffusion_timesteps
-        x_fin, c_fin = self.finish_sampling(st)
-        traj_x, traj_c, bl_out = st["traj_x"].to(out_dev), st["traj_c"].to(out_dev), st["bl"].to(out_dev)
-        traj = {t - 1: (traj_x[t], traj_c[t], bl_out) for t in range(T + 1)}
-        traj[0] = (x_fin.to(out_dev), c_fin.to(out_dev), bl_out)
-        return traj
+        return self._trajectory(st, out_dev, final=self.finish_sampling(st))
 
     @torch.no_grad()
     def sample(self, batch, noise_draws=None, return_device=None, noise=None):
         """diffsbdd.py:240-319. ``noise_draws`` (tests): list of the randn tensors in the reference's draw order.
         ``noise`` (a ``CounterNoise``; default: the batch's ``noise_keys``): counter mode; not together with ``noise_draws``."""
-        T = self.num_diffusion_timesteps
-        st = self.begin_sampling(batch, keep_trajectory=True, noise_draws=noise_draws, noise=noise)
-        for t_idx in reversed(range(T)):
-            self.denoise_step(st, t_idx)
-        x_fin, c_fin = self.finish_sampling(st)
-        out_dev = torch.device("cpu") if return_device is None else torch.device(return_device)
-        traj_x, traj_c, bl_out = st["traj_x"].to(out_dev), st["traj_c"].to(out_dev), st["bl"].to(out_dev)
-        traj = {t - 1: (traj_x[t], traj_c[t], bl_out) for t in range(T + 1)}
-        traj[0] = (x_fin.to(out_dev), c_fin.to(out_dev), bl_out)
-        return traj
+        return self._sample_loop(batch, noise_draws, noise, return_device)

@@ -305,8 +305,16 @@ def resolve(noise, batch=None):
     return noise
 
 
-def attach(st, noise, bl, B):
-    """put the operands of the counter mode into a sampling state: keys, the per-atom graph and the ligand CSR (int32)"""
+def ligand_csr(bl, B):
+    """[B + 1] int32 offsets of the graphs' ligands in ligand arrays sorted by graph (``bl``: the graph of every ligand atom)"""
+    return torch.cat([torch.zeros(1, dtype=torch.long, device=bl.device),
+                      torch.bincount(bl, minlength=B).cumsum(0)]).to(torch.int32).contiguous()
+
+
+def attach(st, noise, bl, B, lig_ptr=None, ordered=None):
+    """put the operands of the counter mode into a sampling state: keys, the per-atom graph and the ligand CSR (int32).  ``lig_ptr`` /
+    ``ordered``: that CSR and whether ``bl`` is sorted, from a caller that has them already (the state builder looks once and builds
+    once); without them both are worked out here."""
     if noise is None:
         return st
     dev = bl.device
@@ -314,13 +322,12 @@ def attach(st, noise, bl, B):
         raise ValueError("counter noise is generated by the GPU kernels: the sampling state must live on the GPU")
     if noise.num_graphs != B:
         raise ValueError(f"noise has {noise.num_graphs} stream keys for a batch of {B} graphs")
-    if not bool((bl[1:] >= bl[:-1]).all()):
+    if not (bool((bl[1:] >= bl[:-1]).all()) if ordered is None else ordered):
         raise ValueError("counter noise needs the ligand atoms sorted by graph (an atom is addressed by its index inside its ligand)")
     st["noise"] = noise
     st["noise_keys"] = noise.device_keys(dev)
     st["noise_graph"] = bl.to(torch.int32).contiguous()
-    st["noise_ptr"] = torch.cat([torch.zeros(1, dtype=torch.long, device=dev),
-                                 torch.bincount(bl, minlength=B).cumsum(0)]).to(torch.int32).contiguous()
+    st["noise_ptr"] = ligand_csr(bl, B) if lig_ptr is None else lig_ptr
     return st
 
 

@@ -15,7 +15,6 @@ What differs by design:
 import ctypes
 import math
 import os
-import time
 
 import numpy as np
 import torch
@@ -25,10 +24,9 @@ from torch import nn
 from . import _native
 from . import noise as _noise
 from .registry import get_e3_gnn, register_model
-from .unitransformer import graph_ptr_from_batch
+from .sampling import NUM_AA, BatchesInFlight, _Lap      # (BatchesInFlight: the samplers' shared host path, kept importable from here)
 
-NUM_AA = 20          # len(aa_name_number), repo/utils/protein/constants.py:39
-PROTEIN_FEAT = 7     # len(atomic_numbers) + 1 (is_backbone), protein_featurizer.py:21-26
+PROTEIN_FEAT = 7    # len(atomic_numbers) + 1 (is_backbone), protein_featurizer.py:21-26
 
 
 def _frozen(a):
@@ -365,6 +363,12 @@ class PLContextEmbedder(nn.Module):
         ind1 = self.ligand_indicator.weight[:, 0] + self.ligand_indicator.bias
         return self.ligand_atom_emb(c_lig) + ind1
 
+    def ligand_row_ptrs(self):
+        """what the step kernels that write ligand rows of h take (include/cbgx.h: lig_emb_w, lig_emb_b, ind_w, ind_b), in that order;
+        read at every call: a model moved or reloaded between two steps hands out its new storage"""
+        return (_native.ptr(self.ligand_atom_emb.weight), _native.ptr(self.ligand_atom_emb.bias),
+                _native.ptr(self.ligand_indicator.weight), _native.ptr(self.ligand_indicator.bias))
+
 
 class _ComposeEmbedFunction(torch.autograd.Function):
     """``PLContextEmbedder`` on both atom sets + ``compose_context`` of coordinates, features and the movable flag
@@ -447,119 +451,6 @@ def compose_embed(embedder, x_rec, x_lig, feat_rec, aa_rec, c_lig, sort_idx, gen
     aa = F.one_hot(aa_rec, e.residue_emb.in_features).float()
     h = torch.cat([e.embed_protein(feat_rec, aa), e.embed_ligand(c_lig)], 0)[sort_idx]
     return torch.cat([x_rec, x_lig], 0)[sort_idx], h, torch.cat([gen_r, gen_l], 0)[sort_idx]
-
-
-class _Lap:
-    """``lap(key)``: add the wall seconds since the previous lap to ``timing[key]`` after a device synchronisation; a no-op
-    without a timing dict."""
-
-    def __init__(self, timing, dev):
-        self.timing, self.dev = timing, dev
-        if timing is not None:
-            if dev.type == "cuda":
-                torch.cuda.synchronize(dev)
-            self.t = time.perf_counter()
-
-    def __call__(self, key):
-        if self.timing is None:
-            return
-        if self.dev.type == "cuda":
-            torch.cuda.synchronize(self.dev)
-        now = time.perf_counter()
-        self.timing[key] = self.timing.get(key, 0.0) + (now - self.t)
-        self.t = now
-
-
-class BatchesInFlight:
-    """``sample_many`` for the sampler classes (TargetDiff, DiffBP, DiffSBDD): ``[self.sample(b) for b in batches]`` with the batches
-    IN FLIGHT TOGETHER, round-robin over ``streams`` HIP streams.  The batches are independent (the pocket loop of sample.py:159),
-    and while one batch sits in its matrix-bound edge kernel the HBM-bound node kernels and the small kernels of the others fill what
-    it leaves (measured +5.5 % with three 200-graph batches).  Each batch's steps stay ordered on its own stream.  With
-    ``noise_tapes`` (one per batch, in the form the class's ``sample`` takes) the trajectories equal ``sample``'s bit for bit; without,
-    the torch generator is consumed step by step across the batches instead of batch by batch, i.e. the same distribution under a
-    different assignment of the draws.  A class provides ``_many_begin(batch, tape, noise) -> state``, ``_many_step(state, t, tape)`` and
-    ``_many_finish(state, device) -> trajectory``."""
-
-    def _begin(self, batch, noise, replay):
-        """``begin_sampling`` for ``sample`` / ``sample_many`` of TargetDiff and DiffBP: a replayed tape switches the batch's own
-        CounterNoise off"""
-        if replay:
-            batch = {k: v for k, v in batch.items() if k != "noise_keys"}
-        return self.begin_sampling(batch, keep_trajectory=True, noise=None if replay else noise)
-
-    def _side_streams(self, dev, n):
-        """the model's own side streams, created once per device: the denoiser keeps one workspace per stream (gigabytes at 100 k
-        nodes) and libcbgx one auxiliary stream per caller stream, so the handles must not change from call to call"""
-        pool = self.__dict__.setdefault("_stream_pool", {})
-        have = pool.setdefault(str(dev), [])
-        while len(have) < n:
-            have.append(torch.cuda.Stream(dev))
-        return have[:n]
-
-    @torch.no_grad()
-    def sample_many(self, batches, noise_tapes=None, return_device=None, streams=3, use_graph=False, noise_log=None, timing=None,
-                    noise=None):
-        """``noise``: one ``CounterNoise`` per batch (or None: the one each batch carries as ``noise_keys``, else the torch
-        generator) -- the counter mode, in which the trajectories do not depend on ``streams``, on ``use_graph`` or on which batches
-        are in flight together (cbgbench_amd/noise.py).  Not together with ``noise_tapes``.
-        ``use_graph`` (classes with ``make_step_graph``; ignored with ``noise_tapes``): every batch's step is captured once as a
-        hipGraph on its stream and replayed T times -- one host call per batch and step instead of ~50 launches plus the Python
-        around them.  This is what SMALL batches need (the reference's own 10 graphs per batch, sample.py:177-183): one such batch
-        is a chain of ~50 dependent 20 us kernels that leaves most of the chip idle, and the host cannot feed eight of them at once;
-        eight graphs in flight can.  Same kernels on the same data as the stream launches: identical trajectories
-        for identical noise.  ``noise_log`` (tests): a list that receives ``(batch index, t, eps, u)`` after every replay (which
-        synchronises the stream).  ``timing`` (a dict): the wall seconds of the three parts of the call are ADDED to its keys
-        ``begin_sampling_s`` (static context of every batch), ``steps_s`` (the T steps) and ``traj_download_s`` (trajectory to
-        ``return_device``) -- three device synchronisations per call."""
-        dev = batches[0]["ligand_pos"].device
-        lap = _Lap(timing, dev)
-        out_dev = torch.device("cpu") if return_device is None else torch.device(return_device)
-        tape = lambda k: None if noise_tapes is None else noise_tapes[k]
-        if noise is not None and noise_tapes is not None:
-            raise ValueError("sample_many: noise= (counter mode) and noise_tapes (replay) exclude each other")
-        if noise is not None and len(noise) != len(batches):
-            raise ValueError(f"sample_many: {len(noise)} noise entries for {len(batches)} batches")
-        cn = lambda k: None if noise_tapes is not None else _noise.resolve(None if noise is None else noise[k], batches[k])
-        T = self.num_diffusion_timesteps
-        graphs = bool(use_graph) and noise_tapes is None and dev.type == "cuda" and hasattr(self, "make_step_graph")
-        if dev.type != "cuda" or ((len(batches) == 1 or streams <= 1) and not graphs):
-            out = []
-            for k, b in enumerate(batches):
-                st = self._many_begin(b, tape(k), cn(k))
-                lap("begin_sampling_s")
-                for t_idx in reversed(range(T)):
-                    self._many_step(st, t_idx, tape(k))
-                lap("steps_s")
-                out.append(self._many_finish(st, out_dev))
-                lap("traj_download_s")
-            return out
-        states = [self._many_begin(b, tape(k), cn(k)) for k, b in enumerate(batches)]
-        lap("begin_sampling_s")
-        cur = torch.cuda.current_stream(dev)
-        side = self._side_streams(dev, max(1, min(streams, len(states))))
-        for sx in side:
-            sx.wait_stream(cur)                      # the states were built on the caller's stream
-        if graphs:
-            made = [self.make_step_graph(st, stream=side[k % len(side)]) for k, st in enumerate(states)]
-            for n in range(T):
-                for k, (st, (replay, done)) in enumerate(zip(states, made)):
-                    if n < T - done:
-                        with torch.cuda.stream(side[k % len(side)]):
-                            replay()
-                            if noise_log is not None and st.get("_noise") is not None:    # (counter mode has no noise buffers to log)
-                                side[k % len(side)].synchronize()
-                                noise_log.append((k, T - 1 - done - n, st["_noise"][0].clone(), st["_noise"][1].clone()))   # (torch mode)
-        else:
-            for t_idx in reversed(range(T)):
-                for k, st in enumerate(states):
-                    with torch.cuda.stream(side[k % len(side)]):
-                        self._many_step(st, t_idx, tape(k))
-        for sx in side:
-            cur.wait_stream(sx)
-        lap("steps_s")
-        out = [self._many_finish(st, out_dev) for st in states]
-        lap("traj_download_s")
-        return out
 
 
 @register_model("targetdiff")
@@ -701,39 +592,6 @@ class TargetDiff(BatchesInFlight, nn.Module):
             results["t"], results["xt"] = t, x_t
         return {"pos": loss_pos, "atom": loss_atom}, results
 
-    # ---- static per-batch structure ------------------------------------------------------------
-    @staticmethod
-    def compose_plan(batch_idx_lig, batch_idx_rec, n_graphs=None):
-        """compose_context (repo/modules/common.py:189-214): cat(rec, lig) + stable sort by graph id.
-        Returns (sort_idx, batch_idx, lig_rows, graph_ptr); computed once per batch."""
-        n_rec, n_lig = batch_idx_rec.shape[0], batch_idx_lig.shape[0]
-        if (n_graphs is not None and batch_idx_rec.is_cuda and batch_idx_rec.dtype == torch.int64 and batch_idx_lig.dtype == torch.int64
-                and 0 < n_graphs <= (1 << 20) and n_rec + n_lig > 0 and os.environ.get("CBGX_FUSED_COMPOSE", "1") != "0"):
-            # the same five results from a counting sort in three launches (csrc/train_embed.hip, cbgx_compose_plan) instead of ~20
-            dev = batch_idx_rec.device
-            N = n_rec + n_lig
-            sort_idx = torch.empty(N, dtype=torch.int64, device=dev)
-            batch_idx = torch.empty(N, dtype=torch.int64, device=dev)
-            lig_flag = torch.empty(N, dtype=torch.bool, device=dev)
-            lig_rows = torch.empty(n_lig, dtype=torch.int64, device=dev)
-            graph_ptr = torch.empty(n_graphs + 1, dtype=torch.int32, device=dev)
-            scratch = torch.empty(4 * n_graphs + 1, dtype=torch.int32, device=dev)
-            _native.check(_native.lib().cbgx_compose_plan(
-                _native.ptr(batch_idx_rec.contiguous()), _native.ptr(batch_idx_lig.contiguous()), n_rec, n_lig, int(n_graphs),
-                _native.ptr(scratch), _native.ptr(sort_idx), _native.ptr(batch_idx), _native.ptr(lig_flag), _native.ptr(lig_rows),
-                _native.ptr(graph_ptr), _native.current_stream(dev)), "cbgx_compose_plan")
-            return sort_idx, batch_idx, lig_flag, lig_rows, graph_ptr
-        batch_ctx = torch.cat([batch_idx_rec, batch_idx_lig], 0)
-        sort_idx = torch.sort(batch_ctx, stable=True).indices
-        batch_idx = batch_ctx[sort_idx]
-        n_rec = batch_idx_rec.shape[0]
-        lig_flag = sort_idx >= n_rec
-        # composed rows of ligand atoms, in ligand order = the inverse permutation's tail (no nonzero(): that synchronises)
-        inv = torch.empty_like(sort_idx)
-        inv[sort_idx] = torch.arange(sort_idx.numel(), device=sort_idx.device)
-        lig_rows = inv[n_rec:]
-        return sort_idx, batch_idx, lig_flag, lig_rows, graph_ptr_from_batch(batch_idx, n_graphs)
-
     @torch.no_grad()
     def begin_sampling(self, batch, keep_trajectory=True, static_cache=True, noise=None):
         """Everything that is constant over the T steps of one batch: the composition permutation, CSR
@@ -742,55 +600,22 @@ class TargetDiff(BatchesInFlight, nn.Module):
         noise in the step kernels from the graphs' stream keys instead of drawing it from the torch generator."""
         noise = _noise.resolve(noise, batch)
         x_lig = batch["ligand_pos"].float()
-        dev = x_lig.device
         v_lig_in = batch["ligand_atom_type"]
-        x_rec = batch["protein_pos"].float()
-        v_rec = batch["protein_atom_feature"].float()
-        lig_flag_l = batch["ligand_lig_flag"]
-        gen_l = batch.get("ligand_gen_flag", lig_flag_l).bool()
-        gen_r = batch.get("protein_gen_flag", torch.zeros_like(batch["protein_lig_flag"])).bool()
-        bl, br = batch["ligand_element_batch"], batch["protein_element_batch"]
-        T, C = self.num_diffusion_timesteps, self.num_classes
-        n_rec, n_lig = x_rec.shape[0], x_lig.shape[0]
-        B = int(bl.max().item()) + 1
-        aa = F.one_hot(batch["protein_aa_type"], NUM_AA).float()
-        c_lig = F.one_hot(v_lig_in, C).float() if v_lig_in.dim() == 1 else v_lig_in.float()
-        sort_idx, batch_idx, lig_flag, lig_rows, graph_ptr = self.compose_plan(bl, br, B)
-        gen_flag = torch.cat([gen_r, gen_l], 0)[sort_idx]
-        N = n_rec + n_lig
-        rec_rows = torch.nonzero(~lig_flag).flatten()
-        x = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        h = torch.empty(N, self.context_embedder.emb_dim, dtype=torch.float32, device=dev)
-        x[rec_rows] = x_rec
-        h[rec_rows] = self.context_embedder.embed_protein(v_rec, aa)
-        st = dict(x=x, h=h, x_lig=x_lig.contiguous(), c_lig=c_lig.contiguous(), bl=bl, gen_l=gen_l, batch_idx=batch_idx,
-                  lig_flag=lig_flag, gen_flag=gen_flag, lig_rows=lig_rows, graph_ptr=graph_ptr, B=B, n_lig=n_lig, N=N,
-                  traj_x=None, traj_c=None)
-        st["static_h"] = None
-        # every movable row is a ligand row: the h2x blocks fold the query in the edge kernel (CBGX_FWD_GEN_IS_LIGAND)
-        st["gen_is_ligand"] = not bool(gen_r.any())
-        if dev.type == "cuda" and static_cache and st["gen_is_ligand"]:
-            # protein rows of (x, h) are the same in all T denoiser calls: cache the ligand-free first two layers once
-            st["static_h"] = self.denoiser.static_context(x_rec, h[rec_rows], br, rec_rows, N)
-        if dev.type == "cuda":
-            # operands of the native prologue / epilogue kernels (include/cbgx.h)
-            st["lig_rows32"] = lig_rows.to(torch.int32).contiguous()
-            st["gen_l8"] = gen_l.to(torch.uint8).contiguous()
+        c_lig = F.one_hot(v_lig_in, self.num_classes).float() if v_lig_in.dim() == 1 else v_lig_in.float()
+        # the native prologue / epilogue kernels (include/cbgx.h) take the ligand atoms in any order
+        st = self._plan_sampling(batch, noise, native=x_lig.is_cuda)
+        if st["native"]:
             ps, ts = self.pos_scheduler, self.type_scheduler
             tabs = [ps.posterior_mean_c0_coef, ps.posterior_mean_ct_coef, ps.posterior_logvar, ts.log_alphas_v,
                     ts.log_one_minus_alphas_v, ts.log_alphas_cumprod_v, ts.log_one_minus_alphas_cumprod_v]
             st["tables"] = (ctypes.c_void_p * 7)(*[t.data_ptr() for t in tabs])
-        if noise is not None:
-            if not (self.denoise_structure and self.denoise_atom):
-                raise ValueError("counter noise needs the native step (denoise_structure and denoise_atom)")
-            _noise.attach(st, noise, bl, B)
-        if keep_trajectory:
-            # slot s+1 holds the state entering step s; slot 0 = final state (key -1 of the reference's dict)
-            st["traj_x"] = torch.empty(T + 1, n_lig, 3, dtype=torch.float32, device=dev)
-            st["traj_c"] = torch.empty(T + 1, n_lig, C, dtype=torch.float32, device=dev)
-            st["traj_x"][T] = x_lig
-            st["traj_c"][T] = c_lig
-        return st
+        return self._finish_state(st, x_lig, c_lig, batch["protein_pos"].float(), keep_trajectory, static_cache, noise)
+
+    _step_operands = ("lig_rows32", "gen_l8")
+
+    def _counter_refused(self, st):
+        if not (self.denoise_structure and self.denoise_atom):
+            return "counter noise needs the native step (denoise_structure and denoise_atom)"
 
     @torch.no_grad()
     def denoise_step(self, st, t_idx, noise=None):
@@ -801,12 +626,7 @@ class TargetDiff(BatchesInFlight, nn.Module):
         generates it.  A replayed pair takes precedence for its step."""
         dev = st["x"].device
         if isinstance(noise, _noise.CounterNoise):
-            if st.get("noise") is None:
-                if not (self.denoise_structure and self.denoise_atom):
-                    raise ValueError("counter noise needs the native step (denoise_structure and denoise_atom)")
-                _noise.attach(st, noise, st["bl"], st["B"])
-            elif st["noise"] is not noise:
-                raise ValueError("denoise_step: the state already runs on another CounterNoise")
+            self._adopt_noise(st, noise)
             noise = None
         if dev.type == "cuda" and self.denoise_structure and self.denoise_atom:
             return self._denoise_step_native(st, t_idx, noise)
@@ -814,9 +634,7 @@ class TargetDiff(BatchesInFlight, nn.Module):
         x, h, lig_rows = st["x"], st["h"], st["lig_rows"]
         x[lig_rows] = st["x_lig"]
         h[lig_rows] = self.context_embedder.embed_ligand(st["c_lig"])
-        xo, _, logits = self.denoiser(x=x, h=h, batch_idx=st["batch_idx"], lig_flag=st["lig_flag"],
-                                      gen_flag=st["gen_flag"], graph_ptr=st["graph_ptr"],
-                                      gen_is_ligand=st.get("gen_is_ligand", False))
+        xo, _, logits = self._run_denoiser(st)
         x_pred, c_pred = xo[lig_rows], logits[lig_rows]
         eps, u = noise if noise is not None else (None, None)
         if self.denoise_structure:
@@ -852,73 +670,66 @@ class TargetDiff(BatchesInFlight, nn.Module):
         q[2] = k + 1
         return q[0][k], q[1][k]
 
+    def _prologue(self, st, traj=False):
+        """compose the ligand rows of x / h from the ligand state (traj: from the trajectory slot of the step index on the device)"""
+        name = "cbgx_targetdiff_prologue_traj" if traj else "cbgx_targetdiff_prologue"
+        state = (st["traj_x"], st["traj_c"], st["t_dev"]) if traj else (st["x_lig"], st["c_lig"])
+        _native.check(getattr(_native.lib(), name)(
+            *map(_native.ptr, state), _native.ptr(st["lig_rows32"]), st["n_lig"], self.num_classes,
+            *self.context_embedder.ligand_row_ptrs(), _native.ptr(st["x"]), _native.ptr(st["h"]),
+            _native.current_stream(st["x"].device)), name)
+
+    def _epilogue(self, st, xo, logits, t_idx, noise, next_state=None, boundary=False):
+        """The epilogue entry of one step (include/cbgx.h), chosen from (counter, boundary, traj): the six take one head, then the noise
+        -- ``noise`` = (eps, u), or None: the state's counter operands, the same kernels with the generator inside (NOISE_CHUNK plays no
+        part) --, then a tail.  ``next_state`` = (x_next, c_next): where the next state goes, ``boundary``: the same launch also
+        composes it into x / h (epilogue of this step + prologue of the next, same arithmetic); ``next_state`` None: the trajectory
+        variant, state and step index on the device."""
+        traj = next_state is None
+        name = "cbgx_targetdiff_" + ("epilogue_traj" if traj else "step_boundary" if boundary else "epilogue")
+        if traj:
+            state, step = (st["traj_x"], st["traj_c"]), (_native.ptr(st["t_dev"]),)
+        else:
+            state, step = (st["x_lig"], st["c_lig"]), (int(t_idx), self.num_diffusion_timesteps)
+        args = [_native.ptr(xo), _native.ptr(logits), _native.ptr(st["lig_rows32"]), _native.ptr(state[0]), _native.ptr(state[1]),
+                _native.ptr(st["gen_l8"]), st["n_lig"], self.num_classes, *step, st["tables"]]
+        if noise is None:
+            name += "_rng"
+            args += [_native.ptr(st["noise_keys"]), _native.ptr(st["noise_graph"]), _native.ptr(st["noise_ptr"]), st["B"],
+                     st["noise"].purpose_base]
+        else:
+            args += [_native.ptr(noise[0]), _native.ptr(noise[1])]
+        if not traj:
+            args += [_native.ptr(next_state[0]), _native.ptr(next_state[1])]
+            if boundary:
+                args += [*self.context_embedder.ligand_row_ptrs(), _native.ptr(st["x"]), _native.ptr(st["h"])]
+            else:
+                args.append(None)       # v_next: not wanted
+        _native.check(getattr(_native.lib(), name)(*args, _native.current_stream(st["x"].device)), name)
+
     def _denoise_step_native(self, st, t_idx, noise):
-        lib = _native.lib()
         dev = st["x"].device
-        stream = _native.current_stream(dev)
         n_lig, C = st["n_lig"], self.num_classes
         x_lig, c_lig = st["x_lig"], st["c_lig"]
-        emb = self.context_embedder
         # The composed rows of the ligand atoms are already in place when the previous step's boundary kernel wrote them from
         # exactly this state (same tensor objects, not written since: identity + version counters); otherwise -- the first step
         # of a run, a caller that replaced or edited st["x_lig"] / st["c_lig"] -- the prologue kernel composes them.
         comp = st.get("_composed")
         if not (self.fuse_step_boundary and comp is not None and comp[0] is x_lig and comp[1] is c_lig
                 and comp[2] == _native.version(x_lig) and comp[3] == _native.version(c_lig)):
-            _native.check(lib.cbgx_targetdiff_prologue(
-                _native.ptr(x_lig), _native.ptr(c_lig), _native.ptr(st["lig_rows32"]), n_lig, C,
-                _native.ptr(emb.ligand_atom_emb.weight), _native.ptr(emb.ligand_atom_emb.bias),
-                _native.ptr(emb.ligand_indicator.weight), _native.ptr(emb.ligand_indicator.bias),
-                _native.ptr(st["x"]), _native.ptr(st["h"]), stream), "cbgx_targetdiff_prologue")
-        xo, _, logits = self.denoiser(x=st["x"], h=st["h"], batch_idx=st["batch_idx"], lig_flag=st["lig_flag"],
-                                      gen_flag=st["gen_flag"], graph_ptr=st["graph_ptr"], need_h=False,
-                                      static_h=st["static_h"], gen_is_ligand=st.get("gen_is_ligand", False))
-        counter = st.get("noise") if noise is None else None
+            self._prologue(st)
+        xo, _, logits = self._run_denoiser(st, need_h=False)
         if noise is not None:
-            eps, u = noise[0].float().contiguous(), noise[1].float().contiguous()
-        elif counter is None:
-            eps, u = self._step_noise(st, n_lig, C, dev)
+            noise = noise[0].float().contiguous(), noise[1].float().contiguous()
+        elif st.get("noise") is None:
+            noise = self._step_noise(st, n_lig, C, dev)
         if st["traj_x"] is not None:
             x_next, c_next = st["traj_x"][t_idx], st["traj_c"][t_idx]
         else:
             x_next, c_next = torch.empty_like(x_lig), torch.empty_like(c_lig)
-        if counter is not None:
-            # counter mode: the same two kernels with the generator inside (cbgx_targetdiff_{step_boundary,epilogue}_rng); NOISE_CHUNK
-            # plays no part
-            keys = (_native.ptr(st["noise_keys"]), _native.ptr(st["noise_graph"]), _native.ptr(st["noise_ptr"]), st["B"],
-                    counter.purpose_base)
-            if self.fuse_step_boundary and t_idx > 0:
-                _native.check(lib.cbgx_targetdiff_step_boundary_rng(
-                    _native.ptr(xo), _native.ptr(logits), _native.ptr(st["lig_rows32"]), _native.ptr(x_lig), _native.ptr(c_lig),
-                    _native.ptr(st["gen_l8"]), n_lig, C, int(t_idx), self.num_diffusion_timesteps, st["tables"], *keys,
-                    _native.ptr(x_next), _native.ptr(c_next),
-                    _native.ptr(emb.ligand_atom_emb.weight), _native.ptr(emb.ligand_atom_emb.bias),
-                    _native.ptr(emb.ligand_indicator.weight), _native.ptr(emb.ligand_indicator.bias),
-                    _native.ptr(st["x"]), _native.ptr(st["h"]), stream), "cbgx_targetdiff_step_boundary_rng")
-                st["_composed"] = (x_next, c_next, _native.version(x_next), _native.version(c_next))
-            else:
-                _native.check(lib.cbgx_targetdiff_epilogue_rng(
-                    _native.ptr(xo), _native.ptr(logits), _native.ptr(st["lig_rows32"]), _native.ptr(x_lig), _native.ptr(c_lig),
-                    _native.ptr(st["gen_l8"]), n_lig, C, int(t_idx), self.num_diffusion_timesteps, st["tables"], *keys,
-                    _native.ptr(x_next), _native.ptr(c_next), None, stream), "cbgx_targetdiff_epilogue_rng")
-                st["_composed"] = None
-        elif self.fuse_step_boundary and t_idx > 0:
-            # epilogue of this step + prologue of the next in one launch (cbgx_targetdiff_step_boundary: same arithmetic)
-            _native.check(lib.cbgx_targetdiff_step_boundary(
-                _native.ptr(xo), _native.ptr(logits), _native.ptr(st["lig_rows32"]), _native.ptr(x_lig), _native.ptr(c_lig),
-                _native.ptr(st["gen_l8"]), n_lig, C, int(t_idx), self.num_diffusion_timesteps, st["tables"],
-                _native.ptr(eps), _native.ptr(u), _native.ptr(x_next), _native.ptr(c_next),
-                _native.ptr(emb.ligand_atom_emb.weight), _native.ptr(emb.ligand_atom_emb.bias),
-                _native.ptr(emb.ligand_indicator.weight), _native.ptr(emb.ligand_indicator.bias),
-                _native.ptr(st["x"]), _native.ptr(st["h"]), stream), "cbgx_targetdiff_step_boundary")
-            st["_composed"] = (x_next, c_next, _native.version(x_next), _native.version(c_next))
-        else:
-            _native.check(lib.cbgx_targetdiff_epilogue(
-                _native.ptr(xo), _native.ptr(logits), _native.ptr(st["lig_rows32"]), _native.ptr(x_lig), _native.ptr(c_lig),
-                _native.ptr(st["gen_l8"]), n_lig, C, int(t_idx), self.num_diffusion_timesteps, st["tables"],
-                _native.ptr(eps), _native.ptr(u), _native.ptr(x_next), _native.ptr(c_next), None, stream),
-                "cbgx_targetdiff_epilogue")
-            st["_composed"] = None
+        boundary = self.fuse_step_boundary and t_idx > 0
+        self._epilogue(st, xo, logits, t_idx, noise, (x_next, c_next), boundary)
+        st["_composed"] = (x_next, c_next, _native.version(x_next), _native.version(c_next)) if boundary else None
         st["x_lig"], st["c_lig"] = x_next, c_next
         return st
 
@@ -926,35 +737,15 @@ class TargetDiff(BatchesInFlight, nn.Module):
     def _traj_step(self, st):
         """One step with every argument static: the ligand state lives in the trajectory slots, the step index on the
         device (cbgx_targetdiff_prologue_traj / epilogue_traj).  Capturable in a hipGraph."""
-        lib = _native.lib()
         dev = st["x"].device
-        stream = _native.current_stream(dev)
-        n_lig, C = st["n_lig"], self.num_classes
-        emb = self.context_embedder
-        _native.check(lib.cbgx_targetdiff_prologue_traj(
-            _native.ptr(st["traj_x"]), _native.ptr(st["traj_c"]), _native.ptr(st["t_dev"]), _native.ptr(st["lig_rows32"]),
-            n_lig, C, _native.ptr(emb.ligand_atom_emb.weight), _native.ptr(emb.ligand_atom_emb.bias),
-            _native.ptr(emb.ligand_indicator.weight), _native.ptr(emb.ligand_indicator.bias),
-            _native.ptr(st["x"]), _native.ptr(st["h"]), stream), "cbgx_targetdiff_prologue_traj")
-        xo, _, logits = self.denoiser(x=st["x"], h=st["h"], batch_idx=st["batch_idx"], lig_flag=st["lig_flag"],
-                                      gen_flag=st["gen_flag"], graph_ptr=st["graph_ptr"], need_h=False,
-                                      static_h=st["static_h"], workspace=st.get("_ws"),
-                                      gen_is_ligand=st.get("gen_is_ligand", False))
+        self._prologue(st, traj=True)
+        xo, _, logits = self._run_denoiser(st, need_h=False, workspace=st.get("_ws"))
         if st.get("noise") is not None:     # counter mode: the step index on the device is the counter's step; no noise node
-            _native.check(lib.cbgx_targetdiff_epilogue_traj_rng(
-                _native.ptr(xo), _native.ptr(logits), _native.ptr(st["lig_rows32"]), _native.ptr(st["traj_x"]),
-                _native.ptr(st["traj_c"]), _native.ptr(st["gen_l8"]), n_lig, C, _native.ptr(st["t_dev"]), st["tables"],
-                _native.ptr(st["noise_keys"]), _native.ptr(st["noise_graph"]), _native.ptr(st["noise_ptr"]), st["B"],
-                st["noise"].purpose_base, stream), "cbgx_targetdiff_epilogue_traj_rng")
             st["_noise"] = None
-            return
-        eps = torch.randn(n_lig, 3, dtype=torch.float32, device=dev)      # reference draw order: randn then rand
-        u = torch.rand(n_lig, C, dtype=torch.float32, device=dev)
-        _native.check(lib.cbgx_targetdiff_epilogue_traj(
-            _native.ptr(xo), _native.ptr(logits), _native.ptr(st["lig_rows32"]), _native.ptr(st["traj_x"]),
-            _native.ptr(st["traj_c"]), _native.ptr(st["gen_l8"]), n_lig, C, _native.ptr(st["t_dev"]), st["tables"],
-            _native.ptr(eps), _native.ptr(u), stream), "cbgx_targetdiff_epilogue_traj")
-        st["_noise"] = (eps, u)     # under capture these are the graph's static buffers: readable after every replay
+        else:       # reference draw order: randn then rand.  Under capture these are the graph's static buffers: readable after every replay
+            st["_noise"] = (torch.randn(st["n_lig"], 3, dtype=torch.float32, device=dev),
+                            torch.rand(st["n_lig"], self.num_classes, dtype=torch.float32, device=dev))
+        self._epilogue(st, xo, logits, None, st["_noise"])
 
     @torch.no_grad()
     def make_step_graph(self, st, warmup=2, stream=None):
@@ -1016,20 +807,7 @@ class TargetDiff(BatchesInFlight, nn.Module):
         for t_idx in (reversed(range(T)) if not use_graph else ()):
             self.denoise_step(st, t_idx, noise_tape[t_idx] if noise_tape is not None else None)
         lap("steps_s")
-        out_dev = torch.device("cpu") if return_device is None else torch.device(return_device)
-        traj_x, traj_c, bl_out = st["traj_x"].to(out_dev), st["traj_c"].to(out_dev), st["bl"].to(out_dev)
+        traj = self._trajectory(st, torch.device("cpu") if return_device is None else torch.device(return_device))
         lap("traj_download_s")
-        return {t - 1: (traj_x[t], traj_c[t], bl_out) for t in range(T + 1)}
-
-    # hooks of BatchesInFlight.sample_many
-    def _many_begin(self, batch, tape, noise=None):
-        return self._begin(batch, noise, tape is not None)
-
-    def _many_step(self, st, t_idx, tape):
-        self.denoise_step(st, t_idx, tape[t_idx] if tape is not None else None)
-
-    def _many_finish(self, st, out_dev):
-        T = self.num_diffusion_timesteps
-        traj_x, traj_c, bl_out = st["traj_x"].to(out_dev), st["traj_c"].to(out_dev), st["bl"].to(out_dev)
-        return {t - 1: (traj_x[t], traj_c[t], bl_out) for t in range(T + 1)}
+        return traj
 

@@ -210,6 +210,98 @@ def test_abi_argument_errors_without_gpu():
         _native.check(-3, "x")
 
 
+# ---- the argument checks of the step entry points (include/cbgx.h), none of which reaches the device ------------------------------
+# An argument: (name, kind, value of the valid call).  Kinds: "p" a required pointer, "o" an optional one (left alone here: the GPU
+# tests cover them), "i" an integer, "f" a float, "tab" the seven-entry table array, "s" the stream.
+_P = lambda *names: [(n, "p", 16) for n in names]
+_EMB = _P("lig_emb_w", "lig_emb_b", "ind_w", "ind_b")
+_HEAD = _P("x_den", "logits", "lig_rows", "x_lig", "c_lig", "gen_lig") + [("n_lig", "i", 5), ("C", "i", 13), ("t", "i", 3), ("T", "i", 8),
+                                                                         ("tables", "tab", None)]
+_HEAD_TRAJ = _P("x_den", "logits", "lig_rows", "traj_x", "traj_c", "gen_lig") + [("n_lig", "i", 5), ("C", "i", 13)] + _P("t_dev") + [
+    ("tables", "tab", None)]
+_TAPE = _P("eps", "u")
+_KEYS = _P("stream_keys", "lig_graph", "lig_ptr") + [("n_graphs", "i", 2), ("purpose_base", "i", 16)]
+_NEXT = _P("x_next", "c_next")
+_S = [("stream", "s", None)]
+# entry -> (the short name its messages begin with, arguments in ABI order)
+_STEP_ENTRIES = {
+    "cbgx_targetdiff_prologue": ("prologue", _P("x_lig", "c_lig", "lig_rows") + [("n_lig", "i", 5), ("C", "i", 13)] + _EMB + _P("x", "h") + _S),
+    "cbgx_targetdiff_prologue_traj": ("prologue_traj", _P("traj_x", "traj_c", "t_dev", "lig_rows") + [("n_lig", "i", 5), ("C", "i", 13)]
+                                      + _EMB + _P("x", "h") + _S),
+    "cbgx_targetdiff_epilogue": ("epilogue", _HEAD + _TAPE + _NEXT + [("v_next", "o", None)] + _S),
+    "cbgx_targetdiff_step_boundary": ("step_boundary", _HEAD + _TAPE + _NEXT + _EMB + _P("x", "h") + _S),
+    "cbgx_targetdiff_epilogue_traj": ("epilogue_traj", _HEAD_TRAJ + _TAPE + _S),
+    "cbgx_targetdiff_epilogue_rng": ("epilogue_rng", _HEAD + _KEYS + _NEXT + [("v_next", "o", None)] + _S),
+    "cbgx_targetdiff_step_boundary_rng": ("step_boundary_rng", _HEAD + _KEYS + _NEXT + _EMB + _P("x", "h") + _S),
+    "cbgx_targetdiff_epilogue_traj_rng": ("epilogue_traj_rng", _HEAD_TRAJ + _KEYS + _S),
+    "cbgx_diffbp_epilogue": ("diffbp_epilogue", _P("x_den", "x_com", "x_in", "logits", "lig_rows", "lig_ptr", "x_lig", "c_lig", "gen_lig")
+                             + [("n_lig", "i", 5), ("n_graphs", "i", 2), ("C", "i", 13), ("t", "i", 3), ("T", "i", 8)]
+                             + _P("alphas_cumprod", "betas") + [("absorbing_state", "i", 12)] + _P("eps", "u") + _NEXT + _S),
+    "cbgx_diffsbdd_step": ("diffsbdd_step", _P("x_den", "logits", "graph_ptr", "lig_rows", "lig_ptr", "lig_flag", "x_lig", "c_lig")
+                           + [("n_lig", "i", 5), ("n_graphs", "i", 2), ("C", "i", 8), ("inv_alpha", "f", 1.0), ("coef", "f", 0.5),
+                              ("sigma", "f", 0.5), ("update_positions", "i", 1), ("update_types", "i", 1)] + _P("eps_x", "eps_c") + _EMB
+                           + _NEXT + _P("x", "h") + [("shift", "o", None), ("frame_shift", "o", None)] + _S),
+    "cbgx_noise_fill": ("noise_fill", _P("stream_keys", "lig_ptr") + [("n_graphs", "i", 2), ("n_lig", "i", 5), ("cols", "i", 3),
+                                                                       ("uniform", "i", 0), ("purpose", "i", 0), ("step", "i", 0),
+                                                                       ("step_dev", "o", None)] + _P("out") + _S),
+}
+# the out-of-range values of every size an entry takes, by argument name (T is a bound, not a size: t is moved against it)
+_BAD_SIZES = {"n_lig": [-1], "C": [0, 33], "t": [-1, 8], "absorbing_state": [-1, 13], "cols": [-1], "purpose": [-1], "step": [-1]}
+_BAD_N_GRAPHS = {"cbgx_diffbp_epilogue": [-1], "cbgx_diffsbdd_step": [-1], "cbgx_noise_fill": [-1]}      # (0: a no-op there)
+_BAD_N_GRAPHS_RNG, _BAD_PURPOSE_BASE = [0, -1], [-16, 8, 17]
+
+
+def _step_entry_cases(entry):
+    """(what, {argument: value}) for every single change to the valid call of ``entry`` that must be rejected"""
+    _, args = _STEP_ENTRIES[entry]
+    rng = entry.endswith("_rng")
+    for name, kind, _ in args:
+        if kind == "p":
+            yield f"{name}=NULL", {name: None}
+        elif kind == "tab":
+            yield "tables=NULL", {name: None}
+            for i in range(7):
+                yield f"tables[{i}]=NULL", {name: (ctypes.c_void_p * 7)(*[None if j == i else 16 for j in range(7)])}
+        elif name == "n_graphs":
+            for v in (_BAD_N_GRAPHS_RNG if rng else _BAD_N_GRAPHS[entry]):
+                yield f"n_graphs={v}", {name: v}
+        elif name == "purpose_base":
+            for v in _BAD_PURPOSE_BASE:
+                yield f"purpose_base={v}", {name: v}
+        else:
+            for v in _BAD_SIZES.get(name, []):
+                yield f"{name}={v}", {name: v}
+
+
+@pytest.mark.parametrize("entry", sorted(_STEP_ENTRIES))
+def test_step_entry_argument_checks_without_gpu(entry):
+    """Every size out of range, every required pointer NULL, a NULL among the seven tables and (the ``_rng`` entries) the noise operands:
+    CBGX_E_INVALID with a message that begins with the entry's short name, and n_lig == 0 is a no-op -- all decided before any HIP call,
+    so this runs without a device.  The valid call itself is never made: its pointers are a dummy that must not be dereferenced."""
+    lib = _native.lib()
+    short, args = _STEP_ENTRIES[entry]
+    fn = getattr(lib, entry)
+
+    def call(changes):
+        assert set(changes) <= {name for name, _, _ in args}
+        argv = []
+        for name, kind, value in args:
+            if kind == "tab":
+                value = (ctypes.c_void_p * 7)(*[16] * 7)
+            elif kind == "p":
+                value = ctypes.c_void_p(value)
+            argv.append(changes[name] if name in changes else value)
+        return fn(*argv)
+
+    cases = list(_step_entry_cases(entry))
+    assert len(cases) >= sum(kind == "p" for _, kind, _ in args) + 3
+    for what, changes in cases:
+        assert call(changes) == -1, f"{entry}({what}) was not rejected"
+        msg = lib.cbgx_last_error()
+        assert msg.startswith(short.encode() + b":"), f"{entry}({what}): {msg!r}"
+    assert call({"n_lig": 0}) == 0, f"{entry}(n_lig=0) is a no-op"
+
+
 # ---- multi-GPU path: sharding + timing reduction over gloo, world_size 2 ------------------------------
 def _worker(rank, world, rdzv, q):
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), CBGX_RDZV_FILE=rdzv)
