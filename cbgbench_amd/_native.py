@@ -100,6 +100,8 @@ EXPORTS = {
     "cbgx_ligand_bonds_count": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "cbgx_ligand_bonds_fill": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "cbgx_ligand_rings": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "cbgx_ligand_pair_hist": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "cbgx_ligand_angles": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "cbgx_profile_begin": (_i, [_i]),
     "cbgx_profile_end": (_i, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_i), _i]),
 }

@@ -1,5 +1,5 @@
-// libcbgx -- C ABI of the geometry report, of the bond list and of the ring sizes (include/cbgx.h, geometry.hip, rings.hip): argument
-// checks, the ligand-size check, the launch
+// libcbgx -- C ABI of the geometry report, of the bond list, of the ring sizes and of the distributions (include/cbgx.h, geometry.hip,
+// rings.hip, distributions.hip): argument checks, the ligand-size check, the launch
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -114,6 +114,51 @@ int cbgx_ligand_rings(const int32_t* lig_ptr, int n_lig, int n_graphs, const int
     const hipError_t e = launch_ligand_rings(lig_ptr, n_lig, n_graphs, bond_ptr, bond_index, n_bonds, atom_ring_min, graph_out,
                                              (hipStream_t)stream);
     if (e != hipSuccess) return set_error(CBGX_E_HIP, "ligand_rings: launch: %s", hipGetErrorString(e));
+    return CBGX_OK;
+}
+
+int cbgx_ligand_pair_hist(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,
+                          const double* edges_all, int n_edges_all, const double* edges_cc, int n_edges_cc, int32_t* pair_hist,
+                          void* stream) {
+    if (n_graphs < 0 || n_lig < 0 || n_edges_all < 0 || n_edges_cc < 0)
+        return set_error(CBGX_E_INVALID, "ligand_pair_hist: negative count (B=%d n_lig=%d edges=%d, %d)", n_graphs, n_lig, n_edges_all,
+                         n_edges_cc);
+    if (n_edges_all > CBGX_PAIR_HIST_MAX_EDGES || n_edges_cc > CBGX_PAIR_HIST_MAX_EDGES)
+        return set_error(CBGX_E_INVALID, "ligand_pair_hist: %d and %d edges, more than the %d a histogram row holds", n_edges_all,
+                         n_edges_cc, CBGX_PAIR_HIST_MAX_EDGES);
+    if ((n_graphs > 0 && (!lig_ptr || !pair_hist)) || (n_lig > 0 && (!x_lig || !z_lig)) || (n_edges_all > 0 && !edges_all) ||
+        (n_edges_cc > 0 && !edges_cc))
+        return set_error(CBGX_E_INVALID, "ligand_pair_hist: NULL pointer");
+    if (n_graphs == 0) return CBGX_OK;
+    const int rc = check_ligand_sizes("ligand_pair_hist", lig_ptr, n_lig, n_graphs, (hipStream_t)stream);
+    if (rc != CBGX_OK) return rc;
+    const hipError_t e = launch_ligand_pair_hist(x_lig, z_lig, lig_ptr, n_lig, n_graphs, edges_all, n_edges_all, edges_cc, n_edges_cc,
+                                                 pair_hist, (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(CBGX_E_HIP, "ligand_pair_hist: launch: %s", hipGetErrorString(e));
+    return CBGX_OK;
+}
+
+int cbgx_ligand_angles(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs, const int32_t* adj_ptr,
+                       const int32_t* adj_nbr, const uint8_t* adj_order, int n_adj, const int32_t* angle_ptr, int n_angles,
+                       const double* cos_edges, int n_cos_edges, int32_t* angle_index, double* angle_cos, uint8_t* angle_bin,
+                       int16_t* angle_type, void* stream) {
+    if (n_graphs < 0 || n_lig < 0 || n_adj < 0 || n_angles < 0 || n_cos_edges < 0)
+        return set_error(CBGX_E_INVALID, "ligand_angles: negative count (B=%d n_lig=%d n_adj=%d n_angles=%d edges=%d)", n_graphs, n_lig,
+                         n_adj, n_angles, n_cos_edges);
+    if (n_cos_edges > CBGX_ANGLES_MAX_EDGES)
+        return set_error(CBGX_E_INVALID, "ligand_angles: %d edges, more than the %d a uint8 bin beside the degenerate mark holds",
+                         n_cos_edges, CBGX_ANGLES_MAX_EDGES);
+    if ((n_graphs > 0 && (!lig_ptr || !adj_ptr || !angle_ptr)) || (n_lig > 0 && (!x_lig || !z_lig)) ||
+        (n_adj > 0 && (!adj_nbr || !adj_order)) || (n_angles > 0 && (!angle_index || !angle_cos || !angle_bin || !angle_type)) ||
+        (n_cos_edges > 0 && !cos_edges))
+        return set_error(CBGX_E_INVALID, "ligand_angles: NULL pointer");
+    if (n_graphs == 0 || n_angles == 0) return CBGX_OK;
+    const int rc = check_ligand_sizes("ligand_angles", lig_ptr, n_lig, n_graphs, (hipStream_t)stream);
+    if (rc != CBGX_OK) return rc;
+    const hipError_t e = launch_ligand_angles(x_lig, z_lig, lig_ptr, n_lig, n_graphs, adj_ptr, adj_nbr, adj_order, n_adj, angle_ptr,
+                                              n_angles, cos_edges, n_cos_edges, angle_index, angle_cos, angle_bin, angle_type,
+                                              (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(CBGX_E_HIP, "ligand_angles: launch: %s", hipGetErrorString(e));
     return CBGX_OK;
 }
 

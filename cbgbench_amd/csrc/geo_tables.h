@@ -1,0 +1,69 @@
+// libcbgx -- what the translation units of the geometry reports share (geometry.hip, distributions.hip): the limits, the element codes,
+// the constant tables as a compile-time initialiser, and the fp64 squared distance.  The sources and the meaning of the constants are in
+// the head of geometry.hip.  A translation unit that includes this keeps contraction off (#pragma clang fp contract(off)): geo_dist2's
+// products and sums are plain operators.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/cbgx.h"
+
+namespace cbgx {
+
+constexpr int GEO_THREADS = 256;
+constexpr int GEO_MAX = CBGX_GEOMETRY_MAX_LIGAND;
+constexpr int GEO_EL = 8;         // element codes 0..7 = H C N O F P S Cl: bond table, valences, radii
+constexpr int GEO_VDW = 9;        // code 8 = Br: a radius only
+constexpr int GEO_NONE = 255;     // no code
+constexpr double GEO_FAR2 = 25.0; // squared distance from which no threshold can be met (see `shortcut` in geometry.hip)
+
+enum : int { EL_H = 0, EL_C, EL_N, EL_O, EL_F, EL_P, EL_S, EL_CL, EL_BR };
+
+struct GeoPair { int a, b, pm; };
+
+struct GeoTables {
+    int32_t bond_pm[3][GEO_EL][GEO_EL];   // [order - 1][code][code], -1: no such bond
+    int32_t margin[3];
+    int32_t allowed[GEO_EL];
+    uint8_t z[GEO_VDW];                   // atomic number of a code
+    double radius[GEO_VDW];
+    double tolerance;
+};
+
+constexpr GeoTables make_geo_tables() {
+    constexpr GeoPair single_pm[] = {
+        {EL_H, EL_H, 74},   {EL_H, EL_C, 109},  {EL_H, EL_N, 101},  {EL_H, EL_O, 96},   {EL_H, EL_F, 92},   {EL_H, EL_P, 144},
+        {EL_H, EL_S, 134},  {EL_H, EL_CL, 127}, {EL_C, EL_C, 154},  {EL_C, EL_N, 147},  {EL_C, EL_O, 143},  {EL_C, EL_F, 135},
+        {EL_C, EL_P, 184},  {EL_C, EL_S, 182},  {EL_C, EL_CL, 177}, {EL_N, EL_N, 145},  {EL_N, EL_O, 140},  {EL_N, EL_F, 136},
+        {EL_N, EL_P, 177},  {EL_N, EL_S, 168},  {EL_N, EL_CL, 175}, {EL_O, EL_O, 148},  {EL_O, EL_F, 142},  {EL_O, EL_P, 163},
+        {EL_O, EL_S, 151},  {EL_O, EL_CL, 164}, {EL_F, EL_F, 142},  {EL_F, EL_P, 156},  {EL_F, EL_S, 158},  {EL_F, EL_CL, 166},
+        {EL_P, EL_P, 221},  {EL_P, EL_S, 210},  {EL_P, EL_CL, 203}, {EL_S, EL_S, 204},  {EL_S, EL_CL, 207}, {EL_CL, EL_CL, 199}};
+    constexpr GeoPair double_pm[] = {{EL_C, EL_C, 134}, {EL_C, EL_N, 129}, {EL_C, EL_O, 120}, {EL_C, EL_S, 160}, {EL_N, EL_N, 125},
+                                     {EL_N, EL_O, 121}, {EL_O, EL_O, 121}, {EL_O, EL_P, 150}, {EL_P, EL_S, 186}};
+    constexpr GeoPair triple_pm[] = {{EL_C, EL_C, 120}, {EL_C, EL_N, 116}, {EL_C, EL_O, 113}, {EL_N, EL_N, 110}};
+    GeoTables t{};
+    for (int o = 0; o < 3; ++o)
+        for (int a = 0; a < GEO_EL; ++a)
+            for (int b = 0; b < GEO_EL; ++b) t.bond_pm[o][a][b] = -1;
+    for (const GeoPair& p : single_pm) t.bond_pm[0][p.a][p.b] = t.bond_pm[0][p.b][p.a] = p.pm;
+    for (const GeoPair& p : double_pm) t.bond_pm[1][p.a][p.b] = t.bond_pm[1][p.b][p.a] = p.pm;
+    for (const GeoPair& p : triple_pm) t.bond_pm[2][p.a][p.b] = t.bond_pm[2][p.b][p.a] = p.pm;
+    t.margin[0] = 10; t.margin[1] = 5; t.margin[2] = 3;
+    //                      H  C  N  O  F  P   S   Cl  Br
+    constexpr int zs[] =   {1, 6, 7, 8, 9, 15, 16, 17, 35};
+    constexpr int val[] =  {1, 4, 3, 2, 1, 5,  4,  1};
+    constexpr double r[] = {1.2, 1.7, 1.55, 1.52, 1.47, 1.8, 1.8, 2.27, 1.85};
+    for (int c = 0; c < GEO_VDW; ++c) { t.z[c] = (uint8_t)zs[c]; t.radius[c] = r[c]; }
+    for (int c = 0; c < GEO_EL; ++c) t.allowed[c] = val[c];
+    t.tolerance = 0.4;
+    return t;
+}
+
+// squared distance in fp64 from fp32 coordinates, each operation rounded on its own
+__device__ __forceinline__ double geo_dist2(double ax, double ay, double az, float bx, float by, float bz) {
+    const double dx = ax - (double)bx, dy = ay - (double)by, dz = az - (double)bz;
+    const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
+    return (xx + yy) + zz;
+}
+
+}  // namespace cbgx

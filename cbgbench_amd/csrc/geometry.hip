@@ -23,7 +23,7 @@
 //             bond threshold is 2.31 A (P-P, 221 + 10 pm) and the largest clash threshold 4.14 A (Cl...Cl), so no result can change.
 //   outputs   nr_bonds, flags and the six per-graph counts (integer reductions of the flags) -- every element of every graph is written.
 //
-// Constants (physical; written here as dense arrays over an element code, built at compile time from pair lists):
+// Constants (physical; written in geo_tables.h as dense arrays over an element code, built at compile time from pair lists):
 //   bond lengths  the table EDM's stability metric uses (Hoogeboom et al., "Equivariant Diffusion for Molecule Generation in 3D", 2022,
 //                 qm9/bond_analyze.py), itself from http://www.wiredchemist.com/chemistry/data/bond_energies_lengths.html and
 //                 http://chemistry-reference.com/tables/Bond%20Lengths%20and%20Enthalpies.pdf; margins 10 / 5 / 3 pm as tuned there on QM9.
@@ -38,56 +38,9 @@
 
 #pragma clang fp contract(off)
 
+#include "geo_tables.h"      // limits, element codes, GeoTables / make_geo_tables, geo_dist2
+
 namespace cbgx {
-
-constexpr int GEO_THREADS = 256;
-constexpr int GEO_MAX = CBGX_GEOMETRY_MAX_LIGAND;
-constexpr int GEO_EL = 8;         // element codes 0..7 = H C N O F P S Cl: bond table, valences, radii
-constexpr int GEO_VDW = 9;        // code 8 = Br: a radius only
-constexpr int GEO_NONE = 255;     // no code
-constexpr double GEO_FAR2 = 25.0; // squared distance from which no threshold can be met (see `shortcut` above)
-
-enum : int { EL_H = 0, EL_C, EL_N, EL_O, EL_F, EL_P, EL_S, EL_CL, EL_BR };
-
-struct GeoPair { int a, b, pm; };
-
-struct GeoTables {
-    int32_t bond_pm[3][GEO_EL][GEO_EL];   // [order - 1][code][code], -1: no such bond
-    int32_t margin[3];
-    int32_t allowed[GEO_EL];
-    uint8_t z[GEO_VDW];                   // atomic number of a code
-    double radius[GEO_VDW];
-    double tolerance;
-};
-
-constexpr GeoTables make_geo_tables() {
-    constexpr GeoPair single_pm[] = {
-        {EL_H, EL_H, 74},   {EL_H, EL_C, 109},  {EL_H, EL_N, 101},  {EL_H, EL_O, 96},   {EL_H, EL_F, 92},   {EL_H, EL_P, 144},
-        {EL_H, EL_S, 134},  {EL_H, EL_CL, 127}, {EL_C, EL_C, 154},  {EL_C, EL_N, 147},  {EL_C, EL_O, 143},  {EL_C, EL_F, 135},
-        {EL_C, EL_P, 184},  {EL_C, EL_S, 182},  {EL_C, EL_CL, 177}, {EL_N, EL_N, 145},  {EL_N, EL_O, 140},  {EL_N, EL_F, 136},
-        {EL_N, EL_P, 177},  {EL_N, EL_S, 168},  {EL_N, EL_CL, 175}, {EL_O, EL_O, 148},  {EL_O, EL_F, 142},  {EL_O, EL_P, 163},
-        {EL_O, EL_S, 151},  {EL_O, EL_CL, 164}, {EL_F, EL_F, 142},  {EL_F, EL_P, 156},  {EL_F, EL_S, 158},  {EL_F, EL_CL, 166},
-        {EL_P, EL_P, 221},  {EL_P, EL_S, 210},  {EL_P, EL_CL, 203}, {EL_S, EL_S, 204},  {EL_S, EL_CL, 207}, {EL_CL, EL_CL, 199}};
-    constexpr GeoPair double_pm[] = {{EL_C, EL_C, 134}, {EL_C, EL_N, 129}, {EL_C, EL_O, 120}, {EL_C, EL_S, 160}, {EL_N, EL_N, 125},
-                                     {EL_N, EL_O, 121}, {EL_O, EL_O, 121}, {EL_O, EL_P, 150}, {EL_P, EL_S, 186}};
-    constexpr GeoPair triple_pm[] = {{EL_C, EL_C, 120}, {EL_C, EL_N, 116}, {EL_C, EL_O, 113}, {EL_N, EL_N, 110}};
-    GeoTables t{};
-    for (int o = 0; o < 3; ++o)
-        for (int a = 0; a < GEO_EL; ++a)
-            for (int b = 0; b < GEO_EL; ++b) t.bond_pm[o][a][b] = -1;
-    for (const GeoPair& p : single_pm) t.bond_pm[0][p.a][p.b] = t.bond_pm[0][p.b][p.a] = p.pm;
-    for (const GeoPair& p : double_pm) t.bond_pm[1][p.a][p.b] = t.bond_pm[1][p.b][p.a] = p.pm;
-    for (const GeoPair& p : triple_pm) t.bond_pm[2][p.a][p.b] = t.bond_pm[2][p.b][p.a] = p.pm;
-    t.margin[0] = 10; t.margin[1] = 5; t.margin[2] = 3;
-    //                      H  C  N  O  F  P   S   Cl  Br
-    constexpr int zs[] =   {1, 6, 7, 8, 9, 15, 16, 17, 35};
-    constexpr int val[] =  {1, 4, 3, 2, 1, 5,  4,  1};
-    constexpr double r[] = {1.2, 1.7, 1.55, 1.52, 1.47, 1.8, 1.8, 2.27, 1.85};
-    for (int c = 0; c < GEO_VDW; ++c) { t.z[c] = (uint8_t)zs[c]; t.radius[c] = r[c]; }
-    for (int c = 0; c < GEO_EL; ++c) t.allowed[c] = val[c];
-    t.tolerance = 0.4;
-    return t;
-}
 
 static const GeoTables h_geo = make_geo_tables();      // what cbgx_ligand_geometry_tables hands out
 __constant__ GeoTables d_geo = make_geo_tables();      // what the kernel reads: the same initialiser
@@ -99,13 +52,6 @@ __device__ __forceinline__ int geo_code(uint8_t z, int n_codes) {
     for (int c = 0; c < GEO_VDW; ++c)
         if (c < n_codes && d_geo.z[c] == z) code = c;
     return code;
-}
-
-// squared distance in fp64 from fp32 coordinates, each operation rounded on its own
-__device__ __forceinline__ double geo_dist2(double ax, double ay, double az, float bx, float by, float bz) {
-    const double dx = ax - (double)bx, dy = ay - (double)by, dz = az - (double)bz;
-    const double xx = dx * dx, yy = dy * dy, zz = dz * dz;
-    return (xx + yy) + zz;
 }
 
 __global__ __launch_bounds__(GEO_THREADS) void ligand_geometry_kernel(

@@ -258,6 +258,15 @@ hipError_t launch_ligand_bonds_fill(const float* x_lig, const uint8_t* z_lig, co
 // rings.hip: ring sizes (lengths of a minimum cycle basis) and the shortest ring through every atom, from that bond list; one wave per graph
 hipError_t launch_ligand_rings(const int32_t* lig_ptr, int n_lig, int n_graphs, const int32_t* bond_ptr, const int32_t* bond_index,
                                int n_bonds, uint8_t* atom_ring_min, int32_t* graph_out, hipStream_t s);
+// distributions.hip: pair-distance histograms of the same ligands (two families, LDS integer histograms), and the bond angles of the
+// table-bond graph from its symmetric adjacency -- cosine, bin against a cosine table, canonical type; one workgroup per graph each
+hipError_t launch_ligand_pair_hist(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,
+                                   const double* edges_all, int n_edges_all, const double* edges_cc, int n_edges_cc, int32_t* pair_hist,
+                                   hipStream_t s);
+hipError_t launch_ligand_angles(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,
+                                const int32_t* adj_ptr, const int32_t* adj_nbr, const uint8_t* adj_order, int n_adj,
+                                const int32_t* angle_ptr, int n_angles, const double* cos_edges, int n_cos_edges, int32_t* angle_index,
+                                double* angle_cos, uint8_t* angle_bin, int16_t* angle_type, hipStream_t s);
 constexpr int PACK_MAX = 64;
 struct PackPiece {
     const float* src; float* dst; int src_ld, src_off, transpose, dst_ld, rows, cols;

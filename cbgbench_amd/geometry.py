@@ -23,7 +23,16 @@ counterpart of the reference's ``'.' not in smiles`` (repo/tools/rdkit_utils.py:
 minimum cycle basis, the rings above 9, and the shortest ring through every atom, in one launch on the bond list (``cbgx_ligand_rings``,
 csrc/rings.hip) -- the RDKit-free counterpart of the ring statistics of ``evaluate_geom_single.py:27-33`` (``print_ring_ratio``) and
 ``repo/tools/eval_ring_type.py``, which read the sizes of RDKit's ``AtomRings()``.  Deviations: table bonds; RDKit's SSSR is a heuristic
-that can differ from a minimum cycle basis on cage-like graphs."""
+that can differ from a minimum cycle basis on cage-like graphs.
+
+``ligand_pair_hist`` / ``ligand_angles`` / ``batch_distributions`` / ``summarise_distributions`` are the rest of that report, the
+distributions it compares with a dataset's by Jensen-Shannon distance (``repo/tools/geometry/eval_bond_length.py``,
+``eval_bond_angle.py``): pair-distance histograms (``All_12A``, ``CC_2A``; reproduced exactly: they need coordinates and elements only),
+and bond-length and bond-angle histograms per type on the table-bond graph (``cbgx_ligand_pair_hist`` / ``cbgx_ligand_angles``,
+csrc/distributions.hip).  Angles are binned in cosine space against a table of cosines: no inverse trigonometric function runs on the
+device.  Deviations: table bonds, so no aromatic type; every angle is counted once under its canonical type where the reference lists it
+under both orientations -- the same normalised profile.  ``distribution_jsd`` / ``jsd_against`` take the caller's own reference vectors:
+no dataset constants ship."""
 import ctypes
 
 import numpy as np
@@ -347,3 +356,389 @@ def ring_jsd(distribution, reference):
     mid = 0.5 * (p + q)
     kl = lambda a, b: float(np.sum(np.where(a > 0, a * np.log(np.where(a > 0, a, 1.0) / np.where(a > 0, b, 1.0)), 0.0)))
     return float(np.sqrt(max(0.5 * (kl(p, mid) + kl(q, mid)), 0.0)))
+
+
+# ---- distributions: pair distances, bond lengths, bond angles ------------------------------------------------------------------------
+# include/cbgx.h CBGX_PAIR_HIST_MAX_EDGES / CBGX_ANGLES_MAX_EDGES / CBGX_ANGLES_MAX_PER_GRAPH / CBGX_ANGLE_BIN_DEGENERATE / CBGX_ANGLE_TYPES
+MAX_PAIR_EDGES, MAX_ANGLE_EDGES, MAX_ANGLES_PER_GRAPH, ANGLE_BIN_DEGENERATE, N_ANGLE_TYPES = 255, 254, 16384, 255, 4608
+N_BOND_TYPES = 192                         # ((order - 1) 8 + code_lo) 8 + code_hi
+DISTRIBUTIONS_TOO_MANY_ANGLES = 1          # status bit (include/cbgx.h CBGX_DISTRIBUTIONS_TOO_MANY_ANGLES)
+DISTRIBUTION_GRAPH_COLUMNS = ("n_atoms", "n_bonds", "n_angles", "n_degenerate_angles", "status")
+PAIR_FAMILIES = ("All_12A", "CC_2A")       # family 0, family 1 of cbgx_ligand_pair_hist, named like the reference's profiles
+BOND_SYMBOLS = "-=#"                       # orders 1, 2, 3 (eval_bond_length.get_bond_str; '?' is what it prints for anything else)
+DISTRIBUTION_BINS = (101, 120, 91)         # bins of the pair, bond-length and angle histograms under the default edges
+
+
+def default_pair_edges():
+    """the reference's EMPIRICAL_BINS (eval_bond_length_config.py:10-13) in family order: np.linspace(0, 12, 100), np.linspace(0, 2, 100)"""
+    return np.linspace(0, 12, 100), np.linspace(0, 2, 100)
+
+
+def default_bond_edges():
+    """the reference's DISTANCE_BINS (eval_bond_length_config.py:8): 119 edges, 120 bins"""
+    return np.arange(1.1, 1.7, 0.005)[:-1]
+
+
+def default_cos_edges():
+    """cosines of the reference's angle edges np.arange(0, 180, 2) (eval_bond_angle.py:35), rounded to 15 decimals: that makes the
+    cosines of 0, 60, 90 and 120 degrees exact (cos(90 deg) would otherwise be 6e-17 and move every exact right angle one bin up) and
+    moves no other edge by more than 1e-12 degrees"""
+    return np.round(np.cos(np.deg2rad(np.arange(0, 180, 2))), 15)
+
+
+def _edges(edges, what, limit, decreasing=False):
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
+    if e.shape[0] > limit:
+        raise ValueError(f"{what}: {e.shape[0]} edges, at most {limit}")
+    step = np.diff(e)
+    if not np.isfinite(e).all() or not ((step < 0).all() if decreasing else (step > 0).all()):
+        raise ValueError(f"{what} must be finite and strictly {'decreasing' if decreasing else 'increasing'}")
+    return e
+
+
+def _ligand_arrays(x_lig, z_lig, lig_batch, n_graphs):
+    """the ligand side of every entry: checks, lig_ptr, float32 coordinates, atomic numbers as bytes"""
+    dev = x_lig.device
+    for name, t in (("z_lig", z_lig), ("lig_batch", lig_batch)):
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, x_lig on {dev}")
+    n_lig = int(x_lig.shape[0])
+    if tuple(x_lig.shape) != (n_lig, 3):
+        raise ValueError("coordinates must be [n, 3]")
+    if z_lig.shape != (n_lig,) or lig_batch.shape != (n_lig,):
+        raise ValueError("one atomic number and one graph index per atom")
+    lig_ptr = _csr(lig_batch, n_graphs, "lig_batch")
+    x_lig = x_lig.to(torch.float32).contiguous()
+    z_lig = torch.where((z_lig >= 0) & (z_lig <= 255), z_lig, torch.zeros_like(z_lig)).to(torch.uint8).contiguous()
+    return n_lig, lig_ptr, x_lig, z_lig
+
+
+def ligand_pair_hist(x_lig, z_lig, lig_batch, n_graphs, edges_all=None, edges_cc=None):
+    """Pair-distance histograms of ``n_graphs`` ligands, one launch (``cbgx_ligand_pair_hist``, csrc/distributions.hip; the definition is
+    in include/cbgx.h) on the tensors' current stream: the counterpart of ``pair_distance_from_pos_v`` + ``get_pair_length_profile``
+    (eval_bond_length.py:77-84, 119-129), reproduced exactly.
+
+    Arguments as ``ligand_bonds``; ``edges_all`` / ``edges_cc``: strictly increasing float64 edges of family 0 (every pair i < j of a
+    ligand, atoms of unknown element included) and family 1 (both atoms carbon), at most MAX_PAIR_EDGES each; default
+    ``default_pair_edges()``.  Returns ``pair_hist`` [n_graphs, 2, E_max + 1] int32 on the device: a pair takes part iff d <
+    edges[-1], its bin is ``np.searchsorted(edges, d)``.  There is no CPU path."""
+    dev = x_lig.device
+    if dev.type != "cuda":
+        raise _native.NativeError("ligand_pair_hist runs on the GPU (cbgx_ligand_pair_hist): there is no CPU fallback")
+    n_graphs = int(n_graphs)
+    n_lig, lig_ptr, x_lig, z_lig = _ligand_arrays(x_lig, z_lig, lig_batch, n_graphs)
+    ea, ec = default_pair_edges()
+    ea = _edges(ea if edges_all is None else edges_all, "edges_all", MAX_PAIR_EDGES)
+    ec = _edges(ec if edges_cc is None else edges_cc, "edges_cc", MAX_PAIR_EDGES)
+    dea, dec = torch.from_numpy(ea).to(dev), torch.from_numpy(ec).to(dev)
+    pair_hist = torch.empty(n_graphs, 2, max(len(ea), len(ec)) + 1, dtype=torch.int32, device=dev)
+    p = _native.ptr
+    _native.check(_native.lib().cbgx_ligand_pair_hist(p(x_lig), p(z_lig), p(lig_ptr), n_lig, n_graphs, p(dea) if len(ea) else None, len(ea),
+                                                      p(dec) if len(ec) else None, len(ec), p(pair_hist), _native.current_stream(dev)),
+                  "cbgx_ligand_pair_hist")
+    return pair_hist
+
+
+_ELEMENT_CODE = None
+
+
+def _element_code(dev):
+    """[256] int64 on ``dev``: the element code 0 ... 7 of an atomic number (``tables()['elements']``), -1 when it has none"""
+    global _ELEMENT_CODE
+    if _ELEMENT_CODE is None:
+        code = np.full(256, -1, np.int64)
+        for c, z in enumerate(tables()["elements"].tolist()):
+            code[z] = c
+        _ELEMENT_CODE = torch.from_numpy(code)
+    return _ELEMENT_CODE.to(dev)
+
+
+def ligand_angles(x_lig, z_lig, lig_batch, n_graphs, bonds, cos_edges=None):
+    """The bond angles of the table-bond graphs of ``n_graphs`` ligands (``cbgx_ligand_angles``, csrc/distributions.hip; the definition
+    is in include/cbgx.h), on the tensors' current stream: the counterpart of ``bond_angle_from_mol`` (eval_bond_angle.py:69-96) on
+    TABLE bonds -- same stated deviation as ``ligand_bonds`` / ``ligand_rings``: no aromatic type, no valence repair.
+
+    ``bonds``: what ``ligand_bonds`` returned for the same arrays.  The symmetric adjacency (the list and its flip, sorted by (centre,
+    neighbour)) and the prefix sum of C(deg, 2) are made with torch on the device; its last element is read on the host to size the
+    list.  ``cos_edges``: strictly decreasing float64 cosines of the angle edges, at most MAX_ANGLE_EDGES; default
+    ``default_cos_edges()``.  Returns device tensors: ``angle_index`` [3, n_angles] int32 (rows a, c, b: global ligand rows, a < b bonded
+    partners of the centre c, in (c, a, b) order), ``angle_cos`` [n_angles] float64 (nan: degenerate), ``angle_bin`` [n_angles] uint8 (the
+    number of edges strictly greater than the cosine; ANGLE_BIN_DEGENERATE for a degenerate angle, which belongs to no histogram),
+    ``angle_type`` [n_angles] int16 (canonical, see ``angle_type_code``), ``angle_graph`` [n_angles] int64 and ``graph_counts``
+    [n_graphs, 5] int32 (DISTRIBUTION_GRAPH_COLUMNS).  A graph of more than MAX_ANGLES_PER_GRAPH angles is not an error: its status is
+    DISTRIBUTIONS_TOO_MANY_ANGLES, it has no angles in the list and n_angles = n_degenerate_angles = 0.  There is no CPU path."""
+    dev = x_lig.device
+    if dev.type != "cuda":
+        raise _native.NativeError("ligand_angles runs on the GPU (cbgx_ligand_angles): there is no CPU fallback")
+    n_graphs = int(n_graphs)
+    n_lig, lig_ptr, x_lig, z_lig = _ligand_arrays(x_lig, z_lig, lig_batch, n_graphs)
+    ce = _edges(default_cos_edges() if cos_edges is None else cos_edges, "cos_edges", MAX_ANGLE_EDGES, decreasing=True)
+    bi = bonds["bond_index"].to(torch.long)
+    n_bonds = int(bi.shape[1])
+    graph = lig_batch.to(torch.long)
+    centre, nbr = torch.cat([bi[0], bi[1]]), torch.cat([bi[1], bi[0]])
+    perm = torch.argsort(centre * max(n_lig, 1) + nbr)                  # (a pair is listed once: the keys are distinct)
+    adj_nbr = nbr[perm].to(torch.int32).contiguous()
+    adj_order = torch.cat([bonds["bond_order"], bonds["bond_order"]])[perm].to(torch.uint8).contiguous()
+    deg = torch.bincount(centre, minlength=n_lig) if n_lig else centre.new_zeros(0)
+    adj_ptr = torch.cat([deg.new_zeros(1), deg.cumsum(0)]).to(torch.int32).contiguous()
+    per_centre = deg * (deg - 1) // 2
+    per_graph = torch.zeros(n_graphs, dtype=torch.long, device=dev).index_add_(0, graph, per_centre)
+    over = per_graph > MAX_ANGLES_PER_GRAPH
+    per_centre = torch.where(over[graph], torch.zeros_like(per_centre), per_centre)
+    ends = per_centre.cumsum(0)
+    n_angles = int(ends[-1]) if n_lig else 0
+    if n_angles > 2 ** 31 - 1:
+        raise ValueError(f"{n_angles} angles in one batch: more than an int32 angle_ptr addresses")
+    angle_ptr = torch.cat([ends.new_zeros(1), ends]).to(torch.int32).contiguous()
+    dce = torch.from_numpy(ce).to(dev)
+    angle_index = torch.empty(3, n_angles, dtype=torch.int32, device=dev)
+    angle_cos = torch.empty(n_angles, dtype=torch.float64, device=dev)
+    angle_bin = torch.empty(n_angles, dtype=torch.uint8, device=dev)
+    angle_type = torch.empty(n_angles, dtype=torch.int16, device=dev)
+    p = _native.ptr
+    _native.check(_native.lib().cbgx_ligand_angles(
+        p(x_lig), p(z_lig), p(lig_ptr), n_lig, n_graphs, p(adj_ptr), p(adj_nbr) if n_bonds else None, p(adj_order) if n_bonds else None,
+        2 * n_bonds, p(angle_ptr), n_angles, p(dce) if len(ce) else None, len(ce), p(angle_index) if n_angles else None,
+        p(angle_cos) if n_angles else None, p(angle_bin) if n_angles else None, p(angle_type) if n_angles else None,
+        _native.current_stream(dev)), "cbgx_ligand_angles")
+    angle_graph = graph[angle_index[1].to(torch.long)]
+    n_degenerate = torch.bincount(angle_graph[angle_bin == ANGLE_BIN_DEGENERATE], minlength=n_graphs)
+    graph_counts = torch.stack([torch.bincount(graph, minlength=n_graphs), torch.bincount(graph[bi[0]], minlength=n_graphs),
+                                torch.where(over, torch.zeros_like(per_graph), per_graph), n_degenerate,
+                                over.to(torch.long) * DISTRIBUTIONS_TOO_MANY_ANGLES], 1).to(torch.int32)
+    return {"angle_index": angle_index, "angle_cos": angle_cos, "angle_bin": angle_bin, "angle_type": angle_type,
+            "angle_graph": angle_graph, "graph_counts": graph_counts}
+
+
+def _sparse_hist(graph, code, bins, n_codes, n_bins):
+    """per-graph histogram over (code, bin) as a sorted sparse list: (index [3, m] int32 rows graph, code, bin; count [m] int32), by
+    ``torch.unique`` on graph n_codes n_bins + code n_bins + bin -- the non-zero cells of the dense [B, n_codes, n_bins] table"""
+    key = (graph.to(torch.long) * n_codes + code.to(torch.long)) * n_bins + bins.to(torch.long)
+    key, count = torch.unique(key, return_counts=True)
+    index = torch.stack([key // (n_codes * n_bins), key // n_bins % n_codes, key % n_bins]).to(torch.int32)
+    return index, count.to(torch.int32)
+
+
+def batch_distributions(batch, x, c, lig_batch, mode, bonds=None):
+    """The three distributions of a sampling state under the reference's bins (``default_pair_edges``, ``default_bond_edges``,
+    ``default_cos_edges``); ``bonds``: what ``batch_bonds`` returned for the same state (it is called here when None).  Returns device
+    tensors: the per-angle lists and ``graph_counts`` of ``ligand_angles``; ``bond_bin`` [n_bonds] uint8 (the number of edges strictly
+    less than ``bond_length``: ``torch.bucketize``) and ``bond_type`` [n_bonds] int16 (``bond_type_code``) of the bond list;
+    ``pair_hist`` [B, 2, 101] int32 of ``ligand_pair_hist``; and the per-graph histograms by type as sorted sparse lists,
+    ``bond_hist_index`` [3, m] int32 (rows graph, type, bin) with ``bond_hist_count`` [m] int32, and ``angle_hist_index`` /
+    ``angle_hist_count`` likewise (degenerate angles left out)."""
+    if mode not in _ATOMIC_NUMBER:
+        raise ValueError(mode)
+    if bonds is None:
+        bonds = batch_bonds(batch, x, c, lig_batch, mode)
+    dev = bonds["bond_index"].device
+    x, c, lig_batch = x.to(dev), c.to(dev), lig_batch.to(dev)
+    typ = c.argmax(-1) if c.dim() == 2 else c
+    z = torch.tensor(_ATOMIC_NUMBER[mode], dtype=torch.long, device=dev)[typ.to(torch.long)]
+    n_graphs = int(bonds["graph_counts"].shape[0])
+    out = ligand_angles(x, z, lig_batch, n_graphs, bonds)
+    out["pair_hist"] = ligand_pair_hist(x, z, lig_batch, n_graphs)
+    edges = torch.from_numpy(_edges(default_bond_edges(), "bond edges", 255)).to(dev)
+    out["bond_bin"] = torch.bucketize(bonds["bond_length"], edges, right=False).to(torch.uint8)
+    code = _element_code(dev)[z]
+    ci, cj = code[bonds["bond_index"][0].to(torch.long)], code[bonds["bond_index"][1].to(torch.long)]
+    out["bond_type"] = (((bonds["bond_order"].to(torch.long) - 1) * 8 + torch.minimum(ci, cj)) * 8 + torch.maximum(ci, cj)).to(torch.int16)
+    n_pair, n_bond_bins, n_angle_bins = DISTRIBUTION_BINS
+    out["bond_hist_index"], out["bond_hist_count"] = _sparse_hist(bonds["bond_graph"], out["bond_type"], out["bond_bin"], N_BOND_TYPES,
+                                                                  n_bond_bins)
+    ok = out["angle_bin"] != ANGLE_BIN_DEGENERATE
+    out["angle_hist_index"], out["angle_hist_count"] = _sparse_hist(out["angle_graph"][ok], out["angle_type"][ok], out["angle_bin"][ok],
+                                                                    N_ANGLE_TYPES, n_angle_bins)
+    return out
+
+
+# ---- type codes and their strings ----------------------------------------------------------------------------------------------------
+_ELEMENTS = (1, 6, 7, 8, 9, 15, 16, 17)      # atomic numbers of the element codes 0 ... 7 (``tables()['elements']``; asserted in the tests)
+
+
+def bond_type_code(code_a, order, code_b):
+    """((order - 1) 8 + code_lo) 8 + code_hi, code_lo <= code_hi: element codes 0 ... 7, order 1 ... 3"""
+    lo, hi = min(code_a, code_b), max(code_a, code_b)
+    return ((order - 1) * 8 + lo) * 8 + hi
+
+
+def angle_type_code(code_a, order_ac, code_c, order_bc, code_b):
+    """the canonical code of an angle a - c - b: of the two orientations the one whose end (code, order) is lexicographically smaller
+    comes first, packed as (((code_1 3 + (o_1 - 1)) 8 + code_c) 3 + (o_2 - 1)) 8 + code_2, in [0, N_ANGLE_TYPES)"""
+    (c1, o1), (c2, o2) = sorted([(code_a, order_ac), (code_b, order_bc)])
+    return (((c1 * 3 + (o1 - 1)) * 8 + code_c) * 3 + (o2 - 1)) * 8 + c2
+
+
+def bond_type_string(code):
+    """'6-6', '6=8', '6#7': atomic numbers in ascending order around the bond symbol, as eval_bond_length._bond_type_str prints them"""
+    code = int(code)
+    return f"{_ELEMENTS[code // 8 % 8]}{BOND_SYMBOLS[code // 64]}{_ELEMENTS[code % 8]}"
+
+
+def angle_type_string(code):
+    """'6-6=8': as eval_bond_angle._angle_type_str prints the canonical orientation"""
+    code = int(code)
+    c2, o2, cc, o1, c1 = code % 8, code // 8 % 3, code // 24 % 8, code // 192 % 3, code // 576
+    return f"{_ELEMENTS[c1]}{BOND_SYMBOLS[o1]}{_ELEMENTS[cc]}{BOND_SYMBOLS[o2]}{_ELEMENTS[c2]}"
+
+
+def _parse_type(key):
+    """a reference key -- 'CC_2A' / 'All_12A', a bond '6-6' or (6, 6, 1), an angle '8=6-6' or (8, 2, 6, 1, 6), in either orientation ->
+    (kind, canonical string) or (None, reason).  Orders are 1, 2, 3 or the symbols - = #; 4, ':' and '?' (what the reference prints for
+    it) name an aromatic bond"""
+    if isinstance(key, str) and key in PAIR_FAMILIES:
+        return "pair_length", key
+    if isinstance(key, str):
+        import re
+        m = re.fullmatch(r"(\d+)([-=#:?])(\d+)(?:([-=#:?])(\d+))?", key.strip())
+        if not m:
+            return None, "not a pair family, a bond type or an angle type"
+        f = [t for t in m.groups() if t is not None]
+        atoms, orders = [int(t) for t in f[0::2]], [BOND_SYMBOLS.index(t) + 1 if t in BOND_SYMBOLS else 4 for t in f[1::2]]
+    else:
+        f = [int(t) for t in key]
+        if len(f) == 3:
+            atoms, orders = f[:2], f[2:]
+        elif len(f) == 5:
+            atoms, orders = f[0::2], f[1::2]
+        else:
+            return None, "not a pair family, a bond type or an angle type"
+    if any(o == 4 for o in orders):
+        return None, "aromatic bond type: table bonds have orders 1, 2, 3 only"
+    if any(o not in (1, 2, 3) for o in orders):
+        return None, "unknown bond order"
+    if any(z not in _ELEMENTS for z in atoms):
+        return None, "an element outside H C N O F P S Cl"
+    codes = [_ELEMENTS.index(z) for z in atoms]
+    if len(codes) == 2:
+        return "bond_length", bond_type_string(bond_type_code(codes[0], orders[0], codes[1]))
+    return "bond_angle", angle_type_string(angle_type_code(codes[0], orders[0], codes[1], orders[1], codes[2]))
+
+
+def _key_string(key):
+    """a reference key as the reference prints it: a string as it is; (6, 6, 4) -> '6?6', (8, 2, 6, 1, 6) -> '8=6-6'"""
+    if isinstance(key, str):
+        return key
+    f = [int(t) for t in key]
+    f = [f[0], f[2], f[1]] if len(f) == 3 else f            # a bond tuple carries its order last
+    return "".join((BOND_SYMBOLS[t - 1] if 1 <= t <= 3 else "?") if k % 2 else str(t) for k, t in enumerate(f))
+
+
+# ---- job totals, summaries, Jensen-Shannon distances ---------------------------------------------------------------------------------
+DISTRIBUTION_COUNT_KEYS = ("n_mol", "n_mol_over_limit", "n_atoms", "n_bonds", "n_angles", "n_degenerate_angles")
+
+
+def distribution_totals_length(bins=DISTRIBUTION_BINS):
+    """the length of the flat totals of ``distribution_totals``"""
+    return len(DISTRIBUTION_COUNT_KEYS) + 2 * bins[0] + N_BOND_TYPES * bins[1] + N_ANGLE_TYPES * bins[2]
+
+
+def _np(t):
+    return t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+
+
+def distribution_totals(dist, graphs=None, bins=DISTRIBUTION_BINS):
+    """what ``batch_distributions`` returned (tensors or arrays) -> the integer totals of its graphs, or of the graphs ``graphs`` = (g0, g1)
+    only, as one flat int64 array that ranks can add: DISTRIBUTION_COUNT_KEYS, then the dense histograms flattened -- pairs [2, bins[0]],
+    bond lengths [N_BOND_TYPES, bins[1]], angles [N_ANGLE_TYPES, bins[2]].  A molecule over the angle limit counts in n_mol and
+    n_mol_over_limit, with its atoms, bonds, pair and bond-length histograms; it has no angles"""
+    gc = _np(dist["graph_counts"]).astype(np.int64).reshape(-1, len(DISTRIBUTION_GRAPH_COLUMNS))
+    g0, g1 = (0, gc.shape[0]) if graphs is None else (int(graphs[0]), int(graphs[1]))
+    n_pair, n_bond_bins, n_angle_bins = bins
+    pair = _np(dist["pair_hist"]).astype(np.int64)
+    if pair.shape[1:] != (2, n_pair):
+        raise ValueError(f"pair_hist is {pair.shape}, expected [B, 2, {n_pair}]")
+    part = gc[g0:g1]
+    head = [part.shape[0], int((part[:, 4] != 0).sum())] + [int(v) for v in part[:, :4].sum(0)]
+
+    def dense(index, count, n_codes, n_bins):
+        index, count = _np(index).astype(np.int64).reshape(3, -1), _np(count).astype(np.int64).reshape(-1)
+        m = (index[0] >= g0) & (index[0] < g1)
+        out = np.zeros(n_codes * n_bins, np.int64)
+        np.add.at(out, index[1][m] * n_bins + index[2][m], count[m])
+        return out
+
+    return np.concatenate([np.asarray(head, np.int64), pair[g0:g1].sum(0).reshape(-1),
+                           dense(dist["bond_hist_index"], dist["bond_hist_count"], N_BOND_TYPES, n_bond_bins),
+                           dense(dist["angle_hist_index"], dist["angle_hist_count"], N_ANGLE_TYPES, n_angle_bins)])
+
+
+def distribution_counts(totals, bins=DISTRIBUTION_BINS):
+    """the flat totals of ``distribution_totals`` as integers by name: ``counts`` (DISTRIBUTION_COUNT_KEYS), ``pair_hist`` [2][bins[0]],
+    ``bond_hist`` / ``angle_hist`` {type string: [counts per bin]} for the types with a non-zero count"""
+    t = np.asarray(totals, dtype=np.int64).reshape(-1)
+    n_pair, n_bond_bins, n_angle_bins = bins
+    n_head = len(DISTRIBUTION_COUNT_KEYS)
+    sizes = [n_head, 2 * n_pair, N_BOND_TYPES * n_bond_bins, N_ANGLE_TYPES * n_angle_bins]
+    if t.shape[0] != sum(sizes):
+        raise ValueError(f"{t.shape[0]} totals, expected {sum(sizes)} for bins {tuple(bins)}")
+    head, pair, bond, angle = np.split(t, np.cumsum(sizes)[:-1])
+    bond, angle = bond.reshape(N_BOND_TYPES, n_bond_bins), angle.reshape(N_ANGLE_TYPES, n_angle_bins)
+    return {"counts": {k: int(v) for k, v in zip(DISTRIBUTION_COUNT_KEYS, head)}, "pair_hist": pair.reshape(2, n_pair).tolist(),
+            "bond_hist": {bond_type_string(k): bond[k].tolist() for k in np.flatnonzero(bond.sum(1))},
+            "angle_hist": {angle_type_string(k): angle[k].tolist() for k in np.flatnonzero(angle.sum(1))}}
+
+
+def summarise_distribution_totals(totals, bins=DISTRIBUTION_BINS):
+    """the normalised distributions of integer totals (``distribution_totals``, summed over ranks): ``pair_length`` {'All_12A', 'CC_2A'},
+    ``bond_length`` {'6-6', '6=8', ...} and ``bond_angle`` {'6-6=8', ...} -- keyed like the reference's profiles, atomic numbers around
+    - = # -- each {'count': n, 'distribution': counts / n}; bond and angle types are listed when their count is non-zero, a pair family
+    always, and a ratio over nothing is nan.  Plus ``counts`` (DISTRIBUTION_COUNT_KEYS).  What the reference compares with a dataset's
+    profile by Jensen-Shannon distance (``jsd_against``)"""
+    c = distribution_counts(totals, bins)
+
+    def profile(h):
+        h = np.asarray(h, np.float64)
+        n = h.sum()
+        return {"count": int(n), "distribution": (h / n if n else np.full(h.shape, np.nan)).tolist()}
+
+    return {"counts": c["counts"], "pair_length": {k: profile(h) for k, h in zip(PAIR_FAMILIES, c["pair_hist"])},
+            "bond_length": {k: profile(h) for k, h in c["bond_hist"].items()},
+            "bond_angle": {k: profile(h) for k, h in c["angle_hist"].items()}}
+
+
+def summarise_distributions(dist):
+    """``summarise_distribution_totals`` of what ``batch_distributions`` returned"""
+    return summarise_distribution_totals(distribution_totals(dist))
+
+
+def distribution_jsd(p, q):
+    """Jensen-Shannon distance (the square root of the divergence, natural logarithm: ``scipy.spatial.distance.jensenshannon``) of two
+    non-negative vectors of equal length; both are normalised to sum 1 first.  nan when either sums to nothing.  ``ring_jsd`` is this over
+    the six ring sizes"""
+    p, q = (np.asarray(v, dtype=np.float64).reshape(-1) for v in (p, q))
+    if p.shape != q.shape or p.shape[0] == 0:
+        raise ValueError(f"distribution_jsd takes two vectors of one length, got {p.shape[0]} and {q.shape[0]}")
+    if not (p.sum() > 0 and q.sum() > 0):
+        return float("nan")
+    p, q = p / p.sum(), q / q.sum()
+    mid = (p + q) / 2.0
+    kl = lambda a, b: np.sum(np.where(a > 0, a * np.log(np.where(a > 0, a, 1.0) / np.where(a > 0, b, 1.0)), 0.0))
+    return float(np.sqrt(max((kl(p, mid) + kl(q, mid)) / 2.0, 0.0)))
+
+
+def jsd_against(summary, reference):
+    """Jensen-Shannon distances of a job's distributions (``summarise_distribution_totals``) against the caller's own reference vectors --
+    none ship with this package.  ``reference``: {key: vector}; a key is 'All_12A' / 'CC_2A', a bond type ('6-6' or (6, 6, 1)) or an angle
+    type ('8=6-6' or (8, 2, 6, 1, 6)) in either orientation (canonicalised here).  Returns {'JSD_<key>': distance or None, ...} under
+    the key's own spelling and ``not_evaluated`` {'JSD_<key>': reason}: a key that names an aromatic bond (type 4) cannot be met by table
+    bonds; a type without a sample has no distribution (the reference reports None there too).  A vector of another length than the
+    job's raises ValueError"""
+    out, why = {}, {}
+    for key, vec in reference.items():
+        name = "JSD_" + _key_string(key)
+        kind, canon = _parse_type(key)
+        if kind is None:
+            out[name], why[name] = None, canon
+            continue
+        mine = summary[kind].get(canon)
+        if mine is None or not mine["count"]:
+            out[name], why[name] = None, "no such type among the samples"
+            continue
+        vec = np.asarray(vec, np.float64).reshape(-1)
+        if vec.shape[0] != len(mine["distribution"]):
+            raise ValueError(f"reference {key!r} has {vec.shape[0]} bins, the job's distribution {len(mine['distribution'])}")
+        out[name] = distribution_jsd(mine["distribution"], vec)
+    out["not_evaluated"] = why
+    return out

@@ -27,6 +27,10 @@ launches per batch (``geometry.batch_bonds``), and ``{out_dir}/bonds_summary.jso
 ``--rings`` adds the ring sizes of that graph -- rings of every size 3 ... 9 in a minimum cycle basis, rings above 9, the shortest ring
 through every atom -- computed on the device in one more launch per batch (``geometry.batch_rings``), and
 ``{out_dir}/rings_summary.json`` for the job.
+``--distributions`` adds the bond angles of that graph to every sample and, per pocket and for the job, the three histograms the
+reference's geometry report compares with a dataset's by Jensen-Shannon distance -- pair distances (All_12A, CC_2A), bond lengths per
+bond type, bond angles per angle type -- computed on the device in two more launches per batch (``geometry.batch_distributions``), and
+``{out_dir}/distributions_summary.json`` for the job; ``--distributions_reference`` adds the distances to the caller's own vectors.
 A checkpoint is the reference's format: ``{'config': ..., 'model': state_dict}`` (``sample.py:153-156``)."""
 import argparse
 import json
@@ -119,6 +123,17 @@ def split_samples(x, c, batch_idx, n_graphs, mode="add_aromatic"):
     return out
 
 
+def load_reference_distributions(path):
+    """``--distributions_reference``: {key: vector} from a ``.npz`` (np.savez(path, **{'6-6': v, ...})) or a ``torch.save``d dict"""
+    if path.endswith(".npz"):
+        with np.load(path) as f:
+            return {k: np.asarray(f[k], np.float64) for k in f.files}
+    raw = torch.load(path, map_location="cpu", weights_only=False)
+    if not isinstance(raw, dict):
+        raise SystemExit(f"sample_cli: {path} does not hold a dict of reference distributions")
+    return {k: np.asarray(v, np.float64) for k, v in raw.items()}
+
+
 def decode_mode(plan_mode, config_mode, num_classes):
     """the atom-type vocabulary the samples are decoded with (sample.py:211-214 passes the transform's ``mode`` on to
     ``reconstruct_mol``): the ``mode`` of the config's assign_atomtype / assign_genatomtype transform (``SamplingPlan.mode``), else the
@@ -135,7 +150,8 @@ def main(argv=None, stats=None):
     construction, sample = model.sample incl. the trajectory download, write = per-pocket records and files; with ``--geometry``
     also geometry = the report's launches, a part of write; with ``--bonds`` also bonds = the bond report's launches and downloads, a part
     of write; with ``--rings`` also rings = the ring report's launch and downloads -- and the bond launches when ``--bonds`` is absent --,
-    a part of write)."""
+    a part of write; with ``--distributions`` also distributions = that report's launches and downloads -- and the bond launches when
+    ``--bonds`` is absent --, a part of write)."""
     t_phase = time.perf_counter()
     phases = {"setup": 0.0, "batch": 0.0, "sample": 0.0, "write": 0.0}
 
@@ -199,6 +215,20 @@ def main(argv=None, stats=None):
                          "bond list (cbgbench_amd/geometry.py).  A sample above 256 atoms or 128 independent cycles is reported "
                          "(ring_status != 0, sizes -1) and left out of the ratios.  Rings of TABLE bonds, not RDKit's SSSR.  Independent "
                          "of --geometry and --bonds: without --bonds the bonds are computed and not written")
+    ap.add_argument("--distributions", action="store_true",
+                    help="add the bond angles of the table-bond graph to every sample (angle_index [3, n] ligand-local rows a, c, b; "
+                         "angle_cos; angle_deg, for convenience only: never binned; angle_type; distribution_status), a `distributions` "
+                         "dict of integer histograms to every pocket record (pair distances [2, 101], bond lengths and bond angles by "
+                         "type) and {out_dir}/distributions_summary.json: the normalised pair-distance (All_12A, CC_2A), bond-length and "
+                         "bond-angle profiles of the reference's geometry report, of the state the record holds, evaluated on the GPU in "
+                         "two launches per batch on the bond list (cbgbench_amd/geometry.py).  Angles are binned in cosine space.  A sample "
+                         "above 16384 angles is reported (distribution_status != 0) and contributes no angles.  TABLE bonds, not RDKit's: "
+                         "no aromatic type.  Independent of --geometry, --bonds and --rings: without --bonds the bonds are computed and "
+                         "not written")
+    ap.add_argument("--distributions_reference", default=None,
+                    help="with --distributions: a .npz or torch.save'd dict {key: vector} of the caller's own reference distributions "
+                         "(keys 'All_12A', 'CC_2A', bond types like '6-6', angle types like '6-6=8' in either orientation; none ship "
+                         "with this package); distributions_summary.json then carries their Jensen-Shannon distances as JSD_<key>")
     ap.add_argument("--atom_num_dist", default=None,
                     help="the reference's size-conditioned ligand-size histogram (repo/datasets/transforms/_atom_num_dist.npy); "
                          "without it ligand sizes are U{10..45}")
@@ -221,6 +251,10 @@ def main(argv=None, stats=None):
         raise SystemExit("sample_cli: --bonds runs on the GPU (cbgx_ligand_bonds_count / _fill have no CPU fallback)")
     if args.rings and dev.type != "cuda":
         raise SystemExit("sample_cli: --rings runs on the GPU (cbgx_ligand_rings has no CPU fallback)")
+    if args.distributions and dev.type != "cuda":
+        raise SystemExit("sample_cli: --distributions runs on the GPU (cbgx_ligand_pair_hist / cbgx_ligand_angles have no CPU fallback)")
+    if args.distributions_reference and not args.distributions:
+        raise SystemExit("sample_cli: --distributions_reference needs --distributions")
 
     ckpt_path = args.checkpoint or config.model.get("checkpoint", None)
     if ckpt_path and os.path.exists(ckpt_path):
@@ -277,6 +311,8 @@ def main(argv=None, stats=None):
     geometry_seconds, job_counts = [0.0], []             # --geometry: wall time of the report, per-sample counts of this rank
     bonds_seconds, job_bond_counts = [0.0], []           # --bonds: likewise
     rings_seconds, job_ring_counts = [0.0], []           # --rings: likewise
+    # --distributions: likewise; the pockets' flat integer totals are added up as they come (one is 3.5 MB)
+    distributions_seconds, job_distribution_totals = [0.0], np.zeros(geometry.distribution_totals_length(), np.int64)
 
     def write_results(ids, traj, batch):
         # sample.py:198-201 hands traj[0] to the reconstruction -- for targetdiff / diffbp that is the state entering the
@@ -305,6 +341,14 @@ def main(argv=None, stats=None):
             rings = geometry.batch_rings({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode, bonds=bonds_dev)
             rings = {k: v.cpu() for k, v in rings.items()}
             rings_seconds[0] += time.perf_counter() - t_rings
+        dists = None
+        if args.distributions:
+            # the same state again, on the bond list of --bonds when there is one (else the bonds are made here and not written)
+            t_dist = time.perf_counter()
+            dists = geometry.batch_distributions({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode,
+                                                 bonds=bonds_dev)
+            dists = {k: v.cpu() for k, v in dists.items()}
+            distributions_seconds[0] += time.perf_counter() - t_dist
         x, c, bidx = x.cpu(), c.cpu(), bidx.cpu()
         if translate:       # back to the frame the pockets came in (sample.py:198-199; here per graph: a batch holds many pockets)
             x = x + batch["ligand_translation"].cpu()
@@ -341,8 +385,23 @@ def main(argv=None, stats=None):
                 smp["n_rings_larger"] = int(gc[g, -3])
                 smp["atom_ring_min"] = rings["atom_ring_min"][atom_end[g] - int(gc[g, 0]):atom_end[g]].clone()
                 smp["ring_status"] = int(gc[g, -1])
+        if dists is not None:
+            # angles are sorted by their centre and atoms by graph: a graph's angles and atoms are ranges; rows become ligand-local
+            gc = dists["graph_counts"].to(torch.int64)
+            atom_end, angle_end = gc[:, 0].cumsum(0).tolist(), gc[:, 2].cumsum(0).tolist()
+            for g, smp in enumerate(samples):
+                a0, n0, n1 = atom_end[g] - int(gc[g, 0]), angle_end[g] - int(gc[g, 2]), angle_end[g]
+                smp["angle_index"] = dists["angle_index"][:, n0:n1] - a0
+                smp["angle_cos"] = dists["angle_cos"][n0:n1].clone()
+                smp["angle_deg"] = torch.from_numpy(np.degrees(np.arccos(smp["angle_cos"].numpy())))
+                smp["angle_type"] = dists["angle_type"][n0:n1].clone()
+                smp["distribution_status"] = int(gc[g, 4])
         for k, pid in enumerate(ids):
             rec = {"pocket_index": pid, "samples": samples[k * num_samples:(k + 1) * num_samples]}
+            if dists is not None:
+                totals = geometry.distribution_totals(dists, graphs=(k * num_samples, (k + 1) * num_samples))
+                job_distribution_totals[:] += totals
+                rec["distributions"] = geometry.distribution_counts(totals)
             if rings is not None:
                 gc = rings["graph_counts"][k * num_samples:(k + 1) * num_samples].to(torch.int64)
                 job_ring_counts.append(gc)
@@ -395,6 +454,8 @@ def main(argv=None, stats=None):
             stats["bonds"] = bonds_seconds[0]
         if args.rings:
             stats["rings"] = rings_seconds[0]
+        if args.distributions:
+            stats["distributions"] = distributions_seconds[0]
     if args.geometry:
         # integer counts of all ranks, summed: the job's numbers do not depend on how the pockets were sharded
         totals = geometry.job_totals(torch.cat(job_counts) if job_counts else torch.zeros(0, len(geometry.GRAPH_COLUMNS)))
@@ -424,6 +485,20 @@ def main(argv=None, stats=None):
             print("rings: " + ", ".join(f"ring_mol_ratio_{k} {summary[f'ring_mol_ratio_{k}']:.4f}" for k in geometry.RING_SIZES)
                   + f", macrocycle_mol_ratio {summary['macrocycle_mol_ratio']:.4f}, ring_atom_ratio {summary['ring_atom_ratio']:.4f}"
                   + f" ({cnt['n_mol_evaluated']} of {cnt['n_mol']} molecules evaluated, {cnt['n_rings']} rings)")
+    if args.distributions:
+        summary = geometry.summarise_distribution_totals(sharding.sum_counts(job_distribution_totals.tolist(), device=dev))
+        if rank == 0:
+            if args.distributions_reference:
+                summary.update(geometry.jsd_against(summary, load_reference_distributions(args.distributions_reference)))
+            with open(os.path.join(out_dir, "distributions_summary.json"), "w") as f:
+                json.dump(summary, f, indent=1, sort_keys=True)
+            cnt, all_12a = summary["counts"], summary["pair_length"]["All_12A"]
+            edges = geometry.default_pair_edges()[0]
+            mode_bin = int(np.argmax(all_12a["distribution"])) if all_12a["count"] else -1
+            # bin b > 0 holds edges[b - 1] < d <= edges[b]; bin 0 the distances that are exactly edges[0]
+            centre = float("nan") if mode_bin < 0 else float(edges[0] if mode_bin == 0 else 0.5 * (edges[mode_bin - 1] + edges[mode_bin]))
+            print(f"distributions: {cnt['n_mol']} molecules, {cnt['n_bonds']} bonds, {cnt['n_angles']} angles, "
+                  f"All_12A modal bin centre {centre:.3f} A, n_mol_over_limit {cnt['n_mol_over_limit']}")
     if rank == 0:
         print(f"sampled {len(pockets)} pockets x {num_samples} samples on {world} rank(s): "
               f"{gs / el:.1f} graph-steps/s, results in {out_dir}")

@@ -790,6 +790,64 @@ int cbgx_ligand_bonds_fill(const float *x_lig, const uint8_t *z_lig, const int32
 int cbgx_ligand_rings(const int32_t *lig_ptr, int n_lig, int n_graphs, const int32_t *bond_ptr, const int32_t *bond_index, int n_bonds,
                       uint8_t *atom_ring_min, int32_t *graph_out, void *stream);
 
+/* ---- distributions of sampled ligands: pair distances, bond lengths, bond angles (distributions.hip) -----------------------------------
+ * The rest of the reference's geometry report (evaluate_scripts/evaluate_geom_single.py; repo/tools/geometry/eval_bond_length.py,
+ *   eval_bond_angle.py): histograms that are compared with a dataset's by Jensen-Shannon distance.  Distances and element codes are those
+ *   of cbgx_ligand_geometry: fp32 coordinates widened to fp64, s = (dx dx + dy dy) + dz dz with every operation rounded on its own,
+ *   d = sqrt(s) correctly rounded, contraction off in the translation unit; codes 0 ... 7 = H C N O F P S Cl.  Same arrays, same limit
+ *   CBGX_GEOMETRY_MAX_LIGAND, same lig_ptr read-back and size check.  No atomics on memory; a graph's rows are a function of its own atoms.
+ * Pair-distance histograms (cbgx_ligand_pair_hist; pair_distance_from_pos_v + get_pair_length_profile, eval_bond_length.py:77-84,
+ *   119-129): per graph two families over the pairs i < j of its ligand atoms -- family 0 (`All`): every pair, atoms of unknown element
+ *   included; family 1 (`CC`): pairs with both atomic numbers 6.  Family f has its own strictly increasing fp64 edge array of
+ *   E_f <= CBGX_PAIR_HIST_MAX_EDGES edges (device memory; that they increase is the caller's contract -- any content gives bins inside
+ *   the row).  A pair takes part iff d < edges[E_f - 1], strictly (so never with E_f == 0, nor with a d that is not a number); its bin is
+ *   the number of edges strictly less than d (np.searchsorted(edges, d), side left).  pair_hist [B, 2, E_max + 1] int32, E_max =
+ *   max(E_0, E_1): every element of every graph is written (bins a family does not have are 0).  The edges are inputs so that the kernel
+ *   never re-derives numpy's linspace arithmetic; the reference's are np.linspace(0, 12, 100) (All_12A) and np.linspace(0, 2, 100) (CC_2A).
+ * Bond angles (cbgx_ligand_angles; bond_angle_from_mol, eval_bond_angle.py:69-96, on the TABLE-bond graph of cbgx_ligand_bonds_fill):
+ *   an angle is an unordered pair {a, b}, a < b, of bonded partners of a centre atom c; the list is in lexicographic (c, a, b) order of
+ *   global ligand rows.  The graph comes as a symmetric adjacency of the bond list: adj_ptr [n_lig + 1] int32, adj_nbr [n_adj] int32
+ *   (n_adj = 2 n_bonds; global rows, ascending per centre), adj_order [n_adj] uint8 (1 ... 3); and angle_ptr [n_lig + 1] int32 = the
+ *   exclusive prefix sum of C(deg, 2) per centre, n_angles = angle_ptr[n_lig].
+ *   With u = x_a - x_c, v = x_b - x_c in fp64: dot = (ux vx + uy vy) + uz vz, su = (ux ux + uy uy) + uz uz, sv likewise,
+ *   cos = dot / sqrt(su sv), every operation rounded on its own, then clamped to [-1, 1].  NO inverse trigonometric function runs on the
+ *   device: angle_bin = the number of entries of the strictly decreasing fp64 table cos_edges [E_a], E_a <= CBGX_ANGLES_MAX_EDGES, that
+ *   are strictly greater than cos -- what searchsorted(edges_deg, theta) gives wherever theta is not within rounding of an edge.  A
+ *   degenerate angle (su sv == 0: a partner coincident with the centre, which IS bonded by the table; or a cos that is not a number, from
+ *   coordinates that are not finite) has angle_cos = NaN and angle_bin = CBGX_ANGLE_BIN_DEGENERATE and belongs to no histogram.
+ *   angle_type int16 = the canonical code of (code_a, order_ac, code_c, order_bc, code_b): of the two orientations the one whose
+ *   (code, order) end pair is lexicographically smaller comes first, packed as (((code_1 3 + (o_1 - 1)) 8 + code_c) 3 + (o_2 - 1)) 8 +
+ *   code_2, in [0, CBGX_ANGLE_TYPES).  The reference appends every angle under both orientations; for a NORMALISED profile that is the
+ *   same distribution as counting each angle once under its canonical type, which is what is done here.
+ *   Outputs: angle_index [3, n_angles] int32 (rows a, c, b: global ligand rows), angle_cos [n_angles] fp64, angle_bin [n_angles] uint8,
+ *   angle_type [n_angles] int16; written without atomics, in that one order.
+ *   Limit: a graph whose number of angles, the sum of C(deg_c, 2) over its centres, exceeds CBGX_ANGLES_MAX_PER_GRAPH (a collapsed
+ *   sample; a sane 128-atom molecule has under 400) is never an error: the caller gives it no slots (its entries of the prefix sum are 0
+ *   wide) and reports it (CBGX_DISTRIBUTIONS_TOO_MANY_ANGLES in the Python side's status column); the kernel writes nothing for such a
+ *   graph whatever angle_ptr says.
+ *   Clamping, as cbgx_ligand_bonds_fill clamps bond_ptr: a centre's adjacency range is clamped to [0, n_adj] and its slots to
+ *   [0, n_angles], both made non-decreasing; the centre writes its first min(slots, C(deg, 2)) angles; an angle with a partner row
+ *   outside the graph's atom range, or an atom without an element code, is skipped.  A wrong angle_ptr or adjacency loses angles (or,
+ *   where slot ranges overlap, overwrites them) and never reaches outside a buffer.
+ * Bond-length bins are elementwise on the bond list (bond_bin = the number of edges strictly less than bond_length, bond_type =
+ *   ((order - 1) 8 + code_lo) 8 + code_hi with code_lo <= code_hi) and are made by the caller; they have no entry here.
+ * Both return 0, and 0 without a launch when B == 0 (cbgx_ligand_angles also when n_angles == 0).  CBGX_E_INVALID before any dereference
+ *   or launch: negative counts, a NULL pointer with a non-zero count, more edges than the limit, a ligand above
+ *   CBGX_GEOMETRY_MAX_LIGAND atoms, lig_ptr the device cannot read. */
+#define CBGX_PAIR_HIST_MAX_EDGES 255
+#define CBGX_ANGLES_MAX_EDGES 254
+#define CBGX_ANGLES_MAX_PER_GRAPH 16384
+#define CBGX_ANGLE_BIN_DEGENERATE 255
+#define CBGX_ANGLE_TYPES 4608
+#define CBGX_DISTRIBUTIONS_TOO_MANY_ANGLES 1
+int cbgx_ligand_pair_hist(const float *x_lig, const uint8_t *z_lig, const int32_t *lig_ptr, int n_lig, int n_graphs,
+                          const double *edges_all, int n_edges_all, const double *edges_cc, int n_edges_cc, int32_t *pair_hist,
+                          void *stream);
+int cbgx_ligand_angles(const float *x_lig, const uint8_t *z_lig, const int32_t *lig_ptr, int n_lig, int n_graphs, const int32_t *adj_ptr,
+                       const int32_t *adj_nbr, const uint8_t *adj_order, int n_adj, const int32_t *angle_ptr, int n_angles,
+                       const double *cos_edges, int n_cos_edges, int32_t *angle_index, double *angle_cos, uint8_t *angle_bin,
+                       int16_t *angle_type, void *stream);
+
 /* ---- measurement hook (bench.py) ----------------------------------------------------------------
  * Between cbgx_profile_begin() and cbgx_profile_end() every kernel launch is bracketed by HIP events on
  * its own stream.  cbgx_profile_end() synchronises them and returns, per kernel class, the summed
