@@ -197,7 +197,7 @@ int cbgx_debug_forward_view(void* workspace, int n_nodes, void** out) {
 int cbgx_set_edge_workgroups(int n) { return set_edge_workgroup_limit(n); }
 
 size_t cbgx_packed_weights_floats(int num_layers, int num_classes) {
-    if (num_layers < 0 || num_classes < 1) return 0;
+    if (num_layers < 0 || num_classes < 1 || num_classes > CBGX_MAX_CLASSES) return 0;
     return packed_floats(num_layers, num_classes);
 }
 
@@ -329,6 +329,7 @@ static int pack_attention_blocks(const BlockRef* refs, int n_blocks, hipStream_t
 }
 
 int cbgx_pack_weights(const float* const* t, int num_tensors, int L, int C, float* packed, void* stream) {
+    if (C > CBGX_MAX_CLASSES) return fail(CBGX_E_INVALID, "pack_weights: num_classes=%d > %d", C, CBGX_MAX_CLASSES);
     if (!t || !packed) return fail(CBGX_E_INVALID, "pack_weights: NULL pointer");
     if (L < 1 || C < 1) return fail(CBGX_E_INVALID, "pack_weights: num_layers=%d num_classes=%d", L, C);
     if (num_tensors != 6 + 36 * L + 4)
@@ -530,6 +531,7 @@ static int classifier_head(const float* packed, int num_layers, int num_classes,
 
 int cbgx_classifier(const float* packed, int num_layers, int num_classes, const float* h, int n_nodes, float* logits,
                     void* workspace, size_t workspace_bytes, void* stream) {
+    if (num_classes > CBGX_MAX_CLASSES) return fail(CBGX_E_INVALID, "classifier: num_classes=%d > %d", num_classes, CBGX_MAX_CLASSES);
     if (n_nodes == 0) return CBGX_OK;
     if (!packed || !h || !logits || !workspace || num_layers < 0 || num_classes < 1 || n_nodes < 0)
         return fail(CBGX_E_INVALID, "classifier: bad argument");
@@ -785,6 +787,7 @@ static int forward_serial(const Forward& f) {
 static int forward_impl(Forward f) {
     if (f.n_nodes < 0 || f.n_graphs < 0 || f.num_layers < 1) return fail(CBGX_E_INVALID, "forward: bad sizes");
     if (f.flags & ~(CBGX_FWD_H_ON_SOURCES | CBGX_FWD_GEN_IS_LIGAND)) return fail(CBGX_E_INVALID, "forward: unknown flags 0x%x", f.flags);
+    if (f.num_classes > CBGX_MAX_CLASSES) return fail(CBGX_E_INVALID, "forward: num_classes=%d > %d", f.num_classes, CBGX_MAX_CLASSES);
     if (f.n_nodes == 0) return CBGX_OK;
     if (!f.packed || !f.x || !f.h || !f.graph_ptr || !f.lig_flag || !f.gen_flag || !f.x_out || !f.workspace)
         return fail(CBGX_E_INVALID, "forward: NULL pointer");

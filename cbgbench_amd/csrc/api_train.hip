@@ -545,6 +545,8 @@ int cbgx_unitransformer_forward_train_ex(const float* packed, int num_layers, in
                                          size_t workspace_bytes, void* stream) {
     if (flags & ~CBGX_FWD_H_ON_SOURCES) return set_error(CBGX_E_INVALID, "forward_train: unknown flags 0x%x", flags);
     if (n_nodes < 0 || n_graphs < 0 || num_layers < 1) return set_error(CBGX_E_INVALID, "forward_train: bad sizes");
+    if (num_classes > CBGX_MAX_CLASSES)
+        return set_error(CBGX_E_INVALID, "forward_train: num_classes=%d > %d", num_classes, CBGX_MAX_CLASSES);
     if (n_nodes == 0) return CBGX_OK;
     if (!packed || !x || !h || !graph_ptr || !lig_flag || !gen_flag || !x_out || !tape || !workspace)
         return set_error(CBGX_E_INVALID, "forward_train: NULL pointer");
@@ -578,7 +580,7 @@ int cbgx_unitransformer_forward_train_ex(const float* packed, int num_layers, in
     // (CBGX_FWD_H_ON_SOURCES: h_out is wanted, but on A1 only -- DiffBP's centre-of-mass head reads it on the movable atoms and their
     // neighbours; the backward then prunes around the support of its dL/dh_out, which lies inside A1, unless CBGX_TRAIN_PRUNE_GH=0)
     const bool fprune = (!h_out || ((flags & CBGX_FWD_H_ON_SOURCES) && env_on("CBGX_TRAIN_PRUNE_GH"))) && num_layers >= 3 &&
-                        g_edge_impl != 1 && env_on("CBGX_TRAIN_FWD_PRUNE") && (!h_out || !logits || num_classes <= 128);
+                        g_edge_impl != 1 && env_on("CBGX_TRAIN_FWD_PRUNE");
     const NodeList every{nullptr, nullptr};
     const NodeList A[3] = {w.A1, w.A2, w.A3};
     if (fprune) {
@@ -706,6 +708,7 @@ int cbgx_unitransformer_backward_ex(const float* packed, int num_layers, int num
                                     float* const* grads, int num_grads, float* grad_h_in, float* grad_x_in, void* workspace,
                                     size_t workspace_bytes, void* stream) {
     if (n_nodes <= 0 || num_layers < 1 || num_classes < 1) return set_error(CBGX_E_INVALID, "backward: bad sizes");
+    if (num_classes > CBGX_MAX_CLASSES) return set_error(CBGX_E_INVALID, "backward: num_classes=%d > %d", num_classes, CBGX_MAX_CLASSES);
     if (!packed || !tape || !lig_flag || !gen_flag || !workspace) return set_error(CBGX_E_INVALID, "backward: NULL pointer");
     if (num_grads != 6 + 36 * num_layers + 4)
         return set_error(CBGX_E_INVALID, "backward: expected %d gradient tensors, got %d", 6 + 36 * num_layers + 4, num_grads);
@@ -724,7 +727,7 @@ int cbgx_unitransformer_backward_ex(const float* packed, int num_layers, int num
     else HIP_TRY(hipMemsetAsync(w.gh, 0, nh * 4, s));
     // (round 6: with a caller gradient on h_out the same listed head runs on the SUPPORT of grad_logits -- the rows with a non-zero
     // entry, marked on the device; DiffBP's losses read the logits of ligand rows only as well.  CBGX_TRAIN_PRUNE_GH=0: the dense head)
-    const bool head_listed = grad_logits && g_edge_impl != 1 && C <= 128 && (grad_h_out == nullptr || env_on("CBGX_TRAIN_PRUNE_GH"));
+    const bool head_listed = grad_logits && g_edge_impl != 1 && (grad_h_out == nullptr || env_on("CBGX_TRAIN_PRUNE_GH"));
     if (grad_logits) {
         NodeList rows = every;
         if (head_listed) {
@@ -755,12 +758,12 @@ int cbgx_unitransformer_backward_ex(const float* packed, int num_layers, int num
     // Round 6: with a caller gradient on h_out the same pruning holds around ITS support (the rows with a non-zero entry, marked on
     // the device): DiffBP's centre-of-mass head reads h_out on the movable atoms and their neighbours only, and until now its
     // training ran all nine x2h blocks -- and the dense products of all nine h2x blocks -- on every row (CBGX_TRAIN_PRUNE_GH=0: as before).
-    const bool prune = (grad_h_out == nullptr || (env_on("CBGX_TRAIN_PRUNE_GH") && (!grad_logits || C <= 128))) && L >= 3;
+    const bool prune = (grad_h_out == nullptr || env_on("CBGX_TRAIN_PRUNE_GH")) && L >= 3;
     if (prune) {
         HIP_TRY(launch_mark_seed(gen_flag, lig_flag, n, w.mask, s));
         if (grad_h_out) {       // the seed: every row where dL/dh_L can be non-zero (no promise about the caller's two gradients)
             HIP_TRY(launch_mark_nonzero_rows(grad_h_out, n, w.mask, s));
-            if (grad_logits && C <= 128) HIP_TRY(launch_mark_nonzero_rows(grad_logits, n, w.mask, s, C, 0));
+            if (grad_logits) HIP_TRY(launch_mark_nonzero_rows(grad_logits, n, w.mask, s, C, 0));
         }
         HIP_TRY(walk_receptive_field(w.mask, w.act, tp.nbr, tp.deg, n, {w.A1, w.A2}, s));
     }

@@ -78,6 +78,11 @@ extern "C" {
 #define CBGX_KNN 32
 #define CBGX_EDGE_TYPES 4
 #define CBGX_GATE_HIDDEN 160
+/* Largest classifier width: the head's node products hold one [128 x num_classes] weight tile per workgroup, so num_classes is
+ * 1 .. CBGX_MAX_CLASSES.  cbgx_pack_weights, every cbgx_unitransformer_forward* entry point, cbgx_classifier and
+ * cbgx_unitransformer_backward(_ex) return CBGX_E_INVALID for a larger value, before anything is launched
+ * (cbgx_packed_weights_floats returns 0). */
+#define CBGX_MAX_CLASSES 128
 
 int cbgx_abi_version(void);
 const char *cbgx_last_error(void);

@@ -210,6 +210,40 @@ def test_abi_argument_errors_without_gpu():
         _native.check(-3, "x")
 
 
+def test_more_than_128_classes_are_refused_without_gpu():
+    """include/cbgx.h CBGX_MAX_CLASSES: the head's node products hold at most 128 output columns, so every entry point that takes
+    num_classes returns CBGX_E_INVALID for 129 with a message that names the limit, before anything is launched (128 passes this check
+    and fails later, on the NULL pointer or the workspace size)"""
+    lib = _native.lib()
+    one = ctypes.c_void_p(16)  # never dereferenced
+    L = 2
+    arr = (ctypes.c_void_p * (6 + 36 * L + 4))(*([16] * (6 + 36 * L + 4)))
+    calls = {
+        "pack_weights": lambda C: lib.cbgx_pack_weights(arr, len(arr), L, C, None, None),
+        "forward": lambda C: lib.cbgx_unitransformer_forward(one, L, C, None, one, one, one, one, 10, 1, one, one, one, one, 8, None),
+        "forward_v2": lambda C: lib.cbgx_unitransformer_forward_v2(one, L, C, None, one, one, one, one, 10, 1, one, one, one, 0, one, 8,
+                                                                   None),
+        "forward_cached": lambda C: lib.cbgx_unitransformer_forward_cached(one, L, C, None, one, one, one, one, 10, 1, one, one, one,
+                                                                           one, one, one, one, one, one, 0, one, 8, None),
+        "forward_train": lambda C: lib.cbgx_unitransformer_forward_train(one, L, C, None, one, one, one, one, 10, 1, one, one, one, one,
+                                                                         8, one, 8, None),
+        "forward_train_ex": lambda C: lib.cbgx_unitransformer_forward_train_ex(one, L, C, None, one, one, one, one, 10, 1, one, one, one,
+                                                                               0, one, 8, one, 8, None),
+        "classifier": lambda C: lib.cbgx_classifier(one, L, C, None, 10, one, one, 8, None),
+        "backward": lambda C: lib.cbgx_unitransformer_backward(one, L, C, None, 8, one, one, 10, one, one, one, arr, len(arr), one,
+                                                               one, 8, None),
+        "backward_ex": lambda C: lib.cbgx_unitransformer_backward_ex(one, L, C, None, 8, one, one, 10, one, one, one, arr, len(arr), one,
+                                                                     one, one, 8, None),
+    }
+    for name, call in calls.items():
+        assert call(129) == -1, name
+        msg = lib.cbgx_last_error()
+        assert b"num_classes=129 > 128" in msg, (name, msg)
+        assert call(128) == -1, name                       # the NULL pointer of the same call
+        assert b"num_classes" not in lib.cbgx_last_error(), (name, lib.cbgx_last_error())
+    assert lib.cbgx_packed_weights_floats(L, 128) > 0 and lib.cbgx_packed_weights_floats(L, 129) == 0
+
+
 # ---- the argument checks of the step entry points (include/cbgx.h), none of which reaches the device ------------------------------
 # An argument: (name, kind, value of the valid call).  Kinds: "p" a required pointer, "o" an optional one (left alone here: the GPU
 # tests cover them), "i" an integer, "f" a float, "tab" the seven-entry table array, "s" the stream.
