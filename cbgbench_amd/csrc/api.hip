@@ -38,7 +38,6 @@ static constexpr auto& fail = cbgx::set_error;
         if (_e != hipSuccess) return fail(CBGX_E_HIP, "%s: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
 
-struct NodeBufs { float *P, *q, *Qt; };   // of one attention block's node stage: projection, query, folded query
 struct Workspace {
     int32_t *nbr, *deg;
     float* e_w;
@@ -392,7 +391,7 @@ int cbgx_h2x_stack_forward_v2(const float* packed, int num_layers, const float* 
     Workspace w;
     if (int rc = carve_checked("h2x_stack", workspace, workspace_bytes, n_nodes, w)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act.rows, w.act.count, s));
+    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act, s));
     if (g_edge_impl == 1) {
         HIP_TRY(launch_knn(x, graph_ptr, n_graphs, n_nodes, w.nbr, w.deg, s));
         HIP_TRY(launch_gate(packed, x, w.nbr, w.deg, n_nodes, w.e_w, s));
@@ -401,24 +400,23 @@ int cbgx_h2x_stack_forward_v2(const float* packed, int num_layers, const float* 
         // both run over the gen_flag list), and the stack's graph is built once from the input coordinates (diffbp.py:84-93): the
         // kNN search and the gate MLP run on the listed rows only -- the ligand atoms, ~5 % of a pocket -- instead of on every node
         // (DiffBP paid 415 + 276 us per step for them at 200 graphs, against 163 + 112 us for the denoiser's cached graph).
-        HIP_TRY(launch_knn_reg(x, graph_ptr, n_graphs, n_nodes, w.nbr, w.deg, s, w.act.rows, w.act.count));
-        HIP_TRY(launch_gate_mfma(packed, x, w.nbr, w.deg, n_nodes, w.e_w, s, w.act.rows, w.act.count));
+        HIP_TRY(launch_knn_reg(x, graph_ptr, n_graphs, n_nodes, w.nbr, w.deg, s, w.act));
+        HIP_TRY(launch_gate_mfma(packed, x, w.nbr, w.deg, n_nodes, w.e_w, s, w.act));
     }
     // The source rows of the stack: the in-neighbours of the movable rows (and those rows themselves).  Only their PS columns are
     // ever gathered, so only they are projected -- and only their rows of h are read, which is what lets the denoiser in front
     // (cbgx_unitransformer_forward_cached, CBGX_FWD_H_ON_SOURCES) skip every other row of its last layers.
-    NodeList src{nullptr, nullptr};
+    RowList src;
     if (g_edge_impl != 1) {
         HIP_TRY(launch_mark_seed(gen_flag, gen_flag, n_nodes, w.fa1, s));
         HIP_TRY(walk_receptive_field(w.fa1, w.act, w.nbr, w.deg, n_nodes, {w.A1}, s));
         src = w.A1;
     }
+    const Graph g{w.nbr, w.deg, w.e_w, lig_flag, gen_flag, n_nodes};
     const float* xc = x;
-    const NodeBufs& b = w.set[0];
     for (int l = 0; l < num_layers; ++l) {
         float* xn = (l == num_layers - 1) ? x_out : w.xbuf[l & 1];
-        HIP_TRY(launch_attention(false, packed + GATE_SIZE + (size_t)l * ATT_SIZE, xc, h, w.nbr, w.deg, lig_flag, gen_flag,
-                                 w.e_w, n_nodes, b.P, b.Qt, b.q, xn, nullptr, w.act.rows, w.act.count, src.rows, src.count, s,
+        HIP_TRY(launch_attention(false, packed + GATE_SIZE + (size_t)l * ATT_SIZE, g, xc, h, w.set[0], xn, nullptr, w.act, src, s,
                                  h2x_lig_selected(flags)));
         xc = xn;
     }
@@ -464,21 +462,22 @@ int cbgx_x2h_attention(const float* packed, int layer, const float* x, const flo
     Workspace w;
     if (int rc = carve_checked("x2h_attention", workspace, workspace_bytes, n_nodes, w)) return rc;
     const NodeBufs& b = w.set[0];
+    const Graph g{nbr, deg, e_w, lig_flag, nullptr, n_nodes};
+    const float* att = packed + x2h_off(layer);
     hipStream_t s = (hipStream_t)stream;
     if (g_edge_impl == 1) {
-        HIP_TRY(launch_attention(true, packed + x2h_off(layer), x, h, nbr, deg, lig_flag, nullptr, e_w, n_nodes, b.P,
-                                 b.Qt, b.q, h_out, nullptr, nullptr, nullptr, nullptr, nullptr, s));
+        HIP_TRY(launch_attention(true, att, g, x, h, b, h_out, nullptr, {}, {}, s));
         return CBGX_OK;
     }
     // what a layer of cbgx_unitransformer_forward runs: protein-only destinations fold their query in registers, Qt is
     // produced for the others only, one two-role edge launch
     HIP_TRY(launch_mark_from_nbr(lig_flag, nbr, deg, n_nodes, w.d1flag, s));
-    HIP_TRY(launch_split_list(nullptr, nullptr, n_nodes, w.d1flag, w.all_gen.rows, w.all_gen.count, w.all_pp.rows, w.all_pp.count, s));
-    const float* att = packed + x2h_off(layer);
-    HIP_TRY(launch_node_mfma(att, h, lig_flag, n_nodes, b.P, b.q, b.Qt, nullptr, nullptr, nullptr, nullptr, s, true,
-                             w.all_gen.rows, w.all_gen.count));
-    HIP_TRY(launch_edge_x2h_dual(att, x, h, b.P, b.Qt, b.q, nbr, deg, lig_flag, nullptr, e_w, n_nodes, h_out, w.all_pp.rows,
-                                 w.all_pp.count, w.all_gen.rows, w.all_gen.count, true, s));
+    HIP_TRY(launch_split_list({}, n_nodes, w.d1flag, w.all_gen, w.all_pp, s));
+    NodeStageOpts o;
+    o.large_lists = true;
+    o.fold = w.all_gen;
+    HIP_TRY(launch_node_mfma(att, h, lig_flag, n_nodes, b, {}, {}, s, o));
+    HIP_TRY(launch_edge_x2h_dual(att, g, x, h, b, h_out, w.all_pp, w.all_gen, true, s));
     return CBGX_OK;
 }
 
@@ -493,10 +492,9 @@ int cbgx_h2x_attention_v2(const float* packed, int layer, const float* x, const 
         return fail(CBGX_E_INVALID, "h2x_attention: bad argument");
     Workspace w;
     if (int rc = carve_checked("h2x_attention", workspace, workspace_bytes, n_nodes, w)) return rc;
-    const NodeBufs& b = w.set[0];
-    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act.rows, w.act.count, (hipStream_t)stream));
-    HIP_TRY(launch_attention(false, packed + h2x_off(layer), x, h, nbr, deg, lig_flag, gen_flag, e_w, n_nodes, b.P,
-                             b.Qt, b.q, x_out, delta_x, w.act.rows, w.act.count, nullptr, nullptr, (hipStream_t)stream,
+    const Graph g{nbr, deg, e_w, lig_flag, gen_flag, n_nodes};
+    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act, (hipStream_t)stream));
+    HIP_TRY(launch_attention(false, packed + h2x_off(layer), g, x, h, w.set[0], x_out, delta_x, w.act, {}, (hipStream_t)stream,
                              h2x_lig_selected(flags)));
     return CBGX_OK;
 }
@@ -514,18 +512,20 @@ int cbgx_node_stage(const float* packed, int layer, int x2h, const float* h, con
     if (n_nodes == 0) return CBGX_OK;
     if (!packed || !h || !lig_flag || !P || !q || !Qt || layer < 0 || n_nodes < 0 || (rows == nullptr) != (n_rows == nullptr))
         return fail(CBGX_E_INVALID, "node_stage: bad argument");
-    HIP_TRY(launch_node_mfma(packed + (x2h ? x2h_off(layer) : h2x_off(layer)), h, lig_flag, n_nodes, P, q, Qt, rows, n_rows, nullptr,
-                             nullptr, (hipStream_t)stream, true, nullptr, nullptr, q_direct != 0));
+    NodeStageOpts o;
+    o.large_lists = true;
+    o.q_direct = q_direct != 0;
+    HIP_TRY(launch_node_mfma(packed + (x2h ? x2h_off(layer) : h2x_off(layer)), h, lig_flag, n_nodes, NodeBufs{P, q, Qt},
+                             RowList{rows, n_rows}, {}, (hipStream_t)stream, o));
     return CBGX_OK;
 }
 
 // the classifier head on every row, or on the listed ones (`hidden`: [n_nodes][128] scratch)
 static int classifier_head(const float* packed, int num_layers, int num_classes, const float* h, int n_nodes, float* hidden,
-                           float* logits, NodeList rows, hipStream_t s) {
+                           float* logits, RowList rows, hipStream_t s) {
     const float* c = packed + cls_off(num_layers);
-    HIP_TRY(launch_node_gemm(h, H, c + C_W0T, c + C_B0, hidden, H, n_nodes, H, 1, s, rows.rows, rows.count));
-    HIP_TRY(launch_node_gemm(hidden, H, c + C_W1T, c + cls_b1(num_classes), logits, num_classes, n_nodes, num_classes, 0, s, rows.rows,
-                             rows.count));
+    HIP_TRY(launch_node_gemm(h, H, c + C_W0T, c + C_B0, hidden, H, n_nodes, H, 1, s, rows));
+    HIP_TRY(launch_node_gemm(hidden, H, c + C_W1T, c + cls_b1(num_classes), logits, num_classes, n_nodes, num_classes, 0, s, rows));
     return CBGX_OK;
 }
 
@@ -537,8 +537,7 @@ int cbgx_classifier(const float* packed, int num_layers, int num_classes, const 
         return fail(CBGX_E_INVALID, "classifier: bad argument");
     Workspace w;
     if (int rc = carve_checked("classifier", workspace, workspace_bytes, n_nodes, w)) return rc;
-    return classifier_head(packed, num_layers, num_classes, h, n_nodes, w.set[0].P, logits, NodeList{nullptr, nullptr},
-                           (hipStream_t)stream);
+    return classifier_head(packed, num_layers, num_classes, h, n_nodes, w.set[0].P, logits, {}, (hipStream_t)stream);
 }
 
 // ---- the denoiser's forward (cbgx_unitransformer_forward, cbgx_unitransformer_forward_cached) ---------------------------------------
@@ -557,6 +556,7 @@ struct Forward {
     const float *static_h1, *static_h2; const int32_t *static_nbr, *static_deg; const float *static_ew, *static_r32sq;
     unsigned flags; void* workspace; size_t workspace_bytes; hipStream_t s;
     Workspace w;
+    Graph graph;                // w.nbr / deg / e_w with the caller's flags: what every attention block of the call runs on
     bool cached, graph_cached, prune, dual;
     bool h2x_lig;               // h2x blocks: ligand-row edge kernel, node stage without the fold (CBGX_FWD_GEN_IS_LIGAND)
     std::vector<LayerPlan> plan;
@@ -584,12 +584,12 @@ static int forward_graph_stage(const Forward& f) {
     static const int merge_gate = [] { const char* e = getenv("CBGX_MERGE_GATE"); return e ? atoi(e) : 1; }();
     if (merge_gate && n_nodes <= GRAPH_LISTS_MAX_NODES) {
         HIP_TRY(launch_knn_merge_gate(f.packed, f.x, f.graph_ptr, n_graphs, n_nodes, f.lig_flag, f.static_nbr, f.static_deg, f.static_ew,
-                                      w.nbr, w.deg, w.e_w, s, w.D1.rows, w.D1.count));
+                                      w.nbr, w.deg, w.e_w, s, w.D1));
     } else {
         const bool carry = merge_gate != 0;
-        HIP_TRY(launch_knn_merge(f.x, f.graph_ptr, n_graphs, n_nodes, f.lig_flag, f.static_nbr, f.static_deg, w.nbr, w.deg, s, w.D1.rows,
-                                 w.D1.count, carry ? f.static_ew : nullptr, carry ? w.e_w : nullptr, carry ? w.newmask : nullptr));
-        HIP_TRY(launch_gate_mfma(f.packed, f.x, w.nbr, w.deg, n_nodes, w.e_w, s, w.D1.rows, w.D1.count, carry ? w.newmask : nullptr));
+        HIP_TRY(launch_knn_merge(f.x, f.graph_ptr, n_graphs, n_nodes, f.lig_flag, f.static_nbr, f.static_deg, w.nbr, w.deg, s, w.D1,
+                                 carry ? f.static_ew : nullptr, carry ? w.e_w : nullptr, carry ? w.newmask : nullptr));
+        HIP_TRY(launch_gate_mfma(f.packed, f.x, w.nbr, w.deg, n_nodes, w.e_w, s, w.D1, carry ? w.newmask : nullptr));
     }
     return CBGX_OK;
 }
@@ -679,20 +679,20 @@ static hipError_t begin_layer(const Forward& f, int l, float*& hn, float*& xn) {
 
 static hipError_t edge_x2h(const Forward& f, int l, const NodeBufs& b, const float* xc, const float* hc, float* hn) {
     const LayerPlan& p = f.plan[l];
-    return launch_edge_x2h_dual(f.packed + x2h_off(l), xc, hc, b.P, b.Qt, b.q, f.w.nbr, f.w.deg, f.lig_flag, f.gen_flag, f.w.e_w,
-                                f.n_nodes, hn, p.pp.rows, p.pp.count, p.gen.rows, p.gen.count, p.full_layer, f.s);
+    return launch_edge_x2h_dual(f.packed + x2h_off(l), f.graph, xc, hc, b, hn, p.pp, p.gen, p.full_layer, f.s);
 }
 // (q straight from h, no q-hidden columns in P: launch_node_mfma, large inputs only)
 static hipError_t node_x2h(const Forward& f, int l, const NodeBufs& b, const float* h_in, hipStream_t on) {
     const LayerPlan& p = f.plan[l];
-    return launch_node_mfma(f.packed + x2h_off(l), h_in, f.lig_flag, f.n_nodes, b.P, b.q, b.Qt, p.dst.rows, p.dst.count, p.src.rows,
-                            p.src.count, on, true, p.gen.rows, p.gen.count, node_qdirect_enabled());
+    NodeStageOpts o;
+    o.large_lists = true;
+    o.fold = p.gen;
+    o.q_direct = node_qdirect_enabled();
+    return launch_node_mfma(f.packed + x2h_off(l), h_in, f.lig_flag, f.n_nodes, b, p.dst, p.src, on, o);
 }
 // the h2x block of layer l, node stage included: moves the `act` rows, whose sources are in A1
 static hipError_t block_h2x(const Forward& f, int l, const NodeBufs& b, const float* xc, const float* hn, float* xn) {
-    const Workspace& w = f.w;
-    return launch_attention(false, f.packed + h2x_off(l), xc, hn, w.nbr, w.deg, f.lig_flag, f.gen_flag, w.e_w, f.n_nodes, b.P, b.Qt, b.q,
-                            xn, nullptr, w.act.rows, w.act.count, w.A1.rows, w.A1.count, f.s, f.h2x_lig);
+    return launch_attention(false, f.packed + h2x_off(l), f.graph, xc, hn, b, xn, nullptr, f.w.act, f.w.A1, f.s, f.h2x_lig);
 }
 
 // Small inputs (round 5): ONE stream and ONE node-stage launch per layer.  The h2x block of layer l and the x2h block of layer
@@ -706,8 +706,7 @@ static int forward_fused(const Forward& f) {
     hipStream_t s = f.s;
     auto add_x2h = [&](NodeStageJobs& jobs, int l) {
         const LayerPlan& p = f.plan[l];
-        const NodeBufs& b = w.set[l & 1];
-        add_node_stage_jobs(jobs, f.packed + x2h_off(l), b.P, b.q, b.Qt, p.dst.rows, p.dst.count, p.src.rows, p.src.count, p.fold_flag);
+        add_node_stage_jobs(jobs, f.packed + x2h_off(l), w.set[l & 1], p.dst, p.src, p.fold_flag);
     };
     NodeStageJobs jobs;
     jobs.n = 0;
@@ -719,16 +718,11 @@ static int forward_fused(const Forward& f) {
         HIP_TRY(begin_layer(f, l, hn, xn));
         HIP_TRY(edge_x2h(f, l, w.set[l & 1], xc, hc, hn));
         jobs.n = 0;
-        add_node_stage_jobs(jobs, f.packed + h2x_off(l), w.set[2].P, w.set[2].q, w.set[2].Qt, w.act.rows, w.act.count, w.A1.rows,
-                            w.A1.count, nullptr, f.h2x_lig);
+        add_node_stage_jobs(jobs, f.packed + h2x_off(l), w.set[2], w.act, w.A1, nullptr, f.h2x_lig);
         if (l + 1 < f.num_layers) add_x2h(jobs, l + 1);
         HIP_TRY(launch_node_stage_jobs(jobs, hn, f.lig_flag, f.n_nodes, s));
-        if (f.h2x_lig)
-            HIP_TRY(launch_edge_h2x_lig(f.packed + h2x_off(l), xc, hn, w.set[2].P, w.set[2].q, w.nbr, w.deg, f.lig_flag, f.gen_flag, w.e_w,
-                                        f.n_nodes, xn, nullptr, w.act.rows, w.act.count, s));
-        else
-            HIP_TRY(launch_edge_mfma(false, f.packed + h2x_off(l), xc, hn, w.set[2].P, w.set[2].Qt, w.nbr, w.deg, f.lig_flag, f.gen_flag,
-                                     w.e_w, f.n_nodes, xn, nullptr, w.act.rows, w.act.count, s));
+        if (f.h2x_lig) HIP_TRY(launch_edge_h2x_lig(f.packed + h2x_off(l), f.graph, xc, hn, w.set[2], xn, nullptr, w.act, s));
+        else HIP_TRY(launch_edge_mfma(false, f.packed + h2x_off(l), f.graph, xc, hn, w.set[2], xn, nullptr, w.act, s));
         xc = xn;
         hc = hn;
     }
@@ -774,8 +768,7 @@ static int forward_serial(const Forward& f) {
             HIP_TRY(edge_x2h(f, l, b, xc, hc, hn));
         } else {
             const LayerPlan& p = f.plan[l];
-            HIP_TRY(launch_attention(true, f.packed + x2h_off(l), xc, hc, w.nbr, w.deg, f.lig_flag, f.gen_flag, w.e_w, f.n_nodes, b.P, b.Qt,
-                                     b.q, hn, nullptr, p.dst.rows, p.dst.count, p.src.rows, p.src.count, f.s));
+            HIP_TRY(launch_attention(true, f.packed + x2h_off(l), f.graph, xc, hc, b, hn, nullptr, p.dst, p.src, f.s));
         }
         HIP_TRY(block_h2x(f, l, b, xc, hn, xn));
         xc = xn;
@@ -793,6 +786,7 @@ static int forward_impl(Forward f) {
         return fail(CBGX_E_INVALID, "forward: NULL pointer");
     if (f.logits && f.num_classes < 1) return fail(CBGX_E_INVALID, "forward: num_classes=%d", f.num_classes);
     if (int rc = carve_checked("forward", f.workspace, f.workspace_bytes, f.n_nodes, f.w)) return rc;
+    f.graph = Graph{f.w.nbr, f.w.deg, f.w.e_w, f.lig_flag, f.gen_flag, f.n_nodes};
     HIP_TRY(hipMemsetAsync(f.w.counters, 0, f.w.counters_bytes, f.s));      // every list count of this call: one fill instead of ~15
     // Static-context cache (optional): static_h1 / static_h2 [N,128] hold the features that leave layer 0 / layer 1 in
     // the ligand-free pocket (rows of ligand atoms unused).  A protein node with no ligand atom among its neighbours sees
@@ -829,7 +823,7 @@ static int forward_impl(Forward f) {
     if (rc || !f.logits) return rc;
     // on what the last layer wrote (begin_layer).  Pruned mode: logits are only defined on ligand rows, which are a subset of A1
     return classifier_head(f.packed, f.num_layers, f.num_classes, f.h_out ? f.h_out : f.w.hbuf[(f.num_layers - 1) & 1], f.n_nodes,
-                           f.w.set[0].P, f.logits, f.prune ? f.w.A1 : NodeList{nullptr, nullptr}, f.s);
+                           f.w.set[0].P, f.logits, f.prune ? RowList(f.w.A1) : RowList(), f.s);
 }
 
 int cbgx_unitransformer_forward_v2(const float* packed, int num_layers, int num_classes, const float* x, const float* h,

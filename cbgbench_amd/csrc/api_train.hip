@@ -202,7 +202,7 @@ static int fold_slabs(const float* src, int n_slabs, size_t stride, int size, fl
 // for the auxiliary work of the block that used the set before it (two blocks earlier -- which also covers g_out: the x2h block two
 // blocks later is the first to overwrite the gradient buffer an x2h block's outer products read).
 struct BlockOverlap {
-    AuxLane* aux;       // auxiliary stream + events of the caller's stream (api.hip); NULL: everything on the caller's stream
+    AuxStream* aux;       // auxiliary stream + events of the caller's stream (api.hip); NULL: everything on the caller's stream
     int next_set;       // set of the next block
     bool used[2];       // done[set] has been recorded
     bool joined = false;
@@ -218,14 +218,12 @@ struct BlockOverlap {
 struct BlockArgs {
     // the block: x2h or h2x, its packed weights, its inputs as the forward saw them, the gradient of its output, the graph
     bool x2h = false;
-    const float *att = nullptr, *x = nullptr, *h_in = nullptr, *g_out = nullptr, *e_w = nullptr;
-    const int32_t *nbr = nullptr, *deg = nullptr;
-    const uint8_t* lig = nullptr;
-    int n = 0;
-    NodeList rows{nullptr, nullptr};       // destination rows of the block ({NULL, NULL}: every row)
+    const float *att = nullptr, *x = nullptr, *h_in = nullptr, *g_out = nullptr;
+    Graph g{};                  // (gen is not read: a block's movable rows are its `rows`)
+    RowList rows;               // destination rows of the block (default: every row)
     // (h2x blocks) a list that contains every row of dP this block can touch (the listed nodes and their neighbours); the dense
     // products and column sums over dP then walk the list instead of all N rows
-    NodeList dp_rows{nullptr, nullptr};
+    RowList dp_rows;
     // the outputs
     float *gh = nullptr, *dx = nullptr, *de_w = nullptr;
     float* const* grads = nullptr;
@@ -241,9 +239,9 @@ struct BlockArgs {
 
 static int attention_block_backward(const BlockArgs& a, TrainWs& w, hipStream_t s) {
     const bool x2h = a.x2h;
-    const int n = a.n;
+    const int n = a.g.n_nodes;
     BlockOverlap* const ov = a.ov;
-    const int *rows = a.rows.rows, *n_rows = a.rows.count, *dp_rows = a.dp_rows.rows, *dp_n_rows = a.dp_rows.count;
+    const RowList rows = a.rows, dp_rows = a.dp_rows;
     const float* dx_init = a.dx_init;
     float* qln = a.qln;
     const int set = (ov && ov->aux) ? ov->next_set : 0;
@@ -273,24 +271,28 @@ static int attention_block_backward(const BlockArgs& a, TrainWs& w, hipStream_t 
     if (!saved) {
 #ifdef CBGX_XCHECK
         if (!mfma) {
-            HIP_TRY(launch_node_gemm_v1(a.h_in, H, a.att + A_WN, a.att + A_BN, w.P, PROW, n, PROW, 0, s, nullptr, nullptr));
+            HIP_TRY(launch_node_gemm_v1(a.h_in, H, a.att + A_WN, a.att + A_BN, w.P, PROW, n, PROW, 0, s, {}));
             HIP_TRY(launch_node_query_v1(a.att, w.P, w.Qt, n, s));
         } else
 #endif
-            HIP_TRY(launch_node_mfma(a.att, a.h_in, a.lig, n, w.P, b.qs, w.Qt, rows, n_rows, nullptr, nullptr, s, x2h));
+        {
+            NodeStageOpts o;
+            o.large_lists = x2h;
+            HIP_TRY(launch_node_mfma(a.att, a.h_in, a.g.lig, n, NodeBufs{w.P, b.qs, w.Qt}, rows, {}, s, o));
+        }
     }
-    if (x2h) HIP_TRY(launch_fold_grad(a.att, a.g_out, n, w.Gt, w.gb, s, mfma ? rows : nullptr, mfma ? n_rows : nullptr));      // (a listed block reads listed rows' folds only)
+    if (x2h) HIP_TRY(launch_fold_grad(a.att, a.g_out, n, w.Gt, w.gb, s, mfma ? rows : RowList()));      // (a listed block reads listed rows' folds only)
     // Edge rows (CBGX_BX_EDGE_ROWS=1, round 6): a full launch of the one-wave-per-node kernel writes d pre of every edge to the edge's own
     // row of w.dE and launch_edge_rows_reduce gathers the rows of every source node in a fixed order -- no atomics on dP.  Every column
     // of dP then has exactly one writer (PD: the edge kernel's plain stores, PS: the gather, q hidden: the query backward), so only the
     // work counters behind it are zeroed.
-    const bool er = gen3 && !rows && a.rin_ready;
+    const bool er = gen3 && !rows.rows && a.rin_ready;
     if (er) HIP_TRY(hipMemsetAsync(b.dP + (size_t)n * PROW, 0, 256, s));
-    else if (!x2h && dp_rows && mfma && ov && ov->aux && env_on("CBGX_TRAIN_ZERO_ROWS"))
+    else if (!x2h && dp_rows.rows && mfma && ov && ov->aux && env_on("CBGX_TRAIN_ZERO_ROWS"))
         // h2x block in the layer loop: every reader of dP walks `dp_rows`, so only those rows are zeroed (a fill of all N rows was 42 MB
         // per block; +0.4 % on the training line, profiles/ab_train_r06r.log)
     {
-        HIP_TRY(launch_zero_rows(b.dP, PROW, dp_rows, dp_n_rows, n, s, dx_init ? a.dx : nullptr, dx_init, n * 3));
+        HIP_TRY(launch_zero_rows(b.dP, PROW, dp_rows, n, s, dx_init ? a.dx : nullptr, dx_init, n * 3));
         dx_init = nullptr;
     } else HIP_TRY(hipMemsetAsync(b.dP, 0, (size_t)n * PROW * sizeof(float) + 256, s));     // (and the work counters behind it)
     if (dx_init) HIP_TRY(hipMemcpyAsync(a.dx, dx_init, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -302,18 +304,17 @@ static int attention_block_backward(const BlockArgs& a, TrainWs& w, hipStream_t 
     // on-device cross-check
 #ifdef CBGX_XCHECK
     if (!mfma)
-        HIP_TRY(launch_edge_backward(x2h, a.att, a.x, Pn, Qn, w.Gt, w.gb, a.g_out, a.nbr, a.deg, a.lig, a.e_w, rows, n_rows, n, b.T,
-                                     b.S, b.sw, b.dP, a.dx, a.de_w, b.partial, eg, s));
+        HIP_TRY(launch_edge_backward(x2h, a.att, a.g, a.x, Pn, Qn, w.Gt, w.gb, a.g_out, rows, b.T, b.S, b.sw, b.dP, a.dx, a.de_w,
+                                     b.partial, eg, s));
     else
 #endif
     if (gen3) {
-        HIP_TRY(launch_edge_backward_x2h(a.att, a.x, Pn, Qn, w.Gt, w.gb, a.nbr, a.deg, a.lig, a.e_w, rows, n_rows, n, b.T, b.S, b.sw,
-                                         b.dP, a.dx, a.de_w, b.partial, w.nk, reinterpret_cast<int*>(b.dP + (size_t)n * PROW), eg, s,
-                                         er ? w.dE : nullptr));
+        HIP_TRY(launch_edge_backward_x2h(a.att, a.g, a.x, Pn, Qn, w.Gt, w.gb, rows, b.T, b.S, b.sw, b.dP, a.dx, a.de_w, b.partial, w.nk,
+                                         reinterpret_cast<int*>(b.dP + (size_t)n * PROW), eg, s, er ? w.dE : nullptr));
         if (er) HIP_TRY(launch_edge_rows_reduce(w.dE, w.rin_ptr, w.rin_edge, n, b.dP, s));
     } else
-        HIP_TRY(launch_edge_backward_mfma(x2h, a.att, a.x, Pn, Qn, w.Gt, w.gb, a.g_out, a.nbr, a.deg, a.lig, a.e_w, rows, n_rows, n,
-                                          b.T, b.S, b.sw, b.dP, a.dx, a.de_w, b.partial, eg, s, 1));
+        HIP_TRY(launch_edge_backward_mfma(x2h, a.att, a.g, a.x, Pn, Qn, w.Gt, w.gb, a.g_out, rows, b.T, b.S, b.sw, b.dP, a.dx, a.de_w,
+                                          b.partial, eg, s, 1));
     float *k0w = a.grads[0], *k0b = a.grads[1], *kg = a.grads[2], *kb = a.grads[3], *k1w = a.grads[4], *k1b = a.grads[5];
     float *v0w = a.grads[6], *v0b = a.grads[7], *vg = a.grads[8], *vb = a.grads[9], *v1w = a.grads[10], *v1b = a.grads[11];
     float *q0w = a.grads[12], *q0b = a.grads[13], *qg = a.grads[14], *qb = a.grads[15], *q1w = a.grads[16], *q1b = a.grads[17];
@@ -355,10 +356,10 @@ static int attention_block_backward(const BlockArgs& a, TrainWs& w, hipStream_t 
     {
         const int tiles = (n + 15) / 16, qgrid = tiles < 1024 ? tiles : 1024;   // 25 KB of LDS, four waves per SIMD: four workgroups per CU
 #ifdef CBGX_XCHECK
-        if (!mfma) HIP_TRY(launch_q_backward(a.att, Pn, b.T, rows, n_rows, n, b.qs, b.dqb, b.zb, b.dP, qln, qgrid, s));
+        if (!mfma) HIP_TRY(launch_q_backward(a.att, Pn, b.T, rows, n, b.qs, b.dqb, b.zb, b.dP, qln, qgrid, s));
         else
 #endif
-            HIP_TRY(launch_q_backward_mfma(a.att, Pn, b.T, rows, n_rows, n, b.qs, b.dqb, b.zb, b.dP, qln, qgrid, s));
+            HIP_TRY(launch_q_backward_mfma(a.att, Pn, b.T, rows, n, b.qs, b.dqb, b.zb, b.dP, qln, qgrid, s));
     }
     // ---- from here to the reduce-and-store: weight gradients only.  With `ov` they go to the auxiliary stream (`s` is shadowed) and
     // dgrad -- what the next block waits for -- is issued on the caller's stream first.
@@ -367,8 +368,7 @@ static int attention_block_backward(const BlockArgs& a, TrainWs& w, hipStream_t 
     // dL/dh_in = (gh_src or gh itself) + dP Wn^T
     auto dgrad = [&](hipStream_t st) -> int {
         if (mfma)
-            HIP_TRY(launch_dgrad_mfma(b.dP, PROW, a.att + A_WN, PROW, a.gh, H, n, PROW, 1, st, a.gh_src, a.gh_src ? nullptr : dp_rows,
-                                      a.gh_src ? nullptr : dp_n_rows));
+            HIP_TRY(launch_dgrad_mfma(b.dP, PROW, a.att + A_WN, PROW, a.gh, H, n, PROW, 1, st, a.gh_src, a.gh_src ? RowList() : dp_rows));
         else {
             if (a.gh_src && a.gh_src != a.gh) HIP_TRY(hipMemcpyAsync(a.gh, a.gh_src, (size_t)n * H * 4, hipMemcpyDeviceToDevice, st));
             HIP_TRY(launch_sgemm(false, true, b.dP, PROW, a.att + A_WN, PROW, a.gh, H, n, H, PROW, 1, 0, 1, st));
@@ -390,14 +390,14 @@ static int attention_block_backward(const BlockArgs& a, TrainWs& w, hipStream_t 
     const auto outer = launch_outer_accum_mfma;
 #endif
     float* pn = b.partial_node;
-    HIP_TRY(outer(true, b.qs, b.T, rows, n_rows, n, pn + NS_WBK, NS_SIZE, ng, s));
+    HIP_TRY(outer(true, b.qs, b.T, rows, n, pn + NS_WBK, NS_SIZE, ng, s));
     if (x2h) {
-        HIP_TRY(outer(true, a.g_out, b.S, rows, n_rows, n, pn + NS_WBV, NS_SIZE, ng, s));
-        HIP_TRY(launch_colsum(a.g_out, H, H, b.sw, rows, n_rows, n, pn + NS_V1B, NS_SIZE, ng, s));
+        HIP_TRY(outer(true, a.g_out, b.S, rows, n, pn + NS_WBV, NS_SIZE, ng, s));
+        HIP_TRY(launch_colsum(a.g_out, H, H, b.sw, rows, n, pn + NS_V1B, NS_SIZE, ng, s));
     }
-    HIP_TRY(outer(false, b.dqb, b.zb, rows, n_rows, n, pn + NS_WQ1, NS_SIZE, ng, s));
-    HIP_TRY(launch_colsum(b.dqb, H, H, nullptr, rows, n_rows, n, pn + NS_Q1B, NS_SIZE, ng, s));
-    HIP_TRY(launch_colsum(b.dP, PROW, PROW, nullptr, dp_rows, dp_n_rows, n, pn + NS_DP, NS_SIZE, ng, s));
+    HIP_TRY(outer(false, b.dqb, b.zb, rows, n, pn + NS_WQ1, NS_SIZE, ng, s));
+    HIP_TRY(launch_colsum(b.dqb, H, H, nullptr, rows, n, pn + NS_Q1B, NS_SIZE, ng, s));
+    HIP_TRY(launch_colsum(b.dP, PROW, PROW, nullptr, dp_rows, n, pn + NS_DP, NS_SIZE, ng, s));
     {
         folded(pn, ng, NS_SIZE, NS_SIZE, b.folded_node);
         piece(fz + NS_WBK, fn, fs, H, H, H, k1w, H, 0);
@@ -417,8 +417,7 @@ static int attention_block_backward(const BlockArgs& a, TrainWs& w, hipStream_t 
     // dense projection: dWn[k][n] = sum_i h_in[i][k] dP[i][n]  -> h_dst / h_src / q columns of the first Linears
     const int sp = mfma ? wgrad_groups(n) : (splits_for(n) > 32 ? 32 : splits_for(n));
     if (mfma)
-        HIP_TRY(launch_wgrad_mfma(a.h_in, H, b.dP, PROW, n, PROW / H, b.partial_wgrad, PROW, (size_t)H * PROW, sp, s, dp_rows,
-                                  dp_n_rows));
+        HIP_TRY(launch_wgrad_mfma(a.h_in, H, b.dP, PROW, n, PROW / H, b.partial_wgrad, PROW, (size_t)H * PROW, sp, s, dp_rows));
     else
         HIP_TRY(launch_sgemm(true, false, a.h_in, H, b.dP, PROW, b.partial_wgrad, PROW, H, PROW, n, sp, (size_t)H * PROW, 0, s));
     {
@@ -443,8 +442,8 @@ static int attention_block_backward(const BlockArgs& a, TrainWs& w, hipStream_t 
 // backward of the distance gate: weight gradients from the accumulated dL/de_w, on the workspace's gate slabs (no buffer of a block set);
 // grad_x != NULL: the gate's coordinate gradient is also ADDED to grad_x (the kernel's DX variant)
 static int gate_backward(const float* packed, const float* xs, const int32_t* nbr, const int32_t* deg, int n, TrainWs& w,
-                         float* const* grads, hipStream_t s, NodeList rows, float* grad_x) {
-    HIP_TRY(launch_gate_backward_mfma(packed, xs, nbr, deg, n, w.de_w, w.gate_partial, GATE_GRID, s, rows.rows, rows.count, grad_x));
+                         float* const* grads, hipStream_t s, RowList rows, float* grad_x) {
+    HIP_TRY(launch_gate_backward_mfma(packed, xs, nbr, deg, n, w.de_w, w.gate_partial, GATE_GRID, s, rows, grad_x));
     Slabs f;
     RC_TRY(fold_slabs(w.gate_partial, GATE_GRID, GB_SIZE, GB_SIZE, w.gate_folded, f, s));
     auto rs = [&](int off, int ld, int rws, int cls, float* dst) { return launch_reduce_store(f.p + off, f.n, f.stride, ld, rws, cls, dst, ld, 0, s); };
@@ -463,7 +462,7 @@ static int gate_backward(const float* packed, const float* xs, const int32_t* nb
 // The head then walks a twentieth of the nodes: listed node GEMMs for the recompute, listed weight- / input-gradient products, nothing
 // read outside the list.  {NULL, NULL}: every row.  The scratch is borrowed from block set 0 (no block has run yet).
 static int classifier_head_backward(const float* c, int C, const float* hl, const float* grad_logits, int n, TrainWs& w,
-                                    float* const* cg, NodeList rows, hipStream_t s) {
+                                    float* const* cg, RowList rows, hipStream_t s) {
     BlockSet& b = w.set[0];
     float *pre = b.qs, *act = b.zb, *dact = b.dqb;      // [N,128] scratch (a listed head: listed rows only)
     const int ng = node_grid(n), sp = splits_for(n), wg = wgrad_groups(n);
@@ -475,27 +474,27 @@ static int classifier_head_backward(const float* c, int C, const float* hl, cons
         HIP_TRY(launch_reduce_store(f.p, f.n, f.stride, cls, rws, cls, dst, cls, 0, s));
         return CBGX_OK;
     };
-    HIP_TRY(launch_node_gemm(hl, H, c + C_W0T, c + C_B0, pre, H, n, H, 0, s, rows.rows, rows.count));
-    HIP_TRY(launch_node_gemm(hl, H, c + C_W0T, c + C_B0, act, H, n, H, 1, s, rows.rows, rows.count));
+    HIP_TRY(launch_node_gemm(hl, H, c + C_W0T, c + C_B0, pre, H, n, H, 0, s, rows));
+    HIP_TRY(launch_node_gemm(hl, H, c + C_W0T, c + C_B0, act, H, n, H, 1, s, rows));
     // classifier.2: dW1[c][k] = sum_i dlogits[i][c] act[i][k];  db1 = colsum(dlogits)
-    if (rows.rows) HIP_TRY(launch_cls_w1_grad_rows(grad_logits, C, act, rows.rows, rows.count, cg[2], s));
+    if (rows.rows) HIP_TRY(launch_cls_w1_grad_rows(grad_logits, C, act, rows, cg[2], s));
     else {
         HIP_TRY(launch_sgemm(true, false, grad_logits, C, act, H, b.partial, H, C, H, n, sp, (size_t)C * H, 0, s));
         RC_TRY(reduce(sp, C, H, cg[2]));
     }
-    HIP_TRY(launch_colsum(grad_logits, C, C, nullptr, rows.rows, rows.count, n, b.partial, C, ng, s));
+    HIP_TRY(launch_colsum(grad_logits, C, C, nullptr, rows, n, b.partial, C, ng, s));
     RC_TRY(reduce(ng, 1, C, cg[3]));
     // d(act) = dlogits W1 (C_W1T is [128][C]; all rows: a [N x C] x [C x 128] product, zero outside the list);  d(pre) = d(act) sigmoid(pre)
     HIP_TRY(launch_sgemm(false, true, grad_logits, C, c + C_W1T, C, dact, H, n, H, C, 1, 0, 0, s));
-    if (rows.rows) HIP_TRY(launch_ssp_backward_rows(pre, dact, rows.rows, rows.count, n, w.tmp, s));
+    if (rows.rows) HIP_TRY(launch_ssp_backward_rows(pre, dact, rows, n, w.tmp, s));
     else HIP_TRY(launch_ssp_backward(pre, dact, (long)n * H, w.tmp, s));
     // classifier.0: dW0[n][k] = sum_i dpre[i][n] h[i][k];  db0 = colsum(dpre);  dh += dpre W0
-    if (mfma) HIP_TRY(launch_wgrad_mfma(w.tmp, H, hl, H, n, 1, b.partial, H, (size_t)H * H, wg, s, rows.rows, rows.count));
+    if (mfma) HIP_TRY(launch_wgrad_mfma(w.tmp, H, hl, H, n, 1, b.partial, H, (size_t)H * H, wg, s, rows));
     else HIP_TRY(launch_sgemm(true, false, w.tmp, H, hl, H, b.partial, H, H, H, n, sp, (size_t)H * H, 0, s));
     RC_TRY(reduce(mfma ? wg : sp, H, H, cg[0]));
-    HIP_TRY(launch_colsum(w.tmp, H, H, nullptr, rows.rows, rows.count, n, b.partial, H, ng, s));
+    HIP_TRY(launch_colsum(w.tmp, H, H, nullptr, rows, n, b.partial, H, ng, s));
     RC_TRY(reduce(ng, 1, H, cg[1]));
-    if (mfma) HIP_TRY(launch_dgrad_mfma(w.tmp, H, c + C_W0T, H, w.gh, H, n, H, 1, s, nullptr, rows.rows, rows.count));
+    if (mfma) HIP_TRY(launch_dgrad_mfma(w.tmp, H, c + C_W0T, H, w.gh, H, n, H, 1, s, nullptr, rows));
     else HIP_TRY(launch_sgemm(false, true, w.tmp, H, c + C_W0T, H, w.gh, H, n, H, H, 1, 0, 1, s));
     return CBGX_OK;
 }
@@ -560,16 +559,17 @@ int cbgx_unitransformer_forward_train_ex(const float* packed, int num_layers, in
     HIP_TRY(hipMemcpyAsync(tp.hs, h, nh * 4, hipMemcpyDeviceToDevice, s));
     HIP_TRY(launch_knn(x, graph_ptr, n_graphs, n_nodes, tp.nbr, tp.deg, s));
     HIP_TRY(launch_gate(packed, x, tp.nbr, tp.deg, n_nodes, tp.e_w, s));
-    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act.rows, w.act.count, s));
+    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act, s));
+    const Graph g{tp.nbr, tp.deg, tp.e_w, lig_flag, gen_flag, n_nodes};
     // Round 6: the node stage of the x2h block of layer l + 1 (projection, query MLP, fold: ~57 us at 16.5 k nodes) reads h_{l+1} only,
     // like the h2x block of layer l (~60 us) -- it runs on the caller's auxiliary stream next to that block (what the sampling forward
     // has done since round 3); every block owns its P / Qt on the tape, the two node stages use different query scratch rows.
     // +0.7 % on the training line (profiles/ab_train_r06r.log).  CBGX_TRAIN_OVERLAP=0 / CBGX_TRAIN_FWD_OVERLAP=0, the per-kernel
     // profile and the VALU cross-check kernels keep one stream.
-    AuxLane* aux = (env_on("CBGX_TRAIN_OVERLAP") && env_on("CBGX_TRAIN_FWD_OVERLAP") && g_edge_impl == 0 && !profile_is_on() &&
+    AuxStream* aux = (env_on("CBGX_TRAIN_OVERLAP") && env_on("CBGX_TRAIN_FWD_OVERLAP") && g_edge_impl == 0 && !profile_is_on() &&
                     num_layers > 1) ? aux_for(s) : nullptr;
     struct Joiner {     // a failure between fork and join must not leave the auxiliary stream writing the tape
-        AuxLane* a; bool out = false;
+        AuxStream* a; bool out = false;
         ~Joiner() { if (a && out) (void)hipStreamSynchronize(a->s); }
     } jn{aux};
     // Round 6, h_out == NULL (the caller does not read h': TargetDiff / DiffSBDD training, whose backward then comes with
@@ -595,41 +595,36 @@ int cbgx_unitransformer_forward_train_ex(const float* packed, int num_layers, in
     };
     const NodeList a1 = fprune ? w.A1 : every;     // sources of the h2x blocks; rows of the logits
     float *qs = w.set[0].qs, *qs_aux = w.set[1].qs;     // query scratch borrowed from the block sets: caller's / auxiliary stream
+    // the node stage of block k (2l: x2h, 2l + 1: h2x) lives on the tape; `q`: the query scratch of the stream it runs on
+    auto bufs = [&](int k, float* q) { return NodeBufs{tp.P + (size_t)k * n_nodes * PROW, q, tp.Qt + (size_t)k * n_nodes * HEADS * H}; };
+    NodeStageOpts large;
+    large.large_lists = true;
     for (int l = 0; l < num_layers; ++l) {
         const float* xc = tp.xs + (size_t)l * nx;
         const float* hc = tp.hs + (size_t)l * nh;
         float* xn = tp.xs + (size_t)(l + 1) * nx;
         float* hn = tp.hs + (size_t)(l + 1) * nh;
-        float* Px = tp.P + (size_t)(2 * l) * n_nodes * PROW;
-        float* Qx = tp.Qt + (size_t)(2 * l) * n_nodes * HEADS * H;
         NodeList d, sr;
         x2h_lists(l, d, sr);
         if (d.rows) HIP_TRY(hipMemsetAsync(hn, 0, nh * 4, s));      // rows the listed launch does not write
         if (!aux) {
-            HIP_TRY(launch_attention(true, packed + x2h_off(l), xc, hc, tp.nbr, tp.deg, lig_flag, gen_flag, tp.e_w, n_nodes,
-                                     Px, Qx, qs, hn, nullptr, d.rows, d.count, sr.rows, sr.count, s));
+            HIP_TRY(launch_attention(true, packed + x2h_off(l), g, xc, hc, bufs(2 * l, qs), hn, nullptr, d, sr, s));
         } else {
             if (l == 0)
-                HIP_TRY(launch_node_mfma(packed + x2h_off(0), hc, lig_flag, n_nodes, Px, qs_aux, Qx, d.rows, d.count, sr.rows, sr.count, s,
-                                         true));
+                HIP_TRY(launch_node_mfma(packed + x2h_off(0), hc, lig_flag, n_nodes, bufs(0, qs_aux), d, sr, s, large));
             else { HIP_TRY(hipStreamWaitEvent(s, aux->join, 0)); jn.out = false; }      // this layer's node stage (auxiliary stream)
-            HIP_TRY(launch_edge_mfma(true, packed + x2h_off(l), xc, hc, Px, Qx, tp.nbr, tp.deg, lig_flag, gen_flag, tp.e_w, n_nodes,
-                                     hn, nullptr, d.rows, d.count, s));
+            HIP_TRY(launch_edge_mfma(true, packed + x2h_off(l), g, xc, hc, bufs(2 * l, qs_aux), hn, nullptr, d, s));
             if (l + 1 < num_layers) {
                 NodeList d2, s2;
                 x2h_lists(l + 1, d2, s2);
                 HIP_TRY(hipEventRecord(aux->fork, s));
                 HIP_TRY(hipStreamWaitEvent(aux->s, aux->fork, 0));
                 jn.out = true;
-                HIP_TRY(launch_node_mfma(packed + x2h_off(l + 1), hn, lig_flag, n_nodes, tp.P + (size_t)(2 * l + 2) * n_nodes * PROW,
-                                         qs_aux, tp.Qt + (size_t)(2 * l + 2) * n_nodes * HEADS * H, d2.rows, d2.count, s2.rows, s2.count,
-                                         aux->s, true));
+                HIP_TRY(launch_node_mfma(packed + x2h_off(l + 1), hn, lig_flag, n_nodes, bufs(2 * l + 2, qs_aux), d2, s2, aux->s, large));
                 HIP_TRY(hipEventRecord(aux->join, aux->s));
             }
         }
-        HIP_TRY(launch_attention(false, packed + h2x_off(l), xc, hn, tp.nbr, tp.deg, lig_flag, gen_flag, tp.e_w, n_nodes,
-                                 Px + (size_t)n_nodes * PROW, Qx + (size_t)n_nodes * HEADS * H, qs, xn, nullptr, w.act.rows,
-                                 w.act.count, a1.rows, a1.count, s));
+        HIP_TRY(launch_attention(false, packed + h2x_off(l), g, xc, hn, bufs(2 * l + 1, qs), xn, nullptr, w.act, a1, s));
     }
     const float* hl = tp.hs + (size_t)num_layers * nh;
     HIP_TRY(hipMemcpyAsync(x_out, tp.xs + (size_t)num_layers * nx, nx * 4, hipMemcpyDeviceToDevice, s));
@@ -638,9 +633,9 @@ int cbgx_unitransformer_forward_train_ex(const float* packed, int num_layers, in
         if (num_classes < 1) return set_error(CBGX_E_INVALID, "forward_train: num_classes=%d", num_classes);
         const float* c = packed + cls_off(num_layers);
         // (pruned: the logits of the A1 rows -- the ligand rows are among them; other rows of `logits` are not written)
-        HIP_TRY(launch_node_gemm(hl, H, c + C_W0T, c + C_B0, w.P, H, n_nodes, H, 1, s, a1.rows, a1.count));
+        HIP_TRY(launch_node_gemm(hl, H, c + C_W0T, c + C_B0, w.P, H, n_nodes, H, 1, s, a1));
         HIP_TRY(launch_node_gemm(w.P, H, c + C_W1T, c + cls_b1(num_classes), logits, num_classes, n_nodes, num_classes,
-                                 0, s, a1.rows, a1.count));
+                                 0, s, a1));
     }
     return CBGX_OK;
 }
@@ -664,7 +659,7 @@ int cbgx_x2h_attention_backward(const float* packed, int layer, const float* x, 
     if (rin) HIP_TRY(launch_rin_build(nbr, deg, n_nodes, w.rin_cnt, w.rin_ptr, w.rin_tmp, w.rin_edge, s));
     BlockArgs a;
     a.x2h = true; a.att = packed + x2h_off(layer); a.x = x; a.h_in = h; a.g_out = grad_h_out;
-    a.nbr = nbr; a.deg = deg; a.lig = lig_flag; a.e_w = e_w; a.n = n_nodes;
+    a.g = Graph{nbr, deg, e_w, lig_flag, nullptr, n_nodes};
     a.gh = grad_h; a.dx = grad_x; a.de_w = grad_e_w; a.grads = grads; a.rin_ready = rin;
     return attention_block_backward(a, w, s);
 }
@@ -681,13 +676,13 @@ int cbgx_h2x_attention_backward(const float* packed, int layer, const float* x, 
     TrainWs w;
     RC_TRY(carve_train_checked("h2x_backward", workspace, workspace_bytes, n_nodes, w));
     hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act.rows, w.act.count, s));
+    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act, s));
     HIP_TRY(hipMemsetAsync(grad_h, 0, (size_t)n_nodes * H * 4, s));
     HIP_TRY(hipMemcpyAsync(grad_x, grad_x_out, (size_t)n_nodes * 3 * 4, hipMemcpyDeviceToDevice, s));   // x_out = x + ...
     HIP_TRY(hipMemsetAsync(grad_e_w, 0, (size_t)n_nodes * KNN * 4, s));
     BlockArgs a;
     a.att = packed + h2x_off(layer); a.x = x; a.h_in = h; a.g_out = grad_x_out;
-    a.nbr = nbr; a.deg = deg; a.lig = lig_flag; a.e_w = e_w; a.n = n_nodes; a.rows = w.act;
+    a.g = Graph{nbr, deg, e_w, lig_flag, gen_flag, n_nodes}; a.rows = w.act;
     a.gh = grad_h; a.dx = grad_x; a.de_w = grad_e_w; a.grads = grads;
     return attention_block_backward(a, w, s);
 }
@@ -721,6 +716,7 @@ int cbgx_unitransformer_backward_ex(const float* packed, int num_layers, int num
     const int n = n_nodes, L = num_layers, C = num_classes;
     const size_t nx = (size_t)n * 3, nh = (size_t)n * H;
     const NodeList every{nullptr, nullptr};
+    const Graph graph{tp.nbr, tp.deg, tp.e_w, lig_flag, gen_flag, n};
 
     // dL/dh_L: the caller's gradient plus the classifier head
     if (grad_h_out) HIP_TRY(hipMemcpyAsync(w.gh, grad_h_out, nh * 4, hipMemcpyDeviceToDevice, s));
@@ -734,9 +730,9 @@ int cbgx_unitransformer_backward_ex(const float* packed, int num_layers, int num
             rows = w.head_rows();
             if (grad_h_out) {       // no promise about grad_logits: its support
                 HIP_TRY(launch_mark_nonzero_rows(grad_logits, n, w.mask, s, C, 1));
-                HIP_TRY(launch_build_active(w.mask, n, rows.rows, rows.count, s));
+                HIP_TRY(launch_build_active(w.mask, n, rows, s));
             } else
-                HIP_TRY(launch_build_active(lig_flag, n, rows.rows, rows.count, s));
+                HIP_TRY(launch_build_active(lig_flag, n, rows, s));
         }
         RC_TRY(classifier_head_backward(packed + cls_off(L), C, tp.hs + (size_t)L * nh, grad_logits, n, w, grads + 6 + 36 * L, rows, s));
     } else {
@@ -750,7 +746,7 @@ int cbgx_unitransformer_backward_ex(const float* packed, int num_layers, int num
     if (grad_x_out) HIP_TRY(hipMemcpyAsync(w.gx[cur], grad_x_out, nx * 4, hipMemcpyDeviceToDevice, s));
     else HIP_TRY(hipMemsetAsync(w.gx[cur], 0, nx * 4, s));
     HIP_TRY(hipMemsetAsync(w.de_w, 0, (size_t)n * KNN * 4, s));
-    HIP_TRY(launch_build_active(gen_flag, n, w.act.rows, w.act.count, s));
+    HIP_TRY(launch_build_active(gen_flag, n, w.act, s));
     // Receptive-field pruning, the mirror image of the forward's: without a caller gradient on h_out, dL/dh_L is non-zero
     // on ligand rows only (classifier), the last h2x block adds rows of A1 = gen | lig | nbr(gen), and the x2h block of a
     // layer spreads its input gradient one hop further (A2 = A1 | nbr(A1)).  Rows outside carry an exactly zero gradient
@@ -793,7 +789,7 @@ int cbgx_unitransformer_backward_ex(const float* packed, int num_layers, int num
         const float* Px = tp.P + (size_t)(2 * l) * n * PROW;
         const float* Qx = tp.Qt + (size_t)(2 * l) * n * HEADS * H;
         BlockArgs both;     // what the layer's two blocks share
-        both.x = xl; both.nbr = tp.nbr; both.deg = tp.deg; both.lig = lig_flag; both.e_w = tp.e_w; both.n = n;
+        both.x = xl; both.g = graph;
         both.dx = w.gx[nxt]; both.de_w = w.de_w; both.ov = &ov;
         BlockArgs a = both;
         a.att = packed + h2x_off(l); a.h_in = h_mid; a.g_out = w.gx[cur]; a.rows = w.act;
@@ -870,15 +866,15 @@ int cbgx_h2x_stack_forward_train(const float* packed, int num_layers, const floa
     hipStream_t s = (hipStream_t)stream;
     const size_t nx = (size_t)n_nodes * 3;
     HIP_TRY(hipMemcpyAsync(tp.xs, x, nx * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act.rows, w.act.count, s));
+    HIP_TRY(launch_build_active(gen_flag, n_nodes, w.act, s));
     // As cbgx_h2x_stack_forward (api.hip): an h2x block only reads the neighbour lists and gate values of the rows it moves and the
     // projections of their in-neighbours, so the kNN search, the gate MLP and the neighbour projection run on those lists (round 6;
     // the backward walks the same lists -- CBGX_TRAIN_STACK_LISTS=0 switches both back to all rows)
     const bool lists = g_edge_impl == 0 && env_on("CBGX_TRAIN_STACK_LISTS");
-    NodeList src{nullptr, nullptr};
+    RowList src;
     if (lists) {
-        HIP_TRY(launch_knn_reg(x, graph_ptr, n_graphs, n_nodes, tp.nbr, tp.deg, s, w.act.rows, w.act.count));
-        HIP_TRY(launch_gate_mfma(packed, x, tp.nbr, tp.deg, n_nodes, tp.e_w, s, w.act.rows, w.act.count));
+        HIP_TRY(launch_knn_reg(x, graph_ptr, n_graphs, n_nodes, tp.nbr, tp.deg, s, w.act));
+        HIP_TRY(launch_gate_mfma(packed, x, tp.nbr, tp.deg, n_nodes, tp.e_w, s, w.act));
         HIP_TRY(launch_mark_seed(gen_flag, gen_flag, n_nodes, w.mask, s));
         HIP_TRY(walk_receptive_field(w.mask, w.act, tp.nbr, tp.deg, n_nodes, {w.A1}, s));
         src = w.A1;
@@ -886,10 +882,11 @@ int cbgx_h2x_stack_forward_train(const float* packed, int num_layers, const floa
         HIP_TRY(launch_knn(x, graph_ptr, n_graphs, n_nodes, tp.nbr, tp.deg, s));
         HIP_TRY(launch_gate(packed, x, tp.nbr, tp.deg, n_nodes, tp.e_w, s));
     }
+    const Graph g{tp.nbr, tp.deg, tp.e_w, lig_flag, gen_flag, n_nodes};
+    const NodeBufs b{w.P, w.set[0].qs, w.Qt};
     for (int l = 0; l < num_layers; ++l)
-        HIP_TRY(launch_attention(false, packed + GATE_SIZE + (size_t)l * ATT_SIZE, tp.xs + (size_t)l * nx, h, tp.nbr, tp.deg,
-                                 lig_flag, gen_flag, tp.e_w, n_nodes, w.P, w.Qt, w.set[0].qs, tp.xs + (size_t)(l + 1) * nx, nullptr,
-                                 w.act.rows, w.act.count, src.rows, src.count, s));
+        HIP_TRY(launch_attention(false, packed + GATE_SIZE + (size_t)l * ATT_SIZE, g, tp.xs + (size_t)l * nx, h, b,
+                                 tp.xs + (size_t)(l + 1) * nx, nullptr, w.act, src, s));
     HIP_TRY(hipMemcpyAsync(x_out, tp.xs + (size_t)num_layers * nx, nx * 4, hipMemcpyDeviceToDevice, s));
     return CBGX_OK;
 }
@@ -923,7 +920,7 @@ int cbgx_h2x_stack_backward_ex(const float* packed, int num_layers, const void* 
     int cur = 0;
     HIP_TRY(hipMemcpyAsync(w.gx[cur], grad_x_out, nx * 4, hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemsetAsync(w.de_w, 0, (size_t)n * KNN * 4, s));
-    HIP_TRY(launch_build_active(gen_flag, n, w.act.rows, w.act.count, s));
+    HIP_TRY(launch_build_active(gen_flag, n, w.act, s));
     // Round 6, as the denoiser's layer loop: the projection gradient of an h2x block is non-zero on gen | nbr(gen) only (this stack's
     // own graph), so its fill and every dense product over it walk that list; the weight-gradient kernels of a block run on the caller's
     // auxiliary stream on alternating buffer sets, one query-LayerNorm accumulator slot per block (CBGX_TRAIN_OVERLAP=0: one stream)
@@ -932,7 +929,7 @@ int cbgx_h2x_stack_backward_ex(const float* packed, int num_layers, const void* 
         HIP_TRY(launch_mark_seed(gen_flag, gen_flag, n, w.mask, s));
         HIP_TRY(walk_receptive_field(w.mask, w.act, tp.nbr, tp.deg, n, {w.A1}, s));
     }
-    const NodeList every{nullptr, nullptr};
+    const Graph g{tp.nbr, tp.deg, tp.e_w, lig_flag, gen_flag, n};
     const bool qln_slots = num_layers <= QLN_SLOTS;
     if (qln_slots) HIP_TRY(hipMemsetAsync(w.qln, 0, (size_t)num_layers * 2 * H * sizeof(float), s));
     BlockOverlap ov{(lists && env_on("CBGX_TRAIN_OVERLAP") && !profile_is_on() && qln_slots) ? aux_for(s) : nullptr, 0, {false, false}};
@@ -941,8 +938,8 @@ int cbgx_h2x_stack_backward_ex(const float* packed, int num_layers, const void* 
         // x_out = x + gen * delta: the identity part of the coordinate gradient is the block's `dx_init`
         BlockArgs a;
         a.att = packed + GATE_SIZE + (size_t)l * ATT_SIZE; a.x = tp.xs + (size_t)l * nx; a.h_in = h; a.g_out = w.gx[cur];
-        a.nbr = tp.nbr; a.deg = tp.deg; a.lig = lig_flag; a.e_w = tp.e_w; a.n = n;
-        a.rows = w.act; a.dp_rows = lists ? w.A1 : every;
+        a.g = g;
+        a.rows = w.act; a.dp_rows = lists ? RowList(w.A1) : RowList();
         a.gh = w.gh; a.dx = w.gx[nxt]; a.dx_init = w.gx[cur]; a.de_w = w.de_w; a.grads = grads + 6 + 18 * l;
         a.qln = qln_slots ? w.qln + (size_t)l * 2 * H : nullptr; a.ov = &ov;
         RC_TRY(attention_block_backward(a, w, s));
@@ -953,7 +950,7 @@ int cbgx_h2x_stack_backward_ex(const float* packed, int num_layers, const void* 
     // exactly zero, as in the denoiser's backward), then the gate's distance path, which lives on the movable rows' edges only
     if (grad_x_in) HIP_TRY(hipMemcpyAsync(grad_x_in, w.gx[cur], nx * 4, hipMemcpyDeviceToDevice, s));
     // (the stack's blocks add to de_w on the movable rows only: the gate backward walks that list -- 16.5 k rows -> ~900)
-    RC_TRY(gate_backward(packed, tp.xs, tp.nbr, tp.deg, n, w, grads, s, lists ? w.act : every, grad_x_in));
+    RC_TRY(gate_backward(packed, tp.xs, tp.nbr, tp.deg, n, w, grads, s, lists ? RowList(w.act) : RowList(), grad_x_in));
     if (ov.aux)
         for (int k = 0; k < 2; ++k)
             if (ov.used[k]) HIP_TRY(hipStreamWaitEvent(s, ov.aux->done[k], 0));
@@ -1288,7 +1285,7 @@ int cbgx_debug_gate_backward(const float* packed, const float* x, const int32_t*
     RC_TRY(carve_train_checked("debug_gate_backward", workspace, workspace_bytes, n_nodes, w));
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemcpyAsync(w.de_w, de_w, (size_t)n_nodes * KNN * 4, hipMemcpyDeviceToDevice, s));
-    return gate_backward(packed, x, nbr, deg, n_nodes, w, grads, s, NodeList{(int*)rows, (int*)n_rows}, grad_x);
+    return gate_backward(packed, x, nbr, deg, n_nodes, w, grads, s, RowList{rows, n_rows}, grad_x);
 }
 #endif
 

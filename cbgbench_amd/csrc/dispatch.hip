@@ -41,20 +41,20 @@ hipError_t launch_gate(const float* packed, const float* x, const int32_t* nbr, 
 }
 
 // node projection + query fold + fused edge kernel of one attention block
-hipError_t launch_attention(bool x2h, const float* att, const float* x, const float* h, const int32_t* nbr,
-                            const int32_t* deg, const uint8_t* lig, const uint8_t* gen, const float* e_w, int n_nodes,
-                            float* P, float* Qt, float* qbuf, float* out, float* dx_out, const int* act, const int* act_count,
-                            const int* src, const int* src_count, hipStream_t s, bool h2x_lig) {
-    if (n_nodes == 0) return hipSuccess;
+hipError_t launch_attention(bool x2h, const float* att, const Graph& g, const float* x, const float* h, const NodeBufs& b, float* out,
+                            float* dx_out, RowList dst, RowList src, hipStream_t s, bool h2x_lig) {
+    if (g.n_nodes == 0) return hipSuccess;
 #ifdef CBGX_XCHECK
-    if (g_edge_impl == 1) return launch_attention_v1(x2h, att, x, h, nbr, deg, lig, gen, e_w, n_nodes, P, Qt, out, dx_out, s);
+    if (g_edge_impl == 1) return launch_attention_v1(x2h, att, g, x, h, b, out, dx_out, s);
 #endif
-    h2x_lig = h2x_lig && !x2h && act != nullptr;
-    hipError_t e0 = launch_node_mfma(att, h, lig, n_nodes, P, qbuf, Qt, act, act_count, src, src_count, s, x2h, nullptr, nullptr, false,
-                                     h2x_lig);
+    h2x_lig = h2x_lig && !x2h && dst.rows != nullptr;
+    NodeStageOpts o;
+    o.large_lists = x2h;      // (x2h blocks list a sizeable part of the nodes, h2x blocks the few movable atoms)
+    o.no_fold = h2x_lig;
+    hipError_t e0 = launch_node_mfma(att, h, g.lig, g.n_nodes, b, dst, src, s, o);
     if (e0 != hipSuccess) return e0;
-    if (h2x_lig) return launch_edge_h2x_lig(att, x, h, P, qbuf, nbr, deg, lig, gen, e_w, n_nodes, out, dx_out, act, act_count, s);
-    return launch_edge_mfma(x2h, att, x, h, P, Qt, nbr, deg, lig, gen, e_w, n_nodes, out, dx_out, act, act_count, s);
+    if (h2x_lig) return launch_edge_h2x_lig(att, g, x, h, b, out, dx_out, dst, s);
+    return launch_edge_mfma(x2h, att, g, x, h, b, out, dx_out, dst, s);
 }
 
 // ---- strided / transposed copies of cbgx_pack_weights ---------------------------------------------------------------

@@ -52,6 +52,18 @@ __host__ __device__ __forceinline__ int edge_active_waves(int n_items, int n_wg,
     const int lo = EDGE_MIN_WAVES < waves ? EDGE_MIN_WAVES : waves;
     return per_wg < lo ? lo : (per_wg > waves ? waves : per_wg);
 }
+// (launchers) the edge kernels address P with 32-bit byte offsets
+static inline bool edge_offsets_fit(int n_nodes) { return (size_t)n_nodes * PROW * sizeof(float) < (1ull << 32); }
+// (launchers) persistent grid of a one-role edge launch: sized for EDGE_MIN_WAVES nodes per workgroup -- a short list spreads over more
+// CUs with one wave per SIMD (edge_active_waves) -- at most one workgroup per CU (LDS-limited) or `wg_limit` (>= 8: the caller keeps
+// CUs free for another stream), and a multiple of 8 from 64 on -> XCD-aware node partition
+static inline int edge_persistent_grid(int n_nodes, int wg_limit = 0) {
+    int grid = (n_nodes + EDGE_MIN_WAVES - 1) / EDGE_MIN_WAVES;
+    if (grid > 256) grid = 256;
+    if (wg_limit >= 8 && grid > wg_limit) grid = wg_limit;
+    if (grid >= 64) grid &= ~7;
+    return grid;
+}
 
 // ---- edge-major path for one half (16 edges): pre-activation -> LayerNorm -> ReLU -> contraction with a
 // per-lane row of B (Qt[i][a] for scores: registers `pre`; Wbv[a] for the h2x values: LDS `lds_brow`, already lane-offset).  Returns the 16x16 result tile:

@@ -86,20 +86,17 @@ bool h2x_fold_enabled() {
     return on;
 }
 
-// the launch of launch_edge_mfma(false, ...) on a work list, with `qbuf` = q[N,128] in place of Qt
-hipError_t launch_edge_h2x_lig(const float* att, const float* x, const float* h, const float* P, const float* qbuf,
-                               const int32_t* nbr, const int32_t* deg, const uint8_t* lig, const uint8_t* gen, const float* e_w,
-                               int n_nodes, float* out, float* dx_out, const int* act, const int* act_count, hipStream_t s) {
-    if (n_nodes == 0) return hipSuccess;
-    if (!act || !act_count) return hipErrorInvalidValue;                                       // a work-list kernel
-    if ((size_t)n_nodes * PROW * sizeof(float) >= (1ull << 32)) return hipErrorInvalidValue;   // 32-bit byte offsets into P
+// the launch of launch_edge_mfma(false, ...) on a work list, with b.q = q[N,128] in place of Qt
+hipError_t launch_edge_h2x_lig(const float* att, const Graph& g, const float* x, const float* h, const NodeBufs& b, float* out,
+                               float* dx_out, RowList dst, hipStream_t s) {
+    if (g.n_nodes == 0) return hipSuccess;
+    if (!dst.rows || !dst.count) return hipErrorInvalidValue;       // a work-list kernel
+    if (!edge_offsets_fit(g.n_nodes)) return hipErrorInvalidValue;
     constexpr int W = 8;
-    int grid = (n_nodes + EDGE_MIN_WAVES - 1) / EDGE_MIN_WAVES;      // as launch_edge_mfma
-    if (grid > 256) grid = 256;
-    if (grid >= 64) grid &= ~7;
+    const int grid = edge_persistent_grid(g.n_nodes);
     profile_mark_begin(K_EDGE_H2X, s);
-    hipLaunchKernelGGL((edge_h2x_lig_kernel<W, true>), dim3(grid), dim3(W * 64), 0, s, att, x, h, P, qbuf, nbr, deg, lig, gen, e_w,
-                       n_nodes, out, dx_out, act, act_count);
+    hipLaunchKernelGGL((edge_h2x_lig_kernel<W, true>), dim3(grid), dim3(W * 64), 0, s, att, x, h, b.P, b.q, g.nbr, g.deg, g.lig, g.gen,
+                       g.e_w, g.n_nodes, out, dx_out, dst.rows, dst.count);
     profile_mark_end(s);
     return hipGetLastError();
 }

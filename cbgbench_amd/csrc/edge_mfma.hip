@@ -272,27 +272,20 @@ hipError_t launch_pack_stage2(const PackBlocks& pb, hipStream_t s) {
 static std::atomic<int> g_edge_wg_limit{0};
 int set_edge_workgroup_limit(int n) { return g_edge_wg_limit.exchange(n < 0 ? 0 : n, std::memory_order_relaxed); }
 
-hipError_t launch_edge_mfma(bool x2h, const float* att, const float* x, const float* h, const float* P,
-                            const float* Qt, const int32_t* nbr, const int32_t* deg, const uint8_t* lig,
-                            const uint8_t* gen, const float* e_w, int n_nodes, float* out, float* dx_out,
-                            const int* act, const int* act_count, hipStream_t s) {
-    if (n_nodes == 0) return hipSuccess;
-    if ((size_t)n_nodes * PROW * sizeof(float) >= (1ull << 32)) return hipErrorInvalidValue;   // 32-bit byte offsets into P
+hipError_t launch_edge_mfma(bool x2h, const float* att, const Graph& g, const float* x, const float* h, const NodeBufs& b, float* out,
+                            float* dx_out, RowList dst, hipStream_t s) {
+    if (g.n_nodes == 0) return hipSuccess;
+    if (!edge_offsets_fit(g.n_nodes)) return hipErrorInvalidValue;
     constexpr int W = 8;                        // waves per persistent workgroup: 2 per SIMD at <= 256 VGPRs per lane
-    // sized for EDGE_MIN_WAVES nodes per workgroup: a short list spreads over more CUs with one wave per SIMD (edge_active_waves)
-    int grid = (n_nodes + EDGE_MIN_WAVES - 1) / EDGE_MIN_WAVES;
-    if (grid > 256) grid = 256;                 // persistent: one workgroup per CU (LDS-limited)
-    const int wg_limit = g_edge_wg_limit.load(std::memory_order_relaxed);
-    if (x2h && wg_limit >= 8 && grid > wg_limit) grid = wg_limit;   // the caller keeps CUs free for another stream
-    if (grid >= 64) grid &= ~7;                 // multiple of 8 -> XCD-aware node partition
-    profile_mark_begin(x2h ? (act ? K_EDGE_X2H_LISTED : K_EDGE_X2H) : K_EDGE_H2X, s);
-#define CBGX_LAUNCH_EDGE(X2H_, L_)                                                                                  \
-    hipLaunchKernelGGL((edge_mfma_kernel<X2H_, W, L_>), dim3(grid), dim3(W * 64), 0, s, att, x, h, P, Qt, nbr, deg, \
-                       lig, gen, e_w, n_nodes, out, dx_out, act, act_count)
+    const int grid = edge_persistent_grid(g.n_nodes, x2h ? g_edge_wg_limit.load(std::memory_order_relaxed) : 0);
+    profile_mark_begin(x2h ? (dst.rows ? K_EDGE_X2H_LISTED : K_EDGE_X2H) : K_EDGE_H2X, s);
+#define CBGX_LAUNCH_EDGE(X2H_, L_)                                                                                          \
+    hipLaunchKernelGGL((edge_mfma_kernel<X2H_, W, L_>), dim3(grid), dim3(W * 64), 0, s, att, x, h, b.P, b.Qt, g.nbr, g.deg, \
+                       g.lig, g.gen, g.e_w, g.n_nodes, out, dx_out, dst.rows, dst.count)
     if (x2h) {
-        if (act) CBGX_LAUNCH_EDGE(true, true); else CBGX_LAUNCH_EDGE(true, false);
+        if (dst.rows) CBGX_LAUNCH_EDGE(true, true); else CBGX_LAUNCH_EDGE(true, false);
     } else {
-        if (act) CBGX_LAUNCH_EDGE(false, true); else CBGX_LAUNCH_EDGE(false, false);
+        if (dst.rows) CBGX_LAUNCH_EDGE(false, true); else CBGX_LAUNCH_EDGE(false, false);
     }
 #undef CBGX_LAUNCH_EDGE
     profile_mark_end(s);
@@ -301,14 +294,12 @@ hipError_t launch_edge_mfma(bool x2h, const float* att, const float* x, const fl
 
 // x2h edge stage over the (protein-only, general) list pair of a layer: one launch of edge_x2h_dual_kernel.  `full_layer`: the two
 // lists together are all N nodes (profile class of the dominant kernel) -- otherwise a cached / pruned layer.
-hipError_t launch_edge_x2h_dual(const float* att, const float* x, const float* h, const float* P, const float* Qt,
-                                const float* qbuf, const int32_t* nbr, const int32_t* deg, const uint8_t* lig,
-                                const uint8_t* gen, const float* e_w, int n_nodes, float* out, const int* list_pp,
-                                const int* count_pp, const int* list_gen, const int* count_gen, bool full_layer, hipStream_t s) {
-    if (n_nodes == 0) return hipSuccess;
-    if ((size_t)n_nodes * PROW * sizeof(float) >= (1ull << 32)) return hipErrorInvalidValue;   // 32-bit byte offsets into P
+hipError_t launch_edge_x2h_dual(const float* att, const Graph& g, const float* x, const float* h, const NodeBufs& b, float* out,
+                                RowList pp, RowList gen, bool full_layer, hipStream_t s) {
+    if (g.n_nodes == 0) return hipSuccess;
+    if (!edge_offsets_fit(g.n_nodes)) return hipErrorInvalidValue;
     constexpr int W = 8;
-    int grid = (n_nodes + EDGE_MIN_WAVES - 1) / EDGE_MIN_WAVES + 1;     // + 1: each role rounds its list up to whole workgroups
+    int grid = (g.n_nodes + EDGE_MIN_WAVES - 1) / EDGE_MIN_WAVES + 1;     // + 1: each role rounds its list up to whole workgroups
     if (grid > 256) grid = 256;                 // persistent: one workgroup per CU (a multiple of 8 -> XCD-aware partition per role)
     const int wg_limit = g_edge_wg_limit.load(std::memory_order_relaxed);
     if (wg_limit >= 8 && grid > wg_limit) grid = wg_limit & ~7;
@@ -317,14 +308,13 @@ hipError_t launch_edge_x2h_dual(const float* att, const float* x, const float* h
     // scores and aggregation on the f16 matrix pipe (edge_x2h_f16.hip) unless CBGX_X2H_F16=0 in the environment (read once per process)
     static const bool use_f16 = [] { const char* v = getenv("CBGX_X2H_F16"); return !(v && v[0] == '0' && v[1] == 0); }();
     if (use_f16)
-        launch_edge_x2h_f16_grid(grid, att, x, h, P, Qt, qbuf, nbr, deg, lig, gen, e_w, n_nodes, out, list_pp, count_pp, list_gen,
-                                 count_gen, full_layer, s);
+        launch_edge_x2h_f16_grid(grid, att, g, x, h, b, out, pp, gen, full_layer, s);
     else if (full_layer)
-        hipLaunchKernelGGL((edge_x2h_dual_kernel<W, true>), dim3(grid), dim3(W * 64), 0, s, att, x, h, P, Qt, qbuf, nbr, deg, lig, gen,
-                           e_w, n_nodes, out, list_pp, count_pp, list_gen, count_gen);
+        hipLaunchKernelGGL((edge_x2h_dual_kernel<W, true>), dim3(grid), dim3(W * 64), 0, s, att, x, h, b.P, b.Qt, b.q, g.nbr, g.deg,
+                           g.lig, g.gen, g.e_w, g.n_nodes, out, pp.rows, pp.count, gen.rows, gen.count);
     else
-        hipLaunchKernelGGL((edge_x2h_dual_kernel<W, false>), dim3(grid), dim3(W * 64), 0, s, att, x, h, P, Qt, qbuf, nbr, deg, lig, gen,
-                           e_w, n_nodes, out, list_pp, count_pp, list_gen, count_gen);
+        hipLaunchKernelGGL((edge_x2h_dual_kernel<W, false>), dim3(grid), dim3(W * 64), 0, s, att, x, h, b.P, b.Qt, b.q, g.nbr, g.deg,
+                           g.lig, g.gen, g.e_w, g.n_nodes, out, pp.rows, pp.count, gen.rows, gen.count);
     profile_mark_end(s);
     return hipGetLastError();
 }

@@ -50,17 +50,15 @@ __global__ __launch_bounds__(WAVES * 64) void edge_x2h_f16_kernel(
 }
 
 // the launch itself; grid, profile marks and argument checks are launch_edge_x2h_dual's (edge_mfma.hip)
-void launch_edge_x2h_f16_grid(int grid, const float* att, const float* x, const float* h, const float* P, const float* Qt,
-                              const float* qbuf, const int32_t* nbr, const int32_t* deg, const uint8_t* lig, const uint8_t* gen,
-                              const float* e_w, int n_nodes, float* out, const int* list_pp, const int* count_pp,
-                              const int* list_gen, const int* count_gen, bool full_layer, hipStream_t s) {
+void launch_edge_x2h_f16_grid(int grid, const float* att, const Graph& g, const float* x, const float* h, const NodeBufs& b,
+                              float* out, RowList pp, RowList gen, bool full_layer, hipStream_t s) {
     constexpr int W = 8;
     if (full_layer)
-        hipLaunchKernelGGL((edge_x2h_f16_kernel<W, true>), dim3(grid), dim3(W * 64), 0, s, att, x, h, P, Qt, qbuf, nbr, deg, lig, gen,
-                           e_w, n_nodes, out, list_pp, count_pp, list_gen, count_gen);
+        hipLaunchKernelGGL((edge_x2h_f16_kernel<W, true>), dim3(grid), dim3(W * 64), 0, s, att, x, h, b.P, b.Qt, b.q, g.nbr, g.deg,
+                           g.lig, g.gen, g.e_w, g.n_nodes, out, pp.rows, pp.count, gen.rows, gen.count);
     else
-        hipLaunchKernelGGL((edge_x2h_f16_kernel<W, false>), dim3(grid), dim3(W * 64), 0, s, att, x, h, P, Qt, qbuf, nbr, deg, lig, gen,
-                           e_w, n_nodes, out, list_pp, count_pp, list_gen, count_gen);
+        hipLaunchKernelGGL((edge_x2h_f16_kernel<W, false>), dim3(grid), dim3(W * 64), 0, s, att, x, h, b.P, b.Qt, b.q, g.nbr, g.deg,
+                           g.lig, g.gen, g.e_w, g.n_nodes, out, pp.rows, pp.count, gen.rows, gen.count);
 }
 
 }  // namespace cbgx

@@ -555,13 +555,13 @@ __global__ __launch_bounds__(256, GATE_WAVES_PER_EU) void knn_merge_gate_kernel(
 
 hipError_t launch_knn_merge_gate(const float* packed, const float* x, const int32_t* graph_ptr, int n_graphs, int n_nodes,
                                  const uint8_t* lig, const int32_t* s_nbr, const int32_t* s_deg, const float* s_ew, int32_t* nbr,
-                                 int32_t* deg, float* e_w, hipStream_t s, const int* rows, const int* n_rows) {
+                                 int32_t* deg, float* e_w, hipStream_t s, RowList rows) {
     if (n_nodes == 0) return hipSuccess;
     int grid = (n_nodes + 3) / 4;
     if (grid > 2048) grid = 2048;
     profile_mark_begin(K_KNN, s);
     hipLaunchKernelGGL(knn_merge_gate_kernel, dim3(grid), dim3(256), 0, s, packed, x, graph_ptr, n_graphs, lig, s_nbr, s_deg, s_ew,
-                       nbr, deg, e_w, rows, n_rows);
+                       nbr, deg, e_w, rows.rows, rows.count);
     profile_mark_end(s);
     return hipGetLastError();
 }
@@ -696,33 +696,33 @@ hipError_t launch_graph_cache_begin(const float* x, const int32_t* graph_ptr, in
 }
 
 hipError_t launch_knn_reg(const float* x, const int32_t* graph_ptr, int n_graphs, int n_nodes, int32_t* nbr,
-                          int32_t* deg, hipStream_t s, const int* rows, const int* n_rows) {
+                          int32_t* deg, hipStream_t s, RowList rows) {
     if (n_nodes == 0) return hipSuccess;
     profile_mark_begin(K_KNN, s);
     hipLaunchKernelGGL(knn_graph_reg_kernel, dim3((n_nodes + 3) / 4), dim3(256), 0, s, x, graph_ptr, n_graphs, n_nodes,
-                       nbr, deg, rows, n_rows);
+                       nbr, deg, rows.rows, rows.count);
     profile_mark_end(s);
     return hipGetLastError();
 }
 
 hipError_t launch_knn_merge(const float* x, const int32_t* graph_ptr, int n_graphs, int n_nodes, const uint8_t* lig,
-                            const int32_t* s_nbr, const int32_t* s_deg, int32_t* nbr, int32_t* deg, hipStream_t s, const int* rows,
-                            const int* n_rows, const float* s_ew, float* e_w, unsigned* newmask) {
+                            const int32_t* s_nbr, const int32_t* s_deg, int32_t* nbr, int32_t* deg, hipStream_t s, RowList rows,
+                            const float* s_ew, float* e_w, unsigned* newmask) {
     if (n_nodes == 0) return hipSuccess;
     profile_mark_begin(K_KNN, s);
     hipLaunchKernelGGL(knn_merge_kernel, dim3((n_nodes + 3) / 4), dim3(256), 0, s, x, graph_ptr, n_graphs, lig, s_nbr, s_deg, nbr,
-                       deg, rows, n_rows, s_ew, e_w, newmask);
+                       deg, rows.rows, rows.count, s_ew, e_w, newmask);
     profile_mark_end(s);
     return hipGetLastError();
 }
 
 hipError_t launch_gate_mfma(const float* packed, const float* x, const int32_t* nbr, const int32_t* deg, int n_nodes,
-                            float* e_w, hipStream_t s, const int* rows, const int* n_rows, const unsigned* newmask) {
+                            float* e_w, hipStream_t s, RowList rows, const unsigned* newmask) {
     if (n_nodes == 0) return hipSuccess;
     int grid = (n_nodes + 3) / 4;
     if (grid > 2048) grid = 2048;
     profile_mark_begin(K_GATE, s);
-    hipLaunchKernelGGL(edge_gate_mfma_kernel, dim3(grid), dim3(256), 0, s, packed, x, nbr, deg, n_nodes, e_w, rows, n_rows, newmask);
+    hipLaunchKernelGGL(edge_gate_mfma_kernel, dim3(grid), dim3(256), 0, s, packed, x, nbr, deg, n_nodes, e_w, rows.rows, rows.count, newmask);
     profile_mark_end(s);
     return hipGetLastError();
 }

@@ -14,7 +14,30 @@ struct AuxStream {
     hipEvent_t fork = nullptr, join = nullptr, done[2] = {nullptr, nullptr};
 };
 AuxStream* aux_for(hipStream_t caller);
-typedef AuxStream AuxLane;
+
+// ---- what the launchers below take instead of loose pointers ----
+// a node list built on the device: row ids (any order) and the address of their number
+struct NodeList {
+    int* rows;
+    int* count;
+};
+// the read-only view of one that a launcher takes; {nullptr, nullptr} (the default): every row
+struct RowList {
+    const int* rows = nullptr;
+    const int* count = nullptr;
+    RowList() = default;
+    RowList(const int* r, const int* c) : rows(r), count(c) {}
+    RowList(NodeList l) : rows(l.rows), count(l.count) {}
+};
+// of one attention block's node stage: projection, query, folded query
+struct NodeBufs { float *P, *q, *Qt; };
+// the graph an attention block runs on, built once per call (`gen` may be NULL where no block of the call moves coordinates)
+struct Graph {
+    const int32_t *nbr, *deg;
+    const float* e_w;
+    const uint8_t *lig, *gen;
+    int n_nodes;
+};
 
 // ---- optional per-kernel timing (cbgx_profile_begin / cbgx_profile_end) ----
 enum KernelClass { K_KNN = 0, K_GATE, K_NODE_GEMM, K_NODE_QUERY, K_EDGE_X2H, K_EDGE_H2X, K_EDGE_X2H_LISTED, K_EDGE_X2H_BWD, K_EDGE_H2X_BWD,
@@ -28,14 +51,12 @@ hipError_t launch_knn(const float* x, const int32_t* graph_ptr, int n_graphs, in
 hipError_t launch_gate(const float* packed, const float* x, const int32_t* nbr, const int32_t* deg, int n_nodes,
                        float* e_w, hipStream_t s);
 hipError_t launch_node_gemm(const float* A, int lda, const float* Wt, const float* bias, float* C, int ldc, int M,
-                            int nout, int act, hipStream_t s, const int* rows = nullptr, const int* n_rows = nullptr);
-// node projection + query fold + fused edge kernel of one attention block.
+                            int nout, int act, hipStream_t s, RowList rows = {});
+// node projection + query fold + fused edge kernel of one attention block on the destination rows `dst`, whose sources are in `src`.
 // x2h: out = h_out[N,128]; h2x: out = x_out[N,3], dx_out optional.
 // h2x_lig (h2x on a work list of ligand atoms, h2x_lig_selected): no fold in the node stage, edge_h2x_lig_kernel folds in registers
-hipError_t launch_attention(bool x2h, const float* att, const float* x, const float* h, const int32_t* nbr,
-                            const int32_t* deg, const uint8_t* lig, const uint8_t* gen, const float* e_w, int n_nodes,
-                            float* P, float* Qt, float* qbuf, float* out, float* dx_out, const int* act, const int* act_count,
-                            const int* src, const int* src_count, hipStream_t s, bool h2x_lig = false);
+hipError_t launch_attention(bool x2h, const float* att, const Graph& g, const float* x, const float* h, const NodeBufs& b, float* out,
+                            float* dx_out, RowList dst, RowList src, hipStream_t s, bool h2x_lig = false);
 // which generation of kernels the stage dispatchers (dispatch.hip) use: always the MFMA one in libcbgx.so; the test-only
 // library libcbgx_xcheck.so (-DCBGX_XCHECK) can switch to the first-generation VALU kernels at run time
 #ifdef CBGX_XCHECK
@@ -44,12 +65,11 @@ hipError_t launch_knn_v1(const float* x, const int32_t* graph_ptr, int n_graphs,
                          hipStream_t s);
 hipError_t launch_gate_v1(const float* packed, const float* x, const int32_t* nbr, const int32_t* deg, int n_nodes,
                           float* e_w, hipStream_t s);
-hipError_t launch_node_gemm_v1(const float* A, int lda, const float* Wt, const float* bias, float* C, int ldc, int M,
-                               int nout, int act, hipStream_t s, const int* rows, const int* n_rows);
+hipError_t launch_node_gemm_v1(const float* A, int lda, const float* Wt, const float* bias, float* C, int ldc, int M, int nout, int act,
+                               hipStream_t s, RowList rows);
 hipError_t launch_node_query_v1(const float* att, const float* P, float* Qt, int n_nodes, hipStream_t s);
-hipError_t launch_attention_v1(bool x2h, const float* att, const float* x, const float* h, const int32_t* nbr,
-                               const int32_t* deg, const uint8_t* lig, const uint8_t* gen, const float* e_w, int n_nodes,
-                               float* P, float* Qt, float* out, float* dx_out, hipStream_t s);
+hipError_t launch_attention_v1(bool x2h, const float* att, const Graph& g, const float* x, const float* h, const NodeBufs& b,
+                               float* out, float* dx_out, hipStream_t s);
 #else
 constexpr int g_edge_impl = 0;
 #endif
@@ -83,21 +103,20 @@ hipError_t launch_pack_stage2(const PackBlocks& pb, hipStream_t s);
 hipError_t launch_pack_gate_img(const float* w1, const float* b1, const float* g, const float* be, const float* w2,
                                 float* img, hipStream_t s);
 hipError_t launch_knn_reg(const float* x, const int32_t* graph_ptr, int n_graphs, int n_nodes, int32_t* nbr,
-                          int32_t* deg, hipStream_t s, const int* rows = nullptr, const int* n_rows = nullptr);
+                          int32_t* deg, hipStream_t s, RowList rows = {});
 // graph-cached calls: the listed centres' lists from (pocket list U the graph's ligand atoms) by rank counting (graph_mfma.hip)
 // `s_ew` / `e_w` / `newmask` (optional): kept pocket entries carry their cached gate value to their new rank, newmask[i] = the ranks
 // that hold new entries -- what launch_gate_mfma(..., newmask) then evaluates instead of all 32 slots
 hipError_t launch_knn_merge(const float* x, const int32_t* graph_ptr, int n_graphs, int n_nodes, const uint8_t* lig,
-                            const int32_t* s_nbr, const int32_t* s_deg, int32_t* nbr, int32_t* deg, hipStream_t s, const int* rows,
-                            const int* n_rows, const float* s_ew = nullptr, float* e_w = nullptr, unsigned* newmask = nullptr);
+                            const int32_t* s_nbr, const int32_t* s_deg, int32_t* nbr, int32_t* deg, hipStream_t s, RowList rows,
+                            const float* s_ew = nullptr, float* e_w = nullptr, unsigned* newmask = nullptr);
 // graph-cached calls: the listed centres' merged neighbour lists and their gate values in one launch -- kept pocket entries carry
 // their cached gate value to their new rank, the gate MLP runs on the entries that are new (graph_mfma.hip, knn_merge_gate_kernel)
 hipError_t launch_knn_merge_gate(const float* packed, const float* x, const int32_t* graph_ptr, int n_graphs, int n_nodes,
                                  const uint8_t* lig, const int32_t* s_nbr, const int32_t* s_deg, const float* s_ew, int32_t* nbr,
-                                 int32_t* deg, float* e_w, hipStream_t s, const int* rows, const int* n_rows);
+                                 int32_t* deg, float* e_w, hipStream_t s, RowList rows);
 hipError_t launch_gate_mfma(const float* packed, const float* x, const int32_t* nbr, const int32_t* deg, int n_nodes,
-                            float* e_w, hipStream_t s, const int* rows = nullptr, const int* n_rows = nullptr,
-                            const unsigned* newmask = nullptr);
+                            float* e_w, hipStream_t s, RowList rows = {}, const unsigned* newmask = nullptr);
 // head of a graph-cached forward call in one launch: proximity flags -> `dirty`, their compaction -> `list` / `count` (zero on
 // entry), the pocket's graph -> nbr / deg / ew, the cached features of layers 0 / 1 -> out1 / out2 (graph_mfma.hip)
 hipError_t launch_graph_cache_begin(const float* x, const int32_t* graph_ptr, int n_graphs, const uint8_t* lig, const float* r32sq,
@@ -108,20 +127,25 @@ hipError_t launch_graph_cache_begin(const float* x, const int32_t* graph_ptr, in
 hipError_t launch_pack_node_tables(const PackBlocks& pb, hipStream_t s);     // node_mfma.hip part of stage 2
 // counter_zeroed: the caller has already set *count to zero on this stream (cbgx_unitransformer_forward zeroes all its list counters
 // with ONE memset instead of one per list: ~15 fills of 4.6 us per denoising step)
-hipError_t launch_build_active(const uint8_t* flag, int n, int* list, int* count, hipStream_t s, bool counter_zeroed = false);
+hipError_t launch_build_active(const uint8_t* flag, int n, NodeList out, hipStream_t s, bool counter_zeroed = false);
 hipError_t launch_mark_seed(const uint8_t* a, const uint8_t* b, int n, uint8_t* m, hipStream_t s);
 hipError_t launch_mark_from_nbr(const uint8_t* flag, const int32_t* nbr, const int32_t* deg, int n, uint8_t* out,
                                 hipStream_t s);
-hipError_t launch_mark_nbr(const int* list, const int* count, int n_upper, const int32_t* nbr, const int32_t* deg,
-                           uint8_t* m, hipStream_t s);
+hipError_t launch_mark_nbr(RowList rows, int n_upper, const int32_t* nbr, const int32_t* deg, uint8_t* m, hipStream_t s);
+// the node stage of one attention block: own columns, q and Qt on `dst`, PS columns on `src`.  Its options, all off by default:
 // large_lists: the destination list (when given) is expected to hold a sizeable part of the nodes (x2h blocks of the cached / pruned
 // layers) rather than the few movable atoms of an h2x block: throughput launches instead of one workgroup per column chunk
 // q_direct (inputs above NODE_STAGE_MAX_ROWS only): q comes straight from h (node_query_kernel) and the q-hidden columns of P are
 // NOT produced -- for callers whose edge stage is all that reads P (the inference forward; the training tape keeps them)
-hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig, int n_nodes, float* P, float* qbuf,
-                            float* Qt, const int* act, const int* act_count, const int* src, const int* src_count,
-                            hipStream_t s, bool large_lists = false, const int* fold = nullptr, const int* fold_count = nullptr,
-                            bool q_direct = false, bool no_fold = false);
+// fold (a list): Qt is produced for these rows instead of for all of `dst`;  no_fold: the stage ends with the query MLP (h2x_lig)
+struct NodeStageOpts {
+    bool large_lists = false;
+    RowList fold;
+    bool q_direct = false;
+    bool no_fold = false;
+};
+hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig, int n_nodes, const NodeBufs& b, RowList dst,
+                            RowList src, hipStream_t s, const NodeStageOpts& o = {});
 // CBGX_NODE_QDIRECT=0 in the environment: the inference forward keeps the projection -> query MLP chain (A/B runs, bit-identity tests)
 bool node_qdirect_enabled();
 // the fused node stage (node_stage_kernel, inputs of <= NODE_STAGE_MAX_ROWS rows) as a list of jobs on the same input features:
@@ -143,10 +167,9 @@ constexpr int NS_JOBS_MAX = 4;
 struct NodeStageJobs { NodeStageJob j[NS_JOBS_MAX]; int n; };
 constexpr int NODE_STAGE_MAX_ROWS = 8192;   // up to here the latency-built fused kernel replaces the three-kernel chain
 // the jobs of one attention block's node stage appended to `jobs` (same selection as launch_node_mfma's fused path): with a
-// destination list two jobs (own columns on `act`, PS columns on `src` -- all rows when src is NULL), without one job on all rows
-bool add_node_stage_jobs(NodeStageJobs& jobs, const float* att, float* P, float* qbuf, float* Qt, const int* act,
-                         const int* act_count, const int* src, const int* src_count, const uint8_t* fold_flag = nullptr,
-                         bool no_fold = false);
+// destination list two jobs (own columns on `dst`, PS columns on `src` -- all rows when src is NULL), without one job on all rows
+bool add_node_stage_jobs(NodeStageJobs& jobs, const float* att, const NodeBufs& b, RowList dst, RowList src,
+                         const uint8_t* fold_flag = nullptr, bool no_fold = false);
 hipError_t launch_node_stage_jobs(const NodeStageJobs& jobs, const float* h, const uint8_t* lig, int n_nodes, hipStream_t s);
 // all node lists of a forward call in four launches (node_mfma.hip): three level kernels over flags + one multi-job compaction
 struct GraphFlags {
@@ -183,30 +206,23 @@ hipError_t launch_graph_lists(const uint8_t* gen, const uint8_t* lig, const uint
                               const int32_t* graph_ptr, int n_graphs, const GraphListJobs& jobs, bool cached, bool prune,
                               uint8_t* d1_out, hipStream_t s);
 hipError_t launch_build_lists(const ListJobs& jobs, int n, hipStream_t s);
-hipError_t launch_split_list(const int* list, const int* count, int n, const uint8_t* flag, int* out1, int* cnt1, int* out0,
-                             int* cnt0, hipStream_t s, bool counters_zeroed = false);
+hipError_t launch_split_list(RowList in, int n, const uint8_t* flag, NodeList out1, NodeList out0, hipStream_t s,
+                             bool counters_zeroed = false);
 // MFMA edge kernel (edge_mfma.hip)
 int set_edge_workgroup_limit(int n);
-hipError_t launch_edge_mfma(bool x2h, const float* att, const float* x, const float* h, const float* P,
-                            const float* Qt, const int32_t* nbr, const int32_t* deg, const uint8_t* lig,
-                            const uint8_t* gen, const float* e_w, int n_nodes, float* out, float* dx_out,
-                            const int* act, const int* act_count, hipStream_t s);
-hipError_t launch_edge_x2h_dual(const float* att, const float* x, const float* h, const float* P, const float* Qt,
-                                const float* qbuf, const int32_t* nbr, const int32_t* deg, const uint8_t* lig,
-                                const uint8_t* gen, const float* e_w, int n_nodes, float* out, const int* list_pp,
-                                const int* count_pp, const int* list_gen, const int* count_gen, bool full_layer, hipStream_t s);
-// edge_h2x_lig.hip: the h2x edge kernel for work lists of ligand atoms (query folded in registers from `qbuf` = q[N,128]), the pack
+hipError_t launch_edge_mfma(bool x2h, const float* att, const Graph& g, const float* x, const float* h, const NodeBufs& b, float* out,
+                            float* dx_out, RowList dst, hipStream_t s);
+hipError_t launch_edge_x2h_dual(const float* att, const Graph& g, const float* x, const float* h, const NodeBufs& b, float* out,
+                                RowList pp, RowList gen, bool full_layer, hipStream_t s);
+// edge_h2x_lig.hip: the h2x edge kernel for work lists of ligand atoms (query folded in registers from b.q = q[N,128]), the pack
 // kernel of its LDS image (part of stage 2), and CBGX_H2X_FOLD (default on)
-hipError_t launch_edge_h2x_lig(const float* att, const float* x, const float* h, const float* P, const float* qbuf,
-                               const int32_t* nbr, const int32_t* deg, const uint8_t* lig, const uint8_t* gen, const float* e_w,
-                               int n_nodes, float* out, float* dx_out, const int* act, const int* act_count, hipStream_t s);
+hipError_t launch_edge_h2x_lig(const float* att, const Graph& g, const float* x, const float* h, const NodeBufs& b, float* out,
+                               float* dx_out, RowList dst, hipStream_t s);
 hipError_t launch_pack_h2l_image(const PackBlocks& pb, hipStream_t s);
 bool h2x_fold_enabled();
 // edge_x2h_f16.hip: the same launch with scores and aggregation in split-f16 (called by launch_edge_x2h_dual, which owns the grid)
-void launch_edge_x2h_f16_grid(int grid, const float* att, const float* x, const float* h, const float* P, const float* Qt,
-                              const float* qbuf, const int32_t* nbr, const int32_t* deg, const uint8_t* lig, const uint8_t* gen,
-                              const float* e_w, int n_nodes, float* out, const int* list_pp, const int* count_pp,
-                              const int* list_gen, const int* count_gen, bool full_layer, hipStream_t s);
+void launch_edge_x2h_f16_grid(int grid, const float* att, const Graph& g, const float* x, const float* h, const NodeBufs& b,
+                              float* out, RowList pp, RowList gen, bool full_layer, hipStream_t s);
 // TargetDiff step prologue / epilogue (step.hip)
 hipError_t launch_step_prologue(const float* x_lig, const float* c_lig, const int32_t* lig_rows, int n_lig, int C,
                                 const float* emb_w, const float* emb_b, const float* ind_w, const float* ind_b, float* x,

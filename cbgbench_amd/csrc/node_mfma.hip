@@ -1013,7 +1013,7 @@ __global__ __launch_bounds__(256) void node_linear_kernel(const float* __restric
 }
 
 hipError_t launch_node_gemm(const float* A, int lda, const float* Wt, const float* bias, float* C, int ldc, int M,
-                            int nout, int act, hipStream_t s, const int* rows, const int* n_rows) {
+                            int nout, int act, hipStream_t s, RowList rows) {
     if (M == 0) return hipSuccess;
     if (nout < 1 || nout > H) return hipErrorInvalidValue;
     const int tiles = (M + 63) / 64;
@@ -1021,9 +1021,9 @@ hipError_t launch_node_gemm(const float* A, int lda, const float* Wt, const floa
     const dim3 grid(tiles < 512 ? tiles : 512, tiles <= 128 ? (nout + 15) / 16 : 1), block(256);
     profile_mark_begin(K_NODE_GEMM, s);
     if (act == 0)
-        hipLaunchKernelGGL(node_linear_kernel<0>, grid, block, 0, s, A, lda, Wt, bias, C, ldc, M, nout, rows, n_rows);
+        hipLaunchKernelGGL(node_linear_kernel<0>, grid, block, 0, s, A, lda, Wt, bias, C, ldc, M, nout, rows.rows, rows.count);
     else
-        hipLaunchKernelGGL(node_linear_kernel<1>, grid, block, 0, s, A, lda, Wt, bias, C, ldc, M, nout, rows, n_rows);
+        hipLaunchKernelGGL(node_linear_kernel<1>, grid, block, 0, s, A, lda, Wt, bias, C, ldc, M, nout, rows.rows, rows.count);
     profile_mark_end(s);
     return hipGetLastError();
 }
@@ -1202,15 +1202,14 @@ __global__ __launch_bounds__(BA_THREADS) void split_list_kernel(const int* __res
     else if (valid) out0[s_base[0] + s_cnt[0][wave] + __popcll(m0 & below)] = node;
 }
 
-hipError_t launch_split_list(const int* list, const int* count, int n, const uint8_t* flag, int* out1, int* cnt1, int* out0,
-                             int* cnt0, hipStream_t s, bool counters_zeroed) {
-    if (!counters_zeroed) {   // the two counters live in one 128-byte region (cnt1 first): one memset
-        hipError_t e = hipMemsetAsync(cnt1, 0, (size_t)((char*)cnt0 - (char*)cnt1) + sizeof(int), s);
+hipError_t launch_split_list(RowList in, int n, const uint8_t* flag, NodeList out1, NodeList out0, hipStream_t s, bool counters_zeroed) {
+    if (!counters_zeroed) {   // the two counters live in one 128-byte region (out1's first): one memset
+        hipError_t e = hipMemsetAsync(out1.count, 0, (size_t)((char*)out0.count - (char*)out1.count) + sizeof(int), s);
         if (e != hipSuccess) return e;
     }
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(split_list_kernel, dim3((n + BA_THREADS - 1) / BA_THREADS), dim3(BA_THREADS), 0, s, list, count, n, flag,
-                       out1, cnt1, out0, cnt0);
+    hipLaunchKernelGGL(split_list_kernel, dim3((n + BA_THREADS - 1) / BA_THREADS), dim3(BA_THREADS), 0, s, in.rows, in.count, n, flag,
+                       out1.rows, out1.count, out0.rows, out0.count);
     return hipGetLastError();
 }
 
@@ -1502,21 +1501,20 @@ hipError_t launch_mark_seed(const uint8_t* a, const uint8_t* b, int n, uint8_t* 
     return hipGetLastError();
 }
 
-hipError_t launch_mark_nbr(const int* list, const int* count, int n_upper, const int32_t* nbr, const int32_t* deg,
-                           uint8_t* m, hipStream_t s) {
+hipError_t launch_mark_nbr(RowList rows, int n_upper, const int32_t* nbr, const int32_t* deg, uint8_t* m, hipStream_t s) {
     if (n_upper == 0) return hipSuccess;
     const long threads = (long)n_upper * 32;
-    hipLaunchKernelGGL(mark_nbr_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, list, count, nbr, deg, m);
+    hipLaunchKernelGGL(mark_nbr_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, rows.rows, rows.count, nbr, deg, m);
     return hipGetLastError();
 }
 
-hipError_t launch_build_active(const uint8_t* flag, int n, int* list, int* count, hipStream_t s, bool counter_zeroed) {
+hipError_t launch_build_active(const uint8_t* flag, int n, NodeList out, hipStream_t s, bool counter_zeroed) {
     if (!counter_zeroed) {
-        hipError_t e = hipMemsetAsync(count, 0, sizeof(int), s);
+        hipError_t e = hipMemsetAsync(out.count, 0, sizeof(int), s);
         if (e != hipSuccess) return e;
     }
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(build_active_kernel, dim3((n + BA_THREADS - 1) / BA_THREADS), dim3(BA_THREADS), 0, s, flag, n, list, count);
+    hipLaunchKernelGGL(build_active_kernel, dim3((n + BA_THREADS - 1) / BA_THREADS), dim3(BA_THREADS), 0, s, flag, n, out.rows, out.count);
     return hipGetLastError();
 }
 
@@ -1526,15 +1524,15 @@ constexpr unsigned CHUNKS_OWN = 0x30fu;   // PDk | PDv | qh: what the destinatio
 constexpr unsigned CHUNKS_QH = 0x300u;    // the q-hidden columns: read by node_qmlp_kernel (and the training backward) only
 
 // node stage of one attention block: P, q (scratch), Qt.
-// `act` / `act_count` (optional): only the listed destination nodes will be processed by the edge kernel (h2x: nodes
-// that can move; x2h in the last layers: nodes whose features can still reach an output).  `src` / `src_count`
+// `dst` (optional): only the listed destination nodes will be processed by the edge kernel (h2x: nodes
+// that can move; x2h in the last layers: nodes whose features can still reach an output).  `src`
 // (optional): the nodes that can be *sources* of those destinations; without it PS is produced for every node.
 
-bool add_node_stage_jobs(NodeStageJobs& jobs, const float* att, float* P, float* qbuf, float* Qt, const int* act,
-                         const int* act_count, const int* src, const int* src_count, const uint8_t* fold_flag, bool no_fold) {
-    if (jobs.n + (act ? 2 : 1) > NS_JOBS_MAX) return false;
-    jobs.j[jobs.n++] = NodeStageJob{att, P, qbuf, Qt, act, act_count, act ? CHUNKS_OWN : CHUNKS_ALL, 0, fold_flag, no_fold ? 1 : 0};
-    if (act) jobs.j[jobs.n++] = NodeStageJob{att, P, qbuf, Qt, src, src_count, CHUNKS_PS, 1, nullptr, 0};
+bool add_node_stage_jobs(NodeStageJobs& jobs, const float* att, const NodeBufs& b, RowList dst, RowList src, const uint8_t* fold_flag,
+                         bool no_fold) {
+    if (jobs.n + (dst.rows ? 2 : 1) > NS_JOBS_MAX) return false;
+    jobs.j[jobs.n++] = NodeStageJob{att, b.P, b.q, b.Qt, dst.rows, dst.count, dst.rows ? CHUNKS_OWN : CHUNKS_ALL, 0, fold_flag, no_fold ? 1 : 0};
+    if (dst.rows) jobs.j[jobs.n++] = NodeStageJob{att, b.P, b.q, b.Qt, src.rows, src.count, CHUNKS_PS, 1, nullptr, 0};
     return true;
 }
 
@@ -1566,17 +1564,16 @@ bool node_qdirect_enabled() {
     return on;
 }
 
-// `fold` / `fold_count` (optional, x2h blocks of the inference path): the rows whose folded query Qt the edge stage will read -- the
+// `o.fold` (optional, x2h blocks of the inference path): the rows whose folded query Qt the edge stage will read -- the
 // GENERAL list of the layer; protein-only destinations fold in registers (edge_mfma.hip) and only need q.  Without it Qt is
-// produced for every destination.  `no_fold`: Qt is not produced at all (the stage ends with q: edge_h2x_lig.hip folds in registers).
-hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig, int n_nodes, float* P, float* qbuf,
-                            float* Qt, const int* act, const int* act_count, const int* src, const int* src_count,
-                            hipStream_t s, bool large_lists, const int* fold, const int* fold_count, bool q_direct, bool no_fold) {
+// produced for every destination.  `o.no_fold`: Qt is not produced at all (the stage ends with q: edge_h2x_lig.hip folds in registers).
+hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig, int n_nodes, const NodeBufs& b, RowList dst,
+                            RowList src, hipStream_t s, const NodeStageOpts& o) {
     if (n_nodes == 0) return hipSuccess;
     const int tiles = (n_nodes + 63) / 64;
     const int grid = min(tiles, 512);
     // few row tiles (small batches, or a work list): spread the heads of the fold / the halves of the query MLP over workgroups too
-    const bool small = tiles <= 128 || (act != nullptr && !large_lists);
+    const bool small = tiles <= 128 || (dst.rows != nullptr && !o.large_lists);
     // node_proj_kernel: one workgroup per (row-tile column x, selected chunk); ALL of them resident at once -- the kernel's
     // __launch_bounds__(256, 3) give three 4-wave workgroups per CU = 768 slots (a grid of 960 ran as two rounds, the second a
     // quarter full: 100 us instead of 67) -- and gridDim.x a multiple of 8 so that the workgroups of one row tile -- linear ids
@@ -1594,26 +1591,26 @@ hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig
     // per CU, need two rounds for 313 row tiles.)
     const bool fused = n_nodes <= NODE_STAGE_MAX_ROWS;
     // q straight from h: the projection launches drop the q-hidden chunks (four chunk groups instead of five on a full layer)
-    const bool direct = q_direct && !fused;
+    const bool direct = o.q_direct && !fused;
     const unsigned chunks_all = direct ? CHUNKS_ALL & ~CHUNKS_QH : CHUNKS_ALL, chunks_own = direct ? CHUNKS_OWN & ~CHUNKS_QH : CHUNKS_OWN;
     profile_mark_begin(K_NODE_GEMM, s);
     // fused with a destination list: the source rows' PS columns are the second job of the node_stage_kernel launch below
-    const bool two_jobs = fused && act != nullptr;
-    if (!act) {
+    const bool two_jobs = fused && dst.rows != nullptr;
+    if (!dst.rows) {
         if (!fused)
-            hipLaunchKernelGGL(node_proj_kernel<false>, proj_grid(chunks_all), dim3(256), 0, s, att, h, lig, P, n_nodes,
+            hipLaunchKernelGGL(node_proj_kernel<false>, proj_grid(chunks_all), dim3(256), 0, s, att, h, lig, b.P, n_nodes,
                                (const int*)nullptr, (const int*)nullptr, chunks_all);
     } else {
         if (!two_jobs) {     // without a source list the PS columns are produced for every node
-            if (src)
-                hipLaunchKernelGGL(node_proj_kernel<true>, proj_grid(CHUNKS_PS), dim3(256), 0, s, att, h, lig, P, n_nodes, src,
-                                   src_count, CHUNKS_PS);
+            if (src.rows)
+                hipLaunchKernelGGL(node_proj_kernel<true>, proj_grid(CHUNKS_PS), dim3(256), 0, s, att, h, lig, b.P, n_nodes, src.rows,
+                                   src.count, CHUNKS_PS);
             else
-                hipLaunchKernelGGL(node_proj_kernel<false>, proj_grid(CHUNKS_PS), dim3(256), 0, s, att, h, lig, P, n_nodes,
+                hipLaunchKernelGGL(node_proj_kernel<false>, proj_grid(CHUNKS_PS), dim3(256), 0, s, att, h, lig, b.P, n_nodes,
                                    (const int*)nullptr, (const int*)nullptr, CHUNKS_PS);
         }
         if (!fused)
-            hipLaunchKernelGGL(node_proj_kernel<true>, proj_grid(chunks_own), dim3(256), 0, s, att, h, lig, P, n_nodes, act, act_count,
+            hipLaunchKernelGGL(node_proj_kernel<true>, proj_grid(chunks_own), dim3(256), 0, s, att, h, lig, b.P, n_nodes, dst.rows, dst.count,
                                chunks_own);
     }
     profile_mark_end(s);
@@ -1623,22 +1620,22 @@ hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig
     if (fused) {
         NodeStageJobs jobs;
         jobs.n = 0;
-        add_node_stage_jobs(jobs, att, P, qbuf, Qt, act, act_count, src, src_count, nullptr, no_fold);
+        add_node_stage_jobs(jobs, att, b, dst, src, nullptr, o.no_fold);
         launch_node_stage_grid(jobs, h, lig, n_nodes, s);
     } else {
         if (direct)      // persistent 8-wave workgroups, one per CU on NQK_GRID of them
             hipLaunchKernelGGL(node_query_kernel, dim3(min((n_nodes + NQK_ROWS - 1) / NQK_ROWS, NQK_GRID)), dim3(NQK_THREADS), 0, s, att, h,
-                               qbuf, n_nodes, act, act_count);
+                               b.q, n_nodes, dst.rows, dst.count);
         else
-            hipLaunchKernelGGL(node_qmlp_kernel, dim3(grid, small ? 2 : 1), dim3(256), 0, s, att, P, qbuf, n_nodes, act, act_count);
-        if (no_fold) {
+            hipLaunchKernelGGL(node_qmlp_kernel, dim3(grid, small ? 2 : 1), dim3(256), 0, s, att, b.P, b.q, n_nodes, dst.rows, dst.count);
+        if (o.no_fold) {
             // the edge kernel reads q
-        } else if (fold)    // heads spread over four workgroups per row tile: the list is a fraction of the nodes, of unknown length
-            hipLaunchKernelGGL(node_qfold_kernel<4>, dim3(grid, 4), dim3(256), 0, s, att, qbuf, Qt, n_nodes, fold, fold_count);
+        } else if (o.fold.rows)    // heads spread over four workgroups per row tile: the list is a fraction of the nodes, of unknown length
+            hipLaunchKernelGGL(node_qfold_kernel<4>, dim3(grid, 4), dim3(256), 0, s, att, b.q, b.Qt, n_nodes, o.fold.rows, o.fold.count);
         else if (small)
-            hipLaunchKernelGGL(node_qfold_kernel<4>, dim3(grid, 4), dim3(256), 0, s, att, qbuf, Qt, n_nodes, act, act_count);
+            hipLaunchKernelGGL(node_qfold_kernel<4>, dim3(grid, 4), dim3(256), 0, s, att, b.q, b.Qt, n_nodes, dst.rows, dst.count);
         else
-            hipLaunchKernelGGL(node_qfold_kernel<16>, dim3(grid, 1), dim3(256), 0, s, att, qbuf, Qt, n_nodes, act, act_count);
+            hipLaunchKernelGGL(node_qfold_kernel<16>, dim3(grid, 1), dim3(256), 0, s, att, b.q, b.Qt, n_nodes, dst.rows, dst.count);
     }
     profile_mark_end(s);
     return hipGetLastError();

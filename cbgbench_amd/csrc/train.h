@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kernels.h"
 #include "layout.h"
 
 namespace cbgx {
@@ -35,25 +36,19 @@ constexpr int GB_B2 = GB_W2 + GH;
 constexpr int GB_SIZE = GB_B2 + 4;
 
 #ifdef CBGX_XCHECK
-hipError_t launch_edge_backward(bool x2h, const float* att, const float* x, const float* P, const float* Qt,
-                                const float* Gt, const float* gb, const float* gx_out, const int32_t* nbr,
-                                const int32_t* deg, const uint8_t* lig, const float* e_w, const int* rows,
-                                const int* n_rows, int n_nodes, float* T, float* S, float* sw, float* dP, float* dx,
-                                float* de_w, float* partial, int grid, hipStream_t s);
+hipError_t launch_edge_backward(bool x2h, const float* att, const Graph& g, const float* x, const float* P, const float* Qt,
+                                const float* Gt, const float* gb, const float* gx_out, RowList rows, float* T, float* S, float* sw,
+                                float* dP, float* dx, float* de_w, float* partial, int grid, hipStream_t s);
 #endif
-hipError_t launch_edge_backward_mfma(bool x2h, const float* att, const float* x, const float* P, const float* Qt,
-                                     const float* Gt, const float* gb, const float* gx_out, const int32_t* nbr,
-                                     const int32_t* deg, const uint8_t* lig, const float* e_w, const int* rows,
-                                     const int* n_rows, int n_nodes, float* T, float* S, float* sw, float* dP, float* dx,
-                                     float* de_w, float* partial, int grid, hipStream_t s, int centred = 0);
+hipError_t launch_edge_backward_mfma(bool x2h, const float* att, const Graph& g, const float* x, const float* P, const float* Qt,
+                                     const float* Gt, const float* gb, const float* gx_out, RowList rows, float* T, float* S, float* sw,
+                                     float* dP, float* dx, float* de_w, float* partial, int grid, hipStream_t s, int centred = 0);
 // third-generation x2h backward (train_bwd_x2h.hip): one wavefront per node, 8 nodes in flight per workgroup; P must be the
 // centred projection of the MFMA node kernel.  grid = edge_grid_x2h(n) workgroups, one PB_SIZE slab each.  work_ctr: 8 ints, ZERO at
 // launch (the per-XCD counters of the last, partial round of nodes).
-hipError_t launch_edge_backward_x2h(const float* att, const float* x, const float* P, const float* Qt, const float* Gt,
-                                    const float* gb, const int32_t* nbr, const int32_t* deg, const uint8_t* lig,
-                                    const float* e_w, const int* rows, const int* n_rows, int n_nodes, float* T, float* S,
-                                    float* sw, float* dP, float* dx, float* de_w, float* partial, float* nk_scratch,
-                                    int* work_ctr, int grid, hipStream_t s, float* dE = nullptr);
+hipError_t launch_edge_backward_x2h(const float* att, const Graph& g, const float* x, const float* P, const float* Qt, const float* Gt,
+                                    const float* gb, RowList rows, float* T, float* S, float* sw, float* dP, float* dx, float* de_w,
+                                    float* partial, float* nk_scratch, int* work_ctr, int grid, hipStream_t s, float* dE = nullptr);
 // Round 6, the neighbour-row gradients without atomics (train_scatter.hip).  `dE` [N][32][256]: the edge backward (full launches)
 // stores d pre of every edge (k | v) in the edge's own row; the incoming-edge lists of every SOURCE node -- `rin_ptr` [N + 1] offsets,
 // `rin_edge` edge ids 32 i + slot in ascending order -- are built once per backward call (the graph is the same for all layers), and
@@ -62,35 +57,30 @@ hipError_t launch_edge_backward_x2h(const float* att, const float* x, const floa
 hipError_t launch_rin_build(const int32_t* nbr, const int32_t* deg, int n_nodes, int* cnt, int* ptr, int* tmp, int* edges,
                             hipStream_t s);
 hipError_t launch_mark_nonzero_rows(const float* g, int n, uint8_t* m, hipStream_t s, int cols = H, int set = 0);
-hipError_t launch_zero_rows(float* A, int ld, const int* rows, const int* n_rows_ptr, int max_rows, hipStream_t s,
-                            float* copy_dst = nullptr, const float* copy_src = nullptr, int copy_n = 0);
+hipError_t launch_zero_rows(float* A, int ld, RowList rows, int max_rows, hipStream_t s, float* copy_dst = nullptr,
+                            const float* copy_src = nullptr, int copy_n = 0);
 hipError_t launch_edge_rows_reduce(const float* dE, const int* rin_ptr, const int* rin_edge, int n_nodes, float* dP, hipStream_t s);
 // floats of nk_scratch: two slots (key | value path) per wave of the largest grid: the normalised pre-activation of a path, parked by its
 // forward part and read back by the backward sweep in the same labeling (the key path also across two phases of a node)
 constexpr size_t BX_NK_FLOATS = (size_t)256 * 8 * 2 * (KNN * H + 128);
-hipError_t launch_fold_grad(const float* att, const float* Gr, int n_nodes, float* Gt, float* gb, hipStream_t s,
-                            const int* rows = nullptr, const int* n_rows = nullptr);
-hipError_t launch_outer_accum_mfma(bool headed, const float* Lm, const float* R, const int* rows, const int* n_rows,
-                                   int n_nodes, float* partial, size_t slab_stride, int grid, hipStream_t s);
-// (`rows` / `n_rows`, wgrad and dgrad: restrict the node dimension to a device-side list -- the rows outside it are known to be zero)
-hipError_t launch_wgrad_mfma(const float* Lm, int ldl, const float* R, int ldr, int n_nodes, int col_blocks, float* partial,
-                             int ldo, size_t slab_stride, int groups, hipStream_t s, const int* rows = nullptr,
-                             const int* n_rows = nullptr);
+hipError_t launch_fold_grad(const float* att, const float* Gr, int n_nodes, float* Gt, float* gb, hipStream_t s, RowList rows = {});
+hipError_t launch_outer_accum_mfma(bool headed, const float* Lm, const float* R, RowList rows, int n_nodes, float* partial,
+                                   size_t slab_stride, int grid, hipStream_t s);
+// (`rows`, wgrad and dgrad: restrict the node dimension to a device-side list -- the rows outside it are known to be zero)
+hipError_t launch_wgrad_mfma(const float* Lm, int ldl, const float* R, int ldr, int n_nodes, int col_blocks, float* partial, int ldo,
+                             size_t slab_stride, int groups, hipStream_t s, RowList rows = {});
 // `C_in` (accumulate only): the addend is read from C_in instead of C (same leading dimension) -- C = C_in + A B^T out of place
-hipError_t launch_dgrad_mfma(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int K,
-                             int accumulate, hipStream_t s, const float* C_in = nullptr, const int* rows = nullptr,
-                             const int* n_rows = nullptr);
-hipError_t launch_q_backward_mfma(const float* att, const float* P, const float* T, const int* rows, const int* n_rows,
-                                  int n_nodes, float* qs, float* dqb, float* zb, float* dP, float* partial, int grid,
-                                  hipStream_t s);
+hipError_t launch_dgrad_mfma(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int K, int accumulate,
+                             hipStream_t s, const float* C_in = nullptr, RowList rows = {});
+hipError_t launch_q_backward_mfma(const float* att, const float* P, const float* T, RowList rows, int n_nodes, float* qs, float* dqb,
+                                  float* zb, float* dP, float* partial, int grid, hipStream_t s);
 #ifdef CBGX_XCHECK
-hipError_t launch_q_backward(const float* att, const float* P, const float* T, const int* rows, const int* n_rows,
-                             int n_nodes, float* qs, float* dqb, float* zb, float* dP, float* partial, int grid,
-                             hipStream_t s);
+hipError_t launch_q_backward(const float* att, const float* P, const float* T, RowList rows, int n_nodes, float* qs, float* dqb,
+                             float* zb, float* dP, float* partial, int grid, hipStream_t s);
 #endif
 #ifdef CBGX_XCHECK
-hipError_t launch_outer_accum(bool headed, const float* Lm, const float* R, const int* rows, const int* n_rows,
-                              int n_nodes, float* partial, size_t slab_stride, int grid, hipStream_t s);
+hipError_t launch_outer_accum(bool headed, const float* Lm, const float* R, RowList rows, int n_nodes, float* partial,
+                              size_t slab_stride, int grid, hipStream_t s);
 #endif
 hipError_t launch_compose_plan(const int64_t* br, const int64_t* bl, int n_rec, int n_lig, int B, int* scratch, int64_t* sort_idx,
                                int64_t* batch_idx, uint8_t* lig_flag, int64_t* lig_rows, int32_t* graph_ptr, hipStream_t s);
@@ -111,8 +101,8 @@ hipError_t launch_embed_compose(const float* x_rec, const float* x_lig, const fl
                                 int A, int C, const EmbedParams& p, float* x, float* h, float* ext, uint8_t* gen, hipStream_t s);
 hipError_t launch_embed_compose_backward(const float* grad_h, const float* ext, int n, int F, int A, int C, float* partial, int groups,
                                          float* grad_out, hipStream_t s);
-hipError_t launch_colsum(const float* A, int lda, int cols, const float* scale, const int* rows, const int* n_rows_ptr,
-                         int n_rows, float* partial, size_t slab_stride, int grid, hipStream_t s);
+hipError_t launch_colsum(const float* A, int lda, int cols, const float* scale, RowList rows, int n_rows, float* partial,
+                         size_t slab_stride, int grid, hipStream_t s);
 // up to RS_MAX reduce_store pieces in one launch
 constexpr int RS_MAX = 32;
 struct RsPiece {
@@ -137,8 +127,8 @@ hipError_t launch_sgemm(bool ta, bool tb, const float* A, int lda, const float* 
                         int N, int K, int splits, size_t c_split_stride, int accumulate, hipStream_t s);
 // grad_x != NULL: also ADD the gate's dL/dx (through the edge distances) to grad_x [N,3] (fp32 atomics)
 hipError_t launch_gate_backward_mfma(const float* packed, const float* x, const int32_t* nbr, const int32_t* deg, int n_nodes,
-                                     const float* de_w, float* partial, int grid, hipStream_t s, const int* rows = nullptr,
-                                     const int* n_rows = nullptr, float* grad_x = nullptr);
+                                     const float* de_w, float* partial, int grid, hipStream_t s, RowList rows = {},
+                                     float* grad_x = nullptr);
 hipError_t launch_ssp_backward(const float* pre, const float* dact, long n, float* dpre, hipStream_t s);
 // train_loss.hip: TargetDiff's forward noising, its two losses with their gradients, and the scatter of those gradients
 hipError_t launch_train_noise(const float* x0, const int64_t* v0, const int64_t* t, const int64_t* batch, const uint8_t* gen,
@@ -182,10 +172,8 @@ hipError_t launch_diffbp_noise(const float* x0, const int64_t* v0, const int64_t
                                const int64_t* sort_idx, const int32_t* graph_ptr, int n_rec, int B, int C, const float* acp,
                                int num_timesteps, int absorbing, float* x_t, float* pos_noise, float* com_noise, int64_t* v_t, float* c_t,
                                uint8_t* type_flag, hipStream_t s);
-hipError_t launch_ssp_backward_rows(const float* pre, const float* dact, const int* rows, const int* n_rows, int max_rows,
-                                    float* dpre, hipStream_t s);
-hipError_t launch_cls_w1_grad_rows(const float* dlogits, int C, const float* act, const int* rows, const int* n_rows, float* dW1,
-                                   hipStream_t s);
+hipError_t launch_ssp_backward_rows(const float* pre, const float* dact, RowList rows, int max_rows, float* dpre, hipStream_t s);
+hipError_t launch_cls_w1_grad_rows(const float* dlogits, int C, const float* act, RowList rows, float* dW1, hipStream_t s);
 hipError_t launch_add_inplace(float* dst, const float* src, long n, hipStream_t s);
 
 }  // namespace cbgx

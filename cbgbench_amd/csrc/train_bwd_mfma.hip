@@ -1122,76 +1122,75 @@ __global__ __launch_bounds__(256) void dgrad_mfma_kernel(const float* __restrict
         if (_e != hipSuccess) return _e;               \
     } while (0)
 
-hipError_t launch_edge_backward_mfma(bool x2h, const float* att, const float* x, const float* P, const float* Qt,
-                                     const float* Gt, const float* gb, const float* gx_out, const int32_t* nbr,
-                                     const int32_t* deg, const uint8_t* lig, const float* e_w, const int* rows,
-                                     const int* n_rows, int n_nodes, float* T, float* S, float* sw, float* dP, float* dx,
-                                     float* de_w, float* partial, int grid, hipStream_t s, int centred) {
-    if ((long)n_nodes * HEADS * H >= (1L << 32)) return hipErrorInvalidValue;   // 32-bit element offsets inside the kernel
+hipError_t launch_edge_backward_mfma(bool x2h, const float* att, const Graph& g, const float* x, const float* P, const float* Qt,
+                                     const float* Gt, const float* gb, const float* gx_out, RowList rows, float* T, float* S, float* sw,
+                                     float* dP, float* dx, float* de_w, float* partial, int grid, hipStream_t s, int centred) {
+    if ((long)g.n_nodes * HEADS * H >= (1L << 32)) return hipErrorInvalidValue;   // 32-bit element offsets inside the kernel
 #ifdef CBGX_ABLATE
     // timing ablations (WRONG results): only in libcbgx_ablate.so, built by scripts/abl_bwd.sh with -DCBGX_ABLATE
     static const int abl = getenv("CBGX_BWD_ABL") ? atoi(getenv("CBGX_BWD_ABL")) : 0;
 #else
     constexpr int abl = 0;
 #endif
-    profile_mark_begin(x2h ? (rows ? K_EDGE_X2H_BWD_LISTED : K_EDGE_X2H_BWD) : K_EDGE_H2X_BWD, s);
+    profile_mark_begin(x2h ? (rows.rows ? K_EDGE_X2H_BWD_LISTED : K_EDGE_X2H_BWD) : K_EDGE_H2X_BWD, s);
     if (x2h) {
         // the product runs x2h blocks through train_bwd_x2h.hip; this instantiation exists in libcbgx_xcheck.so only
         // (cbgx_debug_set_edge_kernel(2)) as an independent on-device implementation of the same contract
 #ifdef CBGX_XCHECK
         hipLaunchKernelGGL(edge_backward_mfma_kernel<true>, dim3(grid), dim3(BWD_THREADS), 0, s, att, x, P, Qt, Gt, gb,
-                           gx_out, nbr, deg, lig, e_w, rows, n_rows, n_nodes, T, S, sw, dP, dx, de_w, partial, abl, centred);
+                           gx_out, g.nbr, g.deg, g.lig, g.e_w, rows.rows, rows.count, g.n_nodes,
+                           T, S, sw, dP, dx, de_w, partial, abl, centred);
 #else
         profile_mark_end(s);
         return hipErrorNotSupported;
 #endif
     } else
         hipLaunchKernelGGL(edge_backward_mfma_kernel<false>, dim3(grid), dim3(BWD_THREADS), 0, s, att, x, P, Qt, Gt, gb,
-                           gx_out, nbr, deg, lig, e_w, rows, n_rows, n_nodes, T, S, sw, dP, dx, de_w, partial, abl, centred);
+                           gx_out, g.nbr, g.deg, g.lig, g.e_w, rows.rows, rows.count, g.n_nodes,
+                           T, S, sw, dP, dx, de_w, partial, abl, centred);
     profile_mark_end(s);
     CBGX_LAUNCH_CHECK();
     return hipSuccess;
 }
 
-hipError_t launch_q_backward_mfma(const float* att, const float* P, const float* T, const int* rows, const int* n_rows,
-                                  int n_nodes, float* qs, float* dqb, float* zb, float* dP, float* partial, int grid,
-                                  hipStream_t s) {
+hipError_t launch_q_backward_mfma(const float* att, const float* P, const float* T, RowList rows, int n_nodes, float* qs, float* dqb,
+                                  float* zb, float* dP, float* partial, int grid, hipStream_t s) {
     if ((long)n_nodes * HEADS * H >= (1L << 32)) return hipErrorInvalidValue;   // 32-bit element offsets inside the kernel
-    hipLaunchKernelGGL(q_backward_mfma_kernel, dim3(grid), dim3(256), 0, s, att, P, T, rows, n_rows, n_nodes, qs, dqb, zb,
+    hipLaunchKernelGGL(q_backward_mfma_kernel, dim3(grid), dim3(256), 0, s, att, P, T, rows.rows, rows.count, n_nodes, qs, dqb, zb,
                        dP, partial);
     CBGX_LAUNCH_CHECK();
     return hipSuccess;
 }
 
-hipError_t launch_outer_accum_mfma(bool headed, const float* Lm, const float* R, const int* rows, const int* n_rows,
-                                   int n_nodes, float* partial, size_t slab_stride, int grid, hipStream_t s) {
+hipError_t launch_outer_accum_mfma(bool headed, const float* Lm, const float* R, RowList rows, int n_nodes, float* partial,
+                                   size_t slab_stride, int grid, hipStream_t s) {
     if ((long)n_nodes * HEADS * H >= (1L << 32)) return hipErrorInvalidValue;   // 32-bit element offsets inside the kernel
     if (headed)
-        hipLaunchKernelGGL(outer_accum_mfma_kernel<true>, dim3(grid), dim3(256), 0, s, Lm, R, rows, n_rows, n_nodes,
+        hipLaunchKernelGGL(outer_accum_mfma_kernel<true>, dim3(grid), dim3(256), 0, s, Lm, R, rows.rows, rows.count, n_nodes,
                            partial, slab_stride);
     else
-        hipLaunchKernelGGL(outer_accum_mfma_kernel<false>, dim3(grid), dim3(256), 0, s, Lm, R, rows, n_rows, n_nodes,
+        hipLaunchKernelGGL(outer_accum_mfma_kernel<false>, dim3(grid), dim3(256), 0, s, Lm, R, rows.rows, rows.count, n_nodes,
                            partial, slab_stride);
     CBGX_LAUNCH_CHECK();
     return hipSuccess;
 }
 
 // C_slabs[g][128][ldo] (column blocks of 128) = partial sums over node groups of L^T R; returns the number of slabs
-hipError_t launch_wgrad_mfma(const float* Lm, int ldl, const float* R, int ldr, int n_nodes, int col_blocks, float* partial,
-                             int ldo, size_t slab_stride, int groups, hipStream_t s, const int* rows, const int* n_rows) {
+hipError_t launch_wgrad_mfma(const float* Lm, int ldl, const float* R, int ldr, int n_nodes, int col_blocks, float* partial, int ldo,
+                             size_t slab_stride, int groups, hipStream_t s, RowList rows) {
     if ((long)n_nodes * (ldl > ldr ? ldl : ldr) >= (1L << 32)) return hipErrorInvalidValue;
     const int per = ((n_nodes + groups - 1) / groups + 15) / 16 * 16;
     profile_mark_begin(K_TRAIN_GEMM, s);
     hipLaunchKernelGGL(wgrad_mfma_kernel, dim3(groups, col_blocks), dim3(256), 0, s, Lm, ldl, R, ldr, n_nodes, per, partial,
-                       ldo, slab_stride, rows, n_rows);
+                       ldo, slab_stride, rows.rows, rows.count);
     profile_mark_end(s);
     CBGX_LAUNCH_CHECK();
     return hipSuccess;
 }
 
 // C[M][128] (+)= A[M][K] B[128][K]^T, K a multiple of 64
-hipError_t launch_dgrad_mfma(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int K,
-                             int accumulate, hipStream_t s, const float* C_in, const int* rows, const int* n_rows) {
+hipError_t launch_dgrad_mfma(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int K, int accumulate,
+                             hipStream_t s, const float* C_in, RowList rows) {
     if (M <= 0) return hipSuccess;
     if (K % 64 != 0 || (long)M * (lda > ldc ? lda : ldc) >= (1L << 32)) return hipErrorInvalidValue;
     profile_mark_begin(K_TRAIN_GEMM, s);
@@ -1204,7 +1203,7 @@ hipError_t launch_dgrad_mfma(const float* A, int lda, const float* B, int ldb, f
 #endif
     // two workgroups of 32 rows per CU overlap each other's barriers and loads better than one of 64 (measured: 51.7 vs ... us)
     hipLaunchKernelGGL(dgrad_mfma_kernel<2>, dim3((M + 31) / 32), dim3(256), 0, s, A, lda, B, ldb, C, ldc, M, K, accumulate,
-                       C_in ? C_in : C, rows, n_rows);
+                       C_in ? C_in : C, rows.rows, rows.count);
     profile_mark_end(s);
     CBGX_LAUNCH_CHECK();
     return hipSuccess;

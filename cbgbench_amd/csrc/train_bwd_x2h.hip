@@ -1005,27 +1005,25 @@ __global__ __launch_bounds__(BX_WAVES * 64) void edge_backward_x2h_kernel(
     for (int u = tid; u < 2 * H; u += BX_WAVES * 64) { slab[PB_LNG + u] = L.lng[u]; slab[PB_LNB + u] = L.lnb[u]; }
 }
 
-hipError_t launch_edge_backward_x2h(const float* att, const float* x, const float* P, const float* Qt, const float* Gt,
-                                    const float* gb, const int32_t* nbr, const int32_t* deg, const uint8_t* lig,
-                                    const float* e_w, const int* rows, const int* n_rows, int n_nodes, float* T, float* S,
-                                    float* sw, float* dP, float* dx, float* de_w, float* partial, float* nk_scratch,
-                                    int* work_ctr, int grid, hipStream_t s, float* dE) {
-    if (dE && rows) return hipErrorInvalidValue;      // edge rows are a full-launch mode (a listed launch would leave stale rows behind)
-    profile_mark_begin(rows ? K_EDGE_X2H_BWD_LISTED : K_EDGE_X2H_BWD, s);
+hipError_t launch_edge_backward_x2h(const float* att, const Graph& g, const float* x, const float* P, const float* Qt, const float* Gt,
+                                    const float* gb, RowList rows, float* T, float* S, float* sw, float* dP, float* dx, float* de_w,
+                                    float* partial, float* nk_scratch, int* work_ctr, int grid, hipStream_t s, float* dE) {
+    if (dE && rows.rows) return hipErrorInvalidValue;      // edge rows are a full-launch mode (a listed launch would leave stale rows behind)
+    profile_mark_begin(rows.rows ? K_EDGE_X2H_BWD_LISTED : K_EDGE_X2H_BWD, s);
 #ifdef CBGX_ABLATE
     static const int abl = getenv("CBGX_BWD_ABL") ? atoi(getenv("CBGX_BWD_ABL")) : 0;
     static const bool prof = (abl & 512) != 0;      // section timers: CBGX_BWD_ABL bit 512
-    if (prof && !rows) {
+    if (prof && !rows.rows) {
         unsigned long long z[16] = {0};
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bx_prof), z, sizeof(z));
     }
     if (dE)
-        hipLaunchKernelGGL(edge_backward_x2h_kernel<true>, dim3(grid), dim3(BX_WAVES * 64), 0, s, att, x, P, Qt, Gt, gb, nbr, deg, lig,
-                           e_w, rows, n_rows, n_nodes, T, S, sw, dP, dx, de_w, partial, nk_scratch, work_ctr, dE, abl);
+        hipLaunchKernelGGL(edge_backward_x2h_kernel<true>, dim3(grid), dim3(BX_WAVES * 64), 0, s, att, x, P, Qt, Gt, gb,
+                           g.nbr, g.deg, g.lig, g.e_w, rows.rows, rows.count, g.n_nodes, T, S, sw, dP, dx, de_w, partial, nk_scratch, work_ctr, dE, abl);
     else
-        hipLaunchKernelGGL(edge_backward_x2h_kernel<false>, dim3(grid), dim3(BX_WAVES * 64), 0, s, att, x, P, Qt, Gt, gb, nbr, deg, lig,
-                           e_w, rows, n_rows, n_nodes, T, S, sw, dP, dx, de_w, partial, nk_scratch, work_ctr, dE, abl);
-    if (prof && !rows) {
+        hipLaunchKernelGGL(edge_backward_x2h_kernel<false>, dim3(grid), dim3(BX_WAVES * 64), 0, s, att, x, P, Qt, Gt, gb,
+                           g.nbr, g.deg, g.lig, g.e_w, rows.rows, rows.count, g.n_nodes, T, S, sw, dP, dx, de_w, partial, nk_scratch, work_ctr, dE, abl);
+    if (prof && !rows.rows) {
         unsigned long long z[16];
         (void)hipStreamSynchronize(s);
         (void)hipMemcpyFromSymbol(z, HIP_SYMBOL(g_bx_prof), sizeof(z));
@@ -1035,18 +1033,18 @@ hipError_t launch_edge_backward_x2h(const float* att, const float* x, const floa
                                   "pass4", "coordinates", "tuple issue", "gather issue"};
             unsigned long long tot = 0;
             for (int k = 0; k < 12; ++k) tot += z[k];
-            fprintf(stderr, "[bx prof] n=%d grid=%d total wave-cycles %llu:", n_nodes, grid, tot);
+            fprintf(stderr, "[bx prof] n=%d grid=%d total wave-cycles %llu:", g.n_nodes, grid, tot);
             for (int k = 0; k < 12; ++k) fprintf(stderr, " %s %.1f%%", nm[k], 100.0 * (double)z[k] / (double)tot);
             fprintf(stderr, "\n");
         }
     }
 #else
     if (dE)
-        hipLaunchKernelGGL(edge_backward_x2h_kernel<true>, dim3(grid), dim3(BX_WAVES * 64), 0, s, att, x, P, Qt, Gt, gb, nbr, deg, lig,
-                           e_w, rows, n_rows, n_nodes, T, S, sw, dP, dx, de_w, partial, nk_scratch, work_ctr, dE);
+        hipLaunchKernelGGL(edge_backward_x2h_kernel<true>, dim3(grid), dim3(BX_WAVES * 64), 0, s, att, x, P, Qt, Gt, gb,
+                           g.nbr, g.deg, g.lig, g.e_w, rows.rows, rows.count, g.n_nodes, T, S, sw, dP, dx, de_w, partial, nk_scratch, work_ctr, dE);
     else
-        hipLaunchKernelGGL(edge_backward_x2h_kernel<false>, dim3(grid), dim3(BX_WAVES * 64), 0, s, att, x, P, Qt, Gt, gb, nbr, deg, lig,
-                           e_w, rows, n_rows, n_nodes, T, S, sw, dP, dx, de_w, partial, nk_scratch, work_ctr, dE);
+        hipLaunchKernelGGL(edge_backward_x2h_kernel<false>, dim3(grid), dim3(BX_WAVES * 64), 0, s, att, x, P, Qt, Gt, gb,
+                           g.nbr, g.deg, g.lig, g.e_w, rows.rows, rows.count, g.n_nodes, T, S, sw, dP, dx, de_w, partial, nk_scratch, work_ctr, dE);
 #endif
     profile_mark_end(s);
     return hipGetLastError();

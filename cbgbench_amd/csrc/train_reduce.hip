@@ -745,24 +745,23 @@ __global__ void add_inplace_kernel(float* __restrict__ dst, const float* __restr
     } while (0)
 
 
-hipError_t launch_fold_grad(const float* att, const float* Gr, int n_nodes, float* Gt, float* gb, hipStream_t s, const int* rows,
-                            const int* n_rows) {
+hipError_t launch_fold_grad(const float* att, const float* Gr, int n_nodes, float* Gt, float* gb, hipStream_t s, RowList rows) {
     if (n_nodes <= 0) return hipSuccess;
     const int tiles = (n_nodes + 15) / 16, grid = tiles < FOLD_GRAD_GRID ? tiles : FOLD_GRAD_GRID;
-    if (rows) hipLaunchKernelGGL(fold_grad_kernel<true>, dim3(grid), dim3(256), 0, s, att, Gr, n_nodes, Gt, gb, rows, n_rows);
-    else hipLaunchKernelGGL(fold_grad_kernel<false>, dim3(grid), dim3(256), 0, s, att, Gr, n_nodes, Gt, gb, rows, n_rows);
+    if (rows.rows) hipLaunchKernelGGL(fold_grad_kernel<true>, dim3(grid), dim3(256), 0, s, att, Gr, n_nodes, Gt, gb, rows.rows, rows.count);
+    else hipLaunchKernelGGL(fold_grad_kernel<false>, dim3(grid), dim3(256), 0, s, att, Gr, n_nodes, Gt, gb, rows.rows, rows.count);
     CBGX_LAUNCH_CHECK();
     return hipSuccess;
 }
 
 
 
-hipError_t launch_colsum(const float* A, int lda, int cols, const float* scale, const int* rows, const int* n_rows_ptr,
-                         int n_rows, float* partial, size_t slab_stride, int grid, hipStream_t s) {
+hipError_t launch_colsum(const float* A, int lda, int cols, const float* scale, RowList rows, int n_rows, float* partial,
+                         size_t slab_stride, int grid, hipStream_t s) {
 #define CBGX_COLSUM(L, S)                                                                                             \
-    hipLaunchKernelGGL((colsum_kernel<L, S>), dim3(grid), dim3(256), 0, s, A, lda, cols, scale, rows, n_rows_ptr, n_rows, \
+    hipLaunchKernelGGL((colsum_kernel<L, S>), dim3(grid), dim3(256), 0, s, A, lda, cols, scale, rows.rows, rows.count, n_rows, \
                        partial, slab_stride)
-    if (rows) { if (scale) CBGX_COLSUM(true, true); else CBGX_COLSUM(true, false); }
+    if (rows.rows) { if (scale) CBGX_COLSUM(true, true); else CBGX_COLSUM(true, false); }
     else      { if (scale) CBGX_COLSUM(false, true); else CBGX_COLSUM(false, false); }
 #undef CBGX_COLSUM
     CBGX_LAUNCH_CHECK();
@@ -825,14 +824,13 @@ hipError_t launch_sgemm(bool ta, bool tb, const float* A, int lda, const float* 
 // product path: one fused kernel; `grid` slabs of GB_SIZE floats in `partial`, every one written (grid a multiple of GATE_WAVES)
 // grad_x != NULL: the DX variant, which also adds the gate's coordinate gradient to grad_x
 hipError_t launch_gate_backward_mfma(const float* packed, const float* x, const int32_t* nbr, const int32_t* deg, int n_nodes,
-                                     const float* de_w, float* partial, int grid, hipStream_t s, const int* rows, const int* n_rows,
-                                     float* grad_x) {
+                                     const float* de_w, float* partial, int grid, hipStream_t s, RowList rows, float* grad_x) {
     if (grad_x)
         hipLaunchKernelGGL(gate_bwd_dx_mfma_kernel, dim3(grid / GATE_WAVES), dim3(GATE_WAVES * 64), 0, s, packed, x, nbr, deg, n_nodes,
-                           de_w, partial, rows, n_rows, grad_x);
+                           de_w, partial, rows.rows, rows.count, grad_x);
     else
         hipLaunchKernelGGL(gate_bwd_mfma_kernel, dim3(grid / GATE_WAVES), dim3(GATE_WAVES * 64), 0, s, packed, x, nbr, deg, n_nodes,
-                           de_w, partial, rows, n_rows);
+                           de_w, partial, rows.rows, rows.count);
     CBGX_LAUNCH_CHECK();
     return hipSuccess;
 }
@@ -845,18 +843,16 @@ hipError_t launch_ssp_backward(const float* pre, const float* dact, long n, floa
     return hipSuccess;
 }
 
-hipError_t launch_ssp_backward_rows(const float* pre, const float* dact, const int* rows, const int* n_rows, int max_rows,
-                                    float* dpre, hipStream_t s) {
+hipError_t launch_ssp_backward_rows(const float* pre, const float* dact, RowList rows, int max_rows, float* dpre, hipStream_t s) {
     if (max_rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(ssp_backward_rows_kernel, dim3(max_rows < 2048 ? max_rows : 2048), dim3(H), 0, s, pre, dact, rows, n_rows,
+    hipLaunchKernelGGL(ssp_backward_rows_kernel, dim3(max_rows < 2048 ? max_rows : 2048), dim3(H), 0, s, pre, dact, rows.rows, rows.count,
                        dpre);
     CBGX_LAUNCH_CHECK();
     return hipSuccess;
 }
 
-hipError_t launch_cls_w1_grad_rows(const float* dlogits, int C, const float* act, const int* rows, const int* n_rows, float* dW1,
-                                   hipStream_t s) {
-    hipLaunchKernelGGL(cls_w1_grad_rows_kernel, dim3(C), dim3(H * CLS_GROUPS), 0, s, dlogits, C, act, rows, n_rows, dW1);
+hipError_t launch_cls_w1_grad_rows(const float* dlogits, int C, const float* act, RowList rows, float* dW1, hipStream_t s) {
+    hipLaunchKernelGGL(cls_w1_grad_rows_kernel, dim3(C), dim3(H * CLS_GROUPS), 0, s, dlogits, C, act, rows.rows, rows.count, dW1);
     CBGX_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -186,12 +186,12 @@ hipError_t launch_mark_nonzero_rows(const float* g, int n, uint8_t* m, hipStream
     return hipGetLastError();
 }
 
-hipError_t launch_zero_rows(float* A, int ld, const int* rows, const int* n_rows_ptr, int max_rows, hipStream_t s, float* copy_dst,
-                            const float* copy_src, int copy_n) {
+hipError_t launch_zero_rows(float* A, int ld, RowList rows, int max_rows, hipStream_t s, float* copy_dst, const float* copy_src,
+                            int copy_n) {
     if (max_rows <= 0 && copy_n <= 0) return hipSuccess;
     // two workgroups per CU: a listed block has ~2 k rows, and 2048 workgroups that mostly read the count and leave took 12 us
     const int g = (max_rows + 3) / 4;
-    hipLaunchKernelGGL(zero_rows_kernel, dim3(g < 1 ? 1 : (g < 512 ? g : 512)), dim3(256), 0, s, A, ld, rows, n_rows_ptr, copy_dst,
+    hipLaunchKernelGGL(zero_rows_kernel, dim3(g < 1 ? 1 : (g < 512 ? g : 512)), dim3(256), 0, s, A, ld, rows.rows, rows.count, copy_dst,
                        copy_src, copy_dst ? copy_n : 0);
     return hipGetLastError();
 }

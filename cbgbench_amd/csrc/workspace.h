@@ -24,19 +24,13 @@ struct Carver {
     }
 };
 
-// a node list built on the device: row ids (any order) and the address of their number
-struct NodeList {
-    int* rows;
-    int* count;
-};
-
 // The receptive-field walk every pruned path shares.  The caller has written the seed flags into `mask` and holds the list the first
 // hop starts from; each hop marks the neighbours of the previous list's rows and compacts the grown mask into the next list of `out`.
 static inline hipError_t walk_receptive_field(uint8_t* mask, NodeList from, const int32_t* nbr, const int32_t* deg, int n,
                                               std::initializer_list<NodeList> out, hipStream_t s) {
     for (const NodeList& to : out) {
-        hipError_t e = launch_mark_nbr(from.rows, from.count, n, nbr, deg, mask, s);
-        if (e == hipSuccess) e = launch_build_active(mask, n, to.rows, to.count, s);
+        hipError_t e = launch_mark_nbr(from, n, nbr, deg, mask, s);
+        if (e == hipSuccess) e = launch_build_active(mask, n, to, s);
         if (e != hipSuccess) return e;
         from = to;
     }

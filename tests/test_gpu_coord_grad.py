@@ -297,10 +297,14 @@ def bp():
     return m.to(DEV), sd
 
 
-@pytest.mark.parametrize("case", ["denoiser_2graphs", "denoiser_linker", "denoiser_small_graphs"])
-def test_com_predictor_coordinate_gradient(golden_dir, bp, case):
+@pytest.mark.parametrize("case", ["denoiser_2graphs", "denoiser_linker", "denoiser_small_graphs", "denoiser_small_graphs/all_rows"])
+def test_com_predictor_coordinate_gradient(golden_dir, bp, case, monkeypatch):
     """CoMPredictor with x_composed.requires_grad_(): x.grad, h.grad and the stack's parameter gradients against oracle.diffbp.com_head
-    autograd (the stack's blocks, its own distance gate and the zero-COM noise term)"""
+    autograd (the stack's blocks, its own distance gate and the zero-COM noise term).  `/all_rows`: the stack's taped forward and backward
+    without their row lists (CBGX_TRAIN_STACK_LISTS=0, read at every call), the same bounds."""
+    case, _, variant = case.partition("/")
+    if variant == "all_rows":
+        monkeypatch.setenv("CBGX_TRAIN_STACK_LISTS", "0")
     m, sd = bp
     head = m.com_head
     g = load(golden_dir, case)

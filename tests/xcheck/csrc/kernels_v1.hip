@@ -446,15 +446,15 @@ hipError_t launch_gate_v1(const float* packed, const float* x, const int32_t* nb
     return hipSuccess;
 }
 
-hipError_t launch_node_gemm_v1(const float* A, int lda, const float* Wt, const float* bias, float* C, int ldc, int M,
-                               int nout, int act, hipStream_t s, const int* rows, const int* n_rows) {
+hipError_t launch_node_gemm_v1(const float* A, int lda, const float* Wt, const float* bias, float* C, int ldc, int M, int nout, int act,
+                               hipStream_t s, RowList rows) {
     if (M == 0) return hipSuccess;
     dim3 grid((M + 15) / 16), block(256);
     profile_mark_begin(K_NODE_GEMM, s);
     if (act == 0)
-        hipLaunchKernelGGL(node_gemm_kernel<0>, grid, block, 0, s, A, lda, Wt, bias, C, ldc, M, nout, rows, n_rows);
+        hipLaunchKernelGGL(node_gemm_kernel<0>, grid, block, 0, s, A, lda, Wt, bias, C, ldc, M, nout, rows.rows, rows.count);
     else
-        hipLaunchKernelGGL(node_gemm_kernel<1>, grid, block, 0, s, A, lda, Wt, bias, C, ldc, M, nout, rows, n_rows);
+        hipLaunchKernelGGL(node_gemm_kernel<1>, grid, block, 0, s, A, lda, Wt, bias, C, ldc, M, nout, rows.rows, rows.count);
     profile_mark_end(s);
     CBGX_LAUNCH_CHECK();
     return hipSuccess;
@@ -469,20 +469,19 @@ hipError_t launch_node_query_v1(const float* att, const float* P, float* Qt, int
     return hipSuccess;
 }
 
-hipError_t launch_attention_v1(bool x2h, const float* att, const float* x, const float* h, const int32_t* nbr,
-                               const int32_t* deg, const uint8_t* lig, const uint8_t* gen, const float* e_w, int n_nodes,
-                               float* P, float* Qt, float* out, float* dx_out, hipStream_t s) {
-    hipError_t e = launch_node_gemm_v1(h, H, att + A_WN, att + A_BN, P, PROW, n_nodes, PROW, 0, s, nullptr, nullptr);
+hipError_t launch_attention_v1(bool x2h, const float* att, const Graph& g, const float* x, const float* h, const NodeBufs& b,
+                               float* out, float* dx_out, hipStream_t s) {
+    hipError_t e = launch_node_gemm_v1(h, H, att + A_WN, att + A_BN, b.P, PROW, g.n_nodes, PROW, 0, s, {});
     if (e != hipSuccess) return e;
-    e = launch_node_query_v1(att, P, Qt, n_nodes, s);
+    e = launch_node_query_v1(att, b.P, b.Qt, g.n_nodes, s);
     if (e != hipSuccess) return e;
     profile_mark_begin(x2h ? K_EDGE_X2H : K_EDGE_H2X, s);
     if (x2h)
-        hipLaunchKernelGGL(edge_attention_kernel<true>, dim3(n_nodes), dim3(128), 0, s, att, x, h, P, Qt, nbr, deg,
-                           lig, gen, e_w, n_nodes, out, dx_out);
+        hipLaunchKernelGGL(edge_attention_kernel<true>, dim3(g.n_nodes), dim3(128), 0, s, att, x, h, b.P, b.Qt, g.nbr, g.deg,
+                           g.lig, g.gen, g.e_w, g.n_nodes, out, dx_out);
     else
-        hipLaunchKernelGGL(edge_attention_kernel<false>, dim3(n_nodes), dim3(128), 0, s, att, x, h, P, Qt, nbr, deg,
-                           lig, gen, e_w, n_nodes, out, dx_out);
+        hipLaunchKernelGGL(edge_attention_kernel<false>, dim3(g.n_nodes), dim3(128), 0, s, att, x, h, b.P, b.Qt, g.nbr, g.deg,
+                           g.lig, g.gen, g.e_w, g.n_nodes, out, dx_out);
     profile_mark_end(s);
     CBGX_LAUNCH_CHECK();
     return hipSuccess;

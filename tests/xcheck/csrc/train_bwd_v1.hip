@@ -524,39 +524,36 @@ __global__ __launch_bounds__(256) void outer_accum_kernel(const float* __restric
     for (int k = 0; k < 64; ++k) slab[(size_t)(nh * 64 + k) * H + m] = acc[k];
 }
 
-hipError_t launch_edge_backward(bool x2h, const float* att, const float* x, const float* P, const float* Qt,
-                                const float* Gt, const float* gb, const float* gx_out, const int32_t* nbr,
-                                const int32_t* deg, const uint8_t* lig, const float* e_w, const int* rows,
-                                const int* n_rows, int n_nodes, float* T, float* S, float* sw, float* dP, float* dx,
-                                float* de_w, float* partial, int grid, hipStream_t s) {
-    profile_mark_begin(x2h ? (rows ? K_EDGE_X2H_BWD_LISTED : K_EDGE_X2H_BWD) : K_EDGE_H2X_BWD, s);
+hipError_t launch_edge_backward(bool x2h, const float* att, const Graph& g, const float* x, const float* P, const float* Qt,
+                                const float* Gt, const float* gb, const float* gx_out, RowList rows, float* T, float* S, float* sw,
+                                float* dP, float* dx, float* de_w, float* partial, int grid, hipStream_t s) {
+    profile_mark_begin(x2h ? (rows.rows ? K_EDGE_X2H_BWD_LISTED : K_EDGE_X2H_BWD) : K_EDGE_H2X_BWD, s);
     if (x2h)
-        hipLaunchKernelGGL(edge_backward_kernel<true>, dim3(grid), dim3(256), 0, s, att, x, P, Qt, Gt, gb, gx_out, nbr,
-                           deg, lig, e_w, rows, n_rows, n_nodes, T, S, sw, dP, dx, de_w, partial);
+        hipLaunchKernelGGL(edge_backward_kernel<true>, dim3(grid), dim3(256), 0, s, att, x, P, Qt, Gt, gb, gx_out,
+                           g.nbr, g.deg, g.lig, g.e_w, rows.rows, rows.count, g.n_nodes, T, S, sw, dP, dx, de_w, partial);
     else
-        hipLaunchKernelGGL(edge_backward_kernel<false>, dim3(grid), dim3(256), 0, s, att, x, P, Qt, Gt, gb, gx_out, nbr,
-                           deg, lig, e_w, rows, n_rows, n_nodes, T, S, sw, dP, dx, de_w, partial);
+        hipLaunchKernelGGL(edge_backward_kernel<false>, dim3(grid), dim3(256), 0, s, att, x, P, Qt, Gt, gb, gx_out,
+                           g.nbr, g.deg, g.lig, g.e_w, rows.rows, rows.count, g.n_nodes, T, S, sw, dP, dx, de_w, partial);
     profile_mark_end(s);
     CBGX_LAUNCH_CHECK();
     return hipSuccess;
 }
 
-hipError_t launch_q_backward(const float* att, const float* P, const float* T, const int* rows, const int* n_rows,
-                             int n_nodes, float* qs, float* dqb, float* zb, float* dP, float* partial, int grid,
-                             hipStream_t s) {
-    hipLaunchKernelGGL(q_backward_kernel, dim3(grid), dim3(256), 0, s, att, P, T, rows, n_rows, n_nodes, qs, dqb, zb, dP,
+hipError_t launch_q_backward(const float* att, const float* P, const float* T, RowList rows, int n_nodes, float* qs, float* dqb,
+                             float* zb, float* dP, float* partial, int grid, hipStream_t s) {
+    hipLaunchKernelGGL(q_backward_kernel, dim3(grid), dim3(256), 0, s, att, P, T, rows.rows, rows.count, n_nodes, qs, dqb, zb, dP,
                        partial);
     CBGX_LAUNCH_CHECK();
     return hipSuccess;
 }
 
-hipError_t launch_outer_accum(bool headed, const float* Lm, const float* R, const int* rows, const int* n_rows,
-                              int n_nodes, float* partial, size_t slab_stride, int grid, hipStream_t s) {
+hipError_t launch_outer_accum(bool headed, const float* Lm, const float* R, RowList rows, int n_nodes, float* partial,
+                              size_t slab_stride, int grid, hipStream_t s) {
     if (headed)
-        hipLaunchKernelGGL(outer_accum_kernel<true>, dim3(grid), dim3(256), 0, s, Lm, R, rows, n_rows, n_nodes, partial,
+        hipLaunchKernelGGL(outer_accum_kernel<true>, dim3(grid), dim3(256), 0, s, Lm, R, rows.rows, rows.count, n_nodes, partial,
                            slab_stride);
     else
-        hipLaunchKernelGGL(outer_accum_kernel<false>, dim3(grid), dim3(256), 0, s, Lm, R, rows, n_rows, n_nodes, partial,
+        hipLaunchKernelGGL(outer_accum_kernel<false>, dim3(grid), dim3(256), 0, s, Lm, R, rows.rows, rows.count, n_nodes, partial,
                            slab_stride);
     CBGX_LAUNCH_CHECK();
     return hipSuccess;
