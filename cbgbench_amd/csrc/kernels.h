@@ -274,6 +274,11 @@ hipError_t launch_ligand_bonds_fill(const float* x_lig, const uint8_t* z_lig, co
 // rings.hip: ring sizes (lengths of a minimum cycle basis) and the shortest ring through every atom, from that bond list; one wave per graph
 hipError_t launch_ligand_rings(const int32_t* lig_ptr, int n_lig, int n_graphs, const int32_t* bond_ptr, const int32_t* bond_index,
                                int n_bonds, uint8_t* atom_ring_min, int32_t* graph_out, hipStream_t s);
+// aromatic.hip: the closure of the model's aromatic flags over the chordless 5- and 6-cycles of that bond list, aromatic atoms and bonds;
+// one wave per graph
+hipError_t launch_ligand_aromatic(const uint8_t* z_lig, const uint8_t* flag_lig, const uint8_t* atom_ring_min, const int32_t* lig_ptr,
+                                  int n_lig, int n_graphs, const int32_t* bond_ptr, const int32_t* bond_index, int n_bonds,
+                                  uint8_t* atom_out, uint8_t* bond_aromatic, int32_t* graph_out, hipStream_t s);
 // distributions.hip: pair-distance histograms of the same ligands (two families, LDS integer histograms), and the bond angles of the
 // table-bond graph from its symmetric adjacency -- cosine, bin against a cosine table, canonical type; one workgroup per graph each
 hipError_t launch_ligand_pair_hist(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,

@@ -25,6 +25,14 @@ csrc/rings.hip) -- the RDKit-free counterpart of the ring statistics of ``evalua
 ``repo/tools/eval_ring_type.py``, which read the sizes of RDKit's ``AtomRings()``.  Deviations: table bonds; RDKit's SSSR is a heuristic
 that can differ from a minimum cycle basis on cage-like graphs.
 
+``ligand_aromatic`` / ``batch_aromatic`` / ``summarise_aromatic`` add the aromatic bond type the table bonds lack: the closure of the
+model's per-atom aromatic flags ('add_aromatic' atom types) under the two rules of the reference's ``reconstruct_mol``
+(repo/tools/rdkit_utils.py:380-389, 552-572) over the chordless 5- and 6-cycles of the graph, in one launch on the bond list and the ring
+report (``cbgx_ligand_aromatic``, csrc/aromatic.hip); a bond is aromatic (``bond_type`` 4) as an edge of a cycle inside the closure.
+Deviations: the rules run to their fixed point (the reference applies each once); the link of biphenyl is not aromatic.  Handed to
+``batch_distributions(..., aromatic=)`` it re-keys the bond-length and bond-angle histograms by four bond types (``n_orders=4``).
+``sdf_record`` writes a sample as a V2000 record on the host.
+
 ``ligand_pair_hist`` / ``ligand_angles`` / ``batch_distributions`` / ``summarise_distributions`` are the rest of that report, the
 distributions it compares with a dataset's by Jensen-Shannon distance (``repo/tools/geometry/eval_bond_length.py``,
 ``eval_bond_angle.py``): pair-distance histograms (``All_12A``, ``CC_2A``; reproduced exactly: they need coordinates and elements only),
@@ -39,7 +47,7 @@ import numpy as np
 import torch
 
 from . import _native
-from .config import _ATOMIC_NUMBER
+from .config import _AROMATIC, _ATOMIC_NUMBER
 
 MAX_LIGAND_ATOMS = 1024       # include/cbgx.h CBGX_GEOMETRY_MAX_LIGAND
 # flags bits (include/cbgx.h CBGX_GEOM_*)
@@ -358,14 +366,177 @@ def ring_jsd(distribution, reference):
     return float(np.sqrt(max(0.5 * (kl(p, mid) + kl(q, mid)), 0.0)))
 
 
+# ---- aromatic atoms and bonds of the table-bond graph --------------------------------------------------------------------------------
+MAX_AROMATIC_ATOMS, MAX_AROMATIC_CYCLES = 256, 128      # include/cbgx.h CBGX_AROMATIC_MAX_ATOMS / _MAX_CYCLES
+# columns of ligand_aromatic's graph_counts (include/cbgx.h CBGX_AROMATIC_GRAPH_COLS)
+AROMATIC_GRAPH_COLUMNS = ("n_atoms", "n_bonds", "n_cycles56", "n_aromatic_cycles", "n_flagged", "n_closure", "n_aromatic_atoms",
+                          "n_aromatic_bonds", "n_unsupported", "status")
+# status bits (include/cbgx.h CBGX_AROMATIC_*): a graph with status != 0 was not evaluated
+AROMATIC_TOO_MANY_ATOMS, AROMATIC_TOO_MANY_CYCLES, AROMATIC_BAD_BONDS, AROMATIC_NO_RINGS = 1, 2, 4, 8
+AROMATIC_BOND_TYPE = 4                     # bond_type of an aromatic bond; 1 ... 3 are the bond orders
+BOND_TYPE_NOT_EVALUATED = 255
+
+
+def ligand_aromatic(z_lig, flag_lig, lig_batch, n_graphs, bonds, rings):
+    """Aromatic atoms and bonds of the bond graphs of ``n_graphs`` ligands, one launch (``cbgx_ligand_aromatic``, csrc/aromatic.hip; the
+    definition is in include/cbgx.h) on the tensors' current stream: the closure F of the model's per-atom flags ``flag_lig`` under the
+    reference's two rules (``reconstruct_mol``, repo/tools/rdkit_utils.py:380-389, 552-572) over the chordless 5- and 6-cycles of the
+    graph, as a least fixed point; an aromatic cycle is such a cycle inside F.
+
+    ``z_lig`` [n_lig] atomic numbers, ``flag_lig`` [n_lig] bool or 0 / 1, ``lig_batch`` [n_lig] grouped by graph; ``bonds``: what
+    ``ligand_bonds`` returned for the same atoms, ``rings``: what ``ligand_rings`` returned for that bond list.  Returns device tensors:
+    ``aromatic_atom`` [n_lig] bool (on an aromatic cycle), ``in_closure`` [n_lig] bool (in F), ``aromatic_bond`` [n_bonds] bool (an edge
+    of an aromatic cycle), ``bond_type`` [n_bonds] uint8 (4 for an aromatic bond, else ``bond_order``; 255 where not evaluated) and
+    ``graph_counts`` [n_graphs, 10] int32 (AROMATIC_GRAPH_COLUMNS).  A graph over a limit, with a malformed list, or that the ring report
+    did not evaluate is not an error: its status is non-zero (AROMATIC_*), its columns from n_cycles56 to n_unsupported are -1, its atoms
+    and bonds are False here and its ``bond_type`` 255.  Deviations from the reference: the rules run to their fixed point (the
+    reference applies each once, in OpenBabel's order: its result is contained in this one); a bond is aromatic only as an edge of an
+    aromatic cycle (the reference marks every bond with two aromatic ends, e.g. the link of biphenyl).  There is no CPU path."""
+    dev = z_lig.device
+    if dev.type != "cuda":
+        raise _native.NativeError("ligand_aromatic runs on the GPU (cbgx_ligand_aromatic): there is no CPU fallback")
+    n_graphs = int(n_graphs)
+    bond_index, bond_order, ring_min = bonds["bond_index"], bonds["bond_order"], rings["atom_ring_min"]
+    for name, t in (("flag_lig", flag_lig), ("lig_batch", lig_batch), ("bond_index", bond_index), ("bond_order", bond_order),
+                    ("atom_ring_min", ring_min)):
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, z_lig on {dev}")
+    if bond_index.dim() != 2 or bond_index.shape[0] != 2:
+        raise ValueError("bond_index must be [2, n_bonds]")
+    n_lig, n_bonds = int(z_lig.shape[0]), int(bond_index.shape[1])
+    if z_lig.shape != (n_lig,) or flag_lig.shape != (n_lig,) or lig_batch.shape != (n_lig,) or ring_min.shape != (n_lig,):
+        raise ValueError("one atomic number, one flag, one graph index and one atom_ring_min per atom")
+    if bond_order.shape != (n_bonds,):
+        raise ValueError("one bond_order per bond")
+    lig_ptr = _csr(lig_batch, n_graphs, "lig_batch")
+    z_lig = torch.where((z_lig >= 0) & (z_lig <= 255), z_lig, torch.zeros_like(z_lig)).to(torch.uint8).contiguous()
+    flag_lig = (flag_lig != 0).to(torch.uint8).contiguous()
+    ring_min = ring_min.to(torch.uint8).contiguous()
+    bond_index = bond_index.to(torch.int32).contiguous()
+    first = bond_index[0].to(torch.long).clamp(0, max(n_lig - 1, 0))          # bond_ptr as the bond entries define it (ligand_rings)
+    counts = torch.bincount(first, minlength=n_lig) if n_lig else first.new_zeros(0)
+    bond_ptr = torch.cat([counts.new_zeros(1), counts.cumsum(0)]).to(torch.int32).contiguous()
+    atom_out = torch.empty(n_lig, dtype=torch.uint8, device=dev)
+    bond_out = torch.empty(n_bonds, dtype=torch.uint8, device=dev)
+    graph_counts = torch.empty(n_graphs, len(AROMATIC_GRAPH_COLUMNS), dtype=torch.int32, device=dev)
+    p = _native.ptr
+    _native.check(_native.lib().cbgx_ligand_aromatic(p(z_lig), p(flag_lig), p(ring_min), p(lig_ptr), n_lig, n_graphs, p(bond_ptr),
+                                                     p(bond_index) if n_bonds else None, n_bonds, p(atom_out),
+                                                     p(bond_out) if n_bonds else None, p(graph_counts), _native.current_stream(dev)),
+                  "cbgx_ligand_aromatic")
+    evaluated, bond_evaluated = atom_out != 255, bond_out != 255
+    bond_type = torch.where(bond_out == 1, torch.full_like(bond_out, AROMATIC_BOND_TYPE), bond_order.to(torch.uint8))
+    bond_type = torch.where(bond_evaluated, bond_type, torch.full_like(bond_out, BOND_TYPE_NOT_EVALUATED))
+    return {"aromatic_atom": evaluated & ((atom_out & 2) != 0), "in_closure": evaluated & ((atom_out & 1) != 0),
+            "aromatic_bond": bond_out == 1, "bond_type": bond_type, "graph_counts": graph_counts}
+
+
+def batch_aromatic(batch, x, c, lig_batch, mode, bonds=None, rings=None):
+    """``ligand_aromatic`` of a sampling state: the flags are the aromatic atom types of the vocabulary (``config._AROMATIC[mode]``), so
+    ``mode='basic'`` -- no flags to start from -- raises ValueError; ``bonds`` / ``rings``: what ``batch_bonds`` / ``batch_rings`` returned
+    for the same state (called here when None)"""
+    if mode not in _AROMATIC:
+        raise ValueError(f"mode {mode!r} has no aromatic atom types: the aromatic report starts from the model's flags ('add_aromatic')")
+    if bonds is None:
+        bonds = batch_bonds(batch, x, c, lig_batch, mode)
+    dev = bonds["bond_index"].device
+    lig_batch = lig_batch.to(dev)
+    if rings is None:
+        rings = ligand_rings(bonds["bond_index"], lig_batch, bonds["graph_counts"].shape[0])
+    typ = (c.argmax(-1) if c.dim() == 2 else c).to(dev).to(torch.long)
+    z = torch.tensor(_ATOMIC_NUMBER[mode], dtype=torch.long, device=dev)[typ]
+    flag = torch.tensor(_AROMATIC[mode], dtype=torch.bool, device=dev)[typ]
+    return ligand_aromatic(z, flag, lig_batch, bonds["graph_counts"].shape[0], bonds, rings)
+
+
+AROMATIC_COUNT_KEYS = ("n_mol", "n_mol_evaluated", "n_mol_over_limit", "n_atoms", "n_bonds", "n_cycles56", "n_aromatic_cycles",
+                       "n_flagged", "n_closure", "n_aromatic_atoms", "n_aromatic_bonds", "n_unsupported", "n_aromatic_mol")
+AROMATIC_RATIOS = ("aromatic_mol_ratio", "aromatic_rings_per_mol", "aromatic_cycle_share", "aromatic_atom_ratio", "aromatic_bond_ratio",
+                   "unsupported_flag_ratio")
+
+
+def aromatic_totals(graph_counts):
+    """per-molecule counts ``graph_counts`` [n_mol, 10] (AROMATIC_GRAPH_COLUMNS; any array-like) -> the integer totals, in
+    AROMATIC_COUNT_KEYS order.  Everything but n_mol and n_mol_over_limit is summed over the evaluated molecules (status == 0) only"""
+    if isinstance(graph_counts, torch.Tensor):
+        graph_counts = graph_counts.cpu().numpy()
+    gc = np.asarray(graph_counts, dtype=np.int64).reshape(-1, len(AROMATIC_GRAPH_COLUMNS))
+    ok = gc[gc[:, -1] == 0]
+    return ([int(gc.shape[0]), int(ok.shape[0]), int(gc.shape[0] - ok.shape[0])] + [int(v) for v in ok[:, :9].sum(0)]
+            + [int((ok[:, 3] > 0).sum())])
+
+
+def summarise_aromatic_totals(totals):
+    """the ratios (AROMATIC_RATIOS) of integer totals in AROMATIC_COUNT_KEYS order, and the totals as ``counts``; every ratio is over the
+    EVALUATED molecules, a ratio over nothing is nan.  aromatic_mol_ratio: the share of molecules with at least one aromatic cycle;
+    aromatic_rings_per_mol; aromatic_cycle_share: aromatic cycles / chordless 5- and 6-cycles; aromatic_atom_ratio / aromatic_bond_ratio:
+    aromatic atoms / atoms, aromatic bonds / bonds; unsupported_flag_ratio: n_unsupported / n_flagged, how often the model emitted an
+    aromatic type where the geometry built no ring to carry it"""
+    c = {k: int(v) for k, v in zip(AROMATIC_COUNT_KEYS, totals)}
+    ratio = lambda a, b: a / b if b else float("nan")
+    return {"aromatic_mol_ratio": ratio(c["n_aromatic_mol"], c["n_mol_evaluated"]),
+            "aromatic_rings_per_mol": ratio(c["n_aromatic_cycles"], c["n_mol_evaluated"]),
+            "aromatic_cycle_share": ratio(c["n_aromatic_cycles"], c["n_cycles56"]),
+            "aromatic_atom_ratio": ratio(c["n_aromatic_atoms"], c["n_atoms"]),
+            "aromatic_bond_ratio": ratio(c["n_aromatic_bonds"], c["n_bonds"]),
+            "unsupported_flag_ratio": ratio(c["n_unsupported"], c["n_flagged"]), "counts": c}
+
+
+def summarise_aromatic(graph_counts):
+    """aromatic statistics of a set of molecules from integer per-molecule counts (``graph_counts`` [n_mol, 10], AROMATIC_GRAPH_COLUMNS):
+    see ``summarise_aromatic_totals``"""
+    return summarise_aromatic_totals(aromatic_totals(graph_counts))
+
+
+# ---- SDF (V2000) records of samples: host only -----------------------------------------------------------------------------------------
+_SDF_SYMBOLS = {1: "H", 6: "C", 7: "N", 8: "O", 9: "F", 15: "P", 16: "S", 17: "Cl"}
+SDF_MAX_COUNT = 999                        # the counts line holds three digits
+
+
+def sdf_record(name, pos, atomic_numbers, bond_index, bond_type):
+    """one V2000 record as text: ``name``, two blank header lines, the counts line, atom lines ``%10.4f%10.4f%10.4f %-3s 0  0 ...``, bond
+    lines ``%3d%3d%3d  0`` (1-based atoms; type 1 ... 3 the order, 4 aromatic), ``M  END`` and ``$$$$``.  ``pos`` [n, 3],
+    ``atomic_numbers`` [n], ``bond_index`` [2, nb] local rows, ``bond_type`` [nb] (any array-like).  Raises ValueError for more than
+    SDF_MAX_COUNT atoms or bonds, an element outside H C N O F P S Cl, or a bond type outside 1 ... 4.  No RDKit: nothing is sanitised,
+    kekulised or given hydrogens"""
+    pos = np.asarray(_np(pos), np.float64).reshape(-1, 3)
+    zs = [int(v) for v in np.asarray(_np(atomic_numbers)).reshape(-1)]
+    idx = np.asarray(_np(bond_index), np.int64).reshape(2, -1)
+    types = [int(v) for v in np.asarray(_np(bond_type)).reshape(-1)]
+    if len(zs) != pos.shape[0] or len(types) != idx.shape[1]:
+        raise ValueError("sdf_record: one atomic number per position and one type per bond")
+    if len(zs) > SDF_MAX_COUNT or len(types) > SDF_MAX_COUNT:
+        raise ValueError(f"sdf_record: {len(zs)} atoms and {len(types)} bonds, a V2000 counts line holds {SDF_MAX_COUNT} of each")
+    if any(z not in _SDF_SYMBOLS for z in zs):
+        raise ValueError("sdf_record: an element outside H C N O F P S Cl")
+    if any(t not in (1, 2, 3, 4) for t in types):
+        raise ValueError("sdf_record: a bond type outside 1 ... 4")
+    if idx.size and (idx.min() < 0 or idx.max() >= len(zs)):
+        raise ValueError("sdf_record: a bond row outside the atoms")
+    lines = [str(name), "  cbgbench_amd", "", "%3d%3d  0  0  0  0  0  0  0  0999 V2000" % (len(zs), len(types))]
+    lines += ["%10.4f%10.4f%10.4f %-3s 0  0  0  0  0  0  0  0  0  0  0  0" % (x, y, z, _SDF_SYMBOLS[e]) for (x, y, z), e in zip(pos, zs)]
+    lines += ["%3d%3d%3d  0" % (i + 1, j + 1, t) for i, j, t in zip(idx[0], idx[1], types)]
+    return "\n".join(lines + ["M  END", "$$$$"]) + "\n"
+
+
 # ---- distributions: pair distances, bond lengths, bond angles ------------------------------------------------------------------------
 # include/cbgx.h CBGX_PAIR_HIST_MAX_EDGES / CBGX_ANGLES_MAX_EDGES / CBGX_ANGLES_MAX_PER_GRAPH / CBGX_ANGLE_BIN_DEGENERATE / CBGX_ANGLE_TYPES
 MAX_PAIR_EDGES, MAX_ANGLE_EDGES, MAX_ANGLES_PER_GRAPH, ANGLE_BIN_DEGENERATE, N_ANGLE_TYPES = 255, 254, 16384, 255, 4608
 N_BOND_TYPES = 192                         # ((order - 1) 8 + code_lo) 8 + code_hi
+# with the aromatic type beside the three orders (include/cbgx.h CBGX_AROMATIC_BOND_TYPES / _ANGLE_TYPES): n_orders = 4
+N_BOND_TYPES_4, N_ANGLE_TYPES_4 = 256, 8192
+
+
+def n_type_codes(n_orders=3):
+    """(bond type codes, angle type codes) of the three-order (default) or four-order (with the aromatic type) vocabulary"""
+    if n_orders not in (3, 4):
+        raise ValueError(f"n_orders is 3 (bond orders) or 4 (orders and the aromatic type), not {n_orders!r}")
+    return (N_BOND_TYPES, N_ANGLE_TYPES) if n_orders == 3 else (N_BOND_TYPES_4, N_ANGLE_TYPES_4)
 DISTRIBUTIONS_TOO_MANY_ANGLES = 1          # status bit (include/cbgx.h CBGX_DISTRIBUTIONS_TOO_MANY_ANGLES)
 DISTRIBUTION_GRAPH_COLUMNS = ("n_atoms", "n_bonds", "n_angles", "n_degenerate_angles", "status")
 PAIR_FAMILIES = ("All_12A", "CC_2A")       # family 0, family 1 of cbgx_ligand_pair_hist, named like the reference's profiles
 BOND_SYMBOLS = "-=#"                       # orders 1, 2, 3 (eval_bond_length.get_bond_str; '?' is what it prints for anything else)
+BOND_SYMBOLS_4 = BOND_SYMBOLS + ":"        # and type 4, the aromatic bond
 DISTRIBUTION_BINS = (101, 120, 91)         # bins of the pair, bond-length and angle histograms under the default edges
 
 
@@ -520,14 +691,42 @@ def _sparse_hist(graph, code, bins, n_codes, n_bins):
     return index, count.to(torch.int32)
 
 
-def batch_distributions(batch, x, c, lig_batch, mode, bonds=None):
+def _aromatic_types(out, bonds, aromatic, z, n_lig):
+    """``bond_type`` / ``angle_type`` of ``batch_distributions`` in the four-order codes: the bond's type is ``aromatic['bond_type']`` (its
+    order where the aromatic report did not evaluate the graph), an angle's two bonds are looked up in the bond list by ``searchsorted`` on
+    lo n_lig + hi -- the list is in (i, j) order, so the keys are sorted -- and the canonical orientation is chosen as the kernel does"""
+    dev = z.device
+    bi = bonds["bond_index"].to(torch.long)
+    t = torch.where(aromatic["bond_type"] == BOND_TYPE_NOT_EVALUATED, bonds["bond_order"].to(torch.uint8), aromatic["bond_type"]).to(torch.long)
+    code = _element_code(dev)[z]
+    ci, cj = code[bi[0]], code[bi[1]]
+    bond_type = (((t - 1) * 8 + torch.minimum(ci, cj)) * 8 + torch.maximum(ci, cj)).to(torch.int16)
+    ai = out["angle_index"].to(torch.long)
+    keys = bi[0] * max(n_lig, 1) + bi[1]
+
+    def type_of(u, v):
+        at = torch.searchsorted(keys, torch.minimum(u, v) * max(n_lig, 1) + torch.maximum(u, v))
+        return t[at.clamp(max=max(keys.numel() - 1, 0))] - 1          # (an angle's bonds are in the list: the clamp never acts)
+
+    ta, tb = type_of(ai[0], ai[1]), type_of(ai[2], ai[1])
+    ca, cc, cb = code[ai[0]], code[ai[1]], code[ai[2]]
+    swap = (ca > cb) | ((ca == cb) & (ta > tb))
+    c1, t1, c2, t2 = torch.where(swap, cb, ca), torch.where(swap, tb, ta), torch.where(swap, ca, cb), torch.where(swap, ta, tb)
+    return bond_type, ((((c1 * 4 + t1) * 8 + cc) * 4 + t2) * 8 + c2).to(torch.int16)
+
+
+def batch_distributions(batch, x, c, lig_batch, mode, bonds=None, aromatic=None):
     """The three distributions of a sampling state under the reference's bins (``default_pair_edges``, ``default_bond_edges``,
     ``default_cos_edges``); ``bonds``: what ``batch_bonds`` returned for the same state (it is called here when None).  Returns device
     tensors: the per-angle lists and ``graph_counts`` of ``ligand_angles``; ``bond_bin`` [n_bonds] uint8 (the number of edges strictly
     less than ``bond_length``: ``torch.bucketize``) and ``bond_type`` [n_bonds] int16 (``bond_type_code``) of the bond list;
     ``pair_hist`` [B, 2, 101] int32 of ``ligand_pair_hist``; and the per-graph histograms by type as sorted sparse lists,
     ``bond_hist_index`` [3, m] int32 (rows graph, type, bin) with ``bond_hist_count`` [m] int32, and ``angle_hist_index`` /
-    ``angle_hist_count`` likewise (degenerate angles left out)."""
+    ``angle_hist_count`` likewise (degenerate angles left out).
+
+    ``aromatic``: what ``batch_aromatic`` returned for the same state and bonds; ``bond_type``, ``angle_type`` and both sparse
+    histograms then use the four-order type codes (``bond_type_code`` / ``angle_type_code`` with ``n_orders=4``: an aromatic bond is type
+    4 and no longer counted under its order).  With None (default) every output is what it is without the argument."""
     if mode not in _ATOMIC_NUMBER:
         raise ValueError(mode)
     if bonds is None:
@@ -544,12 +743,15 @@ def batch_distributions(batch, x, c, lig_batch, mode, bonds=None):
     code = _element_code(dev)[z]
     ci, cj = code[bonds["bond_index"][0].to(torch.long)], code[bonds["bond_index"][1].to(torch.long)]
     out["bond_type"] = (((bonds["bond_order"].to(torch.long) - 1) * 8 + torch.minimum(ci, cj)) * 8 + torch.maximum(ci, cj)).to(torch.int16)
+    n_bond_types, n_angle_types = n_type_codes(3 if aromatic is None else 4)
+    if aromatic is not None:
+        out["bond_type"], out["angle_type"] = _aromatic_types(out, bonds, aromatic, z, int(z.shape[0]))
     n_pair, n_bond_bins, n_angle_bins = DISTRIBUTION_BINS
-    out["bond_hist_index"], out["bond_hist_count"] = _sparse_hist(bonds["bond_graph"], out["bond_type"], out["bond_bin"], N_BOND_TYPES,
+    out["bond_hist_index"], out["bond_hist_count"] = _sparse_hist(bonds["bond_graph"], out["bond_type"], out["bond_bin"], n_bond_types,
                                                                   n_bond_bins)
     ok = out["angle_bin"] != ANGLE_BIN_DEGENERATE
     out["angle_hist_index"], out["angle_hist_count"] = _sparse_hist(out["angle_graph"][ok], out["angle_type"][ok], out["angle_bin"][ok],
-                                                                    N_ANGLE_TYPES, n_angle_bins)
+                                                                    n_angle_types, n_angle_bins)
     return out
 
 
@@ -557,36 +759,39 @@ def batch_distributions(batch, x, c, lig_batch, mode, bonds=None):
 _ELEMENTS = (1, 6, 7, 8, 9, 15, 16, 17)      # atomic numbers of the element codes 0 ... 7 (``tables()['elements']``; asserted in the tests)
 
 
-def bond_type_code(code_a, order, code_b):
-    """((order - 1) 8 + code_lo) 8 + code_hi, code_lo <= code_hi: element codes 0 ... 7, order 1 ... 3"""
+def bond_type_code(code_a, order, code_b, n_orders=3):
+    """((order - 1) 8 + code_lo) 8 + code_hi, code_lo <= code_hi: element codes 0 ... 7, order 1 ... 3 -- with ``n_orders=4`` 1 ... 4, 4
+    the aromatic type (the packing is the same: the three-order codes are the first 192 of the 256)"""
     lo, hi = min(code_a, code_b), max(code_a, code_b)
     return ((order - 1) * 8 + lo) * 8 + hi
 
 
-def angle_type_code(code_a, order_ac, code_c, order_bc, code_b):
+def angle_type_code(code_a, order_ac, code_c, order_bc, code_b, n_orders=3):
     """the canonical code of an angle a - c - b: of the two orientations the one whose end (code, order) is lexicographically smaller
-    comes first, packed as (((code_1 3 + (o_1 - 1)) 8 + code_c) 3 + (o_2 - 1)) 8 + code_2, in [0, N_ANGLE_TYPES)"""
+    comes first, packed as (((code_1 K + (o_1 - 1)) 8 + code_c) K + (o_2 - 1)) 8 + code_2 with K = ``n_orders``: in [0, N_ANGLE_TYPES)
+    for K = 3, in [0, N_ANGLE_TYPES_4) for K = 4 (orders 1 ... 3 and the aromatic type 4)"""
     (c1, o1), (c2, o2) = sorted([(code_a, order_ac), (code_b, order_bc)])
-    return (((c1 * 3 + (o1 - 1)) * 8 + code_c) * 3 + (o2 - 1)) * 8 + c2
+    return (((c1 * n_orders + (o1 - 1)) * 8 + code_c) * n_orders + (o2 - 1)) * 8 + c2
 
 
 def bond_type_string(code):
-    """'6-6', '6=8', '6#7': atomic numbers in ascending order around the bond symbol, as eval_bond_length._bond_type_str prints them"""
+    """'6-6', '6=8', '6#7', '6:6': atomic numbers in ascending order around the bond symbol, as eval_bond_length._bond_type_str prints
+    them; ':' is the aromatic type of the four-order codes"""
     code = int(code)
-    return f"{_ELEMENTS[code // 8 % 8]}{BOND_SYMBOLS[code // 64]}{_ELEMENTS[code % 8]}"
+    return f"{_ELEMENTS[code // 8 % 8]}{BOND_SYMBOLS_4[code // 64]}{_ELEMENTS[code % 8]}"
 
 
-def angle_type_string(code):
-    """'6-6=8': as eval_bond_angle._angle_type_str prints the canonical orientation"""
-    code = int(code)
-    c2, o2, cc, o1, c1 = code % 8, code // 8 % 3, code // 24 % 8, code // 192 % 3, code // 576
-    return f"{_ELEMENTS[c1]}{BOND_SYMBOLS[o1]}{_ELEMENTS[cc]}{BOND_SYMBOLS[o2]}{_ELEMENTS[c2]}"
+def angle_type_string(code, n_orders=3):
+    """'6-6=8', with ``n_orders=4`` also '6:6:6': as eval_bond_angle._angle_type_str prints the canonical orientation"""
+    code, k = int(code), int(n_orders)
+    c2, o2, cc, o1, c1 = code % 8, code // 8 % k, code // (8 * k) % 8, code // (64 * k) % k, code // (64 * k * k)
+    return f"{_ELEMENTS[c1]}{BOND_SYMBOLS_4[o1]}{_ELEMENTS[cc]}{BOND_SYMBOLS_4[o2]}{_ELEMENTS[c2]}"
 
 
-def _parse_type(key):
+def _parse_type(key, n_orders=3):
     """a reference key -- 'CC_2A' / 'All_12A', a bond '6-6' or (6, 6, 1), an angle '8=6-6' or (8, 2, 6, 1, 6), in either orientation ->
     (kind, canonical string) or (None, reason).  Orders are 1, 2, 3 or the symbols - = #; 4, ':' and '?' (what the reference prints for
-    it) name an aromatic bond"""
+    it) name an aromatic bond, which is a type with ``n_orders=4`` and a reason not to evaluate the key with the default"""
     if isinstance(key, str) and key in PAIR_FAMILIES:
         return "pair_length", key
     if isinstance(key, str):
@@ -604,16 +809,17 @@ def _parse_type(key):
             atoms, orders = f[0::2], f[1::2]
         else:
             return None, "not a pair family, a bond type or an angle type"
-    if any(o == 4 for o in orders):
+    n_type_codes(n_orders)
+    if n_orders == 3 and any(o == 4 for o in orders):
         return None, "aromatic bond type: table bonds have orders 1, 2, 3 only"
-    if any(o not in (1, 2, 3) for o in orders):
+    if any(o not in (1, 2, 3, 4) for o in orders):
         return None, "unknown bond order"
     if any(z not in _ELEMENTS for z in atoms):
         return None, "an element outside H C N O F P S Cl"
     codes = [_ELEMENTS.index(z) for z in atoms]
     if len(codes) == 2:
-        return "bond_length", bond_type_string(bond_type_code(codes[0], orders[0], codes[1]))
-    return "bond_angle", angle_type_string(angle_type_code(codes[0], orders[0], codes[1], orders[1], codes[2]))
+        return "bond_length", bond_type_string(bond_type_code(codes[0], orders[0], codes[1], n_orders))
+    return "bond_angle", angle_type_string(angle_type_code(codes[0], orders[0], codes[1], orders[1], codes[2], n_orders), n_orders)
 
 
 def _key_string(key):
@@ -629,20 +835,24 @@ def _key_string(key):
 DISTRIBUTION_COUNT_KEYS = ("n_mol", "n_mol_over_limit", "n_atoms", "n_bonds", "n_angles", "n_degenerate_angles")
 
 
-def distribution_totals_length(bins=DISTRIBUTION_BINS):
-    """the length of the flat totals of ``distribution_totals``"""
-    return len(DISTRIBUTION_COUNT_KEYS) + 2 * bins[0] + N_BOND_TYPES * bins[1] + N_ANGLE_TYPES * bins[2]
+def distribution_totals_length(bins=DISTRIBUTION_BINS, n_orders=3):
+    """the length of the flat totals of ``distribution_totals``; ``n_orders=4``: with the aromatic type (``batch_distributions(...,
+    aromatic=...)``)"""
+    n_bond_types, n_angle_types = n_type_codes(n_orders)
+    return len(DISTRIBUTION_COUNT_KEYS) + 2 * bins[0] + n_bond_types * bins[1] + n_angle_types * bins[2]
 
 
 def _np(t):
     return t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
 
 
-def distribution_totals(dist, graphs=None, bins=DISTRIBUTION_BINS):
+def distribution_totals(dist, graphs=None, bins=DISTRIBUTION_BINS, n_orders=3):
     """what ``batch_distributions`` returned (tensors or arrays) -> the integer totals of its graphs, or of the graphs ``graphs`` = (g0, g1)
     only, as one flat int64 array that ranks can add: DISTRIBUTION_COUNT_KEYS, then the dense histograms flattened -- pairs [2, bins[0]],
     bond lengths [N_BOND_TYPES, bins[1]], angles [N_ANGLE_TYPES, bins[2]].  A molecule over the angle limit counts in n_mol and
-    n_mol_over_limit, with its atoms, bonds, pair and bond-length histograms; it has no angles"""
+    n_mol_over_limit, with its atoms, bonds, pair and bond-length histograms; it has no angles.  ``n_orders=4`` for what
+    ``batch_distributions(..., aromatic=...)`` returned: N_BOND_TYPES_4 and N_ANGLE_TYPES_4 rows"""
+    n_bond_types, n_angle_types = n_type_codes(n_orders)
     gc = _np(dist["graph_counts"]).astype(np.int64).reshape(-1, len(DISTRIBUTION_GRAPH_COLUMNS))
     g0, g1 = (0, gc.shape[0]) if graphs is None else (int(graphs[0]), int(graphs[1]))
     n_pair, n_bond_bins, n_angle_bins = bins
@@ -655,38 +865,41 @@ def distribution_totals(dist, graphs=None, bins=DISTRIBUTION_BINS):
     def dense(index, count, n_codes, n_bins):
         index, count = _np(index).astype(np.int64).reshape(3, -1), _np(count).astype(np.int64).reshape(-1)
         m = (index[0] >= g0) & (index[0] < g1)
+        if index.shape[1] and int(index[1].max()) >= n_codes:
+            raise ValueError(f"type code {int(index[1].max())} in a histogram of {n_codes} types: n_orders={n_orders} is not what made it")
         out = np.zeros(n_codes * n_bins, np.int64)
         np.add.at(out, index[1][m] * n_bins + index[2][m], count[m])
         return out
 
     return np.concatenate([np.asarray(head, np.int64), pair[g0:g1].sum(0).reshape(-1),
-                           dense(dist["bond_hist_index"], dist["bond_hist_count"], N_BOND_TYPES, n_bond_bins),
-                           dense(dist["angle_hist_index"], dist["angle_hist_count"], N_ANGLE_TYPES, n_angle_bins)])
+                           dense(dist["bond_hist_index"], dist["bond_hist_count"], n_bond_types, n_bond_bins),
+                           dense(dist["angle_hist_index"], dist["angle_hist_count"], n_angle_types, n_angle_bins)])
 
 
-def distribution_counts(totals, bins=DISTRIBUTION_BINS):
+def distribution_counts(totals, bins=DISTRIBUTION_BINS, n_orders=3):
     """the flat totals of ``distribution_totals`` as integers by name: ``counts`` (DISTRIBUTION_COUNT_KEYS), ``pair_hist`` [2][bins[0]],
     ``bond_hist`` / ``angle_hist`` {type string: [counts per bin]} for the types with a non-zero count"""
     t = np.asarray(totals, dtype=np.int64).reshape(-1)
     n_pair, n_bond_bins, n_angle_bins = bins
     n_head = len(DISTRIBUTION_COUNT_KEYS)
-    sizes = [n_head, 2 * n_pair, N_BOND_TYPES * n_bond_bins, N_ANGLE_TYPES * n_angle_bins]
+    n_bond_types, n_angle_types = n_type_codes(n_orders)
+    sizes = [n_head, 2 * n_pair, n_bond_types * n_bond_bins, n_angle_types * n_angle_bins]
     if t.shape[0] != sum(sizes):
         raise ValueError(f"{t.shape[0]} totals, expected {sum(sizes)} for bins {tuple(bins)}")
     head, pair, bond, angle = np.split(t, np.cumsum(sizes)[:-1])
-    bond, angle = bond.reshape(N_BOND_TYPES, n_bond_bins), angle.reshape(N_ANGLE_TYPES, n_angle_bins)
+    bond, angle = bond.reshape(n_bond_types, n_bond_bins), angle.reshape(n_angle_types, n_angle_bins)
     return {"counts": {k: int(v) for k, v in zip(DISTRIBUTION_COUNT_KEYS, head)}, "pair_hist": pair.reshape(2, n_pair).tolist(),
             "bond_hist": {bond_type_string(k): bond[k].tolist() for k in np.flatnonzero(bond.sum(1))},
-            "angle_hist": {angle_type_string(k): angle[k].tolist() for k in np.flatnonzero(angle.sum(1))}}
+            "angle_hist": {angle_type_string(k, n_orders): angle[k].tolist() for k in np.flatnonzero(angle.sum(1))}}
 
 
-def summarise_distribution_totals(totals, bins=DISTRIBUTION_BINS):
+def summarise_distribution_totals(totals, bins=DISTRIBUTION_BINS, n_orders=3):
     """the normalised distributions of integer totals (``distribution_totals``, summed over ranks): ``pair_length`` {'All_12A', 'CC_2A'},
     ``bond_length`` {'6-6', '6=8', ...} and ``bond_angle`` {'6-6=8', ...} -- keyed like the reference's profiles, atomic numbers around
     - = # -- each {'count': n, 'distribution': counts / n}; bond and angle types are listed when their count is non-zero, a pair family
     always, and a ratio over nothing is nan.  Plus ``counts`` (DISTRIBUTION_COUNT_KEYS).  What the reference compares with a dataset's
-    profile by Jensen-Shannon distance (``jsd_against``)"""
-    c = distribution_counts(totals, bins)
+    profile by Jensen-Shannon distance (``jsd_against``).  ``n_orders=4``: totals with the aromatic type, keys such as '6:6' and '6:6:6'"""
+    c = distribution_counts(totals, bins, n_orders)
 
     def profile(h):
         h = np.asarray(h, np.float64)
@@ -698,9 +911,9 @@ def summarise_distribution_totals(totals, bins=DISTRIBUTION_BINS):
             "bond_angle": {k: profile(h) for k, h in c["angle_hist"].items()}}
 
 
-def summarise_distributions(dist):
-    """``summarise_distribution_totals`` of what ``batch_distributions`` returned"""
-    return summarise_distribution_totals(distribution_totals(dist))
+def summarise_distributions(dist, n_orders=3):
+    """``summarise_distribution_totals`` of what ``batch_distributions`` returned (``n_orders=4`` when it was given ``aromatic=``)"""
+    return summarise_distribution_totals(distribution_totals(dist, n_orders=n_orders), n_orders=n_orders)
 
 
 def distribution_jsd(p, q):
@@ -718,17 +931,18 @@ def distribution_jsd(p, q):
     return float(np.sqrt(max((kl(p, mid) + kl(q, mid)) / 2.0, 0.0)))
 
 
-def jsd_against(summary, reference):
+def jsd_against(summary, reference, n_orders=3):
     """Jensen-Shannon distances of a job's distributions (``summarise_distribution_totals``) against the caller's own reference vectors --
     none ship with this package.  ``reference``: {key: vector}; a key is 'All_12A' / 'CC_2A', a bond type ('6-6' or (6, 6, 1)) or an angle
     type ('8=6-6' or (8, 2, 6, 1, 6)) in either orientation (canonicalised here).  Returns {'JSD_<key>': distance or None, ...} under
     the key's own spelling and ``not_evaluated`` {'JSD_<key>': reason}: a key that names an aromatic bond (type 4) cannot be met by table
-    bonds; a type without a sample has no distribution (the reference reports None there too).  A vector of another length than the
-    job's raises ValueError"""
+    bonds -- unless the summary is one with the aromatic type and ``n_orders=4`` says so: (6, 6, 4), '6:6' and '6:6:6' are then types
+    like any other --; a type without a sample has no distribution (the reference reports None there too).  A vector of another length
+    than the job's raises ValueError"""
     out, why = {}, {}
     for key, vec in reference.items():
         name = "JSD_" + _key_string(key)
-        kind, canon = _parse_type(key)
+        kind, canon = _parse_type(key, n_orders)
         if kind is None:
             out[name], why[name] = None, canon
             continue

@@ -31,6 +31,12 @@ through every atom -- computed on the device in one more launch per batch (``geo
 reference's geometry report compares with a dataset's by Jensen-Shannon distance -- pair distances (All_12A, CC_2A), bond lengths per
 bond type, bond angles per angle type -- computed on the device in two more launches per batch (``geometry.batch_distributions``), and
 ``{out_dir}/distributions_summary.json`` for the job; ``--distributions_reference`` adds the distances to the caller's own vectors.
+``--aromatic`` adds the aromatic atoms and bonds of that graph -- the closure of the model's aromatic flags under the reference's
+reconstruction rules over the chordless 5- and 6-cycles, bond type 4 for the edges of aromatic cycles -- computed on the device in one more
+launch per batch (``geometry.batch_aromatic``), and ``{out_dir}/aromatic_summary.json`` for the job; with ``--distributions`` the bond-length
+and bond-angle profiles are then keyed by four bond types (``6:6``, ``6:6:6``).
+``--sdf`` writes ``pocket_{i:05d}.sdf`` beside every result file: one V2000 record per sample, bond types from ``--aromatic`` when given,
+table-bond orders otherwise (``geometry.sdf_record``; host side, no RDKit).
 A checkpoint is the reference's format: ``{'config': ..., 'model': state_dict}`` (``sample.py:153-156``)."""
 import argparse
 import json
@@ -151,7 +157,8 @@ def main(argv=None, stats=None):
     also geometry = the report's launches, a part of write; with ``--bonds`` also bonds = the bond report's launches and downloads, a part
     of write; with ``--rings`` also rings = the ring report's launch and downloads -- and the bond launches when ``--bonds`` is absent --,
     a part of write; with ``--distributions`` also distributions = that report's launches and downloads -- and the bond launches when
-    ``--bonds`` is absent --, a part of write)."""
+    ``--bonds`` is absent --, a part of write; with ``--aromatic`` also aromatic = that report's launch and downloads -- and the bond and ring
+    launches when ``--bonds`` / ``--rings`` are absent --, a part of write)."""
     t_phase = time.perf_counter()
     phases = {"setup": 0.0, "batch": 0.0, "sample": 0.0, "write": 0.0}
 
@@ -229,6 +236,22 @@ def main(argv=None, stats=None):
                     help="with --distributions: a .npz or torch.save'd dict {key: vector} of the caller's own reference distributions "
                          "(keys 'All_12A', 'CC_2A', bond types like '6-6', angle types like '6-6=8' in either orientation; none ship "
                          "with this package); distributions_summary.json then carries their Jensen-Shannon distances as JSD_<key>")
+    ap.add_argument("--aromatic", action="store_true",
+                    help="add the aromatic report to every sample (aromatic_atom = on an aromatic cycle, aromatic_bond [nb] aligned with "
+                         "the bond_index of --bonds, bond_type = 4 for an aromatic bond else the order, n_aromatic_rings, "
+                         "aromatic_status), an `aromatic` dict of counts to every pocket record and {out_dir}/aromatic_summary.json: the "
+                         "closure of the model's aromatic flags (the sample's `aromatic` field, which stays as it is) under the rules of "
+                         "the reference's reconstruct_mol over the chordless 5- and 6-cycles of the table-bond graph, evaluated on the "
+                         "GPU in one launch per batch on the bond list and the ring report (cbgbench_amd/geometry.py).  add_aromatic "
+                         "atom types only.  A bond is aromatic as an edge of an aromatic cycle (the link of biphenyl is not).  "
+                         "Independent of --bonds and --rings: without them bonds and rings are computed and not written.  With "
+                         "--distributions the bond-length and bond-angle blocks are keyed by four bond types (6:6, 6:6:6)")
+    ap.add_argument("--sdf", action="store_true",
+                    help="write pocket_XXXXX.sdf beside every pocket_XXXXX.pt: one V2000 record per sample with the positions the record "
+                         "holds, bond types from --aromatic when given (4 = aromatic), else the table-bond orders (bonds are computed "
+                         "when --bonds is absent; GPU only).  A sample above 999 atoms or bonds, or with an element outside "
+                         "H C N O F P S Cl, is left out of the file and counted in one printed line.  No RDKit: no sanitisation, no "
+                         "hydrogens")
     ap.add_argument("--atom_num_dist", default=None,
                     help="the reference's size-conditioned ligand-size histogram (repo/datasets/transforms/_atom_num_dist.npy); "
                          "without it ligand sizes are U{10..45}")
@@ -253,6 +276,16 @@ def main(argv=None, stats=None):
         raise SystemExit("sample_cli: --rings runs on the GPU (cbgx_ligand_rings has no CPU fallback)")
     if args.distributions and dev.type != "cuda":
         raise SystemExit("sample_cli: --distributions runs on the GPU (cbgx_ligand_pair_hist / cbgx_ligand_angles have no CPU fallback)")
+    if args.aromatic:
+        # refused before any model is built, on any device: the report starts from the aromatic atom types
+        atom_mode = decode_mode(priors.SamplingPlan.from_config(config).mode, config.get("mode", None), config.model.num_atomtype)
+        if atom_mode != "add_aromatic":
+            raise SystemExit(f"sample_cli: --aromatic starts from the model's aromatic flags: atom types of mode 'add_aromatic', "
+                             f"not {atom_mode!r}")
+    if args.aromatic and dev.type != "cuda":
+        raise SystemExit("sample_cli: --aromatic runs on the GPU (cbgx_ligand_aromatic has no CPU fallback)")
+    if args.sdf and dev.type != "cuda":
+        raise SystemExit("sample_cli: --sdf takes its bonds from the GPU (cbgx_ligand_bonds_count / _fill have no CPU fallback)")
     if args.distributions_reference and not args.distributions:
         raise SystemExit("sample_cli: --distributions_reference needs --distributions")
 
@@ -312,7 +345,10 @@ def main(argv=None, stats=None):
     bonds_seconds, job_bond_counts = [0.0], []           # --bonds: likewise
     rings_seconds, job_ring_counts = [0.0], []           # --rings: likewise
     # --distributions: likewise; the pockets' flat integer totals are added up as they come (one is 3.5 MB)
-    distributions_seconds, job_distribution_totals = [0.0], np.zeros(geometry.distribution_totals_length(), np.int64)
+    n_orders = 4 if args.aromatic else 3                 # --aromatic --distributions: bond and angle types with the aromatic type
+    distributions_seconds, job_distribution_totals = [0.0], np.zeros(geometry.distribution_totals_length(n_orders=n_orders), np.int64)
+    aromatic_seconds, job_aromatic_counts = [0.0], []    # --aromatic: likewise
+    sdf_left_out = [0, 0]                                # --sdf: samples left out of their file, samples written
 
     def write_results(ids, traj, batch):
         # sample.py:198-201 hands traj[0] to the reconstruction -- for targetdiff / diffbp that is the state entering the
@@ -334,21 +370,41 @@ def main(argv=None, stats=None):
             bonds_dev = geometry.batch_bonds({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode)
             bonds = {k: v.cpu() for k, v in bonds_dev.items()}
             bonds_seconds[0] += time.perf_counter() - t_bonds
-        rings = None
+        rings = rings_dev = None
         if args.rings:
             # the same state again, on the bond list of --bonds when there is one (else the bonds are made here and not written)
             t_rings = time.perf_counter()
-            rings = geometry.batch_rings({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode, bonds=bonds_dev)
-            rings = {k: v.cpu() for k, v in rings.items()}
+            rings_dev = geometry.batch_rings({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode,
+                                             bonds=bonds_dev)
+            rings = {k: v.cpu() for k, v in rings_dev.items()}
             rings_seconds[0] += time.perf_counter() - t_rings
+        aro = aro_dev = aro_bonds = None
+        if args.aromatic:
+            # the same state again, on the bond list of --bonds and the ring report of --rings when there are such (else they are made here
+            # and not written)
+            t_aro = time.perf_counter()
+            aro_bonds = bonds_dev if bonds_dev is not None else geometry.batch_bonds({"num_graphs": len(ids) * num_samples}, x.to(dev),
+                                                                                     c.to(dev), bidx.to(dev), mode)
+            aro_dev = geometry.batch_aromatic({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode,
+                                              bonds=aro_bonds, rings=rings_dev)
+            aro = {k: v.cpu() for k, v in aro_dev.items()}
+            aromatic_seconds[0] += time.perf_counter() - t_aro
         dists = None
         if args.distributions:
             # the same state again, on the bond list of --bonds when there is one (else the bonds are made here and not written)
             t_dist = time.perf_counter()
+            dist_bonds = bonds_dev if bonds_dev is not None else aro_bonds
             dists = geometry.batch_distributions({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode,
-                                                 bonds=bonds_dev)
+                                                 bonds=dist_bonds, aromatic=aro_dev)
             dists = {k: v.cpu() for k, v in dists.items()}
             distributions_seconds[0] += time.perf_counter() - t_dist
+        sdf_bonds = None
+        if args.sdf:
+            # the bond list the records are written from: --aromatic's types when given, else the orders
+            sdf_bonds = bonds_dev if bonds_dev is not None else aro_bonds
+            if sdf_bonds is None:
+                sdf_bonds = geometry.batch_bonds({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode)
+            sdf_bonds = {k: sdf_bonds[k].cpu() for k in ("bond_index", "bond_order", "graph_counts")}
         x, c, bidx = x.cpu(), c.cpu(), bidx.cpu()
         if translate:       # back to the frame the pockets came in (sample.py:198-199; here per graph: a batch holds many pockets)
             x = x + batch["ligand_translation"].cpu()
@@ -385,6 +441,16 @@ def main(argv=None, stats=None):
                 smp["n_rings_larger"] = int(gc[g, -3])
                 smp["atom_ring_min"] = rings["atom_ring_min"][atom_end[g] - int(gc[g, 0]):atom_end[g]].clone()
                 smp["ring_status"] = int(gc[g, -1])
+        if aro is not None:
+            gc, bgc = aro["graph_counts"].to(torch.int64), aro_bonds["graph_counts"].cpu().to(torch.int64)
+            atom_end, bond_end = bgc[:, 0].cumsum(0).tolist(), bgc[:, 1].cumsum(0).tolist()
+            for g, smp in enumerate(samples):
+                a0, b0 = atom_end[g] - int(bgc[g, 0]), bond_end[g] - int(bgc[g, 1])
+                smp["aromatic_atom"] = aro["aromatic_atom"][a0:atom_end[g]].clone()
+                smp["aromatic_bond"] = aro["aromatic_bond"][b0:bond_end[g]].clone()
+                smp["bond_type"] = aro["bond_type"][b0:bond_end[g]].clone()
+                smp["n_aromatic_rings"] = int(gc[g, 3])
+                smp["aromatic_status"] = int(gc[g, 9])
         if dists is not None:
             # angles are sorted by their centre and atoms by graph: a graph's angles and atoms are ranges; rows become ligand-local
             gc = dists["graph_counts"].to(torch.int64)
@@ -399,9 +465,13 @@ def main(argv=None, stats=None):
         for k, pid in enumerate(ids):
             rec = {"pocket_index": pid, "samples": samples[k * num_samples:(k + 1) * num_samples]}
             if dists is not None:
-                totals = geometry.distribution_totals(dists, graphs=(k * num_samples, (k + 1) * num_samples))
+                totals = geometry.distribution_totals(dists, graphs=(k * num_samples, (k + 1) * num_samples), n_orders=n_orders)
                 job_distribution_totals[:] += totals
-                rec["distributions"] = geometry.distribution_counts(totals)
+                rec["distributions"] = geometry.distribution_counts(totals, n_orders=n_orders)
+            if aro is not None:
+                gc = aro["graph_counts"][k * num_samples:(k + 1) * num_samples].to(torch.int64)
+                job_aromatic_counts.append(gc)
+                rec["aromatic"] = geometry.summarise_aromatic(gc)["counts"]
             if rings is not None:
                 gc = rings["graph_counts"][k * num_samples:(k + 1) * num_samples].to(torch.int64)
                 job_ring_counts.append(gc)
@@ -417,6 +487,24 @@ def main(argv=None, stats=None):
             if args.save_traj:
                 rec["traj_keys"] = sorted(traj.keys())
             torch.save(rec, os.path.join(out_dir, f"pocket_{pid:05d}.pt"))
+            if sdf_bonds is not None:
+                gc = sdf_bonds["graph_counts"].to(torch.int64)
+                atom_end, bond_end = gc[:, 0].cumsum(0).tolist(), gc[:, 1].cumsum(0).tolist()
+                records = []
+                for j in range(num_samples):
+                    g = k * num_samples + j
+                    a0, b0, b1 = atom_end[g] - int(gc[g, 0]), bond_end[g] - int(gc[g, 1]), bond_end[g]
+                    # --aromatic's types where that report evaluated the sample, else the orders
+                    evaluated = aro is not None and int(aro["graph_counts"][g, 9]) == 0
+                    types = aro["bond_type"][b0:b1] if evaluated else sdf_bonds["bond_order"][b0:b1]
+                    try:
+                        records.append(geometry.sdf_record(f"pocket_{pid:05d}_sample_{j}", samples[g]["pos"], samples[g]["atom"],
+                                                           sdf_bonds["bond_index"][:, b0:b1] - a0, types))
+                        sdf_left_out[1] += 1
+                    except ValueError:
+                        sdf_left_out[0] += 1
+                with open(os.path.join(out_dir, f"pocket_{pid:05d}.sdf"), "w") as f:
+                    f.write("".join(records))
         return len(ids) * num_samples * model.num_diffusion_timesteps
 
     lap("setup", dev)
@@ -456,6 +544,8 @@ def main(argv=None, stats=None):
             stats["rings"] = rings_seconds[0]
         if args.distributions:
             stats["distributions"] = distributions_seconds[0]
+        if args.aromatic:
+            stats["aromatic"] = aromatic_seconds[0]
     if args.geometry:
         # integer counts of all ranks, summed: the job's numbers do not depend on how the pockets were sharded
         totals = geometry.job_totals(torch.cat(job_counts) if job_counts else torch.zeros(0, len(geometry.GRAPH_COLUMNS)))
@@ -486,10 +576,12 @@ def main(argv=None, stats=None):
                   + f", macrocycle_mol_ratio {summary['macrocycle_mol_ratio']:.4f}, ring_atom_ratio {summary['ring_atom_ratio']:.4f}"
                   + f" ({cnt['n_mol_evaluated']} of {cnt['n_mol']} molecules evaluated, {cnt['n_rings']} rings)")
     if args.distributions:
-        summary = geometry.summarise_distribution_totals(sharding.sum_counts(job_distribution_totals.tolist(), device=dev))
+        summary = geometry.summarise_distribution_totals(sharding.sum_counts(job_distribution_totals.tolist(), device=dev),
+                                                         n_orders=n_orders)
         if rank == 0:
             if args.distributions_reference:
-                summary.update(geometry.jsd_against(summary, load_reference_distributions(args.distributions_reference)))
+                summary.update(geometry.jsd_against(summary, load_reference_distributions(args.distributions_reference),
+                                                    n_orders=n_orders))
             with open(os.path.join(out_dir, "distributions_summary.json"), "w") as f:
                 json.dump(summary, f, indent=1, sort_keys=True)
             cnt, all_12a = summary["counts"], summary["pair_length"]["All_12A"]
@@ -499,6 +591,21 @@ def main(argv=None, stats=None):
             centre = float("nan") if mode_bin < 0 else float(edges[0] if mode_bin == 0 else 0.5 * (edges[mode_bin - 1] + edges[mode_bin]))
             print(f"distributions: {cnt['n_mol']} molecules, {cnt['n_bonds']} bonds, {cnt['n_angles']} angles, "
                   f"All_12A modal bin centre {centre:.3f} A, n_mol_over_limit {cnt['n_mol_over_limit']}")
+    if args.aromatic:
+        totals = geometry.aromatic_totals(torch.cat(job_aromatic_counts) if job_aromatic_counts
+                                          else torch.zeros(0, len(geometry.AROMATIC_GRAPH_COLUMNS)))
+        summary = geometry.summarise_aromatic_totals(sharding.sum_counts(totals, device=dev))
+        if rank == 0:
+            with open(os.path.join(out_dir, "aromatic_summary.json"), "w") as f:
+                json.dump(summary, f, indent=1, sort_keys=True)
+            cnt = summary["counts"]
+            print("aromatic: " + ", ".join(f"{k} {summary[k]:.4f}" for k in geometry.AROMATIC_RATIOS)
+                  + f" ({cnt['n_mol_evaluated']} of {cnt['n_mol']} molecules evaluated, {cnt['n_aromatic_cycles']} aromatic rings)")
+    if args.sdf:
+        left_out, written = sharding.sum_counts(sdf_left_out, device=dev)
+        if rank == 0:
+            print(f"sdf: {written} records written, {left_out} samples left out (above 999 atoms or bonds, or an element outside "
+                  f"H C N O F P S Cl)")
     if rank == 0:
         print(f"sampled {len(pockets)} pockets x {num_samples} samples on {world} rank(s): "
               f"{gs / el:.1f} graph-steps/s, results in {out_dir}")

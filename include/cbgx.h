@@ -795,6 +795,56 @@ int cbgx_ligand_bonds_fill(const float *x_lig, const uint8_t *z_lig, const int32
 int cbgx_ligand_rings(const int32_t *lig_ptr, int n_lig, int n_graphs, const int32_t *bond_ptr, const int32_t *bond_index, int n_bonds,
                       uint8_t *atom_ring_min, int32_t *graph_out, void *stream);
 
+/* ---- aromatic atoms and bonds of the table-bond graph of sampled ligands (aromatic.hip) -------------------------------------------------
+ * What the reference's reconstruct_mol (repo/tools/rdkit_utils.py:522-590) makes of the model's per-atom aromatic flags (`add_aromatic`
+ *   atom types): aromatic bonds, from three rules of its own -- fixup :380-389, the ring loop :552-572, the bond loop :574-579 -- that
+ *   need elements, flags, bonds and small rings only.  Here: per ligand graph, on the bond list of cbgx_ligand_bonds_fill, in ONE launch,
+ *   one wave per graph, integer work only.  lig_ptr, bond_ptr, bond_index as cbgx_ligand_rings takes them.
+ * Inputs per atom: z_lig [n_lig] uint8 atomic numbers, flag_lig [n_lig] uint8 the model's flags (non-zero: flagged), atom_ring_min
+ *   [n_lig] uint8 as cbgx_ligand_rings wrote it for the same list.
+ * Cycles: C56 is every CHORDLESS (induced) simple cycle of length 5 or 6 of the bond graph: a cycle none of whose non-consecutive atoms
+ *   are bonded.  That is what a ring perception reports on fused systems -- naphthalene's two hexagons and not its perimeter, norbornane's
+ *   5, 5 and 6, nothing for the chorded perimeter of bicyclo[2.2.0]hexane -- and it involves no choice (networkx.chordless_cycles is an
+ *   independent truth).
+ * Closure: F is the smallest set of atoms that contains the flagged atoms and is closed under
+ *   R2 (fixup): an atom with z = 7 or 8, with 3 <= atom_ring_min <= 9, and with at least two bonded neighbours in F, is in F;
+ *   R3 (ring loop): if a cycle c of C56 has 2 |{a in c: z = 6, a in F}| >= |{a in c: z = 6}|, all atoms of c are in F.  A cycle without
+ *     carbons satisfies the condition (0 >= 0), as in the reference: a ring of five nitrogens is in F with no flag at all.
+ *   Both rules are monotone, so the least fixed point exists, is unique and does not depend on the order in which atoms or cycles are
+ *   visited.  Deviation 1: the reference applies each rule once, in OpenBabel's atom and ring order; its result is contained in F, and
+ *   equals F whenever no rule fires because of an earlier firing.
+ * Aromatic cycle: a cycle of C56 all of whose atoms are in F.  aromatic_atom: the atom lies on an aromatic cycle.  aromatic_bond: the
+ *   bond is an edge of an aromatic cycle.  Deviation 2: the bond between the rings of biphenyl is therefore NOT aromatic; the reference
+ *   marks every bond with two aromatic ends (:574-579), and RDKit's sanitisation then rejects that molecule.
+ *   bond_type = 4 for an aromatic bond, else the bond's order (made by the caller; elementwise on the list).
+ * Outputs, dense, every element of every graph's ranges written: atom_out [n_lig] uint8 (bit 0: in F, bit 1: aromatic_atom),
+ *   bond_aromatic [n_bonds] uint8 (0 / 1), graph_out [B, CBGX_AROMATIC_GRAPH_COLS] int32: n_atoms, n_bonds, n_cycles56,
+ *   n_aromatic_cycles, n_flagged, n_closure (|F|), n_aromatic_atoms, n_aromatic_bonds, n_unsupported (flagged and not aromatic_atom: an
+ *   aromatic type where the geometry built no ring to carry it), status.
+ * Status, per graph, never an error: CBGX_AROMATIC_TOO_MANY_ATOMS (more than CBGX_AROMATIC_MAX_ATOMS atoms), CBGX_AROMATIC_BAD_BONDS
+ *   (the conditions of CBGX_RINGS_BAD_BONDS), CBGX_AROMATIC_TOO_MANY_CYCLES (neither of those two and n_bonds >= n_atoms +
+ *   CBGX_AROMATIC_MAX_CYCLES: the test cbgx_ligand_rings applies before staging), CBGX_AROMATIC_NO_RINGS (some atom of the graph has
+ *   atom_ring_min == 255: the ring report did not evaluate the graph; set beside any of the others).  With status != 0 the columns
+ *   n_cycles56 ... n_unsupported are -1 and the graph's bytes of atom_out and bond_aromatic are 255; n_atoms and n_bonds are the
+ *   (clamped) sizes of the two ranges.  Every entry of lig_ptr, bond_ptr and bond_index is clamped or checked before it is used as an
+ *   index: no content of the arrays makes the kernel read or write outside the buffers.  A graph writes its own (clamped) ranges; where
+ *   a malformed bond_ptr or lig_ptr makes two graphs' ranges overlap, which of the two writes lasts is not defined.  No atomics on memory;
+ *   nothing in the outputs depends on how the closure was scheduled.
+ * Returns 0, and 0 without a launch when B == 0.  CBGX_E_INVALID before any dereference or launch: negative counts, a NULL pointer with
+ *   a non-zero count (bond_index and bond_aromatic may be NULL when n_bonds == 0), lig_ptr the device cannot read. */
+#define CBGX_AROMATIC_MAX_ATOMS 256
+#define CBGX_AROMATIC_MAX_CYCLES 128
+#define CBGX_AROMATIC_GRAPH_COLS 10   /* n_atoms, n_bonds, n_cycles56, n_aromatic_cycles, n_flagged, n_closure, n_aromatic_atoms, n_aromatic_bonds, n_unsupported, status */
+#define CBGX_AROMATIC_TOO_MANY_ATOMS 1
+#define CBGX_AROMATIC_TOO_MANY_CYCLES 2
+#define CBGX_AROMATIC_BAD_BONDS 4
+#define CBGX_AROMATIC_NO_RINGS 8
+#define CBGX_AROMATIC_BOND_TYPES 256   /* ((type - 1) 8 + code_lo) 8 + code_hi, type 1 ... 4 */
+#define CBGX_AROMATIC_ANGLE_TYPES 8192 /* (((code_1 4 + (t_1 - 1)) 8 + code_c) 4 + (t_2 - 1)) 8 + code_2 */
+int cbgx_ligand_aromatic(const uint8_t *z_lig, const uint8_t *flag_lig, const uint8_t *atom_ring_min, const int32_t *lig_ptr, int n_lig,
+                         int n_graphs, const int32_t *bond_ptr, const int32_t *bond_index, int n_bonds, uint8_t *atom_out,
+                         uint8_t *bond_aromatic, int32_t *graph_out, void *stream);
+
 /* ---- distributions of sampled ligands: pair distances, bond lengths, bond angles (distributions.hip) -----------------------------------
  * The rest of the reference's geometry report (evaluate_scripts/evaluate_geom_single.py; repo/tools/geometry/eval_bond_length.py,
  *   eval_bond_angle.py): histograms that are compared with a dataset's by Jensen-Shannon distance.  Distances and element codes are those
