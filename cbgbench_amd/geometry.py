@@ -41,6 +41,7 @@ csrc/distributions.hip).  Angles are binned in cosine space against a table of c
 device.  Deviations: table bonds, so no aromatic type; every angle is counted once under its canonical type where the reference lists it
 under both orientations -- the same normalised profile.  ``distribution_jsd`` / ``jsd_against`` take the caller's own reference vectors:
 no dataset constants ship."""
+import collections
 import ctypes
 
 import numpy as np
@@ -83,6 +84,50 @@ def _csr(index, n_graphs, what):
     return torch.cat([counts.new_zeros(1), counts.cumsum(0)]).to(torch.int32).contiguous()
 
 
+def _gpu_only(dev, entry, kernels):
+    if dev.type != "cuda":
+        raise _native.NativeError(f"{entry} runs on the GPU ({kernels}): there is no CPU fallback")
+
+
+def _z_bytes(z):
+    """atomic numbers as bytes; anything outside a byte is no element the tables know: 0"""
+    return torch.where((z >= 0) & (z <= 255), z, torch.zeros_like(z)).to(torch.uint8).contiguous()
+
+
+def _ligand_arrays(x, z, batch, n_graphs, side="lig", dev=None):
+    """one side (``lig``; ``rec`` for the pocket of ``ligand_geometry``, which lives on ``dev``, the ligand's device) of every entry:
+    checks, CSR of the graph index, float32 coordinates, atomic numbers as bytes"""
+    dev = x.device if dev is None else dev
+    for name, t in ((f"x_{side}", x), (f"z_{side}", z), (f"{side}_batch", batch)):
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, x_lig on {dev}")
+    n = int(x.shape[0])
+    if tuple(x.shape) != (n, 3):
+        raise ValueError("coordinates must be [n, 3]")
+    if z.shape != (n,) or batch.shape != (n,):
+        raise ValueError("one atomic number and one graph index per atom")
+    return n, _csr(batch, n_graphs, f"{side}_batch"), x.to(torch.float32).contiguous(), _z_bytes(z)
+
+
+def _bond_ptr(bond_index, n_lig):
+    """[n_lig + 1] int32 as the bond entries define it: the bonds are sorted by their first atom, a is the first atom of
+    bond_ptr[a] ... bond_ptr[a + 1]"""
+    first = bond_index[0].to(torch.long).clamp(0, max(n_lig - 1, 0))
+    counts = torch.bincount(first, minlength=n_lig) if n_lig else first.new_zeros(0)
+    return torch.cat([counts.new_zeros(1), counts.cumsum(0)]).to(torch.int32).contiguous()
+
+
+def _state_atoms(c, mode, lig_batch, batch, dev):
+    """a sampling state's type indices (``c``: indices [n_lig] or scores [n_lig, C]: argmax) and atomic numbers, both int64 on ``dev``,
+    and the number of graphs: the batch's ``num_graphs`` when it has it, else what ``lig_batch`` shows"""
+    if mode not in _ATOMIC_NUMBER:
+        raise ValueError(mode)
+    typ = (c.argmax(-1) if c.dim() == 2 else c).to(dev).to(torch.long)
+    z = torch.tensor(_ATOMIC_NUMBER[mode], dtype=torch.long, device=dev)[typ]
+    n_graphs = int(batch["num_graphs"]) if "num_graphs" in batch else (int(lig_batch.max()) + 1 if lig_batch.numel() else 0)
+    return typ, z, n_graphs
+
+
 def ligand_geometry(x_lig, z_lig, lig_batch, x_rec, z_rec, rec_batch, n_graphs):
     """Stability and clash report of ``n_graphs`` ligands in their pockets, one launch on the tensors' current stream.
 
@@ -92,22 +137,10 @@ def ligand_geometry(x_lig, z_lig, lig_batch, x_rec, z_rec, rec_batch, n_graphs):
     ``graph_counts`` [n_graphs, 6] int32 (GRAPH_COLUMNS).  A ligand of more than MAX_LIGAND_ATOMS atoms raises ValueError.  There is no CPU
     path."""
     dev = x_lig.device
-    if dev.type != "cuda":
-        raise _native.NativeError("ligand_geometry runs on the GPU (cbgx_ligand_geometry): there is no CPU fallback")
+    _gpu_only(dev, "ligand_geometry", "cbgx_ligand_geometry")
     n_graphs = int(n_graphs)
-    for name, t in (("z_lig", z_lig), ("lig_batch", lig_batch), ("x_rec", x_rec), ("z_rec", z_rec), ("rec_batch", rec_batch)):
-        if t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, x_lig on {dev}")
-    n_lig, n_rec = int(x_lig.shape[0]), int(x_rec.shape[0])
-    if tuple(x_lig.shape) != (n_lig, 3) or tuple(x_rec.shape) != (n_rec, 3):
-        raise ValueError("coordinates must be [n, 3]")
-    if z_lig.shape != (n_lig,) or lig_batch.shape != (n_lig,) or z_rec.shape != (n_rec,) or rec_batch.shape != (n_rec,):
-        raise ValueError("one atomic number and one graph index per atom")
-    lig_ptr, rec_ptr = _csr(lig_batch, n_graphs, "lig_batch"), _csr(rec_batch, n_graphs, "rec_batch")
-    x_lig, x_rec = x_lig.to(torch.float32).contiguous(), x_rec.to(torch.float32).contiguous()
-    # atomic numbers as bytes; anything outside a byte is no element the tables know: 0
-    as_z = lambda z: torch.where((z >= 0) & (z <= 255), z, torch.zeros_like(z)).to(torch.uint8).contiguous()
-    z_lig, z_rec = as_z(z_lig), as_z(z_rec)
+    n_lig, lig_ptr, x_lig, z_lig = _ligand_arrays(x_lig, z_lig, lig_batch, n_graphs)
+    n_rec, rec_ptr, x_rec, z_rec = _ligand_arrays(x_rec, z_rec, rec_batch, n_graphs, "rec", dev)
     nr_bonds = torch.empty(n_lig, dtype=torch.int32, device=dev)
     flags = torch.empty(n_lig, dtype=torch.uint8, device=dev)
     graph_counts = torch.empty(n_graphs, len(GRAPH_COLUMNS), dtype=torch.int32, device=dev)
@@ -122,13 +155,9 @@ def batch_geometry(batch, x, c, lig_batch, mode):
     """``ligand_geometry`` of a sampling state (``x`` [n_lig, 3], ``c`` type indices [n_lig] or scores [n_lig, C]: argmax, ``lig_batch``)
     against the batch's own pocket (``protein_pos``, ``protein_element``, ``protein_element_batch``), in the frame both share.  ``mode``:
     the atom-type vocabulary ('basic' / 'add_aromatic') that maps a type index to its atomic number."""
-    if mode not in _ATOMIC_NUMBER:
-        raise ValueError(mode)
-    typ = c.argmax(-1) if c.dim() == 2 else c
-    z = torch.tensor(_ATOMIC_NUMBER[mode], dtype=torch.long, device=x.device)[typ.to(torch.long)]
-    n_graphs = int(batch["num_graphs"]) if "num_graphs" in batch else int(max(
-        int(lig_batch.max()) if lig_batch.numel() else -1,
-        int(batch["protein_element_batch"].max()) if batch["protein_element_batch"].numel() else -1)) + 1
+    _, z, n_graphs = _state_atoms(c, mode, lig_batch, batch, x.device)
+    if "num_graphs" not in batch and batch["protein_element_batch"].numel():     # (a pocket whose ligand is empty counts too)
+        n_graphs = max(n_graphs, int(batch["protein_element_batch"].max()) + 1)
     return ligand_geometry(x, z, lig_batch, batch["protein_pos"], batch["protein_element"], batch["protein_element_batch"], n_graphs)
 
 
@@ -138,11 +167,20 @@ COUNT_KEYS = ("n_mol", "n_atoms", "n_stable", "n_mol_stable", "n_inter_clash_ato
 RATIOS = ("mol_stable", "atm_stable", "inter_clash_atom_ratio", "intra_clash_atom_ratio", "clash_mol_ratio")
 
 
-def job_totals(graph_counts):
-    """per-molecule counts ``graph_counts`` [n_mol, 6] (GRAPH_COLUMNS; any array-like) -> the integer totals, in COUNT_KEYS order"""
+def _counts(graph_counts, columns):
+    """per-molecule counts (a tensor or any array-like) as int64 [n_mol, len(columns)]"""
     if isinstance(graph_counts, torch.Tensor):
         graph_counts = graph_counts.cpu().numpy()
-    gc = np.asarray(graph_counts, dtype=np.int64).reshape(-1, len(GRAPH_COLUMNS))
+    return np.asarray(graph_counts, dtype=np.int64).reshape(-1, len(columns))
+
+
+def _ratio(a, b):
+    return a / b if b else float("nan")
+
+
+def job_totals(graph_counts):
+    """per-molecule counts ``graph_counts`` [n_mol, 6] (GRAPH_COLUMNS; any array-like) -> the integer totals, in COUNT_KEYS order"""
+    gc = _counts(graph_counts, GRAPH_COLUMNS)
     n_atoms, n_stable, n_mol_stable, n_inter, n_intra, n_norad = (int(v) for v in gc.sum(0))
     return [int(gc.shape[0]), n_atoms, n_stable, n_mol_stable, n_inter, n_intra, int((gc[:, 3] > 0).sum()), n_norad]
 
@@ -150,11 +188,10 @@ def job_totals(graph_counts):
 def summarise_totals(totals):
     """the five ratios (RATIOS) of integer totals in COUNT_KEYS order, and the totals as ``counts``; a ratio over nothing is nan"""
     c = {k: int(v) for k, v in zip(COUNT_KEYS, totals)}
-    ratio = lambda a, b: a / b if b else float("nan")
-    return {"mol_stable": ratio(c["n_mol_stable"], c["n_mol"]), "atm_stable": ratio(c["n_stable"], c["n_atoms"]),
-            "inter_clash_atom_ratio": ratio(c["n_inter_clash_atoms"], c["n_atoms"]),
-            "intra_clash_atom_ratio": ratio(c["n_intra_clash_atoms"], c["n_atoms"]),
-            "clash_mol_ratio": ratio(c["n_clash_mol"], c["n_mol"]), "counts": c}
+    return {"mol_stable": _ratio(c["n_mol_stable"], c["n_mol"]), "atm_stable": _ratio(c["n_stable"], c["n_atoms"]),
+            "inter_clash_atom_ratio": _ratio(c["n_inter_clash_atoms"], c["n_atoms"]),
+            "intra_clash_atom_ratio": _ratio(c["n_intra_clash_atoms"], c["n_atoms"]),
+            "clash_mol_ratio": _ratio(c["n_clash_mol"], c["n_mol"]), "counts": c}
 
 
 def summarise(graph_counts):
@@ -178,20 +215,9 @@ def ligand_bonds(x_lig, z_lig, lig_batch, n_graphs):
     ligand-LOCAL index of the atom's connected component; ``graph_counts`` [n_graphs, 6] int32 (BOND_GRAPH_COLUMNS).  A ligand of more
     than MAX_LIGAND_ATOMS atoms raises ValueError.  There is no CPU path."""
     dev = x_lig.device
-    if dev.type != "cuda":
-        raise _native.NativeError("ligand_bonds runs on the GPU (cbgx_ligand_bonds_count / _fill): there is no CPU fallback")
+    _gpu_only(dev, "ligand_bonds", "cbgx_ligand_bonds_count / _fill")
     n_graphs = int(n_graphs)
-    for name, t in (("z_lig", z_lig), ("lig_batch", lig_batch)):
-        if t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, x_lig on {dev}")
-    n_lig = int(x_lig.shape[0])
-    if tuple(x_lig.shape) != (n_lig, 3):
-        raise ValueError("coordinates must be [n, 3]")
-    if z_lig.shape != (n_lig,) or lig_batch.shape != (n_lig,):
-        raise ValueError("one atomic number and one graph index per atom")
-    lig_ptr = _csr(lig_batch, n_graphs, "lig_batch")
-    x_lig = x_lig.to(torch.float32).contiguous()
-    z_lig = torch.where((z_lig >= 0) & (z_lig <= 255), z_lig, torch.zeros_like(z_lig)).to(torch.uint8).contiguous()
+    n_lig, lig_ptr, x_lig, z_lig = _ligand_arrays(x_lig, z_lig, lig_batch, n_graphs)
     deg_up = torch.empty(n_lig, dtype=torch.int32, device=dev)
     fragment = torch.empty(n_lig, dtype=torch.int32, device=dev)
     graph_counts = torch.empty(n_graphs, len(BOND_GRAPH_COLUMNS), dtype=torch.int32, device=dev)
@@ -216,11 +242,7 @@ def ligand_bonds(x_lig, z_lig, lig_batch, n_graphs):
 def batch_bonds(batch, x, c, lig_batch, mode):
     """``ligand_bonds`` of a sampling state (``x`` [n_lig, 3], ``c`` type indices [n_lig] or scores [n_lig, C]: argmax, ``lig_batch``);
     ``batch`` gives ``num_graphs`` when it has it.  ``mode``: the atom-type vocabulary that maps a type index to its atomic number."""
-    if mode not in _ATOMIC_NUMBER:
-        raise ValueError(mode)
-    typ = c.argmax(-1) if c.dim() == 2 else c
-    z = torch.tensor(_ATOMIC_NUMBER[mode], dtype=torch.long, device=x.device)[typ.to(torch.long)]
-    n_graphs = int(batch["num_graphs"]) if "num_graphs" in batch else (int(lig_batch.max()) + 1 if lig_batch.numel() else 0)
+    _, z, n_graphs = _state_atoms(c, mode, lig_batch, batch, x.device)
     return ligand_bonds(x, z, lig_batch, n_graphs)
 
 
@@ -231,9 +253,7 @@ BOND_RATIOS = ("connected_mol_ratio", "largest_fragment_atom_ratio", "fragments_
 def bond_totals(graph_counts):
     """per-molecule counts ``graph_counts`` [n_mol, 6] (BOND_GRAPH_COLUMNS; any array-like) -> the integer totals, in BOND_COUNT_KEYS
     order; a molecule is connected iff n_fragments == 1"""
-    if isinstance(graph_counts, torch.Tensor):
-        graph_counts = graph_counts.cpu().numpy()
-    gc = np.asarray(graph_counts, dtype=np.int64).reshape(-1, len(BOND_GRAPH_COLUMNS))
+    gc = _counts(graph_counts, BOND_GRAPH_COLUMNS)
     n_atoms, n_bonds, _, n_frag, n_largest, n_cycles = (int(v) for v in gc.sum(0))
     return [int(gc.shape[0]), n_atoms, n_bonds, int((gc[:, 3] == 1).sum()), n_largest, n_frag, n_cycles]
 
@@ -241,11 +261,10 @@ def bond_totals(graph_counts):
 def summarise_bond_totals(totals):
     """the five ratios (BOND_RATIOS) of integer totals in BOND_COUNT_KEYS order, and the totals as ``counts``; a ratio over nothing is nan"""
     c = {k: int(v) for k, v in zip(BOND_COUNT_KEYS, totals)}
-    ratio = lambda a, b: a / b if b else float("nan")
-    return {"connected_mol_ratio": ratio(c["n_connected_mol"], c["n_mol"]),
-            "largest_fragment_atom_ratio": ratio(c["n_largest_fragment_atoms"], c["n_atoms"]),
-            "fragments_per_mol": ratio(c["n_fragments"], c["n_mol"]), "cycles_per_mol": ratio(c["n_cycles"], c["n_mol"]),
-            "bonds_per_atom": ratio(c["n_bonds"], c["n_atoms"]), "counts": c}
+    return {"connected_mol_ratio": _ratio(c["n_connected_mol"], c["n_mol"]),
+            "largest_fragment_atom_ratio": _ratio(c["n_largest_fragment_atoms"], c["n_atoms"]),
+            "fragments_per_mol": _ratio(c["n_fragments"], c["n_mol"]), "cycles_per_mol": _ratio(c["n_cycles"], c["n_mol"]),
+            "bonds_per_atom": _ratio(c["n_bonds"], c["n_atoms"]), "counts": c}
 
 
 def summarise_bonds(graph_counts):
@@ -277,8 +296,7 @@ def ligand_rings(bond_index, lig_batch, n_graphs):
     is non-zero (RINGS_*), its columns from n_cycles to n_ring_atoms are -1 and its atoms' ``atom_ring_min`` 255.  There is no CPU
     path."""
     dev = bond_index.device
-    if dev.type != "cuda":
-        raise _native.NativeError("ligand_rings runs on the GPU (cbgx_ligand_rings): there is no CPU fallback")
+    _gpu_only(dev, "ligand_rings", "cbgx_ligand_rings")
     n_graphs = int(n_graphs)
     if lig_batch.device != dev:
         raise ValueError(f"lig_batch is on {lig_batch.device}, bond_index on {dev}")
@@ -288,11 +306,7 @@ def ligand_rings(bond_index, lig_batch, n_graphs):
     if lig_batch.shape != (n_lig,):
         raise ValueError("one graph index per atom")
     lig_ptr = _csr(lig_batch, n_graphs, "lig_batch")
-    bond_index = bond_index.to(torch.int32).contiguous()
-    # bond_ptr as the bond entries define it: the bonds are sorted by their first atom, a is the first atom of bond_ptr[a] ... bond_ptr[a + 1]
-    first = bond_index[0].to(torch.long).clamp(0, max(n_lig - 1, 0))
-    counts = torch.bincount(first, minlength=n_lig) if n_lig else first.new_zeros(0)
-    bond_ptr = torch.cat([counts.new_zeros(1), counts.cumsum(0)]).to(torch.int32).contiguous()
+    bond_index, bond_ptr = bond_index.to(torch.int32).contiguous(), _bond_ptr(bond_index, n_lig)
     atom_ring_min = torch.empty(n_lig, dtype=torch.uint8, device=dev)
     graph_counts = torch.empty(n_graphs, len(RING_GRAPH_COLUMNS), dtype=torch.int32, device=dev)
     p = _native.ptr
@@ -318,9 +332,7 @@ RING_RATIOS = (tuple(f"ring_mol_ratio_{k}" for k in RING_SIZES) + tuple(f"rings_
 def ring_totals(graph_counts):
     """per-molecule counts ``graph_counts`` [n_mol, 13] (RING_GRAPH_COLUMNS; any array-like) -> the integer totals, in RING_COUNT_KEYS
     order.  Everything but n_mol and n_mol_over_limit is summed over the evaluated molecules (status == 0) only; n_rings = n_cycles"""
-    if isinstance(graph_counts, torch.Tensor):
-        graph_counts = graph_counts.cpu().numpy()
-    gc = np.asarray(graph_counts, dtype=np.int64).reshape(-1, len(RING_GRAPH_COLUMNS))
+    gc = _counts(graph_counts, RING_GRAPH_COLUMNS)
     ok = gc[gc[:, -1] == 0]
     sizes = ok[:, 3:3 + len(RING_SIZES) + 1]                    # rings_3 ... rings_9, n_rings_larger
     return ([int(gc.shape[0]), int(ok.shape[0]), int(gc.shape[0] - ok.shape[0]), int(ok[:, 0].sum()), int(ok[:, -2].sum()),
@@ -335,14 +347,13 @@ def summarise_ring_totals(totals):
     eval_ring_type_ratio); ring_size_distribution_k, k = 3 ... 8: the share of size k among the rings of those six sizes
     (eval_ring_type_distribution); macrocycle_mol_ratio: the share of molecules with a ring above 9; ring_atom_ratio: ring atoms / atoms"""
     c = {k: int(v) for k, v in zip(RING_COUNT_KEYS, totals)}
-    ratio = lambda a, b: a / b if b else float("nan")
     n_mol = c["n_mol_evaluated"]
     in_six = sum(c[f"n_rings_{k}"] for k in range(3, 9))
-    out = {f"ring_mol_ratio_{k}": ratio(c[f"n_mol_with_ring_{k}"], n_mol) for k in RING_SIZES}
-    out.update({f"rings_per_mol_{k}": ratio(c[f"n_rings_{k}"], n_mol) for k in range(3, 9)})
-    out.update({f"ring_size_distribution_{k}": ratio(c[f"n_rings_{k}"], in_six) for k in range(3, 9)})
-    out["macrocycle_mol_ratio"] = ratio(c["n_mol_with_larger_ring"], n_mol)
-    out["ring_atom_ratio"] = ratio(c["n_ring_atoms"], c["n_atoms"])
+    out = {f"ring_mol_ratio_{k}": _ratio(c[f"n_mol_with_ring_{k}"], n_mol) for k in RING_SIZES}
+    out.update({f"rings_per_mol_{k}": _ratio(c[f"n_rings_{k}"], n_mol) for k in range(3, 9)})
+    out.update({f"ring_size_distribution_{k}": _ratio(c[f"n_rings_{k}"], in_six) for k in range(3, 9)})
+    out["macrocycle_mol_ratio"] = _ratio(c["n_mol_with_larger_ring"], n_mol)
+    out["ring_atom_ratio"] = _ratio(c["n_ring_atoms"], c["n_atoms"])
     out["counts"] = c
     return out
 
@@ -393,8 +404,7 @@ def ligand_aromatic(z_lig, flag_lig, lig_batch, n_graphs, bonds, rings):
     reference applies each once, in OpenBabel's order: its result is contained in this one); a bond is aromatic only as an edge of an
     aromatic cycle (the reference marks every bond with two aromatic ends, e.g. the link of biphenyl).  There is no CPU path."""
     dev = z_lig.device
-    if dev.type != "cuda":
-        raise _native.NativeError("ligand_aromatic runs on the GPU (cbgx_ligand_aromatic): there is no CPU fallback")
+    _gpu_only(dev, "ligand_aromatic", "cbgx_ligand_aromatic")
     n_graphs = int(n_graphs)
     bond_index, bond_order, ring_min = bonds["bond_index"], bonds["bond_order"], rings["atom_ring_min"]
     for name, t in (("flag_lig", flag_lig), ("lig_batch", lig_batch), ("bond_index", bond_index), ("bond_order", bond_order),
@@ -409,13 +419,10 @@ def ligand_aromatic(z_lig, flag_lig, lig_batch, n_graphs, bonds, rings):
     if bond_order.shape != (n_bonds,):
         raise ValueError("one bond_order per bond")
     lig_ptr = _csr(lig_batch, n_graphs, "lig_batch")
-    z_lig = torch.where((z_lig >= 0) & (z_lig <= 255), z_lig, torch.zeros_like(z_lig)).to(torch.uint8).contiguous()
+    z_lig = _z_bytes(z_lig)
     flag_lig = (flag_lig != 0).to(torch.uint8).contiguous()
     ring_min = ring_min.to(torch.uint8).contiguous()
-    bond_index = bond_index.to(torch.int32).contiguous()
-    first = bond_index[0].to(torch.long).clamp(0, max(n_lig - 1, 0))          # bond_ptr as the bond entries define it (ligand_rings)
-    counts = torch.bincount(first, minlength=n_lig) if n_lig else first.new_zeros(0)
-    bond_ptr = torch.cat([counts.new_zeros(1), counts.cumsum(0)]).to(torch.int32).contiguous()
+    bond_index, bond_ptr = bond_index.to(torch.int32).contiguous(), _bond_ptr(bond_index, n_lig)
     atom_out = torch.empty(n_lig, dtype=torch.uint8, device=dev)
     bond_out = torch.empty(n_bonds, dtype=torch.uint8, device=dev)
     graph_counts = torch.empty(n_graphs, len(AROMATIC_GRAPH_COLUMNS), dtype=torch.int32, device=dev)
@@ -441,12 +448,11 @@ def batch_aromatic(batch, x, c, lig_batch, mode, bonds=None, rings=None):
         bonds = batch_bonds(batch, x, c, lig_batch, mode)
     dev = bonds["bond_index"].device
     lig_batch = lig_batch.to(dev)
+    typ, z, n_graphs = _state_atoms(c, mode, lig_batch, {"num_graphs": bonds["graph_counts"].shape[0]}, dev)
     if rings is None:
-        rings = ligand_rings(bonds["bond_index"], lig_batch, bonds["graph_counts"].shape[0])
-    typ = (c.argmax(-1) if c.dim() == 2 else c).to(dev).to(torch.long)
-    z = torch.tensor(_ATOMIC_NUMBER[mode], dtype=torch.long, device=dev)[typ]
+        rings = ligand_rings(bonds["bond_index"], lig_batch, n_graphs)
     flag = torch.tensor(_AROMATIC[mode], dtype=torch.bool, device=dev)[typ]
-    return ligand_aromatic(z, flag, lig_batch, bonds["graph_counts"].shape[0], bonds, rings)
+    return ligand_aromatic(z, flag, lig_batch, n_graphs, bonds, rings)
 
 
 AROMATIC_COUNT_KEYS = ("n_mol", "n_mol_evaluated", "n_mol_over_limit", "n_atoms", "n_bonds", "n_cycles56", "n_aromatic_cycles",
@@ -458,9 +464,7 @@ AROMATIC_RATIOS = ("aromatic_mol_ratio", "aromatic_rings_per_mol", "aromatic_cyc
 def aromatic_totals(graph_counts):
     """per-molecule counts ``graph_counts`` [n_mol, 10] (AROMATIC_GRAPH_COLUMNS; any array-like) -> the integer totals, in
     AROMATIC_COUNT_KEYS order.  Everything but n_mol and n_mol_over_limit is summed over the evaluated molecules (status == 0) only"""
-    if isinstance(graph_counts, torch.Tensor):
-        graph_counts = graph_counts.cpu().numpy()
-    gc = np.asarray(graph_counts, dtype=np.int64).reshape(-1, len(AROMATIC_GRAPH_COLUMNS))
+    gc = _counts(graph_counts, AROMATIC_GRAPH_COLUMNS)
     ok = gc[gc[:, -1] == 0]
     return ([int(gc.shape[0]), int(ok.shape[0]), int(gc.shape[0] - ok.shape[0])] + [int(v) for v in ok[:, :9].sum(0)]
             + [int((ok[:, 3] > 0).sum())])
@@ -473,19 +477,28 @@ def summarise_aromatic_totals(totals):
     aromatic atoms / atoms, aromatic bonds / bonds; unsupported_flag_ratio: n_unsupported / n_flagged, how often the model emitted an
     aromatic type where the geometry built no ring to carry it"""
     c = {k: int(v) for k, v in zip(AROMATIC_COUNT_KEYS, totals)}
-    ratio = lambda a, b: a / b if b else float("nan")
-    return {"aromatic_mol_ratio": ratio(c["n_aromatic_mol"], c["n_mol_evaluated"]),
-            "aromatic_rings_per_mol": ratio(c["n_aromatic_cycles"], c["n_mol_evaluated"]),
-            "aromatic_cycle_share": ratio(c["n_aromatic_cycles"], c["n_cycles56"]),
-            "aromatic_atom_ratio": ratio(c["n_aromatic_atoms"], c["n_atoms"]),
-            "aromatic_bond_ratio": ratio(c["n_aromatic_bonds"], c["n_bonds"]),
-            "unsupported_flag_ratio": ratio(c["n_unsupported"], c["n_flagged"]), "counts": c}
+    return {"aromatic_mol_ratio": _ratio(c["n_aromatic_mol"], c["n_mol_evaluated"]),
+            "aromatic_rings_per_mol": _ratio(c["n_aromatic_cycles"], c["n_mol_evaluated"]),
+            "aromatic_cycle_share": _ratio(c["n_aromatic_cycles"], c["n_cycles56"]),
+            "aromatic_atom_ratio": _ratio(c["n_aromatic_atoms"], c["n_atoms"]),
+            "aromatic_bond_ratio": _ratio(c["n_aromatic_bonds"], c["n_bonds"]),
+            "unsupported_flag_ratio": _ratio(c["n_unsupported"], c["n_flagged"]), "counts": c}
 
 
 def summarise_aromatic(graph_counts):
     """aromatic statistics of a set of molecules from integer per-molecule counts (``graph_counts`` [n_mol, 10], AROMATIC_GRAPH_COLUMNS):
     see ``summarise_aromatic_totals``"""
     return summarise_aromatic_totals(aromatic_totals(graph_counts))
+
+
+# the four reports that are integer counts per molecule, for a driver that treats them alike: per-molecule columns -> totals (what ranks
+# add up; count_keys) -> ratios and ``counts``
+CountReport = collections.namedtuple("CountReport", "name graph_columns count_keys ratios totals summarise_totals")
+COUNT_REPORTS = (CountReport("geometry", GRAPH_COLUMNS, COUNT_KEYS, RATIOS, job_totals, summarise_totals),
+                 CountReport("bonds", BOND_GRAPH_COLUMNS, BOND_COUNT_KEYS, BOND_RATIOS, bond_totals, summarise_bond_totals),
+                 CountReport("rings", RING_GRAPH_COLUMNS, RING_COUNT_KEYS, RING_RATIOS, ring_totals, summarise_ring_totals),
+                 CountReport("aromatic", AROMATIC_GRAPH_COLUMNS, AROMATIC_COUNT_KEYS, AROMATIC_RATIOS, aromatic_totals,
+                             summarise_aromatic_totals))
 
 
 # ---- SDF (V2000) records of samples: host only -----------------------------------------------------------------------------------------
@@ -567,23 +580,6 @@ def _edges(edges, what, limit, decreasing=False):
     return e
 
 
-def _ligand_arrays(x_lig, z_lig, lig_batch, n_graphs):
-    """the ligand side of every entry: checks, lig_ptr, float32 coordinates, atomic numbers as bytes"""
-    dev = x_lig.device
-    for name, t in (("z_lig", z_lig), ("lig_batch", lig_batch)):
-        if t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, x_lig on {dev}")
-    n_lig = int(x_lig.shape[0])
-    if tuple(x_lig.shape) != (n_lig, 3):
-        raise ValueError("coordinates must be [n, 3]")
-    if z_lig.shape != (n_lig,) or lig_batch.shape != (n_lig,):
-        raise ValueError("one atomic number and one graph index per atom")
-    lig_ptr = _csr(lig_batch, n_graphs, "lig_batch")
-    x_lig = x_lig.to(torch.float32).contiguous()
-    z_lig = torch.where((z_lig >= 0) & (z_lig <= 255), z_lig, torch.zeros_like(z_lig)).to(torch.uint8).contiguous()
-    return n_lig, lig_ptr, x_lig, z_lig
-
-
 def ligand_pair_hist(x_lig, z_lig, lig_batch, n_graphs, edges_all=None, edges_cc=None):
     """Pair-distance histograms of ``n_graphs`` ligands, one launch (``cbgx_ligand_pair_hist``, csrc/distributions.hip; the definition is
     in include/cbgx.h) on the tensors' current stream: the counterpart of ``pair_distance_from_pos_v`` + ``get_pair_length_profile``
@@ -594,8 +590,7 @@ def ligand_pair_hist(x_lig, z_lig, lig_batch, n_graphs, edges_all=None, edges_cc
     ``default_pair_edges()``.  Returns ``pair_hist`` [n_graphs, 2, E_max + 1] int32 on the device: a pair takes part iff d <
     edges[-1], its bin is ``np.searchsorted(edges, d)``.  There is no CPU path."""
     dev = x_lig.device
-    if dev.type != "cuda":
-        raise _native.NativeError("ligand_pair_hist runs on the GPU (cbgx_ligand_pair_hist): there is no CPU fallback")
+    _gpu_only(dev, "ligand_pair_hist", "cbgx_ligand_pair_hist")
     n_graphs = int(n_graphs)
     n_lig, lig_ptr, x_lig, z_lig = _ligand_arrays(x_lig, z_lig, lig_batch, n_graphs)
     ea, ec = default_pair_edges()
@@ -639,8 +634,7 @@ def ligand_angles(x_lig, z_lig, lig_batch, n_graphs, bonds, cos_edges=None):
     [n_graphs, 5] int32 (DISTRIBUTION_GRAPH_COLUMNS).  A graph of more than MAX_ANGLES_PER_GRAPH angles is not an error: its status is
     DISTRIBUTIONS_TOO_MANY_ANGLES, it has no angles in the list and n_angles = n_degenerate_angles = 0.  There is no CPU path."""
     dev = x_lig.device
-    if dev.type != "cuda":
-        raise _native.NativeError("ligand_angles runs on the GPU (cbgx_ligand_angles): there is no CPU fallback")
+    _gpu_only(dev, "ligand_angles", "cbgx_ligand_angles")
     n_graphs = int(n_graphs)
     n_lig, lig_ptr, x_lig, z_lig = _ligand_arrays(x_lig, z_lig, lig_batch, n_graphs)
     ce = _edges(default_cos_edges() if cos_edges is None else cos_edges, "cos_edges", MAX_ANGLE_EDGES, decreasing=True)
@@ -727,15 +721,11 @@ def batch_distributions(batch, x, c, lig_batch, mode, bonds=None, aromatic=None)
     ``aromatic``: what ``batch_aromatic`` returned for the same state and bonds; ``bond_type``, ``angle_type`` and both sparse
     histograms then use the four-order type codes (``bond_type_code`` / ``angle_type_code`` with ``n_orders=4``: an aromatic bond is type
     4 and no longer counted under its order).  With None (default) every output is what it is without the argument."""
-    if mode not in _ATOMIC_NUMBER:
-        raise ValueError(mode)
     if bonds is None:
         bonds = batch_bonds(batch, x, c, lig_batch, mode)
     dev = bonds["bond_index"].device
-    x, c, lig_batch = x.to(dev), c.to(dev), lig_batch.to(dev)
-    typ = c.argmax(-1) if c.dim() == 2 else c
-    z = torch.tensor(_ATOMIC_NUMBER[mode], dtype=torch.long, device=dev)[typ.to(torch.long)]
-    n_graphs = int(bonds["graph_counts"].shape[0])
+    x, lig_batch = x.to(dev), lig_batch.to(dev)
+    _, z, n_graphs = _state_atoms(c, mode, lig_batch, {"num_graphs": bonds["graph_counts"].shape[0]}, dev)
     out = ligand_angles(x, z, lig_batch, n_graphs, bonds)
     out["pair_hist"] = ligand_pair_hist(x, z, lig_batch, n_graphs)
     edges = torch.from_numpy(_edges(default_bond_edges(), "bond edges", 255)).to(dev)

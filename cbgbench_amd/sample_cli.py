@@ -39,15 +39,15 @@ and bond-angle profiles are then keyed by four bond types (``6:6``, ``6:6:6``).
 table-bond orders otherwise (``geometry.sdf_record``; host side, no RDKit).
 A checkpoint is the reference's format: ``{'config': ..., 'model': state_dict}`` (``sample.py:153-156``)."""
 import argparse
-import json
 import os
 import time
 
 import numpy as np
 import torch
 
-from . import geometry, get_model, load_config, priors, set_num_atom_type, sharding, synthetic
+from . import get_model, load_config, priors, set_num_atom_type, sharding, synthetic
 from .config import NUM_ATOM_TYPES, get_atomic_number_from_index, is_aromatic_from_index, load_checkpoint_file
+from .sample_reports import SampleReports
 
 
 def build_pocket_batch(pockets, num_samples, rng, num_classes, prior_types="uniform", device="cpu", num_dist=None,
@@ -129,17 +129,6 @@ def split_samples(x, c, batch_idx, n_graphs, mode="add_aromatic"):
     return out
 
 
-def load_reference_distributions(path):
-    """``--distributions_reference``: {key: vector} from a ``.npz`` (np.savez(path, **{'6-6': v, ...})) or a ``torch.save``d dict"""
-    if path.endswith(".npz"):
-        with np.load(path) as f:
-            return {k: np.asarray(f[k], np.float64) for k in f.files}
-    raw = torch.load(path, map_location="cpu", weights_only=False)
-    if not isinstance(raw, dict):
-        raise SystemExit(f"sample_cli: {path} does not hold a dict of reference distributions")
-    return {k: np.asarray(v, np.float64) for k, v in raw.items()}
-
-
 def decode_mode(plan_mode, config_mode, num_classes):
     """the atom-type vocabulary the samples are decoded with (sample.py:211-214 passes the transform's ``mode`` on to
     ``reconstruct_mol``): the ``mode`` of the config's assign_atomtype / assign_genatomtype transform (``SamplingPlan.mode``), else the
@@ -153,12 +142,10 @@ def decode_mode(plan_mode, config_mode, num_classes):
 
 def main(argv=None, stats=None):
     """``stats`` (optional dict): filled with the wall seconds of the phases (setup = config + model + weights, batch = prior
-    construction, sample = model.sample incl. the trajectory download, write = per-pocket records and files; with ``--geometry``
-    also geometry = the report's launches, a part of write; with ``--bonds`` also bonds = the bond report's launches and downloads, a part
-    of write; with ``--rings`` also rings = the ring report's launch and downloads -- and the bond launches when ``--bonds`` is absent --,
-    a part of write; with ``--distributions`` also distributions = that report's launches and downloads -- and the bond launches when
-    ``--bonds`` is absent --, a part of write; with ``--aromatic`` also aromatic = that report's launch and downloads -- and the bond and ring
-    launches when ``--bonds`` / ``--rings`` are absent --, a part of write)."""
+    construction, sample = model.sample incl. the trajectory download, write = per-pocket records and files) and, for every requested report
+    (geometry, bonds, rings, aromatic, distributions: evaluated in that order), its own launches and downloads, a part of write: the bond
+    list and the ring report are made once per batch, and where they were not asked for their time goes to the first requested report
+    in that order that needs them (cbgbench_amd/sample_reports.py)."""
     t_phase = time.perf_counter()
     phases = {"setup": 0.0, "batch": 0.0, "sample": 0.0, "write": 0.0}
 
@@ -268,26 +255,9 @@ def main(argv=None, stats=None):
         dev = torch.device("cuda", local)
     else:
         dev = torch.device(args.device)
-    if args.geometry and dev.type != "cuda":
-        raise SystemExit("sample_cli: --geometry runs on the GPU (cbgx_ligand_geometry has no CPU fallback)")
-    if args.bonds and dev.type != "cuda":
-        raise SystemExit("sample_cli: --bonds runs on the GPU (cbgx_ligand_bonds_count / _fill have no CPU fallback)")
-    if args.rings and dev.type != "cuda":
-        raise SystemExit("sample_cli: --rings runs on the GPU (cbgx_ligand_rings has no CPU fallback)")
-    if args.distributions and dev.type != "cuda":
-        raise SystemExit("sample_cli: --distributions runs on the GPU (cbgx_ligand_pair_hist / cbgx_ligand_angles have no CPU fallback)")
-    if args.aromatic:
-        # refused before any model is built, on any device: the report starts from the aromatic atom types
-        atom_mode = decode_mode(priors.SamplingPlan.from_config(config).mode, config.get("mode", None), config.model.num_atomtype)
-        if atom_mode != "add_aromatic":
-            raise SystemExit(f"sample_cli: --aromatic starts from the model's aromatic flags: atom types of mode 'add_aromatic', "
-                             f"not {atom_mode!r}")
-    if args.aromatic and dev.type != "cuda":
-        raise SystemExit("sample_cli: --aromatic runs on the GPU (cbgx_ligand_aromatic has no CPU fallback)")
-    if args.sdf and dev.type != "cuda":
-        raise SystemExit("sample_cli: --sdf takes its bonds from the GPU (cbgx_ligand_bonds_count / _fill have no CPU fallback)")
-    if args.distributions_reference and not args.distributions:
-        raise SystemExit("sample_cli: --distributions_reference needs --distributions")
+    reports = SampleReports.from_args(args)
+    reports.refuse(dev, lambda: decode_mode(priors.SamplingPlan.from_config(config).mode, config.get("mode", None),
+                                            config.model.num_atomtype))
 
     ckpt_path = args.checkpoint or config.model.get("checkpoint", None)
     if ckpt_path and os.path.exists(ckpt_path):
@@ -341,171 +311,32 @@ def main(argv=None, stats=None):
     else:
         torch.manual_seed(args.seed + rank)             # independent noise streams per shard
         rng = np.random.default_rng([args.seed, rank])
-    geometry_seconds, job_counts = [0.0], []             # --geometry: wall time of the report, per-sample counts of this rank
-    bonds_seconds, job_bond_counts = [0.0], []           # --bonds: likewise
-    rings_seconds, job_ring_counts = [0.0], []           # --rings: likewise
-    # --distributions: likewise; the pockets' flat integer totals are added up as they come (one is 3.5 MB)
-    n_orders = 4 if args.aromatic else 3                 # --aromatic --distributions: bond and angle types with the aromatic type
-    distributions_seconds, job_distribution_totals = [0.0], np.zeros(geometry.distribution_totals_length(n_orders=n_orders), np.int64)
-    aromatic_seconds, job_aromatic_counts = [0.0], []    # --aromatic: likewise
-    sdf_left_out = [0, 0]                                # --sdf: samples left out of their file, samples written
 
     def write_results(ids, traj, batch):
         # sample.py:198-201 hands traj[0] to the reconstruction -- for targetdiff / diffbp that is the state entering the
         # last step, not traj[-1]; kept as the default for drop-in outputs, --final_state selects traj[-1]
         x, c, bidx = traj[-1] if (args.final_state and config.model.type != "diffsbdd") else traj[0]
-        geo = None
-        if args.geometry:
-            # the state the records hold, in the sampling frame (before ligand_translation), against the batch's own pocket
-            t_geo = time.perf_counter()
-            pocket = {k: batch[k].to(dev) for k in ("protein_pos", "protein_element", "protein_element_batch")}
-            pocket["num_graphs"] = len(ids) * num_samples
-            geo = geometry.batch_geometry(pocket, x.to(dev), c.to(dev), bidx.to(dev), mode)
-            geo = {k: v.cpu() for k, v in geo.items()}       # (the download waits for the launch)
-            geometry_seconds[0] += time.perf_counter() - t_geo
-        bonds = bonds_dev = None
-        if args.bonds:
-            # the same state in the same frame; proteins play no part
-            t_bonds = time.perf_counter()
-            bonds_dev = geometry.batch_bonds({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode)
-            bonds = {k: v.cpu() for k, v in bonds_dev.items()}
-            bonds_seconds[0] += time.perf_counter() - t_bonds
-        rings = rings_dev = None
-        if args.rings:
-            # the same state again, on the bond list of --bonds when there is one (else the bonds are made here and not written)
-            t_rings = time.perf_counter()
-            rings_dev = geometry.batch_rings({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode,
-                                             bonds=bonds_dev)
-            rings = {k: v.cpu() for k, v in rings_dev.items()}
-            rings_seconds[0] += time.perf_counter() - t_rings
-        aro = aro_dev = aro_bonds = None
-        if args.aromatic:
-            # the same state again, on the bond list of --bonds and the ring report of --rings when there are such (else they are made here
-            # and not written)
-            t_aro = time.perf_counter()
-            aro_bonds = bonds_dev if bonds_dev is not None else geometry.batch_bonds({"num_graphs": len(ids) * num_samples}, x.to(dev),
-                                                                                     c.to(dev), bidx.to(dev), mode)
-            aro_dev = geometry.batch_aromatic({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode,
-                                              bonds=aro_bonds, rings=rings_dev)
-            aro = {k: v.cpu() for k, v in aro_dev.items()}
-            aromatic_seconds[0] += time.perf_counter() - t_aro
-        dists = None
-        if args.distributions:
-            # the same state again, on the bond list of --bonds when there is one (else the bonds are made here and not written)
-            t_dist = time.perf_counter()
-            dist_bonds = bonds_dev if bonds_dev is not None else aro_bonds
-            dists = geometry.batch_distributions({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode,
-                                                 bonds=dist_bonds, aromatic=aro_dev)
-            dists = {k: v.cpu() for k, v in dists.items()}
-            distributions_seconds[0] += time.perf_counter() - t_dist
-        sdf_bonds = None
-        if args.sdf:
-            # the bond list the records are written from: --aromatic's types when given, else the orders
-            sdf_bonds = bonds_dev if bonds_dev is not None else aro_bonds
-            if sdf_bonds is None:
-                sdf_bonds = geometry.batch_bonds({"num_graphs": len(ids) * num_samples}, x.to(dev), c.to(dev), bidx.to(dev), mode)
-            sdf_bonds = {k: sdf_bonds[k].cpu() for k in ("bond_index", "bond_order", "graph_counts")}
+        n_graphs = len(ids) * num_samples
+        found = reports.evaluate(dev, (x, c, bidx), batch, n_graphs, mode)
         x, c, bidx = x.cpu(), c.cpu(), bidx.cpu()
         if translate:       # back to the frame the pockets came in (sample.py:198-199; here per graph: a batch holds many pockets)
             x = x + batch["ligand_translation"].cpu()
-        samples = split_samples(x, c, bidx, len(ids) * num_samples, mode)
+        samples = split_samples(x, c, bidx, n_graphs, mode)
         if "ligand_gen_flag" in batch:      # context tasks: which atoms of a record were generated
             gen = batch["ligand_gen_flag"].cpu()
             for g, smp in enumerate(samples):
                 smp["gen_flag"] = gen[bidx == g].clone()
-        if geo is not None:
-            for g, smp in enumerate(samples):
-                m, f = bidx == g, geo["flags"]
-                smp["nr_bonds"] = geo["nr_bonds"][m].clone()
-                smp["atom_stable"] = (f[m] & geometry.STABLE) != 0
-                smp["inter_clash"] = (f[m] & geometry.INTER_CLASH) != 0
-                smp["intra_clash_table_bonds"] = (f[m] & geometry.INTRA_CLASH) != 0
-                smp["mol_stable"] = bool(geo["graph_counts"][g, 2])
-        if bonds is not None:
-            # bonds are sorted by their first atom and atoms by graph: a graph's bonds and atoms are ranges; rows become ligand-local
-            gc = bonds["graph_counts"].to(torch.int64)
-            atom_end, bond_end = gc[:, 0].cumsum(0).tolist(), gc[:, 1].cumsum(0).tolist()
-            for g, smp in enumerate(samples):
-                a0, b0, b1 = atom_end[g] - int(gc[g, 0]), bond_end[g] - int(gc[g, 1]), bond_end[g]
-                smp["bond_index"] = bonds["bond_index"][:, b0:b1] - a0
-                smp["bond_order"] = bonds["bond_order"][b0:b1].clone()
-                smp["bond_length"] = bonds["bond_length"][b0:b1].clone()
-                smp["fragment"] = bonds["fragment"][a0:atom_end[g]].clone()
-                smp["n_fragments"] = int(gc[g, 3])
-                smp["connected"] = int(gc[g, 3]) == 1
-        if rings is not None:
-            gc = rings["graph_counts"].to(torch.int64)
-            atom_end = gc[:, 0].cumsum(0).tolist()
-            for g, smp in enumerate(samples):
-                smp["ring_sizes"] = gc[g, 3:3 + len(geometry.RING_SIZES)].clone()
-                smp["n_rings_larger"] = int(gc[g, -3])
-                smp["atom_ring_min"] = rings["atom_ring_min"][atom_end[g] - int(gc[g, 0]):atom_end[g]].clone()
-                smp["ring_status"] = int(gc[g, -1])
-        if aro is not None:
-            gc, bgc = aro["graph_counts"].to(torch.int64), aro_bonds["graph_counts"].cpu().to(torch.int64)
-            atom_end, bond_end = bgc[:, 0].cumsum(0).tolist(), bgc[:, 1].cumsum(0).tolist()
-            for g, smp in enumerate(samples):
-                a0, b0 = atom_end[g] - int(bgc[g, 0]), bond_end[g] - int(bgc[g, 1])
-                smp["aromatic_atom"] = aro["aromatic_atom"][a0:atom_end[g]].clone()
-                smp["aromatic_bond"] = aro["aromatic_bond"][b0:bond_end[g]].clone()
-                smp["bond_type"] = aro["bond_type"][b0:bond_end[g]].clone()
-                smp["n_aromatic_rings"] = int(gc[g, 3])
-                smp["aromatic_status"] = int(gc[g, 9])
-        if dists is not None:
-            # angles are sorted by their centre and atoms by graph: a graph's angles and atoms are ranges; rows become ligand-local
-            gc = dists["graph_counts"].to(torch.int64)
-            atom_end, angle_end = gc[:, 0].cumsum(0).tolist(), gc[:, 2].cumsum(0).tolist()
-            for g, smp in enumerate(samples):
-                a0, n0, n1 = atom_end[g] - int(gc[g, 0]), angle_end[g] - int(gc[g, 2]), angle_end[g]
-                smp["angle_index"] = dists["angle_index"][:, n0:n1] - a0
-                smp["angle_cos"] = dists["angle_cos"][n0:n1].clone()
-                smp["angle_deg"] = torch.from_numpy(np.degrees(np.arccos(smp["angle_cos"].numpy())))
-                smp["angle_type"] = dists["angle_type"][n0:n1].clone()
-                smp["distribution_status"] = int(gc[g, 4])
+        reports.annotate(samples, found)
         for k, pid in enumerate(ids):
-            rec = {"pocket_index": pid, "samples": samples[k * num_samples:(k + 1) * num_samples]}
-            if dists is not None:
-                totals = geometry.distribution_totals(dists, graphs=(k * num_samples, (k + 1) * num_samples), n_orders=n_orders)
-                job_distribution_totals[:] += totals
-                rec["distributions"] = geometry.distribution_counts(totals, n_orders=n_orders)
-            if aro is not None:
-                gc = aro["graph_counts"][k * num_samples:(k + 1) * num_samples].to(torch.int64)
-                job_aromatic_counts.append(gc)
-                rec["aromatic"] = geometry.summarise_aromatic(gc)["counts"]
-            if rings is not None:
-                gc = rings["graph_counts"][k * num_samples:(k + 1) * num_samples].to(torch.int64)
-                job_ring_counts.append(gc)
-                rec["rings"] = geometry.summarise_rings(gc)["counts"]
-            if bonds is not None:
-                gc = bonds["graph_counts"][k * num_samples:(k + 1) * num_samples].to(torch.int64)
-                job_bond_counts.append(gc)
-                rec["bonds"] = geometry.summarise_bonds(gc)["counts"]
-            if geo is not None:
-                gc = geo["graph_counts"][k * num_samples:(k + 1) * num_samples].to(torch.int64)
-                job_counts.append(gc)
-                rec["geometry"] = geometry.summarise(gc)["counts"]
+            g0, g1 = k * num_samples, (k + 1) * num_samples
+            rec = {"pocket_index": pid, "samples": samples[g0:g1], **reports.pocket_counts(found, g0, g1)}
             if args.save_traj:
                 rec["traj_keys"] = sorted(traj.keys())
             torch.save(rec, os.path.join(out_dir, f"pocket_{pid:05d}.pt"))
-            if sdf_bonds is not None:
-                gc = sdf_bonds["graph_counts"].to(torch.int64)
-                atom_end, bond_end = gc[:, 0].cumsum(0).tolist(), gc[:, 1].cumsum(0).tolist()
-                records = []
-                for j in range(num_samples):
-                    g = k * num_samples + j
-                    a0, b0, b1 = atom_end[g] - int(gc[g, 0]), bond_end[g] - int(gc[g, 1]), bond_end[g]
-                    # --aromatic's types where that report evaluated the sample, else the orders
-                    evaluated = aro is not None and int(aro["graph_counts"][g, 9]) == 0
-                    types = aro["bond_type"][b0:b1] if evaluated else sdf_bonds["bond_order"][b0:b1]
-                    try:
-                        records.append(geometry.sdf_record(f"pocket_{pid:05d}_sample_{j}", samples[g]["pos"], samples[g]["atom"],
-                                                           sdf_bonds["bond_index"][:, b0:b1] - a0, types))
-                        sdf_left_out[1] += 1
-                    except ValueError:
-                        sdf_left_out[0] += 1
-                with open(os.path.join(out_dir, f"pocket_{pid:05d}.sdf"), "w") as f:
-                    f.write("".join(records))
-        return len(ids) * num_samples * model.num_diffusion_timesteps
+            for name, text in reports.pocket_files(f"pocket_{pid:05d}", samples[g0:g1], found, g0):
+                with open(os.path.join(out_dir, name), "w") as f:
+                    f.write(text)
+        return n_graphs * model.num_diffusion_timesteps
 
     lap("setup", dev)
     timing = {}
@@ -536,76 +367,8 @@ def main(argv=None, stats=None):
     if stats is not None:
         stats.update(phases)
         stats.update(timing)
-        if args.geometry:
-            stats["geometry"] = geometry_seconds[0]
-        if args.bonds:
-            stats["bonds"] = bonds_seconds[0]
-        if args.rings:
-            stats["rings"] = rings_seconds[0]
-        if args.distributions:
-            stats["distributions"] = distributions_seconds[0]
-        if args.aromatic:
-            stats["aromatic"] = aromatic_seconds[0]
-    if args.geometry:
-        # integer counts of all ranks, summed: the job's numbers do not depend on how the pockets were sharded
-        totals = geometry.job_totals(torch.cat(job_counts) if job_counts else torch.zeros(0, len(geometry.GRAPH_COLUMNS)))
-        summary = geometry.summarise_totals(sharding.sum_counts(totals, device=dev))
-        if rank == 0:
-            with open(os.path.join(out_dir, "geometry_summary.json"), "w") as f:
-                json.dump(summary, f, indent=1, sort_keys=True)
-            print("geometry: " + ", ".join(f"{k} {summary[k]:.4f}" for k in geometry.RATIOS)
-                  + f" ({summary['counts']['n_mol']} molecules, {summary['counts']['n_atoms']} atoms)")
-    if args.bonds:
-        totals = geometry.bond_totals(torch.cat(job_bond_counts) if job_bond_counts
-                                      else torch.zeros(0, len(geometry.BOND_GRAPH_COLUMNS)))
-        summary = geometry.summarise_bond_totals(sharding.sum_counts(totals, device=dev))
-        if rank == 0:
-            with open(os.path.join(out_dir, "bonds_summary.json"), "w") as f:
-                json.dump(summary, f, indent=1, sort_keys=True)
-            print("bonds: " + ", ".join(f"{k} {summary[k]:.4f}" for k in geometry.BOND_RATIOS)
-                  + f" ({summary['counts']['n_mol']} molecules, {summary['counts']['n_bonds']} bonds)")
-    if args.rings:
-        totals = geometry.ring_totals(torch.cat(job_ring_counts) if job_ring_counts
-                                      else torch.zeros(0, len(geometry.RING_GRAPH_COLUMNS)))
-        summary = geometry.summarise_ring_totals(sharding.sum_counts(totals, device=dev))
-        if rank == 0:
-            with open(os.path.join(out_dir, "rings_summary.json"), "w") as f:
-                json.dump(summary, f, indent=1, sort_keys=True)
-            cnt = summary["counts"]
-            print("rings: " + ", ".join(f"ring_mol_ratio_{k} {summary[f'ring_mol_ratio_{k}']:.4f}" for k in geometry.RING_SIZES)
-                  + f", macrocycle_mol_ratio {summary['macrocycle_mol_ratio']:.4f}, ring_atom_ratio {summary['ring_atom_ratio']:.4f}"
-                  + f" ({cnt['n_mol_evaluated']} of {cnt['n_mol']} molecules evaluated, {cnt['n_rings']} rings)")
-    if args.distributions:
-        summary = geometry.summarise_distribution_totals(sharding.sum_counts(job_distribution_totals.tolist(), device=dev),
-                                                         n_orders=n_orders)
-        if rank == 0:
-            if args.distributions_reference:
-                summary.update(geometry.jsd_against(summary, load_reference_distributions(args.distributions_reference),
-                                                    n_orders=n_orders))
-            with open(os.path.join(out_dir, "distributions_summary.json"), "w") as f:
-                json.dump(summary, f, indent=1, sort_keys=True)
-            cnt, all_12a = summary["counts"], summary["pair_length"]["All_12A"]
-            edges = geometry.default_pair_edges()[0]
-            mode_bin = int(np.argmax(all_12a["distribution"])) if all_12a["count"] else -1
-            # bin b > 0 holds edges[b - 1] < d <= edges[b]; bin 0 the distances that are exactly edges[0]
-            centre = float("nan") if mode_bin < 0 else float(edges[0] if mode_bin == 0 else 0.5 * (edges[mode_bin - 1] + edges[mode_bin]))
-            print(f"distributions: {cnt['n_mol']} molecules, {cnt['n_bonds']} bonds, {cnt['n_angles']} angles, "
-                  f"All_12A modal bin centre {centre:.3f} A, n_mol_over_limit {cnt['n_mol_over_limit']}")
-    if args.aromatic:
-        totals = geometry.aromatic_totals(torch.cat(job_aromatic_counts) if job_aromatic_counts
-                                          else torch.zeros(0, len(geometry.AROMATIC_GRAPH_COLUMNS)))
-        summary = geometry.summarise_aromatic_totals(sharding.sum_counts(totals, device=dev))
-        if rank == 0:
-            with open(os.path.join(out_dir, "aromatic_summary.json"), "w") as f:
-                json.dump(summary, f, indent=1, sort_keys=True)
-            cnt = summary["counts"]
-            print("aromatic: " + ", ".join(f"{k} {summary[k]:.4f}" for k in geometry.AROMATIC_RATIOS)
-                  + f" ({cnt['n_mol_evaluated']} of {cnt['n_mol']} molecules evaluated, {cnt['n_aromatic_cycles']} aromatic rings)")
-    if args.sdf:
-        left_out, written = sharding.sum_counts(sdf_left_out, device=dev)
-        if rank == 0:
-            print(f"sdf: {written} records written, {left_out} samples left out (above 999 atoms or bonds, or an element outside "
-                  f"H C N O F P S Cl)")
+        stats.update(reports.seconds)
+    reports.finish(out_dir, rank, dev)
     if rank == 0:
         print(f"sampled {len(pockets)} pockets x {num_samples} samples on {world} rank(s): "
               f"{gs / el:.1f} graph-steps/s, results in {out_dir}")

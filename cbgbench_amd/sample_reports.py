@@ -1,0 +1,235 @@
+"""The reports of ``sample_cli`` (--geometry, --bonds, --rings, --aromatic, --distributions, --sdf) in three stages: ``evaluate`` runs the
+requested reports of one batch on the GPU and returns plain dicts of CPU tensors; ``annotate`` / ``pocket_counts`` / ``pocket_files``
+turn those into the per-sample fields, the per-pocket dicts and the ``.sdf`` text on the host (CPU tensors in, no device); ``finish`` sums
+the job's integer totals over the ranks, writes ``*_summary.json`` and prints one line per report.
+
+Reports run in the order of ORDER.  What a report is computed from beside the state (NEEDS: the bond list, the ring report) is made at
+most once per batch and shared; a dependency that was not asked for is computed, used and not written, and its wall time goes to the first
+requested report in that order that needs it."""
+import json
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import geometry, sharding
+
+ORDER = ("geometry", "bonds", "rings", "aromatic", "distributions")
+NEEDS = {"rings": ("bonds",), "aromatic": ("bonds", "rings"), "distributions": ("bonds",)}
+_COUNT_REPORTS = {rep.name: rep for rep in geometry.COUNT_REPORTS}
+# the refusals off the GPU, in the order they are made (the check of --aromatic's atom types comes before its own)
+_GPU_ONLY = {"geometry": "--geometry runs on the GPU (cbgx_ligand_geometry has no CPU fallback)",
+             "bonds": "--bonds runs on the GPU (cbgx_ligand_bonds_count / _fill have no CPU fallback)",
+             "rings": "--rings runs on the GPU (cbgx_ligand_rings has no CPU fallback)",
+             "distributions": "--distributions runs on the GPU (cbgx_ligand_pair_hist / cbgx_ligand_angles have no CPU fallback)",
+             "aromatic": "--aromatic runs on the GPU (cbgx_ligand_aromatic has no CPU fallback)",
+             "sdf": "--sdf takes its bonds from the GPU (cbgx_ligand_bonds_count / _fill have no CPU fallback)"}
+# a count report's printed line: the ratios it names, and its own tail
+_LINE = {"geometry": (geometry.RATIOS, lambda c: f"{c['n_mol']} molecules, {c['n_atoms']} atoms"),
+         "bonds": (geometry.BOND_RATIOS, lambda c: f"{c['n_mol']} molecules, {c['n_bonds']} bonds"),
+         "rings": (tuple(f"ring_mol_ratio_{k}" for k in geometry.RING_SIZES) + ("macrocycle_mol_ratio", "ring_atom_ratio"),
+                   lambda c: f"{c['n_mol_evaluated']} of {c['n_mol']} molecules evaluated, {c['n_rings']} rings"),
+         "aromatic": (geometry.AROMATIC_RATIOS,
+                      lambda c: f"{c['n_mol_evaluated']} of {c['n_mol']} molecules evaluated, {c['n_aromatic_cycles']} aromatic rings")}
+
+
+def load_reference_distributions(path):
+    """``--distributions_reference``: {key: vector} from a ``.npz`` (np.savez(path, **{'6-6': v, ...})) or a ``torch.save``d dict"""
+    if path.endswith(".npz"):
+        with np.load(path) as f:
+            return {k: np.asarray(f[k], np.float64) for k in f.files}
+    raw = torch.load(path, map_location="cpu", weights_only=False)
+    if not isinstance(raw, dict):
+        raise SystemExit(f"sample_cli: {path} does not hold a dict of reference distributions")
+    return {k: np.asarray(v, np.float64) for k, v in raw.items()}
+
+
+def ranges(counts):
+    """a per-graph count column [B] -> [(start, end)] per graph: rows (atoms, bonds, angles) are grouped by graph, in graph order"""
+    ends = counts.to(torch.int64).cumsum(0).tolist()
+    return list(zip([0] + ends[:-1], ends))
+
+
+class SampleReports:
+    """``requested``: names out of ORDER and 'sdf'; ``reference``: the path of --distributions_reference"""
+
+    def __init__(self, requested, reference=None):
+        self.requested = frozenset(requested)
+        self.reference = reference
+        self.n_orders = 4 if "aromatic" in self.requested else 3        # --aromatic --distributions: types with the aromatic type
+        self.seconds = {name: 0.0 for name in ORDER if name in self.requested}         # wall time of every report (``stats``)
+        self.counts = {name: [] for name in _COUNT_REPORTS if name in self.requested}  # per-sample counts of this rank
+        # the pockets' flat integer totals are added up as they come (one is 3.5 MB)
+        self.distribution_totals = np.zeros(geometry.distribution_totals_length(n_orders=self.n_orders), np.int64)
+        self.sdf_left_out, self.sdf_written = 0, 0
+
+    @classmethod
+    def from_args(cls, args):
+        return cls([name for name in ORDER + ("sdf",) if getattr(args, name)], args.distributions_reference)
+
+    def refuse(self, dev, atom_mode):
+        """what cannot run is refused before any model is built; ``atom_mode()``: the vocabulary the samples are decoded with"""
+        for name in ("geometry", "bonds", "rings", "distributions", "aromatic", "sdf"):
+            if name not in self.requested:
+                continue
+            if name == "aromatic" and atom_mode() != "add_aromatic":
+                # on any device: the report starts from the aromatic atom types
+                raise SystemExit(f"sample_cli: --aromatic starts from the model's aromatic flags: atom types of mode 'add_aromatic', "
+                                 f"not {atom_mode()!r}")
+            if dev.type != "cuda":
+                raise SystemExit("sample_cli: " + _GPU_ONLY[name])
+        if self.reference and "distributions" not in self.requested:
+            raise SystemExit("sample_cli: --distributions_reference needs --distributions")
+
+    # ---- GPU -----------------------------------------------------------------------------------------------------------------------------
+    def evaluate(self, dev, state, batch, n_graphs, mode):
+        """the requested reports of the state ``(x, c, bidx)`` the records hold, in the sampling frame (before ligand_translation), against
+        the batch's own pocket -> {report: {name: CPU tensor}}; with --sdf or --aromatic and no --bonds also the ``bonds`` the host side
+        slices by (not written)"""
+        if not self.requested:
+            return {}
+        x, c, bidx = (t.to(dev) for t in state)
+        info, made, out = {"num_graphs": n_graphs}, {}, {}
+
+        def get(name):
+            if name not in made:
+                deps = {dep: get(dep) for dep in NEEDS.get(name, ())}
+                if name == "geometry":
+                    pocket = {k: batch[k].to(dev) for k in ("protein_pos", "protein_element", "protein_element_batch")}
+                    made[name] = geometry.batch_geometry({**pocket, **info}, x, c, bidx, mode)
+                elif name == "distributions":
+                    made[name] = geometry.batch_distributions(info, x, c, bidx, mode, aromatic=made.get("aromatic"), **deps)
+                else:
+                    made[name] = getattr(geometry, "batch_" + name)(info, x, c, bidx, mode, **deps)
+            return made[name]
+
+        for name in self.seconds:
+            t0 = time.perf_counter()
+            out[name] = {k: v.cpu() for k, v in get(name).items()}      # (the download waits for the launches)
+            self.seconds[name] += time.perf_counter() - t0
+        if "bonds" not in out and self.requested & {"aromatic", "sdf"}:
+            out["bonds"] = {k: get("bonds")[k].cpu() for k in ("bond_index", "bond_order", "graph_counts")}
+        return out
+
+    # ---- host ----------------------------------------------------------------------------------------------------------------------------
+    def annotate(self, samples, ev):
+        """the per-sample fields of the requested reports, added to ``samples`` (one dict per graph of the batch, in graph order).  Atoms
+        are sorted by graph, bonds by their first atom and angles by their centre: a graph's rows are ranges, and bond and angle rows
+        become ligand-local"""
+        if "geometry" in self.requested:
+            geo = ev["geometry"]
+            for g, (smp, (a0, a1)) in enumerate(zip(samples, ranges(geo["graph_counts"][:, 0]))):
+                f = geo["flags"][a0:a1]
+                smp["nr_bonds"] = geo["nr_bonds"][a0:a1].clone()
+                smp["atom_stable"] = (f & geometry.STABLE) != 0
+                smp["inter_clash"] = (f & geometry.INTER_CLASH) != 0
+                smp["intra_clash_table_bonds"] = (f & geometry.INTRA_CLASH) != 0
+                smp["mol_stable"] = bool(geo["graph_counts"][g, 2])
+        if "bonds" in self.requested:
+            bonds, gc = ev["bonds"], ev["bonds"]["graph_counts"]
+            for g, (smp, (a0, a1), (b0, b1)) in enumerate(zip(samples, ranges(gc[:, 0]), ranges(gc[:, 1]))):
+                smp["bond_index"] = bonds["bond_index"][:, b0:b1] - a0
+                smp["bond_order"] = bonds["bond_order"][b0:b1].clone()
+                smp["bond_length"] = bonds["bond_length"][b0:b1].clone()
+                smp["fragment"] = bonds["fragment"][a0:a1].clone()
+                smp["n_fragments"] = int(gc[g, 3])
+                smp["connected"] = int(gc[g, 3]) == 1
+        if "rings" in self.requested:
+            gc = ev["rings"]["graph_counts"].to(torch.int64)
+            for g, (smp, (a0, a1)) in enumerate(zip(samples, ranges(gc[:, 0]))):
+                smp["ring_sizes"] = gc[g, 3:3 + len(geometry.RING_SIZES)].clone()
+                smp["n_rings_larger"] = int(gc[g, -3])
+                smp["atom_ring_min"] = ev["rings"]["atom_ring_min"][a0:a1].clone()
+                smp["ring_status"] = int(gc[g, -1])
+        if "aromatic" in self.requested:
+            aro, gc, bgc = ev["aromatic"], ev["aromatic"]["graph_counts"], ev["bonds"]["graph_counts"]
+            for g, (smp, (a0, a1), (b0, b1)) in enumerate(zip(samples, ranges(bgc[:, 0]), ranges(bgc[:, 1]))):
+                smp["aromatic_atom"] = aro["aromatic_atom"][a0:a1].clone()
+                smp["aromatic_bond"] = aro["aromatic_bond"][b0:b1].clone()
+                smp["bond_type"] = aro["bond_type"][b0:b1].clone()
+                smp["n_aromatic_rings"] = int(gc[g, 3])
+                smp["aromatic_status"] = int(gc[g, 9])
+        if "distributions" in self.requested:
+            dists, gc = ev["distributions"], ev["distributions"]["graph_counts"]
+            for g, (smp, (a0, a1), (n0, n1)) in enumerate(zip(samples, ranges(gc[:, 0]), ranges(gc[:, 2]))):
+                smp["angle_index"] = dists["angle_index"][:, n0:n1] - a0
+                smp["angle_cos"] = dists["angle_cos"][n0:n1].clone()
+                smp["angle_deg"] = torch.from_numpy(np.degrees(np.arccos(smp["angle_cos"].numpy())))
+                smp["angle_type"] = dists["angle_type"][n0:n1].clone()
+                smp["distribution_status"] = int(gc[g, 4])
+
+    def pocket_counts(self, ev, g0, g1):
+        """the dicts of counts a pocket record carries for its graphs g0 ... g1 - 1, which join the job's totals"""
+        rec = {}
+        if "distributions" in self.requested:
+            totals = geometry.distribution_totals(ev["distributions"], graphs=(g0, g1), n_orders=self.n_orders)
+            self.distribution_totals += totals
+            rec["distributions"] = geometry.distribution_counts(totals, n_orders=self.n_orders)
+        for rep in reversed(geometry.COUNT_REPORTS):
+            if rep.name in self.requested:
+                gc = ev[rep.name]["graph_counts"][g0:g1].to(torch.int64)
+                self.counts[rep.name].append(gc)
+                rec[rep.name] = rep.summarise_totals(rep.totals(gc))["counts"]
+        return rec
+
+    def pocket_files(self, stem, samples, ev, g0):
+        """(file name, text) of what is written beside a pocket's record ``stem``.pt: with --sdf one V2000 record per sample of the pocket
+        (``samples``: its records, graphs g0 ... of the batch), bond types from --aromatic where that report evaluated the sample, else the
+        table-bond orders; a sample ``sdf_record`` refuses is left out and counted"""
+        if "sdf" not in self.requested:
+            return []
+        bonds, gc = ev["bonds"], ev["bonds"]["graph_counts"]
+        atoms, rows, records = ranges(gc[:, 0]), ranges(gc[:, 1]), []
+        for j, smp in enumerate(samples):
+            (a0, _), (b0, b1) = atoms[g0 + j], rows[g0 + j]
+            evaluated = "aromatic" in self.requested and int(ev["aromatic"]["graph_counts"][g0 + j, 9]) == 0
+            types = ev["aromatic"]["bond_type"][b0:b1] if evaluated else bonds["bond_order"][b0:b1]
+            try:
+                records.append(geometry.sdf_record(f"{stem}_sample_{j}", smp["pos"], smp["atom"], bonds["bond_index"][:, b0:b1] - a0, types))
+                self.sdf_written += 1
+            except ValueError:
+                self.sdf_left_out += 1
+        return [(stem + ".sdf", "".join(records))]
+
+    # ---- the job -------------------------------------------------------------------------------------------------------------------------
+    def finish(self, out_dir, rank, dev):
+        """integer totals of all ranks, summed: the job's numbers do not depend on how the pockets were sharded.  Rank 0 writes
+        {out_dir}/<report>_summary.json and prints the report's line"""
+        def save(name, summary):
+            with open(os.path.join(out_dir, name + "_summary.json"), "w") as f:
+                json.dump(summary, f, indent=1, sort_keys=True)
+
+        for name in ("geometry", "bonds", "rings", "distributions", "aromatic"):
+            if name not in self.requested:
+                continue
+            if name == "distributions":
+                self._finish_distributions(save, rank, dev)
+                continue
+            rep, (ratios, tail) = _COUNT_REPORTS[name], _LINE[name]
+            totals = rep.totals(torch.cat(self.counts[name]) if self.counts[name] else torch.zeros(0, len(rep.graph_columns)))
+            summary = rep.summarise_totals(sharding.sum_counts(totals, device=dev))
+            if rank == 0:
+                save(name, summary)
+                print(f"{name}: " + ", ".join(f"{k} {summary[k]:.4f}" for k in ratios) + f" ({tail(summary['counts'])})")
+        if "sdf" in self.requested:
+            left_out, written = sharding.sum_counts([self.sdf_left_out, self.sdf_written], device=dev)
+            if rank == 0:
+                print(f"sdf: {written} records written, {left_out} samples left out (above 999 atoms or bonds, or an element outside "
+                      f"H C N O F P S Cl)")
+
+    def _finish_distributions(self, save, rank, dev):
+        summary = geometry.summarise_distribution_totals(sharding.sum_counts(self.distribution_totals.tolist(), device=dev),
+                                                         n_orders=self.n_orders)
+        if rank != 0:
+            return
+        if self.reference:
+            summary.update(geometry.jsd_against(summary, load_reference_distributions(self.reference), n_orders=self.n_orders))
+        save("distributions", summary)
+        cnt, all_12a = summary["counts"], summary["pair_length"]["All_12A"]
+        edges = geometry.default_pair_edges()[0]
+        mode_bin = int(np.argmax(all_12a["distribution"])) if all_12a["count"] else -1
+        # bin b > 0 holds edges[b - 1] < d <= edges[b]; bin 0 the distances that are exactly edges[0]
+        centre = float("nan") if mode_bin < 0 else float(edges[0] if mode_bin == 0 else 0.5 * (edges[mode_bin - 1] + edges[mode_bin]))
+        print(f"distributions: {cnt['n_mol']} molecules, {cnt['n_bonds']} bonds, {cnt['n_angles']} angles, "
+              f"All_12A modal bin centre {centre:.3f} A, n_mol_over_limit {cnt['n_mol_over_limit']}")
