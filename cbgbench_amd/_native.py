@@ -27,6 +27,11 @@ EXPORTS = {
     "cbgx_unitransformer_forward_v2": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, ctypes.c_uint, _vp, _sz, _vp]),
     "cbgx_unitransformer_forward_cached": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                                 _vp, _vp, _vp, ctypes.c_uint, _vp, _sz, _vp]),
+    "cbgx_unitransformer_forward_step_cached": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                     _vp, _vp, _vp, ctypes.c_uint, _vp, _sz, _vp, _sz, _vp]),
+    "cbgx_step_cache_bytes": (_sz, [_i]),
+    "cbgx_step_cache_reset": (_i, [_vp, _sz, _i, _vp]),
+    "cbgx_step_cache_layout": (_i, [_i, ctypes.POINTER(_sz)]),
     "cbgx_knn_graph": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "cbgx_edge_gate": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "cbgx_x2h_attention": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),

@@ -53,6 +53,7 @@ struct Workspace {
     // The (general, protein-only) split of: all nodes | the cached layer 1 (D2) | the pruned layers (A1, A2)
     NodeList all_gen, all_pp, D2_gen, D2_pp, A1_gen, A1_pp, A2_gen, A2_pp;
     NodeList empty;               // always empty: a count nothing writes after the call's fill
+    int* step_count[2];           // counts of the step cache's two lists (their rows live in the cache block: StepCache)
     // per-node flags behind the lists (node_mfma.hip, list_level_kernel), zeroed with the counts by ONE fill per forward call:
     // receptive-field sets a1 a2 a3; "differs from the ligand-free pocket" D1 (proximity flags of the graph cache) D2 S1 S2; d1flag
     uint8_t *fa1, *fa2, *fa3, *fD1, *fD2, *fS1, *fS2;
@@ -99,7 +100,9 @@ static Workspace carve(void* base, int n) {
     counts(256, {&w.A1, &w.A2, &w.A3});
     counts(512, {&w.D1, &w.S1, &w.D2, &w.S2});
     counts(768, {&w.all_gen, &w.all_pp, &w.D2_gen, &w.D2_pp, &w.A1_gen, &w.A1_pp, &w.A2_gen, &w.A2_pp});
-    counts(768 + 4 * 128, {&w.empty});
+    NodeList step_l0, step_u1;    // (the empty list's 256 bytes hold four counts)
+    counts(768 + 4 * 128, {&w.empty, &step_l0, &step_u1});
+    w.step_count[0] = step_l0.count; w.step_count[1] = step_u1.count;
     w.total = c.off;
     return w;
 }
@@ -109,6 +112,48 @@ static int carve_checked(const char* who, void* workspace, size_t workspace_byte
     w = carve(workspace, n_nodes);
     if (workspace_bytes < w.total) return fail(CBGX_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, w.total);
     return CBGX_OK;
+}
+
+// The step cache of a sampling state (cbgx_unitransformer_forward_step_cached): what the first two layers of a static-context call
+// compute again in every one of the T calls although its inputs did not change.  The block outlives the call; the arrays hold EVERY row.
+//   P[0] / q[0]   node stage of layer 0 (input: the caller's h).  Protein rows of h never change, so after the first call only the
+//                 ligand rows are computed.
+//   hbuf[0]       output of layer 0: the static_h1 row outside D1(t).  Per call the rows of D1(t-1) are placed again, then the layer
+//                 writes D1(t).
+//   P[1] / q[1]   node stage of layer 1 (input: hbuf[0]): computed on D1(t) | D1(t-1) -- a row that left D1 is computed from its restored
+//                 static row, which gives the static projection again.
+//   hbuf[1]       output of layer 1, the same with D2 and static_h2.
+// Three flag arrays carry the state from call to call, all ones after cbgx_step_cache_reset, so that the first call computes and places
+// every row through the same launches: fresh0 (layer-0 node stage not yet computed), prevD1 / prevD2 (adjacent: saved by one copy).
+struct StepCache {
+    float *P[2], *q[2], *hbuf[2];
+    NodeList L0, U1;            // rows of the layer-0 / layer-1 node stage of this call (counts: in the workspace's counter block)
+    uint8_t *fresh0, *prevD1, *prevD2;
+    size_t flag_stride, total;
+};
+static StepCache carve_step_cache(void* base, int n) {
+    StepCache c;
+    Carver k(base);
+    const size_t N = (size_t)(n > 0 ? n : 1);
+    for (int l = 0; l < 2; ++l) {
+        c.P[l] = k.take<float>(N * PROW * 4);
+        c.q[l] = k.take<float>(N * H * 4);
+        c.hbuf[l] = k.take<float>(N * H * 4);
+    }
+    c.L0.rows = k.take<int>(N * 4);
+    c.U1.rows = k.take<int>(N * 4);
+    c.L0.count = c.U1.count = nullptr;
+    c.flag_stride = align_up(N);
+    c.fresh0 = k.take<uint8_t>(3 * c.flag_stride);
+    c.prevD1 = c.fresh0 + c.flag_stride;
+    c.prevD2 = c.prevD1 + c.flag_stride;
+    c.total = k.off;
+    return c;
+}
+// CBGX_STEP_CACHE=0 (schedule knob, read once per process): step-cached calls run the launches of cbgx_unitransformer_forward_cached
+static bool step_cache_enabled() {
+    static const bool on = [] { const char* e = getenv("CBGX_STEP_CACHE"); return !e || atoi(e) != 0; }();
+    return on;
 }
 
 // Auxiliary streams: one per (host thread, caller stream), created on first use, with the two events that fork it from and join it
@@ -547,6 +592,7 @@ struct LayerPlan {
     NodeList gen, pp;           // x2h edge launch: general-role and protein-only destinations
     bool full_layer;            // ... which together are every node
     const uint8_t* fold_flag;   // fused node stage: Qt only for the flagged rows of dst (NULL: for all of them)
+    NodeList node;              // step cache: P (own and PS columns) and q on these rows alone, in place of dst / src
 };
 
 // a forward call: its arguments, then what forward_impl derives from them for its parts
@@ -555,10 +601,13 @@ struct Forward {
     int n_nodes, n_graphs; float *x_out, *h_out, *logits;
     const float *static_h1, *static_h2; const int32_t *static_nbr, *static_deg; const float *static_ew, *static_r32sq;
     unsigned flags; void* workspace; size_t workspace_bytes; hipStream_t s;
+    void* step_block = nullptr; size_t step_block_bytes = 0;     // (cbgx_unitransformer_forward_step_cached)
     Workspace w;
     Graph graph;                // w.nbr / deg / e_w with the caller's flags: what every attention block of the call runs on
     bool cached, graph_cached, prune, dual;
     bool h2x_lig;               // h2x blocks: ligand-row edge kernel, node stage without the fold (CBGX_FWD_GEN_IS_LIGAND)
+    bool step;                  // layers 0 / 1 on the step cache `sc`
+    StepCache sc;
     std::vector<LayerPlan> plan;
 };
 
@@ -575,8 +624,9 @@ static int forward_graph_stage(const Forward& f) {
     // D1 flags + list, the pocket's own graph and the cached features of layers 0 / 1 (into hbuf[0] / hbuf[1]: num_layers >= 4,
     // so neither is the caller's h_out, and nothing else touches them before their layer): one launch
     HIP_TRY(launch_graph_cache_begin(f.x, f.graph_ptr, n_graphs, f.lig_flag, f.static_r32sq, n_nodes, w.fD1, w.D1.rows, w.D1.count,
-                                     f.static_nbr, f.static_deg, f.static_ew, w.nbr, w.deg, w.e_w, f.static_h1, f.static_h2, w.hbuf[0],
-                                     w.hbuf[1], s));
+                                     f.static_nbr, f.static_deg, f.static_ew, w.nbr, w.deg, w.e_w, f.static_h1, f.static_h2,
+                                     f.step ? f.sc.hbuf[0] : w.hbuf[0], f.step ? f.sc.hbuf[1] : w.hbuf[1], s,
+                                     f.step ? f.sc.prevD1 : nullptr, f.step ? f.sc.prevD2 : nullptr));
     // the D1 centres' merged neighbour lists and gate values: kept pocket entries carry their cached value to their new rank, the gate
     // MLP runs on the ligand atoms that entered the list.  Small inputs: ONE launch (knn_merge_gate_kernel: a persistent kernel at one
     // wave per SIMD -- at 173 k nodes it measured 612 us against 153 + 175 for the two kernels, profiles/ab_fwd_r05f.log); large inputs:
@@ -630,6 +680,18 @@ static int forward_list_stage(const Forward& f) {
         add(GF_S1, GF_ALL, 0, w.S1);
         add(GF_S2, GF_ALL, 0, w.S2);
     }
+    if (f.step) {
+        // L0 = ligand rows | rows never computed;  U1 = D1(t) | D1(t-1): two disjoint jobs appending to one list each
+        auto add_ptr = [&](const uint8_t* flag, const uint8_t* flag2, NodeList l) {
+            if (jobs.n_jobs >= LIST_JOBS_MAX) { jobs_overflow = true; return; }
+            const int k = jobs.n_jobs++;
+            jobs.flag[k] = flag; jobs.flag2[k] = flag2; jobs.want2[k] = 0; jobs.list[k] = l.rows; jobs.count[k] = l.count;
+        };
+        add_ptr(f.lig_flag, nullptr, f.sc.L0);
+        add_ptr(f.sc.fresh0, f.lig_flag, f.sc.L0);
+        add_ptr(w.fD1, nullptr, f.sc.U1);
+        add_ptr(f.sc.prevD1, w.fD1, f.sc.U1);
+    }
     if (f.dual) {
         pair(GF_ALL, w.all_gen, w.all_pp);
         if (f.cached) pair(GF_D2, w.D2_gen, w.D2_pp);
@@ -647,6 +709,11 @@ static int forward_list_stage(const Forward& f) {
         }
         HIP_TRY(launch_build_lists(jobs, f.n_nodes, s));
     }
+    if (f.step) {
+        // what the next call of this state starts from: every row of the layer-0 node stage exists, D1 / D2 of this call
+        HIP_TRY(hipMemsetAsync(f.sc.fresh0, 0, f.sc.flag_stride, s));
+        HIP_TRY(hipMemcpyAsync(f.sc.prevD1, w.fD1, 2 * f.sc.flag_stride, hipMemcpyDeviceToDevice, s));      // (fD1 | fD2, adjacent)
+    }
     return CBGX_OK;
 }
 
@@ -654,16 +721,16 @@ static void plan_layers(Forward& f) {
     const Workspace& w = f.w;
     const int L = f.num_layers;
     const NodeList every{nullptr, nullptr};
-    f.plan.assign(L, LayerPlan{every, every, w.all_gen, w.all_pp, true, w.d1flag});
+    f.plan.assign(L, LayerPlan{every, every, w.all_gen, w.all_pp, true, w.d1flag, every});
     if (f.cached) {     // (num_layers >= 4)
         // layer 0 on D1, all of it in the general role -- every row of D1 has a ligand atom among itself and its neighbours -- so
         // folded rows for the whole list; layer 1 on D2, of which d1flag picks the general part as in every other layer
-        f.plan[0] = LayerPlan{w.D1, w.S1, w.D1, w.empty, false, nullptr};
-        f.plan[1] = LayerPlan{w.D2, w.S2, w.D2_gen, w.D2_pp, false, w.d1flag};
+        f.plan[0] = LayerPlan{w.D1, w.S1, w.D1, w.empty, false, nullptr, f.step ? f.sc.L0 : every};
+        f.plan[1] = LayerPlan{w.D2, w.S2, w.D2_gen, w.D2_pp, false, w.d1flag, f.step ? f.sc.U1 : every};
     }
     if (f.prune) {      // (num_layers >= 3)
-        f.plan[L - 2] = LayerPlan{w.A2, w.A3, w.A2_gen, w.A2_pp, false, w.d1flag};
-        f.plan[L - 1] = LayerPlan{w.A1, w.A2, w.A1_gen, w.A1_pp, false, w.d1flag};
+        f.plan[L - 2] = LayerPlan{w.A2, w.A3, w.A2_gen, w.A2_pp, false, w.d1flag, every};
+        f.plan[L - 1] = LayerPlan{w.A1, w.A2, w.A1_gen, w.A1_pp, false, w.d1flag, every};
     }
 }
 
@@ -671,7 +738,7 @@ static void plan_layers(Forward& f) {
 // the graph part, the cached rows placed under the layer's output (graph-cached calls: graph_cache_begin has placed both)
 static hipError_t begin_layer(const Forward& f, int l, float*& hn, float*& xn) {
     const bool last = l == f.num_layers - 1;
-    hn = (last && f.h_out) ? f.h_out : f.w.hbuf[l & 1];
+    hn = (last && f.h_out) ? f.h_out : ((f.step && l < 2) ? f.sc.hbuf[l] : f.w.hbuf[l & 1]);     // (step: num_layers >= 4, never last)
     xn = last ? f.x_out : f.w.xbuf[l & 1];
     if (!f.cached || l >= 2 || f.graph_cached) return hipSuccess;
     return hipMemcpyAsync(hn, l == 0 ? f.static_h1 : f.static_h2, (size_t)f.n_nodes * H * sizeof(float), hipMemcpyDeviceToDevice, f.s);
@@ -688,7 +755,15 @@ static hipError_t node_x2h(const Forward& f, int l, const NodeBufs& b, const flo
     o.large_lists = true;
     o.fold = p.gen;
     o.q_direct = node_qdirect_enabled();
+    if (p.node.rows) {
+        o.dst_all_columns = true;
+        return launch_node_mfma(f.packed + x2h_off(l), h_in, f.lig_flag, f.n_nodes, b, p.node, {}, on, o);
+    }
     return launch_node_mfma(f.packed + x2h_off(l), h_in, f.lig_flag, f.n_nodes, b, p.dst, p.src, on, o);
+}
+// the node-stage buffers of x2h layer l: P and q of a step-cached layer live in the cache block, its Qt stays in the workspace set
+static NodeBufs bufs_x2h(const Forward& f, int l, const NodeBufs& set) {
+    return (f.step && l < 2) ? NodeBufs{f.sc.P[l], f.sc.q[l], set.Qt} : set;
 }
 // the h2x block of layer l, node stage included: moves the `act` rows, whose sources are in A1
 static hipError_t block_h2x(const Forward& f, int l, const NodeBufs& b, const float* xc, const float* hn, float* xn) {
@@ -735,17 +810,17 @@ static int forward_fused(const Forward& f) {
 // alternates between two, h2x has its own.
 static int forward_two_streams(const Forward& f, AuxStream* aux) {
     hipStream_t s = f.s;
-    HIP_TRY(node_x2h(f, 0, f.w.set[0], f.h, s));
+    HIP_TRY(node_x2h(f, 0, bufs_x2h(f, 0, f.w.set[0]), f.h, s));
     const float *xc = f.x, *hc = f.h;
     for (int l = 0; l < f.num_layers; ++l) {
         float *hn, *xn;
         HIP_TRY(begin_layer(f, l, hn, xn));
         if (l > 0) HIP_TRY(hipStreamWaitEvent(s, aux->join, 0));       // node stage of this layer (aux stream) done
-        HIP_TRY(edge_x2h(f, l, f.w.set[l & 1], xc, hc, hn));
+        HIP_TRY(edge_x2h(f, l, bufs_x2h(f, l, f.w.set[l & 1]), xc, hc, hn));
         if (l + 1 < f.num_layers) {
             HIP_TRY(hipEventRecord(aux->fork, s));
             HIP_TRY(hipStreamWaitEvent(aux->s, aux->fork, 0));
-            HIP_TRY(node_x2h(f, l + 1, f.w.set[(l + 1) & 1], hn, aux->s));
+            HIP_TRY(node_x2h(f, l + 1, bufs_x2h(f, l + 1, f.w.set[(l + 1) & 1]), hn, aux->s));
             HIP_TRY(hipEventRecord(aux->join, aux->s));
         }
         HIP_TRY(block_h2x(f, l, f.w.set[2], xc, hn, xn));
@@ -764,8 +839,8 @@ static int forward_serial(const Forward& f) {
         float *hn, *xn;
         HIP_TRY(begin_layer(f, l, hn, xn));
         if (f.dual) {
-            HIP_TRY(node_x2h(f, l, b, hc, f.s));
-            HIP_TRY(edge_x2h(f, l, b, xc, hc, hn));
+            HIP_TRY(node_x2h(f, l, bufs_x2h(f, l, b), hc, f.s));
+            HIP_TRY(edge_x2h(f, l, bufs_x2h(f, l, b), xc, hc, hn));
         } else {
             const LayerPlan& p = f.plan[l];
             HIP_TRY(launch_attention(true, f.packed + x2h_off(l), f.graph, xc, hc, b, hn, nullptr, p.dst, p.src, f.s));
@@ -809,6 +884,16 @@ static int forward_impl(Forward f) {
     // x2h layers run their (general, protein-only) list pairs (first-generation kernels: one list)
     f.dual = g_edge_impl != 1;
     f.h2x_lig = h2x_lig_selected(f.flags);
+    // the step cache serves the large-input schedules of a graph-cached call; elsewhere, and with CBGX_STEP_CACHE=0, the block is not
+    // touched and the launches are those of cbgx_unitransformer_forward_cached
+    f.step = f.step_block && f.graph_cached && f.dual && f.n_nodes > NODE_STAGE_MAX_ROWS && step_cache_enabled();
+    if (f.step) {
+        f.sc = carve_step_cache(f.step_block, f.n_nodes);
+        if (f.step_block_bytes < f.sc.total)
+            return fail(CBGX_E_WORKSPACE, "forward: step cache %zu < %zu", f.step_block_bytes, f.sc.total);
+        f.sc.L0.count = f.w.step_count[0];
+        f.sc.U1.count = f.w.step_count[1];
+    }
     if (int rc = forward_graph_stage(f)) return rc;
     if (int rc = forward_list_stage(f)) return rc;
     plan_layers(f);
@@ -853,6 +938,43 @@ int cbgx_unitransformer_forward_cached(const float* packed, int num_layers, int 
     return forward_impl(Forward{packed, num_layers, num_classes, x, h, graph_ptr, lig_flag, gen_flag, n_nodes, n_graphs, x_out,
                                 h_out, logits, static_h1, static_h2, static_nbr, static_deg, static_ew, static_r32sq, flags, workspace,
                                 workspace_bytes, (hipStream_t)stream});
+}
+
+int cbgx_unitransformer_forward_step_cached(const float* packed, int num_layers, int num_classes, const float* x,
+                                            const float* h, const int32_t* graph_ptr, const uint8_t* lig_flag,
+                                            const uint8_t* gen_flag, int n_nodes, int n_graphs, const float* static_h1,
+                                            const float* static_h2, const int32_t* static_nbr, const int32_t* static_deg,
+                                            const float* static_ew, const float* static_r32sq, float* x_out, float* h_out,
+                                            float* logits, unsigned flags, void* step_cache, size_t step_cache_bytes, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+    if (!static_h1 || !static_h2) return fail(CBGX_E_INVALID, "forward_step_cached: NULL static context");
+    Forward f{packed, num_layers, num_classes, x, h, graph_ptr, lig_flag, gen_flag, n_nodes, n_graphs, x_out,
+              h_out, logits, static_h1, static_h2, static_nbr, static_deg, static_ew, static_r32sq, flags, workspace,
+              workspace_bytes, (hipStream_t)stream};
+    f.step_block = step_cache;
+    f.step_block_bytes = step_cache_bytes;
+    return forward_impl(f);
+}
+
+size_t cbgx_step_cache_bytes(int n_nodes) {
+    if (n_nodes <= NODE_STAGE_MAX_ROWS || !step_cache_enabled()) return 0;      // (no schedule would use it)
+    return carve_step_cache(nullptr, n_nodes).total;
+}
+
+int cbgx_step_cache_reset(void* step_cache, size_t step_cache_bytes, int n_nodes, void* stream) {
+    if (!step_cache || n_nodes < 1) return fail(CBGX_E_INVALID, "step_cache_reset: bad argument");
+    const StepCache c = carve_step_cache(step_cache, n_nodes);
+    if (step_cache_bytes < c.total) return fail(CBGX_E_WORKSPACE, "step_cache_reset: block %zu < %zu", step_cache_bytes, c.total);
+    HIP_TRY(hipMemsetAsync(c.fresh0, 1, 3 * c.flag_stride, (hipStream_t)stream));
+    return CBGX_OK;
+}
+
+int cbgx_step_cache_layout(int n_nodes, size_t* offsets) {
+    if (!offsets || n_nodes < 1) return fail(CBGX_E_INVALID, "step_cache_layout: bad argument");
+    const StepCache c = carve_step_cache(nullptr, n_nodes);
+    const void* p[CBGX_STEP_CACHE_ARRAYS] = {c.P[0], c.q[0], c.hbuf[0], c.P[1], c.q[1], c.hbuf[1], c.fresh0, c.prevD1, c.prevD2};
+    for (int k = 0; k < CBGX_STEP_CACHE_ARRAYS; ++k) offsets[k] = (size_t)reinterpret_cast<uintptr_t>(p[k]);     // (carved from NULL)
+    return CBGX_OK;
 }
 
 // ---- the TargetDiff step entries: the two prologues and the six epilogues fill one aggregate; one check and one launch per kind -------

@@ -606,12 +606,15 @@ hipError_t launch_pack_gate_img(const float* w1, const float* b1, const float* g
 // graph-cached forward call was these three dependent launches (9 + 5 + 5 us of a 600 us one-graph step).  1024-thread workgroups:
 // the first ceil(n / 1024) of them also flag their nodes and append the flagged ones to `list` with one returning atomic each
 // (*count zero on entry, like build_active_kernel); every workgroup copies its slice.
+// `keep1` / `keep2` (optional, per node; the step cache of api.hip): out1 / out2 are persistent arrays that already hold the cached row
+// wherever the flag is zero, so only the flagged rows -- the ones the previous call's layer overwrote -- are placed again.
 __global__ __launch_bounds__(1024) void graph_cache_begin_kernel(
     const float* __restrict__ x, const int32_t* __restrict__ graph_ptr, int n_graphs, const uint8_t* __restrict__ lig,
     const float* __restrict__ r32sq, int n, uint8_t* __restrict__ dirty, int* __restrict__ list, int* __restrict__ count,
     const int32_t* __restrict__ s_nbr, const int32_t* __restrict__ s_deg, const float* __restrict__ s_ew,
     int32_t* __restrict__ nbr, int32_t* __restrict__ deg, float* __restrict__ ew, const float* __restrict__ h1,
-    const float* __restrict__ h2, float* __restrict__ out1, float* __restrict__ out2) {
+    const float* __restrict__ h2, float* __restrict__ out1, float* __restrict__ out2, const uint8_t* __restrict__ keep1,
+    const uint8_t* __restrict__ keep2) {
     __shared__ int s_cnt[16];
     __shared__ int s_base;
     const long t = (long)blockIdx.x * 1024 + threadIdx.x;
@@ -622,8 +625,9 @@ __global__ __launch_bounds__(1024) void graph_cache_begin_kernel(
         if ((t & (KNN / 4 - 1)) == 0) deg[t / (KNN / 4)] = s_deg[t / (KNN / 4)];
     }
     if (t < (long)n * (H / 4)) {        // one thread per 4 features
-        reinterpret_cast<float4*>(out1)[t] = reinterpret_cast<const float4*>(h1)[t];
-        reinterpret_cast<float4*>(out2)[t] = reinterpret_cast<const float4*>(h2)[t];
+        const long row = t / (H / 4);
+        if (!keep1 || keep1[row]) reinterpret_cast<float4*>(out1)[t] = reinterpret_cast<const float4*>(h1)[t];
+        if (!keep2 || keep2[row]) reinterpret_cast<float4*>(out2)[t] = reinterpret_cast<const float4*>(h2)[t];
     }
     if ((long)blockIdx.x * 1024 >= n) return;       // workgroup-uniform: no node of its own
     // ---- proximity flag of node t (lig_proximity_kernel) ----
@@ -687,11 +691,11 @@ __global__ __launch_bounds__(1024) void graph_cache_begin_kernel(
 hipError_t launch_graph_cache_begin(const float* x, const int32_t* graph_ptr, int n_graphs, const uint8_t* lig, const float* r32sq,
                                     int n, uint8_t* dirty, int* list, int* count, const int32_t* s_nbr, const int32_t* s_deg,
                                     const float* s_ew, int32_t* nbr, int32_t* deg, float* ew, const float* h1, const float* h2,
-                                    float* out1, float* out2, hipStream_t s) {
+                                    float* out1, float* out2, hipStream_t s, const uint8_t* keep1, const uint8_t* keep2) {
     if (n == 0) return hipSuccess;
     const long threads = (long)n * (H / 4);
     hipLaunchKernelGGL(graph_cache_begin_kernel, dim3((unsigned)((threads + 1023) / 1024)), dim3(1024), 0, s, x, graph_ptr, n_graphs,
-                       lig, r32sq, n, dirty, list, count, s_nbr, s_deg, s_ew, nbr, deg, ew, h1, h2, out1, out2);
+                       lig, r32sq, n, dirty, list, count, s_nbr, s_deg, s_ew, nbr, deg, ew, h1, h2, out1, out2, keep1, keep2);
     return hipGetLastError();
 }
 

@@ -118,11 +118,13 @@ hipError_t launch_knn_merge_gate(const float* packed, const float* x, const int3
 hipError_t launch_gate_mfma(const float* packed, const float* x, const int32_t* nbr, const int32_t* deg, int n_nodes,
                             float* e_w, hipStream_t s, RowList rows = {}, const unsigned* newmask = nullptr);
 // head of a graph-cached forward call in one launch: proximity flags -> `dirty`, their compaction -> `list` / `count` (zero on
-// entry), the pocket's graph -> nbr / deg / ew, the cached features of layers 0 / 1 -> out1 / out2 (graph_mfma.hip)
+// entry), the pocket's graph -> nbr / deg / ew, the cached features of layers 0 / 1 -> out1 / out2 (graph_mfma.hip); with `keep1` /
+// `keep2` (per-node flags) only into the flagged rows: the other rows of out1 / out2 already hold them (step cache, api.hip)
 hipError_t launch_graph_cache_begin(const float* x, const int32_t* graph_ptr, int n_graphs, const uint8_t* lig, const float* r32sq,
                                     int n, uint8_t* dirty, int* list, int* count, const int32_t* s_nbr, const int32_t* s_deg,
                                     const float* s_ew, int32_t* nbr, int32_t* deg, float* ew, const float* h1, const float* h2,
-                                    float* out1, float* out2, hipStream_t s);
+                                    float* out1, float* out2, hipStream_t s, const uint8_t* keep1 = nullptr,
+                                    const uint8_t* keep2 = nullptr);
 // MFMA node kernels (node_mfma.hip): P = h Wn + bn, q = MLP tail, Qt = folded query
 hipError_t launch_pack_node_tables(const PackBlocks& pb, hipStream_t s);     // node_mfma.hip part of stage 2
 // counter_zeroed: the caller has already set *count to zero on this stream (cbgx_unitransformer_forward zeroes all its list counters
@@ -138,11 +140,14 @@ hipError_t launch_mark_nbr(RowList rows, int n_upper, const int32_t* nbr, const 
 // q_direct (inputs above NODE_STAGE_MAX_ROWS only): q comes straight from h (node_query_kernel) and the q-hidden columns of P are
 // NOT produced -- for callers whose edge stage is all that reads P (the inference forward; the training tape keeps them)
 // fold (a list): Qt is produced for these rows instead of for all of `dst`;  no_fold: the stage ends with the query MLP (h2x_lig)
+// dst_all_columns (inputs above NODE_STAGE_MAX_ROWS only): ONE projection launch writes the own AND the PS columns of `dst`, nothing is
+// projected on `src` -- for P arrays that outlive the call and hold every other row already (step cache, api.hip)
 struct NodeStageOpts {
     bool large_lists = false;
     RowList fold;
     bool q_direct = false;
     bool no_fold = false;
+    bool dst_all_columns = false;
 };
 hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig, int n_nodes, const NodeBufs& b, RowList dst,
                             RowList src, hipStream_t s, const NodeStageOpts& o = {});

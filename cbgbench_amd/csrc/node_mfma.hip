@@ -1601,7 +1601,9 @@ hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig
             hipLaunchKernelGGL(node_proj_kernel<false>, proj_grid(chunks_all), dim3(256), 0, s, att, h, lig, b.P, n_nodes,
                                (const int*)nullptr, (const int*)nullptr, chunks_all);
     } else {
-        if (!two_jobs) {     // without a source list the PS columns are produced for every node
+        if (o.dst_all_columns && !fused) {
+            // (the destination launch below writes them)
+        } else if (!two_jobs) {     // without a source list the PS columns are produced for every node
             if (src.rows)
                 hipLaunchKernelGGL(node_proj_kernel<true>, proj_grid(CHUNKS_PS), dim3(256), 0, s, att, h, lig, b.P, n_nodes, src.rows,
                                    src.count, CHUNKS_PS);
@@ -1610,8 +1612,11 @@ hipError_t launch_node_mfma(const float* att, const float* h, const uint8_t* lig
                                    (const int*)nullptr, (const int*)nullptr, CHUNKS_PS);
         }
         if (!fused)
-            hipLaunchKernelGGL(node_proj_kernel<true>, proj_grid(chunks_own), dim3(256), 0, s, att, h, lig, b.P, n_nodes, dst.rows, dst.count,
-                               chunks_own);
+        {
+            const unsigned chunks_dst = o.dst_all_columns ? chunks_all : chunks_own;
+            hipLaunchKernelGGL(node_proj_kernel<true>, proj_grid(chunks_dst), dim3(256), 0, s, att, h, lig, b.P, n_nodes, dst.rows, dst.count,
+                               chunks_dst);
+        }
     }
     profile_mark_end(s);
     hipError_t e = hipGetLastError();

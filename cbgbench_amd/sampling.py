@@ -122,7 +122,7 @@ class BatchesInFlight:
         h[rec_rows] = self.context_embedder.embed_protein(v_rec, F.one_hot(batch["protein_aa_type"], NUM_AA).float())    # step-invariant
         st = {"B": B, "N": n_rec + n_lig, "n_lig": n_lig, "x": x, "h": h, "bl": bl, "br": br, "gen_l": gen_l, "batch_idx": batch_idx,
               "lig_flag": lig_flag, "gen_flag": gen_flag, "lig_rows": lig_rows, "rec_rows": rec_rows, "graph_ptr": graph_ptr,
-              "traj_x": None, "traj_c": None, "static_h": None}
+              "traj_x": None, "traj_c": None, "static_h": None, "step_cache": None}
         # every movable row is a ligand row: the h2x blocks fold the query in the edge kernel (CBGX_FWD_GEN_IS_LIGAND)
         st["gen_is_ligand"] = not bool(gen_r.any())
         csr = "lig_ptr" in self._step_operands
@@ -150,6 +150,8 @@ class BatchesInFlight:
         st["x_lig"], st["c_lig"] = x_lig.contiguous(), c_lig.contiguous()
         if dev.type == "cuda" and static_cache and st["gen_is_ligand"]:
             st["static_h"] = self.denoiser.static_context(x_rec, st["h"][rec_rows], st["br"], rec_rows, st["N"])
+            # the node stage and the outputs of layers 0 / 1 from step to step: a fresh block with every static context
+            st["step_cache"] = None if st["static_h"] is None else self.denoiser.new_step_cache(st["N"], dev)
         if keep_trajectory:
             # slot s+1 holds the state entering step s; slot 0 = final state (key -1 of the reference's dict)
             st["traj_x"] = torch.empty(T + 1, st["n_lig"], 3, dtype=torch.float32, device=dev)
@@ -181,7 +183,7 @@ class BatchesInFlight:
         """the denoiser on the composed arrays of the state -> (x', h', logits)"""
         return self.denoiser(x=st["x"], h=st["h"], batch_idx=st["batch_idx"], lig_flag=st["lig_flag"], gen_flag=st["gen_flag"],
                              graph_ptr=st["graph_ptr"], need_h=need_h, static_h=st["static_h"], workspace=workspace,
-                             h_on_sources=h_on_sources, gen_is_ligand=st["gen_is_ligand"])
+                             h_on_sources=h_on_sources, gen_is_ligand=st["gen_is_ligand"], step_cache=st.get("step_cache"))
 
     def _trajectory(self, st, out_dev, final=None):
         """the returned structure ``traj[t] = (pos, type_onehot, batch_idx)`` for t = T-1 .. -1 from the slots kept on the device (one

@@ -374,6 +374,19 @@ class UniTransformer(nn.Module):
         r32sq[rec_rows] = r32
         return (out[0], out[1], nbr.contiguous(), deg, ew, r32sq)
 
+    @staticmethod
+    def new_step_cache(n_nodes, device):
+        """A reset step-cache block for ``forward(..., step_cache=...)`` on inputs of ``n_nodes`` rows, or None where no call of that size
+        would use one (small inputs, ``CBGX_STEP_CACHE=0``).  One per sampling state, and a new one whenever the state's static context
+        is rebuilt (include/cbgx.h, cbgx_unitransformer_forward_step_cached)."""
+        lib = _native.lib()
+        need = lib.cbgx_step_cache_bytes(n_nodes)
+        if need == 0:
+            return None
+        block = torch.empty(need, dtype=torch.uint8, device=device)
+        _native.check(lib.cbgx_step_cache_reset(_native.ptr(block), need, n_nodes, _native.current_stream(device)), "cbgx_step_cache_reset")
+        return block
+
     def _as_u8(self, flag):
         """the uint8 copy of a boolean flag tensor that libcbgx reads.  A sampler hands the SAME two flag tensors to all T denoiser
         calls of a run; converting them each time was two elementwise launches per step (14 us of a 900 us one-graph step,
@@ -394,7 +407,7 @@ class UniTransformer(nn.Module):
         return u8
 
     def forward(self, x, h, batch_idx, lig_flag, gen_flag, graph_ptr=None, need_h=True, static_h=None,
-                ligand_outputs_only=False, workspace=None, h_on_sources=False, gen_is_ligand=False):
+                ligand_outputs_only=False, workspace=None, h_on_sources=False, gen_is_ligand=False, step_cache=None):
         """Same contract as the reference (unitransformer.py:102-123): returns (x', h', logits).
         ``batch_idx`` must be sorted (compose_context guarantees it).  ``graph_ptr`` (int32 CSR
         offsets) may be passed to avoid recomputing it from ``batch_idx`` every call.  ``need_h=False`` (samplers that
@@ -410,6 +423,8 @@ class UniTransformer(nn.Module):
         with ``need_h=False``; the other rows of ``h'`` are undefined, the logits are defined on those rows only.
         ``gen_is_ligand`` (inference): the caller promises that every ``gen_flag`` row is a ``lig_flag`` row (CBGX_FWD_GEN_IS_LIGAND): the
         h2x blocks then fold the query inside the edge kernel and skip the folded rows.
+        ``step_cache`` (inference, with ``static_h``; from ``new_step_cache``): the block that carries the node stage and the outputs of
+        layers 0 / 1 from one call of a sampling state to the next (cbgx_unitransformer_forward_step_cached; bit-identical results).
         ``workspace`` (inference): caller-owned scratch memory of at least ``workspace_bytes(N, B)`` bytes instead of the per-stream
         one the module keeps -- a captured hipGraph bakes the pointer in, so every captured sampling state brings its own."""
         if not x.is_cuda:
@@ -442,7 +457,15 @@ class UniTransformer(nn.Module):
         logits = torch.empty(N, self.out_classes, dtype=torch.float32, device=device)
         lib = _native.lib()
         flags = _native.FWD_GEN_IS_LIGAND if gen_is_ligand else 0
-        if static_h is not None:
+        if static_h is not None and step_cache is not None:
+            rc = lib.cbgx_unitransformer_forward_step_cached(
+                _native.ptr(packed), self.num_layers, self.out_classes, _native.ptr(x), _native.ptr(h),
+                _native.ptr(graph_ptr), _native.ptr(lig), _native.ptr(gen), N, B, _native.ptr(static_h[0]),
+                _native.ptr(static_h[1]), *[_native.ptr(t) for t in static_h[2:6]], _native.ptr(x_out),
+                _native.ptr(h_out), _native.ptr(logits), flags | (_native.FWD_H_ON_SOURCES if (h_on_sources and need_h) else 0),
+                _native.ptr(step_cache), step_cache.numel(), _native.ptr(ws), ws.numel(),
+                _native.current_stream(device))
+        elif static_h is not None:
             rc = lib.cbgx_unitransformer_forward_cached(
                 _native.ptr(packed), self.num_layers, self.out_classes, _native.ptr(x), _native.ptr(h),
                 _native.ptr(graph_ptr), _native.ptr(lig), _native.ptr(gen), N, B, _native.ptr(static_h[0]),

@@ -167,6 +167,33 @@ int cbgx_unitransformer_forward_cached(const float *packed, int num_layers, int 
                                        float *x_out, float *h_out, float *logits, unsigned flags,
                                        void *workspace, size_t workspace_bytes, void *stream);
 
+/* The cached call with a *step cache*: a block of device memory owned by one sampling state, which carries the node stage of layers
+ * 0 / 1 (P and q of every row) and those layers' output arrays from one denoiser call of the state to the next.  After the first call
+ * on a reset block, layer 0 projects the ligand rows only (the protein rows of h do not change during a run), layer 1 the rows whose
+ * layer-0 output can differ from the previous call's (D1 of this call and of the previous one), and only the rows the previous call
+ * overwrote are placed again from static_h1 / static_h2.  Every output is bit-identical to cbgx_unitransformer_forward_cached.
+ * The caller's promises: the protein rows of (x, h), the flags, the static context and the weights are those of the first call after
+ * the reset (a state whose static context is rebuilt gets a reset block); one call at a time per block, each ordered after the previous
+ * one (same stream, or an event).  Calls of other states, each with a block of its own, may run in between and beside it.
+ * The block serves graph-cached calls (all four static graph arrays given) of more than 8 192 nodes; in every other call, and with
+ * CBGX_STEP_CACHE=0 in the environment (read once per process), it is not touched and the launches are the cached call's.
+ * cbgx_step_cache_bytes: size of the block (0: no call of n_nodes would use one -- pass NULL).  cbgx_step_cache_reset: marks every row
+ * as not computed, on `stream`; nothing of an earlier run is read afterwards.  cbgx_step_cache_layout: byte offsets of the block's
+ * arrays, for tests: P0 [N,640], q0 [N,128], h1 [N,128], P1, q1, h2, then the per-node flags fresh0, prevD1, prevD2. */
+#define CBGX_STEP_CACHE_ARRAYS 9
+size_t cbgx_step_cache_bytes(int n_nodes);
+int cbgx_step_cache_reset(void *step_cache, size_t step_cache_bytes, int n_nodes, void *stream);
+int cbgx_step_cache_layout(int n_nodes, size_t *offsets);
+int cbgx_unitransformer_forward_step_cached(const float *packed, int num_layers, int num_classes,
+                                            const float *x, const float *h, const int32_t *graph_ptr,
+                                            const uint8_t *lig_flag, const uint8_t *gen_flag, int n_nodes, int n_graphs,
+                                            const float *static_h1, const float *static_h2,
+                                            const int32_t *static_nbr, const int32_t *static_deg,
+                                            const float *static_ew, const float *static_r32sq,
+                                            float *x_out, float *h_out, float *logits, unsigned flags,
+                                            void *step_cache, size_t step_cache_bytes,
+                                            void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- stages (also what the parity tests call one by one) ------------------------------------- */
 
 /* torch_cluster.knn_graph(x, k, batch, loop=False, flow='source_to_target') as called at
