@@ -106,6 +106,7 @@ EXPORTS = {
     "cbgx_ligand_bonds_fill": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "cbgx_ligand_rings": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "cbgx_ligand_aromatic": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "cbgx_ligand_valence": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "cbgx_ligand_pair_hist": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "cbgx_ligand_angles": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "cbgx_profile_begin": (_i, [_i]),

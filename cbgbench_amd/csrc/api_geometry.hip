@@ -1,5 +1,5 @@
-// libcbgx -- C ABI of the geometry report, of the bond list, of the ring sizes, of the aromatic report and of the distributions
-// (include/cbgx.h, geometry.hip, rings.hip, aromatic.hip, distributions.hip): argument checks, the ligand-size check, the launch
+// libcbgx -- C ABI of the geometry report, of the bond list, of the ring sizes, of the aromatic report, of the valence report and of the
+// distributions (include/cbgx.h, geometry.hip, rings.hip, aromatic.hip, valence.hip, distributions.hip): argument checks, the ligand-size check, the launch
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -135,6 +135,29 @@ int cbgx_ligand_aromatic(const uint8_t* z_lig, const uint8_t* flag_lig, const ui
     const hipError_t e = launch_ligand_aromatic(z_lig, flag_lig, atom_ring_min, lig_ptr, n_lig, n_graphs, bond_ptr, bond_index, n_bonds,
                                                 atom_out, bond_aromatic, graph_out, (hipStream_t)stream);
     if (e != hipSuccess) return set_error(CBGX_E_HIP, "ligand_aromatic: launch: %s", hipGetErrorString(e));
+    return CBGX_OK;
+}
+
+int cbgx_ligand_valence(const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs, const int32_t* bond_ptr,
+                        const int32_t* bond_index, const uint8_t* bond_order, const uint8_t* bond_aromatic, int n_bonds, int max_steps,
+                        uint8_t* implicit_h, uint8_t* atom_flags, uint8_t* bond_kekule, int32_t* graph_out, void* stream) {
+    if (n_graphs < 0 || n_lig < 0 || n_bonds < 0)
+        return set_error(CBGX_E_INVALID, "ligand_valence: negative count (B=%d n_lig=%d n_bonds=%d)", n_graphs, n_lig, n_bonds);
+    if (max_steps < 1 || max_steps > CBGX_VALENCE_MAX_STEPS)
+        return set_error(CBGX_E_INVALID, "ligand_valence: max_steps=%d outside 1 ... %d", max_steps, CBGX_VALENCE_MAX_STEPS);
+    if ((n_graphs > 0 && (!lig_ptr || !bond_ptr || !graph_out)) || (n_lig > 0 && (!z_lig || !implicit_h || !atom_flags)) ||
+        (n_bonds > 0 && (!bond_index || !bond_order || !bond_kekule)))
+        return set_error(CBGX_E_INVALID, "ligand_valence: NULL pointer");
+    if (n_graphs == 0) return CBGX_OK;
+    // no size is refused here (a graph over a limit is reported in its status), so lig_ptr is not read back: only whether the kernel could
+    hipPointerAttribute_t attr;
+    const hipError_t known = hipPointerGetAttributes(&attr, lig_ptr);
+    if (known != hipSuccess) (void)hipGetLastError();      // not an error of this call: the pointer is simply not the runtime's
+    if (known != hipSuccess || attr.type == hipMemoryTypeUnregistered)
+        return set_error(CBGX_E_INVALID, "ligand_valence: lig_ptr is not memory the device can read");
+    const hipError_t e = launch_ligand_valence(z_lig, lig_ptr, n_lig, n_graphs, bond_ptr, bond_index, bond_order, bond_aromatic, n_bonds,
+                                               max_steps, implicit_h, atom_flags, bond_kekule, graph_out, (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(CBGX_E_HIP, "ligand_valence: launch: %s", hipGetErrorString(e));
     return CBGX_OK;
 }
 

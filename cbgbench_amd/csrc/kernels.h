@@ -284,6 +284,12 @@ hipError_t launch_ligand_rings(const int32_t* lig_ptr, int n_lig, int n_graphs, 
 hipError_t launch_ligand_aromatic(const uint8_t* z_lig, const uint8_t* flag_lig, const uint8_t* atom_ring_min, const int32_t* lig_ptr,
                                   int n_lig, int n_graphs, const int32_t* bond_ptr, const int32_t* bond_index, int n_bonds,
                                   uint8_t* atom_out, uint8_t* bond_aromatic, int32_t* graph_out, hipStream_t s);
+// valence.hip: Kekule orders of the aromatic systems of that bond list (a bounded search, one system per lane), implicit hydrogens and
+// valence flags; one wave per graph
+hipError_t launch_ligand_valence(const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs, const int32_t* bond_ptr,
+                                 const int32_t* bond_index, const uint8_t* bond_order, const uint8_t* bond_aromatic, int n_bonds,
+                                 int max_steps, uint8_t* implicit_h, uint8_t* atom_flags, uint8_t* bond_kekule, int32_t* graph_out,
+                                 hipStream_t s);
 // distributions.hip: pair-distance histograms of the same ligands (two families, LDS integer histograms), and the bond angles of the
 // table-bond graph from its symmetric adjacency -- cosine, bin against a cosine table, canonical type; one workgroup per graph each
 hipError_t launch_ligand_pair_hist(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,

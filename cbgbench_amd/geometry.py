@@ -33,6 +33,13 @@ Deviations: the rules run to their fixed point (the reference applies each once)
 ``batch_distributions(..., aromatic=)`` it re-keys the bond-length and bond-angle histograms by four bond types (``n_orders=4``).
 ``sdf_record`` writes a sample as a V2000 record on the host.
 
+``ligand_valence`` / ``batch_valence`` / ``summarise_valence`` ask whether the sample is a molecule at all: Kekule orders for the aromatic
+bonds (per aromatic system the largest, lexicographically least set of double bonds that covers every carbon able to take one), implicit
+hydrogens and a valence check per atom against this library's own table, in one launch on the bond list and the aromatic report
+(``cbgx_ligand_valence``, csrc/valence.hip) -- the RDKit-free counterpart of kekulisation, ``evaluate_validity`` and the hydrogen counts
+behind ``evaluate_chem_*`` (repo/tools/rdkit_utils.py:522-640) and ``repo/tools/eval_atom_type.py``.  Deviations: table bonds and a
+property-defined Kekule choice; no charges.  ``formula`` / ``mol_weight`` are host helpers on the element counts.
+
 ``ligand_pair_hist`` / ``ligand_angles`` / ``batch_distributions`` / ``summarise_distributions`` are the rest of that report, the
 distributions it compares with a dataset's by Jensen-Shannon distance (``repo/tools/geometry/eval_bond_length.py``,
 ``eval_bond_angle.py``): pair-distance histograms (``All_12A``, ``CC_2A``; reproduced exactly: they need coordinates and elements only),
@@ -491,14 +498,168 @@ def summarise_aromatic(graph_counts):
     return summarise_aromatic_totals(aromatic_totals(graph_counts))
 
 
-# the four reports that are integer counts per molecule, for a driver that treats them alike: per-molecule columns -> totals (what ranks
+# ---- Kekule orders, implicit hydrogens and valence checks of the table-bond graph ---------------------------------------------------------
+# include/cbgx.h CBGX_VALENCE_MAX_ATOMS / _MAX_ELIGIBLE / _MAX_STEPS
+MAX_VALENCE_ATOMS, MAX_VALENCE_ELIGIBLE, MAX_VALENCE_STEPS = 256, 64, 65536
+# columns of ligand_valence's graph_counts (include/cbgx.h CBGX_VALENCE_GRAPH_COLS); el_c: atoms of element code c (H C N O F P S Cl)
+VALENCE_GRAPH_COLUMNS = (("n_atoms", "n_bonds", "n_fragments", "n_systems", "n_systems_failed", "n_kekule_double", "n_implicit_h",
+                          "n_exceeded", "n_unknown", "n_nhoh", "n_no") + tuple(f"el_{c}" for c in range(8))
+                         + ("valence_ok", "steps_max", "status"))
+# atom_flags bits and status bits (include/cbgx.h CBGX_VALENCE_*): a graph with status != 0 was not evaluated
+VALENCE_EXCEEDED, VALENCE_ON_FAILED_SYSTEM, VALENCE_UNKNOWN_ELEMENT, VALENCE_ON_AROMATIC_SYSTEM = 1, 2, 4, 8
+VALENCE_TOO_MANY_ATOMS, VALENCE_BAD_BONDS, VALENCE_NO_AROMATIC, VALENCE_SEARCH_LIMIT = 1, 4, 8, 16
+KEKULE_FAILED = 4                          # bond_kekule of the aromatic bonds of a system without a Kekule structure
+VALENCE_NOT_EVALUATED = 255
+ELEMENT_SYMBOLS = ("H", "C", "N", "O", "F", "P", "S", "Cl")                        # element codes 0 ... 7
+ATOMIC_WEIGHTS = (1.008, 12.011, 14.007, 15.999, 18.998, 30.974, 32.06, 35.45)     # standard atomic weights, in element-code order
+
+
+def ligand_valence(z_lig, lig_batch, n_graphs, bonds, aromatic=None, max_steps=MAX_VALENCE_STEPS):
+    """Kekule bond orders, implicit hydrogens and valence flags of the bond graphs of ``n_graphs`` ligands, one launch
+    (``cbgx_ligand_valence``, csrc/valence.hip; the definition is in include/cbgx.h) on the tensors' current stream: per aromatic system
+    (a connected component of the aromatic bonds) the largest, lexicographically least set of double bonds that covers every carbon able
+    to take one, found by a bounded search; then every atom's valence against this library's table (H 1, C 4, N 3, O 2, F 1, P 3 / 5,
+    S 2 / 4 / 6, Cl 1; no charges).
+
+    ``z_lig`` [n_lig] atomic numbers, ``lig_batch`` [n_lig] grouped by graph; ``bonds``: what ``ligand_bonds`` returned for the same atoms;
+    ``aromatic``: what ``ligand_aromatic`` returned for that list, or None: no bond is aromatic ('basic' atom types); ``max_steps``: the
+    search budget per system, 1 ... MAX_VALENCE_STEPS.  Returns device tensors: ``implicit_h`` [n_lig] uint8, ``atom_flags`` [n_lig] uint8
+    (VALENCE_EXCEEDED, _ON_FAILED_SYSTEM, _UNKNOWN_ELEMENT, _ON_AROMATIC_SYSTEM), ``bond_kekule`` [n_bonds] uint8 (1 ... 3; KEKULE_FAILED
+    = 4 on a system without a Kekule structure) and ``graph_counts`` [n_graphs, 22] int32 (VALENCE_GRAPH_COLUMNS).  A graph over a limit
+    (atoms; 64 eligible bonds or atoms of one system; the step budget), with a malformed list, or that the aromatic report did not
+    evaluate is not an error: its status is non-zero (VALENCE_*), its columns from n_fragments to steps_max are -1 and its bytes of the
+    three arrays 255.  Deviations from the reference: table bonds and a property-defined Kekule choice (the reference's orders come from
+    OpenBabel's perception, its Kekule form from RDKit's traversal); no charges: N(=O)=O, N-oxides and quaternary N are "exceeded".
+    There is no CPU path."""
+    dev = z_lig.device
+    _gpu_only(dev, "ligand_valence", "cbgx_ligand_valence")
+    n_graphs, max_steps = int(n_graphs), int(max_steps)
+    bond_index, bond_order = bonds["bond_index"], bonds["bond_order"]
+    given = [("lig_batch", lig_batch), ("bond_index", bond_index), ("bond_order", bond_order)]
+    if aromatic is not None:
+        given += [("aromatic_bond", aromatic["aromatic_bond"]), ("bond_type", aromatic["bond_type"])]
+    for name, t in given:
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, z_lig on {dev}")
+    if bond_index.dim() != 2 or bond_index.shape[0] != 2:
+        raise ValueError("bond_index must be [2, n_bonds]")
+    n_lig, n_bonds = int(z_lig.shape[0]), int(bond_index.shape[1])
+    if z_lig.shape != (n_lig,) or lig_batch.shape != (n_lig,):
+        raise ValueError("one atomic number and one graph index per atom")
+    if any(t.shape != (n_bonds,) for _, t in given[2:]):
+        raise ValueError("one bond_order (and one aromatic_bond and bond_type) per bond")
+    if not 1 <= max_steps <= MAX_VALENCE_STEPS:
+        raise ValueError(f"max_steps is 1 ... {MAX_VALENCE_STEPS}, not {max_steps}")
+    lig_ptr = _csr(lig_batch, n_graphs, "lig_batch")
+    z_lig = _z_bytes(z_lig)
+    bond_index, bond_ptr = bond_index.to(torch.int32).contiguous(), _bond_ptr(bond_index, n_lig)
+    bond_order = bond_order.to(torch.uint8).contiguous()
+    flag = None
+    if aromatic is not None:      # the bytes cbgx_ligand_aromatic wrote: 0, 1, or 255 where it did not evaluate the graph
+        flag = torch.where(aromatic["bond_type"] == BOND_TYPE_NOT_EVALUATED, torch.full_like(bond_order, VALENCE_NOT_EVALUATED),
+                           (aromatic["aromatic_bond"] != 0).to(torch.uint8)).contiguous()
+    implicit_h = torch.empty(n_lig, dtype=torch.uint8, device=dev)
+    atom_flags = torch.empty(n_lig, dtype=torch.uint8, device=dev)
+    bond_kekule = torch.empty(n_bonds, dtype=torch.uint8, device=dev)
+    graph_counts = torch.empty(n_graphs, len(VALENCE_GRAPH_COLUMNS), dtype=torch.int32, device=dev)
+    p = _native.ptr
+    _native.check(_native.lib().cbgx_ligand_valence(p(z_lig), p(lig_ptr), n_lig, n_graphs, p(bond_ptr), p(bond_index) if n_bonds else None,
+                                                    p(bond_order) if n_bonds else None, p(flag) if flag is not None and n_bonds else None,
+                                                    n_bonds, max_steps, p(implicit_h), p(atom_flags), p(bond_kekule) if n_bonds else None,
+                                                    p(graph_counts), _native.current_stream(dev)), "cbgx_ligand_valence")
+    return {"implicit_h": implicit_h, "atom_flags": atom_flags, "bond_kekule": bond_kekule, "graph_counts": graph_counts}
+
+
+def batch_valence(batch, x, c, lig_batch, mode, bonds=None, aromatic=None):
+    """``ligand_valence`` of a sampling state; ``bonds`` / ``aromatic``: what ``batch_bonds`` / ``batch_aromatic`` returned for the same
+    state.  ``bonds`` is computed here when None; so is ``aromatic`` when None and ``mode`` has aromatic atom types ('add_aromatic').  In
+    any other mode there are no flags to start from and no bond is aromatic"""
+    if bonds is None:
+        bonds = batch_bonds(batch, x, c, lig_batch, mode)
+    if aromatic is None and mode in _AROMATIC:
+        aromatic = batch_aromatic(batch, x, c, lig_batch, mode, bonds=bonds)
+    dev = bonds["bond_index"].device
+    lig_batch = lig_batch.to(dev)
+    _, z, n_graphs = _state_atoms(c, mode, lig_batch, {"num_graphs": bonds["graph_counts"].shape[0]}, dev)
+    return ligand_valence(z, lig_batch, n_graphs, bonds, aromatic)
+
+
+def formula(el_counts, n_h=0):
+    """Hill-order formula of the atoms per element code (``el_counts`` [8]: H C N O F P S Cl) with ``n_h`` implicit hydrogens added to
+    the explicit ones: C, H, then the other symbols alphabetically when there is carbon, else all alphabetically; '' for no atoms"""
+    count = {s: int(v) for s, v in zip(ELEMENT_SYMBOLS, el_counts)}
+    count["H"] += int(n_h)
+    symbols = sorted(s for s in count if count[s])
+    if count["C"]:
+        symbols = ["C"] + (["H"] if count["H"] else []) + [s for s in symbols if s not in ("C", "H")]
+    return "".join(s + (str(count[s]) if count[s] > 1 else "") for s in symbols)
+
+
+def mol_weight(el_counts, n_h=0):
+    """molecular weight: the fp64 dot product of ATOMIC_WEIGHTS with the atoms per element code, the ``n_h`` implicit hydrogens added to
+    el_0, summed in element-code order"""
+    counts = np.asarray([int(v) for v in el_counts], np.float64)
+    counts[0] += int(n_h)
+    total = 0.0
+    for w, k in zip(ATOMIC_WEIGHTS, counts):
+        total += w * float(k)
+    return total
+
+
+VALENCE_COUNT_KEYS = (("n_mol", "n_mol_evaluated", "n_mol_over_limit", "n_atoms", "n_bonds", "n_fragments", "n_systems", "n_systems_failed",
+                       "n_kekule_double", "n_implicit_h", "n_exceeded", "n_unknown", "n_nhoh", "n_no")
+                      + tuple(f"n_el_{c}" for c in range(8)) + ("n_valence_ok_mol", "n_valid_mol"))
+VALENCE_RATIOS = ("valence_ok_mol_ratio", "valid_mol_ratio", "kekulised_system_ratio", "exceeded_atom_ratio", "h_per_heavy_atom",
+                  "nhoh_per_mol", "no_per_mol", "mean_mol_weight")
+
+
+def valence_totals(graph_counts):
+    """per-molecule counts ``graph_counts`` [n_mol, 22] (VALENCE_GRAPH_COLUMNS; any array-like) -> the integer totals, in
+    VALENCE_COUNT_KEYS order.  Everything but n_mol and n_mol_over_limit is summed over the evaluated molecules (status == 0) only; a
+    molecule is valid iff valence_ok and n_fragments == 1"""
+    gc = _counts(graph_counts, VALENCE_GRAPH_COLUMNS)
+    ok = gc[gc[:, -1] == 0]
+    return ([int(gc.shape[0]), int(ok.shape[0]), int(gc.shape[0] - ok.shape[0])] + [int(v) for v in ok[:, :19].sum(0)]
+            + [int((ok[:, 19] == 1).sum()), int(((ok[:, 19] == 1) & (ok[:, 2] == 1)).sum())])
+
+
+def summarise_valence_totals(totals):
+    """the ratios (VALENCE_RATIOS), ``element_distribution`` and the totals as ``counts``, of integer totals in VALENCE_COUNT_KEYS order;
+    every ratio is over the EVALUATED molecules, a ratio over nothing is nan.  valence_ok_mol_ratio: no atom exceeded, no unknown
+    element, every aromatic system kekulised; valid_mol_ratio: that and one fragment -- the table-bond counterpart of a molecule RDKit
+    sanitises whose SMILES has no '.' (evaluate_validity, repo/tools/rdkit_utils.py:615-640); kekulised_system_ratio: solved systems /
+    systems; exceeded_atom_ratio: exceeded atoms / atoms; h_per_heavy_atom: implicit H / atoms that are not H; nhoh_per_mol / no_per_mol:
+    N and O with a hydrogen / N and O, per molecule (Lipinski's donors and acceptors); mean_mol_weight: ATOMIC_WEIGHTS over the element
+    counts with the implicit H, per molecule; element_distribution: the 8 shares of the element codes among the atoms that have one (what
+    repo/tools/eval_atom_type.py compares; no dataset constants ship)"""
+    c = {k: int(v) for k, v in zip(VALENCE_COUNT_KEYS, totals)}
+    el = [c[f"n_el_{k}"] for k in range(8)]
+    n_mol = c["n_mol_evaluated"]
+    return {"valence_ok_mol_ratio": _ratio(c["n_valence_ok_mol"], n_mol), "valid_mol_ratio": _ratio(c["n_valid_mol"], n_mol),
+            "kekulised_system_ratio": _ratio(c["n_systems"] - c["n_systems_failed"], c["n_systems"]),
+            "exceeded_atom_ratio": _ratio(c["n_exceeded"], c["n_atoms"]),
+            "h_per_heavy_atom": _ratio(c["n_implicit_h"], c["n_atoms"] - el[0]),
+            "nhoh_per_mol": _ratio(c["n_nhoh"], n_mol), "no_per_mol": _ratio(c["n_no"], n_mol),
+            "mean_mol_weight": _ratio(mol_weight(el, c["n_implicit_h"]), n_mol),
+            "element_distribution": [_ratio(v, sum(el)) for v in el], "counts": c}
+
+
+def summarise_valence(graph_counts):
+    """valence statistics of a set of molecules from integer per-molecule counts (``graph_counts`` [n_mol, 22], VALENCE_GRAPH_COLUMNS):
+    see ``summarise_valence_totals``"""
+    return summarise_valence_totals(valence_totals(graph_counts))
+
+
+# the five reports that are integer counts per molecule, for a driver that treats them alike: per-molecule columns -> totals (what ranks
 # add up; count_keys) -> ratios and ``counts``
 CountReport = collections.namedtuple("CountReport", "name graph_columns count_keys ratios totals summarise_totals")
 COUNT_REPORTS = (CountReport("geometry", GRAPH_COLUMNS, COUNT_KEYS, RATIOS, job_totals, summarise_totals),
                  CountReport("bonds", BOND_GRAPH_COLUMNS, BOND_COUNT_KEYS, BOND_RATIOS, bond_totals, summarise_bond_totals),
                  CountReport("rings", RING_GRAPH_COLUMNS, RING_COUNT_KEYS, RING_RATIOS, ring_totals, summarise_ring_totals),
                  CountReport("aromatic", AROMATIC_GRAPH_COLUMNS, AROMATIC_COUNT_KEYS, AROMATIC_RATIOS, aromatic_totals,
-                             summarise_aromatic_totals))
+                             summarise_aromatic_totals),
+                 CountReport("valence", VALENCE_GRAPH_COLUMNS, VALENCE_COUNT_KEYS, VALENCE_RATIOS, valence_totals,
+                             summarise_valence_totals))
 
 
 # ---- SDF (V2000) records of samples: host only -----------------------------------------------------------------------------------------

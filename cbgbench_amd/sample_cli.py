@@ -35,8 +35,11 @@ bond type, bond angles per angle type -- computed on the device in two more laun
 reconstruction rules over the chordless 5- and 6-cycles, bond type 4 for the edges of aromatic cycles -- computed on the device in one more
 launch per batch (``geometry.batch_aromatic``), and ``{out_dir}/aromatic_summary.json`` for the job; with ``--distributions`` the bond-length
 and bond-angle profiles are then keyed by four bond types (``6:6``, ``6:6:6``).
-``--sdf`` writes ``pocket_{i:05d}.sdf`` beside every result file: one V2000 record per sample, bond types from ``--aromatic`` when given,
-table-bond orders otherwise (``geometry.sdf_record``; host side, no RDKit).
+``--valence`` asks whether the sample is a molecule at all: Kekule orders for the aromatic bonds, implicit hydrogens and a valence check per
+atom on that graph, computed on the device in one more launch per batch (``geometry.batch_valence``), with the formula, the molecular
+weight and ``mol_valid`` per sample and ``{out_dir}/valence_summary.json`` for the job.
+``--sdf`` writes ``pocket_{i:05d}.sdf`` beside every result file: one V2000 record per sample, bond types the Kekule orders of ``--valence``
+when given, else from ``--aromatic`` when given, table-bond orders otherwise (``geometry.sdf_record``; host side, no RDKit).
 A checkpoint is the reference's format: ``{'config': ..., 'model': state_dict}`` (``sample.py:153-156``)."""
 import argparse
 import os
@@ -143,7 +146,7 @@ def decode_mode(plan_mode, config_mode, num_classes):
 def main(argv=None, stats=None):
     """``stats`` (optional dict): filled with the wall seconds of the phases (setup = config + model + weights, batch = prior
     construction, sample = model.sample incl. the trajectory download, write = per-pocket records and files) and, for every requested report
-    (geometry, bonds, rings, aromatic, distributions: evaluated in that order), its own launches and downloads, a part of write: the bond
+    (geometry, bonds, rings, aromatic, distributions, valence: evaluated in that order), its own launches and downloads, a part of write: the bond
     list and the ring report are made once per batch, and where they were not asked for their time goes to the first requested report
     in that order that needs them (cbgbench_amd/sample_reports.py)."""
     t_phase = time.perf_counter()
@@ -233,6 +236,17 @@ def main(argv=None, stats=None):
                          "atom types only.  A bond is aromatic as an edge of an aromatic cycle (the link of biphenyl is not).  "
                          "Independent of --bonds and --rings: without them bonds and rings are computed and not written.  With "
                          "--distributions the bond-length and bond-angle blocks are keyed by four bond types (6:6, 6:6:6)")
+    ap.add_argument("--valence", action="store_true",
+                    help="add the valence report to every sample (implicit_h and valence_flags per atom: 1 valence exceeded, 2 on an "
+                         "aromatic system without a Kekule structure, 4 unknown element, 8 on an aromatic system; bond_kekule [nb] aligned "
+                         "with the bond_index of --bonds: the aromatic bonds as 1 / 2, 4 where no Kekule structure exists; formula, "
+                         "mol_weight, n_nhoh, n_no, valence_ok, mol_valid = valence_ok and one fragment, valence_status), a `valence` "
+                         "dict of counts to every pocket record and {out_dir}/valence_summary.json, evaluated on the GPU in one launch "
+                         "per batch on the bond list and, with add_aromatic atom types, the aromatic report (cbgbench_amd/geometry.py); "
+                         "with basic atom types no bond is aromatic.  Valences from this library's table (H 1, C 4, N 3, O 2, F 1, P 3/5, "
+                         "S 2/4/6, Cl 1), no charges: a nitro group drawn N(=O)=O counts as exceeded.  TABLE bonds, not RDKit's.  A sample "
+                         "over a limit is reported (valence_status != 0) and left out of every ratio.  Independent of --bonds, --rings "
+                         "and --aromatic: without them they are computed and not written.  With --sdf the records carry bond_kekule")
     ap.add_argument("--sdf", action="store_true",
                     help="write pocket_XXXXX.sdf beside every pocket_XXXXX.pt: one V2000 record per sample with the positions the record "
                          "holds, bond types from --aromatic when given (4 = aromatic), else the table-bond orders (bonds are computed "

@@ -1,11 +1,12 @@
-"""The reports of ``sample_cli`` (--geometry, --bonds, --rings, --aromatic, --distributions, --sdf) in three stages: ``evaluate`` runs the
+"""The reports of ``sample_cli`` (--geometry, --bonds, --rings, --aromatic, --distributions, --valence, --sdf) in three stages: ``evaluate`` runs the
 requested reports of one batch on the GPU and returns plain dicts of CPU tensors; ``annotate`` / ``pocket_counts`` / ``pocket_files``
 turn those into the per-sample fields, the per-pocket dicts and the ``.sdf`` text on the host (CPU tensors in, no device); ``finish`` sums
 the job's integer totals over the ranks, writes ``*_summary.json`` and prints one line per report.
 
 Reports run in the order of ORDER.  What a report is computed from beside the state (NEEDS: the bond list, the ring report) is made at
 most once per batch and shared; a dependency that was not asked for is computed, used and not written, and its wall time goes to the first
-requested report in that order that needs it."""
+requested report in that order that needs it.  The valence report takes the aromatic report (and so the ring report) where the atom types
+have aromatic flags ('add_aromatic'); with any other vocabulary no bond is aromatic and it needs the bond list only."""
 import json
 import os
 import time
@@ -14,9 +15,19 @@ import numpy as np
 import torch
 
 from . import geometry, sharding
+from .config import _AROMATIC
 
-ORDER = ("geometry", "bonds", "rings", "aromatic", "distributions")
-NEEDS = {"rings": ("bonds",), "aromatic": ("bonds", "rings"), "distributions": ("bonds",)}
+ORDER = ("geometry", "bonds", "rings", "aromatic", "distributions", "valence")
+NEEDS = {"rings": ("bonds",), "aromatic": ("bonds", "rings"), "distributions": ("bonds",), "valence": ("bonds", "aromatic")}
+
+
+def needs(name, mode):
+    """what report ``name`` is computed from under the atom-type vocabulary ``mode``"""
+    if name == "valence" and mode not in _AROMATIC:
+        return ("bonds",)
+    return NEEDS.get(name, ())
+
+
 _COUNT_REPORTS = {rep.name: rep for rep in geometry.COUNT_REPORTS}
 # the refusals off the GPU, in the order they are made (the check of --aromatic's atom types comes before its own)
 _GPU_ONLY = {"geometry": "--geometry runs on the GPU (cbgx_ligand_geometry has no CPU fallback)",
@@ -24,6 +35,7 @@ _GPU_ONLY = {"geometry": "--geometry runs on the GPU (cbgx_ligand_geometry has n
              "rings": "--rings runs on the GPU (cbgx_ligand_rings has no CPU fallback)",
              "distributions": "--distributions runs on the GPU (cbgx_ligand_pair_hist / cbgx_ligand_angles have no CPU fallback)",
              "aromatic": "--aromatic runs on the GPU (cbgx_ligand_aromatic has no CPU fallback)",
+             "valence": "--valence runs on the GPU (cbgx_ligand_valence has no CPU fallback)",
              "sdf": "--sdf takes its bonds from the GPU (cbgx_ligand_bonds_count / _fill have no CPU fallback)"}
 # a count report's printed line: the ratios it names, and its own tail
 _LINE = {"geometry": (geometry.RATIOS, lambda c: f"{c['n_mol']} molecules, {c['n_atoms']} atoms"),
@@ -31,7 +43,10 @@ _LINE = {"geometry": (geometry.RATIOS, lambda c: f"{c['n_mol']} molecules, {c['n
          "rings": (tuple(f"ring_mol_ratio_{k}" for k in geometry.RING_SIZES) + ("macrocycle_mol_ratio", "ring_atom_ratio"),
                    lambda c: f"{c['n_mol_evaluated']} of {c['n_mol']} molecules evaluated, {c['n_rings']} rings"),
          "aromatic": (geometry.AROMATIC_RATIOS,
-                      lambda c: f"{c['n_mol_evaluated']} of {c['n_mol']} molecules evaluated, {c['n_aromatic_cycles']} aromatic rings")}
+                      lambda c: f"{c['n_mol_evaluated']} of {c['n_mol']} molecules evaluated, {c['n_aromatic_cycles']} aromatic rings"),
+         "valence": (geometry.VALENCE_RATIOS,
+                     lambda c: f"{c['n_mol_evaluated']} of {c['n_mol']} molecules evaluated, {c['n_systems_failed']} of {c['n_systems']} "
+                               f"aromatic systems without a Kekule structure")}
 
 
 def load_reference_distributions(path):
@@ -70,7 +85,7 @@ class SampleReports:
 
     def refuse(self, dev, atom_mode):
         """what cannot run is refused before any model is built; ``atom_mode()``: the vocabulary the samples are decoded with"""
-        for name in ("geometry", "bonds", "rings", "distributions", "aromatic", "sdf"):
+        for name in ("geometry", "bonds", "rings", "distributions", "aromatic", "valence", "sdf"):
             if name not in self.requested:
                 continue
             if name == "aromatic" and atom_mode() != "add_aromatic":
@@ -94,7 +109,7 @@ class SampleReports:
 
         def get(name):
             if name not in made:
-                deps = {dep: get(dep) for dep in NEEDS.get(name, ())}
+                deps = {dep: get(dep) for dep in needs(name, mode)}
                 if name == "geometry":
                     pocket = {k: batch[k].to(dev) for k in ("protein_pos", "protein_element", "protein_element_batch")}
                     made[name] = geometry.batch_geometry({**pocket, **info}, x, c, bidx, mode)
@@ -150,6 +165,20 @@ class SampleReports:
                 smp["bond_type"] = aro["bond_type"][b0:b1].clone()
                 smp["n_aromatic_rings"] = int(gc[g, 3])
                 smp["aromatic_status"] = int(gc[g, 9])
+        if "valence" in self.requested:
+            val, gc = ev["valence"], ev["valence"]["graph_counts"].to(torch.int64)
+            for g, (smp, (a0, a1), (b0, b1)) in enumerate(zip(samples, ranges(gc[:, 0]), ranges(gc[:, 1]))):
+                row = dict(zip(geometry.VALENCE_GRAPH_COLUMNS, gc[g].tolist()))
+                evaluated, el = row["status"] == 0, [row[f"el_{k}"] for k in range(8)]
+                smp["implicit_h"] = val["implicit_h"][a0:a1].clone()
+                smp["valence_flags"] = val["atom_flags"][a0:a1].clone()
+                smp["bond_kekule"] = val["bond_kekule"][b0:b1].clone()
+                smp["formula"] = geometry.formula(el, row["n_implicit_h"]) if evaluated else ""
+                smp["mol_weight"] = geometry.mol_weight(el, row["n_implicit_h"]) if evaluated else float("nan")
+                smp["n_nhoh"], smp["n_no"] = row["n_nhoh"], row["n_no"]
+                smp["valence_ok"] = evaluated and row["valence_ok"] == 1
+                smp["mol_valid"] = smp["valence_ok"] and row["n_fragments"] == 1
+                smp["valence_status"] = row["status"]
         if "distributions" in self.requested:
             dists, gc = ev["distributions"], ev["distributions"]["graph_counts"]
             for g, (smp, (a0, a1), (n0, n1)) in enumerate(zip(samples, ranges(gc[:, 0]), ranges(gc[:, 2]))):
@@ -175,8 +204,8 @@ class SampleReports:
 
     def pocket_files(self, stem, samples, ev, g0):
         """(file name, text) of what is written beside a pocket's record ``stem``.pt: with --sdf one V2000 record per sample of the pocket
-        (``samples``: its records, graphs g0 ... of the batch), bond types from --aromatic where that report evaluated the sample, else the
-        table-bond orders; a sample ``sdf_record`` refuses is left out and counted"""
+        (``samples``: its records, graphs g0 ... of the batch), bond types: the Kekule orders of --valence where that report evaluated the
+        sample (no type 4 but on a system without a Kekule structure), else from --aromatic where that report did, else the table-bond orders; a sample ``sdf_record`` refuses is left out and counted"""
         if "sdf" not in self.requested:
             return []
         bonds, gc = ev["bonds"], ev["bonds"]["graph_counts"]
@@ -185,6 +214,8 @@ class SampleReports:
             (a0, _), (b0, b1) = atoms[g0 + j], rows[g0 + j]
             evaluated = "aromatic" in self.requested and int(ev["aromatic"]["graph_counts"][g0 + j, 9]) == 0
             types = ev["aromatic"]["bond_type"][b0:b1] if evaluated else bonds["bond_order"][b0:b1]
+            if "valence" in self.requested and int(ev["valence"]["graph_counts"][g0 + j, -1]) == 0:
+                types = ev["valence"]["bond_kekule"][b0:b1]
             try:
                 records.append(geometry.sdf_record(f"{stem}_sample_{j}", smp["pos"], smp["atom"], bonds["bond_index"][:, b0:b1] - a0, types))
                 self.sdf_written += 1
@@ -200,7 +231,7 @@ class SampleReports:
             with open(os.path.join(out_dir, name + "_summary.json"), "w") as f:
                 json.dump(summary, f, indent=1, sort_keys=True)
 
-        for name in ("geometry", "bonds", "rings", "distributions", "aromatic"):
+        for name in ("geometry", "bonds", "rings", "distributions", "aromatic", "valence"):
             if name not in self.requested:
                 continue
             if name == "distributions":

@@ -872,6 +872,75 @@ int cbgx_ligand_aromatic(const uint8_t *z_lig, const uint8_t *flag_lig, const ui
                          int n_graphs, const int32_t *bond_ptr, const int32_t *bond_index, int n_bonds, uint8_t *atom_out,
                          uint8_t *bond_aromatic, int32_t *graph_out, void *stream);
 
+/* ---- Kekule bond orders, implicit hydrogens and valence checks of the table-bond graph of sampled ligands (valence.hip) ----------------
+ * Is the sample a molecule at all?  The reference decides that after reconstruct_mol (repo/tools/rdkit_utils.py:522-590), when RDKit
+ *   kekulises the aromatic bonds, assigns implicit hydrogens and checks valences, and evaluate_validity (:615-640) adds "one piece".
+ *   Here the same questions are answered on the bond list of cbgx_ligand_bonds_fill and the aromatic bonds of cbgx_ligand_aromatic, one
+ *   launch, one wave per graph, integer work only.  Deviations: these are TABLE bonds (the reference's orders come from OpenBabel's
+ *   geometric perception); the Kekule structure is chosen by a property (below), not by RDKit's traversal; no charges are modelled: a
+ *   nitro group drawn N(=O)=O, an N-oxide and a quaternary N count as "valence exceeded".
+ * Inputs: z_lig [n_lig] atomic numbers; lig_ptr [B + 1], bond_ptr [n_lig + 1], bond_index [2, n_bonds] as cbgx_ligand_rings takes them;
+ *   bond_order [n_bonds] in 1..3; bond_aromatic [n_bonds] as cbgx_ligand_aromatic writes it: 1 aromatic, 255 not evaluated, anything else
+ *   not aromatic; NULL means all 0 (8-type 'basic' configs); max_steps in 1 ... CBGX_VALENCE_MAX_STEPS.
+ * Valence table (of this library; NOT the stability table of cbgx_ligand_geometry): H {1}, C {4}, N {3}, O {2}, F {1}, P {3, 5},
+ *   S {2, 4, 6}, Cl {1}.  v0(z) is its smallest entry.
+ * Aromatic system: a connected component of the graph formed by the bonds with bond_aromatic == 1.  For an atom a of a system: k(a) = the
+ *   number of its aromatic bonds, s(a) = the sum of the orders of its other bonds, f(a) = v0(z_a) - s(a) - k(a).  a is a CANDIDATE if
+ *   z in {6, 7} and f(a) >= 1, and a MUST atom if it is a candidate with z = 6.  (O, S and P never take a ring double bond: furan,
+ *   thiophene.  A carbon with an exocyclic double bond has f = 0 and takes none: pyridone.)
+ * Eligible bonds of a system: e_0 < ... < e_(m-1), its aromatic bonds both of whose ends are candidates, in list order.  last(a) = the
+ *   largest p with a in e_p; n_c = the number of atoms that occur in them.
+ * Kekule structure of a system: a set M of eligible bonds such that no two share an atom, every must atom is covered, M has the largest
+ *   size among such sets, and among those of the largest size its sorted list of positions is lexicographically least.  (Imidazole's
+ *   tautomer is decided by the order of the list; the largest size makes a two-neighbour N pyridine-type where it can be and N-H where
+ *   it cannot.)  If no such M exists the system has FAILED (cyclopentadienyl).
+ * Search -- written out because its step count is part of the interface.  A system with more than CBGX_VALENCE_MAX_ELIGIBLE eligible
+ *   bonds, or more than CBGX_VALENCE_MAX_ELIGIBLE atoms in them, is not searched (SEARCH_LIMIT).  Otherwise, if a must atom occurs in
+ *   no eligible bond the system fails in 1 step.  Otherwise node(0, {}, 0) runs, where node(p, M, dead) is:
+ *     steps += 1;
+ *     if p == m: best = M if there is no best yet or |M| > |best|; return;
+ *     if best exists and |M| + floor((n_c - 2 |M| - dead) / 2) <= |best|: return;
+ *     e_p = (i, j);
+ *     include: if i and j are both unmatched by M: node(p + 1, M + {e_p}, dead);
+ *     exclude: D = the ends of e_p that are unmatched by M and have last == p; if no atom of D is a must atom: node(p + 1, M, dead + |D|).
+ *   Include-first order visits sets of equal size in lexicographic order: the first best of the final size is the required M; no best
+ *   at the end: failed.  A search that would take more than max_steps steps is abandoned (SEARCH_LIMIT).
+ * After the search: bond_kekule = 2 for the bonds of M and 1 for the other aromatic bonds of a solved system, 4 for every aromatic bond
+ *   of a failed system, bond_order for every other bond.  v(a) = the sum of bond_kekule over a's bonds, a 4 counted as 1.  implicit_h(a) =
+ *   (the smallest table entry >= v(a)) - v(a); without such an entry the atom is EXCEEDED and implicit_h = 0.  An atom outside the eight
+ *   elements has the flag UNKNOWN_ELEMENT only and implicit_h 0 (the bond list holds no bond of such an atom).
+ * Outputs, dense, every element of every graph's ranges written: implicit_h [n_lig] uint8; atom_flags [n_lig] uint8 (CBGX_VALENCE_EXCEEDED,
+ *   _ON_FAILED_SYSTEM, _UNKNOWN_ELEMENT, _ON_AROMATIC_SYSTEM); bond_kekule [n_bonds] uint8; graph_out [B, CBGX_VALENCE_GRAPH_COLS] int32:
+ *   n_atoms, n_bonds, n_fragments (the components of the bond list, every atom counted: column 3 of cbgx_ligand_bonds_count), n_systems,
+ *   n_systems_failed, n_kekule_double, n_implicit_h, n_exceeded, n_unknown, n_nhoh (z in {7, 8} and implicit_h >= 1), n_no (z in {7, 8}),
+ *   el_0 ... el_7 (atoms per element code H C N O F P S Cl), valence_ok (n_atoms > 0 and n_exceeded == n_unknown == n_systems_failed ==
+ *   0), steps_max (the largest step count among the graph's systems, 0 without systems), status.
+ * Status, per graph, never an error: CBGX_VALENCE_TOO_MANY_ATOMS (more than CBGX_VALENCE_MAX_ATOMS atoms), CBGX_VALENCE_BAD_BONDS (the
+ *   conditions of CBGX_RINGS_BAD_BONDS, or a bond_order outside 1..3), CBGX_VALENCE_NO_AROMATIC (a bond of the graph has bond_aromatic ==
+ *   255) -- these three are set side by side --, CBGX_VALENCE_SEARCH_LIMIT (none of those three, and a system that is not searched or
+ *   whose search is abandoned).  With status != 0 the columns from n_fragments on, except status, are -1 and the graph's bytes of the
+ *   three arrays are 255; n_atoms and n_bonds are the (clamped) sizes of the two ranges.  Every entry of lig_ptr, bond_ptr and
+ *   bond_index is clamped or checked before it is used as an index, as in cbgx_ligand_aromatic, and overlapping ranges of a malformed
+ *   lig_ptr or bond_ptr are undefined in the same way.  No atomics on memory; nothing in the outputs depends on scheduling.
+ * Returns 0, and 0 without a launch when B == 0.  CBGX_E_INVALID before any dereference or launch: negative counts, max_steps outside
+ *   1 ... CBGX_VALENCE_MAX_STEPS, a NULL pointer with a non-zero count (bond_index, bond_order and bond_kekule may be NULL when n_bonds
+ *   == 0; bond_aromatic always), lig_ptr the device cannot read. */
+#define CBGX_VALENCE_MAX_ATOMS 256
+#define CBGX_VALENCE_MAX_ELIGIBLE 64
+#define CBGX_VALENCE_MAX_STEPS 65536
+#define CBGX_VALENCE_GRAPH_COLS 22   /* n_atoms, n_bonds, n_fragments, n_systems, n_systems_failed, n_kekule_double, n_implicit_h, n_exceeded, n_unknown, n_nhoh, n_no, el_0 ... el_7, valence_ok, steps_max, status */
+#define CBGX_VALENCE_EXCEEDED 1
+#define CBGX_VALENCE_ON_FAILED_SYSTEM 2
+#define CBGX_VALENCE_UNKNOWN_ELEMENT 4
+#define CBGX_VALENCE_ON_AROMATIC_SYSTEM 8
+#define CBGX_VALENCE_TOO_MANY_ATOMS 1
+#define CBGX_VALENCE_BAD_BONDS 4
+#define CBGX_VALENCE_NO_AROMATIC 8
+#define CBGX_VALENCE_SEARCH_LIMIT 16
+int cbgx_ligand_valence(const uint8_t *z_lig, const int32_t *lig_ptr, int n_lig, int n_graphs, const int32_t *bond_ptr,
+                        const int32_t *bond_index, const uint8_t *bond_order, const uint8_t *bond_aromatic, int n_bonds, int max_steps,
+                        uint8_t *implicit_h, uint8_t *atom_flags, uint8_t *bond_kekule, int32_t *graph_out, void *stream);
+
 /* ---- distributions of sampled ligands: pair distances, bond lengths, bond angles (distributions.hip) -----------------------------------
  * The rest of the reference's geometry report (evaluate_scripts/evaluate_geom_single.py; repo/tools/geometry/eval_bond_length.py,
  *   eval_bond_angle.py): histograms that are compared with a dataset's by Jensen-Shannon distance.  Distances and element codes are those
