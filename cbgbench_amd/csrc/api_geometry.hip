@@ -1,5 +1,6 @@
-// libcbgx -- C ABI of the geometry report, of the bond list, of the ring sizes, of the aromatic report, of the valence report and of the
-// distributions (include/cbgx.h, geometry.hip, rings.hip, aromatic.hip, valence.hip, distributions.hip): argument checks, the ligand-size check, the launch
+// libcbgx -- C ABI of the geometry report, of the bond list, of the ring sizes, of the aromatic report, of the valence report, of the
+// interaction report and of the distributions (include/cbgx.h, geometry.hip, rings.hip, aromatic.hip, valence.hip, interactions.hip,
+// distributions.hip): argument checks, the ligand-size check, the launch
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -158,6 +159,68 @@ int cbgx_ligand_valence(const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig,
     const hipError_t e = launch_ligand_valence(z_lig, lig_ptr, n_lig, n_graphs, bond_ptr, bond_index, bond_order, bond_aromatic, n_bonds,
                                                max_steps, implicit_h, atom_flags, bond_kekule, graph_out, (hipStream_t)stream);
     if (e != hipSuccess) return set_error(CBGX_E_HIP, "ligand_valence: launch: %s", hipGetErrorString(e));
+    return CBGX_OK;
+}
+
+// no size is refused by the two interaction entries (a graph over a limit is reported in its status), so no CSR is read back: only
+// whether the kernel could touch what it is handed.  EVERY array with a non-zero count is asked for, in argument order: a pointer the
+// runtime does not know (plain host memory) is refused here and never reaches a launch
+struct DeviceArray { const char* name; const void* p; int count; };
+
+static int device_visible(const char* who, const DeviceArray* arrays, int n_arrays) {
+    for (int a = 0; a < n_arrays; ++a) {
+        if (!arrays[a].p || arrays[a].count <= 0) continue;
+        hipPointerAttribute_t attr;
+        const hipError_t known = hipPointerGetAttributes(&attr, arrays[a].p);
+        if (known != hipSuccess) (void)hipGetLastError();      // not an error of this call: the pointer is simply not the runtime's
+        if (known != hipSuccess || attr.type == hipMemoryTypeUnregistered)
+            return set_error(CBGX_E_INVALID, "%s: %s is not memory the device can read", who, arrays[a].name);
+    }
+    return CBGX_OK;
+}
+
+int cbgx_pocket_types(const float* x_rec, const uint8_t* z_rec, const int32_t* rec_ptr, int n_rec, int n_graphs, const uint8_t* rec_aa,
+                      const uint8_t* rec_backbone, uint8_t* rec_type, void* stream) {
+    if (n_graphs < 0 || n_rec < 0) return set_error(CBGX_E_INVALID, "pocket_types: negative count (B=%d n_rec=%d)", n_graphs, n_rec);
+    if ((n_graphs > 0 && !rec_ptr) || (n_rec > 0 && (!x_rec || !z_rec || !rec_aa || !rec_backbone || !rec_type)))
+        return set_error(CBGX_E_INVALID, "pocket_types: NULL pointer");
+    if (n_graphs == 0) return CBGX_OK;
+    const DeviceArray arrays[] = {{"rec_ptr", rec_ptr, n_graphs + 1}, {"x_rec", x_rec, n_rec}, {"z_rec", z_rec, n_rec},
+                                  {"rec_aa", rec_aa, n_rec}, {"rec_backbone", rec_backbone, n_rec}, {"rec_type", rec_type, n_rec}};
+    const int rc = device_visible("pocket_types", arrays, (int)(sizeof(arrays) / sizeof(arrays[0])));
+    if (rc != CBGX_OK) return rc;
+    const hipError_t e = launch_pocket_types(x_rec, z_rec, rec_ptr, n_rec, n_graphs, rec_aa, rec_backbone, rec_type, (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(CBGX_E_HIP, "pocket_types: launch: %s", hipGetErrorString(e));
+    return CBGX_OK;
+}
+
+int cbgx_ligand_interactions(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, const float* x_rec,
+                             const uint8_t* rec_type, const int32_t* rec_ptr, int n_rec, int n_graphs, const int32_t* bond_ptr,
+                             const int32_t* bond_index, const uint8_t* bond_kekule, const uint8_t* bond_aromatic, int n_bonds,
+                             const uint8_t* implicit_h, const uint8_t* atom_flags, const int32_t* valence_status, double* atom_terms,
+                             uint8_t* lig_type, uint8_t* bond_rotatable, double* graph_terms, int32_t* graph_out, void* stream) {
+    if (n_graphs < 0 || n_lig < 0 || n_rec < 0 || n_bonds < 0)
+        return set_error(CBGX_E_INVALID, "ligand_interactions: negative count (B=%d n_lig=%d n_rec=%d n_bonds=%d)", n_graphs, n_lig, n_rec,
+                         n_bonds);
+    if ((n_graphs > 0 && (!lig_ptr || !rec_ptr || !bond_ptr || !valence_status || !graph_terms || !graph_out)) ||
+        (n_lig > 0 && (!x_lig || !z_lig || !implicit_h || !atom_flags || !atom_terms || !lig_type)) || (n_rec > 0 && (!x_rec || !rec_type)) ||
+        (n_bonds > 0 && (!bond_index || !bond_kekule || !bond_rotatable)))
+        return set_error(CBGX_E_INVALID, "ligand_interactions: NULL pointer");
+    if (n_graphs == 0) return CBGX_OK;
+    const DeviceArray arrays[] = {
+        {"lig_ptr", lig_ptr, n_graphs + 1}, {"x_lig", x_lig, n_lig}, {"z_lig", z_lig, n_lig}, {"x_rec", x_rec, n_rec},
+        {"rec_type", rec_type, n_rec}, {"rec_ptr", rec_ptr, n_graphs + 1}, {"bond_ptr", bond_ptr, n_lig + 1},
+        {"bond_index", bond_index, n_bonds}, {"bond_kekule", bond_kekule, n_bonds}, {"bond_aromatic", bond_aromatic, n_bonds},
+        {"implicit_h", implicit_h, n_lig}, {"atom_flags", atom_flags, n_lig}, {"valence_status", valence_status, n_graphs},
+        {"atom_terms", atom_terms, n_lig}, {"lig_type", lig_type, n_lig}, {"bond_rotatable", bond_rotatable, n_bonds},
+        {"graph_terms", graph_terms, n_graphs}, {"graph_out", graph_out, n_graphs}};
+    const int rc = device_visible("ligand_interactions", arrays, (int)(sizeof(arrays) / sizeof(arrays[0])));
+    if (rc != CBGX_OK) return rc;
+    const hipError_t e = launch_ligand_interactions(x_lig, z_lig, lig_ptr, n_lig, x_rec, rec_type, rec_ptr, n_rec, n_graphs, bond_ptr,
+                                                    bond_index, bond_kekule, bond_aromatic, n_bonds, implicit_h, atom_flags,
+                                                    valence_status, atom_terms, lig_type, bond_rotatable, graph_terms, graph_out,
+                                                    (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(CBGX_E_HIP, "ligand_interactions: launch: %s", hipGetErrorString(e));
     return CBGX_OK;
 }
 

@@ -1,4 +1,4 @@
-// libcbgx -- what the translation units of the geometry reports share (geometry.hip, distributions.hip): the limits, the element codes,
+// libcbgx -- what the translation units of the geometry reports share (geometry.hip, distributions.hip, interactions.hip): the limits, the element codes,
 // the constant tables as a compile-time initialiser, and the fp64 squared distance.  The sources and the meaning of the constants are in
 // the head of geometry.hip.  A translation unit that includes this keeps contraction off (#pragma clang fp contract(off)): geo_dist2's
 // products and sums are plain operators.
@@ -56,6 +56,45 @@ constexpr GeoTables make_geo_tables() {
     for (int c = 0; c < GEO_VDW; ++c) { t.z[c] = (uint8_t)zs[c]; t.radius[c] = r[c]; }
     for (int c = 0; c < GEO_EL; ++c) t.allowed[c] = val[c];
     t.tolerance = 0.4;
+    return t;
+}
+
+// ---- the interaction report (interactions.hip; the definition is in include/cbgx.h, cbgx_pocket_types / cbgx_ligand_interactions) ------
+// A type byte: the element code 1 ... 7 (C N O F P S Cl; 0: takes no part) in its low three bits, and the three property bits.
+constexpr int IA_RES = 20;        // residue indices 0 ... 19 in the reference's aa_name_number order; index IA_RES stands for any other
+
+enum : int { AA_ALA = 0, AA_CYS, AA_ASP, AA_GLU, AA_PHE, AA_GLY, AA_HIS, AA_ILE, AA_LYS, AA_LEU, AA_MET, AA_ASN, AA_PRO, AA_GLN, AA_ARG,
+             AA_SER, AA_THR, AA_VAL, AA_TRP, AA_TYR };
+
+struct InteractionTables {
+    double radius[GEO_EL];                // Vina's atom radii by element code (Trott & Olson 2010); 0 for H
+    double c_bond[4];                     // [1 N, 2 O, 3 S]: the C-X single bond length + margin in pm, as the fp64 value p is compared with
+    uint8_t n_type[2][IA_RES + 1];        // [backbone][residue] property bits of a pocket nitrogen
+    uint8_t o_type[2][IA_RES + 1];        // ... of a pocket oxygen
+};
+
+constexpr InteractionTables make_interaction_tables() {
+    constexpr uint8_t don = CBGX_INTERACTIONS_DONOR, acc = CBGX_INTERACTIONS_ACCEPTOR;
+    constexpr int n_donor_side[] = {AA_LYS, AA_ARG, AA_ASN, AA_GLN, AA_TRP};
+    constexpr int o_donor_side[] = {AA_SER, AA_THR, AA_TYR};
+    InteractionTables t{};
+    //                        H    C    N    O    F    P    S    Cl
+    constexpr double r[] = {0.0, 1.9, 1.8, 1.7, 1.5, 2.1, 2.0, 1.8};
+    for (int c = 0; c < GEO_EL; ++c) t.radius[c] = r[c];
+    const GeoTables geo = make_geo_tables();
+    t.c_bond[0] = 0.0;
+    t.c_bond[1] = (double)(geo.bond_pm[0][EL_C][EL_N] + geo.margin[0]);
+    t.c_bond[2] = (double)(geo.bond_pm[0][EL_C][EL_O] + geo.margin[0]);
+    t.c_bond[3] = (double)(geo.bond_pm[0][EL_C][EL_S] + geo.margin[0]);
+    for (int a = 0; a <= IA_RES; ++a) {
+        t.n_type[0][a] = 0;               // side chain: neither, but for the residues below
+        t.n_type[1][a] = don;             // backbone N-H
+        t.o_type[0][a] = t.o_type[1][a] = acc;
+    }
+    t.n_type[1][AA_PRO] = 0;              // no hydrogen on proline's ring nitrogen
+    for (int a : n_donor_side) t.n_type[0][a] = don;
+    t.n_type[0][AA_HIS] = don | acc;      // no protonation state: both, always
+    for (int a : o_donor_side) t.o_type[0][a] = don | acc;
     return t;
 }
 

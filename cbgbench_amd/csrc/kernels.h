@@ -290,6 +290,16 @@ hipError_t launch_ligand_valence(const uint8_t* z_lig, const int32_t* lig_ptr, i
                                  const int32_t* bond_index, const uint8_t* bond_order, const uint8_t* bond_aromatic, int n_bonds,
                                  int max_steps, uint8_t* implicit_h, uint8_t* atom_flags, uint8_t* bond_kekule, int32_t* graph_out,
                                  hipStream_t s);
+// interactions.hip: donor / acceptor / hydrophobic types of the pocket atoms from the residue table (a carbon's table bonds to N, O, S
+// included), then ligand types, rotatable bonds and the five Vina-form pair terms against the typed pocket; one workgroup per graph each
+hipError_t launch_pocket_types(const float* x_rec, const uint8_t* z_rec, const int32_t* rec_ptr, int n_rec, int n_graphs,
+                               const uint8_t* rec_aa, const uint8_t* rec_backbone, uint8_t* rec_type, hipStream_t s);
+hipError_t launch_ligand_interactions(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, const float* x_rec,
+                                      const uint8_t* rec_type, const int32_t* rec_ptr, int n_rec, int n_graphs, const int32_t* bond_ptr,
+                                      const int32_t* bond_index, const uint8_t* bond_kekule, const uint8_t* bond_aromatic, int n_bonds,
+                                      const uint8_t* implicit_h, const uint8_t* atom_flags, const int32_t* valence_status,
+                                      double* atom_terms, uint8_t* lig_type, uint8_t* bond_rotatable, double* graph_terms,
+                                      int32_t* graph_out, hipStream_t s);
 // distributions.hip: pair-distance histograms of the same ligands (two families, LDS integer histograms), and the bond angles of the
 // table-bond graph from its symmetric adjacency -- cosine, bin against a cosine table, canonical type; one workgroup per graph each
 hipError_t launch_ligand_pair_hist(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,

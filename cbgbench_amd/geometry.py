@@ -40,6 +40,15 @@ hydrogens and a valence check per atom against this library's own table, in one 
 behind ``evaluate_chem_*`` (repo/tools/rdkit_utils.py:522-640) and ``repo/tools/eval_atom_type.py``.  Deviations: table bonds and a
 property-defined Kekule choice; no charges.  ``formula`` / ``mol_weight`` are host helpers on the element counts.
 
+``pocket_types`` / ``ligand_interactions`` / ``batch_interactions`` / ``summarise_interactions`` ask how the sample sits in its pocket:
+donor / acceptor / hydrophobic types of both sides (the pocket's from a residue table, the ligand's from the bond list and the valence
+report), rotatable bonds, and the five pair terms of the published Vina scoring function (Trott & Olson 2010) summed in a fixed order, in
+two launches (``cbgx_pocket_types`` / ``cbgx_ligand_interactions``, csrc/interactions.hip) -- where the reference runs
+``vina_task.run(mode='score_only')`` (evaluate_scripts/evaluate_chem_single.py:44-49) and PLIP (repo/tools/interaction.py).  A score in
+Vina's functional form on this library's own atom typing: NOT the Vina program, not validated against it.  Deviations: table bonds, no
+hydrogens or protonation states in the pocket, an acceptor rule of our own for N, no intramolecular term, no metals, no Br / I,
+non-strict rotatable bonds.
+
 ``ligand_pair_hist`` / ``ligand_angles`` / ``batch_distributions`` / ``summarise_distributions`` are the rest of that report, the
 distributions it compares with a dataset's by Jensen-Shannon distance (``repo/tools/geometry/eval_bond_length.py``,
 ``eval_bond_angle.py``): pair-distance histograms (``All_12A``, ``CC_2A``; reproduced exactly: they need coordinates and elements only),
@@ -648,6 +657,199 @@ def summarise_valence(graph_counts):
     """valence statistics of a set of molecules from integer per-molecule counts (``graph_counts`` [n_mol, 22], VALENCE_GRAPH_COLUMNS):
     see ``summarise_valence_totals``"""
     return summarise_valence_totals(valence_totals(graph_counts))
+
+
+# ---- typed pocket contacts and a score in Vina's functional form --------------------------------------------------------------------------
+MAX_INTERACTION_ATOMS = 256                # include/cbgx.h CBGX_INTERACTIONS_MAX_ATOMS
+INTERACTION_TERMS = ("gauss1", "gauss2", "repulsion", "hydrophobic", "hbond")
+# columns of ligand_interactions' graph_counts (include/cbgx.h CBGX_INTERACTIONS_GRAPH_COLS)
+INTERACTION_GRAPH_COLUMNS = ("n_atoms", "n_bonds", "n_rotatable", "n_donors", "n_acceptors", "n_hydrophobic_atoms", "n_pairs",
+                             "n_hbond_pairs", "n_hydrophobic_pairs", "n_close_pairs", "n_contact_atoms", "n_protein_untyped", "status")
+# a type byte (include/cbgx.h CBGX_INTERACTIONS_*): element code 1 ... 7 (C N O F P S Cl) under the mask, three property bits; 0: takes
+# no part; UNTYPED: a pocket atom of an element outside H C N O S
+INTERACTION_ELEMENT_MASK, INTERACTION_HYDROPHOBIC, INTERACTION_DONOR, INTERACTION_ACCEPTOR, INTERACTION_UNTYPED = 7, 8, 16, 32, 64
+# status bits: a graph with status != 0 was not evaluated
+INTERACTIONS_TOO_MANY_ATOMS, INTERACTIONS_BAD_BONDS, INTERACTIONS_NO_VALENCE = 1, 4, 8
+INTERACTION_NOT_EVALUATED = 255
+# the published defaults of AutoDock Vina (O. Trott, A. J. Olson, J. Comput. Chem. 31 (2010) 455-461), in INTERACTION_TERMS order, and
+# its weight per rotatable bond
+INTERACTION_WEIGHTS = (-0.035579, -0.005156, 0.840245, -0.035069, -0.587439)
+INTERACTION_ROT_WEIGHT = 0.05846
+AA_NAMES = ("ALA", "CYS", "ASP", "GLU", "PHE", "GLY", "HIS", "ILE", "LYS", "LEU", "MET", "ASN", "PRO", "GLN", "ARG", "SER", "THR", "VAL",
+            "TRP", "TYR")                 # the reference's aa_name_number order: what ``rec_aa`` indexes
+BACKBONE_FEATURE = 6                       # the is_backbone column of ``protein_atom_feature`` (protein_featurizer.py:21-26)
+
+
+def _small_bytes(t, other):
+    """an index tensor as bytes; anything outside 0 ... 254 becomes ``other``"""
+    t = t.to(torch.long)
+    return torch.where((t >= 0) & (t < 255), t, torch.full_like(t, other)).to(torch.uint8).contiguous()
+
+
+def pocket_types(x_rec, z_rec, rec_batch, n_graphs, rec_aa, rec_backbone):
+    """Donor / acceptor / hydrophobic types of the pocket atoms of ``n_graphs`` graphs, one launch (``cbgx_pocket_types``,
+    csrc/interactions.hip; the table is in include/cbgx.h) on the tensors' current stream.
+
+    ``x_rec`` [n_rec, 3], ``z_rec`` [n_rec] atomic numbers, ``rec_batch`` [n_rec] grouped by graph, ``rec_aa`` [n_rec] residue indices in
+    AA_NAMES order (anything else: "other"), ``rec_backbone`` [n_rec] bool or 0 / 1.  Returns ``rec_type`` [n_rec] uint8 on the device: the
+    element code 1 ... 7 under INTERACTION_ELEMENT_MASK with INTERACTION_HYDROPHOBIC / _DONOR / _ACCEPTOR; 0 for H; INTERACTION_UNTYPED for
+    an element outside H C N O S.  No hydrogens are read and no protonation state is modelled: HIS side-chain N is donor and acceptor.
+    A carbon is hydrophobic unless it has a TABLE bond to an N, O or S atom of its pocket.  There is no CPU path."""
+    dev = x_rec.device
+    _gpu_only(dev, "pocket_types", "cbgx_pocket_types")
+    n_graphs = int(n_graphs)
+    n_rec, rec_ptr, x_rec, z_rec = _ligand_arrays(x_rec, z_rec, rec_batch, n_graphs, "rec")
+    for name, t in (("rec_aa", rec_aa), ("rec_backbone", rec_backbone)):
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, x_rec on {dev}")
+        if t.shape != (n_rec,):
+            raise ValueError("one residue index and one backbone flag per pocket atom")
+    aa = _small_bytes(rec_aa, len(AA_NAMES))
+    backbone = (rec_backbone != 0).to(torch.uint8).contiguous()
+    rec_type = torch.empty(n_rec, dtype=torch.uint8, device=dev)
+    p = _native.ptr
+    _native.check(_native.lib().cbgx_pocket_types(p(x_rec), p(z_rec), p(rec_ptr), n_rec, n_graphs, p(aa), p(backbone), p(rec_type),
+                                                  _native.current_stream(dev)), "cbgx_pocket_types")
+    return rec_type
+
+
+def ligand_interactions(x_lig, z_lig, lig_batch, x_rec, rec_type, rec_batch, n_graphs, bonds, valence, aromatic=None):
+    """Ligand atom types, rotatable bonds and the five pair terms of Vina's functional form of ``n_graphs`` ligands against their typed
+    pockets, one launch (``cbgx_ligand_interactions``, csrc/interactions.hip; the definition, the constants and the order of every sum
+    are in include/cbgx.h) on the tensors' current stream.  A score in Vina's functional form on this library's own atom typing: NOT a
+    reproduction of the Vina program, and not validated against it.
+
+    Ligand and pocket sides as ``ligand_geometry``; ``rec_type``: what ``pocket_types`` returned; ``bonds``: what ``ligand_bonds`` returned
+    for the same atoms; ``valence``: what ``ligand_valence`` returned for that list; ``aromatic``: what ``ligand_aromatic`` returned, or
+    None (an aromatic bond of that report is an edge of a cycle and never rotatable either way).  Returns device tensors: ``atom_terms``
+    [n_lig, 5] float64 (INTERACTION_TERMS: a ligand atom's sums over the pocket), ``lig_type`` [n_lig] uint8, ``bond_rotatable`` [n_bonds]
+    uint8, ``graph_terms`` [n_graphs, 5] float64 and ``graph_counts`` [n_graphs, 13] int32 (INTERACTION_GRAPH_COLUMNS).  A graph of more
+    than MAX_INTERACTION_ATOMS atoms, with a malformed list, or that the valence report did not evaluate is not an error: its status is
+    non-zero (INTERACTIONS_*), its columns from n_rotatable to n_protein_untyped are -1, its floats nan and its bytes 255.  Deviations
+    from the reference's Vina / PLIP path: table bonds; residue-table pocket typing without hydrogens or protonation states; this
+    library's acceptor rule for N; no intramolecular term, no metals, no Br / I; RDKit's non-strict rotatable-bond pattern.  There is no
+    CPU path."""
+    dev = x_lig.device
+    _gpu_only(dev, "ligand_interactions", "cbgx_ligand_interactions")
+    n_graphs = int(n_graphs)
+    n_lig, lig_ptr, x_lig, z_lig = _ligand_arrays(x_lig, z_lig, lig_batch, n_graphs)
+    n_rec, rec_ptr, x_rec, _ = _ligand_arrays(x_rec, rec_type, rec_batch, n_graphs, "rec", dev)
+    bond_index = bonds["bond_index"]
+    given = [("bond_index", bond_index), ("bond_kekule", valence["bond_kekule"]), ("implicit_h", valence["implicit_h"]),
+             ("atom_flags", valence["atom_flags"]), ("valence graph_counts", valence["graph_counts"])]
+    if aromatic is not None:
+        given.append(("aromatic_bond", aromatic["aromatic_bond"]))
+    for name, t in given:
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, x_lig on {dev}")
+    if bond_index.dim() != 2 or bond_index.shape[0] != 2:
+        raise ValueError("bond_index must be [2, n_bonds]")
+    n_bonds = int(bond_index.shape[1])
+    if valence["bond_kekule"].shape != (n_bonds,) or (aromatic is not None and aromatic["aromatic_bond"].shape != (n_bonds,)):
+        raise ValueError("one bond_kekule (and one aromatic_bond) per bond")
+    if valence["implicit_h"].shape != (n_lig,) or valence["atom_flags"].shape != (n_lig,):
+        raise ValueError("one implicit_h and one atom_flags per atom")
+    if tuple(valence["graph_counts"].shape) != (n_graphs, len(VALENCE_GRAPH_COLUMNS)):
+        raise ValueError("the valence report's graph_counts must be [n_graphs, 22]")
+    rec_type = rec_type.to(torch.uint8).contiguous()
+    bond_index, bond_ptr = bond_index.to(torch.int32).contiguous(), _bond_ptr(bond_index, n_lig)
+    kekule = valence["bond_kekule"].to(torch.uint8).contiguous()
+    implicit_h, atom_flags = valence["implicit_h"].to(torch.uint8).contiguous(), valence["atom_flags"].to(torch.uint8).contiguous()
+    val_status = valence["graph_counts"][:, -1].to(torch.int32).contiguous()
+    flag = None if aromatic is None else (aromatic["aromatic_bond"] != 0).to(torch.uint8).contiguous()
+    atom_terms = torch.empty(n_lig, len(INTERACTION_TERMS), dtype=torch.float64, device=dev)
+    lig_type = torch.empty(n_lig, dtype=torch.uint8, device=dev)
+    bond_rotatable = torch.empty(n_bonds, dtype=torch.uint8, device=dev)
+    graph_terms = torch.empty(n_graphs, len(INTERACTION_TERMS), dtype=torch.float64, device=dev)
+    graph_counts = torch.empty(n_graphs, len(INTERACTION_GRAPH_COLUMNS), dtype=torch.int32, device=dev)
+    p = _native.ptr
+    _native.check(_native.lib().cbgx_ligand_interactions(
+        p(x_lig), p(z_lig), p(lig_ptr), n_lig, p(x_rec), p(rec_type), p(rec_ptr), n_rec, n_graphs, p(bond_ptr),
+        p(bond_index) if n_bonds else None, p(kekule) if n_bonds else None, p(flag) if flag is not None and n_bonds else None, n_bonds,
+        p(implicit_h), p(atom_flags), p(val_status), p(atom_terms), p(lig_type), p(bond_rotatable) if n_bonds else None, p(graph_terms),
+        p(graph_counts), _native.current_stream(dev)), "cbgx_ligand_interactions")
+    return {"atom_terms": atom_terms, "lig_type": lig_type, "bond_rotatable": bond_rotatable, "graph_terms": graph_terms,
+            "graph_counts": graph_counts}
+
+
+def batch_interactions(batch, x, c, lig_batch, mode, bonds=None, valence=None):
+    """``pocket_types`` + ``ligand_interactions`` of a sampling state against the batch's own pocket (``protein_pos``,
+    ``protein_element``, ``protein_element_batch``, ``protein_aa_type`` and the is_backbone column of ``protein_atom_feature``), in the
+    frame both share; ``bonds`` / ``valence``: what ``batch_bonds`` / ``batch_valence`` returned for the same state (computed here when
+    None).  Also returns ``rec_type``"""
+    if bonds is None:
+        bonds = batch_bonds(batch, x, c, lig_batch, mode)
+    if valence is None:
+        valence = batch_valence(batch, x, c, lig_batch, mode, bonds=bonds)
+    dev = bonds["bond_index"].device
+    lig_batch = lig_batch.to(dev)
+    _, z, n_graphs = _state_atoms(c, mode, lig_batch, {"num_graphs": bonds["graph_counts"].shape[0]}, dev)
+    x_rec, z_rec, rec_b = (batch[k].to(dev) for k in ("protein_pos", "protein_element", "protein_element_batch"))
+    rec_type = pocket_types(x_rec, z_rec, rec_b, n_graphs, batch["protein_aa_type"].to(dev),
+                            batch["protein_atom_feature"].to(dev)[:, BACKBONE_FEATURE])
+    out = ligand_interactions(x.to(dev), z, lig_batch, x_rec, rec_type, rec_b, n_graphs, bonds, valence)
+    out["rec_type"] = rec_type
+    return out
+
+
+INTERACTION_COUNT_KEYS = (("n_mol", "n_mol_evaluated", "n_mol_over_limit") + INTERACTION_GRAPH_COLUMNS[:-1]
+                          + ("n_mol_with_hbond", "n_mol_negative_score", "score_micro", "score_inter_micro"))
+INTERACTION_RATIOS = ("mean_score", "mean_score_inter", "negative_score_mol_ratio", "hbond_pairs_per_mol", "hydrophobic_pairs_per_mol",
+                      "close_pairs_per_mol", "rotatable_per_mol", "mol_with_hbond_ratio")
+
+
+def interaction_scores(graph_counts, graph_terms):
+    """(score_inter [n_mol], score [n_mol]) float64 of per-molecule counts and terms: score_inter = sum_k INTERACTION_WEIGHTS[k]
+    graph_terms[:, k], added in index order in float64; score = score_inter / (1 + INTERACTION_ROT_WEIGHT n_rotatable); nan where
+    status != 0"""
+    gc = _counts(graph_counts, INTERACTION_GRAPH_COLUMNS)
+    terms = np.asarray(_np(graph_terms), np.float64).reshape(-1, len(INTERACTION_TERMS))
+    if terms.shape[0] != gc.shape[0]:
+        raise ValueError("one row of terms per row of counts")
+    ok = gc[:, -1] == 0
+    inter = np.zeros(gc.shape[0], np.float64)
+    for k, w in enumerate(INTERACTION_WEIGHTS):
+        inter = inter + w * np.where(ok, terms[:, k], 0.0)
+    score = inter / (1.0 + INTERACTION_ROT_WEIGHT * np.where(ok, gc[:, 2], 0).astype(np.float64))
+    return np.where(ok, inter, np.nan), np.where(ok, score, np.nan)
+
+
+def score_micro(score):
+    """a score as the integer ranks add up: int(rint(score 1e6))"""
+    return int(np.rint(float(score) * 1e6))
+
+
+def interaction_totals(graph_counts, graph_terms):
+    """per-molecule counts ``graph_counts`` [n_mol, 13] (INTERACTION_GRAPH_COLUMNS) and terms ``graph_terms`` [n_mol, 5] (any array-likes)
+    -> the integer totals, in INTERACTION_COUNT_KEYS order.  Everything but n_mol and n_mol_over_limit is summed over the evaluated
+    molecules (status == 0) only; score_micro / score_inter_micro: the sums of the per-molecule ``score_micro`` integers, so that a job's
+    mean does not depend on how its molecules were sharded"""
+    gc = _counts(graph_counts, INTERACTION_GRAPH_COLUMNS)
+    inter, score = interaction_scores(gc, graph_terms)
+    ok = gc[:, -1] == 0
+    good = gc[ok]
+    return ([int(gc.shape[0]), int(good.shape[0]), int(gc.shape[0] - good.shape[0])] + [int(v) for v in good[:, :12].sum(0)]
+            + [int((good[:, 7] > 0).sum()), int(sum(score_micro(s) < 0 for s in score[ok])), int(sum(score_micro(s) for s in score[ok])),
+               int(sum(score_micro(s) for s in inter[ok]))])
+
+
+def summarise_interaction_totals(totals):
+    """the ratios (INTERACTION_RATIOS) of integer totals in INTERACTION_COUNT_KEYS order, and the totals as ``counts``; every ratio is
+    over the EVALUATED molecules, a ratio over nothing is nan.  mean_score / mean_score_inter: score_micro / 1e6 per molecule, in the
+    units of Vina's weights (kcal/mol there; here a score in its functional form, not validated against the program);
+    negative_score_mol_ratio: the share of molecules whose score_micro < 0; hbond / hydrophobic / close pairs and rotatable bonds per
+    molecule; mol_with_hbond_ratio: the share with at least one hbond pair"""
+    c = {k: int(v) for k, v in zip(INTERACTION_COUNT_KEYS, totals)}
+    n_mol = c["n_mol_evaluated"]
+    return {"mean_score": _ratio(c["score_micro"] / 1e6, n_mol), "mean_score_inter": _ratio(c["score_inter_micro"] / 1e6, n_mol),
+            "negative_score_mol_ratio": _ratio(c["n_mol_negative_score"], n_mol), "hbond_pairs_per_mol": _ratio(c["n_hbond_pairs"], n_mol),
+            "hydrophobic_pairs_per_mol": _ratio(c["n_hydrophobic_pairs"], n_mol), "close_pairs_per_mol": _ratio(c["n_close_pairs"], n_mol),
+            "rotatable_per_mol": _ratio(c["n_rotatable"], n_mol), "mol_with_hbond_ratio": _ratio(c["n_mol_with_hbond"], n_mol), "counts": c}
+
+
+def summarise_interactions(graph_counts, graph_terms):
+    """interaction statistics of a set of molecules from their per-molecule counts and terms: see ``summarise_interaction_totals``"""
+    return summarise_interaction_totals(interaction_totals(graph_counts, graph_terms))
 
 
 # the five reports that are integer counts per molecule, for a driver that treats them alike: per-molecule columns -> totals (what ranks

@@ -38,6 +38,9 @@ and bond-angle profiles are then keyed by four bond types (``6:6``, ``6:6:6``).
 ``--valence`` asks whether the sample is a molecule at all: Kekule orders for the aromatic bonds, implicit hydrogens and a valence check per
 atom on that graph, computed on the device in one more launch per batch (``geometry.batch_valence``), with the formula, the molecular
 weight and ``mol_valid`` per sample and ``{out_dir}/valence_summary.json`` for the job.
+``--interactions`` asks how the sample sits in its pocket: donor / acceptor / hydrophobic types of both sides, rotatable bonds and the five
+pair terms of Vina's functional form, computed on the device in two more launches per batch (``geometry.batch_interactions``), with
+``score`` per sample and ``{out_dir}/interactions_summary.json`` for the job.  This library's own typing: not the Vina program.
 ``--sdf`` writes ``pocket_{i:05d}.sdf`` beside every result file: one V2000 record per sample, bond types the Kekule orders of ``--valence``
 when given, else from ``--aromatic`` when given, table-bond orders otherwise (``geometry.sdf_record``; host side, no RDKit).
 A checkpoint is the reference's format: ``{'config': ..., 'model': state_dict}`` (``sample.py:153-156``)."""
@@ -146,7 +149,7 @@ def decode_mode(plan_mode, config_mode, num_classes):
 def main(argv=None, stats=None):
     """``stats`` (optional dict): filled with the wall seconds of the phases (setup = config + model + weights, batch = prior
     construction, sample = model.sample incl. the trajectory download, write = per-pocket records and files) and, for every requested report
-    (geometry, bonds, rings, aromatic, distributions, valence: evaluated in that order), its own launches and downloads, a part of write: the bond
+    (geometry, bonds, rings, aromatic, distributions, valence, interactions: evaluated in that order), its own launches and downloads, a part of write: the bond
     list and the ring report are made once per batch, and where they were not asked for their time goes to the first requested report
     in that order that needs them (cbgbench_amd/sample_reports.py)."""
     t_phase = time.perf_counter()
@@ -247,6 +250,18 @@ def main(argv=None, stats=None):
                          "S 2/4/6, Cl 1), no charges: a nitro group drawn N(=O)=O counts as exceeded.  TABLE bonds, not RDKit's.  A sample "
                          "over a limit is reported (valence_status != 0) and left out of every ratio.  Independent of --bonds, --rings "
                          "and --aromatic: without them they are computed and not written.  With --sdf the records carry bond_kekule")
+    ap.add_argument("--interactions", action="store_true",
+                    help="add typed pocket contacts and a score in Vina's functional form to every sample (lig_xs_type [n] type bytes: "
+                         "element code 1 ... 7 = C N O F P S Cl, 8 hydrophobic, 16 donor, 32 acceptor; atom_terms [n, 5] and "
+                         "interaction_terms [5] float64: gauss1, gauss2, repulsion, hydrophobic, hbond; bond_rotatable [nb] aligned with "
+                         "the bond_index of --bonds, n_rotatable; score_inter = the terms under Vina's published weights, score = "
+                         "score_inter / (1 + 0.05846 n_rotatable); n_hbond_pairs, n_hydrophobic_pairs, n_close_pairs, n_contact_atoms, "
+                         "interactions_status), an `interactions` dict of counts to every pocket record and "
+                         "{out_dir}/interactions_summary.json, evaluated on the GPU in two launches per batch on the bond list, the "
+                         "valence report and the pocket's residue types (cbgbench_amd/geometry.py).  This library's own atom typing on "
+                         "TABLE bonds, no hydrogens or protonation states in the pocket, no intramolecular term: NOT the Vina program "
+                         "and not validated against it.  A sample over a limit is reported (interactions_status != 0) and left out of "
+                         "every ratio.  Independent of every other flag: what it needs is computed and not written")
     ap.add_argument("--sdf", action="store_true",
                     help="write pocket_XXXXX.sdf beside every pocket_XXXXX.pt: one V2000 record per sample with the positions the record "
                          "holds, bond types from --aromatic when given (4 = aromatic), else the table-bond orders (bonds are computed "

@@ -1,4 +1,4 @@
-"""The reports of ``sample_cli`` (--geometry, --bonds, --rings, --aromatic, --distributions, --valence, --sdf) in three stages: ``evaluate`` runs the
+"""The reports of ``sample_cli`` (--geometry, --bonds, --rings, --aromatic, --distributions, --valence, --interactions, --sdf) in three stages: ``evaluate`` runs the
 requested reports of one batch on the GPU and returns plain dicts of CPU tensors; ``annotate`` / ``pocket_counts`` / ``pocket_files``
 turn those into the per-sample fields, the per-pocket dicts and the ``.sdf`` text on the host (CPU tensors in, no device); ``finish`` sums
 the job's integer totals over the ranks, writes ``*_summary.json`` and prints one line per report.
@@ -6,7 +6,13 @@ the job's integer totals over the ranks, writes ``*_summary.json`` and prints on
 Reports run in the order of ORDER.  What a report is computed from beside the state (NEEDS: the bond list, the ring report) is made at
 most once per batch and shared; a dependency that was not asked for is computed, used and not written, and its wall time goes to the first
 requested report in that order that needs it.  The valence report takes the aromatic report (and so the ring report) where the atom types
-have aromatic flags ('add_aromatic'); with any other vocabulary no bond is aromatic and it needs the bond list only."""
+have aromatic flags ('add_aromatic'); with any other vocabulary no bond is aromatic and it needs the bond list only.
+
+The reports of EXTRA come after those of ORDER, under the same rules, in every stage.  ``interactions`` (typed pocket contacts and a score
+in Vina's functional form on this library's own atom typing: not the Vina program, not validated against it) is the first report that
+reads the pocket's chemistry (``protein_aa_type``, the backbone column of ``protein_atom_feature``); it takes the bond list and the valence
+report, and through the latter whatever ``needs("valence", mode)`` says.  Its job numbers are sums of integers too: every sample's score is
+rounded to a whole number of millionths before the ranks add them up."""
 import json
 import os
 import time
@@ -18,7 +24,9 @@ from . import geometry, sharding
 from .config import _AROMATIC
 
 ORDER = ("geometry", "bonds", "rings", "aromatic", "distributions", "valence")
-NEEDS = {"rings": ("bonds",), "aromatic": ("bonds", "rings"), "distributions": ("bonds",), "valence": ("bonds", "aromatic")}
+EXTRA = ("interactions",)        # evaluated, annotated and finished after ORDER
+NEEDS = {"rings": ("bonds",), "aromatic": ("bonds", "rings"), "distributions": ("bonds",), "valence": ("bonds", "aromatic"),
+         "interactions": ("bonds", "valence")}
 
 
 def needs(name, mode):
@@ -36,6 +44,7 @@ _GPU_ONLY = {"geometry": "--geometry runs on the GPU (cbgx_ligand_geometry has n
              "distributions": "--distributions runs on the GPU (cbgx_ligand_pair_hist / cbgx_ligand_angles have no CPU fallback)",
              "aromatic": "--aromatic runs on the GPU (cbgx_ligand_aromatic has no CPU fallback)",
              "valence": "--valence runs on the GPU (cbgx_ligand_valence has no CPU fallback)",
+             "interactions": "--interactions runs on the GPU (cbgx_pocket_types / cbgx_ligand_interactions have no CPU fallback)",
              "sdf": "--sdf takes its bonds from the GPU (cbgx_ligand_bonds_count / _fill have no CPU fallback)"}
 # a count report's printed line: the ratios it names, and its own tail
 _LINE = {"geometry": (geometry.RATIOS, lambda c: f"{c['n_mol']} molecules, {c['n_atoms']} atoms"),
@@ -67,25 +76,26 @@ def ranges(counts):
 
 
 class SampleReports:
-    """``requested``: names out of ORDER and 'sdf'; ``reference``: the path of --distributions_reference"""
+    """``requested``: names out of ORDER, EXTRA and 'sdf'; ``reference``: the path of --distributions_reference"""
 
     def __init__(self, requested, reference=None):
         self.requested = frozenset(requested)
         self.reference = reference
         self.n_orders = 4 if "aromatic" in self.requested else 3        # --aromatic --distributions: types with the aromatic type
-        self.seconds = {name: 0.0 for name in ORDER if name in self.requested}         # wall time of every report (``stats``)
+        self.seconds = {name: 0.0 for name in ORDER + EXTRA if name in self.requested}         # wall time of every report (``stats``)
         self.counts = {name: [] for name in _COUNT_REPORTS if name in self.requested}  # per-sample counts of this rank
         # the pockets' flat integer totals are added up as they come (one is 3.5 MB)
         self.distribution_totals = np.zeros(geometry.distribution_totals_length(n_orders=self.n_orders), np.int64)
         self.sdf_left_out, self.sdf_written = 0, 0
+        self.interactions = []                                          # (graph_counts, graph_terms) of this rank's pockets
 
     @classmethod
     def from_args(cls, args):
-        return cls([name for name in ORDER + ("sdf",) if getattr(args, name)], args.distributions_reference)
+        return cls([name for name in ORDER + EXTRA + ("sdf",) if getattr(args, name)], args.distributions_reference)
 
     def refuse(self, dev, atom_mode):
         """what cannot run is refused before any model is built; ``atom_mode()``: the vocabulary the samples are decoded with"""
-        for name in ("geometry", "bonds", "rings", "distributions", "aromatic", "valence", "sdf"):
+        for name in ("geometry", "bonds", "rings", "distributions", "aromatic", "valence") + EXTRA + ("sdf",):
             if name not in self.requested:
                 continue
             if name == "aromatic" and atom_mode() != "add_aromatic":
@@ -113,6 +123,10 @@ class SampleReports:
                 if name == "geometry":
                     pocket = {k: batch[k].to(dev) for k in ("protein_pos", "protein_element", "protein_element_batch")}
                     made[name] = geometry.batch_geometry({**pocket, **info}, x, c, bidx, mode)
+                elif name == "interactions":
+                    pocket = {k: batch[k].to(dev) for k in ("protein_pos", "protein_element", "protein_element_batch", "protein_aa_type",
+                                                            "protein_atom_feature")}
+                    made[name] = geometry.batch_interactions({**pocket, **info}, x, c, bidx, mode, **deps)
                 elif name == "distributions":
                     made[name] = geometry.batch_distributions(info, x, c, bidx, mode, aromatic=made.get("aromatic"), **deps)
                 else:
@@ -187,6 +201,19 @@ class SampleReports:
                 smp["angle_deg"] = torch.from_numpy(np.degrees(np.arccos(smp["angle_cos"].numpy())))
                 smp["angle_type"] = dists["angle_type"][n0:n1].clone()
                 smp["distribution_status"] = int(gc[g, 4])
+        if "interactions" in self.requested:
+            ia, gc = ev["interactions"], ev["interactions"]["graph_counts"].to(torch.int64)
+            inter, score = geometry.interaction_scores(gc, ia["graph_terms"])
+            for g, (smp, (a0, a1), (b0, b1)) in enumerate(zip(samples, ranges(gc[:, 0]), ranges(gc[:, 1]))):
+                row = dict(zip(geometry.INTERACTION_GRAPH_COLUMNS, gc[g].tolist()))
+                smp["lig_xs_type"] = ia["lig_type"][a0:a1].clone()
+                smp["atom_terms"] = ia["atom_terms"][a0:a1].clone()
+                smp["bond_rotatable"] = ia["bond_rotatable"][b0:b1].clone()
+                smp["interaction_terms"] = ia["graph_terms"][g].clone()
+                smp["score_inter"], smp["score"] = float(inter[g]), float(score[g])
+                for k in ("n_rotatable", "n_hbond_pairs", "n_hydrophobic_pairs", "n_close_pairs", "n_contact_atoms"):
+                    smp[k] = row[k]
+                smp["interactions_status"] = row["status"]
 
     def pocket_counts(self, ev, g0, g1):
         """the dicts of counts a pocket record carries for its graphs g0 ... g1 - 1, which join the job's totals"""
@@ -200,6 +227,10 @@ class SampleReports:
                 gc = ev[rep.name]["graph_counts"][g0:g1].to(torch.int64)
                 self.counts[rep.name].append(gc)
                 rec[rep.name] = rep.summarise_totals(rep.totals(gc))["counts"]
+        if "interactions" in self.requested:
+            gc, terms = ev["interactions"]["graph_counts"][g0:g1].to(torch.int64), ev["interactions"]["graph_terms"][g0:g1]
+            self.interactions.append((gc, terms))
+            rec["interactions"] = geometry.summarise_interactions(gc, terms)["counts"]
         return rec
 
     def pocket_files(self, stem, samples, ev, g0):
@@ -243,6 +274,17 @@ class SampleReports:
             if rank == 0:
                 save(name, summary)
                 print(f"{name}: " + ", ".join(f"{k} {summary[k]:.4f}" for k in ratios) + f" ({tail(summary['counts'])})")
+        if "interactions" in self.requested:
+            totals = [0] * len(geometry.INTERACTION_COUNT_KEYS)
+            for gc, terms in self.interactions:      # integer totals: pocket by pocket is the whole
+                totals = [a + b for a, b in zip(totals, geometry.interaction_totals(gc, terms))]
+            summary = geometry.summarise_interaction_totals(sharding.sum_counts(totals, device=dev))
+            if rank == 0:
+                save("interactions", summary)
+                cnt = summary["counts"]
+                print("interactions: " + ", ".join(f"{k} {summary[k]:.4f}" for k in geometry.INTERACTION_RATIOS)
+                      + f" ({cnt['n_mol_evaluated']} of {cnt['n_mol']} molecules evaluated, n_mol_over_limit {cnt['n_mol_over_limit']}; a score "
+                        f"in Vina's functional form, not the Vina program)")
         if "sdf" in self.requested:
             left_out, written = sharding.sum_counts([self.sdf_left_out, self.sdf_written], device=dev)
             if rank == 0:

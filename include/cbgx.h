@@ -941,6 +941,96 @@ int cbgx_ligand_valence(const uint8_t *z_lig, const int32_t *lig_ptr, int n_lig,
                         const int32_t *bond_index, const uint8_t *bond_order, const uint8_t *bond_aromatic, int n_bonds, int max_steps,
                         uint8_t *implicit_h, uint8_t *atom_flags, uint8_t *bond_kekule, int32_t *graph_out, void *stream);
 
+/* ---- typed pocket contacts and a score in Vina's functional form (interactions.hip) -----------------------------------------------------
+ * How well does the sample sit in its pocket?  The reference answers with `vina_task.run(mode='score_only')`
+ *   (evaluate_scripts/evaluate_chem_single.py:44-49) and the PLIP contact counts of repo/tools/interaction.py, behind RDKit, OpenBabel,
+ *   meeko, Vina and PLIP.  Here: the five pair terms of the published Vina scoring function (O. Trott, A. J. Olson, "AutoDock Vina:
+ *   improving the speed and accuracy of docking with a new scoring function, efficient optimization, and multithreading", J. Comput.
+ *   Chem. 31 (2010) 455-461: gauss1, gauss2, repulsion, hydrophobic, hydrogen bonding over surface distances, cutoff 8 A, the radii
+ *   below; its weights -0.035579, -0.005156, 0.840245, -0.035069, -0.587439 and 0.05846 per rotatable bond are applied by the caller) on
+ *   THIS LIBRARY'S OWN atom typing, in two launches, one workgroup per graph.  It is a score in Vina's functional form and NOT a
+ *   reproduction of the Vina program: it has not been validated against it and nothing may claim agreement with it.
+ *   Deviations: TABLE bonds (cbgx_ligand_bonds_fill), Kekule orders and hydrogens of cbgx_ligand_valence; pocket types from a residue
+ *   table, with no hydrogens in the file and no protonation states (HIS is always donor + acceptor); this library's own acceptor rule for
+ *   N; no intramolecular term, no metals, no Br / I; rotatable bonds by RDKit's NON-strict pattern (the reference's obey_lipinski uses the
+ *   strict one).
+ * A type byte: element code 1 ... 7 (C N O F P S Cl) in the bits of CBGX_INTERACTIONS_ELEMENT_MASK, and CBGX_INTERACTIONS_HYDROPHOBIC,
+ *   _DONOR, _ACCEPTOR.  0: the atom takes no part (H; a ligand atom of no known element).  CBGX_INTERACTIONS_UNTYPED: a pocket atom that
+ *   takes no part and is counted.  An atom takes part in the pair terms iff its byte is in 1 ... 63 with a non-zero element code.
+ * Distances and table bonds are cbgx_ligand_geometry's: fp32 coordinates widened to fp64, s = (dx dx + dy dy) + dz dz with every
+ *   operation rounded on its own, r = sqrt(s) correctly rounded, contraction off; order >= 1 iff 100.0 r < b1 + 10 (pm), strictly.
+ *
+ * cbgx_pocket_types -- rec_type [n_rec] uint8 from x_rec [n_rec, 3], z_rec [n_rec] atomic numbers, rec_ptr [B + 1] (as
+ *   cbgx_ligand_geometry takes them; the range of a graph is clamped to the arrays; any number of atoms), rec_aa [n_rec] uint8 (an index
+ *   into the reference's aa_name_number order: ALA 0, CYS 1, ASP 2, GLU 3, PHE 4, GLY 5, HIS 6, ILE 7, LYS 8, LEU 9, MET 10, ASN 11,
+ *   PRO 12, GLN 13, ARG 14, SER 15, THR 16, VAL 17, TRP 18, TYR 19; anything else is "other"), rec_backbone [n_rec] uint8 (non-zero: a
+ *   backbone atom).  H: 0.  An element outside H C N O S (Se included): CBGX_INTERACTIONS_UNTYPED.  N: backbone: donor, except PRO (none);
+ *   side chain of LYS, ARG, ASN, GLN, TRP: donor; of HIS: donor + acceptor; any other: neither.  O: acceptor; side chain of SER, THR, TYR:
+ *   donor + acceptor (ASP / GLU / ASN / GLN and a terminal OXT: acceptor).  S: no bit.  C: hydrophobic unless it has a table bond
+ *   (order >= 1) to an N, O or S protein atom of the same graph.
+ *
+ * cbgx_ligand_interactions -- inputs: x_lig, z_lig, lig_ptr, x_rec, rec_ptr as above; rec_type as written by cbgx_pocket_types; bond_ptr
+ *   [n_lig + 1], bond_index [2, n_bonds] as cbgx_ligand_rings takes them; bond_kekule, implicit_h, atom_flags as cbgx_ligand_valence
+ *   writes them; valence_status [B] int32, the status column of its graph_out; bond_aromatic [n_bonds] as cbgx_ligand_valence takes it
+ *   (1: aromatic; NULL: no bond is).
+ *   Ligand types, with h(a) = implicit_h(a) + the number of a's H neighbours in the bond list and heavy(a) = the number of its other
+ *   neighbours: H: 0.  C: hydrophobic unless bonded to an atom that is neither C nor H.  F, Cl: hydrophobic.  P, S: no bit.  O: acceptor;
+ *   donor iff h > 0.  N: donor iff h > 0; acceptor iff h == 0 and heavy <= 2 and no CBGX_VALENCE_EXCEEDED flag (pyridine, imine, nitrile;
+ *   not a tertiary amine, not an amide).  Any other element: 0.
+ *   Rotatable bonds: bond_rotatable = 1 iff bond_kekule == 1 and bond_aromatic != 1, the bond is a bridge of the bond graph (it lies on no
+ *   cycle), both ends have heavy >= 2 and neither end has a bond with bond_kekule == 3; else 0.  (RDKit's non-strict
+ *   [!$(*#*)&!D1]-&!@[!$(*#*)&!D1] on table bonds.)
+ *   Pair terms: for every ligand atom i and pocket atom j of the same graph that both take part, with r < 8.0 strictly:
+ *   d = (r - R_i) - R_j, radii in A by element C 1.9, N 1.8, O 1.7, P 2.1, S 2.0, F 1.5, Cl 1.8;
+ *     0 gauss1       exp(-(q q)), q = d / 0.5                                        every pair
+ *     1 gauss2       exp(-(q q)), q = (d - 3.0) / 2.0                                every pair
+ *     2 repulsion    d d if d < 0, else 0                                            every pair
+ *     3 hydrophobic  1 if d < 0.5; 1.5 - d if d < 1.5; else 0                        both atoms hydrophobic
+ *     4 hbond        1 if d < -0.7; (-d) / 0.7 if d < 0; else 0                      one atom a donor and the other an acceptor
+ *   Outputs, dense, every element of every graph's ranges written: atom_terms [n_lig, 5] fp64, a ligand atom's sums over the pocket
+ *   (zeros for an atom that takes no part); lig_type [n_lig] uint8; bond_rotatable [n_bonds] uint8; graph_terms [B, 5] fp64;
+ *   graph_out [B, CBGX_INTERACTIONS_GRAPH_COLS] int32: n_atoms, n_bonds, n_rotatable, n_donors, n_acceptors, n_hydrophobic_atoms (ligand
+ *   atoms with the bit), n_pairs (within 8 A), n_hbond_pairs (hbond term > 0), n_hydrophobic_pairs (hydrophobic term > 0), n_close_pairs
+ *   (d < 0 and not a donor-acceptor pair), n_contact_atoms (ligand atoms with any pair at d < 0.5), n_protein_untyped (rec_type ==
+ *   CBGX_INTERACTIONS_UNTYPED in the graph's pocket), status.
+ *   Order of every floating sum (a function of the graph's own sizes only; no float atomics; the bits of a graph's outputs do not depend
+ *   on what else is in the batch or where the graph stands in it): atom_terms[i][t] = (p_0 + p_1) + (p_2 + p_3), where p_s starts at 0.0
+ *   and adds the pairs of i with the pocket atoms j = s, s + 4, s + 8, ... (j counted from the graph's first pocket atom) in ascending j;
+ *   pocket atoms that take no part and pairs with r >= 8 are skipped.  graph_terms[g][t] = ((0.0 + a_0) + a_1) + ... over the graph's
+ *   ligand atoms in ascending order.  exp is the device library's fp64 exp.
+ *   Status, per graph, never an error, set side by side: CBGX_INTERACTIONS_TOO_MANY_ATOMS (more than CBGX_INTERACTIONS_MAX_ATOMS ligand
+ *   atoms), CBGX_INTERACTIONS_BAD_BONDS (the conditions of CBGX_RINGS_BAD_BONDS, or -- where valence_status == 0 -- a bond_kekule outside
+ *   1..4), CBGX_INTERACTIONS_NO_VALENCE (valence_status != 0).  With status != 0 the columns from n_rotatable on, except status, are -1,
+ *   the graph's floats NaN and its bytes of lig_type and bond_rotatable 255; n_atoms and n_bonds are the (clamped) sizes of the two
+ *   ranges.  Every entry of lig_ptr, rec_ptr, bond_ptr and bond_index is clamped or checked before it is used as an index.
+ *   Clamping keeps every access inside the arrays; it does NOT make the ranges of different graphs disjoint.  A lig_ptr, rec_ptr or
+ *   bond_ptr that decreases from one graph to the next (lig_ptr = 0, 10, 5, 12) gives two graphs overlapping ranges: both kernels then
+ *   have two workgroups write the same elements of atom_terms, lig_type, bond_rotatable or rec_type, in no order, and those elements are
+ *   undefined (in bounds, and each graph's own row of graph_terms and graph_out is still what its range gives), as in
+ *   cbgx_ligand_aromatic and cbgx_ligand_valence.  Non-decreasing pointers, which is what the Python side builds, never overlap.
+ * Both return 0, and 0 without a launch when B == 0.  CBGX_E_INVALID before any dereference or launch: negative counts, a NULL pointer
+ *   with a non-zero count (the per-bond arrays may be NULL when n_bonds == 0; bond_aromatic always), and any array with a non-zero count
+ *   whose pointer is not memory the device can read (plain host memory: every pointer argument is asked for, in argument order, and
+ *   the first such array is named in cbgx_last_error). */
+#define CBGX_INTERACTIONS_MAX_ATOMS 256
+#define CBGX_INTERACTIONS_TERMS 5
+#define CBGX_INTERACTIONS_GRAPH_COLS 13   /* n_atoms, n_bonds, n_rotatable, n_donors, n_acceptors, n_hydrophobic_atoms, n_pairs, n_hbond_pairs, n_hydrophobic_pairs, n_close_pairs, n_contact_atoms, n_protein_untyped, status */
+#define CBGX_INTERACTIONS_ELEMENT_MASK 7
+#define CBGX_INTERACTIONS_HYDROPHOBIC 8
+#define CBGX_INTERACTIONS_DONOR 16
+#define CBGX_INTERACTIONS_ACCEPTOR 32
+#define CBGX_INTERACTIONS_UNTYPED 64
+#define CBGX_INTERACTIONS_TOO_MANY_ATOMS 1
+#define CBGX_INTERACTIONS_BAD_BONDS 4
+#define CBGX_INTERACTIONS_NO_VALENCE 8
+int cbgx_pocket_types(const float *x_rec, const uint8_t *z_rec, const int32_t *rec_ptr, int n_rec, int n_graphs, const uint8_t *rec_aa,
+                      const uint8_t *rec_backbone, uint8_t *rec_type, void *stream);
+int cbgx_ligand_interactions(const float *x_lig, const uint8_t *z_lig, const int32_t *lig_ptr, int n_lig, const float *x_rec,
+                             const uint8_t *rec_type, const int32_t *rec_ptr, int n_rec, int n_graphs, const int32_t *bond_ptr,
+                             const int32_t *bond_index, const uint8_t *bond_kekule, const uint8_t *bond_aromatic, int n_bonds,
+                             const uint8_t *implicit_h, const uint8_t *atom_flags, const int32_t *valence_status, double *atom_terms,
+                             uint8_t *lig_type, uint8_t *bond_rotatable, double *graph_terms, int32_t *graph_out, void *stream);
+
 /* ---- distributions of sampled ligands: pair distances, bond lengths, bond angles (distributions.hip) -----------------------------------
  * The rest of the reference's geometry report (evaluate_scripts/evaluate_geom_single.py; repo/tools/geometry/eval_bond_length.py,
  *   eval_bond_angle.py): histograms that are compared with a dataset's by Jensen-Shannon distance.  Distances and element codes are those
