@@ -109,6 +109,8 @@ EXPORTS = {
     "cbgx_ligand_valence": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "cbgx_pocket_types": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "cbgx_ligand_interactions": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i] + [_vp] * 9),
+    "cbgx_ligand_groups": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "cbgx_ligand_groups_templates": (_i, [_vp] * 4),
     "cbgx_ligand_pair_hist": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "cbgx_ligand_angles": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "cbgx_profile_begin": (_i, [_i]),

@@ -1,6 +1,6 @@
 // libcbgx -- C ABI of the geometry report, of the bond list, of the ring sizes, of the aromatic report, of the valence report, of the
-// interaction report and of the distributions (include/cbgx.h, geometry.hip, rings.hip, aromatic.hip, valence.hip, interactions.hip,
-// distributions.hip): argument checks, the ligand-size check, the launch
+// interaction report, of the functional groups and of the distributions (include/cbgx.h, geometry.hip, rings.hip, aromatic.hip,
+// valence.hip, interactions.hip, groups.hip, distributions.hip): argument checks, the ligand-size check, the launch
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -221,6 +221,33 @@ int cbgx_ligand_interactions(const float* x_lig, const uint8_t* z_lig, const int
                                                     valence_status, atom_terms, lig_type, bond_rotatable, graph_terms, graph_out,
                                                     (hipStream_t)stream);
     if (e != hipSuccess) return set_error(CBGX_E_HIP, "ligand_interactions: launch: %s", hipGetErrorString(e));
+    return CBGX_OK;
+}
+
+int cbgx_ligand_groups(const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs, const int32_t* bond_ptr,
+                       const int32_t* bond_index, const uint8_t* bond_order, const uint8_t* bond_aromatic, int n_bonds,
+                       int32_t* atom_group, uint8_t* atom_class, int32_t* graph_out, void* stream) {
+    if (n_graphs < 0 || n_lig < 0 || n_bonds < 0)
+        return set_error(CBGX_E_INVALID, "ligand_groups: negative count (B=%d n_lig=%d n_bonds=%d)", n_graphs, n_lig, n_bonds);
+    if ((n_graphs > 0 && (!lig_ptr || !bond_ptr || !graph_out)) || (n_lig > 0 && (!z_lig || !atom_group || !atom_class)) ||
+        (n_bonds > 0 && (!bond_index || !bond_order)))
+        return set_error(CBGX_E_INVALID, "ligand_groups: NULL pointer");
+    if (n_graphs == 0) return CBGX_OK;
+    const DeviceArray arrays[] = {
+        {"z_lig", z_lig, n_lig}, {"lig_ptr", lig_ptr, n_graphs + 1}, {"bond_ptr", bond_ptr, n_lig + 1}, {"bond_index", bond_index, n_bonds},
+        {"bond_order", bond_order, n_bonds}, {"bond_aromatic", bond_aromatic, n_bonds}, {"atom_group", atom_group, n_lig},
+        {"atom_class", atom_class, n_lig}, {"graph_out", graph_out, n_graphs}};
+    const int rc = device_visible("ligand_groups", arrays, (int)(sizeof(arrays) / sizeof(arrays[0])));
+    if (rc != CBGX_OK) return rc;
+    const hipError_t e = launch_ligand_groups(z_lig, lig_ptr, n_lig, n_graphs, bond_ptr, bond_index, bond_order, bond_aromatic, n_bonds,
+                                              atom_group, atom_class, graph_out, (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(CBGX_E_HIP, "ligand_groups: launch: %s", hipGetErrorString(e));
+    return CBGX_OK;
+}
+
+int cbgx_ligand_groups_templates(uint8_t* n_atoms, uint8_t* n_bonds, uint8_t* labels, uint8_t* bonds) {
+    if (!n_atoms || !n_bonds || !labels || !bonds) return set_error(CBGX_E_INVALID, "ligand_groups_templates: NULL pointer");
+    ligand_groups_templates(n_atoms, n_bonds, labels, bonds);
     return CBGX_OK;
 }
 

@@ -1,4 +1,4 @@
-// libcbgx -- what the translation units of the geometry reports share (geometry.hip, distributions.hip, interactions.hip): the limits, the element codes,
+// libcbgx -- what the translation units of the geometry reports share (geometry.hip, distributions.hip, interactions.hip, groups.hip): the limits, the element codes,
 // the constant tables as a compile-time initialiser, and the fp64 squared distance.  The sources and the meaning of the constants are in
 // the head of geometry.hip.  A translation unit that includes this keeps contraction off (#pragma clang fp contract(off)): geo_dist2's
 // products and sums are plain operators.
@@ -96,6 +96,76 @@ constexpr InteractionTables make_interaction_tables() {
     t.n_type[0][AA_HIS] = don | acc;      // no protonation state: both, always
     for (int a : o_donor_side) t.o_type[0][a] = don | acc;
     return t;
+}
+
+// ---- the functional-group report (groups.hip; the definition is in include/cbgx.h, cbgx_ligand_groups) ----------------------------------
+// A template is a labelled graph: an atom label is (element code << 1) | aromatic bit, a bond is (atom, atom, type 1 ... 4).  The atoms of
+// every template are listed so that each one after the first has a bond to an earlier one: the matcher extends a connected partial map.
+constexpr int GRP_CLASSES = CBGX_GROUPS_CLASSES;        // named classes; index GRP_CLASSES is `other`
+constexpr int GRP_T_ATOMS = CBGX_GROUPS_MAX_TEMPLATE_ATOMS;
+constexpr int GRP_T_BONDS = CBGX_GROUPS_MAX_TEMPLATE_BONDS;   // naphthalene, quinoline
+
+enum : uint8_t { GL_C = EL_C << 1, GL_c = (EL_C << 1) | 1, GL_N = EL_N << 1, GL_n = (EL_N << 1) | 1, GL_O = EL_O << 1, GL_P = EL_P << 1,
+                 GL_S = EL_S << 1, GL_s = (EL_S << 1) | 1 };
+
+struct GroupBond { uint8_t i, j, t; };
+
+struct GroupTemplate {
+    uint8_t n_atoms, n_bonds;
+    uint8_t label[GRP_T_ATOMS];
+    GroupBond bond[GRP_T_BONDS];
+};
+
+struct GroupTables {
+    GroupTemplate t[GRP_CLASSES];
+    uint64_t hist[GRP_CLASSES];                       // 4 bits per label: how many atoms carry it (the sorted labels, as one number)
+    uint8_t adj[GRP_CLASSES][GRP_T_ATOMS][GRP_T_ATOMS]; // bond type between two template atoms, 0: none
+};
+
+constexpr GroupTables make_group_tables() {
+    // a ring of n atoms 0 ... n - 1 is the bonds (k, k + 1) and (0, n - 1), type 4; fused systems add their closing bonds
+    constexpr GroupTemplate list[GRP_CLASSES] = {
+        /*  0 c1ccccc1             */ {6, 6, {GL_c, GL_c, GL_c, GL_c, GL_c, GL_c}, {{0, 1, 4}, {1, 2, 4}, {2, 3, 4}, {3, 4, 4}, {4, 5, 4}, {0, 5, 4}}},
+        /*  1 NC=O                 */ {3, 2, {GL_N, GL_C, GL_O}, {{0, 1, 1}, {1, 2, 2}}},
+        /*  2 O=CO                 */ {3, 2, {GL_O, GL_C, GL_O}, {{0, 1, 2}, {1, 2, 1}}},
+        /*  3 c1ccncc1             */ {6, 6, {GL_c, GL_c, GL_c, GL_n, GL_c, GL_c}, {{0, 1, 4}, {1, 2, 4}, {2, 3, 4}, {3, 4, 4}, {4, 5, 4}, {0, 5, 4}}},
+        /*  4 c1ncc2nc[nH]c2n1     */ {9, 10, {GL_c, GL_n, GL_c, GL_c, GL_n, GL_c, GL_n, GL_c, GL_n},
+                                       {{0, 1, 4}, {1, 2, 4}, {2, 3, 4}, {3, 4, 4}, {4, 5, 4}, {5, 6, 4}, {6, 7, 4}, {3, 7, 4}, {7, 8, 4}, {0, 8, 4}}},
+        /*  5 NS(=O)=O             */ {4, 3, {GL_N, GL_S, GL_O, GL_O}, {{0, 1, 1}, {1, 2, 2}, {1, 3, 2}}},
+        /*  6 O=P(O)(O)O           */ {5, 4, {GL_O, GL_P, GL_O, GL_O, GL_O}, {{0, 1, 2}, {1, 2, 1}, {1, 3, 1}, {1, 4, 1}}},
+        /*  7 OCO                  */ {3, 2, {GL_O, GL_C, GL_O}, {{0, 1, 1}, {1, 2, 1}}},
+        /*  8 c1cncnc1             */ {6, 6, {GL_c, GL_c, GL_n, GL_c, GL_n, GL_c}, {{0, 1, 4}, {1, 2, 4}, {2, 3, 4}, {3, 4, 4}, {4, 5, 4}, {0, 5, 4}}},
+        /*  9 c1cn[nH]c1           */ {5, 5, {GL_c, GL_c, GL_n, GL_n, GL_c}, {{0, 1, 4}, {1, 2, 4}, {2, 3, 4}, {3, 4, 4}, {0, 4, 4}}},
+        /* 10 O=P(O)O              */ {4, 3, {GL_O, GL_P, GL_O, GL_O}, {{0, 1, 2}, {1, 2, 1}, {1, 3, 1}}},
+        /* 11 c1ccc2ccccc2c1       */ {10, 11, {GL_c, GL_c, GL_c, GL_c, GL_c, GL_c, GL_c, GL_c, GL_c, GL_c},
+                                       {{0, 1, 4}, {1, 2, 4}, {2, 3, 4}, {3, 4, 4}, {4, 5, 4}, {5, 6, 4}, {6, 7, 4}, {7, 8, 4}, {3, 8, 4}, {8, 9, 4}, {0, 9, 4}}},
+        /* 12 c1ccsc1              */ {5, 5, {GL_c, GL_c, GL_c, GL_s, GL_c}, {{0, 1, 4}, {1, 2, 4}, {2, 3, 4}, {3, 4, 4}, {0, 4, 4}}},
+        /* 13 N=CN                 */ {3, 2, {GL_N, GL_C, GL_N}, {{0, 1, 2}, {1, 2, 1}}},
+        /* 14 NC(N)=O              */ {4, 3, {GL_N, GL_C, GL_N, GL_O}, {{0, 1, 1}, {1, 2, 1}, {1, 3, 2}}},
+        /* 15 O=c1cc[nH]c(=O)[nH]1 */ {8, 8, {GL_O, GL_c, GL_c, GL_c, GL_n, GL_c, GL_O, GL_n},
+                                       {{0, 1, 2}, {1, 2, 4}, {2, 3, 4}, {3, 4, 4}, {4, 5, 4}, {5, 6, 2}, {5, 7, 4}, {1, 7, 4}}},
+        /* 16 c1ccc2ncccc2c1       */ {10, 11, {GL_c, GL_c, GL_c, GL_c, GL_n, GL_c, GL_c, GL_c, GL_c, GL_c},
+                                       {{0, 1, 4}, {1, 2, 4}, {2, 3, 4}, {3, 4, 4}, {4, 5, 4}, {5, 6, 4}, {6, 7, 4}, {7, 8, 4}, {3, 8, 4}, {8, 9, 4}, {0, 9, 4}}},
+        /* 17 c1cscn1              */ {5, 5, {GL_c, GL_c, GL_s, GL_c, GL_n}, {{0, 1, 4}, {1, 2, 4}, {2, 3, 4}, {3, 4, 4}, {0, 4, 4}}},
+        /* 18 c1ccc2[nH]cnc2c1     */ {9, 10, {GL_c, GL_c, GL_c, GL_c, GL_n, GL_c, GL_n, GL_c, GL_c},
+                                       {{0, 1, 4}, {1, 2, 4}, {2, 3, 4}, {3, 4, 4}, {4, 5, 4}, {5, 6, 4}, {6, 7, 4}, {3, 7, 4}, {7, 8, 4}, {0, 8, 4}}},
+        /* 19 c1c[nH]cn1           */ {5, 5, {GL_c, GL_c, GL_n, GL_c, GL_n}, {{0, 1, 4}, {1, 2, 4}, {2, 3, 4}, {3, 4, 4}, {0, 4, 4}}},
+        /* 20 O=[N+][O-]           */ {3, 2, {GL_O, GL_N, GL_O}, {{0, 1, 2}, {1, 2, 2}}},       // no charges here: the graph N(=O)=O
+        /* 21 O=CNO                */ {4, 3, {GL_O, GL_C, GL_N, GL_O}, {{0, 1, 2}, {1, 2, 1}, {2, 3, 1}}},
+        /* 22 NC(=O)O              */ {4, 3, {GL_N, GL_C, GL_O, GL_O}, {{0, 1, 1}, {1, 2, 2}, {1, 3, 1}}},
+        /* 23 O=S=O                */ {3, 2, {GL_O, GL_S, GL_O}, {{0, 1, 2}, {1, 2, 2}}},
+        /* 24 c1ccc2[nH]ccc2c1     */ {9, 10, {GL_c, GL_c, GL_c, GL_c, GL_n, GL_c, GL_c, GL_c, GL_c},
+                                       {{0, 1, 4}, {1, 2, 4}, {2, 3, 4}, {3, 4, 4}, {4, 5, 4}, {5, 6, 4}, {6, 7, 4}, {3, 7, 4}, {7, 8, 4}, {0, 8, 4}}}};
+    GroupTables g{};
+    for (int k = 0; k < GRP_CLASSES; ++k) {
+        g.t[k] = list[k];
+        for (int a = 0; a < list[k].n_atoms; ++a) g.hist[k] += 1ull << (4 * list[k].label[a]);
+        for (int b = 0; b < list[k].n_bonds; ++b) {
+            const GroupBond e = list[k].bond[b];
+            g.adj[k][e.i][e.j] = g.adj[k][e.j][e.i] = e.t;
+        }
+    }
+    return g;
 }
 
 // squared distance in fp64 from fp32 coordinates, each operation rounded on its own

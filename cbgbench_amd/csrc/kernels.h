@@ -300,6 +300,12 @@ hipError_t launch_ligand_interactions(const float* x_lig, const uint8_t* z_lig, 
                                       const uint8_t* implicit_h, const uint8_t* atom_flags, const int32_t* valence_status,
                                       double* atom_terms, uint8_t* lig_type, uint8_t* bond_rotatable, double* graph_terms,
                                       int32_t* graph_out, hipStream_t s);
+// groups.hip: functional groups of that bond list -- members by marking rules, groups as components under the group bonds, every group
+// held against the 25 template graphs of geo_tables.h by an exact isomorphism test (one group per lane); one wave per graph
+hipError_t launch_ligand_groups(const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs, const int32_t* bond_ptr,
+                                const int32_t* bond_index, const uint8_t* bond_order, const uint8_t* bond_aromatic, int n_bonds,
+                                int32_t* atom_group, uint8_t* atom_class, int32_t* graph_out, hipStream_t s);
+void ligand_groups_templates(uint8_t* n_atoms, uint8_t* n_bonds, uint8_t* labels, uint8_t* bonds);
 // distributions.hip: pair-distance histograms of the same ligands (two families, LDS integer histograms), and the bond angles of the
 // table-bond graph from its symmetric adjacency -- cosine, bin against a cosine table, canonical type; one workgroup per graph each
 hipError_t launch_ligand_pair_hist(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,

@@ -49,6 +49,13 @@ Vina's functional form on this library's own atom typing: NOT the Vina program, 
 hydrogens or protonation states in the pocket, an acceptor rule of our own for N, no intramolecular term, no metals, no Br / I,
 non-strict rotatable bonds.
 
+``ligand_groups`` / ``batch_groups`` / ``summarise_groups`` / ``groups_against`` are the functional-group numbers of the reference's
+substructure block (evaluate_scripts/evaluate_substruct_single.py; ``EFGs.mol2frag`` behind repo/tools/eval_fg_type.py): members by
+marking rules, groups as connected components under the group bonds, and each group's class by an exact isomorphism test against the 25
+template graphs of GROUP_NAMES, in one launch on the bond list and the aromatic report (``cbgx_ligand_groups``, csrc/groups.hip).
+Deviations: table bonds and this library's aromatic bonds; marking rules of our own, not the EFGs program; no charges; a single-atom
+group is 'other'.  ``groups_against`` takes the caller's own reference ratios and distribution: no dataset constants ship.
+
 ``ligand_pair_hist`` / ``ligand_angles`` / ``batch_distributions`` / ``summarise_distributions`` are the rest of that report, the
 distributions it compares with a dataset's by Jensen-Shannon distance (``repo/tools/geometry/eval_bond_length.py``,
 ``eval_bond_angle.py``): pair-distance histograms (``All_12A``, ``CC_2A``; reproduced exactly: they need coordinates and elements only),
@@ -850,6 +857,180 @@ def summarise_interaction_totals(totals):
 def summarise_interactions(graph_counts, graph_terms):
     """interaction statistics of a set of molecules from their per-molecule counts and terms: see ``summarise_interaction_totals``"""
     return summarise_interaction_totals(interaction_totals(graph_counts, graph_terms))
+
+
+# ---- functional groups of the table-bond graph ---------------------------------------------------------------------------------------------
+# include/cbgx.h CBGX_GROUPS_MAX_ATOMS / _CLASSES / _MAX_TEMPLATE_ATOMS / _MAX_TEMPLATE_BONDS
+MAX_GROUP_ATOMS, GROUP_CLASSES, MAX_GROUP_TEMPLATE_ATOMS, MAX_GROUP_TEMPLATE_BONDS = 256, 25, 10, 11
+# the named classes, in the order and under the names of the reference's vocabulary (repo/tools/eval_fg_type.py); class 25 is 'other'
+GROUP_NAMES = ("c1ccccc1", "NC=O", "O=CO", "c1ccncc1", "c1ncc2nc[nH]c2n1", "NS(=O)=O", "O=P(O)(O)O", "OCO", "c1cncnc1", "c1cn[nH]c1",
+               "O=P(O)O", "c1ccc2ccccc2c1", "c1ccsc1", "N=CN", "NC(N)=O", "O=c1cc[nH]c(=O)[nH]1", "c1ccc2ncccc2c1", "c1cscn1",
+               "c1ccc2[nH]cnc2c1", "c1c[nH]cn1", "O=[N+][O-]", "O=CNO", "NC(=O)O", "O=S=O", "c1ccc2[nH]ccc2c1")
+GROUP_OTHER, GROUP_NO_GROUP, GROUP_NOT_EVALUATED = 25, 254, 255       # atom_class beside 0 ... 24 (CBGX_GROUPS_NO_GROUP)
+# columns of ligand_groups' graph_counts (include/cbgx.h CBGX_GROUPS_GRAPH_COLS); fg_k: groups of class k
+GROUP_GRAPH_COLUMNS = (("n_atoms", "n_bonds", "n_groups", "n_group_atoms", "n_named", "largest_group")
+                       + tuple(f"fg_{k}" for k in range(GROUP_CLASSES)) + ("n_other", "status"))
+GROUPS_TOO_MANY_ATOMS, GROUPS_BAD_BONDS, GROUPS_NO_AROMATIC = 1, 4, 8     # status bits: a graph with status != 0 was not evaluated
+
+
+def group_name(cls):
+    """the name of a class 0 ... 25"""
+    return GROUP_NAMES[cls] if cls < GROUP_CLASSES else "other"
+
+
+def group_templates():
+    """the template graphs the library's kernel was built with (``cbgx_ligand_groups_templates``; host only), one per GROUP_NAMES entry:
+    {``name``, ``labels`` [(element code 0 ... 7 = H C N O F P S Cl, aromatic bit)], ``bonds`` [(atom, atom, type 1 ... 4)]}"""
+    n_atoms, n_bonds = np.zeros(GROUP_CLASSES, np.uint8), np.zeros(GROUP_CLASSES, np.uint8)
+    labels = np.zeros((GROUP_CLASSES, MAX_GROUP_TEMPLATE_ATOMS), np.uint8)
+    bonds = np.zeros((GROUP_CLASSES, MAX_GROUP_TEMPLATE_BONDS, 3), np.uint8)
+    _native.check(_native.lib().cbgx_ligand_groups_templates(*[ctypes.c_void_p(a.ctypes.data) for a in (n_atoms, n_bonds, labels, bonds)]),
+                  "cbgx_ligand_groups_templates")
+    return [{"name": GROUP_NAMES[k], "labels": [(int(v) >> 1, int(v) & 1) for v in labels[k, :n_atoms[k]]],
+             "bonds": [tuple(int(v) for v in row) for row in bonds[k, :n_bonds[k]]]} for k in range(GROUP_CLASSES)]
+
+
+def ligand_groups(z_lig, lig_batch, n_graphs, bonds, aromatic=None):
+    """Functional groups of the bond graphs of ``n_graphs`` ligands, one launch (``cbgx_ligand_groups``, csrc/groups.hip; the definition
+    is in include/cbgx.h) on the tensors' current stream: members by marking rules (aromatic atoms, hetero atoms, unsaturated, acetal and
+    hetero-triangle carbons), groups as the connected components of the members under the group bonds, and every group's class by an
+    exact isomorphism test against the 25 template graphs of GROUP_NAMES.
+
+    ``z_lig`` [n_lig] atomic numbers, ``lig_batch`` [n_lig] grouped by graph; ``bonds``: what ``ligand_bonds`` returned for the same atoms;
+    ``aromatic``: what ``ligand_aromatic`` returned for that list, or None: no bond is aromatic ('basic' atom types).  Returns device
+    tensors: ``atom_group`` [n_lig] int32 (the graph-local index of the smallest atom of the atom's group; -1: in no group),
+    ``atom_class`` [n_lig] uint8 (0 ... 24, GROUP_OTHER, GROUP_NO_GROUP) and ``graph_counts`` [n_graphs, 33] int32 (GROUP_GRAPH_COLUMNS).
+    A graph of more than MAX_GROUP_ATOMS atoms, with a malformed list, or that the aromatic report did not evaluate is not an error: its
+    status is non-zero (GROUPS_*), its columns from n_groups to n_other are -1, its ``atom_class`` 255 and its ``atom_group`` -2.
+    Deviations from the reference: table bonds and this library's aromatic bonds; marking rules of this library's own, not the EFGs
+    program (nothing claims agreement with it); no charges; a single-atom group is 'other'.  There is no CPU path."""
+    dev = z_lig.device
+    _gpu_only(dev, "ligand_groups", "cbgx_ligand_groups")
+    n_graphs = int(n_graphs)
+    bond_index, bond_order = bonds["bond_index"], bonds["bond_order"]
+    given = [("lig_batch", lig_batch), ("bond_index", bond_index), ("bond_order", bond_order)]
+    if aromatic is not None:
+        given += [("aromatic_bond", aromatic["aromatic_bond"]), ("bond_type", aromatic["bond_type"])]
+    for name, t in given:
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, z_lig on {dev}")
+    if bond_index.dim() != 2 or bond_index.shape[0] != 2:
+        raise ValueError("bond_index must be [2, n_bonds]")
+    n_lig, n_bonds = int(z_lig.shape[0]), int(bond_index.shape[1])
+    if z_lig.shape != (n_lig,) or lig_batch.shape != (n_lig,):
+        raise ValueError("one atomic number and one graph index per atom")
+    if any(t.shape != (n_bonds,) for _, t in given[2:]):
+        raise ValueError("one bond_order (and one aromatic_bond and bond_type) per bond")
+    lig_ptr = _csr(lig_batch, n_graphs, "lig_batch")
+    z_lig = _z_bytes(z_lig)
+    bond_index, bond_ptr = bond_index.to(torch.int32).contiguous(), _bond_ptr(bond_index, n_lig)
+    bond_order = bond_order.to(torch.uint8).contiguous()
+    flag = None
+    if aromatic is not None:      # the bytes cbgx_ligand_aromatic wrote: 0, 1, or 255 where it did not evaluate the graph
+        flag = torch.where(aromatic["bond_type"] == BOND_TYPE_NOT_EVALUATED, torch.full_like(bond_order, GROUP_NOT_EVALUATED),
+                           (aromatic["aromatic_bond"] != 0).to(torch.uint8)).contiguous()
+    atom_group = torch.empty(n_lig, dtype=torch.int32, device=dev)
+    atom_class = torch.empty(n_lig, dtype=torch.uint8, device=dev)
+    graph_counts = torch.empty(n_graphs, len(GROUP_GRAPH_COLUMNS), dtype=torch.int32, device=dev)
+    p = _native.ptr
+    _native.check(_native.lib().cbgx_ligand_groups(p(z_lig), p(lig_ptr), n_lig, n_graphs, p(bond_ptr), p(bond_index) if n_bonds else None,
+                                                   p(bond_order) if n_bonds else None, p(flag) if flag is not None and n_bonds else None,
+                                                   n_bonds, p(atom_group), p(atom_class), p(graph_counts), _native.current_stream(dev)),
+                  "cbgx_ligand_groups")
+    return {"atom_group": atom_group, "atom_class": atom_class, "graph_counts": graph_counts}
+
+
+def batch_groups(batch, x, c, lig_batch, mode, bonds=None, aromatic=None):
+    """``ligand_groups`` of a sampling state; ``bonds`` / ``aromatic``: what ``batch_bonds`` / ``batch_aromatic`` returned for the same
+    state.  ``bonds`` is computed here when None; so is ``aromatic`` when None and ``mode`` has aromatic atom types ('add_aromatic').  In
+    any other mode there are no flags to start from and no bond is aromatic"""
+    if bonds is None:
+        bonds = batch_bonds(batch, x, c, lig_batch, mode)
+    if aromatic is None and mode in _AROMATIC:
+        aromatic = batch_aromatic(batch, x, c, lig_batch, mode, bonds=bonds)
+    dev = bonds["bond_index"].device
+    lig_batch = lig_batch.to(dev)
+    _, z, n_graphs = _state_atoms(c, mode, lig_batch, {"num_graphs": bonds["graph_counts"].shape[0]}, dev)
+    return ligand_groups(z, lig_batch, n_graphs, bonds, aromatic)
+
+
+def group_names(atom_group, atom_class):
+    """the names of one molecule's groups in the order of their smallest atoms ('other' included), from its ``atom_group`` /
+    ``atom_class`` rows: a group is named at the atom that is its own ``atom_group``"""
+    grp, cls = (np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v).reshape(-1) for v in (atom_group, atom_class))
+    return [group_name(int(cls[a])) for a in range(grp.shape[0]) if int(grp[a]) == a]
+
+
+GROUP_COUNT_KEYS = (("n_mol", "n_mol_evaluated", "n_mol_over_limit", "n_atoms", "n_bonds", "n_groups", "n_group_atoms", "n_named")
+                    + tuple(f"n_fg_{k}" for k in range(GROUP_CLASSES)) + ("n_other", "n_mol_with_named_group"))
+GROUP_RATIOS = ("groups_per_mol", "named_group_ratio", "mol_with_named_group_ratio", "group_atom_ratio")
+
+
+def group_totals(graph_counts):
+    """per-molecule counts ``graph_counts`` [n_mol, 33] (GROUP_GRAPH_COLUMNS; any array-like) -> the integer totals, in GROUP_COUNT_KEYS
+    order.  Everything but n_mol and n_mol_over_limit is summed over the evaluated molecules (status == 0) only"""
+    gc = _counts(graph_counts, GROUP_GRAPH_COLUMNS)
+    ok = gc[gc[:, -1] == 0]
+    return ([int(gc.shape[0]), int(ok.shape[0]), int(gc.shape[0] - ok.shape[0])] + [int(v) for v in ok[:, :5].sum(0)]
+            + [int(v) for v in ok[:, 6:6 + GROUP_CLASSES + 1].sum(0)] + [int((ok[:, 4] > 0).sum())])
+
+
+def summarise_group_totals(totals):
+    """the substructure numbers of integer totals in GROUP_COUNT_KEYS order, over the EVALUATED molecules; a ratio over nothing is nan.
+    ``fg_ratio`` {name: groups of that class / molecules} is the reference's eval_fg_type_ratio, ``fg_distribution`` {name: groups of
+    that class / named groups} its eval_fg_type_distribution (all zeros without a named group); groups_per_mol; named_group_ratio: named
+    groups / groups; mol_with_named_group_ratio: molecules with at least one named group / molecules; group_atom_ratio: atoms in a group /
+    atoms; and the totals as ``counts``"""
+    c = {k: int(v) for k, v in zip(GROUP_COUNT_KEYS, totals)}
+    fg = [c[f"n_fg_{k}"] for k in range(GROUP_CLASSES)]
+    n_mol, n_named = c["n_mol_evaluated"], sum(fg)
+    return {"fg_ratio": {name: _ratio(v, n_mol) for name, v in zip(GROUP_NAMES, fg)},
+            "fg_distribution": {name: v / n_named if n_named else 0.0 for name, v in zip(GROUP_NAMES, fg)},
+            "groups_per_mol": _ratio(c["n_groups"], n_mol), "named_group_ratio": _ratio(c["n_named"], c["n_groups"]),
+            "mol_with_named_group_ratio": _ratio(c["n_mol_with_named_group"], n_mol),
+            "group_atom_ratio": _ratio(c["n_group_atoms"], c["n_atoms"]), "counts": c}
+
+
+def summarise_groups(graph_counts):
+    """functional-group statistics of a set of molecules from integer per-molecule counts (``graph_counts`` [n_mol, 33],
+    GROUP_GRAPH_COLUMNS): see ``summarise_group_totals``"""
+    return summarise_group_totals(group_totals(graph_counts))
+
+
+def _group_vector(values, what):
+    """a reference's 25 values in GROUP_NAMES order, from {name: value} or a vector"""
+    if isinstance(values, dict):
+        missing = [name for name in GROUP_NAMES if name not in values]
+        if missing:
+            raise ValueError(f"the reference {what} lacks {missing}")
+        values = [values[name] for name in GROUP_NAMES]
+    vec = np.asarray(values, np.float64).reshape(-1)
+    if vec.shape[0] != GROUP_CLASSES:
+        raise ValueError(f"the reference {what} has {vec.shape[0]} values, not {GROUP_CLASSES}")
+    return vec
+
+
+def groups_against(summary, reference):
+    """a job's functional groups (``summarise_group_totals``) against the caller's own reference -- none ships with this package --:
+    ``reference`` {'ratio': ..., 'distribution': ...}, each {name: value} over GROUP_NAMES or a 25-vector in that order.  Returns
+    ``MAE_fg``, the mean absolute difference of the 25 ratios (eval_fg_type_ratio), ``JSD_fg``, ``distribution_jsd`` of the two
+    distributions (eval_fg_type_distribution), and ``not_evaluated`` {key: reason} for a number that is None: no evaluated molecule has
+    no ratios, and a side that sums to zero has no distribution"""
+    ratio, dist = _group_vector(reference["ratio"], "ratio"), _group_vector(reference["distribution"], "distribution")
+    mine_ratio = np.asarray([summary["fg_ratio"][name] for name in GROUP_NAMES], np.float64)
+    mine_dist = np.asarray([summary["fg_distribution"][name] for name in GROUP_NAMES], np.float64)
+    out, why = {}, {}
+    if summary["counts"]["n_mol_evaluated"]:
+        out["MAE_fg"] = float(np.abs(ratio - mine_ratio).mean())
+    else:
+        out["MAE_fg"], why["MAE_fg"] = None, "no molecule was evaluated"
+    if mine_dist.sum() > 0 and dist.sum() > 0:
+        out["JSD_fg"] = distribution_jsd(mine_dist, dist)
+    else:
+        out["JSD_fg"] = None
+        why["JSD_fg"] = "no named group among the samples" if not mine_dist.sum() > 0 else "the reference distribution sums to zero"
+    out["not_evaluated"] = why
+    return out
 
 
 # the five reports that are integer counts per molecule, for a driver that treats them alike: per-molecule columns -> totals (what ranks

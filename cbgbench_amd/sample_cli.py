@@ -41,6 +41,10 @@ weight and ``mol_valid`` per sample and ``{out_dir}/valence_summary.json`` for t
 ``--interactions`` asks how the sample sits in its pocket: donor / acceptor / hydrophobic types of both sides, rotatable bonds and the five
 pair terms of Vina's functional form, computed on the device in two more launches per batch (``geometry.batch_interactions``), with
 ``score`` per sample and ``{out_dir}/interactions_summary.json`` for the job.  This library's own typing: not the Vina program.
+``--groups`` asks which functional groups the sample holds: members by marking rules, groups as connected components under the group
+bonds, each group's class out of the reference's 25 names by an exact isomorphism test, computed on the device in one more launch per batch
+(``geometry.batch_groups``), with the group names per sample and ``{out_dir}/groups_summary.json`` for the job; ``--groups_reference`` adds
+the MAE and the Jensen-Shannon distance to the caller's own ratios and distribution.  Marking rules of this library's own: not the EFGs program.
 ``--sdf`` writes ``pocket_{i:05d}.sdf`` beside every result file: one V2000 record per sample, bond types the Kekule orders of ``--valence``
 when given, else from ``--aromatic`` when given, table-bond orders otherwise (``geometry.sdf_record``; host side, no RDKit).
 A checkpoint is the reference's format: ``{'config': ..., 'model': state_dict}`` (``sample.py:153-156``)."""
@@ -149,7 +153,7 @@ def decode_mode(plan_mode, config_mode, num_classes):
 def main(argv=None, stats=None):
     """``stats`` (optional dict): filled with the wall seconds of the phases (setup = config + model + weights, batch = prior
     construction, sample = model.sample incl. the trajectory download, write = per-pocket records and files) and, for every requested report
-    (geometry, bonds, rings, aromatic, distributions, valence, interactions: evaluated in that order), its own launches and downloads, a part of write: the bond
+    (geometry, bonds, rings, aromatic, distributions, valence, interactions, groups: evaluated in that order), its own launches and downloads, a part of write: the bond
     list and the ring report are made once per batch, and where they were not asked for their time goes to the first requested report
     in that order that needs them (cbgbench_amd/sample_reports.py)."""
     t_phase = time.perf_counter()
@@ -262,6 +266,22 @@ def main(argv=None, stats=None):
                          "TABLE bonds, no hydrogens or protonation states in the pocket, no intramolecular term: NOT the Vina program "
                          "and not validated against it.  A sample over a limit is reported (interactions_status != 0) and left out of "
                          "every ratio.  Independent of every other flag: what it needs is computed and not written")
+    ap.add_argument("--groups", action="store_true",
+                    help="add the functional groups to every sample (atom_group [n]: the smallest atom of the atom's group, -1 in no "
+                         "group; atom_class [n]: 0 ... 24 the reference's 25 named groups, 25 other, 254 in no group; groups: the names of "
+                         "the sample's groups in the order of their smallest atoms, 'other' included; n_groups, fg_counts [26], "
+                         "groups_status), a `groups` dict of counts to every pocket record and {out_dir}/groups_summary.json (fg_ratio, "
+                         "fg_distribution as the reference's eval_fg_type_ratio / _distribution), evaluated on the GPU in one launch per "
+                         "batch on the bond list and, with add_aromatic atom types, the aromatic report (cbgbench_amd/geometry.py); with "
+                         "basic atom types no bond is aromatic.  Members: aromatic atoms, hetero atoms, unsaturated, acetal and "
+                         "hetero-triangle carbons; a group's class is isomorphism with a template graph.  TABLE bonds, marking rules of "
+                         "this library's own: NOT the EFGs program, no agreement with it is claimed; no charges; a single-atom group is "
+                         "'other'.  A sample over a limit is reported (groups_status != 0) and left out of every ratio.  Independent of "
+                         "every other flag: what it needs is computed and not written")
+    ap.add_argument("--groups_reference", default=None,
+                    help="with --groups: a .npz or torch.save'd dict {'ratio': ..., 'distribution': ...}, each the 25 values in the order "
+                         "of the vocabulary (a torch.save'd dict may hold {name: value} dicts instead; none ship with this package); "
+                         "groups_summary.json then carries MAE_fg and JSD_fg")
     ap.add_argument("--sdf", action="store_true",
                     help="write pocket_XXXXX.sdf beside every pocket_XXXXX.pt: one V2000 record per sample with the positions the record "
                          "holds, bond types from --aromatic when given (4 = aromatic), else the table-bond orders (bonds are computed "

@@ -1,4 +1,4 @@
-"""The reports of ``sample_cli`` (--geometry, --bonds, --rings, --aromatic, --distributions, --valence, --interactions, --sdf) in three stages: ``evaluate`` runs the
+"""The reports of ``sample_cli`` (--geometry, --bonds, --rings, --aromatic, --distributions, --valence, --interactions, --groups, --sdf) in three stages: ``evaluate`` runs the
 requested reports of one batch on the GPU and returns plain dicts of CPU tensors; ``annotate`` / ``pocket_counts`` / ``pocket_files``
 turn those into the per-sample fields, the per-pocket dicts and the ``.sdf`` text on the host (CPU tensors in, no device); ``finish`` sums
 the job's integer totals over the ranks, writes ``*_summary.json`` and prints one line per report.
@@ -12,7 +12,11 @@ The reports of EXTRA come after those of ORDER, under the same rules, in every s
 in Vina's functional form on this library's own atom typing: not the Vina program, not validated against it) is the first report that
 reads the pocket's chemistry (``protein_aa_type``, the backbone column of ``protein_atom_feature``); it takes the bond list and the valence
 report, and through the latter whatever ``needs("valence", mode)`` says.  Its job numbers are sums of integers too: every sample's score is
-rounded to a whole number of millionths before the ranks add them up."""
+rounded to a whole number of millionths before the ranks add them up.
+
+The reports of LATE come after those of EXTRA, under the same rules again.  ``groups`` (the functional groups of the substructure block:
+marking rules of this library's own, not the EFGs program) takes what the valence report takes: the bond list, and the aromatic report
+where the atom types have aromatic flags."""
 import json
 import os
 import time
@@ -25,13 +29,14 @@ from .config import _AROMATIC
 
 ORDER = ("geometry", "bonds", "rings", "aromatic", "distributions", "valence")
 EXTRA = ("interactions",)        # evaluated, annotated and finished after ORDER
+LATE = ("groups",)               # ... and these after EXTRA
 NEEDS = {"rings": ("bonds",), "aromatic": ("bonds", "rings"), "distributions": ("bonds",), "valence": ("bonds", "aromatic"),
-         "interactions": ("bonds", "valence")}
+         "interactions": ("bonds", "valence"), "groups": ("bonds", "aromatic")}
 
 
 def needs(name, mode):
     """what report ``name`` is computed from under the atom-type vocabulary ``mode``"""
-    if name == "valence" and mode not in _AROMATIC:
+    if name in ("valence", "groups") and mode not in _AROMATIC:
         return ("bonds",)
     return NEEDS.get(name, ())
 
@@ -45,6 +50,7 @@ _GPU_ONLY = {"geometry": "--geometry runs on the GPU (cbgx_ligand_geometry has n
              "aromatic": "--aromatic runs on the GPU (cbgx_ligand_aromatic has no CPU fallback)",
              "valence": "--valence runs on the GPU (cbgx_ligand_valence has no CPU fallback)",
              "interactions": "--interactions runs on the GPU (cbgx_pocket_types / cbgx_ligand_interactions have no CPU fallback)",
+             "groups": "--groups runs on the GPU (cbgx_ligand_groups has no CPU fallback)",
              "sdf": "--sdf takes its bonds from the GPU (cbgx_ligand_bonds_count / _fill have no CPU fallback)"}
 # a count report's printed line: the ratios it names, and its own tail
 _LINE = {"geometry": (geometry.RATIOS, lambda c: f"{c['n_mol']} molecules, {c['n_atoms']} atoms"),
@@ -69,6 +75,19 @@ def load_reference_distributions(path):
     return {k: np.asarray(v, np.float64) for k, v in raw.items()}
 
 
+def load_reference_groups(path):
+    """``--groups_reference``: {'ratio': ..., 'distribution': ...} from a ``.npz`` (np.savez(path, ratio=v25, distribution=v25)) or a
+    ``torch.save``d dict whose two values are 25-vectors or {name: value} dicts"""
+    if path.endswith(".npz"):
+        with np.load(path) as f:
+            raw = {k: np.asarray(f[k], np.float64) for k in f.files}
+    else:
+        raw = torch.load(path, map_location="cpu", weights_only=False)
+    if not isinstance(raw, dict) or not {"ratio", "distribution"} <= set(raw):
+        raise SystemExit(f"sample_cli: {path} does not hold a dict with 'ratio' and 'distribution'")
+    return {k: raw[k] for k in ("ratio", "distribution")}
+
+
 def ranges(counts):
     """a per-graph count column [B] -> [(start, end)] per graph: rows (atoms, bonds, angles) are grouped by graph, in graph order"""
     ends = counts.to(torch.int64).cumsum(0).tolist()
@@ -76,26 +95,30 @@ def ranges(counts):
 
 
 class SampleReports:
-    """``requested``: names out of ORDER, EXTRA and 'sdf'; ``reference``: the path of --distributions_reference"""
+    """``requested``: names out of ORDER, EXTRA, LATE and 'sdf'; ``reference``: the path of --distributions_reference;
+    ``groups_reference``: that of --groups_reference"""
 
-    def __init__(self, requested, reference=None):
+    def __init__(self, requested, reference=None, groups_reference=None):
         self.requested = frozenset(requested)
         self.reference = reference
+        self.groups_reference = groups_reference
         self.n_orders = 4 if "aromatic" in self.requested else 3        # --aromatic --distributions: types with the aromatic type
-        self.seconds = {name: 0.0 for name in ORDER + EXTRA if name in self.requested}         # wall time of every report (``stats``)
+        self.seconds = {name: 0.0 for name in ORDER + EXTRA + LATE if name in self.requested}  # wall time of every report (``stats``)
         self.counts = {name: [] for name in _COUNT_REPORTS if name in self.requested}  # per-sample counts of this rank
         # the pockets' flat integer totals are added up as they come (one is 3.5 MB)
         self.distribution_totals = np.zeros(geometry.distribution_totals_length(n_orders=self.n_orders), np.int64)
         self.sdf_left_out, self.sdf_written = 0, 0
         self.interactions = []                                          # (graph_counts, graph_terms) of this rank's pockets
+        self.groups = []                                                # graph_counts of this rank's pockets
 
     @classmethod
     def from_args(cls, args):
-        return cls([name for name in ORDER + EXTRA + ("sdf",) if getattr(args, name)], args.distributions_reference)
+        return cls([name for name in ORDER + EXTRA + LATE + ("sdf",) if getattr(args, name, False)], args.distributions_reference,
+                   getattr(args, "groups_reference", None))
 
     def refuse(self, dev, atom_mode):
         """what cannot run is refused before any model is built; ``atom_mode()``: the vocabulary the samples are decoded with"""
-        for name in ("geometry", "bonds", "rings", "distributions", "aromatic", "valence") + EXTRA + ("sdf",):
+        for name in ("geometry", "bonds", "rings", "distributions", "aromatic", "valence") + EXTRA + LATE + ("sdf",):
             if name not in self.requested:
                 continue
             if name == "aromatic" and atom_mode() != "add_aromatic":
@@ -106,6 +129,8 @@ class SampleReports:
                 raise SystemExit("sample_cli: " + _GPU_ONLY[name])
         if self.reference and "distributions" not in self.requested:
             raise SystemExit("sample_cli: --distributions_reference needs --distributions")
+        if self.groups_reference and "groups" not in self.requested:
+            raise SystemExit("sample_cli: --groups_reference needs --groups")
 
     # ---- GPU -----------------------------------------------------------------------------------------------------------------------------
     def evaluate(self, dev, state, batch, n_graphs, mode):
@@ -214,6 +239,15 @@ class SampleReports:
                 for k in ("n_rotatable", "n_hbond_pairs", "n_hydrophobic_pairs", "n_close_pairs", "n_contact_atoms"):
                     smp[k] = row[k]
                 smp["interactions_status"] = row["status"]
+        if "groups" in self.requested:
+            grp, gc = ev["groups"], ev["groups"]["graph_counts"].to(torch.int64)
+            for g, (smp, (a0, a1)) in enumerate(zip(samples, ranges(gc[:, 0]))):
+                smp["atom_group"] = grp["atom_group"][a0:a1].clone()
+                smp["atom_class"] = grp["atom_class"][a0:a1].clone()
+                smp["groups"] = geometry.group_names(smp["atom_group"], smp["atom_class"])
+                smp["n_groups"] = int(gc[g, 2])
+                smp["fg_counts"] = gc[g, 6:6 + geometry.GROUP_CLASSES + 1].clone()
+                smp["groups_status"] = int(gc[g, -1])
 
     def pocket_counts(self, ev, g0, g1):
         """the dicts of counts a pocket record carries for its graphs g0 ... g1 - 1, which join the job's totals"""
@@ -231,6 +265,10 @@ class SampleReports:
             gc, terms = ev["interactions"]["graph_counts"][g0:g1].to(torch.int64), ev["interactions"]["graph_terms"][g0:g1]
             self.interactions.append((gc, terms))
             rec["interactions"] = geometry.summarise_interactions(gc, terms)["counts"]
+        if "groups" in self.requested:
+            gc = ev["groups"]["graph_counts"][g0:g1].to(torch.int64)
+            self.groups.append(gc)
+            rec["groups"] = geometry.summarise_groups(gc)["counts"]
         return rec
 
     def pocket_files(self, stem, samples, ev, g0):
@@ -285,6 +323,21 @@ class SampleReports:
                 print("interactions: " + ", ".join(f"{k} {summary[k]:.4f}" for k in geometry.INTERACTION_RATIOS)
                       + f" ({cnt['n_mol_evaluated']} of {cnt['n_mol']} molecules evaluated, n_mol_over_limit {cnt['n_mol_over_limit']}; a score "
                         f"in Vina's functional form, not the Vina program)")
+        if "groups" in self.requested:
+            totals = [0] * len(geometry.GROUP_COUNT_KEYS)
+            for gc in self.groups:                   # integer totals: pocket by pocket is the whole
+                totals = [a + b for a, b in zip(totals, geometry.group_totals(gc))]
+            summary = geometry.summarise_group_totals(sharding.sum_counts(totals, device=dev))
+            if rank == 0:
+                if self.groups_reference:
+                    summary.update(geometry.groups_against(summary, load_reference_groups(self.groups_reference)))
+                save("groups", summary)
+                cnt = summary["counts"]
+                top = sorted(range(geometry.GROUP_CLASSES), key=lambda k: (-cnt[f"n_fg_{k}"], k))[:3]
+                print("groups: " + ", ".join(f"{k} {summary[k]:.4f}" for k in geometry.GROUP_RATIOS)
+                      + "; most frequent: " + ", ".join(f"{geometry.GROUP_NAMES[k]} {cnt[f'n_fg_{k}']}" for k in top)
+                      + f" ({cnt['n_mol_evaluated']} of {cnt['n_mol']} molecules evaluated, n_mol_over_limit {cnt['n_mol_over_limit']}; "
+                        f"marking rules of this library's own, not the EFGs program)")
         if "sdf" in self.requested:
             left_out, written = sharding.sum_counts([self.sdf_left_out, self.sdf_written], device=dev)
             if rank == 0:

@@ -1031,6 +1031,68 @@ int cbgx_ligand_interactions(const float *x_lig, const uint8_t *z_lig, const int
                              const uint8_t *implicit_h, const uint8_t *atom_flags, const int32_t *valence_status, double *atom_terms,
                              uint8_t *lig_type, uint8_t *bond_rotatable, double *graph_terms, int32_t *graph_out, void *stream);
 
+/* ---- functional groups of the table-bond graph of sampled ligands (groups.hip) -----------------------------------------------------------
+ * Which functional groups does the sample hold?  The reference counts them with `EFGs.mol2frag` after RDKit reconstruction
+ *   (repo/tools/eval_fg_type.py; evaluate_scripts/evaluate_substruct_single.py) and compares 25 named ones with a dataset.  Here: a
+ *   partition of the bond graph into groups by marking rules in the manner of P. Ertl ("An algorithm to identify functional groups in
+ *   organic molecules", J. Cheminform. 9 (2017) 36), and an exact graph-isomorphism test of every group against 25 template graphs.  One
+ *   launch, one wave per graph, integer work only.  Deviations: TABLE bonds (cbgx_ligand_bonds_fill) and this library's aromatic bonds
+ *   (cbgx_ligand_aromatic); marking rules of this library's own, NOT the EFGs program: nothing may claim agreement with it; no charges
+ *   (a nitro group is the graph N(=O)=O); a group of a single atom (an ether O, an amine N, a halogen) is `other`.
+ * Inputs: z_lig, lig_ptr, bond_ptr, bond_index, bond_order (1..3), bond_aromatic (1 aromatic, 255 not evaluated, anything else not
+ *   aromatic; NULL: no bond is aromatic) as cbgx_ligand_valence takes them.  The TYPE of a bond is t = 4 if bond_aromatic == 1, else its
+ *   order.  No Kekule structure and no hydrogens are needed.
+ * Atom kinds: an atom is AROMATIC if it has a bond of type 4, HETERO if it is N, O, F, P, S or Cl.  H atoms and atoms outside the eight
+ *   elements belong to no group (their bonds still make their partners aromatic, or unsaturated under (a)).
+ * Members: every aromatic atom, every hetero atom, and a non-aromatic carbon for which one of these holds:
+ *   (a) it has a bond of type 2 or 3;
+ *   (b) acetal: all its bonds are type 1, and at least two of its neighbours are non-aromatic N, O or S atoms all of whose own bonds are
+ *       type 1;
+ *   (c) it lies on a triangle of bonds, none of type 4, one of whose atoms is N, O or S (oxirane, aziridine, thiirane).
+ * Group bonds: a bond between two members is a group bond iff it has type 4, or neither end is aromatic, or exactly one end is aromatic
+ *   and the type is 2 (an exocyclic double bond: pyridone, uracil).  A single bond from a ring to a substituent is none (phenol: a ring
+ *   and an O), nor is a non-aromatic bond between two aromatic atoms (biphenyl: two rings).
+ * Groups: the connected components of the members under the group bonds.  The labelled graph of a group: its atoms as (element code,
+ *   aromatic bit) and its group bonds with their types; a bond between two atoms of a group that is no group bond is not part of it.
+ * Classes: 25 named ones, in the order and under the names of the reference's vocabulary, and other = CBGX_GROUPS_CLASSES:
+ *    0 c1ccccc1   1 NC=O   2 O=CO   3 c1ccncc1   4 c1ncc2nc[nH]c2n1   5 NS(=O)=O   6 O=P(O)(O)O   7 OCO   8 c1cncnc1   9 c1cn[nH]c1
+ *   10 O=P(O)O   11 c1ccc2ccccc2c1   12 c1ccsc1   13 N=CN   14 NC(N)=O   15 O=c1cc[nH]c(=O)[nH]1   16 c1ccc2ncccc2c1   17 c1cscn1
+ *   18 c1ccc2[nH]cnc2c1   19 c1c[nH]cn1   20 O=[N+][O-]   21 O=CNO   22 NC(=O)O   23 O=S=O   24 c1ccc2[nH]ccc2c1
+ *   Each name stands for one template graph in the same labelling (csrc/geo_tables.h; cbgx_ligand_groups_templates hands it out):
+ *   lower-case atoms are aromatic and their ring bonds type 4; [nH] is an aromatic N like any other (hydrogens and tautomers play no
+ *   part); O=[N+][O-] is N(=O)=O; OCO is O-C-O with single bonds.  A group has class k iff its labelled graph is isomorphic to template
+ *   k, elements, aromatic bits and bond types preserved; a group of more than CBGX_GROUPS_MAX_TEMPLATE_ATOMS atoms is `other` without a
+ *   test; everything else is `other`.  The class is a property: no step budget is part of the interface.
+ * Outputs, dense, every element of every graph's ranges written: atom_group [n_lig] int32, the graph-local index of the smallest atom of
+ *   the atom's group, -1 for an atom in no group; atom_class [n_lig] uint8, the class of its group 0 ... 25, CBGX_GROUPS_NO_GROUP for an
+ *   atom in no group; graph_out [B, CBGX_GROUPS_GRAPH_COLS] int32: n_atoms, n_bonds, n_groups, n_group_atoms, n_named (groups of class <
+ *   25), largest_group (atoms; 0 without groups), fg_0 ... fg_24, n_other, status.
+ * Status, per graph, never an error, set side by side: CBGX_GROUPS_TOO_MANY_ATOMS (more than CBGX_GROUPS_MAX_ATOMS atoms),
+ *   CBGX_GROUPS_BAD_BONDS (the conditions of CBGX_RINGS_BAD_BONDS, or a bond_order outside 1..3), CBGX_GROUPS_NO_AROMATIC (a bond of the
+ *   graph has bond_aromatic == 255).  With status != 0 the columns from n_groups on, except status, are -1, the graph's bytes of
+ *   atom_class are 255 and its entries of atom_group -2; n_atoms and n_bonds are the (clamped) sizes of the two ranges.  Every entry of
+ *   lig_ptr, bond_ptr and bond_index is clamped or checked before it is used as an index, and overlapping ranges of a malformed lig_ptr
+ *   or bond_ptr are undefined as in cbgx_ligand_valence.  No atomics on memory; nothing in the outputs depends on scheduling.
+ * Returns 0, and 0 without a launch when B == 0.  CBGX_E_INVALID before any dereference or launch: negative counts, a NULL pointer with a
+ *   non-zero count (bond_index and bond_order may be NULL when n_bonds == 0; bond_aromatic always), and any array with a non-zero count
+ *   whose pointer is not memory the device can read (plain host memory; asked for in argument order, the first such array is named in
+ *   cbgx_last_error).
+ * cbgx_ligand_groups_templates (host only): n_atoms [25] uint8, n_bonds [25] uint8, labels [25, 10] uint8 ((element code << 1) |
+ *   aromatic bit; codes H C N O F P S Cl = 0 ... 7), bonds [25, 11, 3] uint8 (atom, atom, type); unused entries 0. */
+#define CBGX_GROUPS_MAX_ATOMS 256
+#define CBGX_GROUPS_CLASSES 25
+#define CBGX_GROUPS_MAX_TEMPLATE_ATOMS 10
+#define CBGX_GROUPS_MAX_TEMPLATE_BONDS 11
+#define CBGX_GROUPS_NO_GROUP 254
+#define CBGX_GROUPS_GRAPH_COLS 33   /* n_atoms, n_bonds, n_groups, n_group_atoms, n_named, largest_group, fg_0 ... fg_24, n_other, status */
+#define CBGX_GROUPS_TOO_MANY_ATOMS 1
+#define CBGX_GROUPS_BAD_BONDS 4
+#define CBGX_GROUPS_NO_AROMATIC 8
+int cbgx_ligand_groups(const uint8_t *z_lig, const int32_t *lig_ptr, int n_lig, int n_graphs, const int32_t *bond_ptr,
+                       const int32_t *bond_index, const uint8_t *bond_order, const uint8_t *bond_aromatic, int n_bonds,
+                       int32_t *atom_group, uint8_t *atom_class, int32_t *graph_out, void *stream);
+int cbgx_ligand_groups_templates(uint8_t *n_atoms, uint8_t *n_bonds, uint8_t *labels, uint8_t *bonds);
+
 /* ---- distributions of sampled ligands: pair distances, bond lengths, bond angles (distributions.hip) -----------------------------------
  * The rest of the reference's geometry report (evaluate_scripts/evaluate_geom_single.py; repo/tools/geometry/eval_bond_length.py,
  *   eval_bond_angle.py): histograms that are compared with a dataset's by Jensen-Shannon distance.  Distances and element codes are those
