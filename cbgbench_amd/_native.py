@@ -111,6 +111,8 @@ EXPORTS = {
     "cbgx_ligand_interactions": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i] + [_vp] * 9),
     "cbgx_ligand_groups": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "cbgx_ligand_groups_templates": (_i, [_vp] * 4),
+    "cbgx_ligand_fingerprints": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "cbgx_group_diversity": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cbgx_ligand_pair_hist": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "cbgx_ligand_angles": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "cbgx_profile_begin": (_i, [_i]),

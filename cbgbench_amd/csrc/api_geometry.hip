@@ -1,9 +1,11 @@
 // libcbgx -- C ABI of the geometry report, of the bond list, of the ring sizes, of the aromatic report, of the valence report, of the
-// interaction report, of the functional groups and of the distributions (include/cbgx.h, geometry.hip, rings.hip, aromatic.hip,
-// valence.hip, interactions.hip, groups.hip, distributions.hip): argument checks, the ligand-size check, the launch
+// interaction report, of the functional groups, of the fingerprints and of the distributions (include/cbgx.h, geometry.hip, rings.hip,
+// aromatic.hip, valence.hip, interactions.hip, groups.hip, diversity.hip, distributions.hip): argument checks, the ligand-size check, the
+// launch
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdint>
 #include <cstring>
 #include <vector>
 
@@ -251,7 +253,50 @@ int cbgx_ligand_groups_templates(uint8_t* n_atoms, uint8_t* n_bonds, uint8_t* la
     return CBGX_OK;
 }
 
-int cbgx_ligand_pair_hist(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,
+int cbgx_ligand_fingerprints(const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs, const int32_t* bond_ptr,
+                             const int32_t* bond_index, const uint8_t* bond_type, const uint8_t* atom_ring_min, int n_bonds, uint32_t* fp,
+                             uint64_t* mol_hash, int32_t* graph_out, void* stream) {
+    if (n_graphs < 0 || n_lig < 0 || n_bonds < 0)
+        return set_error(CBGX_E_INVALID, "ligand_fingerprints: negative count (B=%d n_lig=%d n_bonds=%d)", n_graphs, n_lig, n_bonds);
+    if ((n_graphs > 0 && (!lig_ptr || !bond_ptr || !fp || !mol_hash || !graph_out)) || (n_lig > 0 && (!z_lig || !atom_ring_min)) ||
+        (n_bonds > 0 && (!bond_index || !bond_type)))
+        return set_error(CBGX_E_INVALID, "ligand_fingerprints: NULL pointer");
+    if (n_graphs == 0) return CBGX_OK;
+    const DeviceArray arrays[] = {
+        {"z_lig", z_lig, n_lig}, {"lig_ptr", lig_ptr, n_graphs + 1}, {"bond_ptr", bond_ptr, n_lig + 1}, {"bond_index", bond_index, n_bonds},
+        {"bond_type", bond_type, n_bonds}, {"atom_ring_min", atom_ring_min, n_lig}, {"fp", fp, n_graphs}, {"mol_hash", mol_hash, n_graphs},
+        {"graph_out", graph_out, n_graphs}};
+    const int rc = device_visible("ligand_fingerprints", arrays, (int)(sizeof(arrays) / sizeof(arrays[0])));
+    if (rc != CBGX_OK) return rc;
+    const hipError_t e = launch_ligand_fingerprints(z_lig, lig_ptr, n_lig, n_graphs, bond_ptr, bond_index, bond_type, atom_ring_min, n_bonds,
+                                                    fp, mol_hash, graph_out, (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(CBGX_E_HIP, "ligand_fingerprints: launch: %s", hipGetErrorString(e));
+    return CBGX_OK;
+}
+
+int cbgx_group_diversity(const uint32_t* fp, const uint64_t* mol_hash, const int32_t* status, const int32_t* group_ptr,
+                         const int64_t* pair_ptr, int n_graphs, int n_groups, long long n_pairs, int32_t* pair_sim, int32_t* first_same,
+                         int32_t* nearest, int32_t* nearest_micro, int64_t* group_out, void* stream) {
+    if (n_graphs < 0 || n_groups < 0 || n_pairs < 0)
+        return set_error(CBGX_E_INVALID, "group_diversity: negative count (B=%d P=%d n_pairs=%lld)", n_graphs, n_groups, n_pairs);
+    if ((n_groups > 0 && (!group_ptr || !pair_ptr || !group_out)) ||
+        (n_graphs > 0 && (!fp || !mol_hash || !status || !first_same || !nearest || !nearest_micro)) || (n_pairs > 0 && !pair_sim))
+        return set_error(CBGX_E_INVALID, "group_diversity: NULL pointer");
+    if (n_groups == 0) return CBGX_OK;
+    if ((uintptr_t)fp % 16 != 0) return set_error(CBGX_E_INVALID, "group_diversity: fp is not aligned to 16 bytes");
+    const DeviceArray arrays[] = {
+        {"fp", fp, n_graphs}, {"mol_hash", mol_hash, n_graphs}, {"status", status, n_graphs}, {"group_ptr", group_ptr, n_groups + 1},
+        {"pair_ptr", pair_ptr, n_groups + 1}, {"pair_sim", pair_sim, n_pairs > 0 ? 1 : 0}, {"first_same", first_same, n_graphs},
+        {"nearest", nearest, n_graphs}, {"nearest_micro", nearest_micro, n_graphs}, {"group_out", group_out, n_groups}};
+    const int rc = device_visible("group_diversity", arrays, (int)(sizeof(arrays) / sizeof(arrays[0])));
+    if (rc != CBGX_OK) return rc;
+    const hipError_t e = launch_group_diversity(fp, mol_hash, status, group_ptr, pair_ptr, n_graphs, n_groups, n_pairs, pair_sim, first_same,
+                                                nearest, nearest_micro, group_out, (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(CBGX_E_HIP, "group_diversity: launch: %s", hipGetErrorString(e));
+    return CBGX_OK;
+}
+
+int cbgx_ligand_pair_hist(const float* x_lig,const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,
                           const double* edges_all, int n_edges_all, const double* edges_cc, int n_edges_cc, int32_t* pair_hist,
                           void* stream) {
     if (n_graphs < 0 || n_lig < 0 || n_edges_all < 0 || n_edges_cc < 0)

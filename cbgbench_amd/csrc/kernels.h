@@ -306,6 +306,15 @@ hipError_t launch_ligand_groups(const uint8_t* z_lig, const int32_t* lig_ptr, in
                                 const int32_t* bond_index, const uint8_t* bond_order, const uint8_t* bond_aromatic, int n_bonds,
                                 int32_t* atom_group, uint8_t* atom_class, int32_t* graph_out, hipStream_t s);
 void ligand_groups_templates(uint8_t* n_atoms, uint8_t* n_bonds, uint8_t* labels, uint8_t* bonds);
+// diversity.hip: a 1024-bit fingerprint and a 64-bit hash of every graph of that bond list by colour refinement over its typed bonds (one
+// wave per graph), and, one workgroup per group of consecutive graphs, the Tanimoto similarity of every pair, each graph's nearest
+// neighbour and the first graph of equal hash
+hipError_t launch_ligand_fingerprints(const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs, const int32_t* bond_ptr,
+                                      const int32_t* bond_index, const uint8_t* bond_type, const uint8_t* atom_ring_min, int n_bonds,
+                                      uint32_t* fp, uint64_t* mol_hash, int32_t* graph_out, hipStream_t s);
+hipError_t launch_group_diversity(const uint32_t* fp, const uint64_t* mol_hash, const int32_t* status, const int32_t* group_ptr,
+                                  const int64_t* pair_ptr, int n_graphs, int n_groups, long long n_pairs, int32_t* pair_sim,
+                                  int32_t* first_same, int32_t* nearest, int32_t* nearest_micro, int64_t* group_out, hipStream_t s);
 // distributions.hip: pair-distance histograms of the same ligands (two families, LDS integer histograms), and the bond angles of the
 // table-bond graph from its symmetric adjacency -- cosine, bin against a cosine table, canonical type; one workgroup per graph each
 hipError_t launch_ligand_pair_hist(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,

@@ -56,6 +56,15 @@ template graphs of GROUP_NAMES, in one launch on the bond list and the aromatic 
 Deviations: table bonds and this library's aromatic bonds; marking rules of our own, not the EFGs program; no charges; a single-atom
 group is 'other'.  ``groups_against`` takes the caller's own reference ratios and distribution: no dataset constants ship.
 
+``ligand_fingerprints`` / ``group_diversity`` / ``batch_diversity`` / ``summarise_diversity`` are the first numbers ACROSS the samples of
+a pocket: the share of distinct molecules and one minus the mean pairwise Tanimoto similarity, where the reference has
+``tanimoto_sim`` on ``Chem.RDKFingerprint`` (repo/tools/similarity.py) and SMILES strings behind RDKit reconstruction.  A 1024-bit
+fingerprint and a 64-bit hash per graph by colour refinement over the typed bonds from (element, degree, aromatic, smallest ring), then
+one workgroup per pocket for the pairs (``cbgx_ligand_fingerprints`` / ``cbgx_group_diversity``, csrc/diversity.hip).  Integer work only.
+Deviations: table bonds and this library's aromatic bonds; a fingerprint of our own in the manner of ECFP4, neither RDKit's Morgan
+fingerprint nor ``RDKFingerprint``; equal hashes mean equivalence under the refinement, not isomorphism.  ``tanimoto_micro`` is the host
+helper for fingerprints of different pockets or a ligand of the caller's own.
+
 ``ligand_pair_hist`` / ``ligand_angles`` / ``batch_distributions`` / ``summarise_distributions`` are the rest of that report, the
 distributions it compares with a dataset's by Jensen-Shannon distance (``repo/tools/geometry/eval_bond_length.py``,
 ``eval_bond_angle.py``): pair-distance histograms (``All_12A``, ``CC_2A``; reproduced exactly: they need coordinates and elements only),
@@ -1031,6 +1040,216 @@ def groups_against(summary, reference):
         why["JSD_fg"] = "no named group among the samples" if not mine_dist.sum() > 0 else "the reference distribution sums to zero"
     out["not_evaluated"] = why
     return out
+
+
+# ---- fingerprints of the table-bond graph; uniqueness and similarity across the samples of a pocket ----------------------------------------
+# include/cbgx.h CBGX_FINGERPRINT_MAX_ATOMS / _BITS / _WORDS, CBGX_DIVERSITY_MAX_GROUP
+MAX_FINGERPRINT_ATOMS, FINGERPRINT_BITS, FINGERPRINT_WORDS, MAX_DIVERSITY_GROUP = 256, 1024, 32, 1024
+# columns of ligand_fingerprints' graph_counts (CBGX_FINGERPRINT_GRAPH_COLS) and of group_diversity's group_counts (CBGX_DIVERSITY_GROUP_COLS)
+FINGERPRINT_GRAPH_COLUMNS = ("n_atoms", "n_bonds", "n_bits", "n_rounds", "status")
+DIVERSITY_GROUP_COLUMNS = ("n_graphs", "n_evaluated", "n_unique", "n_pairs", "sim_micro_sum", "sim_micro_max", "status")
+# status bits of a graph (a graph with status != 0 was not evaluated) and of a group
+FINGERPRINT_TOO_MANY_ATOMS, FINGERPRINT_BAD_BONDS, FINGERPRINT_NO_TYPES, FINGERPRINT_EMPTY = 1, 4, 8, 16
+DIVERSITY_TOO_MANY_GRAPHS, DIVERSITY_BAD_GROUPS = 1, 4
+SIMILARITY_ONE = 1000000                   # similarities are whole millionths
+
+
+def ligand_fingerprints(z_lig, lig_batch, n_graphs, bonds, rings, aromatic=None):
+    """A 1024-bit fingerprint and a 64-bit hash of the bond graphs of ``n_graphs`` ligands, one launch (``cbgx_ligand_fingerprints``,
+    csrc/diversity.hip; the definition is in include/cbgx.h) on the tensors' current stream: colour refinement from (element, degree,
+    aromatic, smallest ring) over the typed bonds, max(n_atoms, 2) rounds; the labels of rounds 0, 1, 2 set the bits, those of the last
+    round make the hash.  Integer work only; neither depends on the order of atoms or bonds.
+
+    ``z_lig`` [n_lig] atomic numbers, ``lig_batch`` [n_lig] grouped by graph; ``bonds`` / ``rings``: what ``ligand_bonds`` /
+    ``ligand_rings`` returned for the same atoms; ``aromatic``: what ``ligand_aromatic`` returned, or None: a bond's type is its order
+    ('basic' atom types).  Returns device tensors: ``fingerprint`` [n_graphs, 32] int32 (the bit patterns of uint32 words: bit b is bit
+    b & 31 of word b >> 5), ``mol_hash`` [n_graphs] int64 (the bit pattern of a uint64: ``mol_hash_int`` makes the Python int) and
+    ``graph_counts`` [n_graphs, 5] int32 (FINGERPRINT_GRAPH_COLUMNS).  A graph of more than MAX_FINGERPRINT_ATOMS atoms, without atoms,
+    with a malformed list, or that the ring or aromatic report did not evaluate is not an error: its status is non-zero
+    (FINGERPRINT_*), its fingerprint and hash are 0, n_bits and n_rounds -1.  Equal hashes mean equivalence under this refinement up to
+    64-bit collisions, not a proof of isomorphism (unsubstituted macrocycles above 9 atoms of equal atom counts are a known blind spot);
+    a fingerprint of this library's own in the manner of ECFP4: neither RDKit's Morgan fingerprint nor ``RDKFingerprint``, and nothing
+    claims agreement with them.  There is no CPU path."""
+    dev = z_lig.device
+    _gpu_only(dev, "ligand_fingerprints", "cbgx_ligand_fingerprints")
+    n_graphs = int(n_graphs)
+    bond_index, ring_min = bonds["bond_index"], rings["atom_ring_min"]
+    bond_type = bonds["bond_order"] if aromatic is None else aromatic["bond_type"]
+    for name, t in (("lig_batch", lig_batch), ("bond_index", bond_index), ("bond_type", bond_type), ("atom_ring_min", ring_min)):
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, z_lig on {dev}")
+    if bond_index.dim() != 2 or bond_index.shape[0] != 2:
+        raise ValueError("bond_index must be [2, n_bonds]")
+    n_lig, n_bonds = int(z_lig.shape[0]), int(bond_index.shape[1])
+    if z_lig.shape != (n_lig,) or lig_batch.shape != (n_lig,) or ring_min.shape != (n_lig,):
+        raise ValueError("one atomic number, one graph index and one atom_ring_min per atom")
+    if bond_type.shape != (n_bonds,):
+        raise ValueError("one bond type per bond")
+    lig_ptr = _csr(lig_batch, n_graphs, "lig_batch")
+    z_lig = _z_bytes(z_lig)
+    bond_index, bond_ptr = bond_index.to(torch.int32).contiguous(), _bond_ptr(bond_index, n_lig)
+    bond_type, ring_min = bond_type.to(torch.uint8).contiguous(), ring_min.to(torch.uint8).contiguous()
+    fp = torch.empty(n_graphs, FINGERPRINT_WORDS, dtype=torch.int32, device=dev)
+    mol_hash = torch.empty(n_graphs, dtype=torch.int64, device=dev)
+    graph_counts = torch.empty(n_graphs, len(FINGERPRINT_GRAPH_COLUMNS), dtype=torch.int32, device=dev)
+    p = _native.ptr
+    _native.check(_native.lib().cbgx_ligand_fingerprints(p(z_lig), p(lig_ptr), n_lig, n_graphs, p(bond_ptr),
+                                                         p(bond_index) if n_bonds else None, p(bond_type) if n_bonds else None,
+                                                         p(ring_min), n_bonds, p(fp), p(mol_hash), p(graph_counts),
+                                                         _native.current_stream(dev)), "cbgx_ligand_fingerprints")
+    return {"fingerprint": fp, "mol_hash": mol_hash, "graph_counts": graph_counts}
+
+
+def group_pair_ptr(group_ptr, n_graphs):
+    """[P + 1] list of ints: n (n - 1) / 2 pairs per group, n the size of the group's range as the kernel clamps it"""
+    ptr = [0]
+    for a, b in zip(group_ptr[:-1], group_ptr[1:]):
+        g0 = min(max(int(a), 0), n_graphs)
+        n = min(max(int(b), g0), n_graphs) - g0
+        ptr.append(ptr[-1] + n * (n - 1) // 2)
+    return ptr
+
+
+def group_diversity(fingerprints, group_ptr):
+    """What the graphs of every group share, one launch (``cbgx_group_diversity``, csrc/diversity.hip; one workgroup per group):
+    ``fingerprints``: what ``ligand_fingerprints`` returned; ``group_ptr`` [P + 1] ints, a CSR over graphs: group p is the consecutive
+    graphs group_ptr[p] ... group_ptr[p + 1] (the samples of a pocket).  Returns device tensors: ``pair_sim`` [sum n_p (n_p - 1) / 2]
+    int32, the Tanimoto similarity in millionths of every pair i < j of a group in (i, j) order (-1 where either graph was not
+    evaluated), with ``pair_ptr`` [P + 1] int64 and ``group_ptr`` [P + 1] int32 as handed to the kernel; per graph ``first_same`` (the
+    group-local index of the first evaluated graph of the group with the same hash), ``nearest`` (that of the most similar other
+    evaluated graph, the smallest on ties; -1: none) and ``nearest_micro`` [n_graphs] int32, all three -1 for a graph that was not
+    evaluated or is in no group; ``group_counts`` [P, 7] int64 (DIVERSITY_GROUP_COLUMNS).  A group of more than MAX_DIVERSITY_GROUP
+    graphs is not an error: status DIVERSITY_TOO_MANY_GRAPHS, -1 in its columns from n_evaluated to sim_micro_max, in its graphs and in
+    its pairs; entries of ``group_ptr`` outside [0, n_graphs] or decreasing are clamped and reported (DIVERSITY_BAD_GROUPS).  There is
+    no CPU path."""
+    fp, mol_hash, gc = fingerprints["fingerprint"], fingerprints["mol_hash"], fingerprints["graph_counts"]
+    dev = fp.device
+    _gpu_only(dev, "group_diversity", "cbgx_group_diversity")
+    n_graphs = int(fp.shape[0])
+    if fp.shape != (n_graphs, FINGERPRINT_WORDS) or mol_hash.shape != (n_graphs,) or gc.shape != (n_graphs, len(FINGERPRINT_GRAPH_COLUMNS)):
+        raise ValueError("one fingerprint row, one hash and one row of counts per graph")
+    ptr = [int(v) for v in (group_ptr.tolist() if isinstance(group_ptr, (torch.Tensor, np.ndarray)) else group_ptr)]
+    if not ptr or any(not -2 ** 31 <= v < 2 ** 31 for v in ptr):
+        raise ValueError("group_ptr must be [P + 1] 32-bit integers")
+    n_groups, pairs = len(ptr) - 1, group_pair_ptr(ptr, n_graphs)
+    group_ptr = torch.tensor(ptr, dtype=torch.int32, device=dev)
+    pair_ptr = torch.tensor(pairs, dtype=torch.int64, device=dev)
+    fp, mol_hash = fp.to(torch.int32).contiguous(), mol_hash.to(torch.int64).contiguous()
+    status = gc[:, -1].to(torch.int32).contiguous()
+    pair_sim = torch.full((pairs[-1],), -1, dtype=torch.int32, device=dev)
+    first_same, nearest, nearest_micro = (torch.full((n_graphs,), -1, dtype=torch.int32, device=dev) for _ in range(3))
+    group_counts = torch.empty(n_groups, len(DIVERSITY_GROUP_COLUMNS), dtype=torch.int64, device=dev)
+    p = _native.ptr
+    some = lambda t: p(t) if t.numel() else None
+    _native.check(_native.lib().cbgx_group_diversity(some(fp), some(mol_hash), some(status), p(group_ptr), p(pair_ptr), n_graphs, n_groups,
+                                                     pairs[-1], some(pair_sim), some(first_same), some(nearest), some(nearest_micro),
+                                                     some(group_counts), _native.current_stream(dev)), "cbgx_group_diversity")
+    return {"pair_sim": pair_sim, "pair_ptr": pair_ptr, "group_ptr": group_ptr, "first_same": first_same, "nearest": nearest,
+            "nearest_micro": nearest_micro, "group_counts": group_counts}
+
+
+def batch_diversity(batch, x, c, lig_batch, mode, group_ptr, bonds=None, rings=None, aromatic=None):
+    """``ligand_fingerprints`` and ``group_diversity`` of a sampling state whose graphs group_ptr[p] ... group_ptr[p + 1] are the samples
+    of pocket p, as one dict; ``bonds`` / ``rings`` / ``aromatic``: what ``batch_bonds`` / ``batch_rings`` / ``batch_aromatic`` returned
+    for the same state.  ``bonds`` and ``rings`` are computed here when None; so is ``aromatic`` when None and ``mode`` has aromatic atom
+    types ('add_aromatic'), the only mode in which it is used: in any other a bond's type is its order"""
+    if bonds is None:
+        bonds = batch_bonds(batch, x, c, lig_batch, mode)
+    if rings is None:
+        rings = batch_rings(batch, x, c, lig_batch, mode, bonds=bonds)
+    if mode not in _AROMATIC:
+        aromatic = None
+    elif aromatic is None:
+        aromatic = batch_aromatic(batch, x, c, lig_batch, mode, bonds=bonds, rings=rings)
+    dev = bonds["bond_index"].device
+    lig_batch = lig_batch.to(dev)
+    _, z, n_graphs = _state_atoms(c, mode, lig_batch, {"num_graphs": bonds["graph_counts"].shape[0]}, dev)
+    fingerprints = ligand_fingerprints(z, lig_batch, n_graphs, bonds, rings, aromatic)
+    return {**fingerprints, **group_diversity(fingerprints, group_ptr)}
+
+
+def mol_hash_int(value):
+    """a ``mol_hash`` element (an int64 bit pattern) as the Python int 0 ... 2**64 - 1 it stands for"""
+    return int(value) & (2 ** 64 - 1)
+
+
+def tanimoto_micro(fp_a, fp_b):
+    """host helper: the Tanimoto similarity in millionths of two fingerprints ([32] words, as ``fingerprint`` rows or any integers
+    holding their bit patterns), (popcount(a & b) 1000000 + popcount(a | b) // 2) // popcount(a | b) as the kernel computes it; 0 if
+    neither has a bit.  For samples of different pockets, or a reference ligand of the caller's own"""
+    a, b = ([int(v) & 0xFFFFFFFF for v in (w.tolist() if hasattr(w, "tolist") else w)] for w in (fp_a, fp_b))
+    if len(a) != FINGERPRINT_WORDS or len(b) != FINGERPRINT_WORDS:
+        raise ValueError(f"a fingerprint has {FINGERPRINT_WORDS} words")
+    inter, uni = sum(bin(x & y).count("1") for x, y in zip(a, b)), sum(bin(x | y).count("1") for x, y in zip(a, b))
+    return (inter * SIMILARITY_ONE + uni // 2) // uni if uni else 0
+
+
+def similarity_matrix(pair_sim, evaluated):
+    """a group's pairs (its range of ``pair_sim``, (i, j) order) and which of its n graphs were evaluated -> [n, n] int32: symmetric,
+    SIMILARITY_ONE on the diagonal of an evaluated graph, -1 in the rows and columns of the others"""
+    n = len(evaluated)
+    out = torch.full((n, n), -1, dtype=torch.int32)
+    upper = torch.triu_indices(n, n, offset=1)
+    out[upper[0], upper[1]] = torch.as_tensor(pair_sim, dtype=torch.int32)
+    out[upper[1], upper[0]] = out[upper[0], upper[1]]
+    for i, ok in enumerate(evaluated):
+        if ok:
+            out[i, i] = SIMILARITY_ONE
+    return out
+
+
+DIVERSITY_POCKET_KEYS = ("n_mol", "n_mol_evaluated", "n_unique", "n_pairs", "sim_micro_sum", "diversity_micro")
+DIVERSITY_COUNT_KEYS = ("n_pockets", "n_mol", "n_mol_evaluated", "n_mol_over_limit", "n_unique", "n_pairs", "sim_micro_sum",
+                        "n_pockets_with_pair", "diversity_micro_sum", "n_pockets_with_two", "n_collapsed_pockets")
+DIVERSITY_RATIOS = ("unique_mol_ratio", "duplicate_mol_ratio", "mean_pair_similarity", "mean_pocket_diversity", "collapsed_pocket_ratio")
+
+
+def diversity_counts(group_row):
+    """one row of ``group_counts`` -> the pocket's dict of integers (DIVERSITY_POCKET_KEYS): diversity_micro = 1000000 - (sim_micro_sum
+    + n_pairs // 2) // n_pairs, one minus the mean pair similarity in millionths, -1 without a pair; a group over the limit has no
+    evaluated molecule"""
+    row = dict(zip(DIVERSITY_GROUP_COLUMNS, (int(v) for v in group_row)))
+    if row["status"] & DIVERSITY_TOO_MANY_GRAPHS:
+        row.update(n_evaluated=0, n_unique=0, n_pairs=0, sim_micro_sum=0)
+    n_pairs, total = row["n_pairs"], row["sim_micro_sum"]
+    return {"n_mol": row["n_graphs"], "n_mol_evaluated": row["n_evaluated"], "n_unique": row["n_unique"], "n_pairs": n_pairs,
+            "sim_micro_sum": total, "diversity_micro": SIMILARITY_ONE - (total + n_pairs // 2) // n_pairs if n_pairs else -1}
+
+
+def diversity_totals(group_counts):
+    """per-pocket rows ``group_counts`` [P, 7] (DIVERSITY_GROUP_COLUMNS; any array-like) -> the integer totals, in DIVERSITY_COUNT_KEYS
+    order: what ranks add up.  n_pockets_with_pair and diversity_micro_sum run over the pockets with a pair of evaluated molecules,
+    n_pockets_with_two counts those with at least two evaluated molecules and n_collapsed_pockets those of them with one distinct hash"""
+    totals = [0] * len(DIVERSITY_COUNT_KEYS)
+    for row in _counts(group_counts, DIVERSITY_GROUP_COLUMNS):
+        c = diversity_counts(row)
+        two, pair = c["n_mol_evaluated"] >= 2, c["n_pairs"] > 0
+        add = [1, c["n_mol"], c["n_mol_evaluated"], c["n_mol"] - c["n_mol_evaluated"], c["n_unique"], c["n_pairs"], c["sim_micro_sum"],
+               int(pair), c["diversity_micro"] if pair else 0, int(two), int(two and c["n_unique"] == 1)]
+        totals = [a + b for a, b in zip(totals, add)]
+    return totals
+
+
+def summarise_diversity_totals(totals):
+    """the job's numbers from integer totals in DIVERSITY_COUNT_KEYS order; a ratio over nothing is nan.  unique_mol_ratio: distinct
+    hashes per pocket, summed, / evaluated molecules; duplicate_mol_ratio: the rest; mean_pair_similarity: over all pairs of the job;
+    mean_pocket_diversity: the mean over the pockets with a pair of 1 - the pocket's mean pair similarity, the per-pocket average papers
+    print; collapsed_pocket_ratio: pockets with one distinct hash among those with at least two evaluated molecules; and the totals as
+    ``counts``.  Uniqueness is per pocket: the same molecule in two pockets counts twice.  Hashes are equivalence under colour
+    refinement, not isomorphism; the fingerprint is this library's own, not RDKit's"""
+    c = {k: int(v) for k, v in zip(DIVERSITY_COUNT_KEYS, totals)}
+    return {"unique_mol_ratio": _ratio(c["n_unique"], c["n_mol_evaluated"]),
+            "duplicate_mol_ratio": _ratio(c["n_mol_evaluated"] - c["n_unique"], c["n_mol_evaluated"]),
+            "mean_pair_similarity": _ratio(c["sim_micro_sum"], SIMILARITY_ONE * c["n_pairs"]),
+            "mean_pocket_diversity": _ratio(c["diversity_micro_sum"], SIMILARITY_ONE * c["n_pockets_with_pair"]),
+            "collapsed_pocket_ratio": _ratio(c["n_collapsed_pockets"], c["n_pockets_with_two"]),
+            "n_mol_over_limit": c["n_mol_over_limit"], "counts": c}
+
+
+def summarise_diversity(group_counts):
+    """uniqueness and diversity of a set of pockets from their integer rows (``group_counts`` [P, 7], DIVERSITY_GROUP_COLUMNS): see
+    ``summarise_diversity_totals``"""
+    return summarise_diversity_totals(diversity_totals(group_counts))
 
 
 # the five reports that are integer counts per molecule, for a driver that treats them alike: per-molecule columns -> totals (what ranks

@@ -45,6 +45,10 @@ pair terms of Vina's functional form, computed on the device in two more launche
 bonds, each group's class out of the reference's 25 names by an exact isomorphism test, computed on the device in one more launch per batch
 (``geometry.batch_groups``), with the group names per sample and ``{out_dir}/groups_summary.json`` for the job; ``--groups_reference`` adds
 the MAE and the Jensen-Shannon distance to the caller's own ratios and distribution.  Marking rules of this library's own: not the EFGs program.
+``--diversity`` asks whether the samples of a pocket are different molecules: a fingerprint and a hash per sample by colour refinement of
+that graph, then per pocket the duplicates, every pair's Tanimoto similarity and each sample's nearest neighbour, computed on the device
+in two more launches per batch (``geometry.batch_diversity``), with ``{out_dir}/diversity_summary.json`` for the job.  A fingerprint of
+this library's own, not RDKit's; equal hashes are equivalence under the refinement, not isomorphism.
 ``--sdf`` writes ``pocket_{i:05d}.sdf`` beside every result file: one V2000 record per sample, bond types the Kekule orders of ``--valence``
 when given, else from ``--aromatic`` when given, table-bond orders otherwise (``geometry.sdf_record``; host side, no RDKit).
 A checkpoint is the reference's format: ``{'config': ..., 'model': state_dict}`` (``sample.py:153-156``)."""
@@ -153,7 +157,7 @@ def decode_mode(plan_mode, config_mode, num_classes):
 def main(argv=None, stats=None):
     """``stats`` (optional dict): filled with the wall seconds of the phases (setup = config + model + weights, batch = prior
     construction, sample = model.sample incl. the trajectory download, write = per-pocket records and files) and, for every requested report
-    (geometry, bonds, rings, aromatic, distributions, valence, interactions, groups: evaluated in that order), its own launches and downloads, a part of write: the bond
+    (geometry, bonds, rings, aromatic, distributions, valence, interactions, groups, diversity: evaluated in that order), its own launches and downloads, a part of write: the bond
     list and the ring report are made once per batch, and where they were not asked for their time goes to the first requested report
     in that order that needs them (cbgbench_amd/sample_reports.py)."""
     t_phase = time.perf_counter()
@@ -278,6 +282,22 @@ def main(argv=None, stats=None):
                          "this library's own: NOT the EFGs program, no agreement with it is claimed; no charges; a single-atom group is "
                          "'other'.  A sample over a limit is reported (groups_status != 0) and left out of every ratio.  Independent of "
                          "every other flag: what it needs is computed and not written")
+    ap.add_argument("--diversity", action="store_true",
+                    help="add what the samples of a pocket share: to every sample fingerprint [32] (int32 words of a 1024-bit "
+                         "fingerprint), mol_hash (a Python int below 2**64), duplicate_of (the index, among the pocket's samples, of the "
+                         "first one with the same hash: its own if it is the first), nearest_sample and nearest_similarity (the most "
+                         "similar other sample; -1 and nan if none) and diversity_status; to every pocket record similarity_micro [n, n] "
+                         "(Tanimoto similarities in millionths, -1 for a sample that was not evaluated) and a `diversity` dict of counts "
+                         "(n_unique, n_pairs, sim_micro_sum, diversity_micro = 1000000 - the rounded mean pair similarity); and "
+                         "{out_dir}/diversity_summary.json (unique_mol_ratio, mean_pocket_diversity = the per-pocket average of 1 - mean "
+                         "pairwise similarity, collapsed_pocket_ratio), evaluated on the GPU in two launches per batch on the bond list, "
+                         "the ring report and, with add_aromatic atom types, the aromatic report (cbgbench_amd/geometry.py).  Integer "
+                         "work only: colour refinement from (element, degree, aromatic, smallest ring) over the typed bonds.  Equal "
+                         "hashes mean equivalence under that refinement, up to 64-bit collisions: NOT a proof of isomorphism.  A "
+                         "fingerprint of this library's own in the manner of ECFP4 on TABLE bonds: neither RDKit's Morgan fingerprint nor "
+                         "RDKFingerprint, no agreement with them is claimed.  Uniqueness is per pocket.  A sample over a limit is reported "
+                         "(diversity_status != 0) and left out of every number.  Independent of every other flag: what it needs is "
+                         "computed and not written")
     ap.add_argument("--groups_reference", default=None,
                     help="with --groups: a .npz or torch.save'd dict {'ratio': ..., 'distribution': ...}, each the 25 values in the order "
                          "of the vocabulary (a torch.save'd dict may hold {name: value} dicts instead; none ship with this package); "
@@ -366,7 +386,7 @@ def main(argv=None, stats=None):
         # last step, not traj[-1]; kept as the default for drop-in outputs, --final_state selects traj[-1]
         x, c, bidx = traj[-1] if (args.final_state and config.model.type != "diffsbdd") else traj[0]
         n_graphs = len(ids) * num_samples
-        found = reports.evaluate(dev, (x, c, bidx), batch, n_graphs, mode)
+        found = reports.evaluate(dev, (x, c, bidx), batch, n_graphs, mode, group_ptr=[k * num_samples for k in range(len(ids) + 1)])
         x, c, bidx = x.cpu(), c.cpu(), bidx.cpu()
         if translate:       # back to the frame the pockets came in (sample.py:198-199; here per graph: a batch holds many pockets)
             x = x + batch["ligand_translation"].cpu()

@@ -1,4 +1,4 @@
-"""The reports of ``sample_cli`` (--geometry, --bonds, --rings, --aromatic, --distributions, --valence, --interactions, --groups, --sdf) in three stages: ``evaluate`` runs the
+"""The reports of ``sample_cli`` (--geometry, --bonds, --rings, --aromatic, --distributions, --valence, --interactions, --groups, --diversity, --sdf) in three stages: ``evaluate`` runs the
 requested reports of one batch on the GPU and returns plain dicts of CPU tensors; ``annotate`` / ``pocket_counts`` / ``pocket_files``
 turn those into the per-sample fields, the per-pocket dicts and the ``.sdf`` text on the host (CPU tensors in, no device); ``finish`` sums
 the job's integer totals over the ranks, writes ``*_summary.json`` and prints one line per report.
@@ -16,7 +16,12 @@ rounded to a whole number of millionths before the ranks add them up.
 
 The reports of LATE come after those of EXTRA, under the same rules again.  ``groups`` (the functional groups of the substructure block:
 marking rules of this library's own, not the EFGs program) takes what the valence report takes: the bond list, and the aromatic report
-where the atom types have aromatic flags."""
+where the atom types have aromatic flags.
+
+The reports of ACROSS come after those of LATE.  ``diversity`` (fingerprints and hashes of this library's own, not RDKit's; uniqueness and
+Tanimoto similarity per pocket) is the first report that reads more than one graph at a time: ``evaluate`` takes the pocket -> graphs
+grouping for it (``group_ptr``), and a pocket's record carries what its samples share.  It takes the bond list, the ring report and,
+where the atom types have aromatic flags, the aromatic report."""
 import json
 import os
 import time
@@ -30,14 +35,17 @@ from .config import _AROMATIC
 ORDER = ("geometry", "bonds", "rings", "aromatic", "distributions", "valence")
 EXTRA = ("interactions",)        # evaluated, annotated and finished after ORDER
 LATE = ("groups",)               # ... and these after EXTRA
+ACROSS = ("diversity",)          # ... and these, which compare the samples of a pocket, after LATE
 NEEDS = {"rings": ("bonds",), "aromatic": ("bonds", "rings"), "distributions": ("bonds",), "valence": ("bonds", "aromatic"),
-         "interactions": ("bonds", "valence"), "groups": ("bonds", "aromatic")}
+         "interactions": ("bonds", "valence"), "groups": ("bonds", "aromatic"), "diversity": ("bonds", "rings", "aromatic")}
 
 
 def needs(name, mode):
     """what report ``name`` is computed from under the atom-type vocabulary ``mode``"""
     if name in ("valence", "groups") and mode not in _AROMATIC:
         return ("bonds",)
+    if name == "diversity" and mode not in _AROMATIC:
+        return ("bonds", "rings")
     return NEEDS.get(name, ())
 
 
@@ -51,6 +59,7 @@ _GPU_ONLY = {"geometry": "--geometry runs on the GPU (cbgx_ligand_geometry has n
              "valence": "--valence runs on the GPU (cbgx_ligand_valence has no CPU fallback)",
              "interactions": "--interactions runs on the GPU (cbgx_pocket_types / cbgx_ligand_interactions have no CPU fallback)",
              "groups": "--groups runs on the GPU (cbgx_ligand_groups has no CPU fallback)",
+             "diversity": "--diversity runs on the GPU (cbgx_ligand_fingerprints / cbgx_group_diversity have no CPU fallback)",
              "sdf": "--sdf takes its bonds from the GPU (cbgx_ligand_bonds_count / _fill have no CPU fallback)"}
 # a count report's printed line: the ratios it names, and its own tail
 _LINE = {"geometry": (geometry.RATIOS, lambda c: f"{c['n_mol']} molecules, {c['n_atoms']} atoms"),
@@ -95,7 +104,7 @@ def ranges(counts):
 
 
 class SampleReports:
-    """``requested``: names out of ORDER, EXTRA, LATE and 'sdf'; ``reference``: the path of --distributions_reference;
+    """``requested``: names out of ORDER, EXTRA, LATE, ACROSS and 'sdf'; ``reference``: the path of --distributions_reference;
     ``groups_reference``: that of --groups_reference"""
 
     def __init__(self, requested, reference=None, groups_reference=None):
@@ -103,22 +112,23 @@ class SampleReports:
         self.reference = reference
         self.groups_reference = groups_reference
         self.n_orders = 4 if "aromatic" in self.requested else 3        # --aromatic --distributions: types with the aromatic type
-        self.seconds = {name: 0.0 for name in ORDER + EXTRA + LATE if name in self.requested}  # wall time of every report (``stats``)
+        self.seconds = {name: 0.0 for name in ORDER + EXTRA + LATE + ACROSS if name in self.requested}  # wall time of every report (``stats``)
         self.counts = {name: [] for name in _COUNT_REPORTS if name in self.requested}  # per-sample counts of this rank
         # the pockets' flat integer totals are added up as they come (one is 3.5 MB)
         self.distribution_totals = np.zeros(geometry.distribution_totals_length(n_orders=self.n_orders), np.int64)
         self.sdf_left_out, self.sdf_written = 0, 0
         self.interactions = []                                          # (graph_counts, graph_terms) of this rank's pockets
         self.groups = []                                                # graph_counts of this rank's pockets
+        self.diversity = []                                             # group_counts rows of this rank's pockets
 
     @classmethod
     def from_args(cls, args):
-        return cls([name for name in ORDER + EXTRA + LATE + ("sdf",) if getattr(args, name, False)], args.distributions_reference,
+        return cls([name for name in ORDER + EXTRA + LATE + ACROSS + ("sdf",) if getattr(args, name, False)], args.distributions_reference,
                    getattr(args, "groups_reference", None))
 
     def refuse(self, dev, atom_mode):
         """what cannot run is refused before any model is built; ``atom_mode()``: the vocabulary the samples are decoded with"""
-        for name in ("geometry", "bonds", "rings", "distributions", "aromatic", "valence") + EXTRA + LATE + ("sdf",):
+        for name in ("geometry", "bonds", "rings", "distributions", "aromatic", "valence") + EXTRA + LATE + ACROSS + ("sdf",):
             if name not in self.requested:
                 continue
             if name == "aromatic" and atom_mode() != "add_aromatic":
@@ -133,12 +143,15 @@ class SampleReports:
             raise SystemExit("sample_cli: --groups_reference needs --groups")
 
     # ---- GPU -----------------------------------------------------------------------------------------------------------------------------
-    def evaluate(self, dev, state, batch, n_graphs, mode):
+    def evaluate(self, dev, state, batch, n_graphs, mode, group_ptr=None):
         """the requested reports of the state ``(x, c, bidx)`` the records hold, in the sampling frame (before ligand_translation), against
         the batch's own pocket -> {report: {name: CPU tensor}}; with --sdf or --aromatic and no --bonds also the ``bonds`` the host side
-        slices by (not written)"""
+        slices by (not written).  ``group_ptr`` [P + 1]: the graphs group_ptr[p] ... group_ptr[p + 1] are the samples of the batch's pocket
+        p; only the reports of ACROSS read it, and they need it"""
         if not self.requested:
             return {}
+        if group_ptr is None and self.requested & set(ACROSS):
+            raise ValueError("the diversity report compares the samples of a pocket: evaluate needs group_ptr")
         x, c, bidx = (t.to(dev) for t in state)
         info, made, out = {"num_graphs": n_graphs}, {}, {}
 
@@ -152,6 +165,8 @@ class SampleReports:
                     pocket = {k: batch[k].to(dev) for k in ("protein_pos", "protein_element", "protein_element_batch", "protein_aa_type",
                                                             "protein_atom_feature")}
                     made[name] = geometry.batch_interactions({**pocket, **info}, x, c, bidx, mode, **deps)
+                elif name == "diversity":
+                    made[name] = geometry.batch_diversity(info, x, c, bidx, mode, group_ptr, **deps)
                 elif name == "distributions":
                     made[name] = geometry.batch_distributions(info, x, c, bidx, mode, aromatic=made.get("aromatic"), **deps)
                 else:
@@ -248,6 +263,17 @@ class SampleReports:
                 smp["n_groups"] = int(gc[g, 2])
                 smp["fg_counts"] = gc[g, 6:6 + geometry.GROUP_CLASSES + 1].clone()
                 smp["groups_status"] = int(gc[g, -1])
+        if "diversity" in self.requested:
+            div = ev["diversity"]
+            for g0, g1 in zip(div["group_ptr"][:-1].tolist(), div["group_ptr"][1:].tolist()):
+                for g in range(g0, g1):             # the cross-sample fields are indices among the pocket's own samples
+                    smp, micro = samples[g], int(div["nearest_micro"][g])
+                    smp["fingerprint"] = div["fingerprint"][g].clone()
+                    smp["mol_hash"] = geometry.mol_hash_int(div["mol_hash"][g])
+                    smp["duplicate_of"] = int(div["first_same"][g])
+                    smp["nearest_sample"] = int(div["nearest"][g])
+                    smp["nearest_similarity"] = micro / geometry.SIMILARITY_ONE if micro >= 0 else float("nan")
+                    smp["diversity_status"] = int(div["graph_counts"][g, -1])
 
     def pocket_counts(self, ev, g0, g1):
         """the dicts of counts a pocket record carries for its graphs g0 ... g1 - 1, which join the job's totals"""
@@ -269,6 +295,18 @@ class SampleReports:
             gc = ev["groups"]["graph_counts"][g0:g1].to(torch.int64)
             self.groups.append(gc)
             rec["groups"] = geometry.summarise_groups(gc)["counts"]
+        if "diversity" in self.requested:
+            div = ev["diversity"]
+            ptr = div["group_ptr"].tolist()
+            found = [p for p in range(len(ptr) - 1) if (ptr[p], ptr[p + 1]) == (g0, g1)]
+            if not found:
+                raise ValueError(f"the graphs {g0} ... {g1} are no group of the group_ptr the diversity report was evaluated with")
+            p = found[0]
+            row = div["group_counts"][p]
+            self.diversity.append(row.clone())
+            q0, q1 = int(div["pair_ptr"][p]), int(div["pair_ptr"][p + 1])
+            rec["similarity_micro"] = geometry.similarity_matrix(div["pair_sim"][q0:q1], (div["graph_counts"][g0:g1, -1] == 0).tolist())
+            rec["diversity"] = geometry.diversity_counts(row)
         return rec
 
     def pocket_files(self, stem, samples, ev, g0):
@@ -338,6 +376,16 @@ class SampleReports:
                       + "; most frequent: " + ", ".join(f"{geometry.GROUP_NAMES[k]} {cnt[f'n_fg_{k}']}" for k in top)
                       + f" ({cnt['n_mol_evaluated']} of {cnt['n_mol']} molecules evaluated, n_mol_over_limit {cnt['n_mol_over_limit']}; "
                         f"marking rules of this library's own, not the EFGs program)")
+        if "diversity" in self.requested:
+            totals = geometry.diversity_totals(torch.stack(self.diversity) if self.diversity else np.zeros((0, 7), np.int64))
+            summary = geometry.summarise_diversity_totals(sharding.sum_counts(totals, device=dev))
+            if rank == 0:
+                save("diversity", summary)
+                cnt = summary["counts"]
+                print("diversity: " + ", ".join(f"{k} {summary[k]:.4f}" for k in geometry.DIVERSITY_RATIOS)
+                      + f" ({cnt['n_mol_evaluated']} of {cnt['n_mol']} molecules evaluated in {cnt['n_pockets']} pockets, n_mol_over_limit "
+                        f"{cnt['n_mol_over_limit']}; uniqueness per pocket by a hash of colour refinement, not an isomorphism test; a "
+                        f"fingerprint of this library's own, not RDKit's)")
         if "sdf" in self.requested:
             left_out, written = sharding.sum_counts([self.sdf_left_out, self.sdf_written], device=dev)
             if rank == 0:

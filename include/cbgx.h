@@ -1093,6 +1093,85 @@ int cbgx_ligand_groups(const uint8_t *z_lig, const int32_t *lig_ptr, int n_lig, 
                        int32_t *atom_group, uint8_t *atom_class, int32_t *graph_out, void *stream);
 int cbgx_ligand_groups_templates(uint8_t *n_atoms, uint8_t *n_bonds, uint8_t *labels, uint8_t *bonds);
 
+/* ---- fingerprints of sampled ligands, and uniqueness and Tanimoto similarity across the samples of a pocket (diversity.hip) ---------------
+ * Does a pocket's set of samples hold different molecules?  The reference's raw material is RDKit after reconstruction: `tanimoto_sim` /
+ *   `tanimoto_sim_N_to_1` on `Chem.RDKFingerprint` (repo/tools/similarity.py) and the SMILES strings of evaluate_chem_single.py.  Here:
+ *   a fingerprint and a hash of this library's own, by colour refinement of the table-bond graph in the manner of ECFP4, and a second
+ *   kernel that compares the graphs of a group.  Integer work only, on unsigned 64-bit integers with wrap-around; every number is a
+ *   function of the graph's own atoms and bonds and of no order among them.  Deviations: TABLE bonds and this library's aromatic bonds;
+ *   the fingerprint is NEITHER RDKit's Morgan fingerprint NOR `RDKFingerprint`: nothing may claim agreement with them.
+ * cbgx_ligand_fingerprints -- one launch, one wave per graph.
+ *   Inputs: z_lig, lig_ptr, bond_ptr, bond_index as cbgx_ligand_groups takes them; bond_type [n_bonds] uint8: 1..3 the order, 4 aromatic,
+ *   255 = the aromatic report did not evaluate the graph (with atom types without aromatic flags: the order); atom_ring_min [n_lig] uint8
+ *   as cbgx_ligand_rings writes it: 0 = no ring of length <= 9 through the atom, 255 = not evaluated.
+ *   G = 0x9E3779B97F4A7C15.  mix(x), the splitmix64 finaliser: x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27;
+ *   x *= 0x94D049BB133111EB; x ^= x >> 31.  For atom a with atomic number z: deg = the number of bonds of the graph it appears in,
+ *   arom = 1 iff one of them has type 4, ring = its atom_ring_min;
+ *     id_0(a) = mix(G + z + 256 deg + 65536 arom + 131072 ring)
+ *     id_(r+1)(a) = mix(id_r(a) + sum over the bonds a - b of type t of mix(id_r(b) ^ (t G)))
+ *   for r = 0 ... R - 1 with R = max(n_atoms, 2): a property of the graph (a refinement is stable after n_atoms rounds at the latest), not
+ *   a budget.  The sum is commutative: no order of atoms or bonds enters.
+ *   fp [B, CBGX_FINGERPRINT_WORDS] uint32, CBGX_FINGERPRINT_BITS bits: bit id_r(a) & 1023 is set for every atom and r = 0, 1, 2 (the
+ *   atom, its neighbours, theirs: the radius of ECFP4); bit b is bit b & 31 of word b >> 5.
+ *   mol_hash [B] uint64 = mix(sum over the atoms of mix(id_R(a) ^ G) + n_atoms + (n_bonds << 32)).
+ *   What the hash means: equal hashes say that the two graphs are equivalent under this colour refinement (1-dimensional
+ *   Weisfeiler-Leman on the labels above), up to collisions of 64-bit values.  That is NOT a proof of isomorphism.  The ring term is an
+ *   input because without it cyclohexane and two cyclopropanes are equivalent, and so are decalin and bicyclopentyl; a known blind spot
+ *   that remains: unsubstituted macrocycles of more than CBGX_RINGS_MAX_SIZE atoms with equal atom counts (one C20 ring against two C10
+ *   rings) get equal hashes.
+ *   graph_out [B, CBGX_FINGERPRINT_GRAPH_COLS] int32: n_atoms, n_bonds (the clamped sizes of the two ranges), n_bits (bits set in the
+ *   graph's row of fp), n_rounds (R), status.  Every element of fp, mol_hash and graph_out is written for every graph.
+ *   Status, per graph, never an error, set side by side: CBGX_FINGERPRINT_TOO_MANY_ATOMS (more than CBGX_FINGERPRINT_MAX_ATOMS atoms),
+ *   CBGX_FINGERPRINT_BAD_BONDS (the conditions of CBGX_RINGS_BAD_BONDS, or a bond_type outside 1..4 that is not 255),
+ *   CBGX_FINGERPRINT_NO_TYPES (a 255 among the graph's bytes of bond_type or atom_ring_min), CBGX_FINGERPRINT_EMPTY (no atom).  With
+ *   status != 0 the graph's row of fp is all zero, its mol_hash 0, n_bits and n_rounds -1.  There is no limit on the bonds.  Every entry of
+ *   lig_ptr, bond_ptr and bond_index is clamped or checked before it is used as an index.  No atomics on memory; nothing in the outputs
+ *   depends on scheduling.
+ *   Returns 0, and 0 without a launch when B == 0.  CBGX_E_INVALID before any dereference or launch: negative counts, a NULL pointer with
+ *   a non-zero count (bond_index and bond_type may be NULL when n_bonds == 0), and any array with a non-zero count whose pointer is not
+ *   memory the device can read (asked for in argument order, the first such array is named in cbgx_last_error).
+ * cbgx_group_diversity -- one launch, one workgroup per group.
+ *   Inputs: fp (16-byte aligned) and mol_hash as above; status [B] int32, the status column; group_ptr [P + 1] int32, a CSR over graphs:
+ *   group p holds the consecutive graphs group_ptr[p] ... group_ptr[p + 1] (entries clamped to [0, B], an end below its start to the
+ *   start: reported as CBGX_DIVERSITY_BAD_GROUPS, the clamped range is evaluated); pair_ptr [P + 1] int64 with pair_ptr[p + 1] -
+ *   pair_ptr[p] = n_p (n_p - 1) / 2, n_p the (clamped) size of group p, computed by the caller; n_pairs, the length of pair_sim.  A group
+ *   whose range of pair_ptr is not that long or does not lie inside [0, n_pairs] carries CBGX_DIVERSITY_BAD_GROUPS too, and nothing of
+ *   pair_sim is written for it.  A graph is evaluated iff its status is 0.
+ *   For two evaluated graphs i < j of a group (group-local indices): inter = popcount(fp_i & fp_j), uni = popcount(fp_i | fp_j),
+ *   sim_micro = (inter 1000000 + uni / 2) / uni in integer division: the Tanimoto similarity in millionths, rounded half up.  uni >= 1
+ *   for rows cbgx_ligand_fingerprints wrote (an evaluated graph has an atom); two all-zero rows of a caller's own have sim_micro 0.
+ *   pair_sim [n_pairs] int32: the group's pairs in (i, j) order from pair_ptr[p] on, -1 where either graph is not evaluated.
+ *   Per graph (int32 [B] each; -1 in all three for a graph that is not evaluated; a graph in no group is not written): first_same, the
+ *   group-local index of the first evaluated graph of the group with the same mol_hash (its own index if none is earlier); nearest, the
+ *   group-local index of the evaluated graph j != i of largest sim_micro, the smallest index on ties, -1 if there is none;
+ *   nearest_micro, that similarity (-1 if there is none).
+ *   group_out [P, CBGX_DIVERSITY_GROUP_COLS] int64: n_graphs, n_evaluated, n_unique (graphs that are their own first_same), n_pairs (pairs
+ *   of evaluated graphs), sim_micro_sum, sim_micro_max (-1 without a pair), status.  A group of more than CBGX_DIVERSITY_MAX_GROUP graphs
+ *   carries CBGX_DIVERSITY_TOO_MANY_GRAPHS: its columns n_evaluated ... sim_micro_max are -1, and so are its per-graph outputs and pairs.
+ *   Every number is a sum, a minimum or a maximum of integers: nothing depends on scheduling.  No atomics on memory.  Overlapping groups
+ *   have two workgroups write the same per-graph elements, in no order: those elements are undefined.
+ *   Returns 0, and 0 without a launch when P == 0.  CBGX_E_INVALID before any dereference or launch: negative counts, a NULL pointer with
+ *   a non-zero count (the per-graph arrays with B, group_ptr, pair_ptr and group_out with P, pair_sim with n_pairs), an fp that is not
+ *   16-byte aligned, and any array with a non-zero count whose pointer is not memory the device can read, named as above. */
+#define CBGX_FINGERPRINT_MAX_ATOMS 256
+#define CBGX_FINGERPRINT_BITS 1024
+#define CBGX_FINGERPRINT_WORDS 32
+#define CBGX_FINGERPRINT_GRAPH_COLS 5   /* n_atoms, n_bonds, n_bits, n_rounds, status */
+#define CBGX_FINGERPRINT_TOO_MANY_ATOMS 1
+#define CBGX_FINGERPRINT_BAD_BONDS 4
+#define CBGX_FINGERPRINT_NO_TYPES 8
+#define CBGX_FINGERPRINT_EMPTY 16
+#define CBGX_DIVERSITY_MAX_GROUP 1024
+#define CBGX_DIVERSITY_GROUP_COLS 7   /* n_graphs, n_evaluated, n_unique, n_pairs, sim_micro_sum, sim_micro_max, status */
+#define CBGX_DIVERSITY_TOO_MANY_GRAPHS 1
+#define CBGX_DIVERSITY_BAD_GROUPS 4
+int cbgx_ligand_fingerprints(const uint8_t *z_lig, const int32_t *lig_ptr, int n_lig, int n_graphs, const int32_t *bond_ptr,
+                             const int32_t *bond_index, const uint8_t *bond_type, const uint8_t *atom_ring_min, int n_bonds, uint32_t *fp,
+                             uint64_t *mol_hash, int32_t *graph_out, void *stream);
+int cbgx_group_diversity(const uint32_t *fp, const uint64_t *mol_hash, const int32_t *status, const int32_t *group_ptr,
+                         const int64_t *pair_ptr, int n_graphs, int n_groups, long long n_pairs, int32_t *pair_sim, int32_t *first_same,
+                         int32_t *nearest, int32_t *nearest_micro, int64_t *group_out, void *stream);
+
 /* ---- distributions of sampled ligands: pair distances, bond lengths, bond angles (distributions.hip) -----------------------------------
  * The rest of the reference's geometry report (evaluate_scripts/evaluate_geom_single.py; repo/tools/geometry/eval_bond_length.py,
  *   eval_bond_angle.py): histograms that are compared with a dataset's by Jensen-Shannon distance.  Distances and element codes are those
