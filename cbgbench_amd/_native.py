@@ -113,6 +113,8 @@ EXPORTS = {
     "cbgx_ligand_groups_templates": (_i, [_vp] * 4),
     "cbgx_ligand_fingerprints": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "cbgx_group_diversity": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cbgx_pocket_contacts": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "cbgx_native_compare": (_i, [_vp] * 7 + [_i, _i] + [_vp] * 7 + [_i, _i] + [_vp] * 5),
     "cbgx_ligand_pair_hist": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "cbgx_ligand_angles": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "cbgx_profile_begin": (_i, [_i]),

@@ -1,7 +1,7 @@
 // libcbgx -- C ABI of the geometry report, of the bond list, of the ring sizes, of the aromatic report, of the valence report, of the
-// interaction report, of the functional groups, of the fingerprints and of the distributions (include/cbgx.h, geometry.hip, rings.hip,
-// aromatic.hip, valence.hip, interactions.hip, groups.hip, diversity.hip, distributions.hip): argument checks, the ligand-size check, the
-// launch
+// interaction report, of the functional groups, of the fingerprints, of the comparison with a native ligand and of the distributions
+// (include/cbgx.h, geometry.hip, rings.hip, aromatic.hip, valence.hip, interactions.hip, groups.hip, diversity.hip, native.hip,
+// distributions.hip): argument checks, the ligand-size check, the launch
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -293,6 +293,63 @@ int cbgx_group_diversity(const uint32_t* fp, const uint64_t* mol_hash, const int
     const hipError_t e = launch_group_diversity(fp, mol_hash, status, group_ptr, pair_ptr, n_graphs, n_groups, n_pairs, pair_sim, first_same,
                                                 nearest, nearest_micro, group_out, (hipStream_t)stream);
     if (e != hipSuccess) return set_error(CBGX_E_HIP, "group_diversity: launch: %s", hipGetErrorString(e));
+    return CBGX_OK;
+}
+
+int cbgx_pocket_contacts(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, const float* x_rec,
+                         const uint8_t* z_rec, const int32_t* rec_ptr, int n_rec, int n_graphs, double cutoff2, uint8_t* rec_contact,
+                         uint8_t* lig_contact, double* centroid, int32_t* graph_out, void* stream) {
+    if (n_graphs < 0 || n_lig < 0 || n_rec < 0)
+        return set_error(CBGX_E_INVALID, "pocket_contacts: negative count (B=%d n_lig=%d n_rec=%d)", n_graphs, n_lig, n_rec);
+    if ((n_graphs > 0 && (!lig_ptr || !rec_ptr || !centroid || !graph_out)) || (n_lig > 0 && (!x_lig || !z_lig || !lig_contact)) ||
+        (n_rec > 0 && (!x_rec || !z_rec || !rec_contact)))
+        return set_error(CBGX_E_INVALID, "pocket_contacts: NULL pointer");
+    if (n_graphs == 0) return CBGX_OK;
+    const DeviceArray arrays[] = {
+        {"x_lig", x_lig, n_lig}, {"z_lig", z_lig, n_lig}, {"lig_ptr", lig_ptr, n_graphs + 1}, {"x_rec", x_rec, n_rec},
+        {"z_rec", z_rec, n_rec}, {"rec_ptr", rec_ptr, n_graphs + 1}, {"rec_contact", rec_contact, n_rec},
+        {"lig_contact", lig_contact, n_lig}, {"centroid", centroid, n_graphs}, {"graph_out", graph_out, n_graphs}};
+    int rc = device_visible("pocket_contacts", arrays, (int)(sizeof(arrays) / sizeof(arrays[0])));
+    if (rc != CBGX_OK) return rc;
+    rc = check_ligand_sizes("pocket_contacts", lig_ptr, n_lig, n_graphs, (hipStream_t)stream);
+    if (rc != CBGX_OK) return rc;
+    const hipError_t e = launch_pocket_contacts(x_lig, z_lig, lig_ptr, n_lig, x_rec, z_rec, rec_ptr, n_rec, n_graphs, cutoff2, rec_contact,
+                                                lig_contact, centroid, graph_out, (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(CBGX_E_HIP, "pocket_contacts: launch: %s", hipGetErrorString(e));
+    return CBGX_OK;
+}
+
+int cbgx_native_compare(const uint32_t* fp, const uint64_t* mol_hash, const int32_t* fp_status, const uint8_t* rec_contact,
+                        const int32_t* rec_ptr, const double* centroid, const int32_t* contacts_status, int n_graphs, int n_rec,
+                        const uint32_t* fp_nat, const uint64_t* mol_hash_nat, const int32_t* fp_status_nat, const uint8_t* rec_contact_nat,
+                        const int32_t* rec_ptr_nat, const double* centroid_nat, const int32_t* contacts_status_nat, int n_groups,
+                        int n_rec_nat, const int32_t* group_ptr, int64_t* sample_out, double* centroid_d2, int64_t* group_out,
+                        void* stream) {
+    if (n_graphs < 0 || n_rec < 0 || n_groups < 0 || n_rec_nat < 0)
+        return set_error(CBGX_E_INVALID, "native_compare: negative count (B=%d n_rec=%d P=%d n_rec_nat=%d)", n_graphs, n_rec, n_groups,
+                         n_rec_nat);
+    if ((n_graphs > 0 && (!fp || !mol_hash || !fp_status || !centroid || !contacts_status || !sample_out || !centroid_d2)) ||
+        (n_rec > 0 && !rec_contact) ||
+        (n_groups > 0 && (!rec_ptr || !fp_nat || !mol_hash_nat || !fp_status_nat || !rec_ptr_nat || !centroid_nat || !contacts_status_nat ||
+                          !group_ptr || !group_out)) ||
+        (n_rec_nat > 0 && !rec_contact_nat))
+        return set_error(CBGX_E_INVALID, "native_compare: NULL pointer");
+    if (n_groups == 0) return CBGX_OK;
+    if ((uintptr_t)fp % 16 != 0 || (uintptr_t)fp_nat % 16 != 0)
+        return set_error(CBGX_E_INVALID, "native_compare: %s is not aligned to 16 bytes", (uintptr_t)fp % 16 != 0 ? "fp" : "fp_nat");
+    const DeviceArray arrays[] = {
+        {"fp", fp, n_graphs}, {"mol_hash", mol_hash, n_graphs}, {"fp_status", fp_status, n_graphs}, {"rec_contact", rec_contact, n_rec},
+        {"rec_ptr", rec_ptr, n_graphs + 1}, {"centroid", centroid, n_graphs}, {"contacts_status", contacts_status, n_graphs},
+        {"fp_nat", fp_nat, n_groups}, {"mol_hash_nat", mol_hash_nat, n_groups}, {"fp_status_nat", fp_status_nat, n_groups},
+        {"rec_contact_nat", rec_contact_nat, n_rec_nat}, {"rec_ptr_nat", rec_ptr_nat, n_groups + 1}, {"centroid_nat", centroid_nat, n_groups},
+        {"contacts_status_nat", contacts_status_nat, n_groups}, {"group_ptr", group_ptr, n_groups + 1},
+        {"sample_out", sample_out, n_graphs}, {"centroid_d2", centroid_d2, n_graphs}, {"group_out", group_out, n_groups}};
+    const int rc = device_visible("native_compare", arrays, (int)(sizeof(arrays) / sizeof(arrays[0])));
+    if (rc != CBGX_OK) return rc;
+    const hipError_t e = launch_native_compare(fp, mol_hash, fp_status, rec_contact, rec_ptr, centroid, contacts_status, n_graphs, n_rec, fp_nat,
+                                               mol_hash_nat, fp_status_nat, rec_contact_nat, rec_ptr_nat, centroid_nat, contacts_status_nat,
+                                               n_groups, n_rec_nat, group_ptr, sample_out, centroid_d2, group_out, (hipStream_t)stream);
+    if (e != hipSuccess) return set_error(CBGX_E_HIP, "native_compare: launch: %s", hipGetErrorString(e));
     return CBGX_OK;
 }
 

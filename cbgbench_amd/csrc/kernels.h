@@ -315,6 +315,18 @@ hipError_t launch_ligand_fingerprints(const uint8_t* z_lig, const int32_t* lig_p
 hipError_t launch_group_diversity(const uint32_t* fp, const uint64_t* mol_hash, const int32_t* status, const int32_t* group_ptr,
                                   const int64_t* pair_ptr, int n_graphs, int n_groups, long long n_pairs, int32_t* pair_sim,
                                   int32_t* first_same, int32_t* nearest, int32_t* nearest_micro, int64_t* group_out, hipStream_t s);
+// native.hip: the heavy pocket atoms within a cutoff of a ligand's heavy atoms, the ligand's side of the same, and the centroid of its heavy
+// atoms (one workgroup per graph); and, one workgroup per pocket, every sample against the pocket's native ligand: fingerprint
+// similarity, equal hash, the overlap of the two contact sets, the squared distance of the two centroids
+hipError_t launch_pocket_contacts(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, const float* x_rec,
+                                  const uint8_t* z_rec, const int32_t* rec_ptr, int n_rec, int n_graphs, double cutoff2,
+                                  uint8_t* rec_contact, uint8_t* lig_contact, double* centroid, int32_t* graph_out, hipStream_t s);
+hipError_t launch_native_compare(const uint32_t* fp, const uint64_t* mol_hash, const int32_t* fp_status, const uint8_t* rec_contact,
+                                 const int32_t* rec_ptr, const double* centroid, const int32_t* contacts_status, int n_graphs, int n_rec,
+                                 const uint32_t* fp_nat, const uint64_t* mol_hash_nat, const int32_t* fp_status_nat,
+                                 const uint8_t* rec_contact_nat, const int32_t* rec_ptr_nat, const double* centroid_nat,
+                                 const int32_t* contacts_status_nat, int n_groups, int n_rec_nat, const int32_t* group_ptr,
+                                 int64_t* sample_out, double* centroid_d2, int64_t* group_out, hipStream_t s);
 // distributions.hip: pair-distance histograms of the same ligands (two families, LDS integer histograms), and the bond angles of the
 // table-bond graph from its symmetric adjacency -- cosine, bin against a cosine table, canonical type; one workgroup per graph each
 hipError_t launch_ligand_pair_hist(const float* x_lig, const uint8_t* z_lig, const int32_t* lig_ptr, int n_lig, int n_graphs,

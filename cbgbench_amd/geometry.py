@@ -1252,6 +1252,269 @@ def summarise_diversity(group_counts):
     return summarise_diversity_totals(diversity_totals(group_counts))
 
 
+# ---- samples against the ligand a pocket was crystallised with -------------------------------------------------------------------------------
+CONTACTS_CUTOFF2 = 16.0                    # include/cbgx.h CBGX_CONTACTS_CUTOFF2: (4 A)^2
+# columns of pocket_contacts' graph_counts (CBGX_CONTACTS_GRAPH_COLS), of native_compare's sample_counts and group_counts
+CONTACTS_GRAPH_COLUMNS = ("n_atoms", "n_heavy", "n_rec", "n_rec_contact", "n_lig_contact", "status")
+NATIVE_SAMPLE_COLUMNS = ("sim_micro", "same_hash", "contact_common", "contact_union", "contact_micro", "status")
+NATIVE_GROUP_COLUMNS = ("n_graphs", "n_fp_compared", "n_same_hash", "sim_micro_sum", "sim_micro_max", "n_contact_compared",
+                        "contact_micro_sum", "contact_micro_max", "status")
+CONTACTS_EMPTY = 16
+NATIVE_SAMPLE_NOT_EVALUATED, NATIVE_NATIVE_NOT_EVALUATED, NATIVE_POCKET_MISMATCH, NATIVE_BAD_GROUPS = 1, 2, 4, 8
+
+
+def pocket_contacts(x_lig, z_lig, lig_batch, x_rec, z_rec, rec_batch, n_graphs, cutoff2=CONTACTS_CUTOFF2):
+    """Which heavy pocket atoms the heavy atoms of ``n_graphs`` ligands touch, one launch (``cbgx_pocket_contacts``, csrc/native.hip; the
+    definition is in include/cbgx.h) on the tensors' current stream.  Both sides as ``ligand_geometry`` takes them.  A heavy ligand atom
+    and a heavy pocket atom (atomic number not 1) are in contact iff d2 <= ``cutoff2`` with the float64 squared distance of
+    ``ligand_geometry``.  Returns device tensors: ``rec_contact`` [n_rec] / ``lig_contact`` [n_lig] uint8, ``centroid`` [n_graphs, 3]
+    float64 (the heavy atoms' coordinates summed in atom order, divided by their number; nan without one), ``graph_counts`` [n_graphs, 6]
+    int32 (CONTACTS_GRAPH_COLUMNS; status CONTACTS_EMPTY without a heavy atom, never an error) and ``rec_ptr`` [n_graphs + 1] int32.  A
+    ligand of more than MAX_LIGAND_ATOMS atoms raises ValueError.  A descriptor of this library's own.  There is no CPU path."""
+    dev = x_lig.device
+    _gpu_only(dev, "pocket_contacts", "cbgx_pocket_contacts")
+    n_graphs = int(n_graphs)
+    n_lig, lig_ptr, x_lig, z_lig = _ligand_arrays(x_lig, z_lig, lig_batch, n_graphs)
+    n_rec, rec_ptr, x_rec, z_rec = _ligand_arrays(x_rec, z_rec, rec_batch, n_graphs, "rec", dev)
+    rec_contact = torch.empty(n_rec, dtype=torch.uint8, device=dev)
+    lig_contact = torch.empty(n_lig, dtype=torch.uint8, device=dev)
+    centroid = torch.empty(n_graphs, 3, dtype=torch.float64, device=dev)
+    graph_counts = torch.empty(n_graphs, len(CONTACTS_GRAPH_COLUMNS), dtype=torch.int32, device=dev)
+    p = _native.ptr
+    some = lambda t: p(t) if t.numel() else None
+    _native.check(_native.lib().cbgx_pocket_contacts(some(x_lig), some(z_lig), p(lig_ptr), n_lig, some(x_rec), some(z_rec), p(rec_ptr),
+                                                     n_rec, n_graphs, float(cutoff2), some(rec_contact), some(lig_contact),
+                                                     some(centroid), some(graph_counts), _native.current_stream(dev)),
+                  "cbgx_pocket_contacts")
+    return {"rec_contact": rec_contact, "lig_contact": lig_contact, "centroid": centroid, "graph_counts": graph_counts, "rec_ptr": rec_ptr}
+
+
+def native_compare(fingerprints, contacts, native_fingerprints, native_contacts, group_ptr):
+    """Every sample of a pocket against the pocket's native ligand, one launch (``cbgx_native_compare``, csrc/native.hip; one workgroup
+    per pocket).  ``fingerprints`` / ``contacts``: what ``ligand_fingerprints`` / ``pocket_contacts`` returned for the B sample graphs;
+    ``native_fingerprints`` / ``native_contacts``: the same for the P native ligands, one graph per pocket; ``group_ptr`` [P + 1] ints:
+    the samples of pocket p are the graphs group_ptr[p] ... group_ptr[p + 1].  Returns device tensors: ``sample_counts`` [B, 6] int64
+    (NATIVE_SAMPLE_COLUMNS: the Tanimoto similarity in millionths as ``tanimoto_micro`` computes it, equal hash, the pocket atoms both
+    touch, those either touches, their quotient in millionths by the same rounding, status), ``centroid_d2`` [B] float64 and
+    ``group_counts`` [P, 9] int64 (NATIVE_GROUP_COLUMNS), with ``group_ptr`` as handed to the kernel.  Nothing is an error: a fingerprint
+    that was not evaluated on either side gives -1 in sim_micro and same_hash, pocket ranges of different lengths -1 in the contact
+    columns, each with its status bit (NATIVE_*); a graph in no group keeps -1 in every column and nan.  There is no CPU path."""
+    fp, mol_hash, fgc = fingerprints["fingerprint"], fingerprints["mol_hash"], fingerprints["graph_counts"]
+    dev = fp.device
+    _gpu_only(dev, "native_compare", "cbgx_native_compare")
+    n_graphs, n_rec = int(fp.shape[0]), int(contacts["rec_contact"].shape[0])
+    ptr = [int(v) for v in (group_ptr.tolist() if isinstance(group_ptr, (torch.Tensor, np.ndarray)) else group_ptr)]
+    if not ptr or any(not -2 ** 31 <= v < 2 ** 31 for v in ptr):
+        raise ValueError("group_ptr must be [P + 1] 32-bit integers")
+    n_groups, n_rec_nat = len(ptr) - 1, int(native_contacts["rec_contact"].shape[0])
+    for what, n, f, k in (("sample", n_graphs, fingerprints, contacts), ("native", n_groups, native_fingerprints, native_contacts)):
+        if (f["fingerprint"].shape != (n, FINGERPRINT_WORDS) or f["mol_hash"].shape != (n,)
+                or f["graph_counts"].shape != (n, len(FINGERPRINT_GRAPH_COLUMNS)) or k["centroid"].shape != (n, 3)
+                or k["graph_counts"].shape != (n, len(CONTACTS_GRAPH_COLUMNS)) or k["rec_ptr"].shape != (n + 1,)):
+            raise ValueError(f"one fingerprint row, hash, centroid and row of counts per {what} graph ({n}), and a rec_ptr of one more")
+        for name, t in list(f.items()) + list(k.items()):
+            if isinstance(t, torch.Tensor) and t.device != dev:
+                raise ValueError(f"{what} {name} is on {t.device}, the fingerprints on {dev}")
+
+    def side(f, k):
+        return (f["fingerprint"].to(torch.int32).contiguous(), f["mol_hash"].to(torch.int64).contiguous(),
+                f["graph_counts"][:, -1].to(torch.int32).contiguous(), k["rec_contact"].to(torch.uint8).contiguous(),
+                k["rec_ptr"].to(torch.int32).contiguous(), k["centroid"].to(torch.float64).contiguous(),
+                k["graph_counts"][:, -1].to(torch.int32).contiguous())
+
+    mine, theirs = side(fingerprints, contacts), side(native_fingerprints, native_contacts)
+    group_ptr = torch.tensor(ptr, dtype=torch.int32, device=dev)
+    sample_counts = torch.full((n_graphs, len(NATIVE_SAMPLE_COLUMNS)), -1, dtype=torch.int64, device=dev)
+    centroid_d2 = torch.full((n_graphs,), float("nan"), dtype=torch.float64, device=dev)
+    group_counts = torch.empty(n_groups, len(NATIVE_GROUP_COLUMNS), dtype=torch.int64, device=dev)
+    p = _native.ptr
+    some = lambda t: p(t) if t.numel() else None
+    _native.check(_native.lib().cbgx_native_compare(
+        *[some(t) if i != 4 else p(t) for i, t in enumerate(mine)], n_graphs, n_rec,
+        *[some(t) if i != 4 else p(t) for i, t in enumerate(theirs)], n_groups, n_rec_nat, p(group_ptr), some(sample_counts),
+        some(centroid_d2), some(group_counts), _native.current_stream(dev)), "cbgx_native_compare")
+    return {"sample_counts": sample_counts, "centroid_d2": centroid_d2, "group_counts": group_counts, "group_ptr": group_ptr}
+
+
+_NATIVE_DEPS = ("bonds", "rings", "aromatic", "valence", "interactions", "diversity")
+
+
+def _native_deps(batch, x, c, lig_batch, mode, group_ptr, given):
+    """the reports ``batch_native`` reads of one state, in ``given`` (computed where None): bonds, rings, aromatic (with aromatic atom
+    types only), valence, interactions and the fingerprints of ``batch_diversity``"""
+    made = {k: given.get(k) for k in _NATIVE_DEPS}
+    if made["bonds"] is None:
+        made["bonds"] = batch_bonds(batch, x, c, lig_batch, mode)
+    if made["rings"] is None:
+        made["rings"] = batch_rings(batch, x, c, lig_batch, mode, bonds=made["bonds"])
+    if mode not in _AROMATIC:
+        made["aromatic"] = None
+    elif made["aromatic"] is None:
+        made["aromatic"] = batch_aromatic(batch, x, c, lig_batch, mode, bonds=made["bonds"], rings=made["rings"])
+    if made["valence"] is None:
+        made["valence"] = batch_valence(batch, x, c, lig_batch, mode, bonds=made["bonds"], aromatic=made["aromatic"])
+    if made["interactions"] is None:
+        made["interactions"] = batch_interactions(batch, x, c, lig_batch, mode, bonds=made["bonds"], valence=made["valence"])
+    if made["diversity"] is None:
+        made["diversity"] = batch_diversity(batch, x, c, lig_batch, mode, group_ptr, bonds=made["bonds"], rings=made["rings"],
+                                            aromatic=made["aromatic"])
+    return made
+
+
+def batch_native(batch, x, c, lig_batch, mode, group_ptr, native_state, bonds=None, rings=None, aromatic=None, valence=None,
+                 interactions=None, diversity=None):
+    """A sampling state whose graphs group_ptr[p] ... group_ptr[p + 1] are the samples of pocket p against the P native ligands of
+    ``native_state``: a dict with ``x`` [n_nat, 3], ``c`` (type indices of ``mode``) and ``lig_batch`` of a state of P graphs, ``batch``
+    (the P pocket copies those graphs sit in: the keys ``batch_interactions`` reads, in the frame of ``x``) and, optionally, under the
+    names of the keyword arguments what the ``batch_*`` functions returned for that state.  ``bonds`` ... ``diversity``: the same for the
+    sample state; whatever is None is computed here, for the native state by the same functions (its fingerprints with groups of one).
+    Two ``pocket_contacts`` launches and one ``native_compare`` on top.  Returns one dict of device tensors: ``sample_counts``,
+    ``centroid_d2``, ``group_counts``, ``group_ptr`` (``native_compare``); ``rec_contact``, ``lig_contact``, ``centroid``,
+    ``contact_counts``, ``rec_ptr`` (``pocket_contacts`` of the samples); ``interaction_counts`` / ``interaction_terms`` (the samples'
+    rows of ``ligand_interactions``, from which ``interaction_scores`` makes the scores); and the same seven of the native ligands under
+    ``native_`` + name."""
+    ptr = [int(v) for v in (group_ptr.tolist() if isinstance(group_ptr, (torch.Tensor, np.ndarray)) else group_ptr)]
+    n_groups = len(ptr) - 1
+    mine = _native_deps(batch, x, c, lig_batch, mode, ptr, {"bonds": bonds, "rings": rings, "aromatic": aromatic, "valence": valence,
+                                                            "interactions": interactions, "diversity": diversity})
+    dev = mine["bonds"]["bond_index"].device
+    nat_batch = {**{k: v.to(dev) if isinstance(v, torch.Tensor) else v for k, v in native_state["batch"].items()}, "num_graphs": n_groups}
+    nx, nc, nb = native_state["x"].to(dev), native_state["c"].to(dev), native_state["lig_batch"].to(dev)
+    theirs = _native_deps(nat_batch, nx, nc, nb, mode, list(range(n_groups + 1)), native_state)
+    out = {}
+    for prefix, made, (bt, xs, cs, lb, n) in (("", mine, (batch, x.to(dev), c, lig_batch.to(dev), mine["bonds"]["graph_counts"].shape[0])),
+                                              ("native_", theirs, (nat_batch, nx, nc, nb, n_groups))):
+        _, z, _ = _state_atoms(cs, mode, lb, {"num_graphs": n}, dev)
+        x_rec, z_rec, rec_b = (bt[k].to(dev) for k in ("protein_pos", "protein_element", "protein_element_batch"))
+        made["contacts"] = pocket_contacts(xs, z, lb, x_rec, z_rec, rec_b, n)
+        for k in ("rec_contact", "lig_contact", "centroid", "rec_ptr"):
+            out[prefix + k] = made["contacts"][k]
+        out[prefix + "contact_counts"] = made["contacts"]["graph_counts"]
+        out[prefix + "interaction_counts"] = made["interactions"]["graph_counts"]
+        out[prefix + "interaction_terms"] = made["interactions"]["graph_terms"]
+    out.update(native_compare(mine["diversity"], mine["contacts"], theirs["diversity"], theirs["contacts"], ptr))
+    return out
+
+
+def _half_up_micro(value):
+    """a float rounded half up to whole millionths, None where it is not finite"""
+    return int(np.floor(value * 1e6 + 0.5)) if np.isfinite(value) else None
+
+
+NATIVE_EVALUATED, NATIVE_POSITIVE_NATIVE, NATIVE_NO_NATIVE_SCORE, NATIVE_NO_SAMPLE = 0, 1, 2, 3
+
+
+def native_pocket_metrics(score_micro_samples, n_heavy_samples, score_micro_native):
+    """``calculate_vina_metrics`` (the reference's evaluate_scripts/cal_chem_results.py:51-67) of one pocket, restated on this library's
+    score: ``score_micro_samples``: the samples' ``score_micro`` integers (None: not evaluated), ``n_heavy_samples``: their heavy-atom
+    counts, ``score_micro_native``: that of the native ligand (None: not evaluated).  With vina = score_micro / 1e6 of the evaluated
+    samples with a heavy atom and ref = the native's: binding_gap = mean((vina - ref) / ref) 100 (MPBG, in percent as the reference
+    prints it), improved_ratio = the share of samples with vina < ref (strictly; IMP / 100), mean_score = mean(vina),
+    ligand_efficiency = mean(vina / n_heavy) (LBE, the reference's sign), all in float64 numpy arithmetic as the reference writes
+    them; a native score of 0 divides by zero as it does there.  ``skipped``: NATIVE_EVALUATED, or why the four are nan:
+    NATIVE_POSITIVE_NATIVE (ref > 0, the reference's condition), NATIVE_NO_NATIVE_SCORE, NATIVE_NO_SAMPLE.  Each of the four also
+    rounded half up to whole millionths (``*_micro``; None where nan or infinite): what ranks add up.  n_scored, n_improved and
+    native_score_micro are carried along.  A score in Vina's functional form on this library's typing, not the Vina program."""
+    pairs = [(int(s), int(n)) for s, n in zip(score_micro_samples, n_heavy_samples) if s is not None and int(n) > 0]
+    out = {"skipped": NATIVE_EVALUATED, "n_scored": len(pairs), "n_improved": 0,
+           "native_score_micro": None if score_micro_native is None else int(score_micro_native)}
+    names = ("binding_gap", "improved_ratio", "mean_score", "ligand_efficiency")
+    if score_micro_native is None:
+        out["skipped"] = NATIVE_NO_NATIVE_SCORE
+    elif int(score_micro_native) > 0:
+        out["skipped"] = NATIVE_POSITIVE_NATIVE
+    elif not pairs:
+        out["skipped"] = NATIVE_NO_SAMPLE
+    if out["skipped"] != NATIVE_EVALUATED:
+        out.update({k: float("nan") for k in names}, **{k + "_micro": None for k in names})
+        return out
+    vina = np.array([s for s, _ in pairs], np.int64) / 1e6
+    atom_num = np.array([n for _, n in pairs], np.int64)
+    ref = int(score_micro_native) / 1e6
+    with np.errstate(divide="ignore", invalid="ignore"):
+        values = (float(np.mean((vina - ref) / ref) * 100), float((vina < ref).sum() / len(vina)), float(np.mean(vina)),
+                  float(np.mean(vina / atom_num)))
+    out["n_improved"] = int((vina < ref).sum())
+    out.update(zip(names, values), **{k + "_micro": _half_up_micro(v) for k, v in zip(names, values)})
+    return out
+
+
+NATIVE_POCKET_KEYS = (("n_mol",) + NATIVE_GROUP_COLUMNS[1:] + ("skipped", "n_scored", "n_improved", "native_score_micro", "binding_gap_micro",
+                      "improved_ratio_micro", "mean_score_micro", "ligand_efficiency_micro"))
+NATIVE_COUNT_KEYS = ("n_pockets", "n_pockets_evaluated", "n_pockets_positive_native", "n_pockets_native_not_evaluated",
+                     "n_pockets_no_sample", "n_pockets_with_gap", "binding_gap_micro_sum", "improved_ratio_micro_sum",
+                     "mean_score_micro_sum", "native_score_micro_sum", "ligand_efficiency_micro_sum", "n_mol", "n_mol_scored",
+                     "n_mol_improved", "n_fp_compared", "n_same_hash", "sim_micro_sum", "n_contact_compared", "contact_micro_sum",
+                     "n_pockets_fp_compared", "n_pockets_with_rediscovery")
+NATIVE_RATIOS = ("improved_mol_ratio", "mean_binding_gap", "mean_score", "mean_native_score", "mean_ligand_efficiency",
+                 "mean_native_similarity", "rediscovered_mol_ratio", "mean_contact_jaccard", "pockets_with_rediscovery_ratio")
+
+
+def native_pocket_counts(group_row, metrics):
+    """one row of ``native_compare``'s group_counts and the pocket's ``native_pocket_metrics`` -> the pocket's ``native_comparison``
+    dict (NATIVE_POCKET_KEYS): integers, None for a number the pocket does not have"""
+    row = dict(zip(NATIVE_GROUP_COLUMNS, (int(v) for v in group_row)))
+    out = {"n_mol": row.pop("n_graphs"), **row}
+    out.update({k: metrics[k] for k in NATIVE_POCKET_KEYS[len(NATIVE_GROUP_COLUMNS):]})
+    return out
+
+
+def native_totals(pockets):
+    """the pockets' ``native_comparison`` dicts -> the integer totals, in NATIVE_COUNT_KEYS order: what ranks add up.  The sums of the
+    four metrics and of the native score run over the evaluated pockets (skipped == NATIVE_EVALUATED); the binding gap, which a native
+    score of exactly 0 makes infinite, over those of them where it is finite (n_pockets_with_gap)"""
+    t = dict.fromkeys(NATIVE_COUNT_KEYS, 0)
+    for c in pockets:
+        t["n_pockets"] += 1
+        for code, key in ((NATIVE_EVALUATED, "n_pockets_evaluated"), (NATIVE_POSITIVE_NATIVE, "n_pockets_positive_native"),
+                          (NATIVE_NO_NATIVE_SCORE, "n_pockets_native_not_evaluated"), (NATIVE_NO_SAMPLE, "n_pockets_no_sample")):
+            t[key] += int(c["skipped"] == code)
+        if c["skipped"] == NATIVE_EVALUATED:
+            if c["binding_gap_micro"] is not None:
+                t["n_pockets_with_gap"] += 1
+                t["binding_gap_micro_sum"] += c["binding_gap_micro"]
+            for k in ("improved_ratio", "mean_score", "ligand_efficiency"):
+                t[k + "_micro_sum"] += c[k + "_micro"]
+            t["native_score_micro_sum"] += c["native_score_micro"]
+            t["n_mol_scored"] += c["n_scored"]
+            t["n_mol_improved"] += c["n_improved"]
+        for k in ("n_mol", "n_fp_compared", "n_same_hash", "sim_micro_sum", "n_contact_compared", "contact_micro_sum"):
+            t[k] += c[k]
+        t["n_pockets_fp_compared"] += int(c["n_fp_compared"] > 0)
+        t["n_pockets_with_rediscovery"] += int(c["n_same_hash"] > 0)
+    return [t[k] for k in NATIVE_COUNT_KEYS]
+
+
+def summarise_native_totals(totals):
+    """the job's numbers (NATIVE_RATIOS) from integer totals in NATIVE_COUNT_KEYS order; a ratio over nothing is nan.  The first five are
+    per-pocket averages over the evaluated pockets, as the reference averages (cal_chem_results.py:110-117): improved_mol_ratio (IMP as
+    a ratio, not in percent), mean_binding_gap (MPBG, in percent; over the pockets with a finite gap), mean_score, mean_native_score,
+    mean_ligand_efficiency (LBE).  mean_native_similarity and rediscovered_mol_ratio (equal hash) run over the samples whose
+    fingerprint was compared, mean_contact_jaccard over those whose contacts were, pockets_with_rediscovery_ratio over the pockets with
+    a compared sample.  The reference's formulas on this library's score in Vina's functional form, not Vina's; a fingerprint of this
+    library's own, not RDKit's; the contact Jaccard index is a descriptor of this library's own"""
+    c = {k: int(v) for k, v in zip(NATIVE_COUNT_KEYS, totals)}
+    n = c["n_pockets_evaluated"]
+    return {"improved_mol_ratio": _ratio(c["improved_ratio_micro_sum"], SIMILARITY_ONE * n),
+            "mean_binding_gap": _ratio(c["binding_gap_micro_sum"], SIMILARITY_ONE * c["n_pockets_with_gap"]),
+            "mean_score": _ratio(c["mean_score_micro_sum"], SIMILARITY_ONE * n),
+            "mean_native_score": _ratio(c["native_score_micro_sum"], SIMILARITY_ONE * n),
+            "mean_ligand_efficiency": _ratio(c["ligand_efficiency_micro_sum"], SIMILARITY_ONE * n),
+            "mean_native_similarity": _ratio(c["sim_micro_sum"], SIMILARITY_ONE * c["n_fp_compared"]),
+            "rediscovered_mol_ratio": _ratio(c["n_same_hash"], c["n_fp_compared"]),
+            "mean_contact_jaccard": _ratio(c["contact_micro_sum"], SIMILARITY_ONE * c["n_contact_compared"]),
+            "pockets_with_rediscovery_ratio": _ratio(c["n_pockets_with_rediscovery"], c["n_pockets_fp_compared"]),
+            "n_pockets_positive_native": c["n_pockets_positive_native"],
+            "n_pockets_native_not_evaluated": c["n_pockets_native_not_evaluated"], "n_pockets_no_sample": c["n_pockets_no_sample"],
+            "counts": c}
+
+
+def summarise_native(pockets):
+    """the comparison with the native ligands of a set of pockets from their ``native_comparison`` dicts: see
+    ``summarise_native_totals``"""
+    return summarise_native_totals(native_totals(pockets))
+
+
 # the five reports that are integer counts per molecule, for a driver that treats them alike: per-molecule columns -> totals (what ranks
 # add up; count_keys) -> ratios and ``counts``
 CountReport = collections.namedtuple("CountReport", "name graph_columns count_keys ratios totals summarise_totals")

@@ -49,6 +49,12 @@ the MAE and the Jensen-Shannon distance to the caller's own ratios and distribut
 that graph, then per pocket the duplicates, every pair's Tanimoto similarity and each sample's nearest neighbour, computed on the device
 in two more launches per batch (``geometry.batch_diversity``), with ``{out_dir}/diversity_summary.json`` for the job.  A fingerprint of
 this library's own, not RDKit's; equal hashes are equivalence under the refinement, not isomorphism.
+``--native`` (with ``--pockets`` whose dicts carry ``ligand_pos`` / ``ligand_atom_type``) compares every sample with the ligand its
+pocket was crystallised with: that ligand goes through the same reports as one more graph per pocket, two more kernels say which pocket
+atoms a ligand touches and compare fingerprints, contact sets and centroids (``geometry.batch_native``), and the reference's MPBG / IMP /
+LBE formulas (``calculate_vina_metrics``) are taken on the scores of ``--interactions``, with ``{out_dir}/native_summary.json`` for the job.
+It inherits the deviations of ``--interactions`` and ``--diversity``: a score in Vina's functional form, not Vina; a fingerprint of this
+library's own, not RDKit's.  The contact Jaccard index and the centroid distance are descriptors of this library's own.
 ``--sdf`` writes ``pocket_{i:05d}.sdf`` beside every result file: one V2000 record per sample, bond types the Kekule orders of ``--valence``
 when given, else from ``--aromatic`` when given, table-bond orders otherwise (``geometry.sdf_record``; host side, no RDKit).
 A checkpoint is the reference's format: ``{'config': ..., 'model': state_dict}`` (``sample.py:153-156``)."""
@@ -129,6 +135,25 @@ def load_context(raw_pockets, path, choose=None, rng=None, counter=False):
     return None
 
 
+def load_native(raw_pockets, num_classes):
+    """``--native``: per pocket (pos [n, 3] float32, atom_type [n] int64) of the ligand the pocket file carries (``ligand_pos``,
+    ``ligand_atom_type``: indices of the ``num_classes`` types the samples are decoded with), n >= 1; whatever else a context task reads
+    of the dict (``ligand_gen_index``) changes nothing.  A pocket without them, a length mismatch or a type out of range is a SystemExit
+    naming the pocket"""
+    out = []
+    for k, p in enumerate(raw_pockets):
+        if "ligand_pos" not in p or "ligand_atom_type" not in p:
+            raise SystemExit(f"sample_cli: --native: pocket {k} carries no ligand_pos / ligand_atom_type")
+        pos, typ = np.asarray(p["ligand_pos"], np.float32), np.asarray(p["ligand_atom_type"], np.int64).reshape(-1)
+        if pos.ndim != 2 or pos.shape[1] != 3 or pos.shape[0] != typ.shape[0] or typ.shape[0] < 1:
+            raise SystemExit(f"sample_cli: --native: pocket {k}: ligand_pos {tuple(pos.shape)} and ligand_atom_type {tuple(typ.shape)} "
+                             f"are not [n, 3] and [n] with n >= 1")
+        if typ.min() < 0 or typ.max() >= num_classes:
+            raise SystemExit(f"sample_cli: --native: pocket {k}: ligand_atom_type out of range [0, {num_classes})")
+        out.append((np.ascontiguousarray(pos), typ))
+    return out
+
+
 def split_samples(x, c, batch_idx, n_graphs, mode="add_aromatic"):
     """per-graph records like ``split_batch_into_samples`` (sample.py:16-32): ``pos``, ``type`` (index), ``atom`` (atomic
     numbers) and ``aromatic`` (flags, None in 'basic' mode) -- the arguments of ``reconstruct_mol`` (sample.py:211-214) -- plus
@@ -157,7 +182,7 @@ def decode_mode(plan_mode, config_mode, num_classes):
 def main(argv=None, stats=None):
     """``stats`` (optional dict): filled with the wall seconds of the phases (setup = config + model + weights, batch = prior
     construction, sample = model.sample incl. the trajectory download, write = per-pocket records and files) and, for every requested report
-    (geometry, bonds, rings, aromatic, distributions, valence, interactions, groups, diversity: evaluated in that order), its own launches and downloads, a part of write: the bond
+    (geometry, bonds, rings, aromatic, distributions, valence, interactions, groups, diversity, native: evaluated in that order), its own launches and downloads, a part of write: the bond
     list and the ring report are made once per batch, and where they were not asked for their time goes to the first requested report
     in that order that needs them (cbgbench_amd/sample_reports.py)."""
     t_phase = time.perf_counter()
@@ -298,6 +323,24 @@ def main(argv=None, stats=None):
                          "RDKFingerprint, no agreement with them is claimed.  Uniqueness is per pocket.  A sample over a limit is reported "
                          "(diversity_status != 0) and left out of every number.  Independent of every other flag: what it needs is "
                          "computed and not written")
+    ap.add_argument("--native", action="store_true",
+                    help="with --pockets whose dicts carry the pocket's own ligand (ligand_pos [n, 3], ligand_atom_type [n]: indices of "
+                         "the vocabulary the samples are decoded with; the whole ligand in a context task too): compare every sample "
+                         "with it.  Adds to every sample native_similarity (Tanimoto similarity of the two fingerprints), "
+                         "native_same_hash, native_contact_jaccard / native_contact_common / native_contact_union (the heavy pocket atoms "
+                         "within 4 A of a heavy ligand atom that both touch), native_centroid_distance, score_minus_native, "
+                         "better_than_native (None where either score is missing), ligand_efficiency (score / heavy atoms) and "
+                         "native_status; to every pocket record `native` (the ligand's own record with the fields of every requested "
+                         "report, plus score, score_micro, n_contact_atoms and n_pocket_contact_atoms: the pocket atoms it touches) and `native_comparison` (integer counts); and "
+                         "{out_dir}/native_summary.json (improved_mol_ratio, mean_binding_gap, mean_score, mean_native_score, "
+                         "mean_ligand_efficiency as per-pocket averages: the reference's IMP, MPBG, Evina and LBE of "
+                         "calculate_vina_metrics; mean_native_similarity, rediscovered_mol_ratio, mean_contact_jaccard, "
+                         "pockets_with_rediscovery_ratio; pockets with a positive native score are left out as there), evaluated on the "
+                         "GPU (cbgbench_amd/geometry.py batch_native).  The native ligand is moved into the sampling frame by its "
+                         "pocket's translation and goes through the same kernels as a sample.  Inherits the deviations of --interactions "
+                         "and --diversity: a score in Vina's functional form, NOT the Vina program; a fingerprint of this library's own, "
+                         "NOT RDKit's.  The contact Jaccard index and the centroid distance are descriptors of this library's own.  "
+                         "Independent of every other flag: what it needs is computed and not written")
     ap.add_argument("--groups_reference", default=None,
                     help="with --groups: a .npz or torch.save'd dict {'ratio': ..., 'distribution': ...}, each the 25 values in the order "
                          "of the vocabulary (a torch.save'd dict may hold {name: value} dicts instead; none ship with this package); "
@@ -327,6 +370,11 @@ def main(argv=None, stats=None):
     reports = SampleReports.from_args(args)
     reports.refuse(dev, lambda: decode_mode(priors.SamplingPlan.from_config(config).mode, config.get("mode", None),
                                             config.model.num_atomtype))
+    native_ligands = None
+    if args.native:
+        if not args.pockets:
+            raise SystemExit("sample_cli: --native needs --pockets: the native ligand comes with its pocket (ligand_pos, ligand_atom_type)")
+        native_ligands = load_native(torch.load(args.pockets, map_location="cpu", weights_only=False), config.model.num_atomtype)
 
     ckpt_path = args.checkpoint or config.model.get("checkpoint", None)
     if ckpt_path and os.path.exists(ckpt_path):
@@ -386,7 +434,9 @@ def main(argv=None, stats=None):
         # last step, not traj[-1]; kept as the default for drop-in outputs, --final_state selects traj[-1]
         x, c, bidx = traj[-1] if (args.final_state and config.model.type != "diffsbdd") else traj[0]
         n_graphs = len(ids) * num_samples
-        found = reports.evaluate(dev, (x, c, bidx), batch, n_graphs, mode, group_ptr=[k * num_samples for k in range(len(ids) + 1)])
+        group_ptr = [k * num_samples for k in range(len(ids) + 1)]
+        native = reports.native_state(batch, group_ptr, [native_ligands[i] for i in ids]) if native_ligands is not None else None
+        found = reports.evaluate(dev, (x, c, bidx), batch, n_graphs, mode, group_ptr=group_ptr, native=native)
         x, c, bidx = x.cpu(), c.cpu(), bidx.cpu()
         if translate:       # back to the frame the pockets came in (sample.py:198-199; here per graph: a batch holds many pockets)
             x = x + batch["ligand_translation"].cpu()
@@ -396,9 +446,14 @@ def main(argv=None, stats=None):
             for g, smp in enumerate(samples):
                 smp["gen_flag"] = gen[bidx == g].clone()
         reports.annotate(samples, found)
+        if native is not None:      # the native ligands' own records, in the frame the samples' are written in
+            nat_x = torch.cat([torch.from_numpy(native_ligands[i][0]) for i in ids]) if translate else native["x"].cpu()
+            natives = reports.annotate_native(split_samples(nat_x, native["c"].cpu(), native["lig_batch"].cpu(), len(ids), mode), found)
         for k, pid in enumerate(ids):
             g0, g1 = k * num_samples, (k + 1) * num_samples
             rec = {"pocket_index": pid, "samples": samples[g0:g1], **reports.pocket_counts(found, g0, g1)}
+            if native is not None:
+                rec["native"] = natives[k]
             if args.save_traj:
                 rec["traj_keys"] = sorted(traj.keys())
             torch.save(rec, os.path.join(out_dir, f"pocket_{pid:05d}.pt"))

@@ -1,4 +1,4 @@
-"""The reports of ``sample_cli`` (--geometry, --bonds, --rings, --aromatic, --distributions, --valence, --interactions, --groups, --diversity, --sdf) in three stages: ``evaluate`` runs the
+"""The reports of ``sample_cli`` (--geometry, --bonds, --rings, --aromatic, --distributions, --valence, --interactions, --groups, --diversity, --native, --sdf) in three stages: ``evaluate`` runs the
 requested reports of one batch on the GPU and returns plain dicts of CPU tensors; ``annotate`` / ``pocket_counts`` / ``pocket_files``
 turn those into the per-sample fields, the per-pocket dicts and the ``.sdf`` text on the host (CPU tensors in, no device); ``finish`` sums
 the job's integer totals over the ranks, writes ``*_summary.json`` and prints one line per report.
@@ -21,7 +21,14 @@ where the atom types have aromatic flags.
 The reports of ACROSS come after those of LATE.  ``diversity`` (fingerprints and hashes of this library's own, not RDKit's; uniqueness and
 Tanimoto similarity per pocket) is the first report that reads more than one graph at a time: ``evaluate`` takes the pocket -> graphs
 grouping for it (``group_ptr``), and a pocket's record carries what its samples share.  It takes the bond list, the ring report and,
-where the atom types have aromatic flags, the aromatic report."""
+where the atom types have aromatic flags, the aromatic report.
+
+The reports of AGAINST come after those of ACROSS.  ``native`` compares every sample with the ligand its pocket was crystallised with:
+``evaluate`` takes that ligand of every pocket of the batch as one more state of P graphs (``native=``, built by ``native_state``), runs it
+through the same functions as the samples -- the bond list, the ring, aromatic and valence reports, ``interactions`` and the fingerprints,
+and whatever else was requested -- and hands both to ``geometry.batch_native``.  All of that is the report's own time.  MPBG / IMP / LBE
+are the reference's formulas on this library's score in Vina's functional form, not Vina's; the fingerprint is this library's own, not
+RDKit's; the contact Jaccard index and the centroid distance are descriptors of this library's own."""
 import json
 import os
 import time
@@ -36,8 +43,10 @@ ORDER = ("geometry", "bonds", "rings", "aromatic", "distributions", "valence")
 EXTRA = ("interactions",)        # evaluated, annotated and finished after ORDER
 LATE = ("groups",)               # ... and these after EXTRA
 ACROSS = ("diversity",)          # ... and these, which compare the samples of a pocket, after LATE
+AGAINST = ("native",)            # ... and these, which compare every sample with its pocket's native ligand, after ACROSS
 NEEDS = {"rings": ("bonds",), "aromatic": ("bonds", "rings"), "distributions": ("bonds",), "valence": ("bonds", "aromatic"),
-         "interactions": ("bonds", "valence"), "groups": ("bonds", "aromatic"), "diversity": ("bonds", "rings", "aromatic")}
+         "interactions": ("bonds", "valence"), "groups": ("bonds", "aromatic"), "diversity": ("bonds", "rings", "aromatic"),
+         "native": ("bonds", "rings", "aromatic", "valence", "interactions", "diversity")}
 
 
 def needs(name, mode):
@@ -46,6 +55,8 @@ def needs(name, mode):
         return ("bonds",)
     if name == "diversity" and mode not in _AROMATIC:
         return ("bonds", "rings")
+    if name == "native" and mode not in _AROMATIC:
+        return ("bonds", "rings", "valence", "interactions", "diversity")
     return NEEDS.get(name, ())
 
 
@@ -60,6 +71,7 @@ _GPU_ONLY = {"geometry": "--geometry runs on the GPU (cbgx_ligand_geometry has n
              "interactions": "--interactions runs on the GPU (cbgx_pocket_types / cbgx_ligand_interactions have no CPU fallback)",
              "groups": "--groups runs on the GPU (cbgx_ligand_groups has no CPU fallback)",
              "diversity": "--diversity runs on the GPU (cbgx_ligand_fingerprints / cbgx_group_diversity have no CPU fallback)",
+             "native": "--native runs on the GPU (cbgx_pocket_contacts / cbgx_native_compare have no CPU fallback)",
              "sdf": "--sdf takes its bonds from the GPU (cbgx_ligand_bonds_count / _fill have no CPU fallback)"}
 # a count report's printed line: the ratios it names, and its own tail
 _LINE = {"geometry": (geometry.RATIOS, lambda c: f"{c['n_mol']} molecules, {c['n_atoms']} atoms"),
@@ -104,7 +116,7 @@ def ranges(counts):
 
 
 class SampleReports:
-    """``requested``: names out of ORDER, EXTRA, LATE, ACROSS and 'sdf'; ``reference``: the path of --distributions_reference;
+    """``requested``: names out of ORDER, EXTRA, LATE, ACROSS, AGAINST and 'sdf'; ``reference``: the path of --distributions_reference;
     ``groups_reference``: that of --groups_reference"""
 
     def __init__(self, requested, reference=None, groups_reference=None):
@@ -112,7 +124,7 @@ class SampleReports:
         self.reference = reference
         self.groups_reference = groups_reference
         self.n_orders = 4 if "aromatic" in self.requested else 3        # --aromatic --distributions: types with the aromatic type
-        self.seconds = {name: 0.0 for name in ORDER + EXTRA + LATE + ACROSS if name in self.requested}  # wall time of every report (``stats``)
+        self.seconds = {name: 0.0 for name in ORDER + EXTRA + LATE + ACROSS + AGAINST if name in self.requested}  # wall time of every report (``stats``)
         self.counts = {name: [] for name in _COUNT_REPORTS if name in self.requested}  # per-sample counts of this rank
         # the pockets' flat integer totals are added up as they come (one is 3.5 MB)
         self.distribution_totals = np.zeros(geometry.distribution_totals_length(n_orders=self.n_orders), np.int64)
@@ -120,15 +132,16 @@ class SampleReports:
         self.interactions = []                                          # (graph_counts, graph_terms) of this rank's pockets
         self.groups = []                                                # graph_counts of this rank's pockets
         self.diversity = []                                             # group_counts rows of this rank's pockets
+        self.native = []                                                # native_comparison dicts of this rank's pockets
 
     @classmethod
     def from_args(cls, args):
-        return cls([name for name in ORDER + EXTRA + LATE + ACROSS + ("sdf",) if getattr(args, name, False)], args.distributions_reference,
+        return cls([name for name in ORDER + EXTRA + LATE + ACROSS + AGAINST + ("sdf",) if getattr(args, name, False)], args.distributions_reference,
                    getattr(args, "groups_reference", None))
 
     def refuse(self, dev, atom_mode):
         """what cannot run is refused before any model is built; ``atom_mode()``: the vocabulary the samples are decoded with"""
-        for name in ("geometry", "bonds", "rings", "distributions", "aromatic", "valence") + EXTRA + LATE + ACROSS + ("sdf",):
+        for name in ("geometry", "bonds", "rings", "distributions", "aromatic", "valence") + EXTRA + LATE + ACROSS + AGAINST + ("sdf",):
             if name not in self.requested:
                 continue
             if name == "aromatic" and atom_mode() != "add_aromatic":
@@ -143,43 +156,95 @@ class SampleReports:
             raise SystemExit("sample_cli: --groups_reference needs --groups")
 
     # ---- GPU -----------------------------------------------------------------------------------------------------------------------------
-    def evaluate(self, dev, state, batch, n_graphs, mode, group_ptr=None):
+    def evaluate(self, dev, state, batch, n_graphs, mode, group_ptr=None, native=None):
         """the requested reports of the state ``(x, c, bidx)`` the records hold, in the sampling frame (before ligand_translation), against
         the batch's own pocket -> {report: {name: CPU tensor}}; with --sdf or --aromatic and no --bonds also the ``bonds`` the host side
         slices by (not written).  ``group_ptr`` [P + 1]: the graphs group_ptr[p] ... group_ptr[p + 1] are the samples of the batch's pocket
-        p; only the reports of ACROSS read it, and they need it"""
+        p; only the reports of ACROSS and AGAINST read it, and they need it.  ``native``: what ``native_state`` made of the pockets' own
+        ligands; the native report needs it, and also returns ``native_reports``: the native ligands' rows of every other requested
+        report, a dict like this one over P graphs"""
         if not self.requested:
             return {}
-        if group_ptr is None and self.requested & set(ACROSS):
-            raise ValueError("the diversity report compares the samples of a pocket: evaluate needs group_ptr")
-        x, c, bidx = (t.to(dev) for t in state)
-        info, made, out = {"num_graphs": n_graphs}, {}, {}
+        if group_ptr is None and self.requested & set(ACROSS + AGAINST):
+            raise ValueError("the diversity and native reports compare the samples of a pocket: evaluate needs group_ptr")
+        if native is None and "native" in self.requested:
+            raise ValueError("the native report compares with the pockets' own ligands: evaluate needs native")
+        out = {}
 
-        def get(name):
-            if name not in made:
-                deps = {dep: get(dep) for dep in needs(name, mode)}
-                if name == "geometry":
-                    pocket = {k: batch[k].to(dev) for k in ("protein_pos", "protein_element", "protein_element_batch")}
-                    made[name] = geometry.batch_geometry({**pocket, **info}, x, c, bidx, mode)
-                elif name == "interactions":
-                    pocket = {k: batch[k].to(dev) for k in ("protein_pos", "protein_element", "protein_element_batch", "protein_aa_type",
+        def reports_of(state, batch, n_graphs, group_ptr, against=None):
+            """``get(name)`` of one state: every report is made once; ``against``: the ``get`` of the native ligands' state"""
+            x, c, bidx = (t.to(dev) for t in state)
+            info, made = {"num_graphs": n_graphs}, {}
+            pocket = lambda: {k: batch[k].to(dev) for k in ("protein_pos", "protein_element", "protein_element_batch", "protein_aa_type",
                                                             "protein_atom_feature")}
-                    made[name] = geometry.batch_interactions({**pocket, **info}, x, c, bidx, mode, **deps)
-                elif name == "diversity":
-                    made[name] = geometry.batch_diversity(info, x, c, bidx, mode, group_ptr, **deps)
-                elif name == "distributions":
-                    made[name] = geometry.batch_distributions(info, x, c, bidx, mode, aromatic=made.get("aromatic"), **deps)
-                else:
-                    made[name] = getattr(geometry, "batch_" + name)(info, x, c, bidx, mode, **deps)
-            return made[name]
 
+            def get(name):
+                if name not in made:
+                    deps = {dep: get(dep) for dep in needs(name, mode)}
+                    if name == "geometry":
+                        rec = {k: batch[k].to(dev) for k in ("protein_pos", "protein_element", "protein_element_batch")}
+                        made[name] = geometry.batch_geometry({**rec, **info}, x, c, bidx, mode)
+                    elif name == "interactions":
+                        made[name] = geometry.batch_interactions({**pocket(), **info}, x, c, bidx, mode, **deps)
+                    elif name == "diversity":
+                        made[name] = geometry.batch_diversity(info, x, c, bidx, mode, group_ptr, **deps)
+                    elif name == "native":
+                        theirs = {**native, **{dep: against(dep) for dep in needs(name, mode)}}
+                        made[name] = geometry.batch_native({**pocket(), **info}, x, c, bidx, mode, group_ptr, theirs, **deps)
+                    elif name == "distributions":
+                        made[name] = geometry.batch_distributions(info, x, c, bidx, mode, aromatic=made.get("aromatic"), **deps)
+                    else:
+                        made[name] = getattr(geometry, "batch_" + name)(info, x, c, bidx, mode, **deps)
+                return made[name]
+            return get
+
+        get_native = None
+        if "native" in self.requested:
+            n_pockets = len(group_ptr) - 1
+            get_native = reports_of((native["x"], native["c"], native["lig_batch"]), native["batch"], n_pockets,
+                                    list(range(n_pockets + 1)))
+        get = reports_of(state, batch, n_graphs, group_ptr, get_native)
         for name in self.seconds:
             t0 = time.perf_counter()
             out[name] = {k: v.cpu() for k, v in get(name).items()}      # (the download waits for the launches)
+            if name == "native":    # the native ligands' rows of every other requested report: what their records carry
+                theirs = {other: {k: v.cpu() for k, v in get_native(other).items()} for other in self.seconds if other != "native"}
+                if "bonds" not in theirs and "aromatic" in self.requested:
+                    theirs["bonds"] = {k: get_native("bonds")[k].cpu() for k in ("bond_index", "bond_order", "graph_counts")}
+                out["native_reports"] = theirs
             self.seconds[name] += time.perf_counter() - t0
         if "bonds" not in out and self.requested & {"aromatic", "sdf"}:
             out["bonds"] = {k: get("bonds")[k].cpu() for k in ("bond_index", "bond_order", "graph_counts")}
         return out
+
+    @staticmethod
+    def native_state(batch, group_ptr, ligands):
+        """what ``evaluate`` takes as ``native``: the native ligands ``ligands`` ([(pos [n, 3], type indices [n])], one per pocket of the
+        batch, in the frame the pockets came in) as a state of P graphs in the sampling frame -- float32(pos) minus the translation the
+        graphs of the pocket carry in ``batch`` (``ligand_translation``; one fp32 subtraction per component) -- with the pocket copy of
+        the pocket's first graph group_ptr[p]"""
+        dev = batch["protein_pos"].device
+        rec_b, bidx = batch["protein_element_batch"], batch["ligand_element_batch"]
+        keys = ("protein_pos", "protein_element", "protein_aa_type", "protein_atom_feature")
+        rows, xs, cs, lbs, pocket = [], [], [], [], {k: [] for k in keys}
+        for p, (pos, typ) in enumerate(ligands):
+            g = int(group_ptr[p])
+            mine = (rec_b == g).nonzero().reshape(-1)
+            own = (bidx == g).nonzero().reshape(-1)
+            if own.numel():
+                shift = batch["ligand_translation"][own[0]]
+            elif mine.numel():
+                shift = batch["protein_translation"][mine[0]]
+            else:
+                shift = torch.zeros(3, device=dev)
+            xs.append(torch.as_tensor(np.asarray(pos, np.float32).reshape(-1, 3)).to(dev) - shift.to(torch.float32))
+            cs.append(torch.as_tensor(np.asarray(typ, np.int64).reshape(-1)).to(dev))
+            lbs.append(torch.full((cs[-1].shape[0],), p, dtype=torch.long, device=dev))
+            rows.append(torch.full((mine.shape[0],), p, dtype=torch.long, device=dev))
+            for k in keys:
+                pocket[k].append(batch[k][mine])
+        return {"x": torch.cat(xs), "c": torch.cat(cs), "lig_batch": torch.cat(lbs),
+                "batch": {**{k: torch.cat(v) for k, v in pocket.items()}, "protein_element_batch": torch.cat(rows)}}
 
     # ---- host ----------------------------------------------------------------------------------------------------------------------------
     def annotate(self, samples, ev):
@@ -274,6 +339,47 @@ class SampleReports:
                     smp["nearest_sample"] = int(div["nearest"][g])
                     smp["nearest_similarity"] = micro / geometry.SIMILARITY_ONE if micro >= 0 else float("nan")
                     smp["diversity_status"] = int(div["graph_counts"][g, -1])
+        if "native" in self.requested:
+            nat = ev["native"]
+            micro, heavy = self._score_micro(nat["interaction_counts"], nat["interaction_terms"]), nat["contact_counts"][:, 1].tolist()
+            theirs = self._score_micro(nat["native_interaction_counts"], nat["native_interaction_terms"])
+            ptr = nat["group_ptr"].tolist()
+            for p, (g0, g1) in enumerate(zip(ptr[:-1], ptr[1:])):
+                for g in range(g0, g1):
+                    smp, row = samples[g], dict(zip(geometry.NATIVE_SAMPLE_COLUMNS, nat["sample_counts"][g].tolist()))
+                    both = micro[g] is not None and theirs[p] is not None
+                    smp["native_similarity"] = row["sim_micro"] / geometry.SIMILARITY_ONE if row["sim_micro"] >= 0 else float("nan")
+                    smp["native_same_hash"] = row["same_hash"] == 1 if row["same_hash"] >= 0 else None
+                    smp["native_contact_jaccard"] = (row["contact_micro"] / geometry.SIMILARITY_ONE if row["contact_micro"] >= 0
+                                                     else float("nan"))
+                    smp["native_contact_common"], smp["native_contact_union"] = row["contact_common"], row["contact_union"]
+                    smp["native_centroid_distance"] = float(np.sqrt(float(nat["centroid_d2"][g])))
+                    smp["score_minus_native"] = (micro[g] - theirs[p]) / 1e6 if both else float("nan")
+                    smp["better_than_native"] = micro[g] < theirs[p] if both else None
+                    smp["ligand_efficiency"] = micro[g] / 1e6 / heavy[g] if micro[g] is not None and heavy[g] > 0 else float("nan")
+                    smp["native_status"] = row["status"]
+
+    @staticmethod
+    def _score_micro(graph_counts, graph_terms):
+        """per graph the score as whole millionths (``geometry.score_micro``), None where the interaction report did not evaluate it"""
+        _, score = geometry.interaction_scores(graph_counts.to(torch.int64), graph_terms)
+        return [None if np.isnan(v) else geometry.score_micro(v) for v in score]
+
+    def annotate_native(self, records, ev):
+        """the native ligands' records (``records``: one dict per pocket of the batch, as ``samples`` are per graph) with the fields of
+        every other requested report -- the same functions on the same atoms give what the ligand would get as a sample -- plus
+        ``score``, ``score_micro`` (None where not evaluated) and ``n_contact_atoms`` as the interaction report defines them, and
+        ``n_pocket_contact_atoms``: the heavy pocket atoms it touches, what ``native_contact_union`` of a sample is counted against"""
+        SampleReports(self.requested - {"native", "sdf"}).annotate(records, ev["native_reports"])
+        nat = ev["native"]
+        micro = self._score_micro(nat["native_interaction_counts"], nat["native_interaction_terms"])
+        _, score = geometry.interaction_scores(nat["native_interaction_counts"].to(torch.int64), nat["native_interaction_terms"])
+        for p, rec in enumerate(records):
+            rec["score"] = float(score[p])
+            rec["score_micro"] = micro[p]
+            rec["n_contact_atoms"] = int(nat["native_interaction_counts"][p, geometry.INTERACTION_GRAPH_COLUMNS.index("n_contact_atoms")])
+            rec["n_pocket_contact_atoms"] = int(nat["native_contact_counts"][p, 3])
+        return records
 
     def pocket_counts(self, ev, g0, g1):
         """the dicts of counts a pocket record carries for its graphs g0 ... g1 - 1, which join the job's totals"""
@@ -307,6 +413,18 @@ class SampleReports:
             q0, q1 = int(div["pair_ptr"][p]), int(div["pair_ptr"][p + 1])
             rec["similarity_micro"] = geometry.similarity_matrix(div["pair_sim"][q0:q1], (div["graph_counts"][g0:g1, -1] == 0).tolist())
             rec["diversity"] = geometry.diversity_counts(row)
+        if "native" in self.requested:
+            nat = ev["native"]
+            ptr = nat["group_ptr"].tolist()
+            found = [p for p in range(len(ptr) - 1) if (ptr[p], ptr[p + 1]) == (g0, g1)]
+            if not found:
+                raise ValueError(f"the graphs {g0} ... {g1} are no group of the group_ptr the native report was evaluated with")
+            p = found[0]
+            micro = self._score_micro(nat["interaction_counts"][g0:g1], nat["interaction_terms"][g0:g1])
+            theirs = self._score_micro(nat["native_interaction_counts"][p:p + 1], nat["native_interaction_terms"][p:p + 1])[0]
+            metrics = geometry.native_pocket_metrics(micro, nat["contact_counts"][g0:g1, 1].tolist(), theirs)
+            rec["native_comparison"] = geometry.native_pocket_counts(nat["group_counts"][p], metrics)
+            self.native.append(rec["native_comparison"])
         return rec
 
     def pocket_files(self, stem, samples, ev, g0):
@@ -386,6 +504,16 @@ class SampleReports:
                       + f" ({cnt['n_mol_evaluated']} of {cnt['n_mol']} molecules evaluated in {cnt['n_pockets']} pockets, n_mol_over_limit "
                         f"{cnt['n_mol_over_limit']}; uniqueness per pocket by a hash of colour refinement, not an isomorphism test; a "
                         f"fingerprint of this library's own, not RDKit's)")
+        if "native" in self.requested:
+            summary = geometry.summarise_native_totals(sharding.sum_counts(geometry.native_totals(self.native), device=dev))
+            if rank == 0:
+                save("native", summary)
+                cnt = summary["counts"]
+                print("native: " + ", ".join(f"{k} {summary[k]:.4f}" for k in geometry.NATIVE_RATIOS)
+                      + f" ({cnt['n_pockets_evaluated']} of {cnt['n_pockets']} pockets evaluated, n_pockets_positive_native "
+                        f"{cnt['n_pockets_positive_native']}, n_pockets_native_not_evaluated {cnt['n_pockets_native_not_evaluated']}, "
+                        f"n_pockets_no_sample {cnt['n_pockets_no_sample']}; the reference's MPBG / IMP / LBE formulas on a score in Vina's "
+                        f"functional form, not the Vina program; a fingerprint of this library's own, not RDKit's)")
         if "sdf" in self.requested:
             left_out, written = sharding.sum_counts([self.sdf_left_out, self.sdf_written], device=dev)
             if rank == 0:

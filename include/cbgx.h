@@ -1172,6 +1172,76 @@ int cbgx_group_diversity(const uint32_t *fp, const uint64_t *mol_hash, const int
                          const int64_t *pair_ptr, int n_graphs, int n_groups, long long n_pairs, int32_t *pair_sim, int32_t *first_same,
                          int32_t *nearest, int32_t *nearest_micro, int64_t *group_out, void *stream);
 
+/* ---- samples against the ligand a pocket was crystallised with (native.hip) ----------------------------------------------------------------
+ * The reference reports its interaction numbers relative to the pocket's own ligand (evaluate_scripts/cal_chem_results.py,
+ *   calculate_vina_metrics).  The native ligand goes through the entries above like a sample; these two say which pocket atoms a ligand
+ *   touches and where it sits, and compare every sample of a pocket with the pocket's native ligand.  The contact set, its Jaccard
+ *   index and the centroid distance are descriptors of this library's own: the reference has no counterpart.
+ * cbgx_pocket_contacts -- one launch, one workgroup per graph; any pocket size, a ligand of at most CBGX_GEOMETRY_MAX_LIGAND atoms.
+ *   Inputs: x_lig [n_lig, 3] / x_rec [n_rec, 3] float32, z_lig / z_rec atomic numbers as bytes, lig_ptr / rec_ptr [B + 1] int32 (entries
+ *   clamped to their arrays, an end below its start to the start), cutoff2 (double; CBGX_CONTACTS_CUTOFF2 = 16.0 = (4 A)^2 is the default
+ *   of the Python side).  An atom is HEAVY iff its atomic number is not 1; hydrogens on either side take no part.
+ *   A heavy ligand atom l and a heavy pocket atom r of one graph are in CONTACT iff d2 <= cutoff2 with
+ *     dx = (double)x_l - (double)x_r (exact; dy, dz likewise), d2 = (dx dx + dy dy) + dz dz,
+ *   every product and sum rounded to float64 once, nothing fused: the distance of cbgx_ligand_geometry.  A NaN d2 or cutoff2 is no contact.
+ *   rec_contact [n_rec] uint8: 1 iff some heavy ligand atom of the graph is in contact with that pocket atom, else 0.
+ *   lig_contact [n_lig] uint8: the same from the ligand's side.  Atoms in no graph's range are not written.
+ *   centroid [B, 3] float64: per component s = 0.0; s = s + (double)x_a for the graph's heavy atoms a in atom order, one float64 addition
+ *   after the other; centroid = s / (double)n_heavy (one IEEE division).  NaN in all three without a heavy atom.
+ *   graph_out [B, CBGX_CONTACTS_GRAPH_COLS] int32: n_atoms, n_heavy, n_rec (the clamped sizes of the ranges), n_rec_contact,
+ *   n_lig_contact, status: CBGX_CONTACTS_EMPTY without a heavy ligand atom, never an error.  Every output is written for every graph:
+ *   bytes 0 and counts 0 on an empty one.  No atomics on memory; nothing depends on scheduling.
+ *   Returns 0, and 0 without a launch when B == 0.  CBGX_E_INVALID before any launch: negative counts, a NULL pointer with a non-zero
+ *   count, a graph of more than CBGX_GEOMETRY_MAX_LIGAND ligand atoms (lig_ptr is read back, as cbgx_ligand_geometry does), and any
+ *   array with a non-zero count whose pointer is not memory the device can read (the first such array is named in cbgx_last_error).
+ * cbgx_native_compare -- one launch, one workgroup per pocket; integer work and one float64 distance per sample.
+ *   Inputs for the B sample graphs: fp [B, 32] (16-byte aligned), mol_hash [B], fp_status [B] int32 (the status column of
+ *   cbgx_ligand_fingerprints), rec_contact [n_rec] with rec_ptr [B + 1], centroid [B, 3], contacts_status [B] int32 (the status column
+ *   above).  The same six for the P native ligands, one per pocket (fp_nat ... contacts_status_nat, rec_ptr_nat [P + 1], n_rec_nat).
+ *   group_ptr [P + 1] int32: the samples of pocket p are the consecutive graphs group_ptr[p] ... group_ptr[p + 1], clamped as
+ *   cbgx_group_diversity clamps them; there is no limit on the size of a group.  All four pocket ranges are clamped to their arrays.
+ *   sample_out [B, CBGX_NATIVE_SAMPLE_COLS] int64, for sample g of pocket p:
+ *     sim_micro       (common 1000000 + union / 2) / union in integer division with common = popcount(fp_g & fp_nat_p), union =
+ *                     popcount(fp_g | fp_nat_p); 0 when union is 0: the Tanimoto similarity in millionths, rounded half up
+ *     same_hash       1 iff mol_hash[g] == mol_hash_nat[p], else 0
+ *     contact_common  pocket atoms k with rec_contact[r0 + k] != 0 and rec_contact_nat[q0 + k] != 0 (r0, q0 the starts of the two ranges)
+ *     contact_union   ... with either != 0
+ *     contact_micro   the same rounding formula on those two, 0 when contact_union is 0
+ *     status          bits, side by side: CBGX_NATIVE_SAMPLE_NOT_EVALUATED (fp_status[g] != 0) and CBGX_NATIVE_NATIVE_NOT_EVALUATED
+ *                     (fp_status_nat[p] != 0): sim_micro and same_hash are -1 with either; CBGX_NATIVE_POCKET_MISMATCH (the two
+ *                     clamped pocket ranges differ in length): the three contact columns are -1
+ *   centroid_d2 [B] float64: the squared distance of the two centroids by the formula above on float64 components; NaN where either
+ *   contacts status is not 0 or either centroid has a NaN.
+ *   group_out [P, CBGX_NATIVE_GROUP_COLS] int64: n_graphs, n_fp_compared (samples with sim_micro >= 0), n_same_hash, sim_micro_sum,
+ *   sim_micro_max (-1 without one), n_contact_compared (samples without CBGX_NATIVE_POCKET_MISMATCH), contact_micro_sum,
+ *   contact_micro_max (-1 without one), status: CBGX_NATIVE_NATIVE_NOT_EVALUATED, and CBGX_NATIVE_BAD_GROUPS where the range of
+ *   group_ptr is decreasing or outside [0, B] (the clamped range is evaluated).
+ *   A graph in no group is not written.  Sums, maxima and counts of integers: nothing depends on scheduling.  No atomics on memory.
+ *   Overlapping groups have two workgroups write the same rows, in no order: those rows are undefined.
+ *   Returns 0, and 0 without a launch when P == 0.  CBGX_E_INVALID before any dereference or launch: negative counts, a NULL pointer with
+ *   a non-zero count (the per-sample arrays with B, rec_contact with n_rec, the per-native arrays, rec_ptr_nat, group_ptr and group_out
+ *   with P, rec_contact_nat with n_rec_nat; rec_ptr whenever P > 0), an fp or fp_nat that is not 16-byte aligned, and any array with a
+ *   non-zero count whose pointer is not memory the device can read, named as above. */
+#define CBGX_CONTACTS_CUTOFF2 16.0
+#define CBGX_CONTACTS_GRAPH_COLS 6   /* n_atoms, n_heavy, n_rec, n_rec_contact, n_lig_contact, status */
+#define CBGX_CONTACTS_EMPTY 16
+#define CBGX_NATIVE_SAMPLE_COLS 6    /* sim_micro, same_hash, contact_common, contact_union, contact_micro, status */
+#define CBGX_NATIVE_GROUP_COLS 9     /* n_graphs, n_fp_compared, n_same_hash, sim_micro_sum, sim_micro_max, n_contact_compared,
+                                        contact_micro_sum, contact_micro_max, status */
+#define CBGX_NATIVE_SAMPLE_NOT_EVALUATED 1
+#define CBGX_NATIVE_NATIVE_NOT_EVALUATED 2
+#define CBGX_NATIVE_POCKET_MISMATCH 4
+#define CBGX_NATIVE_BAD_GROUPS 8
+int cbgx_pocket_contacts(const float *x_lig, const uint8_t *z_lig, const int32_t *lig_ptr, int n_lig, const float *x_rec,
+                         const uint8_t *z_rec, const int32_t *rec_ptr, int n_rec, int n_graphs, double cutoff2, uint8_t *rec_contact,
+                         uint8_t *lig_contact, double *centroid, int32_t *graph_out, void *stream);
+int cbgx_native_compare(const uint32_t *fp, const uint64_t *mol_hash, const int32_t *fp_status, const uint8_t *rec_contact,
+                        const int32_t *rec_ptr, const double *centroid, const int32_t *contacts_status, int n_graphs, int n_rec,
+                        const uint32_t *fp_nat, const uint64_t *mol_hash_nat, const int32_t *fp_status_nat, const uint8_t *rec_contact_nat,
+                        const int32_t *rec_ptr_nat, const double *centroid_nat, const int32_t *contacts_status_nat, int n_groups,
+                        int n_rec_nat, const int32_t *group_ptr, int64_t *sample_out, double *centroid_d2, int64_t *group_out,
+                        void *stream);
+
 /* ---- distributions of sampled ligands: pair distances, bond lengths, bond angles (distributions.hip) -----------------------------------
  * The rest of the reference's geometry report (evaluate_scripts/evaluate_geom_single.py; repo/tools/geometry/eval_bond_length.py,
  *   eval_bond_angle.py): histograms that are compared with a dataset's by Jensen-Shannon distance.  Distances and element codes are those
